@@ -7,21 +7,26 @@ x 4 actions) with 10 MC samples and depth 5, followed by the action posterior.
     so the N = 1 point of a scaling curve is the BENCH line and every point runs the same per-GPU workload (weak scaling).
     Episodes shard with no data-path collective; at N > 1 ONE all_gather of the [32, 4] action posteriors per step is the
     only RCCL traffic (its own time is reported as `all_gather_ms`).
-Inputs are resident in HBM before the timed region.  The timed region is exactly K steps between barrier + synchronize
-pairs, with NO profiling inside it; it is REPEATED (same K) until about 10 s of GPU time have been measured, and
-`ms_per_step` / `value` come from the median region (all region times are in the JSON), so the run is long enough to be
-observed from outside.  Per-kernel HIP-event times (the `roofline` entry included) come from extra, un-timed steps after it.
+Inputs are resident in HBM before the timed region.  The timed region is exactly K = --steps steps between barrier +
+synchronize pairs, with NO profiling inside it; `ms_per_step` / `value` come from it.  --min-seconds S repeats the region
+(same K) until S seconds of GPU time have been measured and reports the median region (all region times are in the JSON).
+--dump-outputs DIR writes what the last timed step returned (sum_G, sum_terms, po1, P, logP) as DIR/<name>.npy.
 
-The same JSON line carries, under "extras", the other BASELINE configurations: configs[2] (full lock-step MCTS, 64 episodes
-per GPU x 50 expansions x 10 samples, simulation depth 5; at N > 1 this is configs[3]: the root visit distributions of
-64 x N episodes are all-gathered) and configs[4] (3 x 84 x 84, 30 samples, depth 7, 32 episodes per GPU), each with its own
-roofline and -- at N = 1 -- CPU baseline.
+A plain run does only that: set up, warm up, time the K steps, dump, print the line.  --full adds everything else, after
+the timed region: per-kernel HIP-event times and the `roofline` entry (extra, un-timed steps), the shader clock sampled under
+load, the CPU baseline, the all_gather time at N > 1, and under "extras" the other BASELINE configurations: configs[2] (full
+lock-step MCTS, 64 episodes per GPU x 50 expansions x 10 samples, simulation depth 5; at N > 1 this is configs[3]: the root
+visit distributions of 64 x N episodes are all-gathered) and configs[4] (3 x 84 x 84, 30 samples, depth 7, 32 episodes per
+GPU), each with its own roofline and -- at N = 1 -- CPU baseline, plus the two-stream and split-operand legs and the
+one-episode latencies.
 
   python bench.py --gpus N --steps 20 --warmup 5          (N > 1 without WORLD_SIZE in the environment: bench.py launches its own
                                                            N ranks, one per GPU, through torch.distributed.run on 127.0.0.1)
+  python bench.py --full                                  (the headline plus every other leg)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
+import contextlib
 import glob
 import json
 import os
@@ -231,6 +236,38 @@ def rank_of(rk):
     return int(getattr(rk, 'rank', 0))
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each array as <path>/<name>.npy (float64 stays float64, everything else float32).  When the arrays
+    exceed `budget` bytes in all, the largest ones are cut to a fixed, seeded sample of their rows (sorted), so the same arguments
+    give the same rows and two builds compare output for output.  -> {name: shape written}"""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k, v in arrays.items():
+        x = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrs[k] = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+    total = sum(x.nbytes for x in arrs.values())
+    for k in sorted(arrs, key=lambda k: -arrs[k].nbytes):
+        x = arrs[k]
+        if total <= budget:
+            break
+        if x.ndim == 0 or x.shape[0] < 2:
+            continue
+        row = x.nbytes // x.shape[0]
+        keep = int(min(x.shape[0] - 1, max(1, (budget - (total - x.nbytes)) // row)))
+        idx = np.sort(np.random.default_rng(0).choice(x.shape[0], keep, replace=False))
+        arrs[k] = np.ascontiguousarray(x[idx])
+        total += arrs[k].nbytes - x.nbytes
+        print(f'[bench] --dump-outputs: {k} cut to a seeded sample of {keep} of {x.shape[0]} rows', file=sys.stderr, flush=True)
+    if total > budget:
+        raise ValueError(f'--dump-outputs: {total} bytes after sampling, over the {budget}-byte budget')
+    for k, x in arrs.items():
+        np.save(os.path.join(path, k + '.npy'), x)
+    return {k: list(x.shape) for k, x in arrs.items()}
+
+
 class ClockSampler:
     """Shader clock of this rank's GPU while the timed regions run, sampled from a SIDE THREAD that only reads the driver's sysfs file
     (/sys/class/drm/card*/device/pp_dpm_sclk: the level marked '*'; rocm-smi --showclocks as a fallback) -- nothing is put on any HIP
@@ -374,7 +411,7 @@ class Ranks:
         return mine
 
 
-def bench_mcts(a, model, device, rk, steps, warmup, with_cpu, threshold=2.0, min_total_s=2.5):
+def bench_mcts(a, model, device, rk, steps, warmup, with_cpu, threshold=2.0, min_total_s=2.5, dump=None):
     """BASELINE configs[2]/[3]: E episodes per GPU, each a full MCTS decision (50 expansions with S MC samples,
     simulation depth 5, use_means=False), planned in lock-step; the root visit distributions are gathered across ranks
     (N > 1: configs[3]).  threshold = 2.0 disables the early stop (every episode does all 50 expansions: the FLOP count of the
@@ -400,6 +437,9 @@ def bench_mcts(a, model, device, rk, steps, warmup, with_cpu, threshold=2.0, min
     del work[:]
     with ClockSampler(device) as clk:
         regions, local, _ = timed_regions(step, steps, 0, rk, min_total_s=min_total_s, max_regions=12)
+    if dump and rank == 0:
+        dump_outputs(dump, {'root_visits': last['P'], 'iterations_done': np.array([o[1] for o in last['out']], dtype=np.float64),
+                            'states_explored': np.array([o[2] for o in last['out']], dtype=np.float64)})
     work_timed = list(work)
     per_rank_ms = rk.per_rank(1e3 * statistics.median(local) / steps)
     dt = statistics.median(regions)
@@ -542,7 +582,7 @@ def cpu_baseline_generic(A, C, R, depth, samples):
                       f'restatement (oracle/efe_oracle.py, channels={C}, resolution={R}), torch RNG; parity unpinned'}
 
 
-def bench_generic(a, device, rk, steps, warmup, with_cpu, min_total_s=2.0):
+def bench_generic(a, device, rk, steps, warmup, with_cpu, min_total_s=2.0, dump=None):
     """BASELINE configs[4]: Animal-AI-sized observations (3 x 84 x 84, 3 actions), 30 MC samples, depth 7, 32 episodes per GPU
     (256 over 8 GPUs).  Build-defined network, PARITY UNPINNED: no reference semantics exist for this geometry."""
     import daimc_amd
@@ -561,9 +601,9 @@ def bench_generic(a, device, rk, steps, warmup, with_cpu, min_total_s=2.0):
     last = {}
 
     def step(k):
-        G, _, _ = model.calculate_G_repeated(o, pi, steps=D, samples=S, stage=k * D)
-        P, _ = model.action_posterior(G, A)
-        last['P'] = P
+        G, terms, po1 = model.calculate_G_repeated(o, pi, steps=D, samples=S, stage=k * D)
+        P, logP = model.action_posterior(G, A)
+        last.update(sum_G=G, sum_terms=terms, po1=po1, P=P, logP=logP)
         rk.gather(P, world * E)
         return G
 
@@ -573,6 +613,9 @@ def bench_generic(a, device, rk, steps, warmup, with_cpu, min_total_s=2.0):
     macs_row = model.last_call_macs() / rows
     with ClockSampler(device) as clk:
         regions, local, _ = timed_regions(step, steps, warmup, rk, min_total_s=min_total_s, max_regions=12)
+    if dump and rank_of(rk) == 0:
+        dump_outputs(dump, {'sum_G': last['sum_G'], 'sum_terms': torch.stack(last['sum_terms']), 'po1': last['po1'], 'P': last['P'],
+                            'logP': last['logP']})
     per_rank_ms = rk.per_rank(1e3 * statistics.median(local) / steps)
     dt = statistics.median(regions)
     value = world * rows * steps / dt
@@ -678,12 +721,23 @@ def main():
     ap.add_argument('--threshold', type=float, default=2.0, help="--workload mcts: early-stop threshold (2.0 = disabled, 0.5 = the reference's default)")
     ap.add_argument('--force-dist', action='store_true', help='initialise torch.distributed (RCCL) even with one rank: exercises the N>1 code path on a 1-GPU box')
     ap.add_argument('--share-device', action='store_true', help='N > 1 on a box with fewer GPUs: every rank uses cuda:0 and the gather runs over gloo (launcher test only)')
-    ap.add_argument('--min-seconds', type=float, default=10.0, help='measured GPU time of the headline workload (the K-step region is repeated)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-prof', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the configs[2]/[3] (MCTS) and configs[4] legs')
-    ap.add_argument('--single-region', action='store_true', help='time the K steps once (no repeats)')
+    ap.add_argument('--min-seconds', type=float, default=0.0,
+                    help='repeat the K-step timed region until this much GPU time has been measured (median region); 0 = time the K steps once')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, everything else: CPU baselines, per-kernel classes and rooflines, the clock under load, all_gather '
+                         'timing, and the extras legs (MCTS, 3 x 84 x 84, two streams, split-operand experiments, one-episode latencies)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full without the CPU baselines')
+    ap.add_argument('--no-prof', action='store_true', help='--full without the per-kernel HIP-event passes')
+    ap.add_argument('--no-extras', action='store_true', help='--full without the configs[2]/[3] (MCTS) and configs[4] legs')
+    ap.add_argument('--single-region', action='store_true', help='time the K steps once (no repeats, whatever --min-seconds says)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all, larger outputs as a '
+                         'seeded sample of their rows)')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not a.full:              # a plain run: set up, warm up, time the K steps, dump, print the line -- nothing else
+        a.no_cpu = a.no_prof = a.no_extras = True
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(a))
@@ -725,7 +779,8 @@ def main():
 
     import daimc_amd
     if a.workload == 'animalai':
-        return emit(bench_generic(a, device, rk, max(1, min(a.steps, 3)), max(1, min(a.warmup, 1)), with_cpu, min_total_s=a.min_seconds))
+        return emit(bench_generic(a, device, rk, max(1, min(a.steps, 3)), max(1, min(a.warmup, 1)), with_cpu, min_total_s=a.min_seconds,
+                                  dump=a.dump_outputs))
     R = a.rows or 128
     S, D = a.samples, a.depth
     model = daimc_amd.ActiveInferenceModel(10, 4, 0.0, 1.0, 1.0, device=device, seed=1, row_offset=rank * R)
@@ -736,7 +791,7 @@ def main():
         model.set_option(k_, int(v_))
     if a.workload == 'mcts':
         return emit(bench_mcts(a, model, device, rk, max(1, min(a.steps, 3)), max(1, min(a.warmup, 1)), with_cpu, threshold=a.threshold,
-                               min_total_s=a.min_seconds))
+                               min_total_s=a.min_seconds, dump=a.dump_outputs))
     model.reserve(R, D, S)                                       # steady-state steps never hipMalloc
     frames = synth_frames(R // 4, device, seed=100 + rank)
     o = frames.repeat_interleave(4, dim=0).contiguous()          # row 4i+a = (root i, action a), util.py:56-60
@@ -744,10 +799,10 @@ def main():
     last = {}
 
     def step(k):
-        G, _, _ = model.calculate_G_repeated(o, pi, steps=D, samples=S, stage=k * D)
-        P, _ = model.action_posterior(G)
-        last['P'] = P
-        rk.gather(P, world * (R // 4))             # the only RCCL traffic: [R/4, 4] floats per rank
+        G, terms, po1 = model.calculate_G_repeated(o, pi, steps=D, samples=S, stage=k * D)
+        P, logP = model.action_posterior(G)
+        last.update(sum_G=G, sum_terms=terms, po1=po1, P=P, logP=logP)
+        last['P_all'] = rk.gather(P, world * (R // 4))    # the only RCCL traffic: [R/4, 4] floats per rank
         return G
 
     print(f'[bench] rank {rank}: model ready, warm-up', file=sys.stderr, flush=True)
@@ -755,16 +810,19 @@ def main():
         step(k)
     rk.sync()
     grows0 = model.arena_stats()['grow_count']
-    with ClockSampler(device) as clk:
+    with (ClockSampler(device) if a.full else contextlib.nullcontext()) as clk:      # the clock under load is a roofline figure (--full)
         regions, local, kk = timed_regions(step, a.steps, a.warmup, rk, min_total_s=0.0 if a.single_region else a.min_seconds)
-    G = step(kk); kk += 1
-    torch.cuda.synchronize()
     print(f'[bench] rank {rank}: {len(regions)} timed regions of {a.steps} steps, {sum(regions):.3f}s', file=sys.stderr, flush=True)
-    assert torch.isfinite(G).all()
+    assert torch.isfinite(last['sum_G']).all()
     assert model.arena_stats()['grow_count'] == grows0, 'the scratch arena grew inside the timed region'
+    if a.dump_outputs and rank == 0:
+        outs = {'sum_G': last['sum_G'], 'sum_terms': torch.stack(last['sum_terms']), 'po1': last['po1'], 'P': last['P'], 'logP': last['logP']}
+        if use_dist:
+            outs['P_all_ranks'] = last['P_all']
+        dump_outputs(a.dump_outputs, outs)
     per_rank_ms = rk.per_rank(1e3 * statistics.median(local) / a.steps)
     dt = statistics.median(regions)                  # per region: the slowest rank (max over ranks)
-    gather_ms = rk.time_gather(last['P'], world * (R // 4))
+    gather_ms = rk.time_gather(last['P'], world * (R // 4)) if a.full else None
     breakdown = {}
     if not a.no_prof:
         # per-class HIP-event times from extra, UN-TIMED steps, one class at a time: event pairs around every launch of a step
@@ -801,7 +859,8 @@ def main():
         out['devices'] = devs
         if use_dist:
             out['per_rank_ms_per_step'] = [round(x, 3) for x in per_rank_ms]
-            out['all_gather_ms'] = gather_ms
+            if gather_ms is not None:
+                out['all_gather_ms'] = gather_ms
             if a.share_device:
                 out['share_device'] = True
         if breakdown:

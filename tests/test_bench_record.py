@@ -72,3 +72,28 @@ def test_split_mode_traffic_comes_from_that_modes_profile():
         a_, _ = bench.committed_split_traffic('k_dec_a_b3', opt)
         assert 6.0e9 <= a_ <= 7.5e9, a_              # x4 in (1.26 GB) + weights + y2 out (5.03 GB)
     assert bench.committed_split_traffic('k_nothing', 'mfma_f16x2') == (None, None)
+
+
+def test_dump_outputs_writes_float_arrays_and_a_seeded_row_sample_over_budget(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 (float64 kept); over the byte budget the largest array is cut to a seeded
+    sample of its rows, in order, the same rows on every call"""
+    import numpy as np
+    import torch
+    import bench
+    G = torch.linspace(-3.0, 5.0, 8)
+    big = np.arange(100 * 250, dtype=np.float64).reshape(100, 250)          # 200 000 bytes
+    arrays = {'sum_G': G, 'count': np.array([1, 2, 3]), 'big': big}
+    shapes = bench.dump_outputs(str(tmp_path / 'a'), arrays, budget=100_000)
+    assert shapes['sum_G'] == [8] and shapes['count'] == [3] and shapes['big'][1] == 250 and 1 <= shapes['big'][0] < 100
+    g = np.load(tmp_path / 'a' / 'sum_G.npy')
+    assert g.dtype == np.float32 and np.array_equal(g, G.numpy())
+    cnt = np.load(tmp_path / 'a' / 'count.npy')
+    assert cnt.dtype == np.float32 and cnt.tolist() == [1.0, 2.0, 3.0]
+    b = np.load(tmp_path / 'a' / 'big.npy')
+    assert b.dtype == np.float64 and sum(np.load(tmp_path / 'a' / f'{n}.npy').nbytes for n in arrays) <= 100_000
+    rows = (b[:, 0] // 250).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(b, big[rows])          # whole rows of the original, in order
+    bench.dump_outputs(str(tmp_path / 'b'), arrays, budget=100_000)
+    assert np.array_equal(np.load(tmp_path / 'b' / 'big.npy'), b)              # the same rows again
+    bench.dump_outputs(str(tmp_path / 'c'), arrays)                             # under the default 64 MB: nothing is cut
+    assert np.array_equal(np.load(tmp_path / 'c' / 'big.npy'), big)

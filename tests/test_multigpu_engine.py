@@ -121,7 +121,7 @@ def test_bench_rccl_path_at_one_rank():
     """the N > 1 code path of bench.py through RCCL itself on a 1-GPU box: `--force-dist` initialises the "nccl" process group with one
     rank, so the device-tensor all_gather of the action posteriors, the max-over-ranks timing and the collective fields of the line run
     through the library the 8-GPU line will use"""
-    d = _bench_line(['--force-dist', '--no-extras', '--steps', '3', '--warmup', '2', '--min-seconds', '0.5'], 600)
+    d = _bench_line(['--full', '--force-dist', '--no-extras', '--steps', '3', '--warmup', '2', '--min-seconds', '0.5'], 600)
     assert d['n_gpus'] == 1 and d['rccl_ranks'] == 1 and d['backend'] == 'nccl'
     assert len(d['per_rank_ms_per_step']) == 1 and d['all_gather_ms'] > 0
     assert d['roofline']['frac'] > 0.3 and d['roofline']['bound'] == 'mfma' and 'sclk_mhz_under_load' in d['roofline']
@@ -136,7 +136,7 @@ def test_bench_launcher_at_n_ranks_on_one_device(n):
     JSON line with the per-rank figures, the per-rank (device, PCI bus id) list and the CPU leg -- every rank on cuda:0 over gloo (a
     rehearsal of the 8-GPU line, which needs a multi-GPU node).  Without --share-device the same command REFUSES to put two ranks on one
     GPU (bench.py Ranks.check_devices: efe_get_device of every rank's engine context, gathered)."""
-    d = _bench_line(['--gpus', str(n), '--share-device', '--no-extras', '--no-prof', '--steps', '2', '--warmup', '1', '--min-seconds', '0.5'], 1200)
+    d = _bench_line(['--gpus', str(n), '--share-device', '--full', '--no-extras', '--no-prof', '--steps', '2', '--warmup', '1', '--min-seconds', '0.5'], 1200)
     assert d['n_gpus'] == n and d['ranks'] == n and 'rccl_ranks' not in d and d['backend'] == 'gloo' and d.get('share_device') is True
     assert len(d['per_rank_ms_per_step']) == n and d['all_gather_ms'] > 0 and d['scaling'] == 'weak'
     assert len(d['devices']) == n and all(dev[0] == 0 and dev[1] == d['devices'][0][1] and len(dev[1]) >= 7 for dev in d['devices'])

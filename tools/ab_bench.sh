@@ -4,8 +4,8 @@
 TAG=$1; ALT=$2; REPS=$3; shift 3
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for i in $(seq 1 $REPS); do
-  timeout 300 python bench.py --no-cpu --min-seconds 2 "$@" > $OUT/new_$i.json 2> $OUT/new_$i.err
-  EFE_LIB_PATH=tools/ubench/alt/$ALT/libefe_mi355x.so timeout 300 python bench.py --no-cpu --min-seconds 2 "$@" > $OUT/old_$i.json 2> $OUT/old_$i.err
+  timeout 300 python bench.py --full --no-cpu --min-seconds 2 "$@" > $OUT/new_$i.json 2> $OUT/new_$i.err
+  EFE_LIB_PATH=tools/ubench/alt/$ALT/libefe_mi355x.so timeout 300 python bench.py --full --no-cpu --min-seconds 2 "$@" > $OUT/old_$i.json 2> $OUT/old_$i.err
 done
 python - <<PY
 import json, glob

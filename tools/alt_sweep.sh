@@ -3,7 +3,7 @@
 #   tools/alt_sweep.sh <tag> "<alt names>" [bench args...]
 TAG=$1; ALTS=$2; shift 2
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-run() { timeout 300 python bench.py --no-cpu --min-seconds 2 "$@" ; }
+run() { timeout 300 python bench.py --full --no-cpu --min-seconds 2 "$@" ; }
 run "$@" > $OUT/00_product.json 2> $OUT/00_product.err
 for a in $ALTS; do EFE_LIB_PATH=tools/ubench/alt/$a/libefe_mi355x.so run "$@" > $OUT/alt_$a.json 2> $OUT/alt_$a.err; done
 run "$@" > $OUT/zz_product.json 2> $OUT/zz_product.err
