@@ -236,8 +236,9 @@ struct NoiseCfg {
 };
 inline RowMask live_of(const NoiseCfg& nc, int m0) { return RowMask{nc.mask, nc.mask_div, m0, nc.rows_per_group, nc.mask ? nc.gm.ids : nullptr}; }
 
+// split16 = false: the decoder's Linear(256, 16384) stays on the exact fp32 k_fc4 even under a split-operand option (its consumer is fp32)
 void fc(efe_ctx* ctx, const Layer& L, const float* X, int ldx, int x_mod, float* Y, int ldy, int M, bool relu, bool drop,
-        uint32_t tag, const NoiseCfg& nc, int m0, hipStream_t st) {
+        uint32_t tag, const NoiseCfg& nc, int m0, hipStream_t st, bool split16 = true) {
     GemmArgs a{};
     a.Wp = L.Wp; a.bias = L.bias; a.X = X; a.Y = Y; a.zeros = ctx->zeros;
     a.n_pix = M; a.cin = L.cin; a.cout = L.cout; a.mtiles = L.mtiles; a.ldx = ldx; a.ldy = ldy; a.x_mod = x_mod;
@@ -245,7 +246,7 @@ void fc(efe_ctx* ctx, const Layer& L, const float* X, int ldx, int x_mod, float*
     a.rows_per_group = nc.rows_per_group; a.row_offset = nc.row_offset; a.m0 = m0;
     hipEvent_t e0 = ctx->prof_begin(st);
     if (L.mtiles >= 64 && !(L.mtiles & 1) && L.cin == 256 && ldx == 256 && x_mod == 0 && relu && drop) {
-        if (ctx->mfma_bf16x3 && ctx->fc4_b3 && &L == &ctx->dec_fc[3]) {      // opt-in experiment
+        if (split16 && ctx->mfma_bf16x3 && ctx->fc4_b3 && &L == &ctx->dec_fc[3]) {      // opt-in experiment
             a.Wb3 = ctx->fc4_b3; a.split = (int)ctx->mfma_bf16x3; a.wb3_scale_inv = 1.0f / ctx->s_fc4;
             launch_fc4_b3(a, st);
         }
@@ -472,6 +473,12 @@ int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const Nois
                 float* val /*[N], or [N][4] quarter sums when dec_split(ctx, N)*/, float* po_store, hipStream_t st) {
     if (ctx->generic) return run_decoder_g(ctx, dec_in, N, nc, reward0, store0, val, po_store, st);
     const bool split = dec_split(ctx, N);
+    // mfma_f16x2 marks a row / image whose activation overflowed fp16 with +inf, and only its own split kernels turn that into a NaN
+    // sum: an exact-fp32 consumer (k_dec_a_s / k_dec_a / k_dec_b4) can make a finite wrong image of it (inf - inf = NaN, and relu_bits
+    // maps a negative-signed NaN or -inf to 0).  So under that mode the chain is split from k_fc4_b3 to k_dec_b_b3 or not at all: small
+    // launches keep k_fc4 too, and ConvT3 always runs on k_dec_b_b3 (b3_convt3 = 0 applies to mfma_bf16x3, which cannot overflow).
+    const bool f16 = ctx->mfma_bf16x3 == 2;
+    const bool fc4_16 = !(f16 && split), ct3_16 = ctx->b3_convt3 || f16;
     const int C = (int)std::min<int64_t>(ctx->dec_chunk, N);
     float* hA = ctx->allocT<float>((size_t)N * 256);
     float* hB = ctx->allocT<float>((size_t)N * 256);
@@ -492,7 +499,7 @@ int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const Nois
     for (int m0 = 0; m0 < N; m0 += C) {
         const int c = std::min(C, N - m0);
         ctx->cls = PROF_DEC_FC4;
-        fc(ctx, ctx->dec_fc[3], hA + (size_t)m0 * 256, 256, 0, x4, 16384, c, true, true, TAG_DEC + 3, nc, m0, st);
+        fc(ctx, ctx->dec_fc[3], hA + (size_t)m0 * 256, 256, 0, x4, 16384, c, true, true, TAG_DEC + 3, nc, m0, st, fc4_16);
         ctx->cls = PROF_CT2;
         DecAArgs da{};
         da.x4 = x4; da.y2 = y2; da.w1 = ctx->dec_ct[0].Wp; da.b1 = ctx->dec_ct[0].bias; da.w2 = ctx->dec_ct[1].Wp;
@@ -511,7 +518,7 @@ int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const Nois
         db.rows = c; db.live = live_of(nc, m0); db.m0 = m0; db.rows_per_group = nc.rows_per_group; db.gm = nc.gm; db.reward0 = reward0; db.store0 = store0;
         db.val = val; db.parts = split ? 4 : 1; db.valq = split ? val : nullptr; db.po = po_store; db.reward_intent = (int)ctx->reward_intent;
         e0 = ctx->prof_begin(st);
-        if (ctx->mfma_bf16x3 && ctx->b3_convt3 && ctx->ct3_b3 && !split) {      // opt-in experiment
+        if (ctx->mfma_bf16x3 && ct3_16 && ctx->ct3_b3 && !split) {      // opt-in experiment
             db.w3b3 = ctx->ct3_b3; db.split = (int)ctx->mfma_bf16x3; db.w3s = ctx->s_ct3; db.w3s_inv = 1.0f / ctx->s_ct3;
             launch_dec_b_b3(db, st);
         }

@@ -87,6 +87,10 @@ int efe_commit_weights(efe_ctx* ctx);
  *                   product, fp32 accumulation: csrc/bf16x3.hip).  Inputs narrower than the reference's fp32 arithmetic, results inside the same
  *                   tolerances (every fixture is run through it); never the default, never the benchmark's headline.  With it, results are no
  *                   longer bit-identical across launch sizes (launches of <= 128 images keep the fp32 small-launch kernels), only within tolerance.
+ *                   "mfma_f16x2" (0 / 1, default 0; same scope): the same layers with two fp16 planes (weights scaled by a power of two).  An
+ *                   activation beyond fp16's range poisons its row / image, and the result is NaN, never a finite wrong number: the poison
+ *                   only travels through the split kernels, so under this option launches of <= 128 images run all four layers on the
+ *                   exact fp32 kernels and ConvT3 always runs split ("b3_convt3" = 0 applies to mfma_bf16x3 alone).
  *   development   : "poison" (pre-fill scratch with a byte), "trace" (synchronise and log every profiled launch), "arena_align", "check_rows"
  *                   (range-check efe_rows.ids against efe_rows.n_total on the host before every _rows call: one synchronisation per call) */
 int efe_set_option(efe_ctx* ctx, const char* name, int64_t value);

@@ -35,19 +35,29 @@ def entropy_normal_from_logvar(logvar):
     return 0.5 * (LOG_2_PI_E + logvar)
 
 
+def _displacements(displacement):
+    """the reference's constants as its fp32 arithmetic sees them: `displacement` and the Python float `displacement + 1`, each rounded
+    to fp32 (torch casts a Python scalar to the tensor's dtype).  Exact at float32; in the float64 mode the constants stay the fp32
+    ones, so the fp64 oracle measures the rounding of the arithmetic, not of the constant 1.00001 (a 1.4e-3 relative shift of
+    log(1.00001 - 1) that would otherwise dominate term0)."""
+    return float(np.float32(displacement)), float(np.float32(displacement + 1))
+
+
 def entropy_bernoulli(p, displacement=0.00001):
     """torchutils.py:26-27"""
-    return -(1 - p) * torch.log(displacement + 1 - p) - p * torch.log(displacement + p)
+    d, d1 = _displacements(displacement)
+    return -(1 - p) * torch.log(d1 - p) - p * torch.log(d + p)
 
 
 def log_bernoulli(x, p, displacement=0.00001):
     """torchutils.py:30-31"""
-    return x * torch.log(displacement + p) + (1 - x) * torch.log(displacement + 1 - p)
+    d, d1 = _displacements(displacement)
+    return x * torch.log(d + p) + (1 - x) * torch.log(d1 - p)
 
 
 def calc_reward(o, resolution=64):
     """torchutils.py:34-37 (NCHW broadcast semantics replicated)."""
-    perfect_reward = torch.zeros((3, resolution, 1), dtype=torch.float32)
+    perfect_reward = torch.zeros((3, resolution, 1), dtype=o.dtype)
     perfect_reward[:, :int(resolution / 2)] = 1.0
     return log_bernoulli(o[:, 0:3, 0:resolution, :], perfect_reward)
 
@@ -62,7 +72,7 @@ def check_reward_generic(o):
     torchmodel.py:213-214, does not exist): the NCHW-broadcast target of torchutils.py:34-37 -- 1 for image rows
     h < H/2, 0 below -- applied to every channel, summed over [1,2,3] like the reference's resolution-32 branch."""
     H = o.shape[2]
-    target = torch.zeros((1, 1, H, 1), dtype=torch.float32)
+    target = torch.zeros((1, 1, H, 1), dtype=o.dtype)
     target[:, :, :H // 2] = 1.0
     return torch.sum(log_bernoulli(o, target), dim=[1, 2, 3])
 
@@ -74,7 +84,7 @@ def check_reward_upstream_intent(o, generic=False):
     Restated for this repository's NCHW tensors: log_bernoulli over rows 0..2 with target 1 for columns < W/2, every channel;
     dSprites: mean over those 3*W*C elements * 10 (torchmodel.py:212); generic geometries: their sum (torchmodel.py:214 form)."""
     W = o.shape[3]
-    target = torch.zeros((1, 1, 1, W), dtype=torch.float32)
+    target = torch.zeros((1, 1, 1, W), dtype=o.dtype)
     target[..., :W // 2] = 1.0
     lb = log_bernoulli(o[:, :, 0:3, :], target)
     return torch.sum(lb, dim=[1, 2, 3]) if generic else torch.mean(lb, dim=[1, 2, 3]) * 10.0
@@ -163,10 +173,16 @@ class OracleModel:
 
     `channels` / `resolution` other than (1, 64) select the BUILD-DEFINED geometry of SURVEY 8a-13 (BASELINE configs[4]):
     the same layer list with the sizes the resolution implies and check_reward_generic -- the reference cannot run it
-    (torchmodel.py:77-82, 213-214), so for that geometry this restatement is the only oracle: PARITY UNPINNED."""
+    (torchmodel.py:77-82, 213-214), so for that geometry this restatement is the only oracle: PARITY UNPINNED.
 
-    def __init__(self, weights, noise, s_dim=10, pi_dim=4, channels=1, resolution=64):
-        self.w = {k: torch.as_tensor(np.asarray(v, dtype=np.float32)) for k, v in weights.items()}
+    `dtype` = torch.float64 evaluates the networks and the EFE terms (calculate_G*, calculate_G_given_trajectory) in double precision:
+    the fp32 weights, inputs, dropout masks and normals are widened exactly, and every accumulator and reward target is created in that
+    dtype.  It is the high-precision reference the kernels' error is measured against (tests/test_fp64_parity.py).  The planner
+    (mcts_step_simulate, categorical_from_uniform) makes discrete decisions and stays fp32.  The default float32 is the restatement itself."""
+
+    def __init__(self, weights, noise, s_dim=10, pi_dim=4, channels=1, resolution=64, dtype=torch.float32):
+        self.dtype = dtype
+        self.w = {k: torch.as_tensor(np.asarray(v, dtype=np.float32)).to(dtype) for k, v in weights.items()}
         self.noise = noise
         self.s_dim = s_dim
         self.pi_dim = pi_dim
@@ -175,7 +191,17 @@ class OracleModel:
         self.base = resolution // 2 if resolution == 32 else resolution // 4
         self.generic = (channels, resolution) != (1, 64)
         self.reward_upstream_intent = False         # engine option of the same name: see check_reward_upstream_intent
-        self.pi_one_hot = torch.eye(pi_dim)      # torchmodel.py:164-165
+        self.pi_one_hot = torch.eye(pi_dim, dtype=dtype)      # torchmodel.py:164-165
+
+    # inputs, masks and accumulators in the model's dtype (no-ops at float32)
+    def _in(self, x):
+        return torch.as_tensor(x).to(self.dtype)
+
+    def _mask(self, *a, **k):
+        return self.noise.mask(*a, **k).to(self.dtype)
+
+    def _zeros(self, *shape):
+        return torch.zeros(*shape, dtype=self.dtype)
 
     def check_reward(self, o):
         if self.reward_upstream_intent:
@@ -185,7 +211,7 @@ class OracleModel:
     # ---- ModelTop.encode_s (torchmodel.py:27-31); no dropout --------------
     def encode_s(self, s0):
         w = self.w
-        h = F.relu(F.linear(s0, w['top.qpi_net.0.weight'], w['top.qpi_net.0.bias']))
+        h = F.relu(F.linear(self._in(s0), w['top.qpi_net.0.weight'], w['top.qpi_net.0.bias']))
         h = F.relu(F.linear(h, w['top.qpi_net.2.weight'], w['top.qpi_net.2.bias']))
         logits_pi = F.linear(h, w['top.qpi_net.4.weight'], w['top.qpi_net.4.bias'])
         q_pi = F.softmax(logits_pi, dim=-1)
@@ -196,17 +222,17 @@ class OracleModel:
     def transition(self, pi, s0, pas, sample, stage, ro=None):
         w = self.w
         M = s0.shape[0]
-        h = torch.cat([pi, s0], dim=1)
+        h = torch.cat([self._in(pi), self._in(s0)], dim=1)
         for li, idx in enumerate((0, 3, 6)):
             h = F.relu(F.linear(h, w[f'mid.ps_net.{idx}.weight'], w[f'mid.ps_net.{idx}.bias']))
-            h = h * self.noise.mask(PX.TAG_MID + li, M, 512, pas, sample, stage, ro)
+            h = h * self._mask(PX.TAG_MID + li, M, 512, pas, sample, stage, ro)
         out = F.linear(h, w['mid.ps_net.9.weight'], w['mid.ps_net.9.bias'])
         mean, logvar = torch.split(out, self.s_dim, dim=1)
         return mean, logvar
 
     def reparameterize(self, mean, logvar, pas, sample, stage, ro=None):
         """torchmodel.py:54-56 / 130-132"""
-        eps = self.noise.eps(mean.shape[0], mean.shape[1], pas, sample, stage, ro)
+        eps = self.noise.eps(mean.shape[0], mean.shape[1], pas, sample, stage, ro).to(self.dtype)
         return eps * torch.exp(logvar * 0.5) + mean
 
     def transition_with_sample(self, pi, s0, pas, sample, stage, ro=None):
@@ -218,11 +244,11 @@ class OracleModel:
     def decoder(self, s, pas, sample, stage, ro=None):
         w = self.w
         M = s.shape[0]
-        h = s
+        h = self._in(s)
         for li, idx in enumerate((0, 3, 6, 9)):
             h = F.relu(F.linear(h, w[f'down.po_net.{idx}.weight'], w[f'down.po_net.{idx}.bias']))
             nf = h.shape[1]
-            h = h * self.noise.mask(PX.TAG_DEC + li, M, nf, pas, sample, stage, ro, fc4_perm=(li == 3))
+            h = h * self._mask(PX.TAG_DEC + li, M, nf, pas, sample, stage, ro, fc4_perm=(li == 3))
         h = h.reshape(M, 64, self.base, self.base)
         h = F.relu(F.conv_transpose2d(h, w['down.po_net.13.weight'], w['down.po_net.13.bias'], stride=1, padding=1))
         h = F.relu(F.conv_transpose2d(h, w['down.po_net.15.weight'], w['down.po_net.15.bias'], stride=2, padding=1, output_padding=1))
@@ -235,13 +261,13 @@ class OracleModel:
     def encoder(self, o, pas, sample, stage, ro=None):
         w = self.w
         M = o.shape[0]
-        h = o
+        h = self._in(o)
         for idx in (0, 2, 4, 6):
             h = F.relu(F.conv2d(h, w[f'down.qs_net.{idx}.weight'], w[f'down.qs_net.{idx}.bias'], stride=2))
         h = h.reshape(M, -1)                       # Flatten: c*9 + h*3 + w -> 576
         for li, idx in enumerate((9, 12, 15)):
             h = F.relu(F.linear(h, w[f'down.qs_net.{idx}.weight'], w[f'down.qs_net.{idx}.bias']))
-            h = h * self.noise.mask(PX.TAG_ENC + li, M, 256, pas, sample, stage, ro)
+            h = h * self._mask(PX.TAG_ENC + li, M, 256, pas, sample, stage, ro)
         out = F.linear(h, w['down.qs_net.18.weight'], w['down.qs_net.18.bias'])
         mean, logvar = torch.split(out, self.s_dim, dim=1)
         return mean, logvar
@@ -254,8 +280,8 @@ class OracleModel:
     # ---- calculate_G (torchmodel.py:270-300) -------------------------------
     def calculate_G(self, s0, pi0, samples, stage, ro=None):
         M = s0.shape[0]
-        term0 = torch.zeros(M)
-        term1 = torch.zeros(M)
+        term0 = self._zeros(M)
+        term1 = self._zeros(M)
         for i in range(samples):
             ps1, ps1_mean, ps1_logvar = self.transition_with_sample(pi0, s0, PX.PASS_T1, i, stage, ro)
             po1 = self.decoder(ps1, PX.PASS_D1, i, stage, ro)
@@ -266,8 +292,8 @@ class OracleModel:
         term0 /= float(samples)
         term1 /= float(samples)
 
-        term2_1 = torch.zeros(M)
-        term2_2 = torch.zeros(M)
+        term2_1 = self._zeros(M)
+        term2_2 = self._zeros(M)
         for j in range(samples):
             po1_temp1 = self.decoder(self.transition_with_sample(pi0, s0, PX.PASS_T2, j, stage, ro)[0], PX.PASS_D2A, j, stage, ro)
             term2_1 += torch.sum(entropy_bernoulli(po1_temp1), dim=[1, 2, 3])
@@ -302,8 +328,8 @@ class OracleModel:
         qs0_mean, qs0_logvar = self.encoder(o, PX.PASS_ROOT, 0, stage0, ro)
         qs0 = self.reparameterize(qs0_mean, qs0_logvar, PX.PASS_ROOT, 0, stage0, ro)
         M = o.shape[0]
-        sum_terms = [torch.zeros(M) for _ in range(3)]
-        sum_G = torch.zeros(M)
+        sum_terms = [self._zeros(M) for _ in range(3)]
+        sum_G = self._zeros(M)
         s0_temp = qs0_mean if calc_mean else qs0
         po1 = None
         for t in range(steps):
@@ -318,8 +344,8 @@ class OracleModel:
     def calculate_G_4_repeated(self, o, steps, calc_mean, samples, stage0, ro=None):
         qs0_mean, qs0_logvar = self.encoder(o, PX.PASS_ROOT, 0, stage0, ro)
         qs0 = self.reparameterize(qs0_mean, qs0_logvar, PX.PASS_ROOT, 0, stage0, ro)
-        sum_terms = [torch.zeros(4) for _ in range(3)]
-        sum_G = torch.zeros(4)
+        sum_terms = [self._zeros(4) for _ in range(3)]
+        sum_G = self._zeros(4)
         s0_temp = qs0_mean if calc_mean else qs0
         po1 = None
         for t in range(steps):
@@ -335,6 +361,7 @@ class OracleModel:
 
     # ---- calculate_G_given_trajectory (torchmodel.py:329-352) --------------
     def calculate_G_given_trajectory(self, s0_traj, ps1_traj, ps1_mean_traj, ps1_logvar_traj, pi0_traj, stage, ro=None):
+        ps1_mean_traj, ps1_logvar_traj = self._in(ps1_mean_traj), self._in(ps1_logvar_traj)
         po1 = self.decoder(ps1_traj, PX.PASS_D1, 0, stage, ro)
         qs1, _, qs1_logvar = self.encoder_with_sample(po1, PX.PASS_E1, 0, stage, ro)
         term0 = self.check_reward(po1)

@@ -13,4 +13,5 @@ python -m oracle.make_golden_thr        # the planner's early stops at benchmark
 python -m oracle.make_golden_defaults   # the reference planner at MCTS_Params() defaults (300 repeats) and with simulation_repeats = 2
 python -m oracle.make_golden_stats      # SAMPLES of the unpatched reference under torch's own generator (statistical pin)
 python -m oracle.make_golden_stats_planner   # ... and 512 whole planner decisions under that generator
+python -m oracle.make_golden_stress     # stress weight families (oracle/synth.stress_weights): networks, calculate_G, a rollout
 python tests/golden/make_c_blob.py      # calcG_m4s1_g115.npz -> flat blob for tests/c_abi_smoke.c (needs no reference)

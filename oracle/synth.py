@@ -95,3 +95,54 @@ def make_frames(seed, n):
         else:
             frames[i, 0, 0:3, 32:64] = -r
     return frames
+
+
+# --------------------------------------------------------------------------
+# stress families: weights that drive the kernels into the regimes the fixture family (make_weights at gains 1.00 / 1.15 / 1.35,
+# images around p = 0.5) never reaches.  Each one names the hazard it targets; tests/test_fp64_oracle.py checks that it still
+# reaches its regime.  make_weights itself is untouched: every fixture depends on it bit for bit.
+# --------------------------------------------------------------------------
+STRESS_FAMILIES = ('seed2', 'gain2', 'sparse', 'saturated')
+
+
+def stress_weights(family, pi_dim=4, channels=1, resolution=64):
+    """dict key -> float32 array for one stress family (any geometry):
+      * 'seed2'     -- gain 1.15 from another weight seed: a second draw of the fixture family (control).
+      * 'gain2'     -- gain 2.0: large pre-activations, cancellation in term2_1 - term2_2, about half the pixels below 1e-3 (the
+                       encoder's output layer scaled back, see below, so that rollouts stay finite).
+      * 'sparse'    -- trained-like: per-layer weight scales spread over a decade (fixed Philox draw), biases uniform in +-1 (the
+                       logvar halves kept at make_weights' -2 offset), a transition net above gain 1 that is still contractive over
+                       depth 5, and po_net.19 (weights x 6, bias -6) such that most pixels are dark, as in dSprites: p ln p on tiny p.
+      * 'saturated' -- po_net.19 weights x 40: some pre-sigmoids above +17 (p rounds to 1 in fp32, 1 - p = 0) and some below -89
+                       (hw_sigmoid's exp2 overflows to p = 0 where torch gives a denormal; csrc/mfma_pipe.h hw_sigmoid)."""
+    geo = (pi_dim, channels, resolution)
+    if family == 'seed2':
+        return make_weights(4321, 1.15, *geo)
+    if family == 'gain2':
+        w = make_weights(1234, 2.0, *geo)
+        # the encoder's output layer x 2^-6: gain 2 over its eight layers would put the posterior logvar near 110, exp(logvar / 2) near
+        # 1e24, and every rollout from a frame would be NaN in the reference itself; its hidden layers keep their large pre-activations
+        w['down.qs_net.18.weight'] = w['down.qs_net.18.weight'] * np.float32(2.0 ** -6)
+        return w
+    if family == 'saturated':
+        w = make_weights(1234, 1.15, *geo)
+        w['down.po_net.19.weight'] = w['down.po_net.19.weight'] * np.float32(40.0)
+        return w
+    if family == 'sparse':
+        specs = specs_for(*geo)
+        scale = 10.0 ** PX.uniform_fill(77, (len(specs),), 3000, -0.5, 0.5)      # per-layer factor in [0.32, 3.2]
+        w = {}
+        for i, (name, shape) in enumerate(specs):
+            fan = _fan_in(name, shape)
+            g = 1.3 if name.startswith('mid.') else float(scale[i])
+            bound = g * np.sqrt(3.0 / fan)
+            w[name + '.weight'] = PX.uniform_fill(77, shape, 3001 + 2 * i, -bound, bound)
+            bshape = (shape[1],) if name in CONVT else (shape[0],)
+            w[name + '.bias'] = PX.uniform_fill(77, bshape, 3002 + 2 * i, -1.0, 1.0)
+        w['mid.ps_net.9.weight'] *= 0.3
+        for k in ('mid.ps_net.9', 'down.qs_net.18'):
+            w[k + '.bias'][10:] = w[k + '.bias'][10:] * np.float32(0.1) - np.float32(2.0)
+        w['down.po_net.19.weight'] *= 6.0         # logits spread over ~ -9 .. -4 around the bias: a quarter of the pixels below 1e-3
+        w['down.po_net.19.bias'][:] = -6.0
+        return w
+    raise ValueError(f'unknown stress family {family!r}')
