@@ -4,7 +4,7 @@
 //
 // One workgroup (4 waves) owns one decoder image; activations live in LDS between layers:
 //
-//   k_dec_a :  x4[16x16x64] --LDS--> ConvT(64,64,s1)+ReLU --LDS (in place)--> ConvT(64,64,s2)+ReLU --> y2[32x32x64] (HBM)
+//   k_dec_a :  x4[16x16x64] --LDS--> ConvT(64,64,s1)+ReLU (Winograd F(2x2,3x3)) --LDS (in place)--> ConvT(64,64,s2)+ReLU --> y2[32x32x64] (HBM)
 //   k_dec_b4:  y2 strips --LDS--> ConvT(64,32,s2)+ReLU (registers) --MFMA--> tap values of the 32->1 conv, horizontal sums in registers
 //              --LDS ring of H planes--> vertical gather + sigmoid + entropy / reward reduction (+ optional image store)
 //   k_dec_a_s / k_dec_b4<4>: the same kernels with an image over eight / four workgroups, for launches of <= 128 images
@@ -26,11 +26,124 @@ namespace efe {
 // of rounds 1-2 cost an XOR and an add per chunk and 11 % of the LDS cycles in bank conflicts).
 constexpr int DA_PS = 17;
 constexpr int DA_BIAS = 257 * DA_PS;       // float4 index of the two bias vectors behind the image + zero pixel
+
+// ---------------------------------------------------------------------------------------------------------
+// Layer 1 (ConvTranspose2d(64,64,3,s1,p1) = a 3x3 correlation with the flipped kernel g, pad 1) by Winograd F(2x2, 3x3) (Lavin):
+//   output tile (ty, tx) = pixels (2ty + r, 2tx + c), r, c in {0, 1}; input tile d[i][jj] = x[2ty - 1 + i][2tx - 1 + jj] (zero outside)
+//   xi = (a, b) in 4 x 4:  V_xi = (B^T d B)[a][b],  M_xi[co][tile] = sum_ci U_xi[co][ci] V_xi[ci][tile],  out[r][c] = bias + sum_xi AT[r][a] AT[c][b] M_xi
+// U = G g G^T is formed in fp64 at commit time and rounded once (engine.hip), packed like a 16-tap conv: [xi][2 tiles][8 chunks][64 lanes][4].
+// Each row of B^T has two non-zero entries, the first +1: row a of B^T d is d[wino_i0(a)] + wino_s1(a) d[wino_i1(a)], so a B fragment is four LDS reads
+// and three fp32 adds per component (a signed add is written as fma(+-1, x, y): exactly y +- x).  16 xi-GEMMs of 32 MFMAs per 32-channel x
+// 32-tile block replace the 9 x 32 of the direct form.  The output transform runs in ascending xi = 4a + b, one signed add per non-zero AT
+// coefficient (AT[r][a] AT[c][b] in {0, +-1}): out[r][c] sees the same operations, in the same order, whichever output rows a wave owns.
+// NR = output rows R0 .. R0 + NR - 1 of the tiles this wave owns (2: k_dec_a; 1: k_dec_a_s, whose waves split the rows):
+// only the xi rows a with AT[r][a] != 0 for one of them are contracted (r = 0: a = 0..2; r = 1: a = 1..3).
+// pix(i, jj) -> LDS float4 index of input pixel (i, jj) of the lane's tile (the zero pixel outside the image).
+// ---------------------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int wino_i0(int a) { return a == 0 ? 0 : (a == 2 ? 2 : 1); }     // B^T row a: +1 at wino_i0(a), wino_s1(a) at wino_i1(a)
+__host__ __device__ constexpr int wino_i1(int a) { return a == 0 ? 2 : (a == 1 ? 2 : (a == 2 ? 1 : 3)); }
+__host__ __device__ constexpr float wino_s1(int a) { return a == 1 ? 1.0f : -1.0f; }
+__host__ __device__ constexpr float wino_at(int r, int a) { return r == 0 ? (a < 3 ? 1.0f : 0.0f) : (a == 0 ? 0.0f : (a == 1 ? 1.0f : -1.0f)); }   // AT = [[1,1,1,0],[0,1,-1,-1]]
+
+template <int NR, int R0, class Pix>
+__device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __restrict__ U, const float4* sm, const int h,
+                                        const int mt_, Pix pix) {
+    constexpr int PD = 4;                                   // A-fragment prefetch distance in chunks (4 MFMAs each; fragments come from L2)
+    const unsigned ln = (threadIdx.x & 63u) * 16u;
+    const __amdgpu_buffer_rsrc_t ur = wrsrc(U);
+    // laundered per call: stops hipcc hoisting the ~80 constant fragment offsets of the peeled xi rows out of the image loop (SGPR spills)
+    int mt = mt_; asm volatile("" : "+s"(mt));
+    constexpr int a_lo = NR == 2 ? 0 : R0, a_hi = NR == 2 ? 4 : R0 + 3;
+    // A fragment of chunk kc of xi (a, b): byte offset a * 64 KiB + (2 b + mt) * 8 KiB + kc * 1 KiB (one scalar base per a + a literal)
+    auto ufrag = [&](int a, int b, int kc) { return wfrag(ur, ln, (size_t)(((4 * a + b) * 2 + mt) * 8 + kc) * 64); };
+    auto bases = [&](int a, int b, int (&pb)[4]) {          // d[i0][j0], d[i0][j1], d[i1][j0], d[i1][j1] of xi (a, b)
+        const int i0 = wino_i0(a), i1 = wino_i1(a), j0 = wino_i0(b), j1 = wino_i1(b);
+        pb[0] = pix(i0, j0); pb[1] = pix(i0, j1); pb[2] = pix(i1, j0); pb[3] = pix(i1, j1);
+    };
+    float4 aq[PD], raw[4];
+    int pb[4];
+#pragma unroll
+    for (int p = 0; p < PD; ++p) aq[p] = ufrag(a_lo, 0, p);
+    bases(a_lo, 0, pb);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) raw[q] = sm[pb[q] + h];
+    f32x16 xacc;
+    const f32x16 zero = {};
+    // the transform of xi (a, b) into the outputs
+    // (MASK: the output rows whose AT[r][a] is non-zero for this a -- a constant, so that no update is conditional at run time:
+    // hipcc turns a run-time skip into selects that hold every output twice)
+    auto otrans = [&](int a, int b, const f32x16& m, auto mask) {
+        constexpr int MASK = decltype(mask)::value;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            if (!((MASK >> r) & 1)) continue;
+            const float car = wino_at(R0 + r, a);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const float cbc = wino_at(c, b);
+                if (cbc == 0.0f) continue;
+                const float cf = car * cbc;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) out[r][c][e] = __builtin_fmaf(cf, m[e], out[r][c][e]);
+            }
+        }
+    };
+    auto xi_row = [&](int a, auto mask) {               // the four xi (a, 0..3)
+        const float s1 = wino_s1(a);
+        const int an = a + 1 < a_hi ? a + 1 : a;        // the next xi row (the last one re-reads its own fragments: never used)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const float t1 = wino_s1(b);
+#pragma unroll
+            for (int kc = 0; kc < 8; ++kc) {
+                const float4 av = aq[kc % PD];
+                aq[kc % PD] = (b * 8 + kc + PD < 32) ? ufrag(a, (b * 8 + kc + PD) >> 3, (kc + PD) & 7) : ufrag(an, 0, (kc + PD) & 7);
+                // V fragment of this chunk: (d00 + s1 d10) + t1 (d01 + s1 d11), per component
+                float4 v;
+                {
+                    const float4 c0 = make_float4(__builtin_fmaf(s1, raw[2].x, raw[0].x), __builtin_fmaf(s1, raw[2].y, raw[0].y),
+                                                  __builtin_fmaf(s1, raw[2].z, raw[0].z), __builtin_fmaf(s1, raw[2].w, raw[0].w));
+                    const float4 c1 = make_float4(__builtin_fmaf(s1, raw[3].x, raw[1].x), __builtin_fmaf(s1, raw[3].y, raw[1].y),
+                                                  __builtin_fmaf(s1, raw[3].z, raw[1].z), __builtin_fmaf(s1, raw[3].w, raw[1].w));
+                    v = make_float4(__builtin_fmaf(t1, c1.x, c0.x), __builtin_fmaf(t1, c1.y, c0.y), __builtin_fmaf(t1, c1.z, c0.z), __builtin_fmaf(t1, c1.w, c0.w));
+                }
+                // the next chunk's input pixels (the next xi's first chunk behind the last one)
+                if (kc < 7) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) raw[q] = sm[pb[q] + 2 * (kc + 1) + h];
+                } else {
+                    if (b < 3) bases(a, b + 1, pb);
+                    else bases(an, 0, pb);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) raw[q] = sm[pb[q] + h];
+                }
+                __builtin_amdgcn_sched_barrier(0);      // keep the prefetch loads AHEAD of this chunk's MFMAs
+                f32x16& x = xacc;
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, v.x, kc == 0 ? zero : x, 0, 0, 0);
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, v.y, x, 0, 0, 0);
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, v.z, x, 0, 0, 0);
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, v.w, x, 0, 0, 0);
+            }
+            // the xi's output transform (a second accumulator to overlap it with the next xi's MFMAs does not fit the register budget)
+            otrans(a, b, xacc, mask);
+        }
+    };
+    if constexpr (NR == 2) {                            // a = 0: row 0 only; a = 1, 2: both; a = 3: row 1 only
+        xi_row(0, std::integral_constant<int, 1>{});
+#pragma unroll 1
+        for (int a = 1; a < 3; ++a) xi_row(a, std::integral_constant<int, 3>{});
+        xi_row(3, std::integral_constant<int, 2>{});
+    } else {
+#pragma unroll 1
+        for (int a = a_lo; a < a_hi; ++a) xi_row(a, std::integral_constant<int, 1>{});
+    }
+}
 // Four waves of 64 features x 64 pixels each (NTW = 2 32-pixel tiles per wave; 256 VGPRs, 2 waves per SIMD).
 __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
     constexpr int NTW = 2;
     constexpr int NTHR = 512 / NTW;
     constexpr int NPH = 2048 / NTHR;                  // float4s per thread of each image half
+    constexpr int NPE = 8;                            // of them requested before layer 1 (its registers hold no more), the other 2 NPH - NPE behind it
     extern __shared__ __attribute__((aligned(16))) float4 sm[];        // [257 pixels][DA_PS slots]; pixel 256 = zeros
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -48,14 +161,12 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
     if (tid == 0) slot[0] = 2 * (int)gridDim.x + atomicAdd(a.queue, 1);
     int nimg = (int)blockIdx.x + (int)gridDim.x;
     // next image, in flight during compute
-    f32x4 pfa[NPH], pfb[NPH];
+    f32x4 pf[2 * NPH];
     f32x4* smv = reinterpret_cast<f32x4*>(sm);
     {
         const f32x4* X = reinterpret_cast<const f32x4*>(a.x4) + (size_t)blockIdx.x * 4096;
 #pragma unroll
-        for (int it = 0; it < NPH; ++it) pfa[it] = X[it * NTHR + tid];
-#pragma unroll
-        for (int it = 0; it < NPH; ++it) pfb[it] = X[(it + NPH) * NTHR + tid];
+        for (int it = 0; it < 2 * NPH; ++it) pf[it] = X[it * NTHR + tid];
     }
     if (tid < 16) sm[256 * DA_PS + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     // biases live in LDS: a global bias load inside an epilogue forces s_waitcnt vmcnt(0), i.e. waits for every store
@@ -78,22 +189,19 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
         if (live) {   // pixel it * (NTHR / 16) + (tid >> 4), quad tid & 15: one address register, immediate offsets
             const int sbase = (tl_ >> 4) * DA_PS + (tl_ & 15);
 #pragma unroll
-            for (int it = 0; it < NPH; ++it) smv[sbase + it * (NTHR / 16) * DA_PS] = pfa[it];
-#pragma unroll
-            for (int it = 0; it < NPH; ++it) smv[sbase + (it + NPH) * (NTHR / 16) * DA_PS] = pfb[it];
+            for (int it = 0; it < 2 * NPH; ++it) smv[sbase + it * (NTHR / 16) * DA_PS] = pf[it];
         }
         __syncthreads();
         const int nnimg = slot[0];                     // the image after nimg (written one iteration ago)
         int ticket = 0;
         if (tid == 0) ticket = 2 * (int)gridDim.x + atomicAdd(a.queue, 1);     // lands during the layer-1 contraction
-        const bool more = nimg < a.rows;
-        {   // request the next image now (clamped on the last pass: unconditional loads keep pf[] in registers)
-            const f32x4* X = reinterpret_cast<const f32x4*>(a.x4) + (size_t)(more ? nimg : img) * 4096;
+        // request the first NPE float4s of the next image now (clamped on the last pass: unconditional loads keep pf[] in registers).  Buffer loads
+        // (uniform image base, one lane offset): flat loads hold a 64-bit address per load
+        const int pimg = __builtin_amdgcn_readfirstlane(nimg < a.rows ? nimg : img);
+        const __amdgpu_buffer_rsrc_t xr = wrsrc(a.x4 + (size_t)pimg * 16384);
+        const unsigned tlo = (unsigned)tl_ * 16u;
 #pragma unroll
-            for (int it = 0; it < NPH; ++it) pfa[it] = (X + it * NTHR)[tl_];
-#pragma unroll
-            for (int it = 0; it < NPH; ++it) pfb[it] = (X + (it + NPH) * NTHR)[tl_];
-        }
+        for (int it = 0; it < NPE; ++it) pf[it] = __builtin_bit_cast(f32x4, wfrag(xr, tlo, (size_t)it * NTHR));
 
         f32x16 acc[2][NTW];
         // the accumulators start at the bias (register e of tile mt holds channel 32mt + (e&3) + 8(e>>2) + 4h) and ReLU is one
@@ -108,40 +216,43 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
                     for (int nt = 0; nt < NTW; ++nt) { acc[mt][nt][4 * g4] = bb.x; acc[mt][nt][4 * g4 + 1] = bb.y; acc[mt][nt][4 * g4 + 2] = bb.z; acc[mt][nt][4 * g4 + 3] = bb.w; }
                 }
         };
-        // ---------------- layer 1: out[oh,ow] = sum_{kh,kw} in[oh+1-kh, ow+1-kw] . W[:, :, kh, kw] --------------
+        // ---------------- layer 1 (Winograd F(2x2, 3x3), see wino_l1): wave w owns channels 32 (w >> 1) .. + 31 of the 32 tiles
+        // 32 (w & 1) .. + 31 (tile n = 8 ty + tx: tile rows 4 (w & 1) .. + 3), lane j = tile
+        const int l1mt = w >> 1, l1n = 32 * (w & 1) + j;
+        const int l1y = 2 * (l1n >> 3) - 1, l1x = 2 * (l1n & 7) - 1;      // the tile's input corner (may be -1: padding)
+        f32x16 (&l1o)[2][2] = acc;                  // (layer 2 reuses the registers)
         if (live) {
-        acc_init(0);
-        tap_loop_pd<2, NTW, 1>(acc, 9, W1, sm, h, [&](int t, int (&bs)[NTW], int (&sw)[NTW], int& wt) {
-            const int kh = t / 3, kw = t - kh * 3;
-            wt = t;
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                const int sy = prow0 + 2 * nt + 1 - kh, sx = pcol + 1 - kw;
-                const bool ok = sy >= 0 && sy < 16 && sx >= 0 && sx < 16;
-                const int sp = ok ? sy * 16 + sx : 256;
-                bs[nt] = sp * DA_PS; sw[nt] = 0;
+            for (int g4 = 0; g4 < 4; ++g4) {           // the outputs start at the bias (register e holds channel 32 mt + (e & 3) + 8 (e >> 2) + 4 h)
+                const float4 bb = sm[DA_BIAS + l1mt * 8 + 2 * g4 + h];
+#pragma unroll
+                for (int rc = 0; rc < 4; ++rc) { l1o[rc >> 1][rc & 1][4 * g4] = bb.x; l1o[rc >> 1][rc & 1][4 * g4 + 1] = bb.y; l1o[rc >> 1][rc & 1][4 * g4 + 2] = bb.z; l1o[rc >> 1][rc & 1][4 * g4 + 3] = bb.w; }
             }
-        }, ConvWIdx{});
+            wino_l1<2, 0>(l1o, W1, sm, h, l1mt, [&](int i, int jj) {
+                const int y = l1y + i, x = l1x + jj;
+                return ((unsigned)y < 16u && (unsigned)x < 16u ? y * 16 + x : 256) * DA_PS;
+            });
         }
         __syncthreads();                // every wave is done reading the input image (and slot[0])
         if (tid == 0) slot[0] = ticket;
         // bias + ReLU, written back IN PLACE as the input image of layer 2 (same padded layout)
         if (live)
 #pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) {
-            const int pix = 32 * NTW * w + 32 * nt + j;
+        for (int rc = 0; rc < 4; ++rc) {
+            const int pix = (l1y + 1 + (rc >> 1)) * 16 + l1x + 1 + (rc & 1);
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const int c4 = mt * 8 + 2 * g4 + h;
-                    float4 v;
-                    v.x = relu_bits(acc[mt][nt][4 * g4 + 0]); v.y = relu_bits(acc[mt][nt][4 * g4 + 1]);
-                    v.z = relu_bits(acc[mt][nt][4 * g4 + 2]); v.w = relu_bits(acc[mt][nt][4 * g4 + 3]);
-                    sm[pix * DA_PS + c4] = v;
-                }
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const f32x16& o = l1o[rc >> 1][rc & 1];
+                float4 v;
+                v.x = relu_bits(o[4 * g4 + 0]); v.y = relu_bits(o[4 * g4 + 1]);
+                v.z = relu_bits(o[4 * g4 + 2]); v.w = relu_bits(o[4 * g4 + 3]);
+                sm[pix * DA_PS + l1mt * 8 + 2 * g4 + h] = v;
+            }
         }
         __syncthreads();
+        // the rest of the next image, behind layer 1 (whose accumulators leave room for NPE float4s only; layer 2 covers its latency)
+#pragma unroll
+        for (int it = NPE; it < 2 * NPH; ++it) pf[it] = __builtin_bit_cast(f32x4, wfrag(xr, tlo, (size_t)it * NTHR));
 
         // ---------------- layer 2 (stride 2): 4 output parities, oh = 2*ih - 1 + kh ----------------------------
         float* Y = a.y2 + (size_t)img * (32 * 32 * 64);
@@ -176,9 +287,9 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
 // k_dec_a_s: the same two layers for SMALL launches (<= 128 images: the one-episode planner), one image over EIGHT workgroups.
 // Workgroup (image, p) owns the layer-2 input rows 2p, 2p + 1 (output rows 4p .. 4p + 3): it computes layer 1 for rows 2p .. 2p + 3
 // (the stride-2 layer reads one row below its own) from the input rows 2p - 1 .. 2p + 4, keeps them in LDS and contracts layer 2
-// for its row pair.  25 % more layer-1 work per image, an eighth of the latency (74 -> ~17 us per launch).  Every output element
-// sees the operations of k_dec_a in the same order (bias as start value, taps 0..8, channel blocks 0..7): bit-identical results.
-// Waves: layer 1: (feature tile mt = w >> 1, row pair nt = w & 1); layer 2: (mt = w >> 1, parities {(0,0), (1,1)} or {(0,1), (1,0)}).
+// for its row pair.  Every output element sees the operations of k_dec_a in the same order (layer 1: bias as start value, then xi
+// ascending, each xi-GEMM over channel blocks 0..7; layer 2: bias, taps, channel blocks 0..7): bit-identical results.
+// Waves: layer 1: (feature tile mt = w >> 1, output row r = w & 1 of the 16 Winograd tiles); layer 2: (mt = w >> 1, parities {(0,0), (1,1)} or {(0,1), (1,0)}).
 // ---------------------------------------------------------------------------------------------------------
 constexpr int DAS_IN = 6 * 16;                      // staged input pixels (+ a zero pixel)
 constexpr int DAS_L1 = 4 * 16;                      // layer-1 pixels kept (+ a zero pixel)
@@ -220,24 +331,33 @@ __global__ void __launch_bounds__(256, 2) k_dec_a_s(const DecAArgs a) {
             acc[0][0][4 * g4] = bb.x; acc[0][0][4 * g4 + 1] = bb.y; acc[0][0][4 * g4 + 2] = bb.z; acc[0][0][4 * g4 + 3] = bb.w;
         }
     };
-    {   // ---- layer 1 for image rows 2p + 2 nt + (j >> 4), nt = w & 1
-        const int nt = w & 1;
-        const int orow = 2 * p + 2 * nt + (j >> 4), ocol = j & 15;
-        acc_init(0);
-        tap_loop_pd<1, 1, 2>(acc, 9, W1, sin, h, [&](int t, int (&bs)[1], int (&sw)[1], int& wt) {
-            const int kh = t / 3, kw = t - kh * 3;
-            wt = t;
-            const int sy = orow + 1 - kh, sx = ocol + 1 - kw;
-            const bool ok = sy >= 0 && sy < 16 && sx >= 0 && sx < 16;
-            bs[0] = (ok ? (sy - (2 * p - 1)) * 16 + sx : DAS_IN) * DA_PS; sw[0] = 0;
-        }, PackedWIdx{2, 8, mt});
+    {   // ---- layer 1 (Winograd, wino_l1) for the 16 tiles of tile rows p, p + 1 (image rows 2p .. 2p + 3): wave w owns output row
+        // r = w & 1 of every tile (lanes j and j + 16 hold the same tile; the upper half is not stored)
+        const int r = w & 1, n = j & 15;
+        const int ly = 2 * (n >> 3) - 1, lx = 2 * (n & 7) - 1;          // the tile's input corner, in staged rows (2p - 1 = row 0) + 1
+        f32x16 o[1][2];
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-            float4 v;
-            v.x = relu_bits(acc[0][0][4 * g4 + 0]); v.y = relu_bits(acc[0][0][4 * g4 + 1]);
-            v.z = relu_bits(acc[0][0][4 * g4 + 2]); v.w = relu_bits(acc[0][0][4 * g4 + 3]);
-            sl1[(32 * nt + j) * DA_PS + mt * 8 + 2 * g4 + h] = v;
+            const float4 bb = sm[DAS_BIAS + mt * 8 + 2 * g4 + h];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) { o[0][c][4 * g4] = bb.x; o[0][c][4 * g4 + 1] = bb.y; o[0][c][4 * g4 + 2] = bb.z; o[0][c][4 * g4 + 3] = bb.w; }
         }
+        auto pix = [&](int i, int jj) {
+            const int sy = ly + 1 + i, x = lx + jj, y = 2 * p - 1 + sy;
+            return ((unsigned)y < 16u && (unsigned)x < 16u ? sy * 16 + x : DAS_IN) * DA_PS;
+        };
+        if (r) wino_l1<1, 1>(o, W1, sin, h, mt, pix);
+        else wino_l1<1, 0>(o, W1, sin, h, mt, pix);
+        if (j < 16)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                float4 v;
+                v.x = relu_bits(o[0][c][4 * g4 + 0]); v.y = relu_bits(o[0][c][4 * g4 + 1]);
+                v.z = relu_bits(o[0][c][4 * g4 + 2]); v.w = relu_bits(o[0][c][4 * g4 + 3]);
+                sl1[((ly + 1 + r) * 16 + lx + 1 + c) * DA_PS + mt * 8 + 2 * g4 + h] = v;
+            }
     }
     __syncthreads();
     // ---- layer 2 (stride 2) for the input rows 2p, 2p + 1: two output parities per wave

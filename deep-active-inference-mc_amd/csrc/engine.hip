@@ -1090,6 +1090,31 @@ int efe_commit_weights(efe_ctx* ctx) {
         const HostTensor* b = need(ctx, std::string(tk[i]) + ".bias", {tco[i]});
         if (!w || !b) return 1;
         const float* W = w->data.data(); const int Cout = tco[i];
+        if (i == 0) {   // po_net.13 (k_dec_a's layer 1, decoder.hip wino_l1): Winograd F(2x2, 3x3) weights U_xi = G g G^T, xi = 4a + b, in fp64,
+                        // rounded once; g[u][v] = W[ci][co][2 - u][2 - v] (the correlation form of the stride-1 transposed conv)
+            static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+            std::vector<float> U((size_t)16 * 64 * 64);
+            for (int co = 0; co < 64; ++co)
+                for (int ci = 0; ci < 64; ++ci) {
+                    const float* k = W + ((size_t)ci * 64 + co) * 9;
+                    double Gg[4][3];
+                    for (int a = 0; a < 4; ++a)
+                        for (int v = 0; v < 3; ++v) {
+                            double s = 0;
+                            for (int u = 0; u < 3; ++u) s += Gm[a][u] * (double)k[(2 - u) * 3 + (2 - v)];
+                            Gg[a][v] = s;
+                        }
+                    for (int a = 0; a < 4; ++a)
+                        for (int b = 0; b < 4; ++b) {
+                            double s = 0;
+                            for (int v = 0; v < 3; ++v) s += Gg[a][v] * Gm[b][v];
+                            U[((size_t)(a * 4 + b) * 64 + co) * 64 + ci] = (float)s;
+                        }
+                }
+            if (upload_packed(ctx, ctx->dec_ct[0], 16, 64, 64, [&](int t, int co, int ci) { return U[((size_t)t * 64 + co) * 64 + ci]; },
+                              b->data.data(), nullptr)) return 1;
+            continue;
+        }
         if (upload_packed(ctx, ctx->dec_ct[i], 9, Cout, tci[i],
                           [&](int t, int co, int ci) { return W[((size_t)ci * Cout + co) * 9 + t]; }, b->data.data(), nullptr)) return 1;
     }

@@ -105,7 +105,7 @@ struct GemmArgs {
 // fused decoder, stage A: x4 [rows][16][16][64] -> ConvT(64,64,s1)+ReLU -> ConvT(64,64,s2)+ReLU -> y2 [rows][4 parities][8 channel groups][16x16 positions][8] (see k_dec_a)
 struct DecAArgs {
     const float* x4; float* y2;
-    const float* w1; const float* b1;   // packed [9][2][8][64][4], bias [64]
+    const float* w1; const float* b1;   // Winograd F(2x2,3x3) weights packed [16 xi][2][8][64][4] (decoder.hip wino_l1), bias [64]
     const float* w2; const float* b2;
     int rows;
     RowMask live;
