@@ -10,9 +10,9 @@
 #include <map>
 #include <mutex>
 #include <string>
-#include <unordered_set>
 #include <vector>
 #include "../../include/efe_engine.h"
+#include "ctx_registry.h"
 #include "kernels.h"
 
 using namespace efe;
@@ -39,6 +39,7 @@ struct Arena {
     std::vector<std::pair<char*, size_t>> blocks;
     size_t cur = 0, off = 0, used_total = 0;
     void reset() { cur = 0; off = 0; used_total = 0; }
+    size_t capacity() const { size_t n = 0; for (auto& b : blocks) n += b.second; return n; }
 };
 
 }  // namespace
@@ -73,8 +74,8 @@ struct efe_ctx {
     Arena arena;
     // One scratch arena per context: calls are serialised by `mu` (host threads) and ordered across streams by `done_ev`
     // (a call on a different stream than the previous one first waits for that call's last kernel), so the arena reset at the
-    // start of a call never races with work still in flight.
-    std::mutex mu;
+    // start of a call never races with work still in flight.  `mu` and `dead` belong to the registry's protocol (ctx_registry.h).
+    std::mutex mu; bool dead = false;
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     hipEvent_t done_ev = nullptr;
@@ -105,7 +106,7 @@ struct efe_ctx {
     bool arch_gfx950 = false;      // hipDeviceProp_t.gcnArchName starts with gfx950 (checked at creation)
     int64_t sim_split = 1;         // simulations of <= 16 episodes: the chain kernel on eight workgroups per 8 episodes (k_sim_chain<8>); 0 = one workgroup (A/B, bit-identical)
     bool sim_sync_dirty = false;   // the last split launch's call did not complete on the host: zero sim_sync before the next one
-    float* sim_xch = nullptr; int* sim_sync = nullptr;      // its exchange buffer and arrival counters / sticky timeout flag (owned; zeroed on the stream before every split launch)
+    float* sim_xch = nullptr; int* sim_sync = nullptr;      // its exchange buffer and arrival counters / sticky timeout flag (owned; zeroed at creation, and on the stream when sim_sync_dirty; otherwise, after an in-kernel timeout too, the kernel's epilogue re-arms them)
     int64_t check_rows = 0;        // development: range-check efe_rows.ids on the host before every _rows call
     int64_t last_macs = 0;
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline)
@@ -666,61 +667,10 @@ inline bool capturing(hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
 }
-// Start of an engine call on stream `st`: the scratch arena is reused from its start, so work of the previous call that is still
-// in flight on ANOTHER stream must finish first (same stream: stream order already guarantees it).
-int check_ready(efe_ctx* ctx, hipStream_t st) {
-    if (!ctx) return 1;
-    if (!ctx->committed) return ctx->fail("weights not committed");
-    if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail("hipSetDevice failed");
-    if (ctx->have_last && ctx->last_stream != st && !capturing(st)) {
-        if (hipStreamWaitEvent(st, ctx->done_ev, 0) != hipSuccess) return ctx->fail("hipStreamWaitEvent failed");
-    }
-    ctx->arena.reset();
-    if (ctx->poison >= 0)                  // development: every call starts on scratch filled with this byte (reads of never-written scratch show up)
-        for (auto& b : ctx->arena.blocks)
-            if (hipMemsetAsync(b.first, (int)(ctx->poison & 0xff), b.second, st) != hipSuccess) return ctx->fail("poison memset failed");
-    ctx->last_macs = 0;
-    return 0;
-}
-
-// Every exit of an entry point that passed check_ready() -- success or failure (a bad argument, an arena hipMalloc failure, an
-// unsupported geometry after some kernels were already queued) -- records done_ev behind whatever was enqueued on `st`, so that the
-// next call, on any stream, orders its arena reuse behind it.
-struct CallGuard {
-    efe_ctx* ctx; hipStream_t st;
-    ~CallGuard() {
-        if (capturing(st)) return;
-        if (hipEventRecord(ctx->done_ev, st) == hipSuccess) { ctx->last_stream = st; ctx->have_last = true; }
-    }
-};
-
-int finish(efe_ctx* ctx, hipStream_t) {
-    if (!ctx->pending.empty()) { ctx->err = ctx->pending; ctx->pending.clear(); return 1; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ctx->fail(std::string("kernel launch: ") + hipGetErrorString(e));
-    return 0;
-}
-int finish(efe_ctx* ctx) {          // calls that use no engine scratch (environment, tree kernels, helpers)
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ctx->fail(std::string("kernel launch: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// Registry of live contexts: efe_create_cfg adds, efe_destroy removes.  Every entry point checks its handle against it before touching
-// the object (EFE_LOCK), so a stale or made-up efe_ctx* is an error return, not a dereference of freed memory (efe_ctx_alive exports the
-// test for bindings that carry the handle as an integer: csrc/torch_ops.cpp).
-std::mutex g_live_mu;
-std::unordered_set<const efe_ctx*> g_live;
-inline bool ctx_alive(const efe_ctx* c) {
-    if (!c) return false;
-    std::lock_guard<std::mutex> l(g_live_mu);
-    return g_live.count(c) != 0;
-}
-// An entry point makes the context's device current (hipSetDevice) for its launches / allocations and puts the CALLER's device back on
-// every exit: in a process that drives several GPUs a call on a context of GPU 1 must not leave the thread on GPU 1.
+// puts the caller's device back on exit if it is not `dev` (< 0: none): a call on a context of GPU 1 must not leave the thread on GPU 1
 struct DeviceScope {
     int prev = -1;
-    explicit DeviceScope(int dev) { int cur = -1; if (hipGetDevice(&cur) == hipSuccess && cur != dev) prev = cur; }
+    explicit DeviceScope(int dev) { int cur = -1; if (dev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != dev) prev = cur; }
     ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 // frees everything a context owns (device of the context current); also the failure paths of efe_create_cfg
@@ -732,7 +682,69 @@ void release_ctx(efe_ctx* ctx) {
     for (auto& b : ctx->arena.blocks) (void)hipFree(b.first);
     delete ctx;
 }
-#define EFE_LOCK(ctx) if (!ctx_alive(ctx)) return 1; std::lock_guard<std::mutex> lock_((ctx)->mu); DeviceScope dev_scope_((ctx)->device)
+// the registry's deleter: runs once efe_destroy has retired the context and its last admitted call has let go
+void destroy_ctx(efe_ctx* ctx) {
+    DeviceScope dev_scope_(ctx->device);
+    (void)hipSetDevice(ctx->device);
+    (void)hipDeviceSynchronize();
+    release_ctx(ctx);
+}
+// never destroyed: a context still live at exit is left to the process teardown, not released after the HIP runtime has shut down
+CtxRegistry<efe_ctx>& registry() { static auto* r = new CtxRegistry<efe_ctx>(destroy_ctx); return *r; }
+
+// The scope of one C ABI call: it admits the handle (ctx->mu held to its end) and puts the caller's device back on every exit.  Modes: host,
+// nothing more; device, the context's device made current; scratch, that and a call on the scratch arena on stream `st`: work of the previous
+// call still in flight on ANOTHER stream finishes first (same stream: stream order guarantees it), and every exit after that -- success or
+// failure, kernels maybe queued -- records done_ev behind `st`'s work, so that the next call, on any stream, can order its arena reuse behind it.
+// false: a refused handle (return code 1, efe_last_error explains) or a failed start (its message in ctx->err).
+enum class Mode { host, device, scratch };
+struct Call {
+    CtxRegistry<efe_ctx>::Admission adm;
+    efe_ctx* const ctx;
+    DeviceScope dev;
+    hipStream_t st;
+    bool ok = false, record = false;
+    Call(efe_ctx* c, Mode mode, hipStream_t stream = nullptr)
+        : adm(registry().admit(c)), ctx(adm.ctx.get()), dev(ctx ? ctx->device : -1), st(stream) { ok = ctx && !start(mode); }
+    int start(Mode mode) {
+        if (mode == Mode::scratch && !ctx->committed) return ctx->fail("weights not committed");
+        if (mode != Mode::host && hipSetDevice(ctx->device) != hipSuccess) return ctx->fail("hipSetDevice failed");
+        if (mode != Mode::scratch) return 0;
+        if (ctx->have_last && ctx->last_stream != st && !capturing(st) && hipStreamWaitEvent(st, ctx->done_ev, 0) != hipSuccess)
+            return ctx->fail("hipStreamWaitEvent failed");
+        ctx->arena.reset();
+        if (ctx->poison >= 0)                      // development: every call starts on scratch filled with this byte (reads of never-written scratch show up)
+            for (auto& b : ctx->arena.blocks)
+                if (hipMemsetAsync(b.first, (int)(ctx->poison & 0xff), b.second, st) != hipSuccess) return ctx->fail("poison memset failed");
+        ctx->last_macs = 0;
+        record = true;
+        return 0;
+    }
+    ~Call() {
+        if (record && !capturing(st) && hipEventRecord(ctx->done_ev, st) == hipSuccess) { ctx->last_stream = st; ctx->have_last = true; }
+        if (ctx) ctx->pending.clear();             // a launch helper's error belongs to this call, reported or not
+    }
+    explicit operator bool() const { return ok; }
+    // the end of a call that queued kernels: an error raised inside a launch helper, else the last launch error
+    int finish() {
+        if (!ctx->pending.empty()) return ctx->fail(ctx->pending);
+        hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : ctx->fail(std::string("kernel launch: ") + hipGetErrorString(e));
+    }
+};
+
+// the noise of a single-group network call (efe_transition / efe_decoder / efe_encoder)
+NoiseCfg noise_cfg(const efe_noise* nz, int M) {
+    NoiseCfg nc; nc.k0 = (uint32_t)nz->seed; nc.k1 = (uint32_t)(nz->seed >> 32); nc.rows_per_group = M; nc.row_offset = nz->row_offset;
+    nc.gm = GroupMap{1, 1, {nz->pass, 0, 0}, nz->stage, nz->sample};
+    return nc;
+}
+int mcts_tree(efe_ctx* ctx, const efe_mcts_tree* t, MctsTree& o) {
+    if (!t || !t->W || !t->N || !t->Qpi || !t->child || !t->S || t->E < 1 || t->cap < 1 || t->A < 1 || t->A > 8 || t->s_dim < 1)
+        return ctx->fail("efe_mcts: bad tree");
+    o = MctsTree{t->W, t->N, t->Qpi, t->child, t->S, t->E, t->cap, t->A, t->s_dim};
+    return 0;
+}
 
 }  // namespace
 
@@ -743,7 +755,7 @@ extern "C" {
 
 int efe_abi_version(void) { return 6; }
 
-int efe_ctx_alive(const efe_ctx* ctx) { return ctx_alive(ctx) ? 1 : 0; }
+int efe_ctx_alive(const efe_ctx* ctx) { return registry().alive(ctx) ? 1 : 0; }
 
 // efe_build_id(): the digest of the sources this library was compiled from -- a generated translation unit (build.py writes it at
 // link time, so an edit of one kernel file recompiles that file only)
@@ -801,24 +813,15 @@ int efe_create_cfg(efe_ctx** out, int device, int s_dim, int pi_dim, int channel
         ctx->owned.push_back(ctx->sim_sync);
         if (hipMemset(ctx->sim_sync, 0, sb) != hipSuccess) { release_ctx(ctx); return 4; }
     }
-    { std::lock_guard<std::mutex> l(g_live_mu); g_live.insert(ctx); }
+    registry().insert(ctx);
     *out = ctx;
     return 0;
 }
 
-void efe_destroy(efe_ctx* ctx) {
-    {   // leaves the registry first: a second efe_destroy of the same handle, or any later call with it, is refused instead of touching freed memory
-        std::lock_guard<std::mutex> l(g_live_mu);
-        if (!ctx || !g_live.erase(ctx)) return;
-    }
-    DeviceScope dev_scope_(ctx->device);
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
-    release_ctx(ctx);
-}
+void efe_destroy(efe_ctx* ctx) { registry().retire(ctx); }
 
 int efe_get_config(efe_ctx* ctx, int* s_dim, int* pi_dim, int* channels, int* resolution) {
-    if (!ctx_alive(ctx)) return 1;
+    Call call(ctx, Mode::host); if (!call) return 1;
     if (s_dim) *s_dim = S_DIM;
     if (pi_dim) *pi_dim = ctx->pi_dim;
     if (channels) *channels = ctx->chan;
@@ -827,7 +830,7 @@ int efe_get_config(efe_ctx* ctx, int* s_dim, int* pi_dim, int* channels, int* re
 }
 
 int efe_get_device(efe_ctx* ctx, int* device, char* pci_bus_id, int pci_bus_id_len) {
-    if (!ctx_alive(ctx)) return 1;
+    Call call(ctx, Mode::host); if (!call) return 1;
     if (device) *device = ctx->device;
     if (pci_bus_id && pci_bus_id_len > 0) {
         pci_bus_id[0] = 0;
@@ -836,11 +839,11 @@ int efe_get_device(efe_ctx* ctx, int* device, char* pci_bus_id, int pci_bus_id_l
     return 0;
 }
 
-const char* efe_last_error(efe_ctx* ctx) { return !ctx ? "null context" : ctx_alive(ctx) ? ctx->err.c_str() : "stale or invalid context handle"; }
+const char* efe_last_error(efe_ctx* ctx) { return !ctx ? "null context" : registry().alive(ctx) ? ctx->err.c_str() : "stale or invalid context handle"; }
 
 int efe_set_weight(efe_ctx* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim) {
     if (!key || !data_host || !shape || ndim < 1 || ndim > 4) return 1;
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::host); if (!call) return 1;
     HostTensor t;
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
@@ -854,7 +857,7 @@ static int pack_fc4_b3(efe_ctx* ctx, int mode);
 
 int efe_set_option(efe_ctx* ctx, const char* name, int64_t value) {
     if (!name) return 1;
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::host); if (!call) return 1;
     if (!strcmp(name, "dec_chunk")) { if (value < 1) return ctx->fail("dec_chunk < 1"); ctx->dec_chunk = value; return 0; }
     if (!strcmp(name, "reward_upstream_intent")) { ctx->reward_intent = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ct_fuse12")) { ctx->ct_fuse12 = value ? 1 : 0; return 0; }
@@ -939,8 +942,7 @@ static int pack_fc4_b3(efe_ctx* ctx, int mode) {
 }
 
 int efe_commit_weights(efe_ctx* ctx) {
-    EFE_LOCK(ctx);
-    HIPCHK(hipSetDevice(ctx->device));
+    Call call(ctx, Mode::device); if (!call) return 1;
     // a re-commit replaces the packed buffers of the previous one: wait for work that may still read them, then free them
     if (!ctx->wbufs.empty()) {
         HIPCHK(hipDeviceSynchronize());
@@ -1134,119 +1136,96 @@ int efe_commit_weights(efe_ctx* ctx) {
 }
 
 int efe_env_reset(efe_ctx* ctx, float* state, float* last_r, int E, const efe_noise* nz, void* stream) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (!state || !last_r || !nz || E < 1) return ctx->fail("efe_env_reset: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_env_reset(state, last_r, E, (uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), nz->stage, nz->row_offset, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_env_new_image(efe_ctx* ctx, float* state, int E, const efe_noise* nz, void* stream) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (!state || !nz || E < 1) return ctx->fail("efe_env_new_image: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_env_new_image(state, E, (uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), nz->stage, nz->row_offset, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_env_step(efe_ctx* ctx, float* state, float* last_r, const int32_t* actions, int E, int repeats, const efe_noise* nz,
                  int32_t* round_changed, void* stream) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (!state || !last_r || !actions || !nz || E < 1 || repeats < 1) return ctx->fail("efe_env_step: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_env_step(state, last_r, actions, round_changed, E, repeats, (uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), nz->stage,
                     nz->row_offset, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_env_render(efe_ctx* ctx, const float* state, const float* last_r, const uint8_t* imgs, int64_t n_imgs, float* frames,
                    int32_t* err, int E, void* stream) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (!state || !last_r || !imgs || !frames || n_imgs < 1 || E < 1) return ctx->fail("efe_env_render: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_env_render(state, last_r, imgs, (long)n_imgs, frames, err, E, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
-
-namespace {
-int mcts_tree(efe_ctx* ctx, const efe_mcts_tree* t, MctsTree& o) {
-    if (!t || !t->W || !t->N || !t->Qpi || !t->child || !t->S || t->E < 1 || t->cap < 1 || t->A < 1 || t->A > 8 || t->s_dim < 1)
-        return ctx->fail("efe_mcts: bad tree");
-    o = MctsTree{t->W, t->N, t->Qpi, t->child, t->S, t->E, t->cap, t->A, t->s_dim};
-    return 0;
-}
-}  // namespace
 
 int efe_mcts_select(efe_ctx* ctx, const efe_mcts_tree* tree, const uint8_t* active, float C, int use_prior, int max_depth,
                     int32_t* path_nodes, int32_t* path_act, int32_t* path_len, int32_t* leaf, float* leaf_s, float* leaf_s_rep,
                     void* stream) {
-    EFE_LOCK(ctx);
-    MctsTree t;
-    if (mcts_tree(ctx, tree, t)) return 1;
+    Call call(ctx, Mode::device); if (!call) return 1;
+    MctsTree t; if (mcts_tree(ctx, tree, t)) return 1;
     if (!active || !path_nodes || !path_act || !path_len || !leaf || !leaf_s || !leaf_s_rep || max_depth < 1)
         return ctx->fail("efe_mcts_select: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_mcts_select(t, active, C, use_prior, max_depth, path_nodes, path_act, path_len, leaf, leaf_s, leaf_s_rep, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_mcts_expand(efe_ctx* ctx, const efe_mcts_tree* tree, int32_t* n_nodes, const int32_t* nodes, const uint8_t* mask, const float* G,
                     const float* ps_next, void* stream) {
-    EFE_LOCK(ctx);
-    MctsTree t;
-    if (mcts_tree(ctx, tree, t)) return 1;
+    Call call(ctx, Mode::device); if (!call) return 1;
+    MctsTree t; if (mcts_tree(ctx, tree, t)) return 1;
     if (!n_nodes || !nodes || !mask || !G || !ps_next) return ctx->fail("efe_mcts_expand: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_mcts_expand(t, n_nodes, nodes, mask, G, ps_next, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_mcts_backprop(efe_ctx* ctx, const efe_mcts_tree* tree, const int32_t* path_nodes, const int32_t* path_act, const int32_t* path_len,
                       const int32_t* leaf, const uint8_t* active, const float* sims, int n_sims, const float* q0, int max_depth,
                       float* g_out, uint8_t* active_out, void* stream) {
-    EFE_LOCK(ctx);
-    MctsTree t;
-    if (mcts_tree(ctx, tree, t)) return 1;
+    Call call(ctx, Mode::device); if (!call) return 1;
+    MctsTree t; if (mcts_tree(ctx, tree, t)) return 1;
     if (!path_nodes || !path_act || !path_len || !leaf || !active || !sims || n_sims < 1 || !q0 || !g_out || !active_out || max_depth < 1)
         return ctx->fail("efe_mcts_backprop: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_mcts_backprop(t, path_nodes, path_act, path_len, leaf, active, sims, n_sims, q0, max_depth, g_out, active_out, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_mcts_step(efe_ctx* ctx, const efe_mcts_tree* tree, const int32_t* prev_path_act, const int32_t* prev_path_len, const float* sims, int n_sims,
                   const float* q0, float* prev_g_out, uint8_t* prev_active_out, uint8_t* active, int32_t* stop_at, int repeat, float threshold,
                   int32_t* n_active, float C, int use_prior, int max_depth, int32_t* path_nodes, int32_t* path_act, int32_t* path_len, int32_t* leaf,
                   float* leaf_s, float* leaf_s_rep, int32_t* prev_n_nodes, const float* prev_G, const float* prev_ps_next, void* stream) {
-    EFE_LOCK(ctx);
-    MctsTree t;
-    if (mcts_tree(ctx, tree, t)) return 1;
+    Call call(ctx, Mode::device); if (!call) return 1;
+    MctsTree t; if (mcts_tree(ctx, tree, t)) return 1;
     const int n_exp = (prev_n_nodes != nullptr) + (prev_G != nullptr) + (prev_ps_next != nullptr);
     if (!active || !stop_at || !n_active || !path_nodes || !path_act || !path_len || !leaf || !leaf_s || !leaf_s_rep || max_depth < 1 ||
         (prev_path_len && (!prev_path_act || !sims || n_sims < 1 || !q0 || !prev_g_out || !prev_active_out)) || (n_exp != 0 && n_exp != 3))
         return ctx->fail("efe_mcts_step: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     MctsStepArgs a{prev_path_act, prev_path_len, sims, n_sims, q0, prev_g_out, prev_active_out, active, stop_at, repeat, threshold, n_active,
                    C, use_prior, max_depth, path_nodes, path_act, path_len, leaf, leaf_s, leaf_s_rep, prev_n_nodes, prev_G, prev_ps_next};
     launch_mcts_step(t, a, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_mcts_stop(efe_ctx* ctx, const efe_mcts_tree* tree, uint8_t* active, int32_t* stop_at, int repeat, float threshold,
                   int32_t* n_active, void* stream) {
-    EFE_LOCK(ctx);
-    MctsTree t;
-    if (mcts_tree(ctx, tree, t)) return 1;
+    Call call(ctx, Mode::device); if (!call) return 1;
+    MctsTree t; if (mcts_tree(ctx, tree, t)) return 1;
     if (!active || !stop_at || !n_active) return ctx->fail("efe_mcts_stop: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_mcts_stop(t, active, stop_at, repeat, threshold, n_active, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
-int64_t efe_last_call_macs(efe_ctx* ctx) { return ctx ? ctx->last_macs : 0; }
+int64_t efe_last_call_macs(efe_ctx* ctx) { Call call(ctx, Mode::host); return call ? ctx->last_macs : 0; }
 
 int efe_prof_enable(efe_ctx* ctx, int on) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::host); if (!call) return 1;
     ctx->prof = (on < 0) ? 0xFFFFFFFFu : (unsigned)on;       // < 0 = all classes, otherwise a bitmask (bit c = class c)
     ctx->ev_used = 0;
     ctx->ev_spans.clear();
@@ -1257,8 +1236,7 @@ int efe_prof_classes(void) { return PROF_NCLS; }
 
 int efe_prof_read(efe_ctx* ctx, double* ms, int64_t* launches) {
     if (!ms || !launches) return 1;
-    EFE_LOCK(ctx);
-    HIPCHK(hipSetDevice(ctx->device));
+    Call call(ctx, Mode::device); if (!call) return 1;
     HIPCHK(hipDeviceSynchronize());
     for (int i = 0; i < PROF_NCLS; ++i) { ms[i] = 0.0; launches[i] = 0; }
     for (auto& sp : ctx->ev_spans) {
@@ -1274,54 +1252,42 @@ int efe_prof_read(efe_ctx* ctx, double* ms, int64_t* launches) {
 // ---- network level -------------------------------------------------------------------------------------
 int efe_transition(efe_ctx* ctx, const float* pi, const float* s0, int M, const efe_noise* nz, const float* eps,
                    float* ps1, float* mean, float* logvar, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!pi || !s0 || !nz || M < 1) return ctx->fail("efe_transition: bad arguments");
     float* x = ctx->allocT<float>((size_t)M * 16);
     float* tr = ctx->allocT<float>((size_t)M * 32);
     if (!x || !tr) return 1;
     launch_pack_x(pi, s0, x, M, ctx->pi_dim, S_DIM, st);
-    NoiseCfg nc; nc.k0 = (uint32_t)nz->seed; nc.k1 = (uint32_t)(nz->seed >> 32); nc.rows_per_group = M; nc.row_offset = nz->row_offset;
-    nc.gm = GroupMap{1, 1, {nz->pass, 0, 0}, nz->stage, nz->sample};
+    const NoiseCfg nc = noise_cfg(nz, M);
     if (run_mid(ctx, x, 0, M, tr, nc, st)) return 1;
     launch_split_enc(tr, mean, logvar, M, st);
     if (ps1) launch_root_post(tr, nullptr, eps, nullptr, ps1, M, 0, nc.k0, nc.k1, nz->pass, nz->sample, nz->stage, nz->row_offset, ctx->pi_dim, st);
-    return finish(ctx, st);
+    return call.finish();
 }
 
 int efe_decoder(efe_ctx* ctx, const float* s, int M, const efe_noise* nz, float* po, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!s || !nz || !po || M < 1) return ctx->fail("efe_decoder: bad arguments");
     float* x = ctx->allocT<float>((size_t)M * 16);
     float* val = ctx->allocT<float>((size_t)M * 4);        // (quarter sums when the launch is split; unused by this entry point)
     if (!x || !val) return 1;
     launch_pad16(s, x, M, S_DIM, st);
-    NoiseCfg nc; nc.k0 = (uint32_t)nz->seed; nc.k1 = (uint32_t)(nz->seed >> 32); nc.rows_per_group = M; nc.row_offset = nz->row_offset;
-    nc.gm = GroupMap{1, 1, {nz->pass, 0, 0}, nz->stage, nz->sample};
+    const NoiseCfg nc = noise_cfg(nz, M);
     if (ctx->generic) {            // the generic path stores NHWC4 images: convert to the NCHW the API returns
         float* tmp = ctx->allocT<float>((size_t)M * ctx->img_store);
         if (!tmp) return 1;
         if (run_decoder(ctx, x, M, nc, 0, 1, val, tmp, st)) return 1;
         launch_to_nchw(tmp, po, M, ctx->res * ctx->res, ctx->chan, st);
     } else if (run_decoder(ctx, x, M, nc, 0, 1, val, po, st)) return 1;
-    return finish(ctx, st);
+    return call.finish();
 }
 
 int efe_encoder(efe_ctx* ctx, const float* o, int M, const efe_noise* nz, const float* eps, float* s, float* mean, float* logvar, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!o || !nz || M < 1) return ctx->fail("efe_encoder: bad arguments");
     float* enc = ctx->allocT<float>((size_t)M * 32);
     if (!enc) return 1;
-    NoiseCfg nc; nc.k0 = (uint32_t)nz->seed; nc.k1 = (uint32_t)(nz->seed >> 32); nc.rows_per_group = M; nc.row_offset = nz->row_offset;
-    nc.gm = GroupMap{1, 1, {nz->pass, 0, 0}, nz->stage, nz->sample};
+    const NoiseCfg nc = noise_cfg(nz, M);
     if (ctx->generic) {
         float* o8 = ctx->allocT<float>((size_t)M * ctx->img_store);
         if (!o8) return 1;
@@ -1331,14 +1297,11 @@ int efe_encoder(efe_ctx* ctx, const float* o, int M, const efe_noise* nz, const 
     if (run_encoder(ctx, o, M, nc, enc, st)) return 1;
     launch_split_enc(enc, mean, logvar, M, st);
     if (s) launch_root_post(enc, nullptr, eps, nullptr, s, M, 0, nc.k0, nc.k1, nz->pass, nz->sample, nz->stage, nz->row_offset, ctx->pi_dim, st);
-    return finish(ctx, st);
+    return call.finish();
 }
 
 int efe_habit(efe_ctx* ctx, const float* s, int M, float* logits, float* q, float* logq, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!s || M < 1) return ctx->fail("efe_habit: bad arguments");
     float* x = ctx->allocT<float>((size_t)M * 16);
     float* l32 = ctx->allocT<float>((size_t)M * 32);
@@ -1346,26 +1309,24 @@ int efe_habit(efe_ctx* ctx, const float* s, int M, float* logits, float* q, floa
     launch_pad16(s, x, M, S_DIM, st);
     if (run_habit(ctx, x, M, l32, st)) return 1;
     launch_softmax4(l32, logits, q, logq, M, ctx->pi_dim, st);
-    return finish(ctx, st);
+    return call.finish();
 }
 
 int efe_check_reward(efe_ctx* ctx, const float* o, int M, float* out, void* stream) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (!o || !out || M < 1) return ctx->fail("efe_check_reward: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     if (ctx->generic) launch_check_reward_g(o, out, M, ctx->chan, ctx->res, ctx->res, (int)ctx->reward_intent, (hipStream_t)stream);
     else launch_check_reward(o, out, M, (int)ctx->reward_intent, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 int efe_reparameterize(efe_ctx* ctx, const float* mean, const float* logvar, int M, int n, const efe_noise* nz, const float* eps,
                        float* out, void* stream) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (!mean || !logvar || !nz || !out || M < 1 || n < 1) return ctx->fail("efe_reparameterize: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_reparam(mean, logvar, eps, out, M, n, (uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), nz->pass, nz->sample, nz->stage,
                    nz->row_offset, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 // ---- EFE level -----------------------------------------------------------------------------------------
@@ -1374,22 +1335,17 @@ struct RowSet { const uint8_t* mask; const int32_t* ids; int div; };
 static int row_set(efe_ctx* ctx, const efe_rows* rows, int n_rows, int fixed_div, RowSet& out, const char* who, hipStream_t st) {
     if (!rows) { out = RowSet{nullptr, nullptr, fixed_div > 0 ? fixed_div : 1}; return 0; }
     const int div = fixed_div > 0 ? fixed_div : rows->rows_per_entry;
-    if (div < 1 || ((rows->mask || rows->ids) && n_rows % div != 0)) { ctx->fail((std::string(who) + ": efe_rows.rows_per_entry must divide the row count").c_str()); return 1; }
+    if (div < 1 || ((rows->mask || rows->ids) && n_rows % div != 0)) return ctx->fail(std::string(who) + ": efe_rows.rows_per_entry must divide the row count");
     const int n_entries = n_rows / div;
-    if (rows->n_total < 0 || (rows->n_total > 0 && n_entries > rows->n_total)) {
-        ctx->fail((std::string(who) + ": the call has " + std::to_string(n_entries) + " entries, efe_rows.n_total says " + std::to_string(rows->n_total)).c_str());
-        return 1;
-    }
+    if (rows->n_total < 0 || (rows->n_total > 0 && n_entries > rows->n_total))
+        return ctx->fail(std::string(who) + ": the call has " + std::to_string(n_entries) + " entries, efe_rows.n_total says " + std::to_string(rows->n_total));
     if (ctx->check_rows && rows->ids && rows->n_total > 0) {          // development option: ids range-checked on the host (synchronises)
         std::vector<int32_t> hid((size_t)n_entries);
-        if (hipMemcpyAsync(hid.data(), rows->ids, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            ctx->fail((std::string(who) + ": check_rows could not read efe_rows.ids").c_str()); return 1;
-        }
+        if (hipMemcpyAsync(hid.data(), rows->ids, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return ctx->fail(std::string(who) + ": check_rows could not read efe_rows.ids");
         for (int i = 0; i < n_entries; ++i)
-            if (hid[(size_t)i] < 0 || hid[(size_t)i] >= rows->n_total) {
-                ctx->fail((std::string(who) + ": efe_rows.ids[" + std::to_string(i) + "] = " + std::to_string(hid[(size_t)i]) + " is outside [0, n_total = " + std::to_string(rows->n_total) + ")").c_str());
-                return 1;
-            }
+            if (hid[(size_t)i] < 0 || hid[(size_t)i] >= rows->n_total)
+                return ctx->fail(std::string(who) + ": efe_rows.ids[" + std::to_string(i) + "] = " + std::to_string(hid[(size_t)i]) + " is outside [0, n_total = " + std::to_string(rows->n_total) + ")");
     }
     out = RowSet{rows->mask, rows->ids, div};
     return 0;
@@ -1403,10 +1359,7 @@ int efe_calculate_g(efe_ctx* ctx, const float* s0, const float* pi0, int M, int 
 int efe_calculate_g_rows(efe_ctx* ctx, const float* s0, const float* pi0, int M, int samples, int mean_mode, const efe_noise* nz,
                          const float* eps, const efe_rows* rows, float* G, float* terms, float* ps1, float* ps1_mean, float* po1,
                          float* t2parts, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!s0 || !pi0 || !nz || !G || M < 1 || samples < 1 || samples > 65535) return ctx->fail("efe_calculate_g: bad arguments");
     float* x = ctx->allocT<float>((size_t)M * 16);
     if (!x) return 1;
@@ -1419,15 +1372,12 @@ int efe_calculate_g_rows(efe_ctx* ctx, const float* s0, const float* pi0, int M,
     if (row_set(ctx, rows, M, 0, rs, "efe_calculate_g_rows", st)) return 1;
     io.mask = rs.mask; io.ids = rs.ids; io.mask_div = rs.div;
     if (run_core(ctx, io, st)) return 1;
-    return finish(ctx, st);
+    return call.finish();
 }
 
 int efe_rollout(efe_ctx* ctx, const float* o, const float* pi, int M, int steps, int samples, int calc_mean, int per_stage_mean,
                 const efe_noise* nz, const float* eps, float* sum_G, float* sum_terms, float* po1, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!o || !pi || !nz || !sum_G || M < 1 || steps < 1 || samples < 1 || samples > 65535) return ctx->fail("efe_rollout: bad arguments");
     const uint32_t k0 = (uint32_t)nz->seed, k1 = (uint32_t)(nz->seed >> 32);
     float* enc0 = ctx->allocT<float>((size_t)M * 32);
@@ -1452,7 +1402,7 @@ int efe_rollout(efe_ctx* ctx, const float* o, const float* pi, int M, int steps,
     io.eps = eps ? eps + (size_t)M * 10 : nullptr;
     io.G = sum_G; io.terms = sum_terms; io.po1 = po1;
     if (run_core(ctx, io, st)) return 1;
-    return finish(ctx, st);
+    return call.finish();
 }
 
 static int trajectory_impl(efe_ctx* ctx, const float* s0_traj, const float* ps1_traj, const float* mean_traj, const float* lv_traj,
@@ -1471,15 +1421,12 @@ static int trajectory_impl(efe_ctx* ctx, const float* s0_traj, const float* ps1_
 
 int efe_trajectory(efe_ctx* ctx, const float* s0_traj, const float* ps1_traj, const float* ps1_mean_traj, const float* ps1_logvar_traj,
                    const float* pi0_traj, int T, const efe_noise* nz, const float* eps, float* G, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!s0_traj || !ps1_traj || !ps1_mean_traj || !ps1_logvar_traj || !pi0_traj || !nz || !G || T < 1)
         return ctx->fail("efe_trajectory: bad arguments");
     if (trajectory_impl(ctx, s0_traj, ps1_traj, ps1_mean_traj, ps1_logvar_traj, pi0_traj, T, (uint32_t)nz->seed,
                         (uint32_t)(nz->seed >> 32), nz->stage, nz->row_offset, eps, G, nullptr, nullptr, 1, nullptr, st)) return 1;
-    return finish(ctx, st);
+    return call.finish();
 }
 
 int efe_simulate(efe_ctx* ctx, const float* starting_s, int E, int depth, int use_means, const efe_noise* nz,
@@ -1489,10 +1436,7 @@ int efe_simulate(efe_ctx* ctx, const float* starting_s, int E, int depth, int us
 
 int efe_simulate_rows(efe_ctx* ctx, const float* starting_s, int E, int depth, int use_means, const efe_noise* nz,
                       const float* eps, const float* u, const efe_rows* rows, float* G_mean, float* pi0, float* Qpi0, void* stream) {
-    EFE_LOCK(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (check_ready(ctx, st)) return 1;
-    CallGuard guard_{ctx, st};
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!starting_s || !nz || !G_mean || !pi0 || E < 1 || depth < 1 || depth > 65535) return ctx->fail("efe_simulate: bad arguments");
     const uint32_t k0 = (uint32_t)nz->seed, k1 = (uint32_t)(nz->seed >> 32);
     const int T = depth;
@@ -1535,26 +1479,23 @@ int efe_simulate_rows(efe_ctx* ctx, const float* starting_s, int E, int depth, i
     if (trajectory_impl(ctx, s0t, ps1t, mt, lvt, pi0, E * T, k0, k1, nz->stage, nz->row_offset * (uint32_t)T,
                         eps ? eps + (size_t)T * E * 10 : nullptr, Gt, rs.mask, rs.ids, T, pre_tr, st)) return 1;     // trajectory row e * T + t belongs to episode slot e
     launch_mean_rows(Gt, G_mean, E, T, st);
-    const int rc = finish(ctx, st);
+    const int rc = call.finish();
     if (rc == 0 && split_launch) ctx->sim_sync_dirty = false;
     return rc;
 }
 
 int efe_action_posterior(efe_ctx* ctx, const float* sum_G, int n_groups, int n, float temperature, float* P, float* logP, void* stream) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (!sum_G || !P || !logP || n_groups < 1 || n < 1 || n > 8) return ctx->fail("efe_action_posterior: bad arguments");
-    HIPCHK(hipSetDevice(ctx->device));
     launch_posterior(sum_G, P, logP, n_groups, n, temperature, (hipStream_t)stream);
-    return finish(ctx);
+    return call.finish();
 }
 
 // ---- scratch management --------------------------------------------------------------------------------
 int efe_reserve(efe_ctx* ctx, int64_t bytes) {
-    EFE_LOCK(ctx);
+    Call call(ctx, Mode::device); if (!call) return 1;
     if (bytes < 0) return ctx->fail("efe_reserve: bytes < 0");
-    HIPCHK(hipSetDevice(ctx->device));
-    size_t have = 0;
-    for (auto& b : ctx->arena.blocks) have += b.second;
+    const size_t have = ctx->arena.capacity();
     if (ctx->arena.blocks.size() <= 1 && have >= (size_t)bytes) return 0;
     // one block that holds everything: a bump allocation never has to skip to the next block (no fragmentation, no growth)
     HIPCHK(hipDeviceSynchronize());
@@ -1571,7 +1512,8 @@ int efe_reserve(efe_ctx* ctx, int64_t bytes) {
 int64_t efe_rollout_scratch_bytes(efe_ctx* ctx, int M, int steps, int samples) {
     // mirrors the allocations of efe_rollout (run_encoder for the root, run_core: run_mid per stage, run_decoder, run_encoder);
     // tests/test_gpu_parity.py::test_reserve_no_growth keeps it honest
-    if (!ctx_alive(ctx) || M < 1 || steps < 1 || samples < 1) return 0;
+    Call call(ctx, Mode::host);
+    if (!call || M < 1 || steps < 1 || samples < 1) return 0;
     const size_t A = (size_t)ctx->arena_align;
     const int64_t dec_chunk = ctx->dec_chunk, enc_chunk = ctx->enc_chunk;
     auto al = [A](size_t b) { return (b + A - 1) / A * A; };
@@ -1608,10 +1550,8 @@ int64_t efe_rollout_scratch_bytes(efe_ctx* ctx, int M, int steps, int samples) {
 }
 
 int efe_arena_stats(efe_ctx* ctx, int64_t* capacity_bytes, int64_t* high_water_bytes, int64_t* grow_count) {
-    EFE_LOCK(ctx);
-    size_t have = 0;
-    for (auto& b : ctx->arena.blocks) have += b.second;
-    if (capacity_bytes) *capacity_bytes = (int64_t)have;
+    Call call(ctx, Mode::host); if (!call) return 1;
+    if (capacity_bytes) *capacity_bytes = (int64_t)ctx->arena.capacity();
     if (high_water_bytes) *high_water_bytes = (int64_t)ctx->high_water;
     if (grow_count) *grow_count = ctx->arena_grows;
     return 0;

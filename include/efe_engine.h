@@ -13,11 +13,14 @@
  *     its packed weights and a scratch arena.  Calls are stream-ordered on `stream` (a hipStream_t
  *     passed as void*; NULL = default stream) and return without synchronising, unless the arena must
  *     grow (first call at a new size; efe_reserve pre-sizes it so that steady-state calls never hipMalloc).
- *   - threading / streams: a context has ONE scratch arena.  Entry points take a per-context mutex, so
- *     several host threads may share a context (their calls serialise); a call issued on a different
- *     stream than the previous call first waits (hipStreamWaitEvent) for that call's last kernel, so
- *     switching streams is safe and costs one event wait.  For concurrent execution on several streams
- *     use one context per stream (weights are 21 MB).
+ *   - threading / streams: a context has ONE scratch arena.  Every entry point, the getters and
+ *     efe_last_call_macs included, first checks its handle against the library's registry of live
+ *     contexts and takes the context's mutex, so several host threads may share a context (their calls
+ *     serialise).  efe_destroy may be called while other threads are in calls on the same context: it
+ *     waits for the call in progress, and calls admitted after it are refused (return code 1).  A call
+ *     issued on a different stream than the previous call first waits (hipStreamWaitEvent) for that
+ *     call's last kernel, so switching streams is safe and costs one event wait.  For concurrent
+ *     execution on several streams use one context per stream (weights are 21 MB).
  *   - return value: 0 on success, non-zero on error (efe_last_error() gives the message).
  *   - noise: MC-dropout masks / normals / action uniforms are a pure function of
  *     (seed, stage, pass, sample, global row = row_offset + r, element) -- see csrc/philox.h --
@@ -49,12 +52,17 @@ int efe_get_config(efe_ctx* ctx, int* s_dim, int* pi_dim, int* channels, int* re
 /* the HIP device the context was created on (efe_create's `device`) and the PCI bus id string of that device ("0000:c1:00.0"; buf may be
  * NULL): what a multi-GPU launcher checks so that rank r really owns GPU r (bench.py gathers them and refuses two ranks on one device) */
 int efe_get_device(efe_ctx* ctx, int* device, char* pci_bus_id, int pci_bus_id_len);
-void efe_destroy(efe_ctx* ctx);                                  /* a handle that is not live (already destroyed, never created) is ignored */
+/* Removes the context from the registry, so that later calls with it are refused; waits for a call in progress on another thread; the
+ * context's memory is released (after a device synchronisation) once no call holds it.  A handle that is not live (already destroyed,
+ * never created) is ignored. */
+void efe_destroy(efe_ctx* ctx);
 const char* efe_last_error(efe_ctx* ctx);
 /* 1 if `ctx` is a live context of this process (created by efe_create[_cfg], not yet destroyed), else 0; never dereferences the pointer.
- * The library keeps a registry of its contexts and EVERY entry point checks its handle against it first (a stale handle is return code 1,
- * not a use of freed memory); bindings that carry the handle as an integer (torch.ops.efe.*, ctypes) use this to raise a proper error.
- * Every entry point also restores the CALLER's current HIP device before it returns (the context's device is current only inside the call). */
+ * The library keeps a registry of its contexts and EVERY entry point checks its handle against it first, before it reads the context: a
+ * stale or made-up handle is return code 1 (efe_last_call_macs: 0, efe_rollout_scratch_bytes: 0) and efe_last_error reads "stale or
+ * invalid context handle", never a use of freed memory, also when efe_destroy runs on another thread.  Bindings that carry the handle as an
+ * integer (torch.ops.efe.*, ctypes) use this to raise a proper error.  Every entry point also restores the CALLER's current HIP device
+ * before it returns (the context's device is current only inside the call). */
 int efe_ctx_alive(const efe_ctx* ctx);
 int efe_abi_version(void);                                       /* 6 (history of the versions: INTEGRATION.md section 4) */
 /* hex digest of the sources this library was compiled from (build.py stamps it; the Python loader refuses a library whose
@@ -245,7 +253,7 @@ int efe_mcts_stop(efe_ctx*, const efe_mcts_tree* tree, uint8_t* active, int32_t*
                   int32_t* n_active, void* stream);
 
 
-/* introspection for benches: algorithmic MACs of the last EFE-level call. */
+/* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
 /* per-kernel-class timing with HIP events recorded on the launch stream (bench.py roofline leg).

@@ -1098,6 +1098,12 @@ def test_custom_op_boundary_refuses_stale_handles_and_foreign_devices(weights_ca
     # the C ABI itself refuses them too (return code 1, "stale or invalid context handle"), and a second destroy is a no-op
     assert lib.efe_habit(C.c_void_p(h), C.c_void_p(s.data_ptr()), 4, None, None, None, None) == 1
     assert b'stale' in lib.efe_last_error(C.c_void_p(h))
+    # ... the getters and the introspection calls as well: none of them reads the freed context
+    assert lib.efe_last_call_macs(C.c_void_p(h)) == 0
+    i = [C.c_int(-1) for _ in range(4)]
+    assert lib.efe_get_config(C.c_void_p(h), *[C.byref(v) for v in i]) == 1
+    assert lib.efe_get_device(C.c_void_p(h), C.byref(i[0]), None, 0) == 1
+    assert lib.efe_rollout_scratch_bytes(C.c_void_p(h), 4, 1, 1) == 0
     lib.efe_destroy(C.c_void_p(h))
     # device discipline
     m2 = daimc_amd.ActiveInferenceModel(10, 4, 0.0, 1.0, 1.0, device='cuda:0', seed=3, init_weights=False)
