@@ -10,3 +10,5 @@ from .mcts import (Node, MCTS_Params, active_inference_mcts, calc_threshold, nor
 from .util import softmax_multi_with_log, plan_actions_batch, make_batch_dsprites_active_inference  # noqa: F401
 from .env import Game, synthetic_sprite_bank  # noqa: F401
 from .parallel import episode_shard, gather_action_posteriors  # noqa: F401
+from . import loss  # noqa: F401
+from .loss import free_energy, FreeEnergy  # noqa: F401

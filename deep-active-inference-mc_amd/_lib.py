@@ -12,7 +12,8 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_prof_enable', 'efe_prof_classes', 'efe_prof_read', 'efe_env_reset', 'efe_env_step', 'efe_env_render',
            'efe_check_reward', 'efe_reparameterize', 'efe_mcts_select', 'efe_mcts_expand', 'efe_mcts_backprop', 'efe_mcts_stop',
            'efe_build_id', 'efe_reserve', 'efe_rollout_scratch_bytes', 'efe_arena_stats', 'efe_env_new_image', 'efe_create_cfg', 'efe_get_config', 'efe_get_device', 'efe_ctx_alive',
-           'efe_calculate_g_rows', 'efe_simulate_rows', 'efe_mcts_step']
+           'efe_calculate_g_rows', 'efe_simulate_rows', 'efe_mcts_step',
+           'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down']
 ABI_VERSION = 6
 
 
@@ -24,6 +25,23 @@ class EfeMctsTree(C.Structure):
 class EfeNoise(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('stage', C.c_uint32), ('pass_', C.c_uint32), ('sample', C.c_uint32),
                 ('row_offset', C.c_uint32)]
+
+
+EFE_OMEGA_ARRAY, EFE_OMEGA_SCALAR, EFE_OMEGA_DERIVED = 0, 1, 2
+
+
+class EfeFeParams(C.Structure):
+    _fields_ = [('gamma', C.c_float), ('beta_s', C.c_float), ('beta_o', C.c_float), ('omega_mode', C.c_int32),
+                ('omega', C.c_void_p), ('omega_scalar', C.c_float), ('a', C.c_float), ('b', C.c_float), ('c', C.c_float),
+                ('d', C.c_float)]
+
+
+FE_OUT_FIELDS = ('F_top', 'kl_pi', 'kl_pi_anal', 'Qpi', 'omega', 'F_mid', 'kl_s_mid', 'kl_s_mid_anal', 'ps1', 'ps1_mean', 'ps1_logvar',
+                 'F_down', 'nlogpo1', 'kl_s', 'kl_s_anal', 'kl_naive', 'kl_naive_anal', 'po1', 'qs1', 's0', 'qs1_mean', 'qs1_logvar')
+
+
+class EfeFeOut(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in FE_OUT_FIELDS]
 
 
 _lib = None
@@ -119,5 +137,10 @@ def load():
     lib.efe_mcts_backprop.argtypes = [p, tp, p, p, p, p, p, f32p, i, f32p, i, f32p, p, p]; lib.efe_mcts_backprop.restype = i
     lib.efe_mcts_stop.argtypes = [p, tp, p, p, i, C.c_float, p, p]; lib.efe_mcts_stop.restype = i
     lib.efe_mcts_step.argtypes = [p, tp, p, p, f32p, i, f32p, f32p, p, p, p, i, C.c_float, p, C.c_float, i, i, p, p, p, p, f32p, f32p, p, f32p, f32p, p]; lib.efe_mcts_step.restype = i
+    fpp, fop = C.POINTER(EfeFeParams), C.POINTER(EfeFeOut)
+    lib.efe_free_energy.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_free_energy.restype = i
+    lib.efe_loss_top.argtypes = [p, f32p, f32p, i, fop, p]; lib.efe_loss_top.restype = i
+    lib.efe_loss_mid.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_loss_mid.restype = i
+    lib.efe_loss_down.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_loss_down.restype = i
     _lib = lib
     return lib

@@ -349,6 +349,28 @@ void launch_nhwc4_to_8(const float* in, float* out, long n_pix, hipStream_t st);
 void launch_to_nchw(const float* in, float* out, long M, int HW, int C, hipStream_t st);
 void launch_check_reward_g(const float* o, float* out, int M, int C, int H, int W, int intent, hipStream_t st);
 
+// forward free energy (loss.hip): per-row tails of compute_loss_top / _mid / _down.  Row r of every [M]/[M][k] array is row r of the call.
+constexpr int S_DIM_FE = 10;
+struct FeArgs {
+    int M, A;                                           // rows of the call, pi_dim
+    // top: Qpi, log_Qpi [M][A] (habit head), log_Ppi [M][A]; q == nullptr: no top part
+    const float* q; const float* logq; const float* log_Ppi;
+    float* kl_pi_anal; float* kl_pi; float* F_top;
+    // omega: 0 = omega_in [M], 1 = omega_scalar, 2 = compute_omega(kl_pi, oa_a, oa_b, oa_c, oa_d) (k_fe_top_mid only); omega_out [M] nullable
+    int omega_mode; const float* omega_in; float omega_scalar; float oa_a, oa_b, oa_c, oa_d;
+    float* omega_out;
+    // posterior q(s1) and prior p(s1) means / logvars, row strides q1_ld / p1_ld; q1_mean == nullptr in k_fe_top_mid: no mid part
+    const float* q1_mean; const float* q1_lv; int q1_ld;
+    const float* p1_mean; const float* p1_lv; int p1_ld;
+    float* kl_mid_anal; float* kl_mid; float* F_mid;
+    // down: o1 NCHW [M][C*HW]; the image block handed to launch_fe_down is NCHW, or NHWC4 (generic store) when nhwc4
+    const float* o1; int C, HW, nhwc4;
+    float gamma, beta_s, beta_o;
+    float* F_down; float* nlogpo1; float* kl_s; float* kl_s_anal; float* kl_naive; float* kl_naive_anal;
+};
+void launch_fe_top_mid(const FeArgs& a, hipStream_t st);
+void launch_fe_down(const FeArgs& a, const float* po, int m0, int rows, hipStream_t st);     // rows [m0, m0 + rows); po = their images
+
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);
 void launch_root_post(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,

@@ -21,7 +21,10 @@ namespace efe {
 
 enum : uint32_t { TAG_MID = 0x10, TAG_DEC = 0x20, TAG_ENC = 0x30, TAG_EPS = 0x40, TAG_ACT = 0x50 };
 enum : uint32_t { PASS_T1 = 0, PASS_D1 = 1, PASS_E1 = 2, PASS_T2 = 3, PASS_D2A = 4, PASS_D2B = 5,
-                  PASS_ROOT = 6, PASS_HABIT = 7, PASS_SIM = 8 };
+                  PASS_ROOT = 6, PASS_HABIT = 7, PASS_SIM = 8,
+                  // forward free energy of a training step (efe_free_energy, loss.hip): o0 encoder + normals, o1 encoder, transition +
+                  // normals, compute_loss_down's o1 encoder + normals + decoder.  (The environment's pass 9 draws under its own tag, TAG_ENV.)
+                  PASS_FE_Q0 = 9, PASS_FE_Q1 = 10, PASS_FE_T = 11, PASS_FE_DOWN = 12 };
 
 __host__ __device__ inline uint32_t stream_id(uint32_t pass, uint32_t sample) {
     return ((pass & 0xFFFFu) << 16) | (sample & 0xFFFFu);

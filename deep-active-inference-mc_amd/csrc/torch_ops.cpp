@@ -11,6 +11,7 @@
 #include <torch/library.h>
 
 #include <tuple>
+#include <vector>
 
 #include "efe_engine.h"
 
@@ -263,6 +264,102 @@ Tensor reparameterize(int64_t h, const Tensor& mean_, const Tensor& lv_, int64_t
     return out;
 }
 
+// ---- training-side free energy, forward (/root/reference/src/torchloss.py) ----
+efe_fe_params fe_params(double gamma, double beta_s, double beta_o, int64_t omega_mode, const OptT& omega, Tensor& keep, double omega_scalar,
+                        int64_t M) {
+    efe_fe_params p{};
+    p.gamma = (float)gamma; p.beta_s = (float)beta_s; p.beta_o = (float)beta_o; p.omega_mode = (int32_t)omega_mode;
+    p.omega = optp(omega, keep, "omega", M); p.omega_scalar = (float)omega_scalar;
+    TORCH_CHECK(omega_mode != EFE_OMEGA_ARRAY || p.omega, "efe: omega_mode 0 (per-row omega) needs an omega tensor of M elements");
+    return p;
+}
+float* P(Tensor& t) { return t.data_ptr<float>(); }
+
+// ActiveInferenceModel training step, train.py:104-123 (compute_loss_top / _mid / _down composed); outputs in efe_fe_out order
+std::vector<Tensor> free_energy(int64_t h, const Tensor& o0_, const Tensor& o1_, const Tensor& pi0_, const Tensor& lp_, double gamma, double beta_s,
+                                double beta_o, int64_t omega_mode, const OptT& omega, double omega_scalar, double a, double b, double cc, double d,
+                                int64_t seed, int64_t stage, int64_t row_offset, const OptT& eps) {
+    efe_ctx* c = CTX(h);
+    Tensor o0 = in(o0_, "o0"), o1 = in(o1_, "o1"), pi0 = in(pi0_, "pi0"), lp = in(lp_, "log_Ppi"), ok_, ek;
+    const Geo g = geo(c);
+    const int M = rows(o0, g.img(), "o0");
+    TORCH_CHECK(o1.numel() == (int64_t)M * g.img(), "efe: o1 must have the shape of o0");
+    TORCH_CHECK(pi0.numel() == (int64_t)M * g.A && lp.numel() == (int64_t)M * g.A, "efe: pi0 and log_Ppi must be [M, pi_dim]");
+    efe_fe_params p = fe_params(gamma, beta_s, beta_o, omega_mode, omega, ok_, omega_scalar, M);
+    p.a = (float)a; p.b = (float)b; p.c = (float)cc; p.d = (float)d;
+    auto op = o0.options();
+    const int64_t S = g.s, A = g.A;
+    std::vector<Tensor> r = {
+        at::empty({M}, op), at::empty({M}, op), at::empty({M, A}, op), at::empty({M, A}, op), at::empty({M}, op),
+        at::empty({M}, op), at::empty({M}, op), at::empty({M, S}, op), at::empty({M, S}, op), at::empty({M, S}, op), at::empty({M, S}, op),
+        at::empty({M}, op), at::empty({M}, op), at::empty({M}, op), at::empty({M, S}, op), at::empty({M}, op), at::empty({M, S}, op),
+        at::empty({M, g.C, g.R, g.R}, op), at::empty({M, S}, op), at::empty({M, S}, op), at::empty({M, S}, op), at::empty({M, S}, op)};
+    efe_fe_out out{P(r[0]), P(r[1]), P(r[2]), P(r[3]), P(r[4]), P(r[5]), P(r[6]), P(r[7]), P(r[8]), P(r[9]), P(r[10]), P(r[11]), P(r[12]),
+                   P(r[13]), P(r[14]), P(r[15]), P(r[16]), P(r[17]), P(r[18]), P(r[19]), P(r[20]), P(r[21])};
+    efe_noise nz = noise(seed, stage, 0, 0, row_offset);
+    ok(c, efe_free_energy(c, o0.data_ptr<float>(), o1.data_ptr<float>(), pi0.data_ptr<float>(), lp.data_ptr<float>(), M, &p, &nz,
+                          optp(eps, ek, "eps", (int64_t)3 * M * S), &out, stream_of(o0)));
+    return r;
+}
+
+// compute_loss_top, torchloss.py:19-26
+std::tuple<Tensor, Tensor, Tensor, Tensor> loss_top(int64_t h, const Tensor& s_, const Tensor& lp_) {
+    efe_ctx* c = CTX(h);
+    Tensor s = in(s_, "s"), lp = in(lp_, "log_Ppi");
+    const int M = rows(s, 10, "s");
+    const int A = geo(c).A;
+    TORCH_CHECK(lp.numel() == (int64_t)M * A, "efe: log_Ppi must be [M, pi_dim]");
+    auto op = s.options();
+    Tensor F = at::empty({M}, op), kl = at::empty({M}, op), anal = at::empty({M, A}, op), q = at::empty({M, A}, op);
+    efe_fe_out out{};
+    out.F_top = P(F); out.kl_pi = P(kl); out.kl_pi_anal = P(anal); out.Qpi = P(q);
+    ok(c, efe_loss_top(c, s.data_ptr<float>(), lp.data_ptr<float>(), M, &out, stream_of(s)));
+    return {F, kl, anal, q};
+}
+
+// compute_loss_mid, torchloss.py:28-36
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> loss_mid(int64_t h, const Tensor& s0_, const Tensor& pi0_, const Tensor& qm_, const Tensor& qv_,
+                                                                    int64_t omega_mode, const OptT& omega, double omega_scalar, int64_t seed,
+                                                                    int64_t stage, int64_t pass, int64_t sample, int64_t row_offset, const OptT& eps) {
+    efe_ctx* c = CTX(h);
+    Tensor s0 = in(s0_, "s0"), pi0 = in(pi0_, "Ppi_sampled"), qm = in(qm_, "qs1_mean"), qv = in(qv_, "qs1_logvar"), ok_, ek;
+    const int M = rows(s0, 10, "s0");
+    TORCH_CHECK(pi0.numel() == (int64_t)M * geo(c).A, "efe: Ppi_sampled must be [M, pi_dim]");
+    TORCH_CHECK(qm.numel() == (int64_t)M * 10 && qv.numel() == (int64_t)M * 10, "efe: qs1_mean and qs1_logvar must be [M, 10]");
+    efe_fe_params p = fe_params(0.0, 0.0, 0.0, omega_mode, omega, ok_, omega_scalar, M);
+    auto op = s0.options();
+    Tensor F = at::empty({M}, op), kl = at::empty({M}, op), anal = at::empty({M, 10}, op), ps1 = at::empty({M, 10}, op),
+           pm = at::empty({M, 10}, op), pv = at::empty({M, 10}, op);
+    efe_fe_out out{};
+    out.F_mid = P(F); out.kl_s_mid = P(kl); out.kl_s_mid_anal = P(anal); out.ps1 = P(ps1); out.ps1_mean = P(pm); out.ps1_logvar = P(pv);
+    efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    ok(c, efe_loss_mid(c, s0.data_ptr<float>(), pi0.data_ptr<float>(), qm.data_ptr<float>(), qv.data_ptr<float>(), M, &p, &nz,
+                       optp(eps, ek, "eps", (int64_t)M * 10), &out, stream_of(s0)));
+    return {F, kl, anal, ps1, pm, pv};
+}
+
+// compute_loss_down, torchloss.py:53-74
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> loss_down(
+        int64_t h, const Tensor& o1_, const Tensor& pm_, const Tensor& pv_, double gamma, double beta_s, double beta_o, int64_t omega_mode,
+        const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample, int64_t row_offset, const OptT& eps) {
+    efe_ctx* c = CTX(h);
+    Tensor o1 = in(o1_, "o1"), pm = in(pm_, "ps1_mean"), pv = in(pv_, "ps1_logvar"), ok_, ek;
+    const Geo g = geo(c);
+    const int M = rows(o1, g.img(), "o1");
+    TORCH_CHECK(pm.numel() == (int64_t)M * 10 && pv.numel() == (int64_t)M * 10, "efe: ps1_mean and ps1_logvar must be [M, 10]");
+    efe_fe_params p = fe_params(gamma, beta_s, beta_o, omega_mode, omega, ok_, omega_scalar, M);
+    auto op = o1.options();
+    Tensor F = at::empty({M}, op), nl = at::empty({M}, op), kls = at::empty({M}, op), klsa = at::empty({M, 10}, op), kln = at::empty({M}, op),
+           klna = at::empty({M, 10}, op), po1 = at::empty({M, g.C, g.R, g.R}, op), qs1 = at::empty({M, 10}, op);
+    efe_fe_out out{};
+    out.F_down = P(F); out.nlogpo1 = P(nl); out.kl_s = P(kls); out.kl_s_anal = P(klsa); out.kl_naive = P(kln); out.kl_naive_anal = P(klna);
+    out.po1 = P(po1); out.qs1 = P(qs1);
+    efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    ok(c, efe_loss_down(c, o1.data_ptr<float>(), pm.data_ptr<float>(), pv.data_ptr<float>(), M, &p, &nz, optp(eps, ek, "eps", (int64_t)M * 10),
+                        &out, stream_of(o1)));
+    return {F, nl, kls, klsa, kln, klna, po1, qs1};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -277,6 +374,10 @@ TORCH_LIBRARY(efe, m) {
     m.def("action_posterior(int ctx, Tensor sum_G, int n, float temperature) -> (Tensor P, Tensor logP)");
     m.def("check_reward(int ctx, Tensor o) -> Tensor");
     m.def("reparameterize(int ctx, Tensor mean, Tensor logvar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> Tensor");
+    m.def("free_energy(int ctx, Tensor o0, Tensor o1, Tensor pi0, Tensor log_Ppi, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, float a, float b, float c, float d, int seed, int stage, int row_offset, Tensor? eps) -> Tensor[]");
+    m.def("loss_top(int ctx, Tensor s, Tensor log_Ppi) -> (Tensor F_top, Tensor kl_pi, Tensor kl_pi_anal, Tensor Qpi)");
+    m.def("loss_mid(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> (Tensor F_mid, Tensor kl_s, Tensor kl_s_anal, Tensor ps1, Tensor ps1_mean, Tensor ps1_logvar)");
+    m.def("loss_down(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> (Tensor F_down, Tensor nlogpo1, Tensor kl_s, Tensor kl_s_anal, Tensor kl_naive, Tensor kl_naive_anal, Tensor po1, Tensor qs1)");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -291,4 +392,8 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("action_posterior", &action_posterior);
     m.impl("check_reward", &check_reward);
     m.impl("reparameterize", &reparameterize);
+    m.impl("free_energy", &free_energy);
+    m.impl("loss_top", &loss_top);
+    m.impl("loss_mid", &loss_mid);
+    m.impl("loss_down", &loss_down);
 }

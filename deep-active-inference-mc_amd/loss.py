@@ -1,0 +1,128 @@
+"""Forward free energy of one training step on the engine: mirror of /root/reference/src/torchloss.py (compute_omega, compute_kl_div_pi,
+compute_loss_top, compute_loss_mid, compute_loss_down) with the reference's names, arguments and return tuples, plus `free_energy`, the
+composition train.py:104-123 evaluates before its optimizer steps, in one engine call (efe_free_energy, csrc/loss.hip).
+
+Forward values only: no autograd graph is built (gradients, optimizers and a training loop are out of scope).  Every call dispatches
+through torch.ops.efe.* on the model's device; there is no CPU fallback.
+
+Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
+encoder, FE_T for the transition + sample, FE_DOWN for compute_loss_down's encoder + sample + decoder), one stage per call, rows keyed
+by global row (`row_offset`).  So encoder_with_sample(o0, pass_=PASS_FE_Q0), encoder(o1, pass_=PASS_FE_Q1), compute_loss_top,
+compute_loss_mid and compute_loss_down at one stage reproduce `free_energy` bit for bit.  `model.eps_source` (injected normals) is honoured.
+
+Deviations from the reference, each a defect of the shipped code ("training-side free energy"):
+  * compute_loss_down reads gamma / beta_s / beta_o from the owning ActiveInferenceModel: the reference reads them from ModelDown,
+    which has none (train.py:101), and passes 0.0 to torch.exp, which raises TypeError (exp(0) = 1 is used).
+  * compute_kl_div_pi encodes with encoder_with_sample: the reference calls a nonexistent encode_o_and_sample_s.
+  * compute_omega accepts a tensor, a numpy array or a number (train.py:118 passes numpy, which torch.exp rejects) and computes in fp32.
+  * omega may be a Python float (the evaluation block, train.py:142-143, whose torch.log rejects it): it is broadcast to every row.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib
+from .model import PASS_FE_Q0, PASS_FE_Q1, PASS_FE_T, PASS_FE_DOWN
+
+FreeEnergy = collections.namedtuple('FreeEnergy', _lib.FE_OUT_FIELDS)
+OMEGA_PARAMS = (1.0, 25.0, 5.0, 1.5)        # train.py:29-32 (var_a, var_b, var_c, var_d)
+
+
+def _f32(x):
+    return float(np.float32(float(x)))
+
+
+def compute_omega(kl_pi, a, b, c, d):
+    """torchloss.py:8-9 in fp32 -> tensor (on kl_pi's device when kl_pi is a tensor)"""
+    t = kl_pi if isinstance(kl_pi, torch.Tensor) else torch.as_tensor(np.asarray(kl_pi))
+    t = t.to(torch.float32)
+    return a * (1.0 - 1.0 / (1.0 + torch.exp(-(t - b) / c))) + d
+
+
+def _omega(e, omega, M):
+    """-> (omega_mode, per-row tensor or None, scalar): a number (or one-element value) is broadcast to every row, otherwise M values"""
+    if isinstance(omega, (int, float, np.floating, np.integer)):
+        return _lib.EFE_OMEGA_SCALAR, None, _f32(omega)
+    t = e.tensor(omega).reshape(-1)
+    if t.numel() == 1 and M != 1:
+        return _lib.EFE_OMEGA_SCALAR, None, _f32(t.item())
+    if t.numel() != M:
+        raise ValueError(f'omega has {t.numel()} elements, expected a scalar or one per row ({M})')
+    return _lib.EFE_OMEGA_ARRAY, t, 1.0
+
+
+def _eps(m, e, eps, M, pass_, sample, stage, row_offset):
+    if eps is None and m.eps_source is not None:
+        eps = m._src_eps(M, m.s_dim, pass_, sample, stage, row_offset)
+    return e.tensor(eps, (M, m.s_dim)) if eps is not None else None
+
+
+def compute_loss_top(model_top, s, log_Ppi):
+    """torchloss.py:19-26 -> (F_top, kl_div_pi, kl_div_pi_anal, Qpi)"""
+    m = model_top._owner
+    e = m._ready()
+    s = e.tensor(s, (-1, m.s_dim))
+    return tuple(e.ops.loss_top(e.h, s, e.tensor(log_Ppi, (s.shape[0], m.pi_dim))))
+
+
+def compute_kl_div_pi(model, o0, log_Ppi, *, stage=None, row_offset=None):
+    """torchloss.py:11-17 -> kl_div_pi [M]; the posterior sample comes from encoder_with_sample (pass PASS_FE_Q0)"""
+    qs0, _, _ = model.model_down.encoder_with_sample(o0, stage=stage, pass_=PASS_FE_Q0, row_offset=row_offset)
+    return compute_loss_top(model.model_top, qs0, log_Ppi)[1]
+
+
+def compute_loss_mid(model_mid, s0, Ppi_sampled, qs1_mean, qs1_logvar, omega, *, stage=None, pass_=PASS_FE_T, sample=0, eps=None,
+                     row_offset=None):
+    """torchloss.py:28-36 -> (F_mid, (kl_div_s, kl_div_s_anal), ps1, ps1_mean, ps1_logvar)"""
+    m = model_mid._owner
+    e = m._ready()
+    s0 = e.tensor(s0, (-1, m.s_dim))
+    M = s0.shape[0]
+    mode, om, sc = _omega(e, omega, M)
+    nz = m._noise(stage, pass_, sample, row_offset)
+    F, kl, anal, ps1, mean, lv = e.ops.loss_mid(e.h, s0, e.tensor(Ppi_sampled, (M, m.pi_dim)), e.tensor(qs1_mean, (M, m.s_dim)),
+                                                e.tensor(qs1_logvar, (M, m.s_dim)), mode, om, sc, m._seed64(), nz.stage, pass_, sample,
+                                                nz.row_offset, _eps(m, e, eps, M, pass_, sample, nz.stage, row_offset))
+    return F, (kl, anal), ps1, mean, lv
+
+
+def compute_loss_down(model_down, o1, ps1_mean, ps1_logvar, omega, displacement=1e-5, *, stage=None, pass_=PASS_FE_DOWN, sample=0, eps=None,
+                      row_offset=None):
+    """torchloss.py:53-74 -> (F_down, (-logpo1_s1, kl_div_s, kl_div_s_anal, kl_div_s_naive, kl_div_s_naive_anal), po1, qs1);
+    gamma / beta_s / beta_o are the owning ActiveInferenceModel's"""
+    if float(displacement) != 1e-5:
+        raise ValueError('compute_loss_down: the engine evaluates the reference displacement 1e-5 only')
+    m = model_down._owner
+    e = m._ready()
+    o1 = e.tensor(o1, (-1, m.colour_channels, m.resolution, m.resolution))
+    M = o1.shape[0]
+    mode, om, sc = _omega(e, omega, M)
+    nz = m._noise(stage, pass_, sample, row_offset)
+    F, nl, kls, klsa, kln, klna, po1, qs1 = e.ops.loss_down(
+        e.h, o1, e.tensor(ps1_mean, (M, m.s_dim)), e.tensor(ps1_logvar, (M, m.s_dim)), _f32(m.gamma), _f32(m.beta_s), _f32(m.beta_o),
+        mode, om, sc, m._seed64(), nz.stage, pass_, sample, nz.row_offset, _eps(m, e, eps, M, pass_, sample, nz.stage, row_offset))
+    return F, (nl, kls, klsa, kln, klna), po1, qs1
+
+
+def free_energy(model, o0, o1, pi0, log_Ppi, *, omega=None, omega_params=OMEGA_PARAMS, stage=None, row_offset=None, eps=None):
+    """The forward free energy of one training step (train.py:104-123) -> FreeEnergy (fields: _lib.FE_OUT_FIELDS, include/efe_engine.h
+    efe_fe_out).  omega: None = compute_omega(kl_pi, *omega_params) of this call (train.py's current_omega), a number = that value for
+    every row (the evaluation block), or M values.  eps: optional injected normals [3, M, s_dim] (FE_Q0, FE_T, FE_DOWN)."""
+    e = model._ready()
+    shp = (-1, model.colour_channels, model.resolution, model.resolution)
+    o0 = e.tensor(o0, shp)
+    M = o0.shape[0]
+    o1 = e.tensor(o1, (M,) + shp[1:])
+    if omega is None:
+        mode, om, sc = _lib.EFE_OMEGA_DERIVED, None, 1.0
+    else:
+        mode, om, sc = _omega(e, omega, M)
+    a, b, c, d = (_f32(v) for v in omega_params)
+    nz = model._noise(stage, 0, 0, row_offset)
+    if eps is None and model.eps_source is not None:
+        eps = np.stack([model._src_eps(M, model.s_dim, p, 0, nz.stage, row_offset) for p in (PASS_FE_Q0, PASS_FE_T, PASS_FE_DOWN)], 0)
+    eps_t = e.tensor(eps, (3, M, model.s_dim)) if eps is not None else None
+    outs = e.ops.free_energy(e.h, o0, o1, e.tensor(pi0, (M, model.pi_dim)), e.tensor(log_Ppi, (M, model.pi_dim)), _f32(model.gamma),
+                             _f32(model.beta_s), _f32(model.beta_o), mode, om, sc, a, b, c, d, model._seed64(), nz.stage, nz.row_offset, eps_t)
+    return FreeEnergy(*outs)

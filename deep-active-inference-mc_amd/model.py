@@ -24,6 +24,7 @@ import torch
 from . import _lib
 
 PASS_T1, PASS_D1, PASS_E1, PASS_T2, PASS_D2A, PASS_D2B, PASS_ROOT, PASS_HABIT, PASS_SIM = range(9)
+PASS_FE_Q0, PASS_FE_Q1, PASS_FE_T, PASS_FE_DOWN = range(9, 13)      # training-side free energy (loss.py, csrc/philox.h)
 
 def layer_shapes(pi_dim=4, channels=1, resolution=64):
     """state_dict tensor shapes per sub-model (reference key names, torchmodel.py:13-128).  (pi 4, 1 x 64 x 64) is the reference's

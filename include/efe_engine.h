@@ -253,6 +253,58 @@ int efe_mcts_stop(efe_ctx*, const efe_mcts_tree* tree, uint8_t* active, int32_t*
                   int32_t* n_active, void* stream);
 
 
+/* ---- training-side free energy, forward only (additive to ABI 6; /root/reference/src/torchloss.py, train.py:104-123) ----------------
+ * efe_free_energy evaluates what one training step of train.py computes before its optimizer steps, for M rows:
+ *   s0             = encoder_with_sample(o0)                                  pass PASS_FE_Q0 (9):   encoder masks + normals
+ *   F_top, kl_pi, kl_pi_anal, Qpi = compute_loss_top(s0, log_Ppi)              (habit head, no noise)
+ *   omega          = params->omega_mode: EFE_OMEGA_ARRAY (omega [M]), EFE_OMEGA_SCALAR (omega_scalar for every row), or
+ *                    EFE_OMEGA_DERIVED: compute_omega(kl_pi, a, b, c, d) of this call (train.py's current_omega; defaults 1, 25, 5, 1.5)
+ *   qs1_mean, qs1_logvar = encoder(o1)                                        pass PASS_FE_Q1 (10):  encoder masks
+ *   F_mid, kl_s_mid, kl_s_mid_anal, ps1, ps1_mean, ps1_logvar = compute_loss_mid(s0, pi0, qs1_mean, qs1_logvar, omega)
+ *                                                                              pass PASS_FE_T (11):   transition masks + normals
+ *   F_down, nlogpo1, kl_s, kl_s_anal, kl_naive, kl_naive_anal, po1, qs1 = compute_loss_down(o1, ps1_mean, ps1_logvar, omega)
+ *                                                                              pass PASS_FE_DOWN (12): encoder masks + normals, decoder masks
+ * One stage (nz->stage) per call; nz->pass / nz->sample are not read (the four passes above, sample 0).  Rows are keyed by global row
+ * nz->row_offset + r.  o0, o1: NCHW [M,C,H,W] fp32 (need not be binary); pi0 [M,pi_dim]; log_Ppi [M,pi_dim].
+ * eps: NULL or injected normals [3][M][s_dim] = the FE_Q0, FE_T and FE_DOWN draws.
+ * Every expression is the reference's in fp32 operation order (csrc/loss.hip); gamma is compared with 0.05 / 0.95 in fp32, as torch does
+ * for its fp32 gamma tensor.  The BCE image sum has a fixed reduction order, so every output is bit-identical however the rows are
+ * split over calls (with matching row_offset).  Under "mfma_bf16x3" / "mfma_f16x2" the decoder runs whatever the option selects, as in
+ * efe_decoder, and F_down follows from that image.  A generic-geometry context works the same way (C*H*W pixels; parity unpinned). */
+typedef enum { EFE_OMEGA_ARRAY = 0, EFE_OMEGA_SCALAR = 1, EFE_OMEGA_DERIVED = 2 } efe_omega_mode;
+typedef struct efe_fe_params {
+    float gamma, beta_s, beta_o;      /* ModelDown.gamma / beta_s / beta_o (the reference keeps them on ActiveInferenceModel, train.py:101) */
+    int32_t omega_mode;               /* efe_omega_mode */
+    const float* omega;               /* EFE_OMEGA_ARRAY: device [M] */
+    float omega_scalar;               /* EFE_OMEGA_SCALAR */
+    float a, b, c, d;                 /* EFE_OMEGA_DERIVED: compute_omega's parameters (train.py:29-32) */
+} efe_fe_params;
+/* outputs (device pointers; NULL = not wanted, except F_top / F_mid / F_down).  [M] unless stated; A = pi_dim, s = s_dim, image NCHW. */
+typedef struct efe_fe_out {
+    float* F_top; float* kl_pi; float* kl_pi_anal /*[M,A]*/; float* Qpi /*[M,A]*/;
+    float* omega;
+    float* F_mid; float* kl_s_mid; float* kl_s_mid_anal /*[M,s]*/; float* ps1 /*[M,s]*/; float* ps1_mean /*[M,s]*/; float* ps1_logvar /*[M,s]*/;
+    float* F_down; float* nlogpo1 /* -sum log P(o1|s1) */; float* kl_s; float* kl_s_anal /*[M,s]*/; float* kl_naive; float* kl_naive_anal /*[M,s]*/;
+    float* po1 /*[M,C,H,W]*/; float* qs1 /*[M,s]*/;
+    float* s0 /*[M,s]*/; float* qs1_mean /*[M,s]*/; float* qs1_logvar /*[M,s]*/;
+} efe_fe_out;
+int efe_free_energy(efe_ctx*, const float* o0, const float* o1, const float* pi0, const float* log_Ppi, int M, const efe_fe_params* params,
+                    const efe_noise* nz, const float* eps, efe_fe_out* out, void* stream);
+/* The three reference functions one by one, on the same kernels; noise follows the network-level convention (nz->pass / sample / stage /
+ * row_offset key every mask and normal of the call), so loss_top(encoder_with_sample(o0, PASS_FE_Q0)), loss_mid(PASS_FE_T) and
+ * loss_down(PASS_FE_DOWN) reproduce efe_free_energy bit for bit.  Only the outputs each function returns are read from `out`.
+ *   efe_loss_top  : compute_loss_top(s [M,s], log_Ppi)                 -> F_top, kl_pi, kl_pi_anal, Qpi (no noise, nz unused)
+ *   efe_loss_mid  : compute_loss_mid(s0, pi0, qs1_mean, qs1_logvar, omega) -> F_mid, kl_s_mid, kl_s_mid_anal, ps1, ps1_mean, ps1_logvar;
+ *                   eps NULL or [M,s]
+ *   efe_loss_down : compute_loss_down(o1, ps1_mean, ps1_logvar, omega)  -> F_down, nlogpo1, kl_s, kl_s_anal, kl_naive, kl_naive_anal,
+ *                   po1, qs1 (+ qs1_mean / qs1_logvar of its own encoder pass); eps NULL or [M,s]
+ * omega for loss_mid / loss_down: EFE_OMEGA_ARRAY or EFE_OMEGA_SCALAR (EFE_OMEGA_DERIVED needs kl_pi: efe_free_energy only). */
+int efe_loss_top(efe_ctx*, const float* s, const float* log_Ppi, int M, efe_fe_out* out, void* stream);
+int efe_loss_mid(efe_ctx*, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M,
+                 const efe_fe_params* params, const efe_noise* nz, const float* eps, efe_fe_out* out, void* stream);
+int efe_loss_down(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, const float* eps, efe_fe_out* out, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
