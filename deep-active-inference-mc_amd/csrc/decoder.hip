@@ -5,7 +5,7 @@
 // One workgroup (4 waves) owns one decoder image; activations live in LDS between layers:
 //
 //   k_dec_a :  x4[16x16x64] --LDS--> ConvT(64,64,s1)+ReLU (Winograd F(2x2,3x3)) --LDS (in place)--> ConvT(64,64,s2)+ReLU --> y2[32x32x64] (HBM)
-//   k_dec_b4:  y2 strips --LDS--> ConvT(64,32,s2)+ReLU (registers) --MFMA--> tap values of the 32->1 conv, horizontal sums in registers
+//   k_dec_b4:  y2 strips --LDS--> ConvT(64,32,s2)+ReLU (F(2,2), registers) --MFMA--> tap values of the 32->1 conv, horizontal sums in registers
 //              --LDS ring of H planes--> vertical gather + sigmoid + entropy / reward reduction (+ optional image store)
 //   k_dec_a_s / k_dec_b4<4>: the same kernels with an image over eight / four workgroups, for launches of <= 128 images
 //
@@ -14,6 +14,7 @@
 // fragment address is pixel base + an immediate (k_fc4's batch tile alone is still XOR-swizzled).  Weights are read as pre-packed A
 // fragments straight from L2 (1 KiB coalesced per wave-load, shared by all workgroups).  fp32 MFMA (v_mfma_f32_32x32x2_f32 and the
 // 4x4x1 16-block form): exact fp32 numerics.
+#include <utility>
 #include "mfma_pipe.h"
 
 namespace efe {
@@ -401,52 +402,93 @@ void launch_dec_a(const DecAArgs& a, hipStream_t st) {
 
 // ---------------------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------------------
-// k_dec_b4: the same layer pair, INPUT-STATIONARY.  One wave owns one input row of the strip (32 positions) and ALL FOUR output
-// parities of it.  The nine (kh, kw) taps of the stride-2 transposed conv read only four shifted views of the input,
-//     shift (0,0): taps of parities (0,0) (0,1) (1,0) (1,1)      shift (0,+1): parities (0,1) (1,1)
-//     shift (+1,0): parities (1,0) (1,1)                          shift (+1,+1): parity (1,1)
-// so a B fragment (LDS) is read once per shift and chunk and feeds up to four INDEPENDENT accumulator chains (4 / 2 / 2 / 1
-// weight fragments): 9 tap-tiles per wave for every wave (the parity-pair split of k_dec_b gives 5 and 4), 4 LDS reads per chunk
-// instead of 9, and back-to-back MFMAs never wait on their own accumulator.  SR = 4 input rows per strip, 4 waves.
+// ConvT3 (ConvTranspose2d(64, 32, 3, s2, p1, op1)) by per-parity minimal filtering F(2, 2).  Along one dimension, with taps g0, g1, g2
+// (oh = 2 ih - 1 + kh) and x[32] = 0, output 2m = x[m] g1 and 2m + 1 = x[m] g2 + x[m + 1] g0.  For an input pair block u
+// (x0 = x[2u], x1 = x[2u + 1], x2 = x[2u + 2]) the views d0 = x0 - x1, d1 = x1, d2 = x2 - x1 give the four outputs 4u .. 4u + 3 from
+// five products instead of six:
+//     P1 = d0 g1 -> 0    P2 = d1 g1 -> 0, 2    P3 = d0 g2 -> 1    P4 = d1 (g0 + g2) -> 1, 3    P5 = d2 g0 -> 3
+// In 2D (the outer product of this table with itself) a 2 x 2 input block needs 25 products instead of 36: 9 views d_a (x) d_b and 16
+// weight matrices U = w_r (x) w_c, w in {g1, g2, g0 + g2, g0}, formed in fp64 at commit time and rounded once (engine.hip).  The 9
+// products with one output in both dimensions chain straight into that output; the other 16 run in a short-lived accumulator that is
+// then added into its 2 or 4 outputs.  (The 1D table f22_* is in kernels.h: engine.hip forms the weights from it.)
 //
-// The 32 -> 1 conv: tap planes by v_mfma_f32_16x16x1_4b on the accumulators (as in k_dec_b), with the taps placed in A rows
-// {0-2, 4-6, 8-10} so that the 16-lane group kh of a wave holds the three kw taps of every pixel.  The horizontal part of the 3 x 3
-// sum is then formed IN REGISTERS (the two column parities of a pixel are the same lane of two accumulators, its left / right
-// neighbours one DPP row shift away):   H[kh][r][ow] = sum_kw T[kh,kw][r][ow + 1 - kw],
-// and only the three H planes of a source row go through LDS (two ds_write_b64 per parity row instead of twenty ds_write_b32; the
-// gather reads 3 values per pixel instead of 9).  The plane ring shrinks from 23.7 to 7.7 KiB: 49 KiB of LDS per workgroup.
-// ---------------------------------------------------------------------------------------------------------
-// Measured alternatives of this kernel (profiles/r2_decb4_variants.txt): persistent over images with a ticket queue (prologue 28k ->
-// 0 cycles per image) and / or three workgroups per CU (166 VGPRs without spills after laundering the lane index per strip, tap
-// weights re-read from LDS, channel halves merged with a cross-lane add: 50 KiB LDS) all land on the same 5.96-5.98 ms per 19200
-// images; the per-strip index laundering alone costs 2-3 % at two waves.  The shader clock is at 2.38 GHz in steady state (it
-// ramps from 2.05 GHz over the first four launches after idle): the kernel is not clock- or power-limited.
-// Deferred gather: the gather of a strip (sigmoid + entropy / reward terms of its 2 SR output rows: ~130 VALU instructions per wave) is not done
-// between the strip's two barriers -- where it is pure non-MFMA wave time -- but DURING THE NEXT STRIP'S CONTRACTION, in pieces
-// placed between the MFMA groups of the unrolled channel-block steps (a wave's VALU instructions issue in the shadow of its own
-// 64-cycle MFMAs).  The H-plane ring holds 4 SR + 2 rows (27.6 KiB) so that the next strip's planes do not overwrite rows still
-// being gathered; the next strip's input is requested behind the contraction's last weight-fragment request (the tap phase covers
-// its latency instead of the gather); the images of the deferred rows are stored after the strip barrier.  Per-thread summation
-// order is the same as when every strip is gathered between its own barriers (0.812 of the fp32 MFMA peak in that form, 0.843 in this one).
+// compile-time loop: f(std::integral_constant<int, 0>{}) .. f(std::integral_constant<int, N - 1>{})
+template <class F, int... I> __device__ __forceinline__ void static_for_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_(f, std::make_integer_sequence<int, N>{}); }
+
+// The schedule of k_dec_b4: six groups of products that share their views (every B fragment read feeds 4 or 5 independent chains):
+//   G0 V(0,0): (P1|P3) x (P1|P3)  direct      G1 V(0,1): (P1|P3) x (P2|P4)      G2 V(1,0): (P2|P4) x (P1|P3)      G3 V(1,1): (P2|P4) x (P2|P4)
+//   G4 V(1,2), V(2,1), V(2,2): (P2|P4) x P5, P5 x (P2|P4), P5 x P5 (direct)      G5 V(0,2), V(2,0): (P1|P3) x P5, P5 x (P1|P3)  direct
+// w3_prod(G, c) = 5 pr + pc of chain c of group G (rows x columns)
+__host__ __device__ constexpr int w3_nch(int G) { return G == 4 ? 5 : 4; }
+__host__ __device__ constexpr int w3_prod(int G, int c) {
+    return G < 4 ? 5 * ((G >> 1) + 2 * (c >> 1)) + (G & 1) + 2 * (c & 1)
+         : G == 4 ? (c < 2 ? 5 * (1 + 2 * c) + 4 : c < 4 ? 20 + 1 + 2 * (c - 2) : 24)
+                  : (c < 2 ? 5 * (2 * c) + 4 : 20 + 2 * (c - 2));
+}
+__host__ __device__ constexpr bool w3_direct(int pp) { return f22_o1(pp / 5) < 0 && f22_o1(pp % 5) < 0; }
+__host__ __device__ constexpr int w3_view(int pp) { return 3 * f22_view(pp / 5) + f22_view(pp % 5); }
+__host__ __device__ constexpr int w3_mat(int pp) { return 4 * f22_wt(pp / 5) + f22_wt(pp % 5); }
+__host__ __device__ constexpr bool w3_hits(int pp, int o) {          // product pp feeds output o = 4 orow + ocol of the block
+    const int r = o >> 2, c = o & 3, pr = pp / 5, pc = pp % 5;
+    return (r == f22_o0(pr) || r == f22_o1(pr)) && (c == f22_o0(pc) || c == f22_o1(pc));
+}
+// output o already holds a value when chain c of group G reaches it (a group's direct chains run before its temporaries are added,
+// those in chain order): otherwise the chain starts from the bias (direct: the C operand of its first MFMA; temporary: bias + M)
+__host__ __device__ constexpr bool w3_seen(int G, int c, int o) {
+    for (int g = 0; g < G; ++g)
+        for (int k = 0; k < w3_nch(g); ++k) if (w3_hits(w3_prod(g, k), o)) return true;
+    if (!w3_direct(w3_prod(G, c)))
+        for (int k = 0; k < w3_nch(G); ++k)
+            if ((w3_direct(w3_prod(G, k)) || k < c) && w3_hits(w3_prod(G, k), o)) return true;
+    return false;
+}
+__host__ __device__ constexpr bool w3_uses_view(int G, int vi) {
+    for (int k = 0; k < w3_nch(G); ++k) if (w3_view(w3_prod(G, k)) == vi) return true;
+    return false;
+}
+__host__ __device__ constexpr bool f22_in(int a, int r) { return a == 0 ? r <= 1 : (a == 1 ? r == 1 : r >= 1); }   // view a reads x_r
+__host__ __device__ constexpr bool w3_reads(int G, int r, int c) {   // input pixel (r, c) of the 3 x 3 block neighbourhood
+    for (int vi = 0; vi < 9; ++vi) if (w3_uses_view(G, vi) && f22_in(vi / 3, r) && f22_in(vi % 3, c)) return true;
+    return false;
+}
+
+// k_dec_b4: ConvT3 + ReLU + ConvT4 + sigmoid + the per-image sums.  One workgroup (4 waves) per image walks 8 strips of SR = 4 input
+// rows (+ 1 halo row) staged in LDS.  Wave w owns block row u = w >> 1 of the strip (input rows 2u .. 2u + 2, y3 rows 4u .. 4u + 3) and
+// output channels 16 hf .. + 15, hf = w & 1, on v_mfma_f32_16x16x4_f32: M = 16 channels, N = the 16 block columns (lane v = lane & 15),
+// K = 4 channels per instruction (lane group g = lane >> 4 supplies channel quad 4 kc + g of chunk kc; one ds_read_b128 feeds 4 MFMAs).
+// 25 products x 16 instructions = 400 x 32 cycles per strip and wave (the direct form on 32x32x2: 288 x 64).  The accumulators: 16 output
+// positions (orow, ocol) of the block x f32x4 (channels 16 hf + 4 g + r) = 64 VGPRs.
+// Staged pixels are [row][33 columns][17 float4 slots] (column 32 = zeros, the x2 of the last block column): a view's lanes read 16 pixels
+// at a 2-pixel stride, lane groups g and g + 1 (one ds_read_b128 lane group) quads of odd distance, so the 16 lanes of a lane group hit 16
+// distinct bank quads (even pixel offsets for one, odd for the other).
+// The 32 -> 1 conv: per output position, 4 v_mfma_f32_16x16x4_f32 on the ReLU'd accumulators with A rows = taps 4 kh + kw (9 of 16 used):
+// lane group kh then holds the three kw taps of its block column's four pixels, and the horizontal part of the 3 x 3 sum,
+//     H[kh][r][ow] = sum_kw T[kh,kw][r][ow + 1 - kw],
+// is formed in registers (the neighbours across a block edge are one DPP row shift away; the shifts' zeros are the image edges).  Each
+// channel half writes its H planes (one ds_write_b128 per lane and y3 row) to an LDS ring; the gather adds the halves.
+// Deferred gather: the gather of a strip (sigmoid + entropy / reward terms of its 2 SR output rows) runs DURING THE NEXT STRIP'S
+// CONTRACTION, in pieces between its MFMA groups (a wave's VALU instructions issue in the shadow of the other wave's MFMAs).  The H-plane
+// ring holds 4 SR + 2 rows so that the next strip's planes do not overwrite rows still being gathered; the next strip's input is requested
+// behind the contraction's last weight-fragment request; the images of the deferred rows are stored after the strip barrier.
 template <int PARTS>        // 1 = one workgroup per image, 4 = four (small launches)
 __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     constexpr int SR = 4, NW = 4, NTHR = 256;
-    constexpr int DB_ZERO = (SR + 1) * 32;
-    // float4 slots per input pixel: 16 channel quads + 1 pad.  Padded, not XOR-swizzled: 16 consecutive pixels still cover the 16 bank
-    // quads (17 j mod 16 = j), and a fragment address is (pixel base + h) + a constant chunk offset -- an immediate of the ds_read, where
-    // the swizzle cost the contraction an XOR / OR and an add per chunk (VALU work beside the other wave's MFMA stream)
-    constexpr int DB_PS = 17;
-    constexpr int DB_IN_F4 = (DB_ZERO + 1) * DB_PS;
+    constexpr int DB_RP = 33;                         // staged pixels per row: 32 columns + a zero column
+    constexpr int DB_PS = 17;                         // float4 slots per pixel: 16 channel quads + 1 pad
+    constexpr int DB_IN_F4 = (SR + 1) * DB_RP * DB_PS;
     constexpr int DB_YROWS = 4 * SR + 2;
     constexpr int NPF = (SR + 1) * 512 / NTHR;        // 10 float4s of the input strip per thread
     constexpr int NS = 32 / SR;
+    constexpr int NST = 24;                           // contraction steps: 6 groups x 4 chunks of 16 channels
     extern __shared__ __attribute__((aligned(16))) float4 sm[];
-    float* sH = reinterpret_cast<float*>(sm + DB_IN_F4);       // [ring row][kh][64 output columns]
+    float* sH = reinterpret_cast<float*>(sm + DB_IN_F4);       // [ring row][channel half][kh][64 output columns]
     __shared__ float4 sb3[8];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, h = lane >> 5;
+    const int g = lane >> 4, v = lane & 15;
+    const int u = w >> 1, hf = w & 1;
     // Small launches (a.parts == 4: <= 128 images, the one-episode planner's expansions and simulations) split an image over four
     // workgroups: quarter k owns the output rows gathered from strips 2k and 2k + 1 (their H planes need the last y3 row pair of strip
     // 2k - 1, so a quarter contracts that strip again as a halo) -- 3 of the 8 strips of latency instead of 8.  The per-image sum is
@@ -461,10 +503,10 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     const int s_hi = parts == 1 ? NS : 2 * qtr + 2;
 
     const int mg = a.m0 + img;
-    const int g = mg / a.rows_per_group;
-    const int r = mg - g * a.rows_per_group;
+    const int gi = mg / a.rows_per_group;
+    const int r = mg - gi * a.rows_per_group;
     int gt, gp, gs;
-    group_decode(a.gm, g, gt, gp, gs);
+    group_decode(a.gm, gi, gt, gp, gs);
     const int mode = (gp == 0 && a.reward0) ? 1 : 0;
     const int slot = (gp == 0 && a.store0) ? gt * a.gm.S + gs : -1;
     float* po = (slot >= 0) ? a.po + ((size_t)slot * a.rows_per_group + r) * 4096 : nullptr;
@@ -472,23 +514,20 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     __shared__ float sq[4 * NTHR];       // [quarter][thread]: the threads' partial sums of a quarter, reduced once per image
     __shared__ float sQ[4];
     if (tid < 8) sb3[tid] = reinterpret_cast<const float4*>(a.b3)[tid];
-    // 16-block 4x4x1 form of the tap contraction: block = 4 consecutive lanes = 4 pixels of one channel half, A row i = lane & 3 = kw,
-    // one instruction per (kh, accumulator register): 3 x 16 A values per lane, 12 tap rows (9 used) instead of 16.  The 48 values depend
-    // on (lane & 3, h) only: they live in an LDS table of 8 patterns and are re-read (12 broadcast ds_read_b128) in front of every
-    // strip's tap phase instead of occupying 48 VGPRs through the contraction.
-    __shared__ float4 sW4[8 * 12];
-    if (tid < 96) {
-        const int pat = tid / 12, i4 = tid - pat * 12;           // pattern = h * 4 + kw, float4 i4 = (kh, g4)
-        const int kw = pat & 3, hh = pat >> 2, kh = i4 >> 2, g4 = i4 & 3;
-        sW4[tid] = kw < 3 ? reinterpret_cast<const float4*>(a.w4 + (3 * kh + kw) * 32)[2 * g4 + hh] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < (SR + 1) * 16) sm[((tid >> 4) * DB_RP + 32) * DB_PS + (tid & 15)] = make_float4(0.f, 0.f, 0.f, 0.f);      // the zero column
+    // A operand of the 32 -> 1 conv: lane (tap row i = lane & 15 = 4 kh + kw, K row g) holds w4[kh][kw][16 hf + 4 g + rr] in w4a[rr]
+    f32x4 w4a;
+    {
+        const int kh = v >> 2, kw = v & 3;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) w4a[rr] = (kh < 3 && kw < 3) ? a.w4[(3 * kh + kw) * 32 + 16 * hf + 4 * g + rr] : 0.f;
     }
-    const float4* w4p = sW4 + (h * 4 + (lane & 3)) * 12;
-    if (tid < 16) sm[DB_ZERO * DB_PS + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
 
     const float4* X = reinterpret_cast<const float4*>(a.y2) + (size_t)img * (32 * 32 * 16);
-    const float4* W3 = reinterpret_cast<const float4*>(a.w3);
-    const __amdgpu_buffer_rsrc_t wr = wrsrc(W3);
+    // packed U fragments [16 matrices][2 channel halves][4 chunks][64 lanes] (engine.hip): the channel half is folded into the base
+    const __amdgpu_buffer_rsrc_t wr = wrsrc(a.w3 + (size_t)hf * 4 * 64 * 4);
     const unsigned ln = (unsigned)lane * 16u;
+    auto wf = [&](int m, int kc) -> f32x4 { return __builtin_bit_cast(f32x4, wfrag(wr, ln, (size_t)(m * 8 + kc) * 64)); };
     const float D1 = 1.00001f, D0 = 0.00001f;
     float part = 0.f;
     f32x4 pf[NPF];
@@ -498,14 +537,16 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
 #pragma unroll
     for (int it = 0; it < NPF; ++it) { const int idx = it * NTHR + tid; pf[it] = Xv[y2_at(min(SR * s_lo + (idx >> 9), 31), idx)]; }
 
-    // the four shifted B views of this wave's row: LDS float4 base and swizzle key
-    const int spA = w * 32 + j;                                   // (row w,     col j)
-    const int spB = (j < 31) ? w * 32 + j + 1 : DB_ZERO;          // (row w,     col j + 1)   (column 32 does not exist)
-    const int spC = (w + 1) * 32 + j;                             // (row w + 1, col j)
-    const int spD = (j < 31) ? (w + 1) * 32 + j + 1 : DB_ZERO;    // (row w + 1, col j + 1)
-    // packed-weight tap indices kh * 3 + kw: parity p = 2 * ph + pw
-    //   shift A: p0 (1,1)=4  p1 (1,2)=5  p2 (2,1)=7  p3 (2,2)=8 | shift B: p1 (1,0)=3  p3 (2,0)=6 | shift C: p2 (0,1)=1  p3 (0,2)=2 | shift D: p3 (0,0)=0
-    auto wf = [&](int tap, int kc) -> float4 { return wfrag(wr, ln, (size_t)(tap * 8 + kc) * 64); };
+    // this lane's block neighbourhood: pixel (2u + i, 2v + jj), quad 4 kc + g at xb + (33 i + jj) * DB_PS + 4 kc (all immediates)
+    const int xb = (2 * u * DB_RP + 2 * v) * DB_PS + g;
+    auto px = [&](int i, int jj, int kc) -> f32x4 { return smv[xb + (i * DB_RP + jj) * DB_PS + 4 * kc]; };
+    // view (a, b) of the raw neighbourhood x[i][jj]: the columns first (c_b(i) = x[i][0] - x[i][1] | x[i][1] | x[i][2] - x[i][1]),
+    // then the rows in the same form
+    auto view = [&](const f32x4 (&x)[9], int vi) -> f32x4 {
+        const int va = vi / 3, vb = vi % 3;
+        auto cv = [&](int i) -> f32x4 { return vb == 0 ? x[3 * i] - x[3 * i + 1] : (vb == 1 ? x[3 * i + 1] : x[3 * i + 2] - x[3 * i + 1]); };
+        return va == 0 ? cv(0) - cv(1) : (va == 1 ? cv(1) : cv(2) - cv(1));
+    };
 
     // ---- gather of output row oh (lane = column): out = b4 + H[0][oh + 1] + H[1][oh] + H[2][oh - 1] (source row r contributes to
     // oh = r - 1 + kh), the two channel halves added here; split into pieces for the deferred form
@@ -526,16 +567,16 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
         }
     };
     auto g_sig = [&](int oh, int q) {
-        float v = a.b4;
+        float val = a.b4;
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
             const int tr = oh + 1 - kh;
-            v += (tr >= 0 && tr <= 63) ? gh[q][2 * kh] + gh[q][2 * kh + 1] : 0.f;
+            val += (tr >= 0 && tr <= 63) ? gh[q][2 * kh] + gh[q][2 * kh + 1] : 0.f;
         }
         // hardware exp2 / rcp / log2 (v_exp_f32, v_rcp_f32, v_log_f32: 1 ulp each) instead of the libm expansions: ~14 instead of ~60 VALU
         // instructions per pixel, each of which costs ~19 cycles of wave time beside the other wave's MFMA stream; the image stays within
         // 3e-7 of the libm form, the 4096-pixel sums within their own fp32 rounding (tests/test_gpu_parity.py tolerances unchanged)
-        gpr[q] = hw_sigmoid(v);
+        gpr[q] = hw_sigmoid(val);
     };
     auto g_term = [&](int oh, int q) {          // branch-free: both forms are evaluated (the reward form is four FMAs), rows above the image add zero
         // (the products are contracted EXPLICITLY: this lambda is inlined at several places -- deferred pieces, strip epilogues, both
@@ -568,118 +609,100 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     auto fold = [&](int k) { sq[k * NTHR + tid] = part; part = 0.f; };
     int hb = 0, hbp = 0;                                   // H-ring slots of y3 rows 2 SR s (this strip's first) and 2 SR (s - 1)
     for (int s = s_lo; s < s_hi; ++s) {
-        const int tl = tid;
+        // per-strip laundering of the thread index: stops hipcc hoisting the ~15 staging / prefetch addresses out of the strip loop
+        // (VGPR spills behind the 64 accumulators)
+        int tl = tid; asm volatile("" : "+v"(tl));
         const bool gq = parts == 1 ? true : s == 2 * qtr + 1;   // (uniform) the previous strip's rows are this workgroup's to gather
-        const int oh0 = 2 * SR * (s - 1) - 1 + w, oh1 = oh0 + NW;         // this wave's two output rows of the previous strip        // (laundering the index per strip frees ~20 VGPRs -- 168, three waves per SIMD, 4 spills -- for no gain: 0.814 vs 0.812)
+        const int oh0 = 2 * SR * (s - 1) - 1 + w, oh1 = oh0 + NW;         // this wave's two output rows of the previous strip
+        // stage the strip: y2 is [row parity][8 channel groups][16 x 16 positions][2 quads], i.e. pixel column 2 (wi >> 1) + (seg >> 3)
 #pragma unroll
         for (int it = 0; it < NPF; ++it) {
             const int idx = it * NTHR + tl;
             const int rl = idx >> 9, seg = (idx & 511) >> 5, wi = idx & 31;
             const int ix = 2 * (wi >> 1) + (seg >> 3), c4 = 2 * (seg & 7) + (wi & 1);
-            smv[(rl * 32 + ix) * DB_PS + c4] = (SR * s + rl < 32) ? pf[it] : (f32x4)(0.f);
+            smv[(rl * DB_RP + ix) * DB_PS + c4] = (SR * s + rl < 32) ? pf[it] : (f32x4)(0.f);
         }
-        float4 a0 = wf(4, 0), a1 = wf(5, 0), a2 = wf(7, 0), a3 = wf(8, 0);      // the strip's first weight fragments: in flight across the barrier
+        f32x4 aq[5];                                       // the strip's first weight fragments: in flight across the barrier
+#pragma unroll
+        for (int c = 0; c < w3_nch(0); ++c) aq[c] = wf(w3_mat(w3_prod(0, c)), 0);
         __syncthreads();
 
-        // the accumulators start at the layer-3 bias (register e holds channel (e & 3) + 8 (e >> 2) + 4 h): the bias vector is the C operand
-        // of each chain's FIRST MFMA -- 16 short-lived registers instead of 64 moves into the four accumulator tiles
-        f32x16 acc[4], bias16;
+        // the accumulators start at the layer-3 bias (lane: channels 16 hf + 4 g + 0..3): the C operand of an output's first MFMA, or
+        // the first addend of its first temporary
+        const f32x4 bias4 = __builtin_bit_cast(f32x4, sb3[4 * hf + g]);
+        const f32x4 zero4 = {};
+        f32x4 acc[16], tq[5];
+        // ---- contraction, software-pipelined one step ahead: step ST = (group ST >> 2, chunk ST & 3), every index a compile-time constant
+        f32x4 xr[9];
+        static_for<9>([&](auto i) { if constexpr (w3_reads(0, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, 0); });
+        static_for<NST>([&](auto stc) {
+            constexpr int ST = decltype(stc)::value, G = ST >> 2, KC = ST & 3, GN = (ST + 1) >> 2, KN = (ST + 1) & 3;
+            f32x4 vw[9], ac[5];
+            static_for<9>([&](auto vi) { if constexpr (w3_uses_view(G, vi)) vw[vi] = view(xr, vi); });
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 bb = sb3[2 * g4 + h];
-            bias16[4 * g4] = bb.x; bias16[4 * g4 + 1] = bb.y; bias16[4 * g4 + 2] = bb.z; bias16[4 * g4 + 3] = bb.w;
-        }
-        // ---- contraction, software-pipelined one chunk ahead: shift A (4 chains), shift B (2), shifts C + D fused (2 + 1, so the
-        // single-chain shift never runs alone).  The first weight fragments were requested before the staging barrier.
-        {
-            float4 b = sm[spA * DB_PS + h];
-#pragma unroll
-            for (int kc = 0; kc < 8; ++kc) {
-                const float4 c0 = a0, c1 = a1, c2 = a2, c3 = a3, cb = b;
-                if (kc < 7) {
-                    a0 = wf(4, kc + 1); a1 = wf(5, kc + 1); a2 = wf(7, kc + 1); a3 = wf(8, kc + 1);
-                    b = sm[spA * DB_PS + 2 * (kc + 1) + h];
-                } else {
-                    a0 = wf(3, 0); a1 = wf(6, 0);
-                    b = sm[spB * DB_PS + h];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (kc == 0) { MFMA4I(acc[0], bias16, c0, cb) MFMA4I(acc[1], bias16, c1, cb) MFMA4I(acc[2], bias16, c2, cb) MFMA4I(acc[3], bias16, c3, cb) }
-                else { MFMA4(acc[0], c0, cb) MFMA4(acc[1], c1, cb) MFMA4(acc[2], c2, cb) MFMA4(acc[3], c3, cb) }
-                // the previous strip's gather, a piece per channel-block step
-                if (gq) {
-                    if (kc == 0) { g_load(oh0, 0, 2 * SR * (s - 1), hbp); g_load(oh1, 1, 2 * SR * (s - 1), hbp); }
-                    if (kc == 2) g_sig(oh0, 0);
-                    if (kc == 4) g_term(oh0, 0);
-                    if (kc == 6) g_sig(oh1, 1);
-                }
+            for (int c = 0; c < 5; ++c) ac[c] = aq[c];
+            if constexpr (ST + 1 < NST) {
+                static_for<w3_nch(GN)>([&](auto c) { aq[c] = wf(w3_mat(w3_prod(GN, c)), KN); });
+                static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
             }
-            float4 bd;
+            __builtin_amdgcn_sched_barrier(0);         // keep the prefetch loads AHEAD of this step's MFMAs
 #pragma unroll
-            for (int kc = 0; kc < 8; ++kc) {
-                const float4 c0 = a0, c1 = a1, cb = b;
-                if (kc < 7) {
-                    a0 = wf(3, kc + 1); a1 = wf(6, kc + 1);
-                    b = sm[spB * DB_PS + 2 * (kc + 1) + h];
-                } else {
-                    a0 = wf(1, 0); a1 = wf(2, 0); a2 = wf(0, 0);
-                    b = sm[spC * DB_PS + h];
-                    bd = sm[spD * DB_PS + h];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                MFMA4(acc[1], c0, cb) MFMA4(acc[3], c1, cb)
-                if (kc == 1 && gq) g_term(oh1, 1);
+            for (int e = 0; e < 4; ++e)
+                static_for<w3_nch(G)>([&](auto c) {
+                    constexpr int PP = w3_prod(G, c);
+                    const float b = vw[w3_view(PP)][e], av = ac[c][e];
+                    if constexpr (w3_direct(PP)) {
+                        constexpr int O = 4 * f22_o0(PP / 5) + f22_o0(PP % 5);
+                        constexpr bool FIRST = KC == 0 && !w3_seen(G, c, O);
+                        acc[O] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (FIRST && e == 0) ? bias4 : acc[O], 0, 0, 0);
+                    } else {
+                        tq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (KC == 0 && e == 0) ? zero4 : tq[c], 0, 0, 0);
+                    }
+                });
+            if constexpr (KC == 3)                         // the group's temporaries into their outputs, in chain order
+                static_for<w3_nch(G)>([&](auto c) {
+                    constexpr int PP = w3_prod(G, c);
+                    if constexpr (!w3_direct(PP))
+                        static_for<16>([&](auto o) {
+                            if constexpr (w3_hits(PP, o)) {
+                                if constexpr (w3_seen(G, c, o)) acc[o] = acc[o] + tq[c];
+                                else acc[o] = bias4 + tq[c];
+                            }
+                        });
+                });
+            // the previous strip's gather, a piece per step
+            if (gq) {
+                if constexpr (ST == 0) { g_load(oh0, 0, 2 * SR * (s - 1), hbp); g_load(oh1, 1, 2 * SR * (s - 1), hbp); }
+                if constexpr (ST == 2) g_sig(oh0, 0);
+                if constexpr (ST == 5) g_term(oh0, 0);
+                if constexpr (ST == 8) g_sig(oh1, 1);
+                if constexpr (ST == 11) g_term(oh1, 1);
             }
+        });
+        // ---- ReLU, then the 32 -> 1 conv as tap planes (4 v_mfma_f32_16x16x4_f32 per output position, the four columns' chains
+        // interleaved) and the horizontal presums of this channel half, one y3 row at a time
+        prefetch((s < NS - 1) ? s + 1 : NS - 1, tl);     // the next strip's input, behind this strip's last weight-fragment request
 #pragma unroll
-            for (int kc = 0; kc < 8; ++kc) {
-                const float4 c0 = a0, c1 = a1, c2 = a2, cb = b, cd = bd;
-                if (kc < 7) {
-                    a0 = wf(1, kc + 1); a1 = wf(2, kc + 1); a2 = wf(0, kc + 1);
-                    b = sm[spC * DB_PS + 2 * (kc + 1) + h];
-                    bd = sm[spD * DB_PS + 2 * (kc + 1) + h];
-                }
-                if (kc == 6) prefetch((s < NS - 1) ? s + 1 : NS - 1, tl);       // the next strip's input, behind this strip's last weight-fragment request
-                __builtin_amdgcn_sched_barrier(0);
-                MFMA4(acc[3], c1, cb) MFMA4(acc[2], c0, cb) MFMA4(acc[3], c2, cd)
-            }
-        }
-        // ---- ReLU, then the 32 -> 1 conv as tap planes: 16 x v_mfma_f32_16x16x1_4b per parity, the four parities' chains interleaved
-        float w4g[3][16];
+        for (int orow = 0; orow < 4; ++orow) {
+            f32x4 T[4];
 #pragma unroll
-        for (int i4 = 0; i4 < 12; ++i4) {
-            const float4 q = w4p[i4];
-            w4g[i4 >> 2][4 * (i4 & 3)] = q.x; w4g[i4 >> 2][4 * (i4 & 3) + 1] = q.y; w4g[i4 >> 2][4 * (i4 & 3) + 2] = q.z; w4g[i4 >> 2][4 * (i4 & 3) + 3] = q.w;
-        }
+            for (int oc = 0; oc < 4; ++oc)
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-            f32x4 Tq[2][3];                                  // [column parity][kh]: registers kw = 0..2 (3 = padding) of this lane's pixel and channel half
+                for (int e = 0; e < 4; ++e) acc[4 * orow + oc][e] = relu_bits(acc[4 * orow + oc][e]);
 #pragma unroll
-            for (int e = 0; e < 16; ++e) { acc[2 * ph][e] = relu_bits(acc[2 * ph][e]); acc[2 * ph + 1][e] = relu_bits(acc[2 * ph + 1][e]); }
+            for (int e = 0; e < 4; ++e)
 #pragma unroll
-            for (int pw = 0; pw < 2; ++pw)
-#pragma unroll
-                for (int kh = 0; kh < 3; ++kh) Tq[pw][kh] = (f32x4)(0.f);
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-#pragma unroll
-                for (int kh = 0; kh < 3; ++kh) {
-                    Tq[0][kh] = __builtin_amdgcn_mfma_f32_4x4x1f32(w4g[kh][e], acc[2 * ph][e], Tq[0][kh], 0, 0, 0);
-                    Tq[1][kh] = __builtin_amdgcn_mfma_f32_4x4x1f32(w4g[kh][e], acc[2 * ph + 1][e], Tq[1][kh], 0, 0, 0);
-                }
-            // horizontal presum per channel half (the halves are added by the gather): lane = (pixel c' = lane & 31, half h)
-            int hsw = hb + 2 * w + ph;                       // ring slot of this wave's y3 row 2 (SR s + w) + ph
+                for (int oc = 0; oc < 4; ++oc)
+                    T[oc] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4a[e], acc[4 * orow + oc][e], e == 0 ? zero4 : T[oc], 0, 0, 0);
+            // T[oc][kw] = tap (kh = g, kw) at column 4 v + oc; H(c) = (T[kw 0] at c + 1 + T[kw 1] at c) + T[kw 2] at c - 1
+            f32x4 hv;
+            hv[0] = (T[1][0] + T[0][1]) + dpp_shr1_zero(T[3][2]);
+            hv[1] = (T[2][0] + T[1][1]) + T[0][2];
+            hv[2] = (T[3][0] + T[2][1]) + T[1][2];
+            hv[3] = (dpp_shl1_zero(T[0][0]) + T[3][1]) + T[2][2];
+            int hsw = hb + 4 * u + orow;                   // ring slot of this wave's y3 row 2 SR s + 4 u + orow
             hsw = hsw >= DB_YROWS ? hsw - DB_YROWS : hsw;
-            float* hp = sH + ((hsw * 2 + h) * 3) * 64 + 2 * j;
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh) {
-                float l = wave_shr1(Tq[1][kh][2]), r = wave_shl1(Tq[0][kh][0]);
-                l = (j == 0) ? 0.f : l;                       // lane 32 received lane 31 (the other channel half's pixel 31): image edge
-                r = (j == 31) ? 0.f : r;
-                float2 eo;
-                eo.x = (Tq[1][kh][0] + Tq[0][kh][1]) + l;
-                eo.y = (r + Tq[1][kh][1]) + Tq[0][kh][2];
-                *reinterpret_cast<float2*>(hp + kh * 64) = eo;
-            }
+            if (g < 3) *reinterpret_cast<f32x4*>(sH + ((hsw * 2 + hf) * 3 + g) * 64 + 4 * v) = hv;
         }
         __syncthreads();
         if (gq) { g_store(oh0, 0); g_store(oh1, 1); }     // the deferred rows' pixels (stores behind the prefetch loads)
@@ -701,10 +724,10 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     // Q_k = the xor-tree sum over the 64 lanes of ((wave 0 + wave 1) + (wave 2 + wave 3)) of the parked partials: wave k reduces quarter k
     if (w < (parts == 1 ? 4 : 1)) {
         const float* qk = sq + w * NTHR + lane;
-        float v = (qk[0] + qk[64]) + (qk[128] + qk[192]);
+        float val = (qk[0] + qk[64]) + (qk[128] + qk[192]);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) sQ[w] = v;
+        for (int o = 32; o > 0; o >>= 1) val += __shfl_xor(val, o);
+        if (lane == 0) sQ[w] = val;
     }
     __syncthreads();
     if (tid == 0) {
@@ -713,7 +736,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     }
 }
 
-constexpr size_t DB_LDS4D = ((5 * 32 + 1) * 17) * sizeof(float4) + 18 * 2 * 3 * 64 * sizeof(float);  // input strip + H planes per channel half (4 SR + 2 rows)
+constexpr size_t DB_LDS4D = ((5 * 33) * 17) * sizeof(float4) + 18 * 2 * 3 * 64 * sizeof(float);  // input strip (+ zero column) + H planes per channel half (4 SR + 2 rows)
 int init_dec_b_kernels() {
     if (hipFuncSetAttribute((const void*)k_dec_b4<1>, hipFuncAttributeMaxDynamicSharedMemorySize, DB_LDS4D) != hipSuccess) return 1;
     if (hipFuncSetAttribute((const void*)k_dec_b4<4>, hipFuncAttributeMaxDynamicSharedMemorySize, DB_LDS4D) != hipSuccess) return 1;

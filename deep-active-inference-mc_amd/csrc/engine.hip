@@ -185,6 +185,23 @@ int upload_packed(efe_ctx* ctx, Layer& L, int ntaps, int cout, int cin, Get get,
     return 0;
 }
 
+// Minimal-filtering F(2, 2) weights of a stride-2 ConvTranspose2d(cin, cout, 3, s2, p1, op1), W [cin][cout][kh][kw] (kernels.h f22_*):
+// U[4 wr + wc][co][ci] = sum_{kh, kw} f22_cw(wr, kh) f22_cw(wc, kw) W[ci][co][kh][kw], formed in fp64 and rounded once
+std::vector<float> convt_s2_f22_weights(const float* W, int cin, int cout) {
+    std::vector<float> U((size_t)16 * cout * cin);
+    for (int wr = 0; wr < 4; ++wr)
+        for (int wc = 0; wc < 4; ++wc)
+            for (int co = 0; co < cout; ++co)
+                for (int ci = 0; ci < cin; ++ci) {
+                    const float* k = W + ((size_t)ci * cout + co) * 9;
+                    double s = 0;
+                    for (int kh = 0; kh < 3; ++kh)
+                        for (int kw = 0; kw < 3; ++kw) s += (double)(f22_cw(wr, kh) * f22_cw(wc, kw)) * (double)k[kh * 3 + kw];
+                    U[((size_t)(4 * wr + wc) * cout + co) * cin + ci] = (float)s;
+                }
+    return U;
+}
+
 const HostTensor* need(efe_ctx* ctx, const std::string& key, std::initializer_list<int64_t> shape) {
     auto it = ctx->raw.find(key);
     if (it == ctx->raw.end()) { ctx->err = "missing weight " + key; return nullptr; }
@@ -1173,6 +1190,17 @@ int efe_commit_weights(efe_ctx* ctx) {
                 }
             if (upload_packed(ctx, ctx->dec_ct[0], 16, 64, 64, [&](int t, int co, int ci) { return U[((size_t)t * 64 + co) * 64 + ci]; },
                               b->data.data(), nullptr)) return 1;
+            continue;
+        }
+        if (i == 2) {   // po_net.17 (k_dec_b4's ConvT3, v_mfma_f32_16x16x4_f32): the 16 F(2, 2) matrices U, packed
+                        // [U][channel half hf][chunk kc][lane][s] = U[16 hf + (lane & 15)][16 kc + 4 (lane >> 4) + s]
+            const std::vector<float> U = convt_s2_f22_weights(W, 64, 32);
+            if (upload_packed(ctx, ctx->dec_ct[2], 16, 32, 64, [](int, int, int) { return 0.f; }, b->data.data(), nullptr)) return 1;   // buffer + bias
+            std::vector<float> p(U.size());
+            for (int m = 0; m < 16; ++m) for (int hf = 0; hf < 2; ++hf) for (int kc = 0; kc < 4; ++kc) for (int lane = 0; lane < 64; ++lane)
+                for (int s_ = 0; s_ < 4; ++s_)
+                    p[((((size_t)m * 2 + hf) * 4 + kc) * 64 + lane) * 4 + s_] = U[((size_t)m * 32 + 16 * hf + (lane & 15)) * 64 + 16 * kc + 4 * (lane >> 4) + s_];
+            HIPCHK(hipMemcpy(ctx->dec_ct[2].Wp, p.data(), p.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
         if (upload_packed(ctx, ctx->dec_ct[i], 9, Cout, tci[i],

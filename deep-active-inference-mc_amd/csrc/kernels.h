@@ -116,9 +116,20 @@ struct DecAArgs {
     float w1s = 1.0f, w1s_inv = 1.0f, w2s = 1.0f, w2s_inv = 1.0f;  // fp16 split: the layers' weight scales (powers of two) and their inverses
 };
 // fused decoder, stage B: y2 -> ConvT(64,32,s2)+ReLU -> ConvT(32,1,s1)+Sigmoid -> per-image reduction (+ image store)
+// Minimal filtering F(2, 2) of a stride-2 transposed conv along one dimension (ConvTranspose2d(k 3, s 2, p 1, op 1), oh = 2 ih - 1 + kh;
+// decoder.hip k_dec_b4): for the input pair block u, x0 = x[2u], x1 = x[2u + 1], x2 = x[2u + 2], the views d0 = x0 - x1, d1 = x1,
+// d2 = x2 - x1 and the weights {g1, g2, g0 + g2, g0} give outputs 4u .. 4u + 3 from five products P1..P5 (p = 0..4):
+//     P1 = d0 g1 -> 0    P2 = d1 g1 -> 0, 2    P3 = d0 g2 -> 1    P4 = d1 (g0 + g2) -> 1, 3    P5 = d2 g0 -> 3
+// f22_view / f22_wt / f22_o0 / f22_o1 (-1: none) of product p; f22_cw(wt, k): coefficient of tap k in weight wt.
+__host__ __device__ constexpr int f22_view(int p) { return p == 4 ? 2 : (p & 1); }
+__host__ __device__ constexpr int f22_wt(int p) { return p < 2 ? 0 : p - 1; }
+__host__ __device__ constexpr int f22_o0(int p) { return p < 2 ? 0 : (p < 4 ? 1 : 3); }
+__host__ __device__ constexpr int f22_o1(int p) { return p == 1 ? 2 : (p == 3 ? 3 : -1); }
+__host__ __device__ constexpr int f22_cw(int wt, int k) { return wt == 0 ? (k == 1) : wt == 1 ? (k == 2) : wt == 2 ? (k != 1) : (k == 0); }
+
 struct DecBArgs {
     const float* y2;
-    const float* w3; const float* b3;   // packed [9][1][8][64][4], bias [32]
+    const float* w3; const float* b3;   // F(2, 2) weights packed [16 U][2 channel halves][4 chunks][64][4] (engine.hip), bias [32]
     const float* w4; float b4;          // [9 taps][32 ch], scalar bias
     int rows;             // decoder rows (images) in this launch
     RowMask live;
