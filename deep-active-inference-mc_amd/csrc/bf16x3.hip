@@ -334,7 +334,7 @@ __global__ void __launch_bounds__(512 / NTW, 1) k_dec_a_b3(const DecAArgs a) {
     for (int i = tid; i < DA3_PXB / 4; i += NTHR) reinterpret_cast<uint32_t*>(sm3 + 256 * DA3_PXB)[i] = 0u;      // the zero pixel
     const float4* W1 = reinterpret_cast<const float4*>(a.w1b3);
     const float4* W2 = reinterpret_cast<const float4*>(a.w2b3);
-    // packed tap index kh * 3 + kw of tap t of output parity par of the stride-2 layer (the order of ConvT2Addr, mfma_pipe.h)
+    // packed tap index kh * 3 + kw of tap t of output parity par of the stride-2 layer (per dimension, even parity: tap 1 at source ih; odd parity: tap 0 at ih + 1, then tap 2 at ih; rows outside, columns inside)
     auto l2_wt = [](int par, int t) -> int {
         const int ph = par >> 1, pw = par & 1;
         const int th = t / (1 + pw), tw = t - th * (1 + pw);
@@ -479,7 +479,7 @@ __global__ void __launch_bounds__(512 / NTW, 1) k_dec_a_b3(const DecAArgs a) {
             }
             if (SC::SCALED && ovf) { sovf[fpar] = 1; ovf = 0; }
         }
-        // ---------------- layer 2 (stride 2): 4 output parities, oh = 2 ih - 1 + kh (the tap order of ConvT2Addr, mfma_pipe.h) ---------------
+        // ---------------- layer 2 (stride 2): 4 output parities, oh = 2 ih - 1 + kh (per dimension, even parity: tap 1; odd parity: tap 0, then tap 2; rows outside, columns inside) ---------------
         float* Y = a.y2 + (size_t)img * (32 * 32 * 64);
         int T = 9;
 #pragma unroll 1

@@ -4,7 +4,7 @@
 //
 // One workgroup (4 waves) owns one decoder image; activations live in LDS between layers:
 //
-//   k_dec_a :  x4[16x16x64] --LDS--> ConvT(64,64,s1)+ReLU (Winograd F(2x2,3x3)) --LDS (in place)--> ConvT(64,64,s2)+ReLU --> y2[32x32x64] (HBM)
+//   k_dec_a :  x4[16x16x64] --LDS--> ConvT(64,64,s1)+ReLU (Winograd F(2x2,3x3)) --LDS (in place)--> ConvT(64,64,s2)+ReLU (F(2,2), registers) --> y2[32x32x64] (HBM)
 //   k_dec_b4:  y2 strips --LDS--> ConvT(64,32,s2)+ReLU (F(2,2), registers) --MFMA--> tap values of the 32->1 conv, horizontal sums in registers
 //              --LDS ring of H planes--> vertical gather + sigmoid + entropy / reward reduction (+ optional image store)
 //   k_dec_a_s / k_dec_b4<4>: the same kernels with an image over eight / four workgroups, for launches of <= 128 images
@@ -12,12 +12,65 @@
 // LDS images are [pixel][17 float4 slots]: the 16 channel quads of a pixel plus one slot of padding, so that the ds_read_b128 of an
 // MFMA B fragment (32 pixels x same quad) is bank-conflict free (16 consecutive pixels cover the 16 bank quads: 17 p mod 16 = p) and a
 // fragment address is pixel base + an immediate (k_fc4's batch tile alone is still XOR-swizzled).  Weights are read as pre-packed A
-// fragments straight from L2 (1 KiB coalesced per wave-load, shared by all workgroups).  fp32 MFMA (v_mfma_f32_32x32x2_f32 and the
-// 4x4x1 16-block form): exact fp32 numerics.
+// fragments straight from L2 (1 KiB coalesced per wave-load, shared by all workgroups).  fp32 MFMA (v_mfma_f32_32x32x2_f32 for ConvT1 and
+// k_fc4, v_mfma_f32_16x16x4_f32 for the two F(2, 2) layers and the 32 -> 1 conv): exact fp32 numerics.
 #include <utility>
 #include "mfma_pipe.h"
 
 namespace efe {
+
+// ---------------------------------------------------------------------------------------------------------
+// The stride-2 layers ConvT2 (ConvTranspose2d(64, 64, 3, s2, p1, op1): f22_l2 in k_dec_a / k_dec_a_s) and ConvT3 (ConvTranspose2d(64, 32, 3, s2,
+// p1, op1): k_dec_b4) by per-parity minimal filtering F(2, 2).  Along one dimension, with taps g0, g1, g2 (oh = 2 ih - 1 + kh) and x = 0
+// behind the last row / column, output 2m = x[m] g1 and 2m + 1 = x[m] g2 + x[m + 1] g0.  For an input pair block u
+// (x0 = x[2u], x1 = x[2u + 1], x2 = x[2u + 2]) the views d0 = x0 - x1, d1 = x1, d2 = x2 - x1 give the four outputs 4u .. 4u + 3 from
+// five products instead of six:
+//     P1 = d0 g1 -> 0    P2 = d1 g1 -> 0, 2    P3 = d0 g2 -> 1    P4 = d1 (g0 + g2) -> 1, 3    P5 = d2 g0 -> 3
+// In 2D (the outer product of this table with itself) a 2 x 2 input block needs 25 products instead of 36: 9 views d_a (x) d_b and 16
+// weight matrices U = w_r (x) w_c, w in {g1, g2, g0 + g2, g0}, formed in fp64 at commit time and rounded once (engine.hip).  The 9
+// products with one output in both dimensions chain straight into that output; the other 16 run in a short-lived accumulator that is
+// then added into its 2 or 4 outputs.  (The 1D table f22_* is in kernels.h: engine.hip forms the weights from it.)
+//
+// compile-time loop: f(std::integral_constant<int, 0>{}) .. f(std::integral_constant<int, N - 1>{})
+template <class F, int... I> __device__ __forceinline__ void static_for_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_(f, std::make_integer_sequence<int, N>{}); }
+
+// The schedule of both layers: six groups of products that share their views (every B fragment read feeds 4 or 5 independent chains):
+//   G0 V(0,0): (P1|P3) x (P1|P3)  direct      G1 V(0,1): (P1|P3) x (P2|P4)      G2 V(1,0): (P2|P4) x (P1|P3)      G3 V(1,1): (P2|P4) x (P2|P4)
+//   G4 V(1,2), V(2,1), V(2,2): (P2|P4) x P5, P5 x (P2|P4), P5 x P5 (direct)      G5 V(0,2), V(2,0): (P1|P3) x P5, P5 x (P1|P3)  direct
+// w3_prod(G, c) = 5 pr + pc of chain c of group G (rows x columns)
+__host__ __device__ constexpr int w3_nch(int G) { return G == 4 ? 5 : 4; }
+__host__ __device__ constexpr int w3_prod(int G, int c) {
+    return G < 4 ? 5 * ((G >> 1) + 2 * (c >> 1)) + (G & 1) + 2 * (c & 1)
+         : G == 4 ? (c < 2 ? 5 * (1 + 2 * c) + 4 : c < 4 ? 20 + 1 + 2 * (c - 2) : 24)
+                  : (c < 2 ? 5 * (2 * c) + 4 : 20 + 2 * (c - 2));
+}
+__host__ __device__ constexpr bool w3_direct(int pp) { return f22_o1(pp / 5) < 0 && f22_o1(pp % 5) < 0; }
+__host__ __device__ constexpr int w3_view(int pp) { return 3 * f22_view(pp / 5) + f22_view(pp % 5); }
+__host__ __device__ constexpr int w3_mat(int pp) { return 4 * f22_wt(pp / 5) + f22_wt(pp % 5); }
+__host__ __device__ constexpr bool w3_hits(int pp, int o) {          // product pp feeds output o = 4 orow + ocol of the block
+    const int r = o >> 2, c = o & 3, pr = pp / 5, pc = pp % 5;
+    return (r == f22_o0(pr) || r == f22_o1(pr)) && (c == f22_o0(pc) || c == f22_o1(pc));
+}
+// output o already holds a value when chain c of group G reaches it (a group's direct chains run before its temporaries are added,
+// those in chain order): otherwise the chain starts from the bias (direct: the C operand of its first MFMA; temporary: bias + M)
+__host__ __device__ constexpr bool w3_seen(int G, int c, int o) {
+    for (int g = 0; g < G; ++g)
+        for (int k = 0; k < w3_nch(g); ++k) if (w3_hits(w3_prod(g, k), o)) return true;
+    if (!w3_direct(w3_prod(G, c)))
+        for (int k = 0; k < w3_nch(G); ++k)
+            if ((w3_direct(w3_prod(G, k)) || k < c) && w3_hits(w3_prod(G, k), o)) return true;
+    return false;
+}
+__host__ __device__ constexpr bool w3_uses_view(int G, int vi) {
+    for (int k = 0; k < w3_nch(G); ++k) if (w3_view(w3_prod(G, k)) == vi) return true;
+    return false;
+}
+__host__ __device__ constexpr bool f22_in(int a, int r) { return a == 0 ? r <= 1 : (a == 1 ? r == 1 : r >= 1); }   // view a reads x_r
+__host__ __device__ constexpr bool w3_reads(int G, int r, int c) {   // input pixel (r, c) of the 3 x 3 block neighbourhood
+    for (int vi = 0; vi < 9; ++vi) if (w3_uses_view(G, vi) && f22_in(vi / 3, r) && f22_in(vi % 3, c)) return true;
+    return false;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // k_dec_a: ConvTranspose2d(64,64,3,s1,p1)+ReLU then ConvTranspose2d(64,64,3,s2,p1,op1)+ReLU, one image per WG.
@@ -26,7 +79,7 @@ namespace efe {
 // (17 p mod 16 = p), and a fragment address is pixel base + constant -- the chunk offset is an immediate of the ds_read (the XOR swizzle
 // of rounds 1-2 cost an XOR and an add per chunk and 11 % of the LDS cycles in bank conflicts).
 constexpr int DA_PS = 17;
-constexpr int DA_BIAS = 257 * DA_PS;       // float4 index of the two bias vectors behind the image + zero pixel
+constexpr int DA_BIAS = 273 * DA_PS;       // float4 index of the two bias vectors behind the image + a zero row (pixels 256 .. 272: row 16, which layer 2's last block row reads as its x_2)
 
 // ---------------------------------------------------------------------------------------------------------
 // Layer 1 (ConvTranspose2d(64,64,3,s1,p1) = a 3x3 correlation with the flipped kernel g, pad 1) by Winograd F(2x2, 3x3) (Lavin):
@@ -139,13 +192,119 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
         for (int a = a_lo; a < a_hi; ++a) xi_row(a, std::integral_constant<int, 1>{});
     }
 }
-// Four waves of 64 features x 64 pixels each (NTW = 2 32-pixel tiles per wave; 256 VGPRs, 2 waves per SIMD).
+// ---------------------------------------------------------------------------------------------------------
+// Layer 2 (ConvTranspose2d(64,64,3,s2,p1,op1)) by F(2, 2) (the table and the six-group schedule at the top of this file) on
+// v_mfma_f32_16x16x4_f32: one call contracts a tile of 16 output channels (M) x 16 blocks of 2 x 2 layer-1 pixels (N, lane n = lane & 15)
+// over the 64 input channels (K = 4 per instruction: lane group g = lane >> 4 supplies channel quad 4 kc + g of chunk kc, so one
+// ds_read_b128 feeds four MFMAs).  acc[4 orow + ocol] holds channels 16 ct + 4 g + 0..3 of output pixel (orow, ocol) of the lane's block.
+// The association of every output element, the same in k_dec_a and k_dec_a_s: the bias; then groups 0..5 in order, in each the direct
+// chains (channel chunks 0..3, four channels per MFMA) straight into their output, then the temporaries added in chain order.
+// nb: LDS float4 indices (the lane's quad g included) of the block's 3 x 3 pixel neighbourhood: pixel (i, jj), i, jj < 2, at
+// xb + (16 i + jj) DA_PS; column 2 of row i at c2[i]; row 2, column jj < 2, at r2 + jj DA_PS (the callers point x_2 beyond the last
+// row / column at zero pixels).  With the lane order n = 8 (block row & 1) + block column the lanes that one ds_read_b128 pass serves
+// ({0-3, 12-15} of a lane group and {4-11} of the next: pixels at a stride of two, quads at distance one) hit 16 distinct bank quads.
+// U: packed [16 matrices][4 channel tiles][4 chunks][64 lanes][4] (engine.hip); wr: the resource based at this channel tile; dn: distance
+// to the tile contracted next (0 or 1), whose first fragments are requested behind this tile's last ones.  aq: the fragments of the
+// tile's first F22_PD steps on entry (f22_l2_first), of the next tile's on exit.
+// ---------------------------------------------------------------------------------------------------------
+struct F22Nb { int xb, c2[3], r2; };
+__device__ __forceinline__ f32x4 f22_wfrag(const __amdgpu_buffer_rsrc_t wr, const unsigned ln, int ct, int m, int kc) {
+    return __builtin_bit_cast(f32x4, wfrag(wr, ln + (unsigned)kc * 1024u, (size_t)(m * 4 + ct) * 256));      // kc: the load's immediate offset
+}
+constexpr int F22_PD = 2;                              // A-fragment prefetch distance in steps (16 - 20 MFMAs each; fragments come from L2)
+// the fragments of steps 0 .. F22_PD - 1 of the tile dn tiles behind wr's
+__device__ __forceinline__ void f22_l2_first(f32x4 (&aq)[F22_PD][5], const __amdgpu_buffer_rsrc_t wr, const int dn, const unsigned ln) {
+    static_for<F22_PD>([&](auto p) {
+        static_for<w3_nch(p >> 2)>([&](auto c) { aq[p][c] = f22_wfrag(wr, ln, dn, w3_mat(w3_prod(p >> 2, c)), p & 3); });
+    });
+}
+__device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5], const __amdgpu_buffer_rsrc_t wr, const int dn,
+                                       const unsigned ln, const f32x4 bias4, const f32x4* smv, const F22Nb& nb) {
+    constexpr int NST = 24;                            // contraction steps: 6 groups x 4 chunks of 16 channels
+    auto px = [&](int i, int jj, int kc) -> f32x4 {
+        return smv[(jj == 2 ? nb.c2[i] : (i == 2 ? nb.r2 + jj * DA_PS : nb.xb + (16 * i + jj) * DA_PS)) + 4 * kc];
+    };
+    // view (a, b) of the raw neighbourhood x[i][jj]: the columns first (x[i][0] - x[i][1] | x[i][1] | x[i][2] - x[i][1]), then the rows
+    auto view = [&](const f32x4 (&x)[9], int vi) -> f32x4 {
+        const int va = vi / 3, vb = vi % 3;
+        auto cv = [&](int i) -> f32x4 { return vb == 0 ? x[3 * i] - x[3 * i + 1] : (vb == 1 ? x[3 * i + 1] : x[3 * i + 2] - x[3 * i + 1]); };
+        return va == 0 ? cv(0) - cv(1) : (va == 1 ? cv(1) : cv(2) - cv(1));
+    };
+    const f32x4 zero4 = {};
+    f32x4 tq[5], xr[9];
+    static_for<9>([&](auto i) { if constexpr (w3_reads(0, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, 0); });
+    // software-pipelined one step ahead: step ST = (group ST >> 2, chunk ST & 3), every index a compile-time constant
+    static_for<NST>([&](auto stc) {
+        constexpr int ST = decltype(stc)::value, G = ST >> 2, KC = ST & 3, GN = (ST + 1) >> 2, KN = (ST + 1) & 3;
+        constexpr int SP = (ST + F22_PD) % NST, GP = SP >> 2, KP = SP & 3;      // the step whose fragments are requested now
+        f32x4 vw[9], ac[5];
+        static_for<9>([&](auto vi) { if constexpr (w3_uses_view(G, vi)) vw[vi] = view(xr, vi); });
+#pragma unroll
+        for (int c = 0; c < 5; ++c) ac[c] = aq[ST % F22_PD][c];
+        static_for<w3_nch(GP)>([&](auto c) { aq[ST % F22_PD][c] = f22_wfrag(wr, ln, ST + F22_PD < NST ? 0 : dn, w3_mat(w3_prod(GP, c)), KP); });
+        if constexpr (ST + 1 < NST)
+            static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
+        __builtin_amdgcn_sched_barrier(0);             // keep the prefetch loads AHEAD of this step's MFMAs
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            static_for<w3_nch(G)>([&](auto c) {
+                constexpr int PP = w3_prod(G, c);
+                const float b = vw[w3_view(PP)][e], av = ac[c][e];
+                if constexpr (w3_direct(PP)) {
+                    constexpr int O = 4 * f22_o0(PP / 5) + f22_o0(PP % 5);
+                    constexpr bool FIRST = KC == 0 && !w3_seen(G, c, O);
+                    acc[O] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (FIRST && e == 0) ? bias4 : acc[O], 0, 0, 0);
+                } else {
+                    tq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (KC == 0 && e == 0) ? zero4 : tq[c], 0, 0, 0);
+                }
+            });
+        if constexpr (KC == 3)                         // the group's temporaries into their outputs, in chain order
+            static_for<w3_nch(G)>([&](auto c) {
+                constexpr int PP = w3_prod(G, c);
+                if constexpr (!w3_direct(PP))
+                    static_for<16>([&](auto o) {
+                        if constexpr (w3_hits(PP, o)) {
+                            if constexpr (w3_seen(G, c, o)) acc[o] = acc[o] + tq[c];
+                            else acc[o] = bias4 + tq[c];
+                        }
+                    });
+            });
+    });
+}
+// ReLU + the tile's y2 stores.  y2 is [parity][8 channel groups][16 x 16 positions][8 channels]: outputs (orow, c) and (orow, c + 2) of a
+// block are neighbouring positions of one parity, and lane groups g, g ^ 1 are the two halves of one 8-channel group.  One
+// v_permlane32_swap per register pair gives lanes 0-31 the pair's values of channel group 2 ct (lanes 32-63: the next position) and
+// the second register those of channel group 2 ct + 1, so that a store instruction writes a block row's 16 positions x 32 bytes as
+// one 512-byte run (two block rows: two runs).  yr: the image; yoff: byte offset of (block row, block column, g) inside a plane,
+// ((32 bu + 2 bv + (g >> 1)) 2 + (g & 1)) 16; on: lanes that store (the swaps run on every lane).
+__device__ __forceinline__ void f22_l2_store(f32x4 (&acc)[16], const __amdgpu_buffer_rsrc_t yr, const unsigned yoff, const int ct, const bool on) {
+#pragma unroll
+    for (int orow = 0; orow < 4; ++orow)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            u32x4 lo, hi;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned x0 = __builtin_bit_cast(unsigned, relu_bits(acc[4 * orow + c][e]));
+                const unsigned x1 = __builtin_bit_cast(unsigned, relu_bits(acc[4 * orow + c + 2][e]));
+                const auto sw = __builtin_amdgcn_permlane32_swap(x0, x1, false, false);
+                lo[e] = sw[0]; hi[e] = sw[1];
+            }
+            const unsigned so = (unsigned)(((2 * (orow & 1) + c) * 4096 + 2 * ct * 512 + (orow >> 1) * 32) * 16);
+            if (on) {
+                __builtin_amdgcn_raw_buffer_store_b128(lo, yr, yoff, so, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(hi, yr, yoff, so + 512u * 16u, 0);
+            }
+        }
+}
+
+// Four waves per image (256 VGPRs, 2 waves per SIMD).  Layer 1: 32 channels x 32 Winograd tiles per wave; layer 2: four passes of 16 channels
+// x 16 blocks (block rows 2 w, 2 w + 1) per wave.
 __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
-    constexpr int NTW = 2;
-    constexpr int NTHR = 512 / NTW;
+    constexpr int NTHR = 256;
     constexpr int NPH = 2048 / NTHR;                  // float4s per thread of each image half
-    constexpr int NPE = 8;                            // of them requested before layer 1 (its registers hold no more), the other 2 NPH - NPE behind it
-    extern __shared__ __attribute__((aligned(16))) float4 sm[];        // [257 pixels][DA_PS slots]; pixel 256 = zeros
+    constexpr int NPE = 8;                            // float4s of the next image requested ahead of layer 2, the others behind its last contraction
+    extern __shared__ __attribute__((aligned(16))) float4 sm[];        // [273 pixels][DA_PS slots]; pixels 256 .. 272 = zeros
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -167,9 +326,9 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
     {
         const f32x4* X = reinterpret_cast<const f32x4*>(a.x4) + (size_t)blockIdx.x * 4096;
 #pragma unroll
-        for (int it = 0; it < 2 * NPH; ++it) pf[it] = X[it * NTHR + tid];
+        for (int it = 0; it < 2 * NPH; ++it) pf[it] = X[w * 1024 + it * 64 + lane];      // wave w: pixels 64 w .. 64 w + 63 (16 KiB contiguous)
     }
-    if (tid < 16) sm[256 * DA_PS + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = tid; i < 17 * DA_PS; i += NTHR) sm[256 * DA_PS + i] = make_float4(0.f, 0.f, 0.f, 0.f);
     // biases live in LDS: a global bias load inside an epilogue forces s_waitcnt vmcnt(0), i.e. waits for every store
     // issued before it (vmcnt retires in order) and serialises the whole store stream
     if (tid < 16) sm[DA_BIAS + tid] = reinterpret_cast<const float4*>(a.b1)[tid];
@@ -181,48 +340,24 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
         // the image loop, which pushed the kernel over 256 VGPRs (spill reloads carry s_waitcnt vmcnt(0): they serialised
         // the prefetch loads and waited for every outstanding y2 store)
         int tl_ = tid; asm volatile("" : "+v"(tl_));
-        // this wave's 64 pixels / input positions: image rows 4w .. 4w+3, two 32-pixel tiles of two rows each
         const int j = tl_ & 31, h = (tl_ >> 5) & 1;
-        const int pcol = j & 15;
-        const int prow0 = 2 * NTW * w + (j >> 4);                      // tile nt covers rows prow0 + 2*nt
         // a dead row of the call (efe_rows.mask) keeps the schedule -- barriers, ticket, the next image's prefetch -- and skips the work
         const bool live = row_live(a.live, img);
-        if (live) {   // pixel it * (NTHR / 16) + (tid >> 4), quad tid & 15: one address register, immediate offsets
-            const int sbase = (tl_ >> 4) * DA_PS + (tl_ & 15);
+        if (live) {   // pixel 64 w + 4 it + (lane >> 4), quad lane & 15: one address register, immediate offsets
+            const int sbase = (64 * w + ((tl_ >> 4) & 3)) * DA_PS + (tl_ & 15);
 #pragma unroll
-            for (int it = 0; it < 2 * NPH; ++it) smv[sbase + it * (NTHR / 16) * DA_PS] = pf[it];
+            for (int it = 0; it < 2 * NPH; ++it) smv[sbase + it * 4 * DA_PS] = pf[it];
         }
         __syncthreads();
         const int nnimg = slot[0];                     // the image after nimg (written one iteration ago)
         int ticket = 0;
         if (tid == 0) ticket = 2 * (int)gridDim.x + atomicAdd(a.queue, 1);     // lands during the layer-1 contraction
-        // request the first NPE float4s of the next image now (clamped on the last pass: unconditional loads keep pf[] in registers).  Buffer loads
-        // (uniform image base, one lane offset): flat loads hold a 64-bit address per load
-        const int pimg = __builtin_amdgcn_readfirstlane(nimg < a.rows ? nimg : img);
-        const __amdgpu_buffer_rsrc_t xr = wrsrc(a.x4 + (size_t)pimg * 16384);
-        const unsigned tlo = (unsigned)tl_ * 16u;
-#pragma unroll
-        for (int it = 0; it < NPE; ++it) pf[it] = __builtin_bit_cast(f32x4, wfrag(xr, tlo, (size_t)it * NTHR));
-
-        f32x16 acc[2][NTW];
-        // the accumulators start at the bias (register e of tile mt holds channel 32mt + (e&3) + 8(e>>2) + 4h) and ReLU is one
-        // integer max in the epilogue: each VALU instruction there costs ~19 cycles of wave time beside the other wave's MFMAs
-        auto acc_init = [&](int boff) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const float4 bb = sm[DA_BIAS + boff + mt * 8 + 2 * g4 + h];
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) { acc[mt][nt][4 * g4] = bb.x; acc[mt][nt][4 * g4 + 1] = bb.y; acc[mt][nt][4 * g4 + 2] = bb.z; acc[mt][nt][4 * g4 + 3] = bb.w; }
-                }
-        };
         // ---------------- layer 1 (Winograd F(2x2, 3x3), see wino_l1): wave w owns channels 32 (w >> 1) .. + 31 of the 32 tiles
         // 32 (w & 1) .. + 31 (tile n = 8 ty + tx: tile rows 4 (w & 1) .. + 3), lane j = tile
         const int l1mt = w >> 1, l1n = 32 * (w & 1) + j;
         const int l1y = 2 * (l1n >> 3) - 1, l1x = 2 * (l1n & 7) - 1;      // the tile's input corner (may be -1: padding)
-        f32x16 (&l1o)[2][2] = acc;                  // (layer 2 reuses the registers)
-        if (live) {
+        if (live) {     // (workgroup-uniform: both branches pass the same barriers; the outputs live in this branch alone)
+            f32x16 l1o[2][2];
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {           // the outputs start at the bias (register e holds channel 32 mt + (e & 3) + 8 (e >> 2) + 4 h)
                 const float4 bb = sm[DA_BIAS + l1mt * 8 + 2 * g4 + h];
@@ -233,50 +368,68 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
                 const int y = l1y + i, x = l1x + jj;
                 return ((unsigned)y < 16u && (unsigned)x < 16u ? y * 16 + x : 256) * DA_PS;
             });
-        }
-        __syncthreads();                // every wave is done reading the input image (and slot[0])
-        if (tid == 0) slot[0] = ticket;
-        // bias + ReLU, written back IN PLACE as the input image of layer 2 (same padded layout)
-        if (live)
+            __syncthreads();            // every wave is done reading the input image (and slot[0])
+            if (tid == 0) slot[0] = ticket;
+            // bias + ReLU, written back IN PLACE as the input image of layer 2 (same padded layout)
 #pragma unroll
-        for (int rc = 0; rc < 4; ++rc) {
-            const int pix = (l1y + 1 + (rc >> 1)) * 16 + l1x + 1 + (rc & 1);
+            for (int rc = 0; rc < 4; ++rc) {
+                const int pix = (l1y + 1 + (rc >> 1)) * 16 + l1x + 1 + (rc & 1);
 #pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const f32x16& o = l1o[rc >> 1][rc & 1];
-                float4 v;
-                v.x = relu_bits(o[4 * g4 + 0]); v.y = relu_bits(o[4 * g4 + 1]);
-                v.z = relu_bits(o[4 * g4 + 2]); v.w = relu_bits(o[4 * g4 + 3]);
-                sm[pix * DA_PS + l1mt * 8 + 2 * g4 + h] = v;
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const f32x16& o = l1o[rc >> 1][rc & 1];
+                    float4 v;
+                    v.x = relu_bits(o[4 * g4 + 0]); v.y = relu_bits(o[4 * g4 + 1]);
+                    v.z = relu_bits(o[4 * g4 + 2]); v.w = relu_bits(o[4 * g4 + 3]);
+                    sm[pix * DA_PS + l1mt * 8 + 2 * g4 + h] = v;
+                }
             }
+        } else {
+            __syncthreads();
+            if (tid == 0) slot[0] = ticket;
         }
         __syncthreads();
-        // the rest of the next image, behind layer 1 (whose accumulators leave room for NPE float4s only; layer 2 covers its latency)
+        // ---------------- layer 2 (stride 2) by F(2, 2), see f22_l2: wave w owns block rows 2 w, 2 w + 1 (lane n = 8 (row & 1) + block
+        // column) and walks the four 16-channel tiles; the last block row reads its x_2 from the zero row, the last block column from pixel 256
+        {
+            // (the thread index laundered again: the lane constants of layer 2 must not be formed ahead of layer 1, which has no registers for them)
+            int t2_ = tid; asm volatile("" : "+v"(t2_));
+            const int n = t2_ & 15, g = (t2_ >> 4) & 3;
+            const int bu = 2 * w + (n >> 3), bv = n & 7;
+            const int zq = 256 * DA_PS + g;
+            F22Nb nb;
+            nb.xb = (32 * bu + 2 * bv) * DA_PS + g;
+            nb.c2[0] = bv == 7 ? zq : nb.xb + 2 * DA_PS;
+            nb.c2[1] = bv == 7 ? zq : nb.xb + 18 * DA_PS;
+            nb.c2[2] = bv == 7 ? zq : nb.xb + 34 * DA_PS;
+            nb.r2 = nb.xb + 32 * DA_PS;                 // (block row 7: the zero row, at the banks of a real row)
+            const unsigned ln = (unsigned)(t2_ & 63) * 16u;
+            const unsigned yoff = (unsigned)(((32 * bu + 2 * bv + (g >> 1)) * 2 + (g & 1)) * 16);
+            const __amdgpu_buffer_rsrc_t yr = wrsrc(a.y2 + (size_t)__builtin_amdgcn_readfirstlane(img) * (32 * 32 * 64));   // (uniform: img comes from LDS)
+            // the next image: NPE float4s are requested ahead of the four passes, the others behind the last contraction (layer 1 has no
+            // registers for any, a pass of layer 2 for half; the last tile's stores and the image barrier cover a part of that latency, the
+            // CU's other workgroup the rest).  Buffer loads (uniform image base, one lane offset; the image is clamped on the last pass:
+            // unconditional loads keep pf[] in registers)
+            auto load_next = [&](const int lo, const int hi) {
+                const int pimg = __builtin_amdgcn_readfirstlane(nimg < a.rows ? nimg : img);
+                const __amdgpu_buffer_rsrc_t xr = wrsrc(a.x4 + (size_t)pimg * 16384);
 #pragma unroll
-        for (int it = NPE; it < 2 * NPH; ++it) pf[it] = __builtin_bit_cast(f32x4, wfrag(xr, tlo, (size_t)it * NTHR));
-
-        // ---------------- layer 2 (stride 2): 4 output parities, oh = 2*ih - 1 + kh ----------------------------
-        float* Y = a.y2 + (size_t)img * (32 * 32 * 64);
+                for (int it = 0; it < 2 * NPH; ++it)     // (it & 3: the load's immediate offset; three scalar offsets instead of fifteen)
+                    if (it >= lo && it < hi) pf[it] = __builtin_bit_cast(f32x4, wfrag(xr, (unsigned)(w * 16384 + (t2_ & 63) * 16 + (it & 3) * 1024), (size_t)(it >> 2) * 256));
+            };
+            if (live) {
+                f32x4 aq[F22_PD][5], acc2[16];
+                f22_l2_first(aq, wrsrc(W2), 0, ln);
+                load_next(0, NPE);
 #pragma unroll 1
-        for (int par = 0; par < (live ? 4 : 0); ++par) {
-            const int ph = par >> 1, pw = par & 1;
-            acc_init(16);
-            tap_loop_pd<2, NTW, 1>(acc, (1 + ph) * (1 + pw), W2, sm, h, ConvT2Addr<NTW, DA_PS>{ph, pw, prow0, 2, pcol, 16, 16, 256}, ConvWIdx{});
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                // y2 layout (float4 units): [parity][8 channel groups][256 input positions][2 quads] -- for one (mt, g4) the 64
-                // lanes (position j of this wave's tile, quad h) write 1 KiB contiguous; the NHWC order would split every
-                // store into 32 scattered 32-byte pieces
-                float4* yp = reinterpret_cast<float4*>(Y) + (size_t)par * 4096 + ((2 * NTW * w + 2 * nt) * 16 + j) * 2 + h;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        float4 v;
-                        v.x = relu_bits(acc[mt][nt][4 * g4 + 0]); v.y = relu_bits(acc[mt][nt][4 * g4 + 1]);
-                        v.z = relu_bits(acc[mt][nt][4 * g4 + 2]); v.w = relu_bits(acc[mt][nt][4 * g4 + 3]);
-                        yp[(mt * 4 + g4) * 512] = v;
-                    }
+                for (int ct = 0; ct < 4; ++ct) {
+                    const f32x4 bias4 = smv[DA_BIAS + 16 + 4 * ct + g];
+                    f22_l2(acc2, aq, wrsrc(W2 + ct * 256), ct < 3 ? 1 : 0, ln, bias4, smv, nb);
+                    if (ct < 3) f22_l2_store(acc2, yr, yoff, ct, true);
+                }
+                load_next(NPE, 2 * NPH);
+                f22_l2_store(acc2, yr, yoff, 3, true);
+            } else {
+                load_next(0, 2 * NPH);
             }
         }
         __syncthreads();                // every wave is done reading layer-1's image before the next one overwrites it
@@ -293,13 +446,13 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
 // Waves: layer 1: (feature tile mt = w >> 1, output row r = w & 1 of the 16 Winograd tiles); layer 2: (mt = w >> 1, parities {(0,0), (1,1)} or {(0,1), (1,0)}).
 // ---------------------------------------------------------------------------------------------------------
 constexpr int DAS_IN = 6 * 16;                      // staged input pixels (+ a zero pixel)
-constexpr int DAS_L1 = 4 * 16;                      // layer-1 pixels kept (+ a zero pixel)
-constexpr int DAS_BIAS = (DAS_IN + 1 + DAS_L1 + 1) * DA_PS;
+constexpr int DAS_L1 = 4 * 16;                      // layer-1 pixels kept (+ two zero pixels)
+constexpr int DAS_BIAS = (DAS_IN + 1 + DAS_L1 + 2) * DA_PS;
 constexpr size_t DAS_LDS_BYTES = (DAS_BIAS + 32) * sizeof(float4);
 __global__ void __launch_bounds__(256, 2) k_dec_a_s(const DecAArgs a) {
     extern __shared__ __attribute__((aligned(16))) float4 sm[];
     float4* sin = sm;                                // [6 rows][16][DA_PS], pixel 96 = zeros
-    float4* sl1 = sm + (DAS_IN + 1) * DA_PS;         // [4 rows][16][DA_PS], pixel 64 = zeros
+    float4* sl1 = sm + (DAS_IN + 1) * DA_PS;         // [4 rows][16][DA_PS], pixels 64, 65 = zeros
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
@@ -319,19 +472,12 @@ __global__ void __launch_bounds__(256, 2) k_dec_a_s(const DecAArgs a) {
 #pragma unroll
         for (int it = 0; it < 6; ++it) sin[(px0 + 16 * it) * DA_PS + c4] = v[it];
     }
-    if (tid < 16) { sin[DAS_IN * DA_PS + tid] = make_float4(0.f, 0.f, 0.f, 0.f); sl1[DAS_L1 * DA_PS + tid] = make_float4(0.f, 0.f, 0.f, 0.f); }
+    if (tid < 16) sin[DAS_IN * DA_PS + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < 2 * DA_PS) sl1[DAS_L1 * DA_PS + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (tid < 16) sm[DAS_BIAS + tid] = reinterpret_cast<const float4*>(a.b1)[tid];
     else if (tid < 32) sm[DAS_BIAS + tid] = reinterpret_cast<const float4*>(a.b2)[tid - 16];
     __syncthreads();
     const int mt = w >> 1;
-    f32x16 acc[1][1];
-    auto acc_init = [&](int boff) {
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 bb = sm[DAS_BIAS + boff + mt * 8 + 2 * g4 + h];
-            acc[0][0][4 * g4] = bb.x; acc[0][0][4 * g4 + 1] = bb.y; acc[0][0][4 * g4 + 2] = bb.z; acc[0][0][4 * g4 + 3] = bb.w;
-        }
-    };
     {   // ---- layer 1 (Winograd, wino_l1) for the 16 tiles of tile rows p, p + 1 (image rows 2p .. 2p + 3): wave w owns output row
         // r = w & 1 of every tile (lanes j and j + 16 hold the same tile; the upper half is not stored)
         const int r = w & 1, n = j & 15;
@@ -361,27 +507,30 @@ __global__ void __launch_bounds__(256, 2) k_dec_a_s(const DecAArgs a) {
             }
     }
     __syncthreads();
-    // ---- layer 2 (stride 2) for the input rows 2p, 2p + 1: two output parities per wave
-    float* Y = a.y2 + (size_t)img * (32 * 32 * 64);
-    const int vrows = min(4, 16 - 2 * p);            // layer-1 rows of the patch that exist in the image
-#pragma unroll 1
-    for (int k = 0; k < 2; ++k) {
-        const int par = (w & 1) ? (k ? 2 : 1) : (k ? 3 : 0);
-        const int ph = par >> 1, pw = par & 1;
-        acc_init(16);
-        tap_loop_pd<1, 1, 2>(acc, (1 + ph) * (1 + pw), W2, sl1, h, ConvT2Addr<1, DA_PS>{ph, pw, j >> 4, 0, j & 15, vrows, 16, DAS_L1}, PackedWIdx{2, 8, mt});
-        float4* yp = reinterpret_cast<float4*>(Y) + (size_t)par * 4096 + ((2 * p) * 16 + j) * 2 + h;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            float4 v;
-            v.x = relu_bits(acc[0][0][4 * g4 + 0]); v.y = relu_bits(acc[0][0][4 * g4 + 1]);
-            v.z = relu_bits(acc[0][0][4 * g4 + 2]); v.w = relu_bits(acc[0][0][4 * g4 + 3]);
-            yp[(mt * 4 + g4) * 512] = v;
-        }
+    // ---- layer 2 (F(2, 2), f22_l2) for the block row p (input rows 2p, 2p + 1, x_2 from row 2p + 2): wave w contracts channel tile w.
+    // A block row has 8 blocks: lanes n >= 8 repeat the blocks of lanes n - 8 and are not stored (half of the MFMA tile is idle)
+    {
+        const int n = lane & 15, g = lane >> 4, bv = n & 7;
+        const int zq = DAS_L1 * DA_PS + g;
+        F22Nb nb;
+        nb.xb = 2 * bv * DA_PS + g;
+        nb.c2[0] = bv == 7 ? zq : nb.xb + 2 * DA_PS;
+        nb.c2[1] = bv == 7 ? zq : nb.xb + 18 * DA_PS;
+        nb.c2[2] = (bv == 7 || p == 7) ? zq : nb.xb + 34 * DA_PS;
+        nb.r2 = p == 7 ? zq : nb.xb + 32 * DA_PS;
+        const unsigned ln = (unsigned)lane * 16u;
+        const unsigned yoff = (unsigned)(((32 * p + 2 * bv + (g >> 1)) * 2 + (g & 1)) * 16);
+        const __amdgpu_buffer_rsrc_t yr = wrsrc(a.y2 + (size_t)img * (32 * 32 * 64));
+        const __amdgpu_buffer_rsrc_t wr = wrsrc(W2 + w * 256);
+        f32x4 aq[F22_PD][5], acc2[16];
+        f22_l2_first(aq, wr, 0, ln);
+        const f32x4 bias4 = reinterpret_cast<const f32x4*>(sm)[DAS_BIAS + 16 + 4 * w + g];
+        f22_l2(acc2, aq, wr, 0, ln, bias4, reinterpret_cast<const f32x4*>(sl1), nb);
+        f22_l2_store(acc2, yr, yoff, w, n < 8);
     }
 }
 
-constexpr size_t DA_LDS_BYTES = (257 * DA_PS + 33) * sizeof(float4);
+constexpr size_t DA_LDS_BYTES = (DA_BIAS + 33) * sizeof(float4);
 int init_dec_b_kernels();
 // kernels that need more than the default 64 KiB of dynamic LDS: set once per device (called from efe_create)
 int init_decoder_kernels() {
@@ -397,61 +546,9 @@ void launch_dec_a(const DecAArgs& a, hipStream_t st) {
     }
     const size_t lds = DA_LDS_BYTES;
     const int grid = a.rows < 512 ? a.rows : 512;         // persistent: 2 workgroups per CU
-    hipLaunchKernelGGL(k_dec_a, dim3(grid), dim3(256), lds, st, a);       // 0.87 of the fp32 MFMA peak alone (19200 images)
+    hipLaunchKernelGGL(k_dec_a, dim3(grid), dim3(256), lds, st, a);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------------------------
-// ConvT3 (ConvTranspose2d(64, 32, 3, s2, p1, op1)) by per-parity minimal filtering F(2, 2).  Along one dimension, with taps g0, g1, g2
-// (oh = 2 ih - 1 + kh) and x[32] = 0, output 2m = x[m] g1 and 2m + 1 = x[m] g2 + x[m + 1] g0.  For an input pair block u
-// (x0 = x[2u], x1 = x[2u + 1], x2 = x[2u + 2]) the views d0 = x0 - x1, d1 = x1, d2 = x2 - x1 give the four outputs 4u .. 4u + 3 from
-// five products instead of six:
-//     P1 = d0 g1 -> 0    P2 = d1 g1 -> 0, 2    P3 = d0 g2 -> 1    P4 = d1 (g0 + g2) -> 1, 3    P5 = d2 g0 -> 3
-// In 2D (the outer product of this table with itself) a 2 x 2 input block needs 25 products instead of 36: 9 views d_a (x) d_b and 16
-// weight matrices U = w_r (x) w_c, w in {g1, g2, g0 + g2, g0}, formed in fp64 at commit time and rounded once (engine.hip).  The 9
-// products with one output in both dimensions chain straight into that output; the other 16 run in a short-lived accumulator that is
-// then added into its 2 or 4 outputs.  (The 1D table f22_* is in kernels.h: engine.hip forms the weights from it.)
-//
-// compile-time loop: f(std::integral_constant<int, 0>{}) .. f(std::integral_constant<int, N - 1>{})
-template <class F, int... I> __device__ __forceinline__ void static_for_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_(f, std::make_integer_sequence<int, N>{}); }
-
-// The schedule of k_dec_b4: six groups of products that share their views (every B fragment read feeds 4 or 5 independent chains):
-//   G0 V(0,0): (P1|P3) x (P1|P3)  direct      G1 V(0,1): (P1|P3) x (P2|P4)      G2 V(1,0): (P2|P4) x (P1|P3)      G3 V(1,1): (P2|P4) x (P2|P4)
-//   G4 V(1,2), V(2,1), V(2,2): (P2|P4) x P5, P5 x (P2|P4), P5 x P5 (direct)      G5 V(0,2), V(2,0): (P1|P3) x P5, P5 x (P1|P3)  direct
-// w3_prod(G, c) = 5 pr + pc of chain c of group G (rows x columns)
-__host__ __device__ constexpr int w3_nch(int G) { return G == 4 ? 5 : 4; }
-__host__ __device__ constexpr int w3_prod(int G, int c) {
-    return G < 4 ? 5 * ((G >> 1) + 2 * (c >> 1)) + (G & 1) + 2 * (c & 1)
-         : G == 4 ? (c < 2 ? 5 * (1 + 2 * c) + 4 : c < 4 ? 20 + 1 + 2 * (c - 2) : 24)
-                  : (c < 2 ? 5 * (2 * c) + 4 : 20 + 2 * (c - 2));
-}
-__host__ __device__ constexpr bool w3_direct(int pp) { return f22_o1(pp / 5) < 0 && f22_o1(pp % 5) < 0; }
-__host__ __device__ constexpr int w3_view(int pp) { return 3 * f22_view(pp / 5) + f22_view(pp % 5); }
-__host__ __device__ constexpr int w3_mat(int pp) { return 4 * f22_wt(pp / 5) + f22_wt(pp % 5); }
-__host__ __device__ constexpr bool w3_hits(int pp, int o) {          // product pp feeds output o = 4 orow + ocol of the block
-    const int r = o >> 2, c = o & 3, pr = pp / 5, pc = pp % 5;
-    return (r == f22_o0(pr) || r == f22_o1(pr)) && (c == f22_o0(pc) || c == f22_o1(pc));
-}
-// output o already holds a value when chain c of group G reaches it (a group's direct chains run before its temporaries are added,
-// those in chain order): otherwise the chain starts from the bias (direct: the C operand of its first MFMA; temporary: bias + M)
-__host__ __device__ constexpr bool w3_seen(int G, int c, int o) {
-    for (int g = 0; g < G; ++g)
-        for (int k = 0; k < w3_nch(g); ++k) if (w3_hits(w3_prod(g, k), o)) return true;
-    if (!w3_direct(w3_prod(G, c)))
-        for (int k = 0; k < w3_nch(G); ++k)
-            if ((w3_direct(w3_prod(G, k)) || k < c) && w3_hits(w3_prod(G, k), o)) return true;
-    return false;
-}
-__host__ __device__ constexpr bool w3_uses_view(int G, int vi) {
-    for (int k = 0; k < w3_nch(G); ++k) if (w3_view(w3_prod(G, k)) == vi) return true;
-    return false;
-}
-__host__ __device__ constexpr bool f22_in(int a, int r) { return a == 0 ? r <= 1 : (a == 1 ? r == 1 : r >= 1); }   // view a reads x_r
-__host__ __device__ constexpr bool w3_reads(int G, int r, int c) {   // input pixel (r, c) of the 3 x 3 block neighbourhood
-    for (int vi = 0; vi < 9; ++vi) if (w3_uses_view(G, vi) && f22_in(vi / 3, r) && f22_in(vi % 3, c)) return true;
-    return false;
-}
 
 // k_dec_b4: ConvT3 + ReLU + ConvT4 + sigmoid + the per-image sums.  One workgroup (4 waves) per image walks 8 strips of SR = 4 input
 // rows (+ 1 halo row) staged in LDS.  Wave w owns block row u = w >> 1 of the strip (input rows 2u .. 2u + 2, y3 rows 4u .. 4u + 3) and

@@ -1203,8 +1203,16 @@ int efe_commit_weights(efe_ctx* ctx) {
             HIPCHK(hipMemcpy(ctx->dec_ct[2].Wp, p.data(), p.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
-        if (upload_packed(ctx, ctx->dec_ct[i], 9, Cout, tci[i],
-                          [&](int t, int co, int ci) { return W[((size_t)ci * Cout + co) * 9 + t]; }, b->data.data(), nullptr)) return 1;
+        {   // po_net.15 (layer 2 of k_dec_a / k_dec_a_s, decoder.hip f22_l2): the same 16 matrices for 64 output channels, packed
+            // [U][channel tile ct][chunk kc][lane][s] = U[16 ct + (lane & 15)][16 kc + 4 (lane >> 4) + s]
+            const std::vector<float> U = convt_s2_f22_weights(W, 64, 64);
+            if (upload_packed(ctx, ctx->dec_ct[1], 16, 64, 64, [](int, int, int) { return 0.f; }, b->data.data(), nullptr)) return 1;   // buffer + bias
+            std::vector<float> p(U.size());
+            for (int m = 0; m < 16; ++m) for (int ct = 0; ct < 4; ++ct) for (int kc = 0; kc < 4; ++kc) for (int lane = 0; lane < 64; ++lane)
+                for (int s_ = 0; s_ < 4; ++s_)
+                    p[((((size_t)m * 4 + ct) * 4 + kc) * 64 + lane) * 4 + s_] = U[((size_t)m * 64 + 16 * ct + (lane & 15)) * 64 + 16 * kc + 4 * (lane >> 4) + s_];
+            HIPCHK(hipMemcpy(ctx->dec_ct[1].Wp, p.data(), p.size() * 4, hipMemcpyHostToDevice));
+        }
     }
     {
         const HostTensor* w = need(ctx, "down.po_net.19.weight", {32, 1, 3, 3});

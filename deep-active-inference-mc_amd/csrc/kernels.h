@@ -106,7 +106,7 @@ struct GemmArgs {
 struct DecAArgs {
     const float* x4; float* y2;
     const float* w1; const float* b1;   // Winograd F(2x2,3x3) weights packed [16 xi][2][8][64][4] (decoder.hip wino_l1), bias [64]
-    const float* w2; const float* b2;
+    const float* w2; const float* b2;   // F(2, 2) weights packed [16 U][4 channel tiles][4 chunks][64][4] (engine.hip; decoder.hip f22_l2), bias [64]
     int rows;
     RowMask live;
     int parts;            // 1 = persistent, one image per workgroup pass; 8 = small launches, an image over eight workgroups (k_dec_a_s)

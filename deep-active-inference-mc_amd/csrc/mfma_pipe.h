@@ -73,32 +73,9 @@ __device__ __forceinline__ float dpp_ror15(float x) { return __builtin_bit_cast(
 // Wl is the UNIFORM base of the packed weights: the fragment address is (scalar base + scalar tap/chunk offset) + lane, i.e.
 // global_load with an SGPR base and one 32-bit lane offset.  A per-lane 64-bit pointer instead makes hipcc materialise a
 // VGPR pair per distinct offset (dozens, hoisted out of the loops and spilled).
-struct ConvWIdx {          // packed conv weights [tap][MT tiles][8 chunks][64 lanes]
-    template <int MT> __device__ __forceinline__ static size_t at(int wt, int mt, int kc) { return (size_t)((wt * MT + mt) * 8 + kc) * 64; }
-};
 struct DenseWIdx {         // packed dense weights [feature tile][32 chunks][64 lanes]; "tap" t = 64-channel slice of K = 256
     int mt0;
     template <int MT> __device__ __forceinline__ size_t at(int wt, int mt, int kc) const { return (size_t)((mt0 + mt) * 32 + wt * 8 + kc) * 64; }
-};
-
-// tap -> LDS source of the stride-2 transposed convs (oh = 2*ih - 1 + kh: even output rows use kh=1 (ih=a); odd rows use
-// kh=0 (ih=a+1) and kh=2 (ih=a)); `rows`/`cols` bound the staged image, `zero` is the zero-pixel slot.
-// PS = float4 slots per staged pixel: 16 = XOR-swizzled quads (swz), 17 = padded slots (no swizzle key)
-template <int NT, int PS = 16>
-struct ConvT2Addr {
-    int ph, pw, row0, row_step, col, rows, cols, zero;
-    __device__ __forceinline__ void operator()(int t, int (&bs)[NT], int (&sw)[NT], int& wt) const {
-        const int th = t / (1 + pw), tw = t - th * (1 + pw);
-        const int kh = ph ? (th ? 2 : 0) : 1, da = (ph && th == 0) ? 1 : 0;
-        const int kw = pw ? (tw ? 2 : 0) : 1, db = (pw && tw == 0) ? 1 : 0;
-        wt = kh * 3 + kw;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int sy = row0 + row_step * nt + da, sx = col + db;
-            const int sp = (sy < rows && sx < cols) ? sy * cols + sx : zero;
-            bs[nt] = sp * PS; sw[nt] = PS == 16 ? (sp & 15) : 0;
-        }
-    }
 };
 
 // PD = prefetch distance of the weight (A) fragments in chunks: they come from L2 (~500-900 cycles under load), and a
@@ -172,15 +149,6 @@ __device__ __forceinline__ void tap_loop(f32x16 (&acc)[MT][NT], const int ntaps,
     p.run(acc, ntaps, Wl, sm, h, addr, widx);
 }
 
-
-// explicit prefetch distance (kernels with 4 waves per SIMD and a tight VGPR budget use PD = 1 for narrow tiles too)
-template <int MT, int NT, int PD, class AddrFn, class WIdx>
-__device__ __forceinline__ void tap_loop_pd(f32x16 (&acc)[MT][NT], const int ntaps, const float4* __restrict__ Wl,
-                                            const float4* sm, const int h, AddrFn addr, WIdx widx) {
-    TapPipe<MT, NT, 8, PD> p;
-    p.begin(Wl, sm, h, addr, widx);
-    p.run(acc, ntaps, Wl, sm, h, addr, widx);
-}
 
 template <int MT, int NT, int KC, class AddrFn, class WIdx>
 __device__ __forceinline__ void tap_loop_kc(f32x16 (&acc)[MT][NT], const int ntaps, const float4* __restrict__ Wl,
