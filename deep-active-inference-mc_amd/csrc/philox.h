@@ -12,6 +12,10 @@
 //   normals : element k = Box-Muller lane (k & 3) of counter blk = k >> 2
 //   uniform : word 0 of blk 0
 //
+// Every counter word is a uint32_t and so is the arithmetic that feeds it: global_row = row_offset + r, stage = stage0 + t and the
+// simulation's trajectory row (row_offset + e) * depth + t are defined modulo 2^32; pass and sample are 16 bits each of the stream word.
+// (tests/test_noise_keys_cpu.py on the mirror, tests/test_noise_keys_gpu.py on every draw site.)
+//
 // The CPU mirror used by the parity tests is oracle/philox.py (checked against Random123 known answers).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -333,7 +333,7 @@ class OracleModel:
         s0_temp = qs0_mean if calc_mean else qs0
         po1 = None
         for t in range(steps):
-            G, terms, s1, ps1_mean, po1 = self.calculate_G(s0_temp, pi, samples, stage0 + t, ro)
+            G, terms, s1, ps1_mean, po1 = self.calculate_G(s0_temp, pi, samples, PX.u32(stage0 + t), ro)
             for i in range(3):
                 sum_terms[i] += terms[i]
             sum_G += G
@@ -350,9 +350,9 @@ class OracleModel:
         po1 = None
         for t in range(steps):
             if calc_mean:
-                G, terms, ps1_mean, po1 = self.calculate_G_mean(s0_temp, self.pi_one_hot, stage0 + t, ro)
+                G, terms, ps1_mean, po1 = self.calculate_G_mean(s0_temp, self.pi_one_hot, PX.u32(stage0 + t), ro)
             else:
-                G, terms, s1, ps1_mean, po1 = self.calculate_G(s0_temp, self.pi_one_hot, samples, stage0 + t, ro)
+                G, terms, s1, ps1_mean, po1 = self.calculate_G(s0_temp, self.pi_one_hot, samples, PX.u32(stage0 + t), ro)
             for i in range(3):
                 sum_terms[i] += terms[i]
             sum_G += G
@@ -376,7 +376,7 @@ class OracleModel:
     # ---- mcts_step_simulate (torchmodel.py:354-393) ------------------------
     def mcts_step_simulate(self, starting_s, depth, use_means, stage, episode=0):
         """One episode.  Noise rows: habit/transition steps use global row `episode`
-        (sample = t); the trajectory batch uses global rows episode*depth + t."""
+        (sample = t); the trajectory batch uses global rows episode*depth + t, in the engine's uint32 arithmetic (fused.hip: k_sim_chain)."""
         s0 = torch.zeros((depth, self.s_dim))
         ps1 = torch.zeros((depth, self.s_dim))
         ps1_mean = torch.zeros((depth, self.s_dim))
@@ -397,5 +397,5 @@ class OracleModel:
             ps1_logvar[t] = n_logvar[0]
             if t + 1 < depth:
                 s0[t + 1] = n_mean[0] if use_means else n_ps1[0]
-        Gt = self.calculate_G_given_trajectory(s0, ps1, ps1_mean, ps1_logvar, pi0, stage, episode * depth)
+        Gt = self.calculate_G_given_trajectory(s0, ps1, ps1_mean, ps1_logvar, pi0, stage, PX.u32(episode * depth))
         return torch.mean(Gt).item(), pi0, Qpi_t_to_return

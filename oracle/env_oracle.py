@@ -14,8 +14,9 @@ BASES = np.array([1, 3, 6, 40, 32, 32], dtype=np.float32)
 
 def env_u(seed, game, stage, blk):
     k0, k1 = PX._key(seed)
-    x0, _, _, _ = PX.philox4x32_10(np.uint64(blk) | (np.uint64(TAG_ENV) << np.uint64(16)), np.uint64(game),
-                                   np.uint64(PX.stream_id(PASS_ENV, 0)), np.uint64(stage), k0, k1)
+    # game (= game_offset + e) and stage modulo 2^32: the engine's uint32 arithmetic (k_env_*)
+    x0, _, _, _ = PX.philox4x32_10(np.uint64(blk) | (np.uint64(TAG_ENV) << np.uint64(16)), np.uint64(PX.u32(game)),
+                                   np.uint64(PX.stream_id(PASS_ENV, 0)), np.uint64(PX.u32(stage)), k0, k1)
     return PX._u01(np.asarray(x0, dtype=np.uint32))
 
 

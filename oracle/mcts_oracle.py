@@ -7,7 +7,8 @@ propagation (an unvisited edge gives Q = 0/0) and argmax tie-breaking are torch'
 
 Noise addressing (what the fixtures of oracle/make_golden.py and the HIP planners use): one `stage` per engine-level
 call -- root encode, every expansion, every simulation -- starting at `stage0`; episode e draws at global rows
-e (root encode, simulation steps), 4e + a (expansion rows) and e * depth + t (trajectory rows).
+e (root encode, simulation steps), 4e + a (expansion rows) and e * depth + t (trajectory rows), each -- like the stage counter --
+modulo 2^32 (the engine's uint32 arithmetic, kernels.h: global_row / group_key).
 
 Pinned against the shimmed reference planner by tests/test_oracle_golden.py (fixtures mcts_means, mcts_samples,
 mcts_prior, mcts_batch_s10)."""
@@ -97,15 +98,15 @@ def plan(orc, frame, params, stage0, episode=0):
 
     def take():
         stage[0] += 1
-        return stage[0] - 1
+        return PX.u32(stage[0] - 1)
 
     def expand(node):
         """mcts.py:64-86"""
         pi_hot = torch.eye(A)
         if params.use_means:
-            G, _, ps_next, _ = orc.calculate_G_mean(node.s, pi_hot, take(), A * episode)
+            G, _, ps_next, _ = orc.calculate_G_mean(node.s, pi_hot, take(), PX.u32(A * episode))
         else:
-            G, _, ps_next, _, _ = orc.calculate_G(node.s, pi_hot, params.samples, take(), A * episode)
+            G, _, ps_next, _, _ = orc.calculate_G(node.s, pi_hot, params.samples, take(), PX.u32(A * episode))
         node.W -= G
         node.N += 1.0
         for a in range(A):

@@ -12,6 +12,8 @@ of every draw, so the result does not depend on batching or on GPU count.
 
 Key      = (seed & 0xffffffff, seed >> 32)
 Counter  = (blk | tag << 16, global_row, pass << 16 | sample, stage)
+           every word 32 bits: global_row = row_offset + r and stage are taken modulo 2^32, pass and sample modulo 2^16 -- the
+           engine's uint32_t arithmetic (`u32`, `_rows`; tests/test_noise_keys_cpu.py)
 
 * dropout mask of a layer with F features: feature f of row r is KEPT iff
   bit (f & 31) of output word ((f >> 5) & 3) of counter blk = f >> 7 is 1
@@ -78,15 +80,26 @@ def stream_id(pas, sample):
     return ((int(pas) & 0xFFFF) << 16) | (int(sample) & 0xFFFF)
 
 
+def u32(x):
+    """x reduced modulo 2^32: the engine keeps row, stage and stream in uint32_t (csrc/philox.h: noise_words), so a row range that
+    straddles 2^32, `stage0 + t` past 0xFFFFFFFF and `episode * depth + t` all wrap.  The row and stage words go through here (`stream_id` masks its own two fields; blk | tag is small)."""
+    return int(x) & 0xFFFFFFFF
+
+
+def _rows(rows, row_offset):
+    """global rows row_offset .. row_offset + rows - 1 as the engine's uint32 arithmetic sees them (kernels.h: global_row)"""
+    return (np.arange(rows, dtype=np.uint64) + np.uint64(u32(row_offset))) & MASK32
+
+
 def dropout_mask(seed, tag, rows, n_feat, pas, sample, stage, row_offset=0):
     """float32 [rows, n_feat] of {0., 2.}: the x*mask*2 multiplier of nn.Dropout(0.5)
      for global rows row_offset..row_offset+rows-1."""
     k0, k1 = _key(seed)
     nblk = (n_feat + 127) // 128
     blk = np.arange(nblk, dtype=np.uint64)[None, :]
-    row = (np.arange(rows, dtype=np.uint64) + np.uint64(row_offset))[:, None]
+    row = _rows(rows, row_offset)[:, None]
     w = philox4x32_10(blk | (np.uint64(tag) << np.uint64(16)), row,
-                      np.uint64(stream_id(pas, sample)), np.uint64(stage), k0, k1)
+                      np.uint64(stream_id(pas, sample)), np.uint64(u32(stage)), k0, k1)
     words = np.stack(w, axis=-1)                      # [rows, nblk, 4]
     bits = (words[..., None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)  # [rows,nblk,4,32]
     bits = bits.reshape(rows, nblk * 128)[:, :n_feat]
@@ -103,9 +116,9 @@ def normals(seed, rows, n, pas, sample, stage, row_offset=0, tag=TAG_EPS):
     k0, k1 = _key(seed)
     nblk = (n + 3) // 4
     blk = np.arange(nblk, dtype=np.uint64)[None, :]
-    row = (np.arange(rows, dtype=np.uint64) + np.uint64(row_offset))[:, None]
+    row = _rows(rows, row_offset)[:, None]
     x0, x1, x2, x3 = philox4x32_10(blk | (np.uint64(tag) << np.uint64(16)), row,
-                                   np.uint64(stream_id(pas, sample)), np.uint64(stage), k0, k1)
+                                   np.uint64(stream_id(pas, sample)), np.uint64(u32(stage)), k0, k1)
     two_pi = np.float32(6.283185307179586)
     out = np.empty((rows, nblk, 4), dtype=np.float32)
     for lane, (a, b) in enumerate(((x0, x1), (x2, x3))):
@@ -120,9 +133,9 @@ def normals(seed, rows, n, pas, sample, stage, row_offset=0, tag=TAG_EPS):
 def uniforms(seed, rows, pas, sample, stage, row_offset=0, tag=TAG_ACT):
     """float32 [rows] uniforms in (0,1) for inverse-CDF categorical sampling."""
     k0, k1 = _key(seed)
-    row = np.arange(rows, dtype=np.uint64) + np.uint64(row_offset)
+    row = _rows(rows, row_offset)
     x0, _, _, _ = philox4x32_10(np.uint64(tag) << np.uint64(16), row,
-                                np.uint64(stream_id(pas, sample)), np.uint64(stage), k0, k1)
+                                np.uint64(stream_id(pas, sample)), np.uint64(u32(stage)), k0, k1)
     return _u01(x0)
 
 
