@@ -620,7 +620,9 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
         for (int rr = 0; rr < 4; ++rr) w4a[rr] = (kh < 3 && kw < 3) ? a.w4[(3 * kh + kw) * 32 + 16 * hf + 4 * g + rr] : 0.f;
     }
 
-    const float4* X = reinterpret_cast<const float4*>(a.y2) + (size_t)img * (32 * 32 * 16);
+    // the image's y2 through a buffer resource over exactly its 256 KiB: a row below the image is requested at an out-of-range offset
+    // and the hardware returns zeros (the halo row of the last strip)
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.y2) + (size_t)img * (32 * 32 * 64), 0, 32 * 32 * 64 * 4, 0x00020000);
     // packed U fragments [16 matrices][2 channel halves][4 chunks][64 lanes] (engine.hip): the channel half is folded into the base
     const __amdgpu_buffer_rsrc_t wr = wrsrc(a.w3 + (size_t)hf * 4 * 64 * 4);
     const unsigned ln = (unsigned)lane * 16u;
@@ -629,10 +631,21 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     float part = 0.f;
     f32x4 pf[NPF];
     f32x4* smv = reinterpret_cast<f32x4*>(sm);
-    const f32x4* Xv = reinterpret_cast<const f32x4*>(X);
-    auto y2_at = [&](int iy, int idx) -> size_t { return (size_t)(((iy & 1) * 16 + ((idx & 511) >> 5)) * 512 + (iy >> 1) * 32 + (idx & 31)); };
+    // Input strip sn (rows SR sn .. SR sn + SR, the last one the halo) in NPF pieces per thread: piece it of thread tl is row it >> 1,
+    // 16-byte word (it & 1) 256 + tl of the row's 512.  y2 is [row parity][8 channel groups][16 x 16 positions][2 quads]: the word is
+    // position (row >> 1, (tl & 31) >> 1), channel group 8 (it & 1) + (tl >> 5), quad tl & 1 -- a lane offset, a constant per piece and
+    // 1 KiB per strip (SR = 4 rows = two rows of positions).  Row 32 (the halo of strip 7) is out of range: the lanes' offsets get bit 31.
+    auto prefetch = [&](int sn, int tl) {
+        const unsigned lo = (unsigned)(((tl >> 5) * 512 + (tl & 31)) * 16);
+        const unsigned lh = lo | (sn == NS - 1 ? 0x80000000u : 0u);
 #pragma unroll
-    for (int it = 0; it < NPF; ++it) { const int idx = it * NTHR + tid; pf[it] = Xv[y2_at(min(SR * s_lo + (idx >> 9), 31), idx)]; }
+        for (int it = 0; it < NPF; ++it) {
+            const int rl = it >> 1;
+            const unsigned pc = (unsigned)((((rl & 1) * 16 + (it & 1) * 8) * 512 + (rl >> 1) * 32) * 16);
+            pf[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, rl == SR ? lh : lo, pc + (unsigned)sn * 1024u, 0));
+        }
+    };
+    prefetch(s_lo, tid);
 
     // this lane's block neighbourhood: pixel (2u + i, 2v + jj), quad 4 kc + g at xb + (33 i + jj) * DB_PS + 4 kc (all immediates)
     const int xb = (2 * u * DB_RP + 2 * v) * DB_PS + g;
@@ -641,8 +654,8 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     // then the rows in the same form
     auto view = [&](const f32x4 (&x)[9], int vi) -> f32x4 {
         const int va = vi / 3, vb = vi % 3;
-        auto cv = [&](int i) -> f32x4 { return vb == 0 ? x[3 * i] - x[3 * i + 1] : (vb == 1 ? x[3 * i + 1] : x[3 * i + 2] - x[3 * i + 1]); };
-        return va == 0 ? cv(0) - cv(1) : (va == 1 ? cv(1) : cv(2) - cv(1));
+        auto cv = [&](int i) -> f32x4 { return vb == 0 ? sub4(x[3 * i], x[3 * i + 1]) : (vb == 1 ? x[3 * i + 1] : sub4(x[3 * i + 2], x[3 * i + 1])); };
+        return va == 0 ? sub4(cv(0), cv(1)) : (va == 1 ? cv(1) : sub4(cv(2), cv(1)));
     };
 
     // ---- gather of output row oh (lane = column): out = b4 + H[0][oh + 1] + H[1][oh] + H[2][oh - 1] (source row r contributes to
@@ -668,7 +681,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
             const int tr = oh + 1 - kh;
-            val += (tr >= 0 && tr <= 63) ? gh[q][2 * kh] + gh[q][2 * kh + 1] : 0.f;
+            val = add1(val, (tr >= 0 && tr <= 63) ? add1(gh[q][2 * kh], gh[q][2 * kh + 1]) : 0.f);
         }
         // hardware exp2 / rcp / log2 (v_exp_f32, v_rcp_f32, v_log_f32: 1 ulp each) instead of the libm expansions: ~14 instead of ~60 VALU
         // instructions per pixel, each of which costs ~19 cycles of wave time beside the other wave's MFMA stream; the image stays within
@@ -693,17 +706,10 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
             (po + oh * 64)[owl] = gpr[q];
         }
     };
-    auto prefetch = [&](int sn, int tl) {
-#pragma unroll
-        for (int it = 0; it < NPF; ++it) {
-            const int idx = it * NTHR + tl;
-            const int grow = min(SR * sn + (idx >> 9), 31);
-            pf[it] = Xv[y2_at(grow, idx)];
-        }
-    };
 
     // a quarter is complete: park the thread's partial sum (one LDS write; the reductions of all quarters run once, behind the last strip)
     auto fold = [&](int k) { sq[k * NTHR + tid] = part; part = 0.f; };
+    float* const sHw = sH + g * 64 + 4 * v;               // this lane's place in an H plane of its tap row
     int hb = 0, hbp = 0;                                   // H-ring slots of y3 rows 2 SR s (this strip's first) and 2 SR (s - 1)
     for (int s = s_lo; s < s_hi; ++s) {
         // per-strip laundering of the thread index: stops hipcc hoisting the ~15 staging / prefetch addresses out of the strip loop
@@ -711,13 +717,12 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
         int tl = tid; asm volatile("" : "+v"(tl));
         const bool gq = parts == 1 ? true : s == 2 * qtr + 1;   // (uniform) the previous strip's rows are this workgroup's to gather
         const int oh0 = 2 * SR * (s - 1) - 1 + w, oh1 = oh0 + NW;         // this wave's two output rows of the previous strip
-        // stage the strip: y2 is [row parity][8 channel groups][16 x 16 positions][2 quads], i.e. pixel column 2 (wi >> 1) + (seg >> 3)
+        // stage the strip: piece it is row it >> 1, pixel column 2 ((tl & 31) >> 1) + (it & 1), quad 2 (tl >> 5) + (tl & 1) -- one address
+        // register, the pieces at immediate offsets (the row below the image arrived as zeros)
+        {
+            f32x4* const sp = smv + ((tl & 31) >> 1) * (2 * DB_PS) + 2 * (tl >> 5) + (tl & 1);
 #pragma unroll
-        for (int it = 0; it < NPF; ++it) {
-            const int idx = it * NTHR + tl;
-            const int rl = idx >> 9, seg = (idx & 511) >> 5, wi = idx & 31;
-            const int ix = 2 * (wi >> 1) + (seg >> 3), c4 = 2 * (seg & 7) + (wi & 1);
-            smv[(rl * DB_RP + ix) * DB_PS + c4] = (SR * s + rl < 32) ? pf[it] : (f32x4)(0.f);
+            for (int it = 0; it < NPF; ++it) sp[((it >> 1) * DB_RP + (it & 1)) * DB_PS] = pf[it];
         }
         f32x4 aq[5];                                       // the strip's first weight fragments: in flight across the barrier
 #pragma unroll
@@ -762,8 +767,8 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
                     if constexpr (!w3_direct(PP))
                         static_for<16>([&](auto o) {
                             if constexpr (w3_hits(PP, o)) {
-                                if constexpr (w3_seen(G, c, o)) acc[o] = acc[o] + tq[c];
-                                else acc[o] = bias4 + tq[c];
+                                if constexpr (w3_seen(G, c, o)) acc[o] = add4(acc[o], tq[c]);
+                                else acc[o] = add4(bias4, tq[c]);
                             }
                         });
                 });
@@ -793,13 +798,13 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
                     T[oc] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4a[e], acc[4 * orow + oc][e], e == 0 ? zero4 : T[oc], 0, 0, 0);
             // T[oc][kw] = tap (kh = g, kw) at column 4 v + oc; H(c) = (T[kw 0] at c + 1 + T[kw 1] at c) + T[kw 2] at c - 1
             f32x4 hv;
-            hv[0] = (T[1][0] + T[0][1]) + dpp_shr1_zero(T[3][2]);
-            hv[1] = (T[2][0] + T[1][1]) + T[0][2];
-            hv[2] = (T[3][0] + T[2][1]) + T[1][2];
-            hv[3] = (dpp_shl1_zero(T[0][0]) + T[3][1]) + T[2][2];
+            hv[0] = add1(add1(T[1][0], T[0][1]), dpp_shr1_zero(T[3][2]));
+            hv[1] = add1(add1(T[2][0], T[1][1]), T[0][2]);
+            hv[2] = add1(add1(T[3][0], T[2][1]), T[1][2]);
+            hv[3] = add1(add1(dpp_shl1_zero(T[0][0]), T[3][1]), T[2][2]);
             int hsw = hb + 4 * u + orow;                   // ring slot of this wave's y3 row 2 SR s + 4 u + orow
             hsw = hsw >= DB_YROWS ? hsw - DB_YROWS : hsw;
-            if (g < 3) *reinterpret_cast<f32x4*>(sH + ((hsw * 2 + hf) * 3 + g) * 64 + 4 * v) = hv;
+            if (g < 3) *reinterpret_cast<f32x4*>(sHw + (hsw * 2 + hf) * (3 * 64)) = hv;     // (the slot is uniform: a scalar offset to the lane's address)
         }
         __syncthreads();
         if (gq) { g_store(oh0, 0); g_store(oh1, 1); }     // the deferred rows' pixels (stores behind the prefetch loads)
@@ -821,14 +826,14 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     // Q_k = the xor-tree sum over the 64 lanes of ((wave 0 + wave 1) + (wave 2 + wave 3)) of the parked partials: wave k reduces quarter k
     if (w < (parts == 1 ? 4 : 1)) {
         const float* qk = sq + w * NTHR + lane;
-        float val = (qk[0] + qk[64]) + (qk[128] + qk[192]);
+        float val = add1(add1(qk[0], qk[64]), add1(qk[128], qk[192]));
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) val += __shfl_xor(val, o);
         if (lane == 0) sQ[w] = val;
     }
     __syncthreads();
     if (tid == 0) {
-        if (parts == 1) a.val[mg] = (sQ[0] + sQ[1]) + (sQ[2] + sQ[3]);
+        if (parts == 1) a.val[mg] = add1(add1(sQ[0], sQ[1]), add1(sQ[2], sQ[3]));
         else a.valq[(size_t)mg * 4 + qtr] = sQ[0];          // summed in the same association by the consumer (k_terms)
     }
 }

@@ -41,6 +41,27 @@ __device__ __forceinline__ float4 wfrag(__amdgpu_buffer_rsrc_t r, unsigned lane_
     return __builtin_bit_cast(float4, v);
 }
 
+// Single-lane fp32 add / subtract that hipcc does not pack: it lowers f32x4 + f32x4 (and SLP-packs neighbouring scalar adds, with
+// v_mov shuffles to pair the registers) to v_pk_add_f32, which costs more issue time than two v_add_f32 in the gaps of an MFMA stream.
+// The operation itself stays the compiler's -- an instruction written in inline asm would read MFMA results without the wait states
+// the hazard recogniser inserts for its own (a v_add_f32 in asm behind a v_mfma returned stale registers in the split decoder launch) -- and an empty
+// asm makes each result opaque, so that no two of them are one vector operation.  IEEE arithmetic either way: the same bits.
+#define EFE_OPAQUE(r) asm("" : "+v"(r))
+__device__ __forceinline__ float add1(float a, float b) { float r = a + b; EFE_OPAQUE(r); return r; }
+__device__ __forceinline__ float sub1(float a, float b) { EFE_OPAQUE(b); float r = a - b; EFE_OPAQUE(r); return r; }     // (the subtrahend too: with the result alone hipcc still paired subtractions of the F(2, 2) views)
+__device__ __forceinline__ f32x4 add4(f32x4 a, f32x4 b) {
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = add1(a[e], b[e]);
+    return r;
+}
+__device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = sub1(a[e], b[e]);
+    return r;
+}
+
 // max(x, 0) for fp32 as a signed-integer max of the bit pattern: negative floats (and -0, -NaN) are negative integers.
 __device__ __forceinline__ float relu_bits(float x) {
     const int b = __builtin_bit_cast(int, x);

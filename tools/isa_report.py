@@ -60,6 +60,21 @@ def kernels(lib=DEFAULT_LIB):
     return {p: res[n] for p, n in zip(pretty, names)}
 
 
+def disassembly(lib=DEFAULT_LIB):
+    """{demangled kernel name (arguments stripped): the instructions of its llvm-objdump listing, one per line}"""
+    res = {}
+    for img in code_objects(lib):
+        with tempfile.NamedTemporaryFile(suffix='.elf') as f:
+            f.write(img); f.flush()
+            txt = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn', f.name], capture_output=True, text=True).stdout
+        for m in re.finditer(r'^[0-9a-f]+ <([^>\n]+)>:\n(.*?)(?=^[0-9a-f]+ <[^>\n]+>:\n|\Z)', txt, re.M | re.S):
+            if not m.group(1).startswith('L'):            # (local labels of a kernel stay in its text)
+                res[m.group(1)] = res.get(m.group(1), '') + m.group(2)
+    names = list(res)
+    pretty = [re.sub(r'\(.*$', '', d).replace('efe::', '').replace('void ', '') for d in demangle(names)]
+    return {p: res[n] for p, n in zip(pretty, names)}
+
+
 if __name__ == '__main__':
     ks = kernels(sys.argv[1] if len(sys.argv) > 1 else DEFAULT_LIB)
     print(f'{"kernel":44s} {"vgpr":>5s} {"agpr":>5s} {"sgpr":>5s} {"vspill":>6s} {"sspill":>6s} {"scratch":>7s} {"lds":>7s} {"wg":>5s}')
