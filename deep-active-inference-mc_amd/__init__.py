@@ -12,3 +12,4 @@ from .env import Game, synthetic_sprite_bank  # noqa: F401
 from .parallel import episode_shard, gather_action_posteriors  # noqa: F401
 from . import loss  # noqa: F401
 from .loss import free_energy, FreeEnergy  # noqa: F401
+from .optim import Adam  # noqa: F401

@@ -13,7 +13,8 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_check_reward', 'efe_reparameterize', 'efe_mcts_select', 'efe_mcts_expand', 'efe_mcts_backprop', 'efe_mcts_stop',
            'efe_build_id', 'efe_reserve', 'efe_rollout_scratch_bytes', 'efe_arena_stats', 'efe_env_new_image', 'efe_create_cfg', 'efe_get_config', 'efe_get_device', 'efe_ctx_alive',
            'efe_calculate_g_rows', 'efe_simulate_rows', 'efe_mcts_step',
-           'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down']
+           'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down',
+           'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top']
 ABI_VERSION = 6
 
 
@@ -38,6 +39,10 @@ class EfeFeParams(C.Structure):
 
 FE_OUT_FIELDS = ('F_top', 'kl_pi', 'kl_pi_anal', 'Qpi', 'omega', 'F_mid', 'kl_s_mid', 'kl_s_mid_anal', 'ps1', 'ps1_mean', 'ps1_logvar',
                  'F_down', 'nlogpo1', 'kl_s', 'kl_s_anal', 'kl_naive', 'kl_naive_anal', 'po1', 'qs1', 's0', 'qs1_mean', 'qs1_logvar')
+
+
+class EfeAdamParams(C.Structure):
+    _fields_ = [('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('step', C.c_int64)]
 
 
 class EfeFeOut(C.Structure):
@@ -142,5 +147,11 @@ def load():
     lib.efe_loss_top.argtypes = [p, f32p, f32p, i, fop, p]; lib.efe_loss_top.restype = i
     lib.efe_loss_mid.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_loss_mid.restype = i
     lib.efe_loss_down.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_loss_down.restype = i
+    ap = C.POINTER(EfeAdamParams)
+    lib.efe_param_count.argtypes = [p, C.c_char_p]; lib.efe_param_count.restype = C.c_int64
+    lib.efe_get_weights.argtypes = [p, C.c_char_p, f32p, C.c_int64, p]; lib.efe_get_weights.restype = i
+    lib.efe_top_grad.argtypes = [p, f32p, f32p, i, f32p, f32p, p]; lib.efe_top_grad.restype = i
+    lib.efe_adam_step.argtypes = [p, C.c_char_p, f32p, f32p, f32p, ap, p]; lib.efe_adam_step.restype = i
+    lib.efe_train_top.argtypes = [p, f32p, f32p, i, f32p, f32p, f32p, ap, p]; lib.efe_train_top.restype = i
     _lib = lib
     return lib

@@ -5,6 +5,7 @@
 // (3) ONE batched encoder pass over rows x D x S,  (4) a per-row term combine.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -65,6 +66,10 @@ struct efe_ctx {
     int enc16_kc0 = 0;
     int64_t head_unfused = 0;      // option: 1 = layer-by-layer k_dense heads (A/B experiments)
     MlpW mid16{}, top16{};         // the same transition / habit weights packed for the fused 16x16x4 kernels (fused.hip)
+    // training (train.hip): the habit net's fp32 master copy (flat, the reference's parameters() order), its layer table on the host
+    // and on the device, and whether an optimiser step has made the device copy newer than `raw`
+    float* top_master = nullptr; TrainNet* top_net_dev = nullptr; TrainNet top_net{};
+    bool top_dirty = false;
     int64_t mid_unfused = 0;       // option: 1 = layer-by-layer k_dense transition (A/B experiments)
     float *enc_w1 = nullptr, *enc_b1 = nullptr, *dec_wf = nullptr;
     float dec_bf = 0.f;
@@ -240,6 +245,64 @@ int pack_linear16(efe_ctx* ctx, const float4*& Wout, const float*& bout, const s
     HIPCHK(hipMemcpy(dW, p.data(), p.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dB, bb.data(), bb.size() * 4, hipMemcpyHostToDevice));
     Wout = reinterpret_cast<const float4*>(dW); bout = dB;
+    return 0;
+}
+
+// ---- training tables (train.hip) ---------------------------------------------------------------------
+const char* const TOP_KEYS[3] = {"top.qpi_net.0", "top.qpi_net.2", "top.qpi_net.4"};
+int top_param_count(int A) { return 10 * 128 + 128 + 128 * 128 + 128 + A * 128 + A; }
+
+// the habit net's master copy and layer table, after its packed forms exist (efe_commit_weights): k_top_grad reads the master copy,
+// k_adam writes it and the packed copies
+int build_top_train(efe_ctx* ctx) {
+    const int A = ctx->pi_dim;
+    const int to[3] = {128, 128, A}, ti[3] = {10, 128, 128};
+    TrainNet nt{};
+    nt.nl = 3;
+    std::vector<float> flat;
+    for (int i = 0; i < 3; ++i) {
+        const HostTensor* w = need(ctx, std::string(TOP_KEYS[i]) + ".weight", {to[i], ti[i]});
+        const HostTensor* b = need(ctx, std::string(TOP_KEYS[i]) + ".bias", {to[i]});
+        if (!w || !b) return 1;
+        TrainLayer& L = nt.L[i];
+        L.in = ti[i]; L.out = to[i]; L.relu = i < 2; L.drop_tag = 0;
+        L.w_off = (int)flat.size(); flat.insert(flat.end(), w->data.begin(), w->data.end());
+        L.b_off = (int)flat.size(); flat.insert(flat.end(), b->data.begin(), b->data.end());
+        L.kc32 = ctx->top[i].cin / 8; L.kc16 = (ti[i] + 15) / 16;
+        L.Wp32 = ctx->top[i].Wp; L.b32 = ctx->top[i].bias;
+        L.Wp16 = const_cast<float*>(reinterpret_cast<const float*>(ctx->top16.w[i])); L.b16 = const_cast<float*>(ctx->top16.b[i]);
+    }
+    nt.P = (int)flat.size();
+    if (nt.P != top_param_count(A) || A > TRAIN_MAX_A) return ctx->fail("habit net outside the training kernels' limits");
+    if (!ctx->top_master) {
+        HIPCHK(hipMalloc((void**)&ctx->top_master, (size_t)nt.P * 4)); ctx->owned.push_back(ctx->top_master);
+        HIPCHK(hipMalloc((void**)&ctx->top_net_dev, sizeof(TrainNet))); ctx->owned.push_back(ctx->top_net_dev);
+    }
+    nt.master = ctx->top_master;
+    HIPCHK(hipMemcpy(ctx->top_master, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->top_net_dev, &nt, sizeof(TrainNet), hipMemcpyHostToDevice));
+    ctx->top_net = nt;
+    ctx->top_dirty = false;
+    return 0;
+}
+
+// an optimiser step has made the device master copy newer than the host tensors: bring them up to date (synchronises), so that neither
+// a re-commit nor a partial efe_set_weight of the part reverts what was learnt
+int refresh_top_host(efe_ctx* ctx) {
+    if (!ctx->top_dirty) return 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    const TrainNet& nt = ctx->top_net;
+    std::vector<float> flat((size_t)nt.P);
+    HIPCHK(hipMemcpy(flat.data(), ctx->top_master, flat.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nt.nl; ++i) {
+        const TrainLayer& L = nt.L[i];
+        auto& w = ctx->raw[std::string(TOP_KEYS[i]) + ".weight"].data;
+        auto& b = ctx->raw[std::string(TOP_KEYS[i]) + ".bias"].data;
+        w.assign(flat.begin() + L.w_off, flat.begin() + L.w_off + (size_t)L.out * L.in);
+        b.assign(flat.begin() + L.b_off, flat.begin() + L.b_off + L.out);
+    }
+    ctx->top_dirty = false;
     return 0;
 }
 
@@ -919,6 +982,7 @@ const char* efe_last_error(efe_ctx* ctx) { return !ctx ? "null context" : regist
 int efe_set_weight(efe_ctx* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim) {
     if (!key || !data_host || !shape || ndim < 1 || ndim > 4) return 1;
     Call call(ctx, Mode::host); if (!call) return 1;
+    if (ctx->top_dirty && !strncmp(key, "top.", 4) && refresh_top_host(ctx)) return 1;      // the other tensors of a trained part keep what was learnt
     HostTensor t;
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
@@ -1026,6 +1090,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
     }
     ctx->committed = false;
+    if (refresh_top_host(ctx)) return 1;          // a trained habit net is never reverted: the host copy follows the device master copy first
     const int A = ctx->pi_dim;
     // habit net (torchmodel.py:19-25)
     if (pack_linear(ctx, ctx->top[0], "top.qpi_net.0", 128, 10, nullptr, nullptr)) return 1;
@@ -1044,6 +1109,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         const int to[3] = {128, 128, A}, ti[3] = {10, 128, 128};
         for (int i = 0; i < 3; ++i) if (pack_linear16(ctx, ctx->top16.w[i], ctx->top16.b[i], tk[i], to[i], ti[i])) return 1;
     }
+    if (build_top_train(ctx)) return 1;
     // shared dense layers of the encoder / decoder heads
     if (pack_linear(ctx, ctx->enc_fc[1], "down.qs_net.12", 256, 256, nullptr, nullptr)) return 1;
     if (pack_linear(ctx, ctx->enc_fc[2], "down.qs_net.15", 256, 256, nullptr, nullptr)) return 1;
@@ -1420,6 +1486,76 @@ int efe_reparameterize(efe_ctx* ctx, const float* mean, const float* logvar, int
     if (!mean || !logvar || !nz || !out || M < 1 || n < 1) return ctx->fail("efe_reparameterize: bad arguments");
     launch_reparam(mean, logvar, eps, out, M, n, (uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), nz->pass, nz->sample, nz->stage,
                    nz->row_offset, (hipStream_t)stream);
+    return call.finish();
+}
+
+// ---- training of the habit net (train.hip) ------------------------------------------------------------
+namespace {
+int adam_args(efe_ctx* ctx, const char* part, const efe_adam_params* hp, AdamArgs& a, const char* who) {
+    if (!part || strcmp(part, "top")) return ctx->fail(std::string(who) + ": part must be \"top\" (the only trainable part)");
+    if (!hp || hp->step < 1 || !(hp->lr >= 0.0) || !(hp->beta1 >= 0.0 && hp->beta1 < 1.0) || !(hp->beta2 >= 0.0 && hp->beta2 < 1.0) || !(hp->eps >= 0.0))
+        return ctx->fail(std::string(who) + ": bad hyper-parameters (step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0)");
+    // torch.optim.Adam's scalars, in double as Python computes them, rounded once
+    const double bc1 = 1.0 - std::pow(hp->beta1, (double)hp->step), bc2 = 1.0 - std::pow(hp->beta2, (double)hp->step);
+    a.net = ctx->top_net_dev;
+    a.omb1 = (float)(1.0 - hp->beta1); a.b2 = (float)hp->beta2; a.omb2 = (float)(1.0 - hp->beta2);
+    a.bc2_sqrt = (float)std::sqrt(bc2); a.step_size = (float)(hp->lr / bc1); a.eps = (float)hp->eps;
+    return 0;
+}
+}  // namespace
+
+int64_t efe_param_count(efe_ctx* ctx, const char* part) {
+    Call call(ctx, Mode::host); if (!call) return 0;
+    if (!part || strcmp(part, "top")) { ctx->fail("efe_param_count: part must be \"top\""); return 0; }
+    return top_param_count(ctx->pi_dim);
+}
+
+int efe_get_weights(efe_ctx* ctx, const char* part, float* dst, int64_t n, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (!part || strcmp(part, "top")) return ctx->fail("efe_get_weights: part must be \"top\"");
+    if (!dst || n != ctx->top_net.P) return ctx->fail("efe_get_weights: dst must hold efe_param_count(part) floats");
+    HIPCHK(hipMemcpyAsync(dst, ctx->top_master, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    return call.finish();
+}
+
+int efe_top_grad(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, float* kl_pi, float* grad, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (!s || !log_Ppi || !grad || M < 1) return ctx->fail("efe_top_grad: bad arguments (s, log_Ppi and grad must be non-NULL, M >= 1)");
+    const int G = train_slabs(M), P = ctx->top_net.P;
+    float* slabs = G == 1 ? grad : ctx->allocT<float>((size_t)G * P);
+    if (!slabs) return 1;
+    ctx->cls = PROF_OTHER;
+    launch_top_grad(TopGradArgs{ctx->top_net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
+    if (G > 1) launch_slab_sum(slabs, G, P, grad, st);
+    return call.finish();
+}
+
+int efe_adam_step(efe_ctx* ctx, const char* part, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (!grad || !exp_avg || !exp_avg_sq) return ctx->fail("efe_adam_step: grad, exp_avg and exp_avg_sq must be non-NULL");
+    AdamArgs a{};
+    if (adam_args(ctx, part, hp, a, "efe_adam_step")) return 1;
+    a.g = grad; a.nslab = 1; a.m = exp_avg; a.v = exp_avg_sq;
+    ctx->top_dirty = true;
+    launch_adam(a, ctx->top_net.P, st);
+    return call.finish();
+}
+
+int efe_train_top(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, float* kl_pi, float* exp_avg, float* exp_avg_sq,
+                  const efe_adam_params* hp, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (!s || !log_Ppi || !exp_avg || !exp_avg_sq || M < 1)
+        return ctx->fail("efe_train_top: bad arguments (s, log_Ppi, exp_avg and exp_avg_sq must be non-NULL, M >= 1)");
+    AdamArgs a{};
+    if (adam_args(ctx, "top", hp, a, "efe_train_top")) return 1;
+    const int G = train_slabs(M), P = ctx->top_net.P;
+    float* slabs = ctx->allocT<float>((size_t)G * P);
+    if (!slabs) return 1;
+    ctx->cls = PROF_OTHER;
+    launch_top_grad(TopGradArgs{ctx->top_net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
+    a.g = slabs; a.nslab = G; a.m = exp_avg; a.v = exp_avg_sq;      // k_adam forms the gradient by the same ascending slab sum as k_slab_sum
+    ctx->top_dirty = true;
+    launch_adam(a, P, st);
     return call.finish();
 }
 

@@ -382,6 +382,42 @@ struct FeArgs {
 void launch_fe_top_mid(const FeArgs& a, hipStream_t st);
 void launch_fe_down(const FeArgs& a, const float* po, int m0, int rows, hipStream_t st);     // rows [m0, m0 + rows); po = their images
 
+// ---- training of the small MLPs (train.hip): backward + Adam over a layer table -----------------------------------
+// A trainable part is a chain of Linear layers described by a DEVICE-RESIDENT table (built at efe_commit_weights): widths, the ReLU flag
+// of each layer's output, a slot for the Philox tag an MC-dropout mask would be regenerated from (0 = no dropout; the habit net has
+// none), the offsets of the layer's weight / bias inside the flat parameter vector (the reference's parameters() order, row-major) and
+// the packed forward copies k_adam refreshes.
+constexpr int TRAIN_MAX_LAYERS = 4;      // layers of a table
+constexpr int TRAIN_MAX_WIDTH = 128;     // widest activation k_top_grad keeps in LDS
+constexpr int TRAIN_MAX_SLABS = 64;      // workgroups (= partial-gradient slabs) of one k_top_grad launch
+constexpr int TRAIN_MAX_A = 8;           // widest categorical head
+struct TrainLayer {
+    int in, out, relu, drop_tag;
+    int w_off, b_off;                    // offsets in the flat parameter vector
+    int kc32, kc16;                      // K chunks of the two packed forms (upload_packed: 8 channels, pack_linear16: 16 channels)
+    float *Wp32, *b32, *Wp16, *b16;      // packed copies read by the forward paths
+};
+struct TrainNet { int nl, P; float* master; TrainLayer L[TRAIN_MAX_LAYERS]; };
+__host__ __device__ inline int train_slabs(int M) { const int t = (M + 15) / 16; return t < TRAIN_MAX_SLABS ? t : TRAIN_MAX_SLABS; }
+struct TopGradArgs {
+    const TrainNet* net;                 // device pointer
+    const float* s; const float* log_Ppi;       // [M][in of layer 0], [M][A]
+    float* kl_pi;                        // nullable [M]
+    float* slabs;                        // [train_slabs(M)][P] partial gradients (slab p = workgroup p)
+    int M, A;
+    float inv_M;
+};
+void launch_top_grad(const TopGradArgs& a, hipStream_t st);
+void launch_slab_sum(const float* slabs, int nslab, int P, float* grad, hipStream_t st);
+struct AdamArgs {
+    const TrainNet* net;                 // device pointer
+    const float* g; int nslab;           // gradient = g[0][i] + g[1][i] + ... in ascending slab order (nslab = 1: a plain gradient)
+    float* m; float* v;                  // exp_avg, exp_avg_sq [P]
+    float omb1, b2, omb2;                // 1 - beta1, beta2, 1 - beta2
+    float bc2_sqrt, step_size, eps;      // sqrt(1 - beta2^t), lr / (1 - beta1^t)
+};
+void launch_adam(const AdamArgs& a, int P, hipStream_t st);
+
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);
 void launch_root_post(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,

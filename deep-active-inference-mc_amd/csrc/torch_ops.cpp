@@ -10,6 +10,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -360,6 +361,59 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> loss_
     return {F, nl, kls, klsa, kln, klna, po1, qs1};
 }
 
+// ---- training of the habit net (csrc/train.hip) ----
+// optimiser state updated in place: a contiguous float32 HIP tensor of efe_param_count("top") elements on the context's device
+float* state(Tensor& t, const char* name, int64_t P) {
+    TORCH_CHECK(t.is_cuda(), "efe: ", name, " must be a HIP device tensor (there is no CPU fallback)");
+    TORCH_CHECK((int)t.device().index() == tl_ctx_device, "efe: ", name, " is on device ", (int)t.device().index(), ", the engine context lives on device ", tl_ctx_device);
+    TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == P, "efe: ", name, " must be a contiguous float32 tensor of ", P, " elements");
+    return t.data_ptr<float>();
+}
+efe_adam_params adam_params(double lr, double beta1, double beta2, double eps, int64_t step) {
+    efe_adam_params hp;
+    hp.lr = lr; hp.beta1 = beta1; hp.beta2 = beta2; hp.eps = eps; hp.step = step;
+    return hp;
+}
+
+// d mean(F_top) / d qpi_net parameters (torchloss.py:65-72 up to optimizer.step) -> (kl_pi [M], grad [P])
+std::tuple<Tensor, Tensor> top_grad(int64_t h, const Tensor& s_, const Tensor& lp_) {
+    efe_ctx* c = CTX(h);
+    Tensor s = in(s_, "s"), lp = in(lp_, "log_Ppi");
+    const int M = rows(s, 10, "s");
+    TORCH_CHECK(lp.numel() == (int64_t)M * geo(c).A, "efe: log_Ppi must be [M, pi_dim]");
+    Tensor kl = at::empty({M}, s.options()), grad = at::empty({efe_param_count(c, "top")}, s.options());
+    ok(c, efe_top_grad(c, s.data_ptr<float>(), lp.data_ptr<float>(), M, kl.data_ptr<float>(), grad.data_ptr<float>(), stream_of(s)));
+    return {kl, grad};
+}
+
+// torch.optim.Adam.step() of one part with the caller's gradient and state
+void adam_step(int64_t h, c10::string_view part, const Tensor& grad_, Tensor exp_avg, Tensor exp_avg_sq, double lr, double beta1, double beta2,
+               double eps, int64_t step) {
+    efe_ctx* c = CTX(h);
+    const std::string pt(part);
+    const int64_t P = efe_param_count(c, pt.c_str());
+    TORCH_CHECK(P > 0, "efe engine: ", efe_last_error(c));
+    Tensor grad = in(grad_, "grad");
+    TORCH_CHECK(grad.numel() == P, "efe: grad has ", grad.numel(), " elements, the part has ", P, " parameters");
+    const efe_adam_params hp = adam_params(lr, beta1, beta2, eps, step);
+    ok(c, efe_adam_step(c, pt.c_str(), grad.data_ptr<float>(), state(exp_avg, "exp_avg", P), state(exp_avg_sq, "exp_avg_sq", P), &hp, stream_of(grad)));
+}
+
+// train_model_top, torchloss.py:65-74 -> kl_pi [M] of the weights before the step
+Tensor train_top(int64_t h, const Tensor& s_, const Tensor& lp_, Tensor exp_avg, Tensor exp_avg_sq, double lr, double beta1, double beta2, double eps,
+                 int64_t step) {
+    efe_ctx* c = CTX(h);
+    Tensor s = in(s_, "s"), lp = in(lp_, "log_Ppi");
+    const int M = rows(s, 10, "s");
+    TORCH_CHECK(lp.numel() == (int64_t)M * geo(c).A, "efe: log_Ppi must be [M, pi_dim]");
+    const int64_t P = efe_param_count(c, "top");
+    Tensor kl = at::empty({M}, s.options());
+    const efe_adam_params hp = adam_params(lr, beta1, beta2, eps, step);
+    ok(c, efe_train_top(c, s.data_ptr<float>(), lp.data_ptr<float>(), M, kl.data_ptr<float>(), state(exp_avg, "exp_avg", P), state(exp_avg_sq, "exp_avg_sq", P),
+                        &hp, stream_of(s)));
+    return kl;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -378,6 +432,9 @@ TORCH_LIBRARY(efe, m) {
     m.def("loss_top(int ctx, Tensor s, Tensor log_Ppi) -> (Tensor F_top, Tensor kl_pi, Tensor kl_pi_anal, Tensor Qpi)");
     m.def("loss_mid(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> (Tensor F_mid, Tensor kl_s, Tensor kl_s_anal, Tensor ps1, Tensor ps1_mean, Tensor ps1_logvar)");
     m.def("loss_down(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> (Tensor F_down, Tensor nlogpo1, Tensor kl_s, Tensor kl_s_anal, Tensor kl_naive, Tensor kl_naive_anal, Tensor po1, Tensor qs1)");
+    m.def("top_grad(int ctx, Tensor s, Tensor log_Ppi) -> (Tensor kl_pi, Tensor grad)");
+    m.def("adam_step(int ctx, str part, Tensor grad, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> ()");
+    m.def("train_top(int ctx, Tensor s, Tensor log_Ppi, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -396,4 +453,7 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("loss_top", &loss_top);
     m.impl("loss_mid", &loss_mid);
     m.impl("loss_down", &loss_down);
+    m.impl("top_grad", &top_grad);
+    m.impl("adam_step", &adam_step);
+    m.impl("train_top", &train_top);
 }

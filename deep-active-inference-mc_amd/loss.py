@@ -2,8 +2,10 @@
 compute_loss_top, compute_loss_mid, compute_loss_down) with the reference's names, arguments and return tuples, plus `free_energy`, the
 composition train.py:104-123 evaluates before its optimizer steps, in one engine call (efe_free_energy, csrc/loss.hip).
 
-Forward values only: no autograd graph is built (gradients, optimizers and a training loop are out of scope).  Every call dispatches
-through torch.ops.efe.* on the model's device; there is no CPU fallback.
+No autograd graph is built.  The habit network is trainable: `train_model_top` (torchloss.py:65-74) is one Adam step on the device
+(csrc/train.hip: backward + update in two launches, with a daimc_amd.Adam holding the state) and `grad_top` returns its gradient; the
+transition network, the encoder / decoder and a training loop are out of scope.  Every call dispatches through torch.ops.efe.* on the
+model's device; there is no CPU fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
 encoder, FE_T for the transition + sample, FE_DOWN for compute_loss_down's encoder + sample + decoder), one stage per call, rows keyed
@@ -126,3 +128,33 @@ def free_energy(model, o0, o1, pi0, log_Ppi, *, omega=None, omega_params=OMEGA_P
     outs = e.ops.free_energy(e.h, o0, o1, e.tensor(pi0, (M, model.pi_dim)), e.tensor(log_Ppi, (M, model.pi_dim)), _f32(model.gamma),
                              _f32(model.beta_s), _f32(model.beta_o), mode, om, sc, a, b, c, d, model._seed64(), nz.stage, nz.row_offset, eps_t)
     return FreeEnergy(*outs)
+
+
+def grad_top(model_top, s, log_Ppi):
+    """-> (kl_div_pi [M], {state_dict key: d mean(F_top) / d tensor}): what torchloss.py:69-72 leaves in .grad (views of one flat tensor)"""
+    m = model_top._owner
+    e = m._ready()
+    s = e.tensor(s, (-1, m.s_dim))
+    kl, flat = e.ops.top_grad(e.h, s, e.tensor(log_Ppi, (s.shape[0], m.pi_dim)))
+    grads, off = {}, 0
+    for key, t in model_top._sd_host.items():
+        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
+        off += t.numel()
+    return kl, grads
+
+
+def train_model_top(model_top, s, log_Ppi, optimizer):
+    """torchloss.py:65-74: one optimiser step of the habit net on F_top.mean() -> kl_div_pi [M] of the weights before the step.
+    optimizer: a daimc_amd.Adam over this model_top.  Bit-identical to grad_top followed by optimizer.step(grads)."""
+    if getattr(optimizer, '_module', None) is not model_top:
+        raise ValueError('train_model_top: optimizer must be a daimc_amd.Adam over this model_top')
+    m = model_top._owner
+    e = m._ready()
+    s = e.tensor(s, (-1, m.s_dim))
+    lp = e.tensor(log_Ppi, (s.shape[0], m.pi_dim))
+    ea, es = optimizer._buffers()
+    hyper = optimizer._hyper()
+    optimizer._step += 1
+    kl = e.ops.train_top(e.h, s, lp, ea, es, *hyper, optimizer._step)
+    model_top._stepped()
+    return kl

@@ -146,12 +146,55 @@ class _Module:
         return self
 
 
+class _ParamList(list):
+    """what ModelTop.parameters() returns: the tensors, plus the module they belong to (daimc_amd.Adam finds its engine through it)"""
+    module = None
+
+
 class ModelTop(_Module):
-    """torchmodel.py:10-31"""
+    """torchmodel.py:10-31.  The habit net is trainable on the device (loss.train_model_top): after an optimiser step the engine's master
+    copy is newer than the host tensors, and state_dict() / parameters() download it first (lazily, one synchronisation)."""
+    _device_newer = False
 
     def __init__(self, owner):
         super().__init__(owner, 'top')
         self.s_dim, self.pi_dim = owner.s_dim, owner.pi_dim
+
+    @property
+    def _sd(self):
+        if self._device_newer:
+            self._download()
+        return self._sd_host
+
+    @_sd.setter
+    def _sd(self, sd):
+        self._sd_host = sd
+        self._device_newer = False
+
+    def _download(self):
+        """efe_get_weights: the device master copy (flat, parameters() order) -> the host state_dict"""
+        e = self._owner._engine
+        P = int(e.lib.efe_param_count(e.ctx, b'top'))
+        buf = e.empty(P)
+        with torch.cuda.device(e.device):
+            e.check(e.lib.efe_get_weights(e.ctx, b'top', _ptr(buf), P, e.stream()))
+            flat = buf.cpu()
+        new, off = {}, 0
+        for key, t in self._sd_host.items():
+            new[key] = flat[off:off + t.numel()].reshape(t.shape).clone()
+            off += t.numel()
+        assert off == P, (off, P)
+        self._sd = new
+
+    def _stepped(self):
+        """an optimiser step ran on the device: the host copy is stale, and replicas built from it are too"""
+        self._device_newer = True
+        self._owner._weights_version = getattr(self._owner, '_weights_version', 0) + 1
+
+    def parameters(self):
+        p = _ParamList(self._sd.values())
+        p.module = self
+        return p
 
     def encode_s(self, s0):
         m = self._owner
@@ -421,10 +464,12 @@ class ActiveInferenceModel:
         self.model_mid.load_state_dict(torch.load(f'{folder_chp}/checkpoint_mid.pth', map_location='cpu'))
 
     def save_all(self, folder_chp, stats, script_file='', optimizers={}):
-        """torchmodel.py:179-189 (weights + stats; optimiser state is training-only and out of scope)."""
+        """torchmodel.py:179-189: weights, stats and optimizers.pkl = {name: optimizer.state_dict()} (daimc_amd.Adam or torch.optim)."""
         self.save_weights(folder_chp)
         with open(f'{folder_chp}/stats.pkl', 'wb') as ff:
             pickle.dump(stats, ff)
+        with open(f'{folder_chp}/optimizers.pkl', 'wb') as ff:
+            pickle.dump({k: v.state_dict() for k, v in optimizers.items()}, ff)
 
     def load_all(self, folder_chp):
         """torchmodel.py:191-208"""
@@ -439,7 +484,25 @@ class ActiveInferenceModel:
             self.gamma = torch.tensor(stats['var_gamma'][-1], device=self.device)
         if stats.get('var_beta_o'):
             self.beta_o = torch.tensor(stats['var_beta_o'][-1], device=self.device)
-        return stats, {}
+        return stats, self._load_optimizers(folder_chp)
+
+    def _load_optimizers(self, folder_chp):
+        """optimizers.pkl -> {name: daimc_amd.Adam} for every entry over the habit net's six parameters (the only part the engine
+        trains; entries of other parts stay in the file).  The reference's own loader (torchmodel.py:197-203) reads the pickle twice
+        and always lands in its bare `except`, i.e. it restarts every optimiser; this one restores them."""
+        path = f'{folder_chp}/optimizers.pkl'
+        if not os.path.exists(path):
+            return {}
+        from .optim import Adam
+        with open(path, 'rb') as ff:
+            saved = pickle.load(ff)
+        out = {}
+        for name, sd in saved.items():
+            groups = sd.get('param_groups', [])
+            if len(groups) == 1 and len(groups[0].get('params', ())) == len(self.model_top._sd_host):
+                out[name] = Adam(self.model_top)
+                out[name].load_state_dict(sd)
+        return out
 
     def to(self, *a, **k):
         return self

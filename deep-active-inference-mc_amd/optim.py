@@ -1,0 +1,93 @@
+"""daimc_amd.Adam: torch.optim.Adam (default flags: no amsgrad, no weight decay) for the part of the model the engine trains on the
+device, the habit network ModelTop.qpi_net.  The update runs in csrc/train.hip (k_adam) on the engine's master copy of the weights; this
+class holds the optimiser state (exp_avg, exp_avg_sq: flat device tensors in parameters() order) and the step count, and speaks
+torch.optim.Adam's state_dict format for those six parameters, so state moves both ways between the two."""
+import torch
+
+from .model import ModelTop
+
+
+def _torch_group():
+    """torch.optim.Adam's param-group keys and defaults of the installed torch (load_state_dict of either side sees what it expects)"""
+    return dict(torch.optim.Adam([torch.zeros(1)]).state_dict()['param_groups'][0])
+
+
+class Adam:
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        mod = params if isinstance(params, ModelTop) else getattr(params, 'module', None)
+        if not isinstance(mod, ModelTop):
+            raise TypeError('daimc_amd.Adam takes model.model_top or model.model_top.parameters() (the habit net is the trainable part)')
+        self._module = mod
+        self._shapes = [tuple(t.shape) for t in mod._sd_host.values()]
+        self._numel = [int(torch.Size(s).numel()) for s in self._shapes]
+        group = _torch_group()
+        group.update(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), params=list(range(len(self._shapes))))
+        self.param_groups = [group]
+        self._step = 0
+        self.exp_avg = self.exp_avg_sq = None
+
+    # ---- state ------------------------------------------------------------------------------------------------------
+    def _buffers(self):
+        if self.exp_avg is None:
+            dev = self._module._owner.device
+            self.exp_avg = torch.zeros(sum(self._numel), dtype=torch.float32, device=dev)
+            self.exp_avg_sq = torch.zeros_like(self.exp_avg)
+        return self.exp_avg, self.exp_avg_sq
+
+    def _hyper(self):
+        g = self.param_groups[0]
+        if g.get('weight_decay', 0) or g.get('amsgrad', False) or g.get('maximize', False):
+            raise ValueError('daimc_amd.Adam: weight_decay, amsgrad and maximize are not implemented (the reference uses none)')
+        return float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps'])
+
+    def zero_grad(self, set_to_none=True):
+        """no-op: the engine never accumulates gradients"""
+
+    def step(self, grad):
+        """one update with the caller's gradient: the dict loss.grad_top returns, or the flat [P] tensor (parameters() order)"""
+        m = self._module._owner
+        e = m._ready()
+        if isinstance(grad, dict):
+            grad = torch.cat([e.tensor(grad[k]).reshape(-1) for k in self._module._sd_host])
+        grad = e.tensor(grad).reshape(-1)
+        ea, es = self._buffers()
+        self._step += 1
+        e.ops.adam_step(e.h, 'top', grad, ea, es, *self._hyper(), self._step)
+        self._module._stepped()
+
+    def state_dict(self):
+        state = {}
+        if self._step > 0:
+            ea, es = (t.cpu() for t in self._buffers())
+            off = 0
+            for i, (shape, n) in enumerate(zip(self._shapes, self._numel)):
+                state[i] = {'step': torch.tensor(float(self._step)), 'exp_avg': ea[off:off + n].reshape(shape).clone(),
+                            'exp_avg_sq': es[off:off + n].reshape(shape).clone()}
+                off += n
+        group = dict(self.param_groups[0])
+        group['params'] = list(range(len(self._shapes)))
+        return {'state': state, 'param_groups': [group]}
+
+    def load_state_dict(self, sd):
+        groups = sd['param_groups']
+        if len(groups) != 1 or len(groups[0]['params']) != len(self._shapes):
+            raise ValueError(f'daimc_amd.Adam: expected one param group of {len(self._shapes)} parameters')
+        group = dict(self.param_groups[0], **{k: v for k, v in groups[0].items() if k != 'params'})
+        state = sd['state']
+        if not state:
+            self.param_groups, self._step, self.exp_avg, self.exp_avg_sq = [group], 0, None, None
+            return
+        ids = list(groups[0]['params'])
+        steps, ea, es = set(), [], []
+        for pid, shape in zip(ids, self._shapes):
+            st = state[pid]
+            if tuple(st['exp_avg'].shape) != shape or tuple(st['exp_avg_sq'].shape) != shape:
+                raise ValueError(f'daimc_amd.Adam: state of parameter {pid} has shape {tuple(st["exp_avg"].shape)}, expected {shape}')
+            steps.add(int(float(st['step'])))
+            ea.append(torch.as_tensor(st['exp_avg']).detach().to('cpu', torch.float32).reshape(-1))
+            es.append(torch.as_tensor(st['exp_avg_sq']).detach().to('cpu', torch.float32).reshape(-1))
+        if len(steps) != 1:
+            raise ValueError(f'daimc_amd.Adam: the parameters carry different step counts {sorted(steps)}')
+        dev = self._module._owner.device
+        self.param_groups, self._step = [group], steps.pop()
+        self.exp_avg, self.exp_avg_sq = torch.cat(ea).to(dev).contiguous(), torch.cat(es).to(dev).contiguous()

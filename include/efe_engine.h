@@ -305,6 +305,29 @@ int efe_loss_mid(efe_ctx*, const float* s0, const float* pi0, const float* qs1_m
 int efe_loss_down(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
                   const efe_noise* nz, const float* eps, efe_fe_out* out, void* stream);
 
+/* ---- training of the habit network (csrc/train.hip): train_model_top of /root/reference/src/torchloss.py:65-74 ----------------------------
+ * One Adam step of ModelTop.qpi_net on F_top.mean(), F_top = sum_a Qpi (log(Qpi + 1e-20) - log_Ppi).  The only trainable part is "top".
+ * The engine owns the weights (an fp32 master copy on the device next to the packed forward copies) and scratch; the gradient and the
+ * optimiser state (exp_avg, exp_avg_sq) are DEVICE arrays of efe_param_count("top") floats owned by the caller, flat in the reference's
+ * parameters() order (qpi_net.0.weight, 0.bias, 2.weight, 2.bias, 4.weight, 4.bias), each row-major.  Every call is ordered on `stream`
+ * like the other entry points: no synchronisation, no allocation in steady state.  Bad arguments and stale handles return 1.
+ *   efe_top_grad   : s [M,s_dim], log_Ppi [M,pi_dim] -> kl_pi [M] (NULL: not wanted) and grad [P] = d mean(F_top) / d parameters.  The
+ *                    gradient is a fixed-order sum: the same call twice gives the same bits.
+ *   efe_adam_step  : torch.optim.Adam's default update (no amsgrad, no weight decay) of `part` with step number hp->step (1 for the first
+ *                    step); writes the master copy and both packed forward copies, so every later call on the stream sees the new weights.
+ *   efe_train_top  : both on the stream, bit-identical to efe_top_grad followed by efe_adam_step; kl_pi is that of the weights BEFORE
+ *                    the update, as the reference returns it.
+ *   efe_get_weights: the part's master copy -> dst (device, efe_param_count floats), ordered on the stream.
+ * After a step the device copy is newer than the tensors given to efe_set_weight; efe_commit_weights and efe_set_weight("top....") first
+ * bring those host copies up to date (one synchronisation), so a re-commit never reverts what was learnt. */
+typedef struct efe_adam_params { double lr, beta1, beta2, eps; int64_t step; } efe_adam_params;
+int64_t efe_param_count(efe_ctx*, const char* part);             /* 0: unknown part or stale handle */
+int efe_get_weights(efe_ctx*, const char* part, float* dst, int64_t n, void* stream);
+int efe_top_grad(efe_ctx*, const float* s, const float* log_Ppi, int M, float* kl_pi, float* grad, void* stream);
+int efe_adam_step(efe_ctx*, const char* part, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
+int efe_train_top(efe_ctx*, const float* s, const float* log_Ppi, int M, float* kl_pi, float* exp_avg, float* exp_avg_sq,
+                  const efe_adam_params* hp, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
