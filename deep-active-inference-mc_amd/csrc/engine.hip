@@ -24,6 +24,7 @@ namespace {
 
 constexpr int S_DIM = 10;
 constexpr int64_t MAC_TRANS = 541696, MAC_DEC = 43256320, MAC_ENC = 3868960, MAC_HABIT = 18176;
+constexpr size_t SCRATCH_HEADROOM = (size_t)1 << 20;      // efe_rollout_scratch_bytes reports this much more than the plans add up to
 
 enum ProfClass { PROF_MID = 0, PROF_DEC_FC = 1, PROF_DEC_FC4 = 2, PROF_CT1 = 3, PROF_CT2 = 4, PROF_CT3 = 5, PROF_FINAL = 6,
                  PROF_ENC = 7, PROF_OTHER = 8, PROF_NCLS = 9 };
@@ -40,6 +41,10 @@ struct Arena {
     std::vector<std::pair<char*, size_t>> blocks;
     size_t cur = 0, off = 0, used_total = 0;
     void reset() { cur = 0; off = 0; used_total = 0; }
+    // the bump position, to put back once a chunk's scratch is done with (the blocks stay)
+    struct Mark { size_t cur, off, used_total; };
+    Mark mark() const { return {cur, off, used_total}; }
+    void rewind(const Mark& m) { cur = m.cur; off = m.off; used_total = m.used_total; }
     size_t capacity() const { size_t n = 0; for (auto& b : blocks) n += b.second; return n; }
 };
 
@@ -141,8 +146,9 @@ struct efe_ctx {
     int fail(const std::string& m) { err = m; return 1; }
 
     // bump allocator over a list of device blocks; grows (synchronously) on first use at a new size
+    size_t al(size_t bytes) const { return (bytes + (size_t)arena_align - 1) / (size_t)arena_align * (size_t)arena_align; }
     void* alloc(size_t bytes) {
-        bytes = (bytes + (size_t)arena_align - 1) / (size_t)arena_align * (size_t)arena_align;
+        bytes = al(bytes);
         while (true) {
             if (arena.cur < arena.blocks.size()) {
                 auto& b = arena.blocks[arena.cur];
@@ -166,28 +172,62 @@ struct efe_ctx {
 
 namespace {
 
-// ---- weight packing into the MFMA fragment-major layout [tap][mtile][kc][lane][4] -------------------
-template <class Get>
-int upload_packed(efe_ctx* ctx, Layer& L, int ntaps, int cout, int cin, Get get, const float* bias_src, const int* bias_perm) {
+// ---- weight packing ----------------------------------------------------------------------------------
+// a host vector as a device buffer of the current commit (freed by the next one); nullptr with ctx->err set on failure
+template <class T>
+T* upload(efe_ctx* ctx, const std::vector<T>& v) {
+    T* d = nullptr;
+    if (hipMalloc((void**)&d, v.size() * sizeof(T)) != hipSuccess) { ctx->err = "weight upload: hipMalloc failed"; return nullptr; }
+    ctx->wbufs.push_back(d);
+    if (hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "weight upload: hipMemcpy failed"; return nullptr; }
+    return d;
+}
+
+const HostTensor* need(efe_ctx* ctx, const std::string& key, std::initializer_list<int64_t> shape) {
+    auto it = ctx->raw.find(key);
+    if (it == ctx->raw.end()) { ctx->err = "missing weight " + key; return nullptr; }
+    if (it->second.shape != std::vector<int64_t>(shape)) { ctx->err = "bad shape for " + key; return nullptr; }
+    return &it->second;
+}
+// key.weight and key.bias of one layer: both, or neither with need()'s message
+struct WB {
+    const HostTensor *w = nullptr, *b = nullptr;
+    explicit operator bool() const { return w && b; }
+    const float* W() const { return w->data.data(); }
+    const float* B() const { return b->data.data(); }
+};
+WB weight_and_bias(efe_ctx* ctx, const std::string& key, std::initializer_list<int64_t> wshape, std::initializer_list<int64_t> bshape) {
+    WB r;
+    r.w = need(ctx, key + ".weight", wshape);
+    if (r.w) r.b = need(ctx, key + ".bias", bshape);
+    return r.b ? r : WB{};
+}
+
+// a layer from its already packed weights ([ntaps][mtiles][cin / 8][256], whatever the order inside) and its bias, padded to the tile count
+int upload_layer(efe_ctx* ctx, Layer& L, int ntaps, int cout, int cin, const std::vector<float>& packed, const float* bias) {
     L.ntaps = ntaps; L.cout = cout; L.mtiles = (cout + 31) / 32; L.cin = (cin + 7) / 8 * 8;
-    const int KC = L.cin / 8;
-    std::vector<float> p((size_t)ntaps * L.mtiles * KC * 256);
+    if (packed.size() != (size_t)ntaps * L.mtiles * (L.cin / 8) * 256) return ctx->fail("upload_layer: packed size does not match the layer");
+    std::vector<float> b((size_t)L.mtiles * 32, 0.f);
+    std::copy(bias, bias + cout, b.begin());
+    L.Wp = upload(ctx, packed);
+    L.bias = L.Wp ? upload(ctx, b) : nullptr;
+    return L.bias ? 0 : 1;
+}
+// ... packed here into the MFMA fragment-major layout of v_mfma_f32_32x32x2_f32, [tap][mtile][kc][lane][4], from get(tap, co, ci)
+template <class Get>
+int upload_packed(efe_ctx* ctx, Layer& L, int ntaps, int cout, int cin, Get get, const float* bias) {
+    const int mtiles = (cout + 31) / 32, KC = (cin + 7) / 8;
+    std::vector<float> p((size_t)ntaps * mtiles * KC * 256);
     size_t idx = 0;
     for (int t = 0; t < ntaps; ++t)
-        for (int mt = 0; mt < L.mtiles; ++mt)
+        for (int mt = 0; mt < mtiles; ++mt)
             for (int kc = 0; kc < KC; ++kc)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int s = 0; s < 4; ++s) {
                         const int co = mt * 32 + (lane & 31), ci = kc * 8 + 4 * (lane >> 5) + s;
                         p[idx++] = (co < cout && ci < cin) ? get(t, co, ci) : 0.f;
                     }
-    std::vector<float> b((size_t)L.mtiles * 32, 0.f);
-    for (int co = 0; co < cout; ++co) b[co] = bias_src[bias_perm ? bias_perm[co] : co];
-    HIPCHK(hipMalloc((void**)&L.Wp, p.size() * 4)); ctx->wbufs.push_back(L.Wp);
-    HIPCHK(hipMalloc((void**)&L.bias, b.size() * 4)); ctx->wbufs.push_back(L.bias);
-    HIPCHK(hipMemcpy(L.Wp, p.data(), p.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(L.bias, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-    return 0;
+    return upload_layer(ctx, L, ntaps, cout, cin, p, bias);
 }
 
 // Minimal-filtering F(2, 2) weights of a stride-2 ConvTranspose2d(cin, cout, 3, s2, p1, op1), W [cin][cout][kh][kw] (kernels.h f22_*):
@@ -206,74 +246,130 @@ std::vector<float> convt_s2_f22_weights(const float* W, int cin, int cout) {
                 }
     return U;
 }
-
-const HostTensor* need(efe_ctx* ctx, const std::string& key, std::initializer_list<int64_t> shape) {
-    auto it = ctx->raw.find(key);
-    if (it == ctx->raw.end()) { ctx->err = "missing weight " + key; return nullptr; }
-    if (it->second.shape != std::vector<int64_t>(shape)) { ctx->err = "bad shape for " + key; return nullptr; }
-    return &it->second;
+// Winograd F(2x2, 3x3) weights of a stride-1 ConvTranspose2d(cin, cout, 3, s1, p1) (decoder.hip wino_l1): U[4 a + b][co][ci] = (G g G^T)[a][b]
+// in fp64, rounded once; g[u][v] = W[ci][co][2 - u][2 - v] (the correlation form of the stride-1 transposed conv)
+std::vector<float> convt_s1_wino_weights(const float* W, int cin, int cout) {
+    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    std::vector<float> U((size_t)16 * cout * cin);
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci) {
+            const float* k = W + ((size_t)ci * cout + co) * 9;
+            double Gg[4][3];
+            for (int a = 0; a < 4; ++a)
+                for (int v = 0; v < 3; ++v) {
+                    double s = 0;
+                    for (int u = 0; u < 3; ++u) s += Gm[a][u] * (double)k[(2 - u) * 3 + (2 - v)];
+                    Gg[a][v] = s;
+                }
+            for (int a = 0; a < 4; ++a)
+                for (int b = 0; b < 4; ++b) {
+                    double s = 0;
+                    for (int v = 0; v < 3; ++v) s += Gg[a][v] * Gm[b][v];
+                    U[((size_t)(a * 4 + b) * cout + co) * cin + ci] = (float)s;
+                }
+        }
+    return U;
+}
+// 16 matrices U [cout][64] for v_mfma_f32_16x16x4_f32: [U][16-channel tile ct][chunk kc][lane][s] = U[16 ct + (lane & 15)][16 kc + 4 (lane >> 4) + s]
+std::vector<float> pack_u16x16x4(const std::vector<float>& U, int cout) {
+    const int T = cout / 16;
+    std::vector<float> p(U.size());
+    for (int m = 0; m < 16; ++m) for (int ct = 0; ct < T; ++ct) for (int kc = 0; kc < 4; ++kc) for (int lane = 0; lane < 64; ++lane)
+        for (int s_ = 0; s_ < 4; ++s_)
+            p[((((size_t)m * T + ct) * 4 + kc) * 64 + lane) * 4 + s_] = U[((size_t)m * cout + 16 * ct + (lane & 15)) * 64 + 16 * kc + 4 * (lane >> 4) + s_];
+    return p;
+}
+// torch's Flatten / Unflatten index a [channels][positions] block channel-major, c * positions + p; the kernels keep it NHWC, p * channels + c:
+// perm[NHWC index] = channel-major index
+std::vector<int> nhwc_perm(int channels, int positions) {
+    std::vector<int> perm((size_t)positions * channels);
+    for (int p = 0; p < positions; ++p) for (int c = 0; c < channels; ++c) perm[(size_t)p * channels + c] = c * positions + p;
+    return perm;
 }
 
-int pack_linear(efe_ctx* ctx, Layer& L, const std::string& key, int out, int in, const int* row_perm, const int* col_perm) {
-    const HostTensor* w = need(ctx, key + ".weight", {out, in});
-    const HostTensor* b = need(ctx, key + ".bias", {out});
-    if (!w || !b) return 1;
-    const float* W = w->data.data();
-    return upload_packed(ctx, L, 1, out, in,
-        [&](int, int co, int ci) { return W[(size_t)(row_perm ? row_perm[co] : co) * in + (col_perm ? col_perm[ci] : ci)]; },
-        b->data.data(), row_perm);
+// one layer of a network as the weight tables below list it: a Linear(in, out), or a 3 x 3 convolution (out = cout, in = cin)
+struct LayerSpec { const char* key; int out, in; };
+constexpr int TOP_NL = 3, MID_NL = 4;
+const char* const TOP_KEYS[TOP_NL] = {"top.qpi_net.0", "top.qpi_net.2", "top.qpi_net.4"};
+// habit net (torchmodel.py:19-25)
+LayerSpec top_layer(int i, int A) { const int out[TOP_NL] = {128, 128, A}, in[TOP_NL] = {10, 128, 128}; return {TOP_KEYS[i], out[i], in[i]}; }
+// transition net (torchmodel.py:41-52); input = cat[pi, s0] (torchmodel.py:59)
+LayerSpec mid_layer(int i, int A) {
+    const LayerSpec t[MID_NL] = {{"mid.ps_net.0", 512, A + 10}, {"mid.ps_net.3", 512, 512}, {"mid.ps_net.6", 512, 512}, {"mid.ps_net.9", 20, 512}};
+    return t[i];
+}
+// decoder head; encoder head behind its first layer (whose width follows the geometry: pack_encoder)
+const LayerSpec DEC_HEAD[3] = {{"down.po_net.0", 256, 10}, {"down.po_net.3", 256, 256}, {"down.po_net.6", 256, 256}};
+const LayerSpec ENC_HEAD[3] = {{"down.qs_net.12", 256, 256}, {"down.qs_net.15", 256, 256}, {"down.qs_net.18", 20, 256}};
+// encoder Conv2d stack (torchmodel.py:84-104; layer 0 reads the image's channels) and decoder ConvTranspose2d stack
+LayerSpec enc_conv_layer(int i, int C) { const LayerSpec t[4] = {{"down.qs_net.0", 32, C}, {"down.qs_net.2", 32, 32}, {"down.qs_net.4", 64, 32}, {"down.qs_net.6", 64, 64}}; return t[i]; }
+const LayerSpec DEC_CT[3] = {{"down.po_net.13", 64, 64}, {"down.po_net.15", 64, 64}, {"down.po_net.17", 32, 64}};
+
+int pack_linear(efe_ctx* ctx, Layer& L, const LayerSpec& s, const int* row_perm = nullptr, const int* col_perm = nullptr) {
+    const WB t = weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
+    if (!t) return 1;
+    const float* W = t.W();
+    const int in = s.in;
+    std::vector<float> b((size_t)s.out);
+    for (int co = 0; co < s.out; ++co) b[co] = t.B()[row_perm ? row_perm[co] : co];
+    return upload_packed(ctx, L, 1, s.out, in,
+        [&](int, int co, int ci) { return W[(size_t)(row_perm ? row_perm[co] : co) * in + (col_perm ? col_perm[ci] : ci)]; }, b.data());
 }
 
 // packed for v_mfma_f32_16x16x4_f32 (fused.hip): [16-feature tile][16-channel chunk][lane = (m, q)][s] = W[16 mt + m][16 kc + 4 q + s]
-int pack_linear16(efe_ctx* ctx, const float4*& Wout, const float*& bout, const std::string& key, int out, int in, const int* col_perm = nullptr) {
-    const HostTensor* w = need(ctx, key + ".weight", {out, in});
-    const HostTensor* b = need(ctx, key + ".bias", {out});
-    if (!w || !b) return 1;
-    const int mtiles = (out + 15) / 16, KC = (in + 15) / 16;
+int pack_linear16(efe_ctx* ctx, MlpW& net, int layer, const LayerSpec& s, const int* col_perm = nullptr) {
+    const WB t = weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
+    if (!t) return 1;
+    const int out = s.out, in = s.in, mtiles = (out + 15) / 16, KC = (in + 15) / 16;
     std::vector<float> p((size_t)mtiles * KC * 256, 0.f), bb((size_t)mtiles * 16, 0.f);
     for (int mt = 0; mt < mtiles; ++mt)
         for (int kc = 0; kc < KC; ++kc)
             for (int lane = 0; lane < 64; ++lane)
                 for (int s_ = 0; s_ < 4; ++s_) {
                     const int co = 16 * mt + (lane & 15), ci = 16 * kc + 4 * (lane >> 4) + s_;
-                    if (co < out && ci < in) p[(((size_t)mt * KC + kc) * 64 + lane) * 4 + s_] = w->data[(size_t)co * in + (col_perm ? col_perm[ci] : ci)];
+                    if (co < out && ci < in) p[(((size_t)mt * KC + kc) * 64 + lane) * 4 + s_] = t.W()[(size_t)co * in + (col_perm ? col_perm[ci] : ci)];
                 }
-    for (int co = 0; co < out; ++co) bb[co] = b->data[co];
-    float *dW = nullptr, *dB = nullptr;
-    HIPCHK(hipMalloc((void**)&dW, p.size() * 4)); ctx->wbufs.push_back(dW);
-    HIPCHK(hipMalloc((void**)&dB, bb.size() * 4)); ctx->wbufs.push_back(dB);
-    HIPCHK(hipMemcpy(dW, p.data(), p.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dB, bb.data(), bb.size() * 4, hipMemcpyHostToDevice));
-    Wout = reinterpret_cast<const float4*>(dW); bout = dB;
+    std::copy(t.B(), t.B() + out, bb.begin());
+    const float* dW = upload(ctx, p);
+    const float* dB = dW ? upload(ctx, bb) : nullptr;
+    if (!dB) return 1;
+    net.w[layer] = reinterpret_cast<const float4*>(dW); net.b[layer] = dB;
     return 0;
+}
+// a 3 x 3 Conv2d (W [cout][cin][3][3]) or ConvTranspose2d (W [cin][cout][3][3]) as nine taps of the 32x32x2 form
+int pack_conv(efe_ctx* ctx, Layer& L, const LayerSpec& s, bool transposed) {
+    const WB t = transposed ? weight_and_bias(ctx, s.key, {s.in, s.out, 3, 3}, {s.out}) : weight_and_bias(ctx, s.key, {s.out, s.in, 3, 3}, {s.out});
+    if (!t) return 1;
+    const float* W = t.W();
+    const int cin = s.in, cout = s.out;
+    if (transposed) return upload_packed(ctx, L, 9, cout, cin, [&](int tap, int co, int ci) { return W[((size_t)ci * cout + co) * 9 + tap]; }, t.B());
+    return upload_packed(ctx, L, 9, cout, cin, [&](int tap, int co, int ci) { return W[((size_t)co * cin + ci) * 9 + tap]; }, t.B());
 }
 
 // ---- training tables (train.hip) ---------------------------------------------------------------------
-const char* const TOP_KEYS[3] = {"top.qpi_net.0", "top.qpi_net.2", "top.qpi_net.4"};
-int top_param_count(int A) { return 10 * 128 + 128 + 128 * 128 + 128 + A * 128 + A; }
+int top_param_count(int A) { int n = 0; for (int i = 0; i < TOP_NL; ++i) { const LayerSpec s = top_layer(i, A); n += s.out * s.in + s.out; } return n; }
 
-// the habit net's master copy and layer table, after its packed forms exist (efe_commit_weights): k_top_grad reads the master copy,
+// the habit net's master copy and layer table, after its packed forms exist (pack_top): k_top_grad reads the master copy,
 // k_adam writes it and the packed copies
 int build_top_train(efe_ctx* ctx) {
     const int A = ctx->pi_dim;
-    const int to[3] = {128, 128, A}, ti[3] = {10, 128, 128};
     TrainNet nt{};
-    nt.nl = 3;
+    nt.nl = TOP_NL;
     std::vector<float> flat;
-    for (int i = 0; i < 3; ++i) {
-        const HostTensor* w = need(ctx, std::string(TOP_KEYS[i]) + ".weight", {to[i], ti[i]});
-        const HostTensor* b = need(ctx, std::string(TOP_KEYS[i]) + ".bias", {to[i]});
-        if (!w || !b) return 1;
+    for (int i = 0; i < TOP_NL; ++i) {
+        const LayerSpec s = top_layer(i, A);
+        const WB t = weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
+        if (!t) return 1;
         TrainLayer& L = nt.L[i];
-        L.in = ti[i]; L.out = to[i]; L.relu = i < 2; L.drop_tag = 0;
-        L.w_off = (int)flat.size(); flat.insert(flat.end(), w->data.begin(), w->data.end());
-        L.b_off = (int)flat.size(); flat.insert(flat.end(), b->data.begin(), b->data.end());
-        L.kc32 = ctx->top[i].cin / 8; L.kc16 = (ti[i] + 15) / 16;
+        L.in = s.in; L.out = s.out; L.relu = i < TOP_NL - 1; L.drop_tag = 0;
+        L.w_off = (int)flat.size(); flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
+        L.b_off = (int)flat.size(); flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
+        L.kc32 = ctx->top[i].cin / 8; L.kc16 = (s.in + 15) / 16;
         L.Wp32 = ctx->top[i].Wp; L.b32 = ctx->top[i].bias;
         L.Wp16 = const_cast<float*>(reinterpret_cast<const float*>(ctx->top16.w[i])); L.b16 = const_cast<float*>(ctx->top16.b[i]);
     }
     nt.P = (int)flat.size();
-    if (nt.P != top_param_count(A) || A > TRAIN_MAX_A) return ctx->fail("habit net outside the training kernels' limits");
+    if (A > TRAIN_MAX_A) return ctx->fail("habit net outside the training kernels' limits");
     if (!ctx->top_master) {
         HIPCHK(hipMalloc((void**)&ctx->top_master, (size_t)nt.P * 4)); ctx->owned.push_back(ctx->top_master);
         HIPCHK(hipMalloc((void**)&ctx->top_net_dev, sizeof(TrainNet))); ctx->owned.push_back(ctx->top_net_dev);
@@ -316,16 +412,44 @@ struct NoiseCfg {
     int mask_div = 1;
 };
 inline RowMask live_of(const NoiseCfg& nc, int m0) { return RowMask{nc.mask, nc.mask_div, m0, nc.rows_per_group, nc.mask ? nc.gm.ids : nullptr}; }
+// the noise addressing of one network pass: key words, rows per group and this rank's row offset, the group -> (pass, sample, stage) map,
+// and optionally the row identities / liveness mask of an efe_rows call (one entry = div rows)
+NoiseCfg make_noise(uint32_t k0, uint32_t k1, int rows_per_group, uint32_t row_offset, GroupMap gm, const int32_t* ids = nullptr, int div = 1,
+                    const uint8_t* mask = nullptr) {
+    NoiseCfg nc;
+    nc.k0 = k0; nc.k1 = k1; nc.rows_per_group = rows_per_group; nc.row_offset = row_offset;
+    nc.gm = gm; nc.gm.ids = ids; nc.gm.ids_div = div;
+    nc.mask = mask; nc.mask_div = div;
+    return nc;
+}
+// ... of a single-group call over M rows: the caller's seed, stage and row offset, one (pass, sample)
+NoiseCfg pass_noise(const efe_noise* nz, uint32_t pass, uint32_t sample, int M) {
+    return make_noise((uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), M, nz->row_offset, GroupMap{1, 1, {pass, 0, 0}, nz->stage, sample});
+}
+// the six noise-addressing fields that GemmArgs, HeadArgs and TransFusedArgs share by name
+template <class Args>
+void set_keys(Args& a, const NoiseCfg& nc, int m0) {
+    a.k0 = nc.k0; a.k1 = nc.k1; a.gm = nc.gm; a.rows_per_group = nc.rows_per_group; a.row_offset = nc.row_offset; a.m0 = m0;
+}
+
+// The profiling span of one launch: the launches of its scope count under class `cls` (efe_prof_read), between two events on the stream when
+// that class is being timed.  The end of the scope closes the span and puts the class back; cancel() = nothing was launched, record no span.
+struct ProfSpan {
+    efe_ctx* const ctx; const hipStream_t st; const int prev; hipEvent_t e0;
+    ProfSpan(efe_ctx* c, int cls, hipStream_t s) : ctx(c), st(s), prev(c->cls) { c->cls = cls; e0 = c->prof_begin(s); }
+    void cancel() { e0 = nullptr; }
+    ~ProfSpan() { ctx->prof_end(e0, st); ctx->cls = prev; }
+};
 
 // split16 = false: the decoder's Linear(256, 16384) stays on the exact fp32 k_fc4 even under a split-operand option (its consumer is fp32)
-void fc(efe_ctx* ctx, const Layer& L, const float* X, int ldx, int x_mod, float* Y, int ldy, int M, bool relu, bool drop,
+void fc(efe_ctx* ctx, int cls, const Layer& L, const float* X, int ldx, int x_mod, float* Y, int ldy, int M, bool relu, bool drop,
         uint32_t tag, const NoiseCfg& nc, int m0, hipStream_t st, bool split16 = true) {
     GemmArgs a{};
     a.Wp = L.Wp; a.bias = L.bias; a.X = X; a.Y = Y; a.zeros = ctx->zeros;
     a.n_pix = M; a.cin = L.cin; a.cout = L.cout; a.mtiles = L.mtiles; a.ldx = ldx; a.ldy = ldy; a.x_mod = x_mod;
-    a.relu = relu; a.dropout = drop; a.tag = tag; a.k0 = nc.k0; a.k1 = nc.k1; a.gm = nc.gm;
-    a.rows_per_group = nc.rows_per_group; a.row_offset = nc.row_offset; a.m0 = m0;
-    hipEvent_t e0 = ctx->prof_begin(st);
+    a.relu = relu; a.dropout = drop; a.tag = tag;
+    set_keys(a, nc, m0);
+    ProfSpan span(ctx, cls, st);
     if (L.mtiles >= 64 && !(L.mtiles & 1) && L.cin == 256 && ldx == 256 && x_mod == 0 && relu && drop) {
         if (split16 && ctx->mfma_bf16x3 && ctx->fc4_b3 && &L == &ctx->dec_fc[3]) {      // opt-in experiment
             a.Wb3 = ctx->fc4_b3; a.split = (int)ctx->mfma_bf16x3; a.wb3_scale_inv = 1.0f / ctx->s_fc4;
@@ -340,172 +464,226 @@ void fc(efe_ctx* ctx, const Layer& L, const float* X, int ldx, int x_mod, float*
         if (tiles22 < 2048) { NT = 1; if (tiles22 * 2 < 2048) MT = 1; }
         if (launch_dense(MT, NT, a, st)) ctx->pending = "launch_dense: unsupported tile shape";
     }
-    ctx->prof_end(e0, st);
 }
 
-// decoder head (enc = false: X [M][16] -> Y [M][256]) or encoder head (X [M][16 * kc0] -> Y [M][32]) as one launch (fused.hip k_head)
-void head(efe_ctx* ctx, bool enc, const float* X, float* Y, int M, const NoiseCfg& nc, int m0, hipStream_t st) {
-    HeadArgs a{};
-    a.W = enc ? ctx->enc16 : ctx->dec16; a.kc0 = enc ? ctx->enc16_kc0 : 1; a.nl = enc ? 4 : 3; a.out_tiles = 2;
-    a.tag0 = enc ? TAG_ENC : TAG_DEC; a.X = X; a.Y = Y; a.M = M; a.k0 = nc.k0; a.k1 = nc.k1; a.gm = nc.gm;
-    a.rows_per_group = nc.rows_per_group; a.row_offset = nc.row_offset; a.m0 = m0;
-    hipEvent_t e0 = ctx->prof_begin(st);
-    launch_head(a, st);
-    ctx->prof_end(e0, st);
+// The dense head of the decoder (enc = false: X [M][16] -> out [M][256], three layers) or of the encoder (X [M][ldx] -> out [M][32], four
+// layers): one launch (fused.hip k_head), or layer by layer through hA / hB ([M][256] each) under the option head_unfused
+void dense_head(efe_ctx* ctx, bool enc, const float* X, int ldx, float* out, int ldy, float* hA, float* hB, int M, const NoiseCfg& nc, int m0,
+                hipStream_t st) {
+    const int cls = enc ? PROF_ENC : PROF_DEC_FC;
+    const uint32_t tag = enc ? TAG_ENC : TAG_DEC;
+    if (!ctx->head_unfused) {
+        HeadArgs a{};
+        a.W = enc ? ctx->enc16 : ctx->dec16; a.kc0 = enc ? ctx->enc16_kc0 : 1; a.nl = enc ? 4 : 3; a.out_tiles = 2;
+        a.tag0 = tag; a.X = X; a.Y = out; a.M = M;
+        set_keys(a, nc, m0);
+        ProfSpan span(ctx, cls, st);
+        launch_head(a, st);
+        return;
+    }
+    const Layer* L = enc ? ctx->enc_fc : ctx->dec_fc;
+    fc(ctx, cls, L[0], X, ldx, 0, hA, 256, M, true, true, tag + 0, nc, m0, st);
+    fc(ctx, cls, L[1], hA, 256, 0, hB, 256, M, true, true, tag + 1, nc, m0, st);
+    if (!enc) { fc(ctx, cls, L[2], hB, 256, 0, out, ldy, M, true, true, tag + 2, nc, m0, st); return; }
+    fc(ctx, cls, L[2], hB, 256, 0, hA, 256, M, true, true, tag + 2, nc, m0, st);
+    fc(ctx, cls, L[3], hA, 256, 0, out, ldy, M, false, false, 0, nc, m0, st);
+}
+
+// one layer of the generic geometry on k_conv_g: mode 0 = Conv2d(k3, s2, p0), 1 / 2 = ConvTranspose2d of stride 1 / 2; square images, + ReLU
+void conv_g(efe_ctx* ctx, int cls, const Layer& L, const float* in, float* out, int n, int hin, int cin, int hout, int cout, int mode,
+            const RowMask& live, hipStream_t st) {
+    ConvGArgs a{};
+    a.in = in; a.out = out; a.Wp = L.Wp; a.bias = L.bias; a.zeros = ctx->zeros; a.n_img = n; a.Hin = hin; a.Win = hin; a.Cin = cin;
+    a.Hout = hout; a.Wout = hout; a.Cout = cout; a.mtiles = L.mtiles; a.mode = mode; a.relu = 1; a.ldo = cout;
+    a.live = live;
+    ProfSpan span(ctx, cls, st);
+    launch_conv_g(a, st);
+}
+
+// ---- scratch plans -----------------------------------------------------------------------------------
+// Every path that takes scratch describes its buffers ONCE, as a plan: a pure function of the context's options and the call's sizes that
+// returns the element count of each buffer (all are 4-byte elements; 0 = the buffer does not exist) and whatever decides a count (chunk
+// sizes, which kernels run).  run_X allocates from its plan, in the order of the plan's fields; efe_rollout_scratch_bytes sums the same
+// plans (plan_bytes: what the arena charges for them).
+size_t arena_bytes(const efe_ctx* ctx, std::initializer_list<size_t> counts) {
+    size_t t = 0;
+    for (size_t n : counts) t += ctx->al(n * 4);
+    return t;
+}
+
+struct MidPlan { size_t h1, h2; };      // layer-by-layer transition only (option mid_unfused)
+MidPlan mid_plan(const efe_ctx* ctx, int64_t M) { const size_t h = ctx->mid_unfused ? (size_t)M * 512 : 0; return {h, h}; }
+size_t plan_bytes(const efe_ctx* c, const MidPlan& p) { return arena_bytes(c, {p.h1, p.h2}); }
+
+// does the generic decoder run its last two layers as k_dec_bg?  Decided from the geometry (y3 exists only when the final layer is its own launch)
+bool generic_dec_fused(const efe_ctx* ctx) { return ctx->fuse_final_g && !ctx->last_s1 && dec_bg_ok(2 * ctx->base, 2 * ctx->base, ctx->chan); }
+struct DecGPlan { int C; bool fused; size_t hA, hB, x4, y1, y2, y3; };      // C: images per launch group; fused: last two layers in one kernel
+DecGPlan dec_g_plan(const efe_ctx* ctx, int64_t N) {
+    const int64_t B = ctx->base, H2 = 2 * B, H3 = ctx->last_s1 ? 2 * B : 4 * B;
+    DecGPlan p{};
+    p.fused = generic_dec_fused(ctx);
+    // images per launch group: bounded by the chunk options and by a byte budget for the group's layer activations
+    const int64_t per_image = (2 * B * B * 64 + H2 * H2 * 64 + (p.fused ? 0 : H3 * H3 * 32)) * (int64_t)sizeof(float);
+    const int64_t by_bytes = std::max<int64_t>(256, ctx->dec_budget_g / per_image);
+    const int64_t C = std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(ctx->dec_chunk, ctx->dec_chunk_g), by_bytes), N);
+    p.C = (int)C;
+    p.hA = p.hB = (size_t)N * 256;
+    p.x4 = p.y1 = (size_t)(C * B * B * 64);
+    p.y2 = (size_t)(C * H2 * H2 * 64);
+    p.y3 = p.fused ? 0 : (size_t)(C * H3 * H3 * 32);
+    return p;
+}
+size_t plan_bytes(const efe_ctx* c, const DecGPlan& p) { return arena_bytes(c, {p.hA, p.hB, p.x4, p.y1, p.y2, p.y3}); }
+
+// dSprites decoder: launches of at most this many images split every image over four workgroups in k_dec_b4 (per-image sums as quarters, valq)
+constexpr int DEC_SPLIT_MAX = 128;
+inline bool dec_split(const efe_ctx* ctx, int64_t N) { return !ctx->generic && ctx->dec_split && N <= DEC_SPLIT_MAX; }
+struct DecPlan { int C; bool split; size_t hA, hB, x4, y2, queues; };       // queues: one image-ticket counter (int) per k_dec_a launch
+DecPlan dec_plan(const efe_ctx* ctx, int64_t N) {
+    const int64_t C = std::min<int64_t>(ctx->dec_chunk, N);
+    return {(int)C, dec_split(ctx, N), (size_t)N * 256, (size_t)N * 256, (size_t)C * 16384, (size_t)C * 65536, (size_t)((N + C - 1) / C)};
+}
+size_t plan_bytes(const efe_ctx* c, const DecPlan& p) { return arena_bytes(c, {p.hA, p.hB, p.x4, p.y2, p.queues}); }
+
+// widen: layer 1 runs on k_conv_g, which reads 8-channel pixels from o8w.  The buffer is taken on first use and the plan foresees the option
+// enc_tiled = 0 only: kernels.h has no predicate that tells beforehand whether k_conv_e declines a geometry (none that efe_create_cfg admits is)
+struct EncGPlan { int C; bool widen; size_t c1, c2, c3, c4, hA, hB, o8w; };
+EncGPlan enc_g_plan(const efe_ctx* ctx, int64_t N) {
+    const int* hw = ctx->enc_hw;
+    const size_t C = (size_t)std::min<int64_t>(std::min<int64_t>(ctx->enc_chunk, 8192), N);
+    return {(int)C, ctx->enc_tiled == 0, C * hw[1] * hw[1] * 32, C * hw[2] * hw[2] * 32, C * hw[3] * hw[3] * 64, C * hw[4] * hw[4] * 64,
+            C * 256, C * 256, C * hw[0] * hw[0] * 8};
+}
+size_t plan_bytes(const efe_ctx* c, const EncGPlan& p) { return arena_bytes(c, {p.c1, p.c2, p.c3, p.c4, p.hA, p.hB, p.widen ? p.o8w : 0}); }
+
+struct EncPlan { int C; size_t c4, hA, hB; };
+EncPlan enc_plan(const efe_ctx* ctx, int64_t N) { const size_t C = (size_t)std::min<int64_t>(ctx->enc_chunk, N); return {(int)C, C * 9 * 64, C * 256, C * 256}; }
+size_t plan_bytes(const efe_ctx* c, const EncPlan& p) { return arena_bytes(c, {p.c4, p.hA, p.hB}); }
+
+// run_core over R rows, D stages, S samples: own_tr = the transition rows are not the caller's (k_sim_chain's), own_terms = no `terms` output given;
+// vsplit: a small decoder launch, whose per-image sums arrive as four quarter sums
+struct CorePlan { bool vsplit; size_t tr_all, dec_in, xbuf, val, po_store, enc, terms_tmp; };
+CorePlan core_plan(const efe_ctx* ctx, int64_t R_, int64_t D_, int64_t S_, bool own_tr, bool own_terms) {
+    const size_t R = (size_t)R_, D = (size_t)D_, S = (size_t)S_;
+    const bool vsplit = dec_split(ctx, D_ * 3 * S_ * R_);
+    return {vsplit, own_tr ? D * 2 * S * R * 32 : 0, D * 3 * S * R * 16, 2 * R * 16, D * 3 * S * R * (vsplit ? 4 : 1), D * S * R * ctx->img_store,
+            D * S * R * 32, own_terms ? 3 * R : 0};
+}
+size_t plan_bytes(const efe_ctx* c, const CorePlan& p) { return arena_bytes(c, {p.tr_all, p.dec_in, p.xbuf, p.val, p.po_store, p.enc, p.terms_tmp}); }
+
+// the root of efe_rollout: the encoded observation, the first transition input, and (generic geometry) the observation as NHWC4
+struct RolloutPlan { size_t enc0, x, o8; };
+RolloutPlan rollout_plan(const efe_ctx* ctx, int64_t M) { return {(size_t)M * 32, (size_t)M * 16, ctx->generic ? (size_t)M * ctx->img_store : 0}; }
+size_t plan_bytes(const efe_ctx* c, const RolloutPlan& p) { return arena_bytes(c, {p.enc0, p.x, p.o8}); }
+
+// the sums, nested as the calls are: run_decoder / run_encoder dispatch on the geometry, run_core runs D transitions and one pass of each
+size_t decoder_bytes(const efe_ctx* ctx, int64_t N) { return ctx->generic ? plan_bytes(ctx, dec_g_plan(ctx, N)) : plan_bytes(ctx, dec_plan(ctx, N)); }
+size_t encoder_bytes(const efe_ctx* ctx, int64_t N) { return ctx->generic ? plan_bytes(ctx, enc_g_plan(ctx, N)) : plan_bytes(ctx, enc_plan(ctx, N)); }
+size_t core_bytes(const efe_ctx* ctx, int64_t R, int64_t D, int64_t S, bool own_terms) {
+    return plan_bytes(ctx, core_plan(ctx, R, D, S, true, own_terms)) + (size_t)D * plan_bytes(ctx, mid_plan(ctx, 2 * S * R))
+         + decoder_bytes(ctx, D * 3 * S * R) + encoder_bytes(ctx, D * S * R);
 }
 
 // ModelMid.ps_net over M = groups*R rows; X is [R][16], every group reads the same rows (x_mod).
 int run_mid(efe_ctx* ctx, const float* X, int x_mod, int M, float* tr /*[M][32]*/, const NoiseCfg& nc, hipStream_t st) {
+    ctx->last_macs += (int64_t)M * ctx->mac_trans;
     if (!ctx->mid_unfused) {           // one launch for the four layers, activations in LDS (fused.hip)
         TransFusedArgs a{};
-        a.W = ctx->mid16; a.X = X; a.tr = tr; a.M = M; a.x_mod = x_mod; a.k0 = nc.k0; a.k1 = nc.k1; a.gm = nc.gm;
-        a.rows_per_group = nc.rows_per_group; a.row_offset = nc.row_offset; a.m0 = 0;
-        ctx->cls = PROF_MID;
-        hipEvent_t e0 = ctx->prof_begin(st);
+        a.W = ctx->mid16; a.X = X; a.tr = tr; a.M = M; a.x_mod = x_mod;
+        set_keys(a, nc, 0);
+        ProfSpan span(ctx, PROF_MID, st);
         launch_trans_fused(a, st);
-        ctx->prof_end(e0, st);
-        ctx->cls = PROF_OTHER;
-        ctx->last_macs += (int64_t)M * ctx->mac_trans;
         return 0;
     }
-    float* h1 = ctx->allocT<float>((size_t)M * 512);
-    float* h2 = ctx->allocT<float>((size_t)M * 512);
+    const MidPlan p = mid_plan(ctx, M);
+    float* h1 = ctx->allocT<float>(p.h1);
+    float* h2 = ctx->allocT<float>(p.h2);
     if (!h1 || !h2) return 1;
-    ctx->cls = PROF_MID;
-    fc(ctx, ctx->mid[0], X, 16, x_mod, h1, 512, M, true, true, TAG_MID + 0, nc, 0, st);
-    fc(ctx, ctx->mid[1], h1, 512, 0, h2, 512, M, true, true, TAG_MID + 1, nc, 0, st);
-    fc(ctx, ctx->mid[2], h2, 512, 0, h1, 512, M, true, true, TAG_MID + 2, nc, 0, st);
-    fc(ctx, ctx->mid[3], h1, 512, 0, tr, 32, M, false, false, 0, nc, 0, st);
-    ctx->cls = PROF_OTHER;
-    ctx->last_macs += (int64_t)M * ctx->mac_trans;
+    fc(ctx, PROF_MID, ctx->mid[0], X, 16, x_mod, h1, 512, M, true, true, TAG_MID + 0, nc, 0, st);
+    fc(ctx, PROF_MID, ctx->mid[1], h1, 512, 0, h2, 512, M, true, true, TAG_MID + 1, nc, 0, st);
+    fc(ctx, PROF_MID, ctx->mid[2], h2, 512, 0, h1, 512, M, true, true, TAG_MID + 2, nc, 0, st);
+    fc(ctx, PROF_MID, ctx->mid[3], h1, 512, 0, tr, 32, M, false, false, 0, nc, 0, st);
     return 0;
-}
-
-// does the generic decoder run its last two layers as k_dec_bg?  Decided from the geometry BEFORE scratch is sized (y3 exists only when
-// the final layer is its own launch), so that efe_reserve / efe_rollout_scratch_bytes and the call itself always agree
-static bool generic_dec_fused(const efe_ctx* ctx) {
-    return ctx->fuse_final_g && !ctx->last_s1 && dec_bg_ok(2 * ctx->base, 2 * ctx->base, ctx->chan);
-}
-// images per launch group of the generic decoder: bounded by the chunk options and by a byte budget for the group's layer activations
-int64_t generic_dec_chunk(const efe_ctx* ctx, int64_t N) {
-    const int64_t B = ctx->base, H2 = 2 * B, H3 = ctx->last_s1 ? 2 * B : 4 * B;
-    const bool fused = generic_dec_fused(ctx);
-    const int64_t per_image = (2 * B * B * 64 + H2 * H2 * 64 + (fused ? 0 : H3 * H3 * 32)) * (int64_t)sizeof(float);
-    const int64_t by_bytes = std::max<int64_t>(256, ctx->dec_budget_g / per_image);
-    return std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(ctx->dec_chunk, ctx->dec_chunk_g), by_bytes), N);
 }
 
 // generic geometry (generic.hip): dense head -> Linear(256, 64*B*B) -> ConvT(64,64,s1) -> ConvT(64,64,s2) -> ConvT(64,32,s2) -> final conv
 int run_decoder_g(efe_ctx* ctx, const float* dec_in, int N, const NoiseCfg& nc, int reward0, int store0, float* val, float* po_store,
                   hipStream_t st) {
     const int B = ctx->base, H2 = 2 * B, H3 = ctx->last_s1 ? 2 * B : 4 * B;
-    const int C = (int)generic_dec_chunk(ctx, N);
-    const bool fused = generic_dec_fused(ctx);
-    float* hA = ctx->allocT<float>((size_t)N * 256);
-    float* hB = ctx->allocT<float>((size_t)N * 256);
-    float* x4 = ctx->allocT<float>((size_t)C * B * B * 64);
-    float* y1 = ctx->allocT<float>((size_t)C * B * B * 64);
-    float* y2 = ctx->allocT<float>((size_t)C * H2 * H2 * 64);
-    float* y3 = fused ? nullptr : ctx->allocT<float>((size_t)C * H3 * H3 * 32);
-    if (!hA || !hB || !x4 || !y1 || !y2 || (!fused && !y3)) return 1;
-    ctx->cls = PROF_DEC_FC;
-    if (!ctx->head_unfused) head(ctx, false, dec_in, hA, N, nc, 0, st);
-    else {
-        fc(ctx, ctx->dec_fc[0], dec_in, 16, 0, hA, 256, N, true, true, TAG_DEC + 0, nc, 0, st);
-        fc(ctx, ctx->dec_fc[1], hA, 256, 0, hB, 256, N, true, true, TAG_DEC + 1, nc, 0, st);
-        fc(ctx, ctx->dec_fc[2], hB, 256, 0, hA, 256, N, true, true, TAG_DEC + 2, nc, 0, st);
-    }
-    int cur_m0 = 0;
-    auto conv = [&](const Layer& L, const float* in, float* out, int n, int hin, int cin, int hout, int cout, int mode) {
-        ConvGArgs a{};
-        a.in = in; a.out = out; a.Wp = L.Wp; a.bias = L.bias; a.zeros = ctx->zeros; a.n_img = n; a.Hin = hin; a.Win = hin; a.Cin = cin;
-        a.Hout = hout; a.Wout = hout; a.Cout = cout; a.mtiles = L.mtiles; a.mode = mode; a.relu = 1; a.ldo = cout;
-        a.live = live_of(nc, cur_m0);
-        hipEvent_t e0 = ctx->prof_begin(st);
-        launch_conv_g(a, st);
-        ctx->prof_end(e0, st);
-    };
+    const DecGPlan p = dec_g_plan(ctx, N);
+    const int C = p.C;
+    float* hA = ctx->allocT<float>(p.hA);
+    float* hB = ctx->allocT<float>(p.hB);
+    float* x4 = ctx->allocT<float>(p.x4);
+    float* y1 = ctx->allocT<float>(p.y1);
+    float* y2 = ctx->allocT<float>(p.y2);
+    float* y3 = p.fused ? nullptr : ctx->allocT<float>(p.y3);
+    if (!hA || !hB || !x4 || !y1 || !y2 || (!p.fused && !y3)) return 1;
+    ctx->last_macs += (int64_t)N * ctx->mac_dec;
+    dense_head(ctx, false, dec_in, 16, hA, 256, hA, hB, N, nc, 0, st);
     for (int m0 = 0; m0 < N; m0 += C) {
         const int c = std::min(C, N - m0);
-        cur_m0 = m0;
-        ctx->cls = PROF_DEC_FC4;
-        fc(ctx, ctx->g_fc4, hA + (size_t)m0 * 256, 256, 0, x4, B * B * 64, c, true, true, TAG_DEC + 3, nc, m0, st);
+        const RowMask live = live_of(nc, m0);
+        fc(ctx, PROF_DEC_FC4, ctx->g_fc4, hA + (size_t)m0 * 256, 256, 0, x4, B * B * 64, c, true, true, TAG_DEC + 3, nc, m0, st);
         int sep12 = 1;                                    // the first two transposed layers as one launch each
         if (ctx->ct_fuse12) {                             // ... or as one kernel, layer 1's output kept in LDS (class PROF_CT2)
-            ctx->cls = PROF_CT2;
             ConvT12Args f{};
             f.in = x4; f.out = y2; f.W1p = ctx->g_ct[0].Wp; f.b1 = ctx->g_ct[0].bias; f.W2p = ctx->g_ct[1].Wp; f.b2 = ctx->g_ct[1].bias;
-            f.n_img = c; f.Hin = B; f.Win = B; f.live = live_of(nc, m0);
-            hipEvent_t e0 = ctx->prof_begin(st);
+            f.n_img = c; f.Hin = B; f.Win = B; f.live = live;
+            ProfSpan span(ctx, PROF_CT2, st);
             sep12 = launch_convt_12(f, st);
-            ctx->prof_end(sep12 ? nullptr : e0, st);
+            if (sep12) span.cancel();
         }
         if (sep12) {
-            ctx->cls = PROF_CT1;
-            conv(ctx->g_ct[0], x4, y1, c, B, 64, B, 64, 1);
-            ctx->cls = PROF_CT2;
-            conv(ctx->g_ct[1], y1, y2, c, B, 64, H2, 64, 2);
+            conv_g(ctx, PROF_CT1, ctx->g_ct[0], x4, y1, c, B, 64, B, 64, 1, live, st);
+            conv_g(ctx, PROF_CT2, ctx->g_ct[1], y1, y2, c, B, 64, H2, 64, 2, live, st);
         }
-        ctx->cls = PROF_CT3;
-        if (fused) {        // ConvT(64,32,s2) + ReLU + ConvT(32,C,s1) + Sigmoid + per-image sums in one kernel: y3 never exists
+        if (p.fused) {      // ConvT(64,32,s2) + ReLU + ConvT(32,C,s1) + Sigmoid + per-image sums in one kernel: y3 never exists
             DecBGArgs f{};
             f.y2 = y2; f.w3 = ctx->g_ct[2].Wp; f.b3 = ctx->g_ct[2].bias; f.w4 = ctx->g_wf; for (int i = 0; i < 4; ++i) f.b4[i] = ctx->g_bf[i];
             f.rows = c; f.m0 = m0; f.rows_per_group = nc.rows_per_group; f.Hin = H2; f.Win = H2; f.C = ctx->chan; f.gm = nc.gm;
-            f.reward0 = reward0; f.store0 = store0; f.reward_intent = (int)ctx->reward_intent; f.val = val; f.po = po_store; f.live = live_of(nc, m0);
-            hipEvent_t e0 = ctx->prof_begin(st);
-            const int rc = launch_dec_bg(f, st);
-            ctx->prof_end(e0, st);
-            if (rc) return ctx->fail("fused decoder tail: unsupported geometry");      // (dec_bg_ok said yes: not reachable)
+            f.reward0 = reward0; f.store0 = store0; f.reward_intent = (int)ctx->reward_intent; f.val = val; f.po = po_store; f.live = live;
+            ProfSpan span(ctx, PROF_CT3, st);
+            if (launch_dec_bg(f, st)) return ctx->fail("fused decoder tail: unsupported geometry");      // (dec_bg_ok said yes: not reachable)
             continue;
         }
-        conv(ctx->g_ct[2], y2, y3, c, H2, 64, H3, 32, ctx->last_s1 ? 1 : 2);
-        ctx->cls = PROF_FINAL;
+        conv_g(ctx, PROF_CT3, ctx->g_ct[2], y2, y3, c, H2, 64, H3, 32, ctx->last_s1 ? 1 : 2, live, st);
         FinalGArgs f{};
         f.y3 = y3; f.w = ctx->g_wf; for (int i = 0; i < 4; ++i) f.b[i] = ctx->g_bf[i];
         f.rows = c; f.m0 = m0; f.rows_per_group = nc.rows_per_group; f.H = H3; f.W = H3; f.C = ctx->chan; f.gm = nc.gm;
-        f.reward0 = reward0; f.store0 = store0; f.reward_intent = (int)ctx->reward_intent; f.val = val; f.po = po_store; f.live = live_of(nc, m0);
-        hipEvent_t e0 = ctx->prof_begin(st);
-        const int frc = launch_final_g(f, st);
-        ctx->prof_end(e0, st);
-        if (frc) return ctx->fail("final decoder layer: unsupported geometry");
+        f.reward0 = reward0; f.store0 = store0; f.reward_intent = (int)ctx->reward_intent; f.val = val; f.po = po_store; f.live = live;
+        ProfSpan span(ctx, PROF_FINAL, st);
+        if (launch_final_g(f, st)) return ctx->fail("final decoder layer: unsupported geometry");
     }
-    ctx->cls = PROF_OTHER;
-    ctx->last_macs += (int64_t)N * ctx->mac_dec;
     return 0;
 }
 
 // generic geometry: o is NHWC4 [N][res*res][4]; four Conv2d(k3,s2,p0)+ReLU, then the dense head
 int run_encoder_g(efe_ctx* ctx, const float* o8, int N, const NoiseCfg& nc, float* enc, hipStream_t st) {
     const int* hw = ctx->enc_hw;
-    const int C = (int)std::min<int64_t>(std::min<int64_t>(ctx->enc_chunk, 8192), N);
-    float* c1 = ctx->allocT<float>((size_t)C * hw[1] * hw[1] * 32);
-    float* c2 = ctx->allocT<float>((size_t)C * hw[2] * hw[2] * 32);
-    float* c3 = ctx->allocT<float>((size_t)C * hw[3] * hw[3] * 64);
-    float* c4 = ctx->allocT<float>((size_t)C * hw[4] * hw[4] * 64);
-    float* hA = ctx->allocT<float>((size_t)C * 256);
-    float* hB = ctx->allocT<float>((size_t)C * 256);
+    const EncGPlan p = enc_g_plan(ctx, N);
+    const int C = p.C;
+    float* c1 = ctx->allocT<float>(p.c1);
+    float* c2 = ctx->allocT<float>(p.c2);
+    float* c3 = ctx->allocT<float>(p.c3);
+    float* c4 = ctx->allocT<float>(p.c4);
+    float* hA = ctx->allocT<float>(p.hA);
+    float* hB = ctx->allocT<float>(p.hB);
     if (!c1 || !c2 || !c3 || !c4 || !hA || !hB) return 1;
+    ctx->last_macs += (int64_t)N * ctx->mac_enc;
     const int flat = hw[4] * hw[4] * 64;
     float* o8w = nullptr;
-    auto conv = [&](const Layer& L, const float* in, float* out, int n, int hin, int cin, int hout, int cout) {
-        ConvGArgs a{};
-        a.in = in; a.out = out; a.Wp = L.Wp; a.bias = L.bias; a.zeros = ctx->zeros; a.n_img = n; a.Hin = hin; a.Win = hin; a.Cin = cin;
-        a.Hout = hout; a.Wout = hout; a.Cout = cout; a.mtiles = L.mtiles; a.mode = 0; a.relu = 1; a.ldo = cout;
-        hipEvent_t e0 = ctx->prof_begin(st);
-        launch_conv_g(a, st);
-        ctx->prof_end(e0, st);
-    };
     for (int m0 = 0; m0 < N; m0 += C) {
         const int c = std::min(C, N - m0);
-        ctx->cls = PROF_ENC;
+        const RowMask live = live_of(nc, m0);
         // layers 1 and 2 LDS-tiled (generic_enc.hip); k_conv_g where a geometry is outside that kernel's limits
         auto conv_e = [&](int layer, const float* in, float* out, const float* Wp, const float* bias, int hin, int hout) -> int {
             ConvEArgs e{};
             e.in = in; e.out = out; e.Wp = Wp; e.bias = bias; e.n_img = c; e.Hin = hin; e.Win = hin; e.Hout = hout; e.Wout = hout;
-            e.live = live_of(nc, m0);
-            hipEvent_t e0 = ctx->prof_begin(st);
+            e.live = live;
+            ProfSpan span(ctx, PROF_ENC, st);
             const int rc = ctx->enc_tiled ? launch_conv_e(e, layer, st) : 1;
-            ctx->prof_end(rc ? nullptr : e0, st);
+            if (rc) span.cancel();
             return rc;
         };
         const float* o4c = o8 + (size_t)m0 * hw[0] * hw[0] * GEN_IMG_LD;
@@ -513,132 +691,105 @@ int run_encoder_g(efe_ctx* ctx, const float* o8, int N, const NoiseCfg& nc, floa
         if (ctx->enc_tiled >= 2) {                        // ... or as one kernel, conv1's output kept in LDS
             ConvE12Args e{};
             e.in = o4c; e.out = c2; e.W1p = ctx->g_enc1p; e.b1 = ctx->g_enc[0].bias; e.W2p = ctx->g_enc[1].Wp; e.b2 = ctx->g_enc[1].bias;
-            e.n_img = c; e.H0 = e.W0 = hw[0]; e.H1 = e.W1 = hw[1]; e.H2 = e.W2 = hw[2]; e.live = live_of(nc, m0);
-            hipEvent_t e0 = ctx->prof_begin(st);
+            e.n_img = c; e.H0 = e.W0 = hw[0]; e.H1 = e.W1 = hw[1]; e.H2 = e.W2 = hw[2]; e.live = live;
+            ProfSpan span(ctx, PROF_ENC, st);
             sep12 = launch_conv_e12(e, st);
-            ctx->prof_end(sep12 ? nullptr : e0, st);
+            if (sep12) span.cancel();
         }
         if (sep12) {
             if (conv_e(1, o4c, c1, ctx->g_enc1p, ctx->g_enc[0].bias, hw[0], hw[1])) {
                 // k_conv_g contracts 8 input channels per tap: widen the image first (this path: option enc_tiled = 0)
-                if (!o8w) o8w = ctx->allocT<float>((size_t)C * hw[0] * hw[0] * 8);
+                if (!o8w) o8w = ctx->allocT<float>(p.o8w);
                 if (!o8w) return 1;
                 launch_nhwc4_to_8(o4c, o8w, (long)c * hw[0] * hw[0], st);
-                conv(ctx->g_enc[0], o8w, c1, c, hw[0], 8, hw[1], 32);
+                conv_g(ctx, PROF_ENC, ctx->g_enc[0], o8w, c1, c, hw[0], 8, hw[1], 32, 0, RowMask{}, st);
             }
-            if (conv_e(2, c1, c2, ctx->g_enc[1].Wp, ctx->g_enc[1].bias, hw[1], hw[2])) conv(ctx->g_enc[1], c1, c2, c, hw[1], 32, hw[2], 32);
+            if (conv_e(2, c1, c2, ctx->g_enc[1].Wp, ctx->g_enc[1].bias, hw[1], hw[2]))
+                conv_g(ctx, PROF_ENC, ctx->g_enc[1], c1, c2, c, hw[1], 32, hw[2], 32, 0, RowMask{}, st);
         }
-        conv(ctx->g_enc[2], c2, c3, c, hw[2], 32, hw[3], 64);
-        conv(ctx->g_enc[3], c3, c4, c, hw[3], 64, hw[4], 64);
-        if (!ctx->head_unfused) head(ctx, true, c4, enc + (size_t)m0 * 32, c, nc, m0, st);
-        else {
-            fc(ctx, ctx->enc_fc[0], c4, flat, 0, hA, 256, c, true, true, TAG_ENC + 0, nc, m0, st);
-            fc(ctx, ctx->enc_fc[1], hA, 256, 0, hB, 256, c, true, true, TAG_ENC + 1, nc, m0, st);
-            fc(ctx, ctx->enc_fc[2], hB, 256, 0, hA, 256, c, true, true, TAG_ENC + 2, nc, m0, st);
-            fc(ctx, ctx->enc_fc[3], hA, 256, 0, enc + (size_t)m0 * 32, 32, c, false, false, 0, nc, m0, st);
-        }
+        conv_g(ctx, PROF_ENC, ctx->g_enc[2], c2, c3, c, hw[2], 32, hw[3], 64, 0, RowMask{}, st);
+        conv_g(ctx, PROF_ENC, ctx->g_enc[3], c3, c4, c, hw[3], 64, hw[4], 64, 0, RowMask{}, st);
+        dense_head(ctx, true, c4, flat, enc + (size_t)m0 * 32, 32, hA, hB, c, nc, m0, st);
     }
-    ctx->cls = PROF_OTHER;
-    ctx->last_macs += (int64_t)N * ctx->mac_enc;
     return 0;
 }
 
 // ModelDown.po_net over N rows ([group][row] batch): the three small dense layers run once over all rows, then per
 // chunk: dense 256->16384 (+dropout) -> k_dec_a (two transposed convs through LDS) -> k_dec_b (third transposed conv,
 // final conv, sigmoid and the per-image reduction, all on chip).
-// launches of at most this many images split every image over four workgroups in k_dec_b4 (per-image sums as quarters, valq)
-constexpr int DEC_SPLIT_MAX = 128;
-inline bool dec_split(const efe_ctx* ctx, int N) { return !ctx->generic && ctx->dec_split && N <= DEC_SPLIT_MAX; }
-
 int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const NoiseCfg& nc, int reward0, int store0,
                 float* val /*[N], or [N][4] quarter sums when dec_split(ctx, N)*/, float* po_store, hipStream_t st) {
     if (ctx->generic) return run_decoder_g(ctx, dec_in, N, nc, reward0, store0, val, po_store, st);
-    const bool split = dec_split(ctx, N);
+    const DecPlan p = dec_plan(ctx, N);
+    const bool split = p.split;
     // mfma_f16x2 marks a row / image whose activation overflowed fp16 with +inf, and only its own split kernels turn that into a NaN
     // sum: an exact-fp32 consumer (k_dec_a_s / k_dec_a / k_dec_b4) can make a finite wrong image of it (inf - inf = NaN, and relu_bits
     // maps a negative-signed NaN or -inf to 0).  So under that mode the chain is split from k_fc4_b3 to k_dec_b_b3 or not at all: small
     // launches keep k_fc4 too, and ConvT3 always runs on k_dec_b_b3 (b3_convt3 = 0 applies to mfma_bf16x3, which cannot overflow).
     const bool f16 = ctx->mfma_bf16x3 == 2;
     const bool fc4_16 = !(f16 && split), ct3_16 = ctx->b3_convt3 || f16;
-    const int C = (int)std::min<int64_t>(ctx->dec_chunk, N);
-    float* hA = ctx->allocT<float>((size_t)N * 256);
-    float* hB = ctx->allocT<float>((size_t)N * 256);
-    float* x4 = ctx->allocT<float>((size_t)C * 16384);
-    float* y2 = ctx->allocT<float>((size_t)C * 65536);
+    const int C = p.C;
+    float* hA = ctx->allocT<float>(p.hA);
+    float* hB = ctx->allocT<float>(p.hB);
+    float* x4 = ctx->allocT<float>(p.x4);
+    float* y2 = ctx->allocT<float>(p.y2);
     if (!hA || !hB || !x4 || !y2) return 1;
-    ctx->cls = PROF_DEC_FC;
-    if (!ctx->head_unfused) head(ctx, false, dec_in, hA, N, nc, 0, st);
-    else {
-        fc(ctx, ctx->dec_fc[0], dec_in, 16, 0, hA, 256, N, true, true, TAG_DEC + 0, nc, 0, st);
-        fc(ctx, ctx->dec_fc[1], hA, 256, 0, hB, 256, N, true, true, TAG_DEC + 1, nc, 0, st);
-        fc(ctx, ctx->dec_fc[2], hB, 256, 0, hA, 256, N, true, true, TAG_DEC + 2, nc, 0, st);
-    }
-    const int nchunks = (N + C - 1) / C;
-    int* queues = ctx->allocT<int>((size_t)nchunks);        // one image-ticket counter per k_dec_a launch
+    ctx->last_macs += (int64_t)N * ctx->mac_dec;
+    dense_head(ctx, false, dec_in, 16, hA, 256, hA, hB, N, nc, 0, st);
+    int* queues = ctx->allocT<int>(p.queues);
     if (!queues) return 1;
-    if (!split && hipMemsetAsync(queues, 0, (size_t)nchunks * sizeof(int), st) != hipSuccess) return ctx->fail("hipMemsetAsync failed");      // (k_dec_a_s takes no tickets)
+    if (!split && hipMemsetAsync(queues, 0, p.queues * sizeof(int), st) != hipSuccess) return ctx->fail("hipMemsetAsync failed");      // (k_dec_a_s takes no tickets)
     for (int m0 = 0; m0 < N; m0 += C) {
         const int c = std::min(C, N - m0);
-        ctx->cls = PROF_DEC_FC4;
-        fc(ctx, ctx->dec_fc[3], hA + (size_t)m0 * 256, 256, 0, x4, 16384, c, true, true, TAG_DEC + 3, nc, m0, st, fc4_16);
-        ctx->cls = PROF_CT2;
+        fc(ctx, PROF_DEC_FC4, ctx->dec_fc[3], hA + (size_t)m0 * 256, 256, 0, x4, 16384, c, true, true, TAG_DEC + 3, nc, m0, st, fc4_16);
         DecAArgs da{};
         da.x4 = x4; da.y2 = y2; da.w1 = ctx->dec_ct[0].Wp; da.b1 = ctx->dec_ct[0].bias; da.w2 = ctx->dec_ct[1].Wp;
         da.b2 = ctx->dec_ct[1].bias; da.rows = c; da.live = live_of(nc, m0); da.queue = queues + m0 / C; da.parts = split ? 8 : 1;
-        hipEvent_t e0 = ctx->prof_begin(st);
-        if (ctx->mfma_bf16x3 && ctx->ct_b3[0] && !split) {      // opt-in experiment
-            da.w1b3 = ctx->ct_b3[0]; da.w2b3 = ctx->ct_b3[1]; da.split = (int)ctx->mfma_bf16x3;
-            da.w1s = ctx->s_ct[0]; da.w1s_inv = 1.0f / ctx->s_ct[0]; da.w2s = ctx->s_ct[1]; da.w2s_inv = 1.0f / ctx->s_ct[1];
-            launch_dec_a_b3(da, st);
+        {
+            ProfSpan span(ctx, PROF_CT2, st);
+            if (ctx->mfma_bf16x3 && ctx->ct_b3[0] && !split) {      // opt-in experiment
+                da.w1b3 = ctx->ct_b3[0]; da.w2b3 = ctx->ct_b3[1]; da.split = (int)ctx->mfma_bf16x3;
+                da.w1s = ctx->s_ct[0]; da.w1s_inv = 1.0f / ctx->s_ct[0]; da.w2s = ctx->s_ct[1]; da.w2s_inv = 1.0f / ctx->s_ct[1];
+                launch_dec_a_b3(da, st);
+            }
+            else launch_dec_a(da, st);
         }
-        else launch_dec_a(da, st);
-        ctx->prof_end(e0, st);
-        ctx->cls = PROF_CT3;
         DecBArgs db{};
         db.y2 = y2; db.w3 = ctx->dec_ct[2].Wp; db.b3 = ctx->dec_ct[2].bias; db.w4 = ctx->dec_wf; db.b4 = ctx->dec_bf;
         db.rows = c; db.live = live_of(nc, m0); db.m0 = m0; db.rows_per_group = nc.rows_per_group; db.gm = nc.gm; db.reward0 = reward0; db.store0 = store0;
         db.val = val; db.parts = split ? 4 : 1; db.valq = split ? val : nullptr; db.po = po_store; db.reward_intent = (int)ctx->reward_intent;
-        e0 = ctx->prof_begin(st);
+        ProfSpan span(ctx, PROF_CT3, st);
         if (ctx->mfma_bf16x3 && ct3_16 && ctx->ct3_b3 && !split) {      // opt-in experiment
             db.w3b3 = ctx->ct3_b3; db.split = (int)ctx->mfma_bf16x3; db.w3s = ctx->s_ct3; db.w3s_inv = 1.0f / ctx->s_ct3;
             launch_dec_b_b3(db, st);
         }
         else launch_dec_b(db, st);
-        ctx->prof_end(e0, st);
     }
-    ctx->cls = PROF_OTHER;
-    ctx->last_macs += (int64_t)N * ctx->mac_dec;
     return 0;
 }
 
 // ModelDown.qs_net over N rows; o is [N][4096]; out enc [N][32] (mean 0..9, logvar 10..19).
 int run_encoder(efe_ctx* ctx, const float* o, int N, const NoiseCfg& nc, float* enc, hipStream_t st) {
     if (ctx->generic) return run_encoder_g(ctx, o, N, nc, enc, st);
-    const int C = (int)std::min<int64_t>(ctx->enc_chunk, N);
-    float* c4 = ctx->allocT<float>((size_t)C * 9 * 64);
-    float* hA = ctx->allocT<float>((size_t)C * 256);
-    float* hB = ctx->allocT<float>((size_t)C * 256);
+    const EncPlan p = enc_plan(ctx, N);
+    const int C = p.C;
+    float* c4 = ctx->allocT<float>(p.c4);
+    float* hA = ctx->allocT<float>(p.hA);
+    float* hB = ctx->allocT<float>(p.hB);
     if (!c4 || !hA || !hB) return 1;
+    ctx->last_macs += (int64_t)N * ctx->mac_enc;
     for (int m0 = 0; m0 < N; m0 += C) {
         const int c = std::min(C, N - m0);
-        ctx->cls = PROF_ENC;
         EncArgs ea{};
         ea.o = o + (size_t)m0 * 4096; ea.out = c4; ea.w1 = ctx->enc_w1; ea.b1 = ctx->enc_b1;
         ea.w2 = ctx->enc_conv[0].Wp; ea.b2 = ctx->enc_conv[0].bias; ea.w3 = ctx->enc_conv[1].Wp; ea.b3 = ctx->enc_conv[1].bias;
         ea.w4 = ctx->enc_conv[2].Wp; ea.b4 = ctx->enc_conv[2].bias; ea.rows = c; ea.live = live_of(nc, m0);
-        hipEvent_t e0 = ctx->prof_begin(st);
-        launch_enc_trunk(ea, st);
-        ctx->prof_end(e0, st);
-        if (!ctx->head_unfused) head(ctx, true, c4, enc + (size_t)m0 * 32, c, nc, m0, st);
-        else {
-            fc(ctx, ctx->enc_fc[0], c4, 576, 0, hA, 256, c, true, true, TAG_ENC + 0, nc, m0, st);
-            fc(ctx, ctx->enc_fc[1], hA, 256, 0, hB, 256, c, true, true, TAG_ENC + 1, nc, m0, st);
-            fc(ctx, ctx->enc_fc[2], hB, 256, 0, hA, 256, c, true, true, TAG_ENC + 2, nc, m0, st);
-            fc(ctx, ctx->enc_fc[3], hA, 256, 0, enc + (size_t)m0 * 32, 32, c, false, false, 0, nc, m0, st);
+        {
+            ProfSpan span(ctx, PROF_ENC, st);
+            launch_enc_trunk(ea, st);
         }
+        dense_head(ctx, true, c4, 576, enc + (size_t)m0 * 32, 32, hA, hB, c, nc, m0, st);
     }
-    ctx->cls = PROF_OTHER;
-    ctx->last_macs += (int64_t)N * ctx->mac_enc;
     return 0;
 }
 
@@ -647,10 +798,9 @@ int run_habit(efe_ctx* ctx, const float* s16 /*[M][16]*/, int M, float* l32 /*[M
     float* h2 = ctx->allocT<float>((size_t)M * 128);
     if (!h1 || !h2) return 1;
     NoiseCfg nc;
-    ctx->cls = PROF_OTHER;
-    fc(ctx, ctx->top[0], s16, 16, 0, h1, 128, M, true, false, 0, nc, 0, st);
-    fc(ctx, ctx->top[1], h1, 128, 0, h2, 128, M, true, false, 0, nc, 0, st);
-    fc(ctx, ctx->top[2], h2, 128, 0, l32, 32, M, false, false, 0, nc, 0, st);
+    fc(ctx, PROF_OTHER, ctx->top[0], s16, 16, 0, h1, 128, M, true, false, 0, nc, 0, st);
+    fc(ctx, PROF_OTHER, ctx->top[1], h1, 128, 0, h2, 128, M, true, false, 0, nc, 0, st);
+    fc(ctx, PROF_OTHER, ctx->top[2], h2, 128, 0, l32, 32, M, false, false, 0, nc, 0, st);
     ctx->last_macs += (int64_t)M * ctx->mac_habit;
     return 0;
 }
@@ -671,32 +821,29 @@ struct CoreIO {
 // calculate_G for D chained stages (torchmodel.py:236-243, 270-300)
 int run_core(efe_ctx* ctx, const CoreIO& io, hipStream_t st) {
     const int R = io.R, D = io.D, S = io.S;
-    float* tr_all = io.pre_tr ? io.pre_tr : ctx->allocT<float>((size_t)D * 2 * S * R * 32);
-    float* dec_in = ctx->allocT<float>((size_t)D * 3 * S * R * 16);
-    float* xbuf = ctx->allocT<float>((size_t)2 * R * 16);
-    const bool vsplit = dec_split(ctx, D * 3 * S * R);          // small decoder launch: per-image sums arrive as four quarter sums
-    float* val = ctx->allocT<float>((size_t)D * 3 * S * R * (vsplit ? 4 : 1));
-    float* po_store = ctx->allocT<float>((size_t)D * S * R * ctx->img_store);
-    float* enc = ctx->allocT<float>((size_t)D * S * R * 32);
-    float* terms_tmp = io.terms ? nullptr : ctx->allocT<float>((size_t)3 * R);
+    const CorePlan plan = core_plan(ctx, R, D, S, !io.pre_tr, !io.terms);
+    float* tr_all = io.pre_tr ? io.pre_tr : ctx->allocT<float>(plan.tr_all);
+    float* dec_in = ctx->allocT<float>(plan.dec_in);
+    float* xbuf = ctx->allocT<float>(plan.xbuf);
+    float* val = ctx->allocT<float>(plan.val);
+    float* po_store = ctx->allocT<float>(plan.po_store);
+    float* enc = ctx->allocT<float>(plan.enc);
+    float* terms_tmp = io.terms ? nullptr : ctx->allocT<float>(plan.terms_tmp);
     if (!tr_all || !dec_in || !xbuf || !val || !po_store || !enc) return 1;
+    // the noise of a pass over the R logical rows: the call's keys and row identities, the pass's group map
+    auto noise = [&](const GroupMap& gm, const uint8_t* mask) { return make_noise(io.k0, io.k1, R, io.row_offset, gm, io.ids, io.mask_div, mask); };
 
     const float* x = io.x0;
     for (int t = 0; t < D; ++t) {
         float* tr = tr_all + (size_t)t * 2 * S * R * 32;
-        NoiseCfg nc; nc.k0 = io.k0; nc.k1 = io.k1; nc.rows_per_group = R; nc.row_offset = io.row_offset;
         if (io.pre_tr) {
             // trajectory mode behind k_sim_chain: it has written both groups
         } else if (io.given_mean) {
             // trajectory mode: group T1 is supplied, only the loop-2 transition runs
             launch_fill_tr(io.given_mean, io.given_logvar, tr, R, st);
-            nc.gm = GroupMap{1, 1, {PASS_T2, 0, 0}, io.stage0 + (uint32_t)t, 0};
-            nc.gm.ids = io.ids; nc.gm.ids_div = io.mask_div;
-            if (run_mid(ctx, x, R, R, tr + (size_t)R * 32, nc, st)) return 1;
+            if (run_mid(ctx, x, R, R, tr + (size_t)R * 32, noise(GroupMap{1, 1, {PASS_T2, 0, 0}, io.stage0 + (uint32_t)t, 0}, nullptr), st)) return 1;
         } else {
-            nc.gm = GroupMap{2 * S, S, {PASS_T1, PASS_T2, 0}, io.stage0 + (uint32_t)t, 0};
-            nc.gm.ids = io.ids; nc.gm.ids_div = io.mask_div;
-            if (run_mid(ctx, x, R, 2 * S * R, tr, nc, st)) return 1;
+            if (run_mid(ctx, x, R, 2 * S * R, tr, noise(GroupMap{2 * S, S, {PASS_T1, PASS_T2, 0}, io.stage0 + (uint32_t)t, 0}, nullptr), st)) return 1;
         }
         TransPostArgs p{};
         p.tr = tr; p.x = x; p.eps_inj = io.eps ? io.eps + (size_t)t * 3 * S * R * 10 : nullptr;
@@ -712,22 +859,11 @@ int run_core(efe_ctx* ctx, const CoreIO& io, hipStream_t st) {
         launch_trans_post(p, st);
         x = nx;
     }
-    {   // one batched decoder pass over D x 3S groups
-        NoiseCfg nc; nc.k0 = io.k0; nc.k1 = io.k1; nc.rows_per_group = R; nc.row_offset = io.row_offset;
-        nc.gm = GroupMap{3 * S, S, {PASS_D1, PASS_D2A, PASS_D2B}, io.stage0, 0};
-        nc.gm.ids = io.ids; nc.gm.ids_div = io.mask_div;
-        nc.mask = io.mask; nc.mask_div = io.mask_div;
-        if (run_decoder(ctx, dec_in, D * 3 * S * R, nc, 1, 1, val, po_store, st)) return 1;
-    }
-    {   // one batched encoder pass over the D x S loop-1 images
-        NoiseCfg nc; nc.k0 = io.k0; nc.k1 = io.k1; nc.rows_per_group = R; nc.row_offset = io.row_offset;
-        nc.gm = GroupMap{S, S, {PASS_E1, 0, 0}, io.stage0, 0};
-        nc.gm.ids = io.ids; nc.gm.ids_div = io.mask_div;
-        nc.mask = io.mask; nc.mask_div = io.mask_div;
-        if (run_encoder(ctx, po_store, D * S * R, nc, enc, st)) return 1;
-    }
+    // one batched decoder pass over D x 3S groups, one batched encoder pass over the D x S loop-1 images
+    if (run_decoder(ctx, dec_in, D * 3 * S * R, noise(GroupMap{3 * S, S, {PASS_D1, PASS_D2A, PASS_D2B}, io.stage0, 0}, io.mask), 1, 1, val, po_store, st)) return 1;
+    if (run_encoder(ctx, po_store, D * S * R, noise(GroupMap{S, S, {PASS_E1, 0, 0}, io.stage0, 0}, io.mask), enc, st)) return 1;
     TermsArgs ta{};
-    ta.val = val; ta.valq = vsplit ? val : nullptr; ta.tr = tr_all; ta.enc = enc; ta.D = D; ta.S = S; ta.R = R;
+    ta.val = val; ta.valq = plan.vsplit ? val : nullptr; ta.tr = tr_all; ta.enc = enc; ta.D = D; ta.S = S; ta.R = R;
     // term0 of an image = 10 * mean over the pixels that count (torchmodel.py:212: all 4096, or the 192 bar pixels of the
     // upstream-intent variant); the generic geometries use the sum form of the reference's resolution-32 branch (torchmodel.py:214)
     ta.reward_div = ctx->generic ? 0.0f : (ctx->reward_intent ? 192.0f : 4096.0f);
@@ -813,12 +949,6 @@ struct Call {
     }
 };
 
-// the noise of a single-group network call (efe_transition / efe_decoder / efe_encoder)
-NoiseCfg noise_cfg(const efe_noise* nz, int M) {
-    NoiseCfg nc; nc.k0 = (uint32_t)nz->seed; nc.k1 = (uint32_t)(nz->seed >> 32); nc.rows_per_group = M; nc.row_offset = nz->row_offset;
-    nc.gm = GroupMap{1, 1, {nz->pass, 0, 0}, nz->stage, nz->sample};
-    return nc;
-}
 int mcts_tree(efe_ctx* ctx, const efe_mcts_tree* t, MctsTree& o) {
     if (!t || !t->W || !t->N || !t->Qpi || !t->child || !t->S || t->E < 1 || t->cap < 1 || t->A < 1 || t->A > 8 || t->s_dim < 1)
         return ctx->fail("efe_mcts: bad tree");
@@ -839,11 +969,6 @@ void fe_omega(FeArgs& a, const efe_fe_params* p) {
     a.omega_mode = p->omega_mode; a.omega_in = p->omega; a.omega_scalar = p->omega_scalar;
     a.oa_a = p->a; a.oa_b = p->b; a.oa_c = p->c; a.oa_d = p->d;
 }
-NoiseCfg fe_noise(uint64_t seed, uint32_t pass, uint32_t sample, uint32_t stage, uint32_t row_offset, int M) {
-    NoiseCfg nc; nc.k0 = (uint32_t)seed; nc.k1 = (uint32_t)(seed >> 32); nc.rows_per_group = M; nc.row_offset = row_offset;
-    nc.gm = GroupMap{1, 1, {pass, 0, 0}, stage, sample};
-    return nc;
-}
 // the observation as the encoder reads it: NCHW as given (dSprites), NHWC4 in scratch (generic geometry)
 const float* fe_obs(efe_ctx* ctx, const float* o, int M, hipStream_t st) {
     if (!ctx->generic) return o;
@@ -862,13 +987,13 @@ int fe_down(efe_ctx* ctx, const float* dec_in, int M, const NoiseCfg& base, cons
     if ((!direct && !po_s) || !val) return 1;
     for (int m0 = 0; m0 < M; m0 += C) {
         const int c = std::min(C, M - m0);
-        const Arena mark = ctx->arena;
+        const Arena::Mark mark = ctx->arena.mark();
         NoiseCfg nc = base; nc.rows_per_group = c; nc.row_offset = base.row_offset + (uint32_t)m0;
         float* img = po_s ? po_s : po1 + (size_t)m0 * ctx->img_store;
         if (run_decoder(ctx, dec_in + (size_t)m0 * 16, c, nc, 0, 1, val, img, st)) return 1;
         if (ctx->generic && po1) launch_to_nchw(img, po1 + (size_t)m0 * ctx->chan * HW, c, HW, ctx->chan, st);
         launch_fe_down(a, img, m0, c, st);
-        ctx->arena.cur = mark.cur; ctx->arena.off = mark.off; ctx->arena.used_total = mark.used_total;
+        ctx->arena.rewind(mark);
     }
     return 0;
 }
@@ -1048,35 +1173,122 @@ static void drop_split_planes(efe_ctx* ctx) {
 static int pack_fc4_b3(efe_ctx* ctx, int mode) {
     drop_split_planes(ctx);
     const int npl = mode == 2 ? 2 : 3;
-    auto upload = [&](uint16_t*& dst, const std::vector<uint16_t>& v) -> int {
-        if (hipMalloc((void**)&dst, v.size() * 2) != hipSuccess) { dst = nullptr; return 1; }
-        ctx->wbufs.push_back(dst);
-        return hipMemcpy(dst, v.data(), v.size() * 2, hipMemcpyHostToDevice) != hipSuccess;
-    };
     auto fail = [&](const char* what) { drop_split_planes(ctx); return ctx->fail(std::string("split-operand planes: ") + what); };
     const HostTensor* w = need(ctx, "down.po_net.9.weight", {16384, 256});
     if (!w) { drop_split_planes(ctx); return 1; }
-    std::vector<int> rowp(16384);
-    for (int p = 0; p < 256; ++p) for (int c = 0; c < 64; ++c) rowp[p * 64 + c] = c * 256 + p;
+    const std::vector<int> rowp = nhwc_perm(64, 256);
     std::vector<uint16_t> planes((size_t)16384 * 256 * npl);
     ctx->s_fc4 = pack_dense_split(mode, w->data.data(), rowp.data(), 16384, 256, planes.data());
-    if (upload(ctx->fc4_b3, planes)) return fail("po_net.9");
-    const char* ck[2] = {"down.po_net.13", "down.po_net.15"};
-    for (int i = 0; i < 2; ++i) {
-        const HostTensor* cw = need(ctx, std::string(ck[i]) + ".weight", {64, 64, 3, 3});
+    if (!(ctx->fc4_b3 = upload(ctx, planes))) return fail("po_net.9");
+    for (int i = 0; i < 3; ++i) {
+        const LayerSpec& s = DEC_CT[i];
+        const HostTensor* cw = need(ctx, std::string(s.key) + ".weight", {s.in, s.out, 3, 3});
         if (!cw) { drop_split_planes(ctx); return 1; }
-        std::vector<uint16_t> cp((size_t)9 * 64 * 64 * npl);
-        ctx->s_ct[i] = pack_conv_split(mode, cw->data.data(), 64, 64, cp.data());
-        if (upload(ctx->ct_b3[i], cp)) return fail(ck[i]);
-    }
-    {
-        const HostTensor* cw = need(ctx, "down.po_net.17.weight", {64, 32, 3, 3});
-        if (!cw) { drop_split_planes(ctx); return 1; }
-        std::vector<uint16_t> cp((size_t)4 * 9 * npl * 64 * 8);
-        ctx->s_ct3 = pack_convt3_split(mode, cw->data.data(), cp.data());
-        if (upload(ctx->ct3_b3, cp)) return fail("po_net.17");
+        if (i < 2) {
+            std::vector<uint16_t> cp((size_t)9 * 64 * 64 * npl);
+            ctx->s_ct[i] = pack_conv_split(mode, cw->data.data(), 64, 64, cp.data());
+            if (!(ctx->ct_b3[i] = upload(ctx, cp))) return fail(s.key);
+        } else {
+            std::vector<uint16_t> cp((size_t)4 * 9 * npl * 64 * 8);
+            ctx->s_ct3 = pack_convt3_split(mode, cw->data.data(), cp.data());
+            if (!(ctx->ct3_b3 = upload(ctx, cp))) return fail(s.key);
+        }
     }
     ctx->split_packed = mode;
+    return 0;
+}
+
+// a dense net in both packed forms: 32x32x2 tiles for k_dense (the layer-by-layer path) and 16x16x4 tiles for the fused kernels
+static int pack_net(efe_ctx* ctx, int nl, LayerSpec (*layer)(int, int), Layer* L32, MlpW& L16) {
+    for (int i = 0; i < nl; ++i) {
+        const LayerSpec s = layer(i, ctx->pi_dim);
+        if (pack_linear(ctx, L32[i], s) || pack_linear16(ctx, L16, i, s)) return 1;
+    }
+    return 0;
+}
+static int pack_top(efe_ctx* ctx) { return pack_net(ctx, TOP_NL, top_layer, ctx->top, ctx->top16) || build_top_train(ctx); }
+static int pack_mid(efe_ctx* ctx) { return pack_net(ctx, MID_NL, mid_layer, ctx->mid, ctx->mid16); }
+// the geometry-independent dense layers of the decoder / encoder heads (the encoder's first layer: pack_encoder)
+static int pack_heads(efe_ctx* ctx) {
+    for (int i = 0; i < 3; ++i) {
+        if (pack_linear(ctx, ctx->dec_fc[i], DEC_HEAD[i]) || pack_linear16(ctx, ctx->dec16, i, DEC_HEAD[i])) return 1;
+        if (pack_linear(ctx, ctx->enc_fc[i + 1], ENC_HEAD[i]) || pack_linear16(ctx, ctx->enc16, i + 1, ENC_HEAD[i])) return 1;
+    }
+    return 0;
+}
+// encoder (torchmodel.py:84-104): the convolution stack, then the head's first layer
+static int pack_encoder(efe_ctx* ctx) {
+    const int C = ctx->chan, F = ctx->enc_hw[4] * ctx->enc_hw[4];
+    if (ctx->generic) {     // build-defined geometry: four k_conv_g layers ...
+        for (int i = 0; i < 4; ++i) if (pack_conv(ctx, ctx->g_enc[i], enc_conv_layer(i, C), false)) return 1;
+        // ... and layer 1 for the LDS-tiled kernel (generic_enc.hip): lane (co = lane & 31, h = lane >> 5) holds its two K operands of a tap
+        const HostTensor* w = need(ctx, "down.qs_net.0.weight", {32, C, 3, 3});
+        if (!w) return 1;
+        std::vector<float> p1(9 * 64 * 2, 0.f);
+        for (int t = 0; t < 9; ++t)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int i = 0; i < 2; ++i) {
+                    const int co = lane & 31, ci = 2 * i + (lane >> 5);
+                    if (ci < C) p1[(t * 64 + lane) * 2 + i] = w->data[((size_t)co * C + ci) * 9 + t];
+                }
+        if (!(ctx->g_enc1p = upload(ctx, p1))) return 1;
+    } else {                // Dynamic-dSprites (1 x 64 x 64), the fused trunk: conv1 (Cin = 1) runs on the VALU: w1[tap][co]
+        const WB t1 = weight_and_bias(ctx, "down.qs_net.0", {32, 1, 3, 3}, {32});
+        if (!t1) return 1;
+        std::vector<float> w1(288);
+        for (int t = 0; t < 9; ++t) for (int co = 0; co < 32; ++co) w1[t * 32 + co] = t1.W()[co * 9 + t];
+        if (!(ctx->enc_w1 = upload(ctx, w1)) || !(ctx->enc_b1 = upload(ctx, t1.b->data))) return 1;
+        for (int i = 0; i < 2; ++i) if (pack_conv(ctx, ctx->enc_conv[i], enc_conv_layer(i + 1, 1), false)) return 1;
+        // conv4 runs on v_mfma_f32_16x16x4_f32 (its 9 output pixels fill 9/16 of that tile, 9/32 of the 32-wide one):
+        // [tap][16-channel block of Cin][16-channel tile of Cout][lane = (m, q)][s] = W[16 mt + m][16 blk + 4 q + s][tap]
+        const WB t4 = weight_and_bias(ctx, "down.qs_net.6", {64, 64, 3, 3}, {64});
+        if (!t4) return 1;
+        std::vector<float> p((size_t)9 * 4 * 4 * 256);
+        for (int t = 0; t < 9; ++t) for (int blk = 0; blk < 4; ++blk) for (int mt = 0; mt < 4; ++mt) for (int lane = 0; lane < 64; ++lane)
+            for (int s_ = 0; s_ < 4; ++s_)
+                p[((((size_t)t * 4 + blk) * 4 + mt) * 64 + lane) * 4 + s_] = t4.W()[((size_t)(16 * mt + (lane & 15)) * 64 + 16 * blk + 4 * (lane >> 4) + s_) * 9 + t];
+        if (upload_layer(ctx, ctx->enc_conv[2], 9, 64, 64, p, t4.B())) return 1;
+    }
+    // Flatten is channel-major c*F + p (torchmodel.py:93); the last convolution's output is NHWC p*64 + c
+    const std::vector<int> colp = nhwc_perm(64, F);
+    const LayerSpec fc0{"down.qs_net.9", 256, F * 64};
+    if (pack_linear(ctx, ctx->enc_fc[0], fc0, nullptr, colp.data()) || pack_linear16(ctx, ctx->enc16, 0, fc0, colp.data())) return 1;
+    ctx->enc16_kc0 = F * 4;
+    return 0;
+}
+// decoder (torchmodel.py:106-128) behind its head: Linear(256, 64 B^2), three ConvTranspose2d ([Cin][Cout][kh][kw]) and the final convolution
+static int pack_decoder(efe_ctx* ctx) {
+    const int C = ctx->chan, B = ctx->base;
+    {   // Unflatten(1, (64, B, B)) is channel-major c*B*B + p (torchmodel.py:119); the layer emits NHWC p*64 + c directly
+        const std::vector<int> rowp = nhwc_perm(64, B * B);
+        if (pack_linear(ctx, ctx->generic ? ctx->g_fc4 : ctx->dec_fc[3], LayerSpec{"down.po_net.9", B * B * 64, 256}, rowp.data())) return 1;
+    }
+    const WB tf = weight_and_bias(ctx, "down.po_net.19", {32, C, 3, 3}, {C});
+    if (!tf) return 1;
+    if (ctx->generic) {
+        for (int i = 0; i < 3; ++i) if (pack_conv(ctx, ctx->g_ct[i], DEC_CT[i], true)) return 1;
+        std::vector<float> wf(9 * 32 * 4, 0.f);         // [tap][ci][c padded to 4]
+        for (int t = 0; t < 9; ++t) for (int ci = 0; ci < 32; ++ci) for (int c = 0; c < C; ++c) wf[(t * 32 + ci) * 4 + c] = tf.W()[((size_t)ci * C + c) * 9 + t];
+        if (!(ctx->g_wf = upload(ctx, wf))) return 1;
+        for (int c = 0; c < 4; ++c) ctx->g_bf[c] = c < C ? tf.B()[c] : 0.f;
+        return 0;
+    }
+    if (ctx->mfma_bf16x3 && pack_fc4_b3(ctx, (int)ctx->mfma_bf16x3)) return 1;
+    for (int i = 0; i < 3; ++i) {
+        const LayerSpec& s = DEC_CT[i];
+        const WB t = weight_and_bias(ctx, s.key, {s.in, s.out, 3, 3}, {s.out});
+        if (!t) return 1;
+        if (i == 0) {       // po_net.13 (k_dec_a's layer 1): the 16 Winograd matrices as taps of the 32x32x2 form
+            const std::vector<float> U = convt_s1_wino_weights(t.W(), s.in, s.out);
+            if (upload_packed(ctx, ctx->dec_ct[0], 16, s.out, s.in, [&](int m, int co, int ci) { return U[((size_t)m * s.out + co) * s.in + ci]; }, t.B())) return 1;
+        } else {            // po_net.15 (layer 2 of k_dec_a / k_dec_a_s, decoder.hip f22_l2) and po_net.17 (k_dec_b4's ConvT3): the 16 F(2, 2) matrices
+            if (upload_layer(ctx, ctx->dec_ct[i], 16, s.out, s.in, pack_u16x16x4(convt_s2_f22_weights(t.W(), s.in, s.out), s.out), t.B())) return 1;
+        }
+    }
+    std::vector<float> wf(288);                         // [tap][ci]
+    for (int t = 0; t < 9; ++t) for (int ci = 0; ci < 32; ++ci) wf[t * 32 + ci] = tf.W()[ci * 9 + t];
+    if (!(ctx->dec_wf = upload(ctx, wf))) return 1;
+    ctx->dec_bf = tf.B()[0];
     return 0;
 }
 
@@ -1091,205 +1303,7 @@ int efe_commit_weights(efe_ctx* ctx) {
     }
     ctx->committed = false;
     if (refresh_top_host(ctx)) return 1;          // a trained habit net is never reverted: the host copy follows the device master copy first
-    const int A = ctx->pi_dim;
-    // habit net (torchmodel.py:19-25)
-    if (pack_linear(ctx, ctx->top[0], "top.qpi_net.0", 128, 10, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->top[1], "top.qpi_net.2", 128, 128, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->top[2], "top.qpi_net.4", A, 128, nullptr, nullptr)) return 1;
-    // transition net (torchmodel.py:41-52); input = cat[pi, s0] (torchmodel.py:59)
-    if (pack_linear(ctx, ctx->mid[0], "mid.ps_net.0", 512, A + 10, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->mid[1], "mid.ps_net.3", 512, 512, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->mid[2], "mid.ps_net.6", 512, 512, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->mid[3], "mid.ps_net.9", 20, 512, nullptr, nullptr)) return 1;
-    {   // the same two nets packed for the fused kernels
-        const char* mk[4] = {"mid.ps_net.0", "mid.ps_net.3", "mid.ps_net.6", "mid.ps_net.9"};
-        const int mo[4] = {512, 512, 512, 20}, mi[4] = {A + 10, 512, 512, 512};
-        for (int i = 0; i < 4; ++i) if (pack_linear16(ctx, ctx->mid16.w[i], ctx->mid16.b[i], mk[i], mo[i], mi[i])) return 1;
-        const char* tk[3] = {"top.qpi_net.0", "top.qpi_net.2", "top.qpi_net.4"};
-        const int to[3] = {128, 128, A}, ti[3] = {10, 128, 128};
-        for (int i = 0; i < 3; ++i) if (pack_linear16(ctx, ctx->top16.w[i], ctx->top16.b[i], tk[i], to[i], ti[i])) return 1;
-    }
-    if (build_top_train(ctx)) return 1;
-    // shared dense layers of the encoder / decoder heads
-    if (pack_linear(ctx, ctx->enc_fc[1], "down.qs_net.12", 256, 256, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->enc_fc[2], "down.qs_net.15", 256, 256, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->enc_fc[3], "down.qs_net.18", 20, 256, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->dec_fc[0], "down.po_net.0", 256, 10, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->dec_fc[1], "down.po_net.3", 256, 256, nullptr, nullptr)) return 1;
-    if (pack_linear(ctx, ctx->dec_fc[2], "down.po_net.6", 256, 256, nullptr, nullptr)) return 1;
-    {   // the heads packed for k_head (the encoder's first layer follows with the geometry below)
-        const char* dk[3] = {"down.po_net.0", "down.po_net.3", "down.po_net.6"};
-        const int di[3] = {10, 256, 256};
-        for (int i = 0; i < 3; ++i) if (pack_linear16(ctx, ctx->dec16.w[i], ctx->dec16.b[i], dk[i], 256, di[i])) return 1;
-        const char* ek[3] = {"down.qs_net.12", "down.qs_net.15", "down.qs_net.18"};
-        const int eo[3] = {256, 256, 20};
-        for (int i = 0; i < 3; ++i) if (pack_linear16(ctx, ctx->enc16.w[i + 1], ctx->enc16.b[i + 1], ek[i], eo[i], 256)) return 1;
-    }
-    const char* tk[3] = {"down.po_net.13", "down.po_net.15", "down.po_net.17"};
-    const int tci[3] = {64, 64, 64}, tco[3] = {64, 64, 32};
-    if (ctx->generic) {
-        // ---- build-defined geometry: same layer list as torchmodel.py:84-128 with the sizes the resolution implies
-        const int C = ctx->chan, B = ctx->base, F = ctx->enc_hw[4] * ctx->enc_hw[4];
-        const char* ck[4] = {"down.qs_net.0", "down.qs_net.2", "down.qs_net.4", "down.qs_net.6"};
-        const int cci[4] = {C, 32, 32, 64}, cco[4] = {32, 32, 64, 64};
-        for (int i = 0; i < 4; ++i) {
-            const HostTensor* w = need(ctx, std::string(ck[i]) + ".weight", {cco[i], cci[i], 3, 3});
-            const HostTensor* b = need(ctx, std::string(ck[i]) + ".bias", {cco[i]});
-            if (!w || !b) return 1;
-            const float* W = w->data.data(); const int Cin = cci[i];
-            if (upload_packed(ctx, ctx->g_enc[i], 9, cco[i], Cin,
-                              [&](int t, int co, int ci) { return W[((size_t)co * Cin + ci) * 9 + t]; }, b->data.data(), nullptr)) return 1;
-        }
-        {   // layer 1 for the LDS-tiled kernel (generic_enc.hip): lane (co = lane & 31, h = lane >> 5) holds its two K operands of a tap
-            const HostTensor* w = need(ctx, "down.qs_net.0.weight", {32, C, 3, 3});
-            if (!w) return 1;
-            std::vector<float> p1(9 * 64 * 2, 0.f);
-            for (int t = 0; t < 9; ++t)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int i = 0; i < 2; ++i) {
-                        const int co = lane & 31, ci = 2 * i + (lane >> 5);
-                        if (ci < C) p1[(t * 64 + lane) * 2 + i] = w->data[((size_t)co * C + ci) * 9 + t];
-                    }
-            HIPCHK(hipMalloc((void**)&ctx->g_enc1p, p1.size() * 4)); ctx->wbufs.push_back(ctx->g_enc1p);
-            HIPCHK(hipMemcpy(ctx->g_enc1p, p1.data(), p1.size() * 4, hipMemcpyHostToDevice));
-        }
-        {   // Flatten is channel-major c*F + p; conv4's output is NHWC p*64 + c
-            std::vector<int> colp((size_t)F * 64);
-            for (int p_ = 0; p_ < F; ++p_) for (int c = 0; c < 64; ++c) colp[(size_t)p_ * 64 + c] = c * F + p_;
-            if (pack_linear(ctx, ctx->enc_fc[0], "down.qs_net.9", 256, F * 64, nullptr, colp.data())) return 1;
-            if (pack_linear16(ctx, ctx->enc16.w[0], ctx->enc16.b[0], "down.qs_net.9", 256, F * 64, colp.data())) return 1;
-            ctx->enc16_kc0 = F * 4;
-        }
-        {   // Unflatten(1,(64,B,B)) is channel-major c*B*B + p; emitted NHWC p*64 + c
-            std::vector<int> rowp((size_t)B * B * 64);
-            for (int p_ = 0; p_ < B * B; ++p_) for (int c = 0; c < 64; ++c) rowp[(size_t)p_ * 64 + c] = c * B * B + p_;
-            if (pack_linear(ctx, ctx->g_fc4, "down.po_net.9", B * B * 64, 256, rowp.data(), nullptr)) return 1;
-        }
-        for (int i = 0; i < 3; ++i) {
-            const HostTensor* w = need(ctx, std::string(tk[i]) + ".weight", {tci[i], tco[i], 3, 3});
-            const HostTensor* b = need(ctx, std::string(tk[i]) + ".bias", {tco[i]});
-            if (!w || !b) return 1;
-            const float* W = w->data.data(); const int Cout = tco[i];
-            if (upload_packed(ctx, ctx->g_ct[i], 9, Cout, tci[i],
-                              [&](int t, int co, int ci) { return W[((size_t)ci * Cout + co) * 9 + t]; }, b->data.data(), nullptr)) return 1;
-        }
-        const HostTensor* w = need(ctx, "down.po_net.19.weight", {32, C, 3, 3});
-        const HostTensor* b = need(ctx, "down.po_net.19.bias", {C});
-        if (!w || !b) return 1;
-        std::vector<float> wf(9 * 32 * 4, 0.f);         // [tap][ci][c padded to 4]
-        for (int t = 0; t < 9; ++t) for (int ci = 0; ci < 32; ++ci) for (int c = 0; c < C; ++c) wf[(t * 32 + ci) * 4 + c] = w->data[((size_t)ci * C + c) * 9 + t];
-        HIPCHK(hipMalloc((void**)&ctx->g_wf, wf.size() * 4)); ctx->wbufs.push_back(ctx->g_wf);
-        HIPCHK(hipMemcpy(ctx->g_wf, wf.data(), wf.size() * 4, hipMemcpyHostToDevice));
-        for (int c = 0; c < 4; ++c) ctx->g_bf[c] = c < C ? b->data[c] : 0.f;
-        ctx->committed = true;
-        return 0;
-    }
-    // ---- Dynamic-dSprites geometry (1 x 64 x 64): fused kernels.  encoder (torchmodel.py:84-104): conv1 (Cin = 1) runs on the VALU: w1[tap][co]
-    {
-        const HostTensor* w = need(ctx, "down.qs_net.0.weight", {32, 1, 3, 3});
-        const HostTensor* b = need(ctx, "down.qs_net.0.bias", {32});
-        if (!w || !b) return 1;
-        std::vector<float> w1(288);
-        for (int t = 0; t < 9; ++t) for (int co = 0; co < 32; ++co) w1[t * 32 + co] = w->data[co * 9 + t];
-        HIPCHK(hipMalloc((void**)&ctx->enc_w1, 288 * 4)); ctx->wbufs.push_back(ctx->enc_w1);
-        HIPCHK(hipMalloc((void**)&ctx->enc_b1, 32 * 4)); ctx->wbufs.push_back(ctx->enc_b1);
-        HIPCHK(hipMemcpy(ctx->enc_w1, w1.data(), 288 * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(ctx->enc_b1, b->data.data(), 32 * 4, hipMemcpyHostToDevice));
-    }
-    const char* ck[3] = {"down.qs_net.2", "down.qs_net.4", "down.qs_net.6"};
-    const int cci[3] = {32, 32, 64}, cco[3] = {32, 64, 64};
-    for (int i = 0; i < 3; ++i) {
-        const HostTensor* w = need(ctx, std::string(ck[i]) + ".weight", {cco[i], cci[i], 3, 3});
-        const HostTensor* b = need(ctx, std::string(ck[i]) + ".bias", {cco[i]});
-        if (!w || !b) return 1;
-        const float* W = w->data.data(); const int Cin = cci[i];
-        if (upload_packed(ctx, ctx->enc_conv[i], 9, cco[i], Cin,
-                          [&](int t, int co, int ci) { return W[((size_t)co * Cin + ci) * 9 + t]; }, b->data.data(), nullptr)) return 1;
-        if (i == 2) {
-            // conv4 runs on v_mfma_f32_16x16x4_f32 (its 9 output pixels fill 9/16 of that tile, 9/32 of the 32-wide one): same buffer size,
-            // [tap][16-channel block of Cin][16-channel tile of Cout][lane = (m, q)][s] = W[16 mt + m][16 blk + 4 q + s][tap]
-            std::vector<float> p((size_t)9 * 4 * 4 * 256);
-            for (int t = 0; t < 9; ++t) for (int blk = 0; blk < 4; ++blk) for (int mt = 0; mt < 4; ++mt) for (int lane = 0; lane < 64; ++lane)
-                for (int s_ = 0; s_ < 4; ++s_)
-                    p[((((size_t)t * 4 + blk) * 4 + mt) * 64 + lane) * 4 + s_] = W[((size_t)(16 * mt + (lane & 15)) * 64 + 16 * blk + 4 * (lane >> 4) + s_) * 9 + t];
-            HIPCHK(hipMemcpy(ctx->enc_conv[2].Wp, p.data(), p.size() * 4, hipMemcpyHostToDevice));
-        }
-    }
-    {   // Flatten is channel-major c*9 + p (torchmodel.py:93); our conv4 output is NHWC p*64 + c
-        std::vector<int> colp(576);
-        for (int p = 0; p < 9; ++p) for (int c = 0; c < 64; ++c) colp[p * 64 + c] = c * 9 + p;
-        if (pack_linear(ctx, ctx->enc_fc[0], "down.qs_net.9", 256, 576, nullptr, colp.data())) return 1;
-        if (pack_linear16(ctx, ctx->enc16.w[0], ctx->enc16.b[0], "down.qs_net.9", 256, 576, colp.data())) return 1;
-        ctx->enc16_kc0 = 36;
-    }
-    {   // Unflatten(1,(64,16,16)) is channel-major c*256 + p (torchmodel.py:119); we emit NHWC p*64 + c directly
-        std::vector<int> rowp(16384);
-        for (int p = 0; p < 256; ++p) for (int c = 0; c < 64; ++c) rowp[p * 64 + c] = c * 256 + p;
-        if (pack_linear(ctx, ctx->dec_fc[3], "down.po_net.9", 16384, 256, rowp.data(), nullptr)) return 1;
-        if (ctx->mfma_bf16x3 && pack_fc4_b3(ctx, (int)ctx->mfma_bf16x3)) return 1;
-    }
-    for (int i = 0; i < 3; ++i) {   // ConvTranspose2d weights are [Cin][Cout][kh][kw]
-        const HostTensor* w = need(ctx, std::string(tk[i]) + ".weight", {tci[i], tco[i], 3, 3});
-        const HostTensor* b = need(ctx, std::string(tk[i]) + ".bias", {tco[i]});
-        if (!w || !b) return 1;
-        const float* W = w->data.data(); const int Cout = tco[i];
-        if (i == 0) {   // po_net.13 (k_dec_a's layer 1, decoder.hip wino_l1): Winograd F(2x2, 3x3) weights U_xi = G g G^T, xi = 4a + b, in fp64,
-                        // rounded once; g[u][v] = W[ci][co][2 - u][2 - v] (the correlation form of the stride-1 transposed conv)
-            static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-            std::vector<float> U((size_t)16 * 64 * 64);
-            for (int co = 0; co < 64; ++co)
-                for (int ci = 0; ci < 64; ++ci) {
-                    const float* k = W + ((size_t)ci * 64 + co) * 9;
-                    double Gg[4][3];
-                    for (int a = 0; a < 4; ++a)
-                        for (int v = 0; v < 3; ++v) {
-                            double s = 0;
-                            for (int u = 0; u < 3; ++u) s += Gm[a][u] * (double)k[(2 - u) * 3 + (2 - v)];
-                            Gg[a][v] = s;
-                        }
-                    for (int a = 0; a < 4; ++a)
-                        for (int b = 0; b < 4; ++b) {
-                            double s = 0;
-                            for (int v = 0; v < 3; ++v) s += Gg[a][v] * Gm[b][v];
-                            U[((size_t)(a * 4 + b) * 64 + co) * 64 + ci] = (float)s;
-                        }
-                }
-            if (upload_packed(ctx, ctx->dec_ct[0], 16, 64, 64, [&](int t, int co, int ci) { return U[((size_t)t * 64 + co) * 64 + ci]; },
-                              b->data.data(), nullptr)) return 1;
-            continue;
-        }
-        if (i == 2) {   // po_net.17 (k_dec_b4's ConvT3, v_mfma_f32_16x16x4_f32): the 16 F(2, 2) matrices U, packed
-                        // [U][channel half hf][chunk kc][lane][s] = U[16 hf + (lane & 15)][16 kc + 4 (lane >> 4) + s]
-            const std::vector<float> U = convt_s2_f22_weights(W, 64, 32);
-            if (upload_packed(ctx, ctx->dec_ct[2], 16, 32, 64, [](int, int, int) { return 0.f; }, b->data.data(), nullptr)) return 1;   // buffer + bias
-            std::vector<float> p(U.size());
-            for (int m = 0; m < 16; ++m) for (int hf = 0; hf < 2; ++hf) for (int kc = 0; kc < 4; ++kc) for (int lane = 0; lane < 64; ++lane)
-                for (int s_ = 0; s_ < 4; ++s_)
-                    p[((((size_t)m * 2 + hf) * 4 + kc) * 64 + lane) * 4 + s_] = U[((size_t)m * 32 + 16 * hf + (lane & 15)) * 64 + 16 * kc + 4 * (lane >> 4) + s_];
-            HIPCHK(hipMemcpy(ctx->dec_ct[2].Wp, p.data(), p.size() * 4, hipMemcpyHostToDevice));
-            continue;
-        }
-        {   // po_net.15 (layer 2 of k_dec_a / k_dec_a_s, decoder.hip f22_l2): the same 16 matrices for 64 output channels, packed
-            // [U][channel tile ct][chunk kc][lane][s] = U[16 ct + (lane & 15)][16 kc + 4 (lane >> 4) + s]
-            const std::vector<float> U = convt_s2_f22_weights(W, 64, 64);
-            if (upload_packed(ctx, ctx->dec_ct[1], 16, 64, 64, [](int, int, int) { return 0.f; }, b->data.data(), nullptr)) return 1;   // buffer + bias
-            std::vector<float> p(U.size());
-            for (int m = 0; m < 16; ++m) for (int ct = 0; ct < 4; ++ct) for (int kc = 0; kc < 4; ++kc) for (int lane = 0; lane < 64; ++lane)
-                for (int s_ = 0; s_ < 4; ++s_)
-                    p[((((size_t)m * 4 + ct) * 4 + kc) * 64 + lane) * 4 + s_] = U[((size_t)m * 64 + 16 * ct + (lane & 15)) * 64 + 16 * kc + 4 * (lane >> 4) + s_];
-            HIPCHK(hipMemcpy(ctx->dec_ct[1].Wp, p.data(), p.size() * 4, hipMemcpyHostToDevice));
-        }
-    }
-    {
-        const HostTensor* w = need(ctx, "down.po_net.19.weight", {32, 1, 3, 3});
-        const HostTensor* b = need(ctx, "down.po_net.19.bias", {1});
-        if (!w || !b) return 1;
-        std::vector<float> wf(288);
-        for (int t = 0; t < 9; ++t) for (int ci = 0; ci < 32; ++ci) wf[t * 32 + ci] = w->data[ci * 9 + t];
-        HIPCHK(hipMalloc((void**)&ctx->dec_wf, 288 * 4)); ctx->wbufs.push_back(ctx->dec_wf);
-        HIPCHK(hipMemcpy(ctx->dec_wf, wf.data(), 288 * 4, hipMemcpyHostToDevice));
-        ctx->dec_bf = b->data[0];
-    }
+    if (pack_top(ctx) || pack_mid(ctx) || pack_heads(ctx) || pack_encoder(ctx) || pack_decoder(ctx)) return 1;
     // the host copies stay: a caller may update a single tensor with efe_set_weight and commit again
     ctx->committed = true;
     return 0;
@@ -1418,7 +1432,7 @@ int efe_transition(efe_ctx* ctx, const float* pi, const float* s0, int M, const 
     float* tr = ctx->allocT<float>((size_t)M * 32);
     if (!x || !tr) return 1;
     launch_pack_x(pi, s0, x, M, ctx->pi_dim, S_DIM, st);
-    const NoiseCfg nc = noise_cfg(nz, M);
+    const NoiseCfg nc = pass_noise(nz, nz->pass, nz->sample, M);
     if (run_mid(ctx, x, 0, M, tr, nc, st)) return 1;
     launch_split_enc(tr, mean, logvar, M, st);
     if (ps1) launch_root_post(tr, nullptr, eps, nullptr, ps1, M, 0, nc.k0, nc.k1, nz->pass, nz->sample, nz->stage, nz->row_offset, ctx->pi_dim, st);
@@ -1432,7 +1446,7 @@ int efe_decoder(efe_ctx* ctx, const float* s, int M, const efe_noise* nz, float*
     float* val = ctx->allocT<float>((size_t)M * 4);        // (quarter sums when the launch is split; unused by this entry point)
     if (!x || !val) return 1;
     launch_pad16(s, x, M, S_DIM, st);
-    const NoiseCfg nc = noise_cfg(nz, M);
+    const NoiseCfg nc = pass_noise(nz, nz->pass, nz->sample, M);
     if (ctx->generic) {            // the generic path stores NHWC4 images: convert to the NCHW the API returns
         float* tmp = ctx->allocT<float>((size_t)M * ctx->img_store);
         if (!tmp) return 1;
@@ -1447,7 +1461,7 @@ int efe_encoder(efe_ctx* ctx, const float* o, int M, const efe_noise* nz, const 
     if (!o || !nz || M < 1) return ctx->fail("efe_encoder: bad arguments");
     float* enc = ctx->allocT<float>((size_t)M * 32);
     if (!enc) return 1;
-    const NoiseCfg nc = noise_cfg(nz, M);
+    const NoiseCfg nc = pass_noise(nz, nz->pass, nz->sample, M);
     if (ctx->generic) {
         float* o8 = ctx->allocT<float>((size_t)M * ctx->img_store);
         if (!o8) return 1;
@@ -1524,7 +1538,6 @@ int efe_top_grad(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, floa
     const int G = train_slabs(M), P = ctx->top_net.P;
     float* slabs = G == 1 ? grad : ctx->allocT<float>((size_t)G * P);
     if (!slabs) return 1;
-    ctx->cls = PROF_OTHER;
     launch_top_grad(TopGradArgs{ctx->top_net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
     if (G > 1) launch_slab_sum(slabs, G, P, grad, st);
     return call.finish();
@@ -1551,7 +1564,6 @@ int efe_train_top(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, flo
     const int G = train_slabs(M), P = ctx->top_net.P;
     float* slabs = ctx->allocT<float>((size_t)G * P);
     if (!slabs) return 1;
-    ctx->cls = PROF_OTHER;
     launch_top_grad(TopGradArgs{ctx->top_net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
     a.g = slabs; a.nslab = G; a.m = exp_avg; a.v = exp_avg_sq;      // k_adam forms the gradient by the same ascending slab sum as k_slab_sum
     ctx->top_dirty = true;
@@ -1589,16 +1601,16 @@ int efe_free_energy(efe_ctx* ctx, const float* o0, const float* o1, const float*
     const float* eps_t = eps ? eps + (size_t)M * S_DIM : nullptr;
     const float* eps_d = eps ? eps + (size_t)2 * M * S_DIM : nullptr;
     // s0 = encoder_with_sample(o0): pass FE_Q0; the habit head reads [s0 | 0] (root_post with pi_dim 0)
-    if (run_encoder(ctx, o0c, M, fe_noise(seed, PASS_FE_Q0, 0, stage, ro, M), enc0, st)) return 1;
+    if (run_encoder(ctx, o0c, M, pass_noise(nz, PASS_FE_Q0, 0, M), enc0, st)) return 1;
     launch_root_post(enc0, nullptr, eps_q0, x16, s0, M, 0, k0, k1, PASS_FE_Q0, 0, stage, ro, 0, st);
     if (run_habit(ctx, x16, M, l32, st)) return 1;
     launch_softmax4(l32, nullptr, q, logq, M, A, st);
     // qs1_mean, qs1_logvar = encoder(o1): pass FE_Q1
-    if (run_encoder(ctx, o1c, M, fe_noise(seed, PASS_FE_Q1, 0, stage, ro, M), enc1, st)) return 1;
+    if (run_encoder(ctx, o1c, M, pass_noise(nz, PASS_FE_Q1, 0, M), enc1, st)) return 1;
     if (out->qs1_mean || out->qs1_logvar) launch_split_enc(enc1, out->qs1_mean, out->qs1_logvar, M, st);
     // ps1 = transition_with_sample(pi0, s0): pass FE_T
     launch_pack_x(pi0, s0, xm, M, A, S_DIM, st);
-    if (run_mid(ctx, xm, 0, M, tr, fe_noise(seed, PASS_FE_T, 0, stage, ro, M), st)) return 1;
+    if (run_mid(ctx, xm, 0, M, tr, pass_noise(nz, PASS_FE_T, 0, M), st)) return 1;
     if (out->ps1_mean || out->ps1_logvar) launch_split_enc(tr, out->ps1_mean, out->ps1_logvar, M, st);
     if (out->ps1) launch_root_post(tr, nullptr, eps_t, nullptr, out->ps1, M, 0, k0, k1, PASS_FE_T, 0, stage, ro, A, st);
     {   // F_top, omega, F_mid
@@ -1611,10 +1623,10 @@ int efe_free_energy(efe_ctx* ctx, const float* o0, const float* o1, const float*
         launch_fe_top_mid(a, st);
     }
     // compute_loss_down: its own encoder pass over o1 + sample (FE_DOWN), the decoder (FE_DOWN), then k_fe_down
-    if (run_encoder(ctx, o1c, M, fe_noise(seed, PASS_FE_DOWN, 0, stage, ro, M), enc2, st)) return 1;
+    if (run_encoder(ctx, o1c, M, pass_noise(nz, PASS_FE_DOWN, 0, M), enc2, st)) return 1;
     launch_root_post(enc2, nullptr, eps_d, dec_in, out->qs1, M, 0, k0, k1, PASS_FE_DOWN, 0, stage, ro, 0, st);
     const FeArgs d = fe_down_args(ctx, M, o1, enc2, tr, tr + 10, 32, params, omega, out);
-    if (fe_down(ctx, dec_in, M, fe_noise(seed, PASS_FE_DOWN, 0, stage, ro, M), d, out->po1, st)) return 1;
+    if (fe_down(ctx, dec_in, M, pass_noise(nz, PASS_FE_DOWN, 0, M), d, out->po1, st)) return 1;
     return call.finish();
 }
 
@@ -1650,7 +1662,7 @@ int efe_loss_mid(efe_ctx* ctx, const float* s0, const float* pi0, const float* q
     float* tr = ctx->allocT<float>((size_t)M * 32);
     if (!xm || !tr) return 1;
     launch_pack_x(pi0, s0, xm, M, ctx->pi_dim, S_DIM, st);
-    const NoiseCfg nc = noise_cfg(nz, M);
+    const NoiseCfg nc = pass_noise(nz, nz->pass, nz->sample, M);
     if (run_mid(ctx, xm, 0, M, tr, nc, st)) return 1;
     if (out->ps1_mean || out->ps1_logvar) launch_split_enc(tr, out->ps1_mean, out->ps1_logvar, M, st);
     if (out->ps1) launch_root_post(tr, nullptr, eps, nullptr, out->ps1, M, 0, nc.k0, nc.k1, nz->pass, nz->sample, nz->stage, nz->row_offset, ctx->pi_dim, st);
@@ -1674,7 +1686,7 @@ int efe_loss_down(efe_ctx* ctx, const float* o1, const float* ps1_mean, const fl
     float* dec_in = ctx->allocT<float>((size_t)M * 16);
     const float* o1c = fe_obs(ctx, o1, M, st);
     if (!enc || !dec_in || !o1c) return 1;
-    const NoiseCfg nc = noise_cfg(nz, M);
+    const NoiseCfg nc = pass_noise(nz, nz->pass, nz->sample, M);
     if (run_encoder(ctx, o1c, M, nc, enc, st)) return 1;
     if (out->qs1_mean || out->qs1_logvar) launch_split_enc(enc, out->qs1_mean, out->qs1_logvar, M, st);
     launch_root_post(enc, nullptr, eps, dec_in, out->qs1, M, 0, nc.k0, nc.k1, nz->pass, nz->sample, nz->stage, nz->row_offset, 0, st);
@@ -1735,19 +1747,18 @@ int efe_rollout(efe_ctx* ctx, const float* o, const float* pi, int M, int steps,
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!o || !pi || !nz || !sum_G || M < 1 || steps < 1 || samples < 1 || samples > 65535) return ctx->fail("efe_rollout: bad arguments");
     const uint32_t k0 = (uint32_t)nz->seed, k1 = (uint32_t)(nz->seed >> 32);
-    float* enc0 = ctx->allocT<float>((size_t)M * 32);
-    float* x = ctx->allocT<float>((size_t)M * 16);
+    const RolloutPlan plan = rollout_plan(ctx, M);
+    float* enc0 = ctx->allocT<float>(plan.enc0);
+    float* x = ctx->allocT<float>(plan.x);
     if (!enc0 || !x) return 1;
     {   // root encode + reparameterize (torchmodel.py:228-234)
-        NoiseCfg nc; nc.k0 = k0; nc.k1 = k1; nc.rows_per_group = M; nc.row_offset = nz->row_offset;
-        nc.gm = GroupMap{1, 1, {PASS_ROOT, 0, 0}, nz->stage, 0};
         if (ctx->generic) {
-            float* o8 = ctx->allocT<float>((size_t)M * ctx->img_store);
+            float* o8 = ctx->allocT<float>(plan.o8);
             if (!o8) return 1;
             launch_to_nhwc4(o, o8, M, ctx->res * ctx->res, ctx->chan, st);
             o = o8;
         }
-        if (run_encoder(ctx, o, M, nc, enc0, st)) return 1;
+        if (run_encoder(ctx, o, M, pass_noise(nz, PASS_ROOT, 0, M), enc0, st)) return 1;
         launch_root_post(enc0, pi, eps, x, nullptr, M, calc_mean ? 1 : 0, k0, k1, PASS_ROOT, 0, nz->stage, nz->row_offset, ctx->pi_dim, st);
     }
     const int mean_mode = (per_stage_mean && calc_mean) ? 1 : 0;
@@ -1824,11 +1835,10 @@ int efe_simulate_rows(efe_ctx* ctx, const float* starting_s, int E, int depth, i
             split_launch = true;
         }
         sa.s0_traj = s0t; sa.ps1_traj = ps1t; sa.mean_traj = mt; sa.lv_traj = lvt; sa.pi0 = pi0; sa.Qpi0 = Qpi0; sa.pi_dim = ctx->pi_dim; sa.tr = pre_tr;
-        ctx->cls = PROF_MID;
-        hipEvent_t e0 = ctx->prof_begin(st);
-        launch_sim_chain(sa, st);
-        ctx->prof_end(e0, st);
-        ctx->cls = PROF_OTHER;
+        {
+            ProfSpan span(ctx, PROF_MID, st);
+            launch_sim_chain(sa, st);
+        }
         ctx->last_macs += (int64_t)E * T * (2 * ctx->mac_trans + ctx->mac_habit);      // the rollout's transition and the trajectory's loop-2 transition
     }
     if (trajectory_impl(ctx, s0t, ps1t, mt, lvt, pi0, E * T, k0, k1, nz->stage, nz->row_offset * (uint32_t)T,
@@ -1865,43 +1875,11 @@ int efe_reserve(efe_ctx* ctx, int64_t bytes) {
 }
 
 int64_t efe_rollout_scratch_bytes(efe_ctx* ctx, int M, int steps, int samples) {
-    // mirrors the allocations of efe_rollout (run_encoder for the root, run_core: run_mid per stage, run_decoder, run_encoder);
-    // tests/test_gpu_parity.py::test_reserve_no_growth keeps it honest
+    // the plans efe_rollout allocates from, nested as it calls them: its root with the root encode, then run_core.  Without a sum_terms
+    // output (counted here) run_core takes 3 M floats that it does not take with one.
     Call call(ctx, Mode::host);
     if (!call || M < 1 || steps < 1 || samples < 1) return 0;
-    const size_t A = (size_t)ctx->arena_align;
-    const int64_t dec_chunk = ctx->dec_chunk, enc_chunk = ctx->enc_chunk;
-    auto al = [A](size_t b) { return (b + A - 1) / A * A; };
-    if (ctx->generic) {
-        const size_t R = (size_t)M, D = (size_t)steps, S = (size_t)samples, B = (size_t)ctx->base, IS = ctx->img_store;
-        const int* hw = ctx->enc_hw;
-        size_t t = 0;
-        auto enc = [&](size_t N) {
-            const size_t C = std::min<size_t>(std::min<size_t>((size_t)enc_chunk, 8192), N);
-            t += al(C * hw[1] * hw[1] * 32 * 4) + al(C * hw[2] * hw[2] * 32 * 4) + al(C * hw[3] * hw[3] * 64 * 4) + al(C * hw[4] * hw[4] * 64 * 4) + 2 * al(C * 256 * 4);
-        };
-        t += al(R * 32 * 4) + al(R * 16 * 4) + al(R * IS * 4);
-        enc(R);
-        t += al(D * 2 * S * R * 32 * 4) + al(D * 3 * S * R * 16 * 4) + al(2 * R * 16 * 4) + al(D * 3 * S * R * 4) + al(D * S * R * IS * 4)
-           + al(D * S * R * 32 * 4) + al(3 * R * 4);
-        {   const size_t N = D * 3 * S * R, C = (size_t)generic_dec_chunk(ctx, (int64_t)N);
-            const bool fused = generic_dec_fused(ctx);
-            t += 2 * al(N * 256 * 4) + 2 * al(C * B * B * 64 * 4) + al(C * 4 * B * B * 64 * 4) + (fused ? 0 : al(C * (size_t)ctx->res * ctx->res * 32 * 4)); }
-        enc(D * S * R);
-        return (int64_t)(t + ((size_t)1 << 20));
-    }
-    const size_t R = (size_t)M, D = (size_t)steps, S = (size_t)samples;
-    size_t t = 0;
-    auto enc = [&](size_t N) { const size_t C = std::min<size_t>((size_t)enc_chunk, N); t += al(C * 576 * 4) + 2 * al(C * 256 * 4); };
-    t += al(R * 32 * 4) + al(R * 16 * 4);                     // enc0, x
-    enc(R);                                                   // root encode
-    t += al(D * 2 * S * R * 32 * 4) + al(D * 3 * S * R * 16 * 4) + al(2 * R * 16 * 4) + al(D * 3 * S * R * 4)
-       + al(D * S * R * 4096 * 4) + al(D * S * R * 32 * 4) + al(3 * R * 4);
-    t += D * 2 * al(2 * S * R * 512 * 4);                     // h1, h2 per stage
-    {   const size_t N = D * 3 * S * R, C = std::min<size_t>((size_t)dec_chunk, N);
-        t += 2 * al(N * 256 * 4) + al(C * 16384 * 4) + al(C * 65536 * 4) + al(((N + C - 1) / C) * 4); }
-    enc(D * S * R);
-    return (int64_t)(t + ((size_t)1 << 20));
+    return (int64_t)(plan_bytes(ctx, rollout_plan(ctx, M)) + encoder_bytes(ctx, M) + core_bytes(ctx, M, steps, samples, true) + SCRATCH_HEADROOM);
 }
 
 int efe_arena_stats(efe_ctx* ctx, int64_t* capacity_bytes, int64_t* high_water_bytes, int64_t* grow_count) {

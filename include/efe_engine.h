@@ -103,9 +103,11 @@ int efe_commit_weights(efe_ctx* ctx);
  *                   (range-check efe_rows.ids against efe_rows.n_total on the host before every _rows call: one synchronisation per call) */
 int efe_set_option(efe_ctx* ctx, const char* name, int64_t value);
 
-/* scratch arena: efe_reserve makes the arena one block of >= bytes (synchronises once); efe_rollout_scratch_bytes is what
- * efe_rollout(M, steps, samples) needs with the current chunk options; efe_arena_stats reports capacity, the largest use
- * of any call so far and how many hipMalloc calls the arena has made (outputs may be NULL). */
+/* scratch arena: efe_reserve makes the arena one block of >= bytes (synchronises once); efe_rollout_scratch_bytes is the exact
+ * arena use of efe_rollout(M, steps, samples) with the current options (sum_terms == NULL; 3 M floats less, rounded up to the
+ * arena's alignment, with a sum_terms output) plus 1 MiB of head-room.  efe_rollout can run at one sample per stage (calc_mean &&
+ * per_stage_mean): the returned value is then an upper bound.  efe_arena_stats reports capacity, the largest use of any call so
+ * far and how many hipMalloc calls the arena has made (outputs may be NULL). */
 int efe_reserve(efe_ctx* ctx, int64_t bytes);
 int64_t efe_rollout_scratch_bytes(efe_ctx* ctx, int M, int steps, int samples);
 int efe_arena_stats(efe_ctx* ctx, int64_t* capacity_bytes, int64_t* high_water_bytes, int64_t* grow_count);

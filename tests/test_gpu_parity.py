@@ -1123,21 +1123,44 @@ def test_custom_op_boundary_refuses_stale_handles_and_foreign_devices(weights_ca
     assert lib.efe_get_device(m2._engine.ctx, C.byref(dev), None, 0) == 0 and dev.value == 0
 
 
-def test_reserve_no_growth(models):
-    """efe_reserve + efe_rollout_scratch_bytes: after reserving for a rollout size, calls at that size never grow the arena"""
+def rollout_without_terms(m, o, pi, steps, samples, stage):
+    """efe_rollout through the C ABI with sum_terms = NULL: the call whose arena use efe_rollout_scratch_bytes counts (run_core then takes
+    its own 3 M floats for the terms; the torch op always passes a sum_terms output)"""
+    import ctypes as C
+    e = m._ready()
+    ot, pit = e.tensor(o, (-1, m.colour_channels, m.resolution, m.resolution)), e.tensor(pi, (-1, m.pi_dim))
+    G = torch.empty(ot.shape[0], device=ot.device)
+    torch.cuda.synchronize()
+    nz = m._noise(stage, 0, 0)
+    e.check(e.lib.efe_rollout(e.ctx, ot.data_ptr(), pit.data_ptr(), ot.shape[0], steps, samples, 0, 0, C.byref(nz), None, G.data_ptr(), None, None, None))
+    torch.cuda.synchronize()
+    return G
+
+
+@pytest.mark.parametrize('rows,steps,samples,option', [
+    pytest.param(2, 2, 2, None, id='quarter_sums'),                         # 24 decoder images: one launch of <= 128, the per-image sums are quarter sums (4 N floats)
+    pytest.param(24, 3, 4, ('dec_chunk', 100), id='dec_chunk_100'),         # 864 images in nine decoder launch groups: nine ticket counters
+    pytest.param(24, 3, 4, ('mid_unfused', 1), id='mid_unfused'),           # the layer-by-layer transition takes h1 / h2 in every stage
+])
+def test_reserve_no_growth(models, rows, steps, samples, option):
+    """efe_reserve + efe_rollout_scratch_bytes: after reserving for a rollout size, calls at that size never grow the arena, and the
+    reported size is exact: the arena use of efe_rollout at that size plus 1 MiB of head-room"""
     import daimc_amd
     m = daimc_amd.ActiveInferenceModel(10, 4, 0.0, 1.0, 1.0, device='cuda:0', seed=2)
-    need = m.reserve(24, 3, 4)
+    if option:
+        m.set_option(*option)
+    need = m.reserve(rows, steps, samples)
     st0 = m.arena_stats()
     assert st0['capacity_bytes'] >= need
-    o = synth.make_frames(35, 24)
-    pi = np.eye(4, dtype=np.float32)[np.arange(24) % 4]
-    for k in range(3):
-        m.calculate_G_repeated(o, pi, steps=3, samples=4, stage=10 * k)
-    torch.cuda.synchronize()
+    o = synth.make_frames(35, rows)
+    pi = np.eye(4, dtype=np.float32)[np.arange(rows) % 4]
+    for k in range(2):
+        m.calculate_G_repeated(o, pi, steps=steps, samples=samples, stage=10 * k)
+    rollout_without_terms(m, o, pi, steps, samples, 20)
     st1 = m.arena_stats()
     assert st1['grow_count'] == st0['grow_count'] and st1['capacity_bytes'] == st0['capacity_bytes']
-    assert 0 < st1['high_water_bytes'] <= need
+    print('need', need, 'high water', st1['high_water_bytes'], 'difference', need - st1['high_water_bytes'])
+    assert need - st1['high_water_bytes'] == 1 << 20
 
 
 def test_stream_switch_is_ordered(models):

@@ -21,7 +21,7 @@ Sites -> tests:
   k_root_post (kernels.hip:359)                  test_site_normals_rollout_root
   k_reparam (kernels.hip:469)                    test_device_normals_vs_mirror
   k_sim_chain (fused.hip:355/380/398)            test_simulate*, test_device_uniforms_bit_equal, test_site_normals_simulate
-  fe_noise (engine.hip)                          test_free_energy
+  pass_noise (engine.hip)                        test_free_energy
   k_env_* (kernels.hip:486/545/546)              test_environment
   generic launchers (GemmArgs filled separately) test_generic_geometry
 
@@ -461,7 +461,7 @@ def test_site_normals_simulate(setup, key):
 # ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('key', ['k1', 'stagewrap', 'rowwrap', 'all'])
 def test_free_energy(setup, weights, key):
-    """daimc_amd.free_energy (fe_noise: four passes), M = 3, against tests/free_energy_ref.py on the oracle keyed the same way, under
+    """daimc_amd.free_energy (pass_noise: four passes), M = 3, against tests/free_energy_ref.py on the oracle keyed the same way, under
     the fp64 rule that tests/test_free_energy_gpu.py applies to its stress rows"""
     import daimc_amd
     m, orc, seed, stage, ro = setup(key)
