@@ -14,7 +14,8 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_build_id', 'efe_reserve', 'efe_rollout_scratch_bytes', 'efe_arena_stats', 'efe_env_new_image', 'efe_create_cfg', 'efe_get_config', 'efe_get_device', 'efe_ctx_alive',
            'efe_calculate_g_rows', 'efe_simulate_rows', 'efe_mcts_step',
            'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down',
-           'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top']
+           'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top',
+           'efe_mid_grad', 'efe_train_mid']
 ABI_VERSION = 6
 
 
@@ -153,5 +154,7 @@ def load():
     lib.efe_top_grad.argtypes = [p, f32p, f32p, i, f32p, f32p, p]; lib.efe_top_grad.restype = i
     lib.efe_adam_step.argtypes = [p, C.c_char_p, f32p, f32p, f32p, ap, p]; lib.efe_adam_step.restype = i
     lib.efe_train_top.argtypes = [p, f32p, f32p, i, f32p, f32p, f32p, ap, p]; lib.efe_train_top.restype = i
+    lib.efe_mid_grad.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, f32p, f32p, f32p, p]; lib.efe_mid_grad.restype = i
+    lib.efe_train_mid.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, f32p, f32p, f32p, f32p, ap, p]; lib.efe_train_mid.restype = i
     _lib = lib
     return lib

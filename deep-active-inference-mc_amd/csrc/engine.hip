@@ -37,6 +37,14 @@ struct Layer {
     int cout = 0; int mtiles = 0; int ntaps = 1;
 };
 
+struct LayerSpec { const char* key; int out, in; };       // one layer of a network as the weight tables list it (see top_layer / mid_layer)
+struct TrainPart {
+    float* master = nullptr; TrainNet* net_dev = nullptr; TrainNet net{};
+    bool dirty = false;
+    int nl = 0; LayerSpec (*layer)(int, int) = nullptr;      // the part's layers (keys of `raw`)
+    const char* prefix = "";                                   // "top." / "mid.": the keys efe_set_weight must not revert
+};
+
 struct Arena {
     std::vector<std::pair<char*, size_t>> blocks;
     size_t cur = 0, off = 0, used_total = 0;
@@ -71,10 +79,10 @@ struct efe_ctx {
     int enc16_kc0 = 0;
     int64_t head_unfused = 0;      // option: 1 = layer-by-layer k_dense heads (A/B experiments)
     MlpW mid16{}, top16{};         // the same transition / habit weights packed for the fused 16x16x4 kernels (fused.hip)
-    // training (train.hip): the habit net's fp32 master copy (flat, the reference's parameters() order), its layer table on the host
-    // and on the device, and whether an optimiser step has made the device copy newer than `raw`
-    float* top_master = nullptr; TrainNet* top_net_dev = nullptr; TrainNet top_net{};
-    bool top_dirty = false;
+    // training (train.hip), per trainable part (habit net "top", transition net "ps_net"): the fp32 master copy (flat, the reference's
+    // parameters() order), its layer table on the host and on the device, and whether an optimiser step has made the device copy newer
+    // than `raw`
+    TrainPart top_train, mid_train;
     int64_t mid_unfused = 0;       // option: 1 = layer-by-layer k_dense transition (A/B experiments)
     float *enc_w1 = nullptr, *enc_b1 = nullptr, *dec_wf = nullptr;
     float dec_bf = 0.f;
@@ -287,8 +295,7 @@ std::vector<int> nhwc_perm(int channels, int positions) {
     return perm;
 }
 
-// one layer of a network as the weight tables below list it: a Linear(in, out), or a 3 x 3 convolution (out = cout, in = cin)
-struct LayerSpec { const char* key; int out, in; };
+// (LayerSpec: one layer of a network as the weight tables below list it: a Linear(in, out), or a 3 x 3 convolution (out = cout, in = cin))
 constexpr int TOP_NL = 3, MID_NL = 4;
 const char* const TOP_KEYS[TOP_NL] = {"top.qpi_net.0", "top.qpi_net.2", "top.qpi_net.4"};
 // habit net (torchmodel.py:19-25)
@@ -347,58 +354,73 @@ int pack_conv(efe_ctx* ctx, Layer& L, const LayerSpec& s, bool transposed) {
 }
 
 // ---- training tables (train.hip) ---------------------------------------------------------------------
-int top_param_count(int A) { int n = 0; for (int i = 0; i < TOP_NL; ++i) { const LayerSpec s = top_layer(i, A); n += s.out * s.in + s.out; } return n; }
+int part_param_count(int nl, LayerSpec (*layer)(int, int), int A) { int n = 0; for (int i = 0; i < nl; ++i) { const LayerSpec s = layer(i, A); n += s.out * s.in + s.out; } return n; }
 
-// the habit net's master copy and layer table, after its packed forms exist (pack_top): k_top_grad reads the master copy,
-// k_adam writes it and the packed copies
-int build_top_train(efe_ctx* ctx) {
+// a trainable part's master copy and layer table, after its packed forms exist (pack_net): the gradient kernel reads the master copy
+// (k_mid_grad: and the 16x16x4 copy), k_adam writes it and both packed copies.  drop_tag0 != 0: every hidden layer is followed by
+// MC-dropout under tag drop_tag0 + layer.
+int build_train(efe_ctx* ctx, TrainPart& tp, const char* prefix, int nl, LayerSpec (*layer)(int, int), const Layer* L32, const MlpW& L16, uint32_t drop_tag0) {
     const int A = ctx->pi_dim;
     TrainNet nt{};
-    nt.nl = TOP_NL;
+    nt.nl = nl;
     std::vector<float> flat;
-    for (int i = 0; i < TOP_NL; ++i) {
-        const LayerSpec s = top_layer(i, A);
+    for (int i = 0; i < nl; ++i) {
+        const LayerSpec s = layer(i, A);
         const WB t = weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
         if (!t) return 1;
         TrainLayer& L = nt.L[i];
-        L.in = s.in; L.out = s.out; L.relu = i < TOP_NL - 1; L.drop_tag = 0;
+        L.in = s.in; L.out = s.out; L.relu = i < nl - 1; L.drop_tag = (drop_tag0 && i < nl - 1) ? (int)drop_tag0 + i : 0;
         L.w_off = (int)flat.size(); flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
         L.b_off = (int)flat.size(); flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
-        L.kc32 = ctx->top[i].cin / 8; L.kc16 = (s.in + 15) / 16;
-        L.Wp32 = ctx->top[i].Wp; L.b32 = ctx->top[i].bias;
-        L.Wp16 = const_cast<float*>(reinterpret_cast<const float*>(ctx->top16.w[i])); L.b16 = const_cast<float*>(ctx->top16.b[i]);
+        L.kc32 = L32[i].cin / 8; L.kc16 = (s.in + 15) / 16;
+        L.Wp32 = L32[i].Wp; L.b32 = L32[i].bias;
+        L.Wp16 = const_cast<float*>(reinterpret_cast<const float*>(L16.w[i])); L.b16 = const_cast<float*>(L16.b[i]);
     }
     nt.P = (int)flat.size();
-    if (A > TRAIN_MAX_A) return ctx->fail("habit net outside the training kernels' limits");
-    if (!ctx->top_master) {
-        HIPCHK(hipMalloc((void**)&ctx->top_master, (size_t)nt.P * 4)); ctx->owned.push_back(ctx->top_master);
-        HIPCHK(hipMalloc((void**)&ctx->top_net_dev, sizeof(TrainNet))); ctx->owned.push_back(ctx->top_net_dev);
+    if (!tp.master) {
+        HIPCHK(hipMalloc((void**)&tp.master, (size_t)nt.P * 4)); ctx->owned.push_back(tp.master);
+        HIPCHK(hipMalloc((void**)&tp.net_dev, sizeof(TrainNet))); ctx->owned.push_back(tp.net_dev);
     }
-    nt.master = ctx->top_master;
-    HIPCHK(hipMemcpy(ctx->top_master, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->top_net_dev, &nt, sizeof(TrainNet), hipMemcpyHostToDevice));
-    ctx->top_net = nt;
-    ctx->top_dirty = false;
+    nt.master = tp.master;
+    HIPCHK(hipMemcpy(tp.master, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(tp.net_dev, &nt, sizeof(TrainNet), hipMemcpyHostToDevice));
+    tp.net = nt; tp.nl = nl; tp.layer = layer; tp.prefix = prefix;
+    tp.dirty = false;
     return 0;
+}
+int build_top_train(efe_ctx* ctx) {
+    if (ctx->pi_dim > TRAIN_MAX_A) return ctx->fail("habit net outside the training kernels' limits");
+    return build_train(ctx, ctx->top_train, "top.", TOP_NL, top_layer, ctx->top, ctx->top16, 0u);
+}
+// k_mid_grad's LDS map: one 16-channel input chunk, hidden layers of TRAIN_MID_WIDTH (whole 16-feature tiles), mean | logvar out
+int build_mid_train(efe_ctx* ctx) {
+    static_assert(MID_NL == TRAIN_MAX_LAYERS, "k_mid_grad keeps one LDS buffer per hidden layer of the table");
+    for (int i = 0; i < MID_NL; ++i) {
+        const LayerSpec s = mid_layer(i, ctx->pi_dim);
+        if ((i == 0 ? s.in > TRAIN_MID_IN : s.in != TRAIN_MID_WIDTH) || (i < MID_NL - 1 ? s.out != TRAIN_MID_WIDTH : s.out != 2 * S_DIM))
+            return ctx->fail("transition net outside the training kernel's limits");
+    }
+    return build_train(ctx, ctx->mid_train, "mid.", MID_NL, mid_layer, ctx->mid, ctx->mid16, TAG_MID);
 }
 
 // an optimiser step has made the device master copy newer than the host tensors: bring them up to date (synchronises), so that neither
 // a re-commit nor a partial efe_set_weight of the part reverts what was learnt
-int refresh_top_host(efe_ctx* ctx) {
-    if (!ctx->top_dirty) return 0;
+int refresh_train_host(efe_ctx* ctx, TrainPart& tp) {
+    if (!tp.dirty) return 0;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipDeviceSynchronize());
-    const TrainNet& nt = ctx->top_net;
+    const TrainNet& nt = tp.net;
     std::vector<float> flat((size_t)nt.P);
-    HIPCHK(hipMemcpy(flat.data(), ctx->top_master, flat.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(flat.data(), tp.master, flat.size() * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < nt.nl; ++i) {
         const TrainLayer& L = nt.L[i];
-        auto& w = ctx->raw[std::string(TOP_KEYS[i]) + ".weight"].data;
-        auto& b = ctx->raw[std::string(TOP_KEYS[i]) + ".bias"].data;
+        const std::string key = tp.layer(i, ctx->pi_dim).key;
+        auto& w = ctx->raw[key + ".weight"].data;
+        auto& b = ctx->raw[key + ".bias"].data;
         w.assign(flat.begin() + L.w_off, flat.begin() + L.w_off + (size_t)L.out * L.in);
         b.assign(flat.begin() + L.b_off, flat.begin() + L.b_off + L.out);
     }
-    ctx->top_dirty = false;
+    tp.dirty = false;
     return 0;
 }
 
@@ -1034,7 +1056,7 @@ int efe_create_cfg(efe_ctx** out, int device, int s_dim, int pi_dim, int channel
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return 2;
     DeviceScope dev_scope_(device);                 // the caller's current device is restored on every exit
     if (hipSetDevice(device) != hipSuccess) return 3;
-    if (init_small_kernels() || init_decoder_kernels() || init_fused_kernels() || init_generic_kernels() || init_bf16x3_kernels()) return 5;       // per device: a second context on another GPU needs them too
+    if (init_small_kernels() || init_decoder_kernels() || init_fused_kernels() || init_train_kernels() || init_generic_kernels() || init_bf16x3_kernels()) return 5;       // per device: a second context on another GPU needs them too
     efe_ctx* ctx = new efe_ctx();
     ctx->device = device;
     ctx->pi_dim = pi_dim; ctx->chan = channels; ctx->res = resolution;
@@ -1107,7 +1129,8 @@ const char* efe_last_error(efe_ctx* ctx) { return !ctx ? "null context" : regist
 int efe_set_weight(efe_ctx* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim) {
     if (!key || !data_host || !shape || ndim < 1 || ndim > 4) return 1;
     Call call(ctx, Mode::host); if (!call) return 1;
-    if (ctx->top_dirty && !strncmp(key, "top.", 4) && refresh_top_host(ctx)) return 1;      // the other tensors of a trained part keep what was learnt
+    for (TrainPart* tp : {&ctx->top_train, &ctx->mid_train})       // the other tensors of a trained part keep what was learnt
+        if (tp->dirty && !strncmp(key, tp->prefix, strlen(tp->prefix)) && refresh_train_host(ctx, *tp)) return 1;
     HostTensor t;
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
@@ -1207,7 +1230,7 @@ static int pack_net(efe_ctx* ctx, int nl, LayerSpec (*layer)(int, int), Layer* L
     return 0;
 }
 static int pack_top(efe_ctx* ctx) { return pack_net(ctx, TOP_NL, top_layer, ctx->top, ctx->top16) || build_top_train(ctx); }
-static int pack_mid(efe_ctx* ctx) { return pack_net(ctx, MID_NL, mid_layer, ctx->mid, ctx->mid16); }
+static int pack_mid(efe_ctx* ctx) { return pack_net(ctx, MID_NL, mid_layer, ctx->mid, ctx->mid16) || build_mid_train(ctx); }
 // the geometry-independent dense layers of the decoder / encoder heads (the encoder's first layer: pack_encoder)
 static int pack_heads(efe_ctx* ctx) {
     for (int i = 0; i < 3; ++i) {
@@ -1302,7 +1325,8 @@ int efe_commit_weights(efe_ctx* ctx) {
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
     }
     ctx->committed = false;
-    if (refresh_top_host(ctx)) return 1;          // a trained habit net is never reverted: the host copy follows the device master copy first
+    // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first
+    if (refresh_train_host(ctx, ctx->top_train) || refresh_train_host(ctx, ctx->mid_train)) return 1;
     if (pack_top(ctx) || pack_mid(ctx) || pack_heads(ctx) || pack_encoder(ctx) || pack_decoder(ctx)) return 1;
     // the host copies stay: a caller may update a single tensor with efe_set_weight and commit again
     ctx->committed = true;
@@ -1503,42 +1527,70 @@ int efe_reparameterize(efe_ctx* ctx, const float* mean, const float* logvar, int
     return call.finish();
 }
 
-// ---- training of the habit net (train.hip) ------------------------------------------------------------
+// ---- training of the habit net and the transition net (train.hip) -------------------------------------
 namespace {
-int adam_args(efe_ctx* ctx, const char* part, const efe_adam_params* hp, AdamArgs& a, const char* who) {
-    if (!part || strcmp(part, "top")) return ctx->fail(std::string(who) + ": part must be \"top\" (the only trainable part)");
+// "top" = ModelTop.qpi_net, "ps_net" = ModelMid.ps_net (the reference's module name; "mid" stays refused: a test of the habit-net
+// commit pins it as an unknown part)
+TrainPart* train_part(efe_ctx* ctx, const char* part, const char* who) {
+    if (part && !strcmp(part, "top")) return &ctx->top_train;
+    if (part && !strcmp(part, "ps_net")) return &ctx->mid_train;
+    ctx->fail(std::string(who) + ": part must be \"top\" (habit net) or \"ps_net\" (transition net), the trainable parts");
+    return nullptr;
+}
+int adam_args(efe_ctx* ctx, const TrainPart& tp, const efe_adam_params* hp, AdamArgs& a, const char* who) {
     if (!hp || hp->step < 1 || !(hp->lr >= 0.0) || !(hp->beta1 >= 0.0 && hp->beta1 < 1.0) || !(hp->beta2 >= 0.0 && hp->beta2 < 1.0) || !(hp->eps >= 0.0))
         return ctx->fail(std::string(who) + ": bad hyper-parameters (step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0)");
     // torch.optim.Adam's scalars, in double as Python computes them, rounded once
     const double bc1 = 1.0 - std::pow(hp->beta1, (double)hp->step), bc2 = 1.0 - std::pow(hp->beta2, (double)hp->step);
-    a.net = ctx->top_net_dev;
+    a.net = tp.net_dev;
     a.omb1 = (float)(1.0 - hp->beta1); a.b2 = (float)hp->beta2; a.omb2 = (float)(1.0 - hp->beta2);
     a.bc2_sqrt = (float)std::sqrt(bc2); a.step_size = (float)(hp->lr / bc1); a.eps = (float)hp->eps;
+    return 0;
+}
+// the arguments of k_mid_grad after efe_loss_mid's checks (params: omega per row or scalar; nz: the keys of every dropout mask)
+// (arrays_ok: the entry point's own arrays -- the gradient, or both moments -- are non-NULL)
+int mid_grad_args(efe_ctx* ctx, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, bool arrays_ok, MidGradArgs& a, const char* who) {
+    if (!s0 || !pi0 || !qs1_mean || !qs1_logvar || !nz || !arrays_ok || M < 1)
+        return ctx->fail(std::string(who) + ": bad arguments (s0, pi0, qs1_mean, qs1_logvar, params, nz and the gradient / state arrays must be non-NULL, M >= 1)");
+    if (fe_params(ctx, params, false, who)) return 1;
+    a.net = ctx->mid_train.net_dev;
+    a.s0 = s0; a.pi0 = pi0; a.q1_mean = qs1_mean; a.q1_lv = qs1_logvar;
+    a.omega_mode = params->omega_mode; a.omega_in = params->omega; a.omega_scalar = params->omega_scalar;
+    // (the kernel writes all three: scratch stands in for an output the caller does not want)
+    a.p1_mean = ps1_mean ? ps1_mean : ctx->allocT<float>((size_t)M * S_DIM);
+    a.p1_lv = ps1_logvar ? ps1_logvar : ctx->allocT<float>((size_t)M * S_DIM);
+    a.F_mid = F_mid ? F_mid : ctx->allocT<float>((size_t)M);
+    if (!a.p1_mean || !a.p1_lv || !a.F_mid) return 1;
+    a.M = M; a.A = ctx->pi_dim; a.S = S_DIM; a.inv_M = 1.0f / (float)M;
+    a.k0 = (uint32_t)nz->seed; a.k1 = (uint32_t)(nz->seed >> 32); a.row_offset = nz->row_offset;
+    a.stream = stream_id(nz->pass, nz->sample); a.stage = nz->stage;
     return 0;
 }
 }  // namespace
 
 int64_t efe_param_count(efe_ctx* ctx, const char* part) {
     Call call(ctx, Mode::host); if (!call) return 0;
-    if (!part || strcmp(part, "top")) { ctx->fail("efe_param_count: part must be \"top\""); return 0; }
-    return top_param_count(ctx->pi_dim);
+    if (!train_part(ctx, part, "efe_param_count")) return 0;
+    return !strcmp(part, "top") ? part_param_count(TOP_NL, top_layer, ctx->pi_dim) : part_param_count(MID_NL, mid_layer, ctx->pi_dim);
 }
 
 int efe_get_weights(efe_ctx* ctx, const char* part, float* dst, int64_t n, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    if (!part || strcmp(part, "top")) return ctx->fail("efe_get_weights: part must be \"top\"");
-    if (!dst || n != ctx->top_net.P) return ctx->fail("efe_get_weights: dst must hold efe_param_count(part) floats");
-    HIPCHK(hipMemcpyAsync(dst, ctx->top_master, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    const TrainPart* tp = train_part(ctx, part, "efe_get_weights"); if (!tp) return 1;
+    if (!dst || n != tp->net.P) return ctx->fail("efe_get_weights: dst must hold efe_param_count(part) floats");
+    HIPCHK(hipMemcpyAsync(dst, tp->master, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return call.finish();
 }
 
 int efe_top_grad(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, float* kl_pi, float* grad, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!s || !log_Ppi || !grad || M < 1) return ctx->fail("efe_top_grad: bad arguments (s, log_Ppi and grad must be non-NULL, M >= 1)");
-    const int G = train_slabs(M), P = ctx->top_net.P;
+    const TrainPart& tp = ctx->top_train;
+    const int G = train_slabs(M), P = tp.net.P;
     float* slabs = G == 1 ? grad : ctx->allocT<float>((size_t)G * P);
     if (!slabs) return 1;
-    launch_top_grad(TopGradArgs{ctx->top_net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
+    launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
     if (G > 1) launch_slab_sum(slabs, G, P, grad, st);
     return call.finish();
 }
@@ -1546,11 +1598,12 @@ int efe_top_grad(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, floa
 int efe_adam_step(efe_ctx* ctx, const char* part, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!grad || !exp_avg || !exp_avg_sq) return ctx->fail("efe_adam_step: grad, exp_avg and exp_avg_sq must be non-NULL");
+    TrainPart* tp = train_part(ctx, part, "efe_adam_step"); if (!tp) return 1;
     AdamArgs a{};
-    if (adam_args(ctx, part, hp, a, "efe_adam_step")) return 1;
+    if (adam_args(ctx, *tp, hp, a, "efe_adam_step")) return 1;
     a.g = grad; a.nslab = 1; a.m = exp_avg; a.v = exp_avg_sq;
-    ctx->top_dirty = true;
-    launch_adam(a, ctx->top_net.P, st);
+    tp->dirty = true;
+    launch_adam(a, tp->net.P, st);
     return call.finish();
 }
 
@@ -1559,14 +1612,47 @@ int efe_train_top(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, flo
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!s || !log_Ppi || !exp_avg || !exp_avg_sq || M < 1)
         return ctx->fail("efe_train_top: bad arguments (s, log_Ppi, exp_avg and exp_avg_sq must be non-NULL, M >= 1)");
+    TrainPart& tp = ctx->top_train;
     AdamArgs a{};
-    if (adam_args(ctx, "top", hp, a, "efe_train_top")) return 1;
-    const int G = train_slabs(M), P = ctx->top_net.P;
+    if (adam_args(ctx, tp, hp, a, "efe_train_top")) return 1;
+    const int G = train_slabs(M), P = tp.net.P;
     float* slabs = ctx->allocT<float>((size_t)G * P);
     if (!slabs) return 1;
-    launch_top_grad(TopGradArgs{ctx->top_net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
+    launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
     a.g = slabs; a.nslab = G; a.m = exp_avg; a.v = exp_avg_sq;      // k_adam forms the gradient by the same ascending slab sum as k_slab_sum
-    ctx->top_dirty = true;
+    tp.dirty = true;
+    launch_adam(a, P, st);
+    return call.finish();
+}
+
+int efe_mid_grad(efe_ctx* ctx, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M, const efe_fe_params* params,
+                 const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, float* grad, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    MidGradArgs g{};
+    if (mid_grad_args(ctx, s0, pi0, qs1_mean, qs1_logvar, M, params, nz, ps1_mean, ps1_logvar, F_mid, grad != nullptr, g, "efe_mid_grad")) return 1;
+    const int G = train_mid_slabs(M), P = ctx->mid_train.net.P;
+    g.slabs = G == 1 ? grad : ctx->allocT<float>((size_t)G * P);
+    if (!g.slabs) return 1;
+    launch_mid_grad(g, st);
+    if (G > 1) launch_slab_sum(g.slabs, G, P, grad, st);
+    return call.finish();
+}
+
+int efe_train_mid(efe_ctx* ctx, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp,
+                  void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    MidGradArgs g{};
+    if (mid_grad_args(ctx, s0, pi0, qs1_mean, qs1_logvar, M, params, nz, ps1_mean, ps1_logvar, F_mid, exp_avg && exp_avg_sq, g, "efe_train_mid")) return 1;
+    TrainPart& tp = ctx->mid_train;
+    AdamArgs a{};
+    if (adam_args(ctx, tp, hp, a, "efe_train_mid")) return 1;
+    const int G = train_mid_slabs(M), P = tp.net.P;
+    g.slabs = ctx->allocT<float>((size_t)G * P);
+    if (!g.slabs) return 1;
+    launch_mid_grad(g, st);
+    a.g = g.slabs; a.nslab = G; a.m = exp_avg; a.v = exp_avg_sq;    // the same ascending slab sum as k_slab_sum
+    tp.dirty = true;
     launch_adam(a, P, st);
     return call.finish();
 }

@@ -384,9 +384,9 @@ void launch_fe_down(const FeArgs& a, const float* po, int m0, int rows, hipStrea
 
 // ---- training of the small MLPs (train.hip): backward + Adam over a layer table -----------------------------------
 // A trainable part is a chain of Linear layers described by a DEVICE-RESIDENT table (built at efe_commit_weights): widths, the ReLU flag
-// of each layer's output, a slot for the Philox tag an MC-dropout mask would be regenerated from (0 = no dropout; the habit net has
-// none), the offsets of the layer's weight / bias inside the flat parameter vector (the reference's parameters() order, row-major) and
-// the packed forward copies k_adam refreshes.
+// of each layer's output, the Philox tag of the MC-dropout mask behind it (0 = no dropout: the habit net; the transition net's hidden
+// layers carry TAG_MID + layer, drawn in k_mid_grad's forward pass), the offsets of the layer's weight / bias inside the flat parameter
+// vector (the reference's parameters() order, row-major) and the packed forward copies k_adam refreshes.
 constexpr int TRAIN_MAX_LAYERS = 4;      // layers of a table
 constexpr int TRAIN_MAX_WIDTH = 128;     // widest activation k_top_grad keeps in LDS
 constexpr int TRAIN_MAX_SLABS = 64;      // workgroups (= partial-gradient slabs) of one k_top_grad launch
@@ -417,6 +417,26 @@ struct AdamArgs {
     float bc2_sqrt, step_size, eps;      // sqrt(1 - beta2^t), lr / (1 - beta1^t)
 };
 void launch_adam(const AdamArgs& a, int P, hipStream_t st);
+// the transition net ModelMid.ps_net (k_mid_grad): hidden layers up to TRAIN_MID_WIDTH wide, each ReLU + MC-dropout; one partial-gradient
+// slab is 2.17 MB (P = 543 252 at pi_dim 4), so the workgroup count has a cap of its own
+constexpr int TRAIN_MID_WIDTH = 512;     // widest hidden activation k_mid_grad keeps in LDS
+constexpr int TRAIN_MID_IN = 16;         // widest input (pi_dim + s_dim, padded to one 16-channel chunk)
+constexpr int TRAIN_MID_OUT = 32;        // widest output (2 s_dim, padded to two 16-feature tiles)
+constexpr int TRAIN_MID_SLABS = 8;       // workgroups (= slabs) of one k_mid_grad launch: 17 MB of scratch at the cap
+__host__ __device__ inline int train_mid_slabs(int M) { const int t = (M + 15) / 16; return t < TRAIN_MID_SLABS ? t : TRAIN_MID_SLABS; }
+struct MidGradArgs {
+    const TrainNet* net;                 // device pointer
+    const float* s0; const float* pi0;   // [M][s_dim], [M][A]: the input row is [pi0 | s0] (torchmodel.py:59)
+    const float* q1_mean; const float* q1_lv;   // [M][s_dim] posterior q(s1)
+    int omega_mode; const float* omega_in; float omega_scalar;      // 0 = omega_in [M], 1 = omega_scalar
+    float* p1_mean; float* p1_lv; float* F_mid; // outputs [M][s_dim], [M][s_dim], [M] (the host hands scratch for those the caller declines)
+    float* slabs;                        // [train_mid_slabs(M)][P]
+    int M, A, S;
+    float inv_M;
+    uint32_t k0, k1, row_offset, stream, stage;  // Philox key, global row of row 0, stream_id(pass, sample), stage
+};
+void launch_mid_grad(const MidGradArgs& a, hipStream_t st);
+int init_train_kernels();
 
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);

@@ -362,7 +362,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> loss_
 }
 
 // ---- training of the habit net (csrc/train.hip) ----
-// optimiser state updated in place: a contiguous float32 HIP tensor of efe_param_count("top") elements on the context's device
+// optimiser state updated in place: a contiguous float32 HIP tensor of efe_param_count(part) elements on the context's device
 float* state(Tensor& t, const char* name, int64_t P) {
     TORCH_CHECK(t.is_cuda(), "efe: ", name, " must be a HIP device tensor (there is no CPU fallback)");
     TORCH_CHECK((int)t.device().index() == tl_ctx_device, "efe: ", name, " is on device ", (int)t.device().index(), ", the engine context lives on device ", tl_ctx_device);
@@ -414,6 +414,50 @@ Tensor train_top(int64_t h, const Tensor& s_, const Tensor& lp_, Tensor exp_avg,
     return kl;
 }
 
+// ---- training of the transition net (csrc/train.hip k_mid_grad) ----
+// the inputs of compute_loss_mid, checked as loss_mid checks them
+struct MidIn { Tensor s0, pi0, qm, qv, keep; int M; efe_fe_params p; efe_noise nz; };
+MidIn mid_in(efe_ctx* c, const Tensor& s0_, const Tensor& pi0_, const Tensor& qm_, const Tensor& qv_, int64_t omega_mode, const OptT& omega,
+             double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample, int64_t row_offset) {
+    MidIn r;
+    r.s0 = in(s0_, "s0"); r.pi0 = in(pi0_, "Ppi_sampled"); r.qm = in(qm_, "qs1_mean"); r.qv = in(qv_, "qs1_logvar");
+    r.M = rows(r.s0, 10, "s0");
+    TORCH_CHECK(r.pi0.numel() == (int64_t)r.M * geo(c).A, "efe: Ppi_sampled must be [M, pi_dim]");
+    TORCH_CHECK(r.qm.numel() == (int64_t)r.M * 10 && r.qv.numel() == (int64_t)r.M * 10, "efe: qs1_mean and qs1_logvar must be [M, 10]");
+    r.p = fe_params(0.0, 0.0, 0.0, omega_mode, omega, r.keep, omega_scalar, r.M);
+    r.nz = noise(seed, stage, pass, sample, row_offset);
+    return r;
+}
+
+// d mean(F_mid) / d ps_net parameters (torchloss.py:76-86 up to optimizer.step) -> (F_mid [M], ps1_mean, ps1_logvar [M,10], grad [P])
+std::tuple<Tensor, Tensor, Tensor, Tensor> mid_grad(int64_t h, const Tensor& s0_, const Tensor& pi0_, const Tensor& qm_, const Tensor& qv_, int64_t omega_mode,
+                                                    const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample,
+                                                    int64_t row_offset) {
+    efe_ctx* c = CTX(h);
+    MidIn a = mid_in(c, s0_, pi0_, qm_, qv_, omega_mode, omega, omega_scalar, seed, stage, pass, sample, row_offset);
+    auto op = a.s0.options();
+    Tensor F = at::empty({a.M}, op), pm = at::empty({a.M, 10}, op), pv = at::empty({a.M, 10}, op), grad = at::empty({efe_param_count(c, "ps_net")}, op);
+    ok(c, efe_mid_grad(c, a.s0.data_ptr<float>(), a.pi0.data_ptr<float>(), a.qm.data_ptr<float>(), a.qv.data_ptr<float>(), a.M, &a.p, &a.nz, P(pm), P(pv),
+                       P(F), P(grad), stream_of(a.s0)));
+    return {F, pm, pv, grad};
+}
+
+// train_model_mid, torchloss.py:76-88 -> (ps1_mean, ps1_logvar, F_mid) of the weights before the step
+std::tuple<Tensor, Tensor, Tensor> train_mid(int64_t h, const Tensor& s0_, const Tensor& pi0_, const Tensor& qm_, const Tensor& qv_, int64_t omega_mode,
+                                             const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample,
+                                             int64_t row_offset, Tensor exp_avg, Tensor exp_avg_sq, double lr, double beta1, double beta2, double eps,
+                                             int64_t step) {
+    efe_ctx* c = CTX(h);
+    MidIn a = mid_in(c, s0_, pi0_, qm_, qv_, omega_mode, omega, omega_scalar, seed, stage, pass, sample, row_offset);
+    const int64_t NP = efe_param_count(c, "ps_net");
+    auto op = a.s0.options();
+    Tensor F = at::empty({a.M}, op), pm = at::empty({a.M, 10}, op), pv = at::empty({a.M, 10}, op);
+    const efe_adam_params hp = adam_params(lr, beta1, beta2, eps, step);
+    ok(c, efe_train_mid(c, a.s0.data_ptr<float>(), a.pi0.data_ptr<float>(), a.qm.data_ptr<float>(), a.qv.data_ptr<float>(), a.M, &a.p, &a.nz, P(pm), P(pv),
+                        P(F), state(exp_avg, "exp_avg", NP), state(exp_avg_sq, "exp_avg_sq", NP), &hp, stream_of(a.s0)));
+    return {pm, pv, F};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -435,6 +479,8 @@ TORCH_LIBRARY(efe, m) {
     m.def("top_grad(int ctx, Tensor s, Tensor log_Ppi) -> (Tensor kl_pi, Tensor grad)");
     m.def("adam_step(int ctx, str part, Tensor grad, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> ()");
     m.def("train_top(int ctx, Tensor s, Tensor log_Ppi, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> Tensor");
+    m.def("mid_grad(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset) -> (Tensor F_mid, Tensor ps1_mean, Tensor ps1_logvar, Tensor grad)");
+    m.def("train_mid(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> (Tensor ps1_mean, Tensor ps1_logvar, Tensor F_mid)");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -456,4 +502,6 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("top_grad", &top_grad);
     m.impl("adam_step", &adam_step);
     m.impl("train_top", &train_top);
+    m.impl("mid_grad", &mid_grad);
+    m.impl("train_mid", &train_mid);
 }

@@ -20,6 +20,13 @@
 // p, p + G, p + 2G, ... in ascending order; a tile's contribution to an element is one MFMA chain over its rows 0..15 in ascending
 // order (bias: a sequential sum), added to the workgroup's slab element by the one thread that owns it; the gradient is
 // ((slab_0 + slab_1) + slab_2) + ... in ascending p.  Two identical calls give identical bits.
+//
+// Training of the transition network ModelMid.ps_net (torchmodel.py:41-52) by train_model_mid (torchloss.py:76-88): one Adam step on
+// F_mid.mean(), F_mid = sum_k kl(q(s1) | p(s1 | s0, pi)) with precision omega (torchutils.py:7-8):
+//     kl = 0.5 (lv2 - log w - lv1) + (exp(lv1) + (mu1 - mu2)^2) / den - 0.5,   den = 2 exp(lv2) / w
+//     d/dmu2 = -(1/M) 2 (mu1 - mu2) / den,   d/dlv2 = (1/M) (0.5 - (exp(lv1) + (mu1 - mu2)^2) / den)          fp32, contraction off
+//   k_mid_grad : k_top_grad's structure for 512-wide hidden layers with MC-dropout (LDS map, chain scheme and its own reduction-order
+//                contract, G = min(T, 8): at the kernel).  k_slab_sum and k_adam serve both nets through their layer tables.
 #include "kernels.h"
 
 namespace efe {
@@ -90,7 +97,7 @@ __global__ void __launch_bounds__(256) k_top_grad(const TopGradArgs a) {
                     const int f = f0 + 4 * q + e;
                     float v = acc[e] + B[f < O ? f : 0];
                     if (relu) v = fmaxf(v, 0.0f);
-                    // (L.drop_tag != 0: the row's Philox keep mask x 2 is applied here and regenerated in the backward pass; the habit net has none)
+                    // (the habit net has no dropout: L.drop_tag is 0 in its table; k_mid_grad below is the kernel for layers that carry one)
                     y[n][f] = f < O ? v : 0.0f;
                 }
             }
@@ -202,6 +209,248 @@ __global__ void __launch_bounds__(256) k_top_grad(const TopGradArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// k_mid_grad: the same three passes for the transition net ModelMid.ps_net (torchmodel.py:41-52): Linear(A + 10, 512), three times
+// ReLU + Dropout(0.5) with 512-wide Linears between, Linear(512, 20) = ps1_mean | ps1_logvar; loss = mean_r sum_k kl (header).
+//
+// LDS (dynamic, MID_LDS_BYTES = 102 656): X0 [16][20] the input tile | H1, H2, H3 [16][516] the post-mask activations (H_l = input of
+// layer l) | DO [16][36] the output tile (logits, then their gradient).  d_{l-1} OVERWRITES H_l in place once dW_l has consumed it: lane
+// (n, q) gates and writes the four elements it reads, and d_l itself sits in H_{l+1} (DO for the last layer).  One workgroup per CU.
+//
+// Dropout: the forward pass draws the keep mask of hidden layer li as k_trans_fused does (tag TAG_MID + li = TrainLayer::drop_tag, block
+// f >> 7, the call's row / stream / stage) and stores relu(a) * mask (kept value x 2).  The backward gate mask * [a > 0] is READ OFF the
+// stored activation, 2 * [h > 0]: no second Philox evaluation, and the two passes cannot key a mask differently.
+//
+// Chains: a contraction over a layer's width (K up to 512) runs on SIXTEEN accumulators: 16-channel chunk c goes to accumulator c & 15
+// (four MFMAs = 16 terms per visit, 32 terms per accumulator at K = 512), combined by the fixed tree of tree16().  The forward pass reads
+// the packed 16x16x4 copy (one coalesced float4 per lane and chunk; MFMA step s contracts channels 16 c + 4 q + s), the transposed
+// product gathers W[o][i] from the master copy with the same chunk / step order over o.  dW is one 16-term chain over the tile's rows.
+// The forward order is not k_trans_fused's single chain: ps1_mean / ps1_logvar agree with efe_loss_mid to rounding, not bit for bit.
+//
+// Reduction-order contract (a function of M alone): T = ceil(M / 16) tiles, G = min(T, TRAIN_MID_SLABS = 8) workgroups, workgroup p walks
+// tiles p, p + G, ... ascending and adds each tile's chain to its slab element; gradient = ((slab_0 + slab_1) + slab_2) + ... ascending.
+namespace {
+
+constexpr int MLD = TRAIN_MID_WIDTH + 4;          // row stride of H1..H3 (516 floats: rows 16-byte aligned, 16 rows on 64 distinct banks)
+constexpr int XLD = TRAIN_MID_IN + 4;             // ... of X0
+constexpr int OLD = TRAIN_MID_OUT + 4;            // ... of DO
+constexpr int MID_LDS_BYTES = (TR * XLD + 3 * TR * MLD + TR * OLD) * (int)sizeof(float);
+
+__device__ __forceinline__ f32x4 tree16(const f32x4 (&a)[16]) {
+#pragma clang fp contract(off)
+    const f32x4 b0 = (a[0] + a[1]) + (a[2] + a[3]), b1 = (a[4] + a[5]) + (a[6] + a[7]);
+    const f32x4 b2 = (a[8] + a[9]) + (a[10] + a[11]), b3 = (a[12] + a[13]) + (a[14] + a[15]);
+    return (b0 + b1) + (b2 + b3);
+}
+
+#define MFMA4(ACC, A0, A1, A2, A3, BV)                                     \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A0, (BV).x, ACC, 0, 0, 0);   \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A1, (BV).y, ACC, 0, 0, 0);   \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A2, (BV).z, ACC, 0, 0, 0);   \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A3, (BV).w, ACC, 0, 0, 0);
+
+}  // namespace
+
+__global__ void __launch_bounds__(256, 1) k_mid_grad(const MidGradArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) float mid_sm[];
+    const TrainNet& net = *a.net;
+    const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, q = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nl = net.nl, P = net.P, in0 = net.L[0].in, S = a.S;
+    const int ntiles = (a.M + TR - 1) / TR;
+    const float* master = net.master;
+    float* slab = a.slabs + (size_t)blockIdx.x * P;
+    float* const X0 = mid_sm;
+    float* const H = mid_sm + TR * XLD;              // H + (l - 1) * TR * MLD = input of layer l >= 1
+    float* const DO = H + 3 * TR * MLD;
+    // input / output buffer of layer l and their row strides
+    auto xin = [&](int l) { return l == 0 ? X0 : H + (l - 1) * TR * MLD; };
+    auto xld = [&](int l) { return l == 0 ? XLD : MLD; };
+    auto yout = [&](int l) { return l + 1 < nl ? H + l * TR * MLD : DO; };
+    auto yld = [&](int l) { return l + 1 < nl ? MLD : OLD; };
+#pragma unroll 1
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const bool first = tile == (int)blockIdx.x;
+        const int r0 = tile * TR;
+        for (int i = tid; i < TR * TRAIN_MID_IN; i += 256) {         // [pi0 | s0], zero beyond the layer's width and beyond row M
+            const int r = i / TRAIN_MID_IN, c = i - r * TRAIN_MID_IN, row = r0 + r;
+            float v = 0.0f;
+            if (row < a.M && c < in0) v = c < a.A ? a.pi0[(size_t)row * a.A + c] : a.s0[(size_t)row * S + (c - a.A)];
+            X0[r * XLD + c] = v;
+        }
+        __syncthreads();
+        // ---- forward ------------------------------------------------------------------------------------------------
+#pragma unroll 1
+        for (int l = 0; l < nl; ++l) {
+            const TrainLayer& L = net.L[l];
+            const int O = L.out, KC = L.kc16, relu = L.relu, OT = (O + 15) / 16, tpw = (OT + 3) / 4;
+            const uint32_t tag = (uint32_t)L.drop_tag;
+            const float* B = master + L.b_off;
+            const float* x = xin(l) + n * xld(l) + 4 * q;
+            float* y = yout(l) + n * yld(l);
+            const int t1 = min(OT, (w + 1) * tpw);
+#pragma unroll 1
+            for (int t = w * tpw; t < t1; ++t) {                  // a wave's tiles are contiguous: 8 tiles = one Philox block at O = 512
+                const int f0 = 16 * t;
+                const float4* Wp = reinterpret_cast<const float4*>(L.Wp16) + (size_t)t * KC * 64 + lane;
+                f32x4 acc[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[j] = (f32x4)(0.f);
+#pragma unroll 1
+                for (int c0 = 0; c0 < KC; c0 += 16) {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const int c = c0 + j;
+                        if (c < KC) {
+                            const float4 av = Wp[(size_t)c * 64];                                     // A(i = feature, k): W[f0 + n][16 c + 4 q + s]
+                            const float4 bv = *reinterpret_cast<const float4*>(x + 16 * c);            // B(k, j = row):     x[n][16 c + 4 q + s]
+                            MFMA4(acc[j], av.x, av.y, av.z, av.w, bv)
+                        }
+                    }
+                }
+                const f32x4 sum = tree16(acc);
+                uint32_t word = 0xFFFFFFFFu;
+                if (tag) {
+                    // the key words pass through vector registers HERE: as loop invariants their ten Philox round keys are hoisted into twenty
+                    // scalar registers for the whole kernel, which then spills scalars
+                    uint32_t k0 = a.k0, k1 = a.k1;
+                    asm volatile("" : "+v"(k0), "+v"(k1));
+                    const uint4 rnd = noise_words(k0, k1, tag, (uint32_t)(f0 >> 7), a.row_offset + (uint32_t)(r0 + n), a.stream, a.stage);
+                    const int wsel = (f0 >> 5) & 3;
+                    word = wsel == 0 ? rnd.x : wsel == 1 ? rnd.y : wsel == 2 ? rnd.z : rnd.w;
+                }
+                float4 out;
+                float* o4 = &out.x;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int f = f0 + 4 * q + e;
+                    float v = sum[e] + B[f < O ? f : 0];
+                    if (relu) v = fmaxf(v, 0.0f);
+                    if (tag) v = ((word >> (f & 31)) & 1u) ? v * 2.0f : 0.0f;
+                    o4[e] = f < O ? v : 0.0f;
+                }
+                *reinterpret_cast<float4*>(y + f0 + 4 * q) = out;
+            }
+            __syncthreads();
+        }
+        // ---- loss gradient, one thread per row (torchloss.py:28-37, torchutils.py:7-8; the 1/M of .mean() enters here) -------------
+        if (tid < TR) {
+            const int row = r0 + tid;
+            float* z = DO + tid * OLD;                  // mean 0..S-1 | logvar S..2S-1, replaced by their gradients
+            if (row < a.M) {
+                const float om = a.omega_mode == 0 ? a.omega_in[row] : a.omega_scalar;
+                const float log_om = logf(om);
+                float F = 0.0f;
+#pragma unroll 1
+                for (int k = 0; k < S; ++k) {
+                    const float mu1 = a.q1_mean[(size_t)row * S + k], lv1 = a.q1_lv[(size_t)row * S + k], mu2 = z[k], lv2 = z[S + k];
+                    a.p1_mean[(size_t)row * S + k] = mu2;
+                    a.p1_lv[(size_t)row * S + k] = lv2;
+                    const float h = 0.5f * ((lv2 - log_om) - lv1);        // kl_term of loss.hip, operation for operation
+                    const float d = mu1 - mu2;
+                    const float num = expf(lv1) + d * d;
+                    const float den = (2.0f * expf(lv2)) / om;
+                    const float ratio = num / den;
+                    const float t = (h + ratio) - 0.5f;
+                    F = k ? F + t : t;
+                    z[k] = a.inv_M * (-((2.0f * d) / den));
+                    z[S + k] = a.inv_M * (0.5f - ratio);
+                }
+                a.F_mid[row] = F;
+            } else {
+#pragma unroll 1
+                for (int k = 0; k < 2 * S; ++k) z[k] = 0.0f;
+            }
+        }
+        __syncthreads();
+        // ---- backward -----------------------------------------------------------------------------------------------
+#pragma unroll 1
+        for (int l = nl - 1; l >= 0; --l) {
+            const TrainLayer& L = net.L[l];
+            const int K = L.in, O = L.out;
+            const float* W = master + L.w_off;
+            float* gW = slab + L.w_off;
+            float* gB = slab + L.b_off;
+            const float* d = yout(l);                  // d_l lives where layer l's output was
+            const int dld = yld(l);
+            float* x = xin(l);
+            const int xs = xld(l);
+            const int IT = (K + 15) / 16, OT = (O + 15) / 16;
+#pragma unroll 1
+            for (int ot = w; ot < OT; ot += 4) {                  // dW[o][i] = sum_r d[r][o] x[r][i]: A(i = o, k = row) stays in registers over the i tiles
+                const int o0 = 16 * ot;
+                float av[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) av[c] = d[(4 * c + q) * dld + o0 + n];
+#pragma unroll 2
+                for (int it = 0; it < IT; ++it) {
+                    const int i0 = 16 * it;
+                    f32x4 acc = (f32x4)(0.f);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], x[(4 * c + q) * xs + i0 + n], acc, 0, 0, 0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int o = o0 + 4 * q + e, i = i0 + n;
+                        if (o < O && i < K) {
+                            float* p = gW + (size_t)o * K + i;
+                            *p = first ? acc[e] : *p + acc[e];
+                        }
+                    }
+                }
+            }
+#pragma unroll 1
+            for (int o = tid; o < O; o += 256) {                  // db[o] = sum_r d[r][o]
+                float sm = d[o];
+#pragma unroll
+                for (int r = 1; r < TR; ++r) sm = sm + d[r * dld + o];
+                gB[o] = first ? sm : gB[o] + sm;
+            }
+            __syncthreads();                                      // dW_l has consumed x = H_l: it may now be overwritten
+            if (l > 0) {                                          // d_{l-1}[r][i] = (sum_o d[r][o] W[o][i]) * mask[r][i] [a[r][i] > 0], written over H_l[r][i]
+                const TrainLayer& Lp = net.L[l - 1];
+                const float keep = Lp.drop_tag ? 2.0f : 1.0f;
+                const int OC = OT, tpw = (IT + 3) / 4, t1 = min(IT, (w + 1) * tpw);
+                const float* dn = d + n * dld + 4 * q;
+#pragma unroll 1
+                for (int t = w * tpw; t < t1; ++t) {
+                    const int i0 = 16 * t;
+                    const float* Wc = W + i0 + n;              // (K = the width of a hidden layer: whole 16-feature tiles)
+                    f32x4 acc[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) acc[j] = (f32x4)(0.f);
+#pragma unroll 1
+                    for (int c0 = 0; c0 < OC; c0 += 16) {
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            const int c = c0 + j;
+                            if (c < OC) {
+                                const int o = 16 * c + 4 * q;
+                                const float4 bv = *reinterpret_cast<const float4*>(dn + 16 * c);       // B(k = o, j = row): d[n][16 c + 4 q + s]
+                                float av[4];                                                           // A(i = input feature, k = o): W[o][i0 + n]; beyond O the
+#pragma unroll                                                                                                 // row index is clamped: d is zero there, the product exactly 0
+                                for (int s = 0; s < 4; ++s) av[s] = Wc[(size_t)min(o + s, O - 1) * K];
+                                MFMA4(acc[j], av[0], av[1], av[2], av[3], bv)
+                            }
+                        }
+                    }
+                    const f32x4 sum = tree16(acc);
+                    float* hp = x + n * xs + i0 + 4 * q;
+                    const float4 h = *reinterpret_cast<const float4*>(hp);
+                    float4 g;
+                    g.x = (!Lp.relu || h.x > 0.0f) ? keep * sum[0] : 0.0f;
+                    g.y = (!Lp.relu || h.y > 0.0f) ? keep * sum[1] : 0.0f;
+                    g.z = (!Lp.relu || h.z > 0.0f) ? keep * sum[2] : 0.0f;
+                    g.w = (!Lp.relu || h.w > 0.0f) ? keep * sum[3] : 0.0f;
+                    *reinterpret_cast<float4*>(hp) = g;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+#undef MFMA4
+
 __global__ void __launch_bounds__(256) k_slab_sum(const float* slabs, int nslab, int P, float* grad) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < P) grad[i] = slab_sum(slabs, nslab, P, i);
@@ -240,6 +489,12 @@ __global__ void __launch_bounds__(256) k_adam(const AdamArgs a) {
 
 void launch_top_grad(const TopGradArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_top_grad, dim3(train_slabs(a.M)), dim3(256), 0, st, a);
+}
+void launch_mid_grad(const MidGradArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_mid_grad, dim3(train_mid_slabs(a.M)), dim3(256), MID_LDS_BYTES, st, a);
+}
+int init_train_kernels() {
+    return hipFuncSetAttribute((const void*)k_mid_grad, hipFuncAttributeMaxDynamicSharedMemorySize, MID_LDS_BYTES) != hipSuccess;
 }
 void launch_slab_sum(const float* slabs, int nslab, int P, float* grad, hipStream_t st) {
     hipLaunchKernelGGL(k_slab_sum, dim3((P + 255) / 256), dim3(256), 0, st, slabs, nslab, P, grad);

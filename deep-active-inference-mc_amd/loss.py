@@ -2,15 +2,18 @@
 compute_loss_top, compute_loss_mid, compute_loss_down) with the reference's names, arguments and return tuples, plus `free_energy`, the
 composition train.py:104-123 evaluates before its optimizer steps, in one engine call (efe_free_energy, csrc/loss.hip).
 
-No autograd graph is built.  The habit network is trainable: `train_model_top` (torchloss.py:65-74) is one Adam step on the device
-(csrc/train.hip: backward + update in two launches, with a daimc_amd.Adam holding the state) and `grad_top` returns its gradient; the
-transition network, the encoder / decoder and a training loop are out of scope.  Every call dispatches through torch.ops.efe.* on the
-model's device; there is no CPU fallback.
+No autograd graph is built.  The habit network and the transition network are trainable: `train_model_top` (torchloss.py:65-74) and
+`train_model_mid` (torchloss.py:76-88) are each one Adam step on the device (csrc/train.hip: backward + update in two launches, with a
+daimc_amd.Adam holding the state), and `grad_top` / `grad_mid` return the gradients.  `train_model_down` (the encoder / decoder) is not
+built, and a training loop is out of scope.  Every call dispatches through torch.ops.efe.* on the model's device; there is no CPU
+fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
 encoder, FE_T for the transition + sample, FE_DOWN for compute_loss_down's encoder + sample + decoder), one stage per call, rows keyed
 by global row (`row_offset`).  So encoder_with_sample(o0, pass_=PASS_FE_Q0), encoder(o1, pass_=PASS_FE_Q1), compute_loss_top,
 compute_loss_mid and compute_loss_down at one stage reproduce `free_energy` bit for bit.  `model.eps_source` (injected normals) is honoured.
+train_model_mid / grad_mid draw the transition's three dropout masks under the same keys as compute_loss_mid (default pass PASS_FE_T) and
+no normals: the reference's randn_like sample does not enter the loss.
 
 Deviations from the reference, each a defect of the shipped code ("training-side free energy"):
   * compute_loss_down reads gamma / beta_s / beta_o from the owning ActiveInferenceModel: the reference reads them from ModelDown,
@@ -158,3 +161,41 @@ def train_model_top(model_top, s, log_Ppi, optimizer):
     kl = e.ops.train_top(e.h, s, lp, ea, es, *hyper, optimizer._step)
     model_top._stepped()
     return kl
+
+
+def _mid_inputs(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, stage, pass_, sample, row_offset):
+    m = model_mid._owner
+    e = m._ready()
+    s0 = e.tensor(s0, (-1, m.s_dim))
+    M = s0.shape[0]
+    mode, om, sc = _omega(e, omega, M)
+    nz = m._noise(stage, pass_, sample, row_offset)
+    return m, e, (e.h, s0, e.tensor(Ppi_sampled, (M, m.pi_dim)), e.tensor(qs1_mean, (M, m.s_dim)), e.tensor(qs1_logvar, (M, m.s_dim)),
+                  mode, om, sc, m._seed64(), nz.stage, pass_, sample, nz.row_offset)
+
+
+def grad_mid(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, *, stage=None, pass_=PASS_FE_T, sample=0, row_offset=None):
+    """-> (F_mid [M], ps1_mean, ps1_logvar [M, s_dim], {state_dict key: d mean(F_mid) / d tensor}): what torchloss.py:83-85 leaves in
+    .grad (views of one flat tensor), with the dropout masks of (stage, pass_, sample, row_offset)"""
+    _, _, args = _mid_inputs(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, stage, pass_, sample, row_offset)
+    F, mean, lv, flat = model_mid._owner._engine.ops.mid_grad(*args)
+    grads, off = {}, 0
+    for key, t in model_mid._sd_host.items():
+        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
+        off += t.numel()
+    return F, mean, lv, grads
+
+
+def train_model_mid(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, optimizer, *, stage=None, pass_=PASS_FE_T, sample=0,
+                    row_offset=None):
+    """torchloss.py:76-88: one optimiser step of the transition net on F_mid.mean() -> (ps1_mean, ps1_logvar) of the weights before the
+    step.  optimizer: a daimc_amd.Adam over this model_mid.  Bit-identical to grad_mid followed by optimizer.step(grads)."""
+    if getattr(optimizer, '_module', None) is not model_mid:
+        raise ValueError('train_model_mid: optimizer must be a daimc_amd.Adam over this model_mid')
+    _, e, args = _mid_inputs(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, stage, pass_, sample, row_offset)
+    ea, es = optimizer._buffers()
+    hyper = optimizer._hyper()
+    optimizer._step += 1
+    mean, lv, _ = e.ops.train_mid(*args, ea, es, *hyper, optimizer._step)
+    model_mid._stepped()
+    return mean, lv

@@ -147,18 +147,17 @@ class _Module:
 
 
 class _ParamList(list):
-    """what ModelTop.parameters() returns: the tensors, plus the module they belong to (daimc_amd.Adam finds its engine through it)"""
+    """what a trainable module's parameters() returns: the tensors, plus the module they belong to (daimc_amd.Adam finds its engine
+    through it)"""
     module = None
 
 
-class ModelTop(_Module):
-    """torchmodel.py:10-31.  The habit net is trainable on the device (loss.train_model_top): after an optimiser step the engine's master
-    copy is newer than the host tensors, and state_dict() / parameters() download it first (lazily, one synchronisation)."""
+class _TrainableModule(_Module):
+    """A part the engine trains on the device (csrc/train.hip): after an optimiser step the engine's master copy is newer than the host
+    tensors, and state_dict() / parameters() download it first (lazily, one synchronisation).  `_train_part` is the part's name in the
+    C ABI (efe_param_count / efe_get_weights / efe_adam_step)."""
     _device_newer = False
-
-    def __init__(self, owner):
-        super().__init__(owner, 'top')
-        self.s_dim, self.pi_dim = owner.s_dim, owner.pi_dim
+    _train_part = None
 
     @property
     def _sd(self):
@@ -174,10 +173,11 @@ class ModelTop(_Module):
     def _download(self):
         """efe_get_weights: the device master copy (flat, parameters() order) -> the host state_dict"""
         e = self._owner._engine
-        P = int(e.lib.efe_param_count(e.ctx, b'top'))
+        part = self._train_part.encode()
+        P = int(e.lib.efe_param_count(e.ctx, part))
         buf = e.empty(P)
         with torch.cuda.device(e.device):
-            e.check(e.lib.efe_get_weights(e.ctx, b'top', _ptr(buf), P, e.stream()))
+            e.check(e.lib.efe_get_weights(e.ctx, part, _ptr(buf), P, e.stream()))
             flat = buf.cpu()
         new, off = {}, 0
         for key, t in self._sd_host.items():
@@ -196,6 +196,15 @@ class ModelTop(_Module):
         p.module = self
         return p
 
+
+class ModelTop(_TrainableModule):
+    """torchmodel.py:10-31.  The habit net is trainable on the device (loss.train_model_top)."""
+    _train_part = 'top'
+
+    def __init__(self, owner):
+        super().__init__(owner, 'top')
+        self.s_dim, self.pi_dim = owner.s_dim, owner.pi_dim
+
     def encode_s(self, s0):
         m = self._owner
         e = m._ready()
@@ -203,8 +212,10 @@ class ModelTop(_Module):
         return e.ops.habit(e.h, s0)
 
 
-class ModelMid(_Module):
-    """torchmodel.py:34-66"""
+class ModelMid(_TrainableModule):
+    """torchmodel.py:34-66.  The transition net is trainable on the device (loss.train_model_mid); its part name in the C ABI is the
+    reference's module name, "ps_net"."""
+    _train_part = 'ps_net'
 
     def __init__(self, owner):
         super().__init__(owner, 'mid')
@@ -487,20 +498,23 @@ class ActiveInferenceModel:
         return stats, self._load_optimizers(folder_chp)
 
     def _load_optimizers(self, folder_chp):
-        """optimizers.pkl -> {name: daimc_amd.Adam} for every entry over the habit net's six parameters (the only part the engine
-        trains; entries of other parts stay in the file).  The reference's own loader (torchmodel.py:197-203) reads the pickle twice
-        and always lands in its bare `except`, i.e. it restarts every optimiser; this one restores them."""
+        """optimizers.pkl -> {name: daimc_amd.Adam} for every entry over a part the engine trains: one group of six parameters is the
+        habit net's, of eight the transition net's (entries of other parts stay in the file).  The reference's own loader
+        (torchmodel.py:197-203) reads the pickle twice and always lands in its bare `except`, i.e. it restarts every optimiser; this one
+        restores them."""
         path = f'{folder_chp}/optimizers.pkl'
         if not os.path.exists(path):
             return {}
         from .optim import Adam
         with open(path, 'rb') as ff:
             saved = pickle.load(ff)
+        by_count = {len(mod._sd_host): mod for mod in (self.model_top, self.model_mid)}
         out = {}
         for name, sd in saved.items():
             groups = sd.get('param_groups', [])
-            if len(groups) == 1 and len(groups[0].get('params', ())) == len(self.model_top._sd_host):
-                out[name] = Adam(self.model_top)
+            mod = by_count.get(len(groups[0].get('params', ()))) if len(groups) == 1 else None
+            if mod is not None:
+                out[name] = Adam(mod)
                 out[name].load_state_dict(sd)
         return out
 

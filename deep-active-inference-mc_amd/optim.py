@@ -1,10 +1,12 @@
-"""daimc_amd.Adam: torch.optim.Adam (default flags: no amsgrad, no weight decay) for the part of the model the engine trains on the
-device, the habit network ModelTop.qpi_net.  The update runs in csrc/train.hip (k_adam) on the engine's master copy of the weights; this
-class holds the optimiser state (exp_avg, exp_avg_sq: flat device tensors in parameters() order) and the step count, and speaks
-torch.optim.Adam's state_dict format for those six parameters, so state moves both ways between the two."""
+"""daimc_amd.Adam: torch.optim.Adam (default flags: no amsgrad, no weight decay) for the parts of the model the engine trains on the
+device: the habit network ModelTop.qpi_net (six parameters, C ABI part "top") and the transition network ModelMid.ps_net (eight
+parameters, part "ps_net").  One optimiser holds one part.  The update runs in csrc/train.hip (k_adam) on the engine's master copy of
+the weights; this class holds the part's name, the optimiser state (exp_avg, exp_avg_sq: flat device tensors in parameters() order) and
+the step count, and speaks torch.optim.Adam's state_dict format for the part's parameters, so state moves both ways between the two.
+The encoder / decoder (train_model_down) is not trainable on the engine."""
 import torch
 
-from .model import ModelTop
+from .model import _TrainableModule
 
 
 def _torch_group():
@@ -14,10 +16,12 @@ def _torch_group():
 
 class Adam:
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        mod = params if isinstance(params, ModelTop) else getattr(params, 'module', None)
-        if not isinstance(mod, ModelTop):
-            raise TypeError('daimc_amd.Adam takes model.model_top or model.model_top.parameters() (the habit net is the trainable part)')
+        mod = params if isinstance(params, _TrainableModule) else getattr(params, 'module', None)
+        if not isinstance(mod, _TrainableModule):
+            raise TypeError('daimc_amd.Adam takes model.model_top, model.model_mid or the parameters() of one of them (the habit net and '
+                            'the transition net are the trainable parts)')
         self._module = mod
+        self._part = mod._train_part                # the part's name in the C ABI: "top" / "ps_net"
         self._shapes = [tuple(t.shape) for t in mod._sd_host.values()]
         self._numel = [int(torch.Size(s).numel()) for s in self._shapes]
         group = _torch_group()
@@ -44,7 +48,7 @@ class Adam:
         """no-op: the engine never accumulates gradients"""
 
     def step(self, grad):
-        """one update with the caller's gradient: the dict loss.grad_top returns, or the flat [P] tensor (parameters() order)"""
+        """one update with the caller's gradient: the dict loss.grad_top / grad_mid returns, or the flat [P] tensor (parameters() order)"""
         m = self._module._owner
         e = m._ready()
         if isinstance(grad, dict):
@@ -52,7 +56,7 @@ class Adam:
         grad = e.tensor(grad).reshape(-1)
         ea, es = self._buffers()
         self._step += 1
-        e.ops.adam_step(e.h, 'top', grad, ea, es, *self._hyper(), self._step)
+        e.ops.adam_step(e.h, self._part, grad, ea, es, *self._hyper(), self._step)
         self._module._stepped()
 
     def state_dict(self):

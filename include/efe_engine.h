@@ -308,7 +308,7 @@ int efe_loss_down(efe_ctx*, const float* o1, const float* ps1_mean, const float*
                   const efe_noise* nz, const float* eps, efe_fe_out* out, void* stream);
 
 /* ---- training of the habit network (csrc/train.hip): train_model_top of /root/reference/src/torchloss.py:65-74 ----------------------------
- * One Adam step of ModelTop.qpi_net on F_top.mean(), F_top = sum_a Qpi (log(Qpi + 1e-20) - log_Ppi).  The only trainable part is "top".
+ * One Adam step of ModelTop.qpi_net on F_top.mean(), F_top = sum_a Qpi (log(Qpi + 1e-20) - log_Ppi).  Its part name is "top".
  * The engine owns the weights (an fp32 master copy on the device next to the packed forward copies) and scratch; the gradient and the
  * optimiser state (exp_avg, exp_avg_sq) are DEVICE arrays of efe_param_count("top") floats owned by the caller, flat in the reference's
  * parameters() order (qpi_net.0.weight, 0.bias, 2.weight, 2.bias, 4.weight, 4.bias), each row-major.  Every call is ordered on `stream`
@@ -328,6 +328,26 @@ int efe_get_weights(efe_ctx*, const char* part, float* dst, int64_t n, void* str
 int efe_top_grad(efe_ctx*, const float* s, const float* log_Ppi, int M, float* kl_pi, float* grad, void* stream);
 int efe_adam_step(efe_ctx*, const char* part, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
 int efe_train_top(efe_ctx*, const float* s, const float* log_Ppi, int M, float* kl_pi, float* exp_avg, float* exp_avg_sq,
+                  const efe_adam_params* hp, void* stream);
+
+/* ---- training of the transition network (csrc/train.hip k_mid_grad): train_model_mid of the reference, src/torchloss.py:76-88 -----------
+ * One Adam step of ModelMid.ps_net on F_mid.mean() (compute_loss_mid: the Gaussian KL of q(s1) against the transition's output with
+ * precision omega).  The part's name is "ps_net", the reference's module name: efe_param_count, efe_get_weights and efe_adam_step take it
+ * next to "top".  ("mid" is NOT a part name: a test of the habit-net commit pins it as refused, and existing tests do not change.)
+ * P = efe_param_count("ps_net") = 543 252 at pi_dim 4, flat in parameters() order: ps_net.0.weight, 0.bias, 3.weight, 3.bias, 6.weight,
+ * 6.bias, 9.weight, 9.bias.  Arguments follow efe_loss_mid: params->omega_mode EFE_OMEGA_ARRAY or EFE_OMEGA_SCALAR (EFE_OMEGA_DERIVED is
+ * refused), nz keys the three MC-dropout masks (row nz->row_offset + r, pass, sample, stage); the reference's randn_like draw does not
+ * enter the loss, so no normals are drawn.  ps1_mean / ps1_logvar [M,s_dim] and F_mid [M] are optional (NULL: not wanted); they agree
+ * with efe_loss_mid's to rounding, not bit for bit (another summation order).
+ *   efe_mid_grad  : -> grad [P] = d mean(F_mid) / d parameters, a fixed-order sum that depends on M alone: twice the same bits.
+ *   efe_train_mid : efe_mid_grad and efe_adam_step("ps_net") on the stream, bit-identical to the two calls; the outputs are those of the
+ *                   weights BEFORE the update, as the reference returns them.
+ * Scratch (at most 8 partial gradients, 17 MB) comes from the context's arena.  efe_commit_weights and efe_set_weight("mid....") first
+ * bring the host copies up to date, as for the habit net: re-committing any part never reverts a trained one. */
+int efe_mid_grad(efe_ctx*, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M, const efe_fe_params* params,
+                 const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, float* grad, void* stream);
+int efe_train_mid(efe_ctx*, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, float* exp_avg, float* exp_avg_sq,
                   const efe_adam_params* hp, void* stream);
 
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
