@@ -27,12 +27,150 @@ typedef unsigned u32x4g __attribute__((ext_vector_type(4)));
 __host__ __device__ inline int convt_th(int pixels_per_strip, int Win) { return pixels_per_strip / Win; }
 
 // ---------------------------------------------------------------------------------------------------------
+// The strip pass of k_convt_p and k_convt_12: ONE definition of its tables, preload, contraction, ring refill and store epilogue
+// ---------------------------------------------------------------------------------------------------------
+// A pass contracts this wave's 32-pixel tile of the strip against the taps of one output-row parity.  Stride 2: two passes over the
+// strip (P = 0: 3 taps -> parities (0,0) (0,1); P = 1: 6 taps -> (1,0) (1,1)): 32 accumulator registers live instead of 64, so three
+// waves per SIMD fit.  Stride 1: one pass of nine taps (P = 2).  MFMA group m of a pass multiplies the fragment of tap[m] by the strip
+// view view[m] into accumulator acc[m]; vlast[v] is the last group that reads view v.
+//
+// A contraction step (one 8-channel block kc): the strip views of block kc (requested a step earlier) against a fragment set; every
+// fragment is re-requested for block kc + AD right behind the MFMAs that consumed it, every view for block kc + 1 behind its last
+// reader, so each wait leaves the newer requests in flight (a bulk request per step made hipcc wait for all of them in the middle of
+// the step); the sched_barrier after each group keeps hipcc from gathering the requests again.  Pass 0 keeps two fragment sets,
+// AD = 2 blocks ahead: its three groups are only 768 cycles; passes 1 and 2 refill one set, AD = 1.
+//
+// The first fragments of a pass (fa = the set of channel block 0, fb = block 1 of pass 0) are requested BEFORE the previous pass's
+// store epilogue (and, for a strip's first pass, before the barriers in front of it): requested at the top of a pass they exposed an
+// L2 round trip per pass -- two per strip on the stride-2 layers.
+//
+// How the shared functions take their arguments is part of the schedule (tools/isa_report.py --diff against the per-kernel lambdas
+// they replace): the ring is named here, not passed (through a generic pointer hipcc forms its addresses in 64 bits); frag0 returns
+// the fragment INDEX of a tap's block 0 and the block is added here ((index + kc + AD) as the kernels wrote it, not index + (kc + AD):
+// another association moved SGPRs); what the lambdas captured by reference arrives by reference.  The image fetch, the strip-0 fill,
+// the cl_off table and the view offsets stay with each kernel: as shared functions each of them changed a kernel's s_waitcnt or
+// register counts.
+extern __shared__ float4 cl_x[];                     // the dynamic LDS of both kernels: the pixel ring(s) + 16 zero slots, Cin / 4 + 1 float4 per slot
+struct ConvtPass {
+    int NMP, NVP, NAC, AD;                           // MFMA groups, strip views, accumulators, blocks a fragment is requested ahead
+    int tap[9], view[9], acc[9], vlast[9];
+};
+constexpr ConvtPass CONVT_PASS[3] = {
+    {3, 2, 2, 2, {4, 5, 3}, {0, 0, 1}, {0, 1, 1}, {1, 2}},
+    {6, 4, 2, 1, {7, 8, 6, 1, 2, 0}, {0, 0, 1, 2, 2, 3}, {0, 1, 1, 0, 1, 1}, {1, 2, 4, 5}},
+    {9, 9, 1, 1, {0, 1, 2, 3, 4, 5, 6, 7, 8}, {0, 1, 2, 3, 4, 5, 6, 7, 8}, {0, 0, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}}};
+
+// the first fragments of pass P; frag0(tap) = index (in 1 KB fragments) of this wave's fragment of that tap, channel block 0 --
+// the blocks of a tap follow each other
+template <int P, class Frag0>
+__device__ __forceinline__ void convt_preload(float4 (&fa)[9], float4 (&fb)[3], __amdgpu_buffer_rsrc_t wr, unsigned wl, Frag0 frag0) {
+    constexpr ConvtPass D = CONVT_PASS[P];
+#pragma unroll
+    for (int m = 0; m < D.NMP; ++m) fa[m] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)(frag0(D.tap[m]) * 64) * 16u, 0));
+    if constexpr (D.AD == 2) {
+#pragma unroll
+        for (int m = 0; m < D.NMP; ++m) fb[m] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)((frag0(D.tap[m]) + 1) * 64) * 16u, 0));
+    }
+}
+
+// the contraction of pass P over KC channel blocks (an int, or an integral_constant where it is a compile-time 8): ac = bias + sum
+// over the pass's taps; vb[v] = LDS float4 index of view v's block 0.  next() runs behind the pass's last fragment request: where the
+// caller requests the next strip's rows.  The epilogue is the caller's.
+template <int P, int NV, class Frag0, class KCT, class Next>
+__device__ __forceinline__ void convt_contract(f32x16 (&ac)[CONVT_PASS[P].NAC], const float& bias, const float4 (&fa)[9], const float4 (&fb)[3],
+                                               const __amdgpu_buffer_rsrc_t& wr, const unsigned& wl, const Frag0& frag0, const KCT& KC,
+                                               const int (&vb)[NV], const Next& next) {
+    constexpr ConvtPass D = CONVT_PASS[P];
+    constexpr int NMP = D.NMP, NVP = D.NVP, NAC = D.NAC, AD = D.AD;
+#pragma unroll
+    for (int p = 0; p < NAC; ++p)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) ac[p][e] = bias;       // a lane owns one output channel: the bias is the accumulator's start value
+    auto step = [&](float4 (&av)[NMP], float4 (&bv)[NVP], int kc) {
+#pragma unroll
+        for (int m = 0; m < NMP; ++m) {
+            const float4 b = bv[D.view[m]];
+            f32x16& c = ac[D.acc[m]];
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, av[m].x, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, av[m].y, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, av[m].z, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, av[m].w, c, 0, 0, 0);
+            if (kc + AD < KC) {
+                const u32x4g v = __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)((frag0(D.tap[m]) + kc + AD) * 64) * 16u, 0);
+                av[m] = __builtin_bit_cast(float4, v);
+            }
+#pragma unroll
+            for (int v = 0; v < NVP; ++v)
+                if (D.vlast[v] == m && kc + 1 < KC) bv[v] = cl_x[vb[v] + 2 * (kc + 1)];      // view v is free: block kc + 1 in place
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    float4 a0[NMP], a1[AD == 2 ? NMP : 1], bv[NVP];
+#pragma unroll
+    for (int m = 0; m < NMP; ++m) a0[m] = fa[m];                  // requested before the previous pass's epilogue / the strip barriers
+    if (AD == 2) {
+#pragma unroll
+        for (int m = 0; m < NMP; ++m) a1[m % (AD == 2 ? NMP : 1)] = fb[m % 3];
+    }
+#pragma unroll
+    for (int v = 0; v < NVP; ++v) bv[v] = cl_x[vb[v]];
+    for (int kc = 0; kc < KC; kc += 2) {
+        if (kc + 2 >= KC) next();
+        __builtin_amdgcn_sched_barrier(0);
+        step(a0, bv, kc);
+        if constexpr (AD == 2) step(a1, bv, kc + 1); else step(a0, bv, kc + 1);
+    }
+}
+
+// a strip's new rows, one contiguous block of SPX pixels from pixel P0 on: requested into registers ...
+template <int NPF, class Fetch>
+__device__ __forceinline__ void ring_request(float4 (&pf)[NPF], const Fetch& fetch, const int& P0, const int& pp0, const int& pstep, const int& SPX) {
+#pragma unroll
+    for (int i = 0; i < NPF; ++i) pf[i] = fetch(P0 + pp0 + i * pstep, pp0 + i * pstep < SPX);
+}
+// ... and written (between two barriers) over the oldest rows: from slot nb on, around the ring of RPa slots
+template <int NPF>
+__device__ __forceinline__ void ring_commit(const float4 (&pf)[NPF], int nb, int pp0, int pstep, int SPX, int RPa, int PS4, int c4) {
+    if (nb >= RPa) nb -= RPa;
+#pragma unroll
+    for (int i = 0; i < NPF; ++i) {
+        const int pp = pp0 + i * pstep;
+        int sl = nb + pp;
+        if (sl >= RPa) sl -= RPa;
+        if (pp < SPX) cl_x[sl * PS4 + c4] = pf[i];
+    }
+}
+// store epilogue of pass P: C/D layout column = lane & 31 (channel), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (pixel of the tile).
+// Stores go through a buffer resource that covers exactly this image: a strip pixel outside it (a short last strip, the table's
+// sentinel) has an out-of-range offset and is dropped by the hardware -- no branches around the stores.  sbase = byte offset of
+// (the strip's first output row, this lane's channel); a stride-2 pass P writes output-row parity P, accumulator pw column parity pw.
+template <int P>
+__device__ __forceinline__ void convt_store(const f32x16 (&ac)[CONVT_PASS[P].NAC], __amdgpu_buffer_rsrc_t yr, const int* cl_off, int nt, int h,
+                                            unsigned sbase, bool relu, int Wout, int ldo) {
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        const int4 off = *reinterpret_cast<const int4*>(cl_off + nt * 32 + 8 * g4 + 4 * h);
+        const unsigned offs[4] = {(unsigned)off.x, (unsigned)off.y, (unsigned)off.z, (unsigned)off.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const unsigned o = offs[i] + sbase;
+#pragma unroll
+            for (int pw = 0; pw < CONVT_PASS[P].NAC; ++pw) {
+                float v = ac[pw][4 * g4 + i];
+                if (relu) v = fmaxf(v, 0.0f);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr, o, P == 2 ? 0u : (unsigned)((P * Wout + pw) * ldo) * 4u, 0);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // k_convt_p
 // ---------------------------------------------------------------------------------------------------------
 template <int MODE, int NPF>
 __global__ void __launch_bounds__(256, 3) k_convt_p(const ConvGArgs a) {
     __shared__ int cl_off[128];                      // per strip pixel: byte offset of its (first-parity) output pixel for r0 = 0
-    extern __shared__ float4 cl_x[];                 // [RPa ring slots + 16 zero slots][Cin / 4 + 1] float4
+    // cl_x: [RPa ring slots + 16 zero slots][Cin / 4 + 1] float4
     constexpr int PADT = MODE == 1 ? 1 : 0;
     constexpr int NV = MODE == 1 ? 9 : 4;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -77,22 +215,9 @@ __global__ void __launch_bounds__(256, 3) k_convt_p(const ConvGArgs a) {
     const int nt = wave % ntw, mt = wave / ntw;
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Wp), 0, 0x7fffffff, 0x00020000);
     const unsigned wl = (unsigned)lane * 16u;
-    // The first weight fragments of a pass are requested BEFORE the previous pass's store epilogue (and, for a strip's first pass,
-    // before the barriers in front of it): requested at the top of a pass they exposed an L2 round trip per pass -- two per strip on
-    // the stride-2 layers.  fa = fragment set of channel block 0 of the upcoming pass, fb = block 1 (pass 0 keeps two sets).
-    constexpr int ptp_[3][9] = {{4, 5, 3, 0, 0, 0, 0, 0, 0}, {7, 8, 6, 1, 2, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};
+    auto frag0 = [&](int tap) -> int { return (tap * a.mtiles + mt) * KC; };
     float4 fa[9], fb[3];
-    auto preload = [&](int P) {        // P = table row of the upcoming pass
-        const int n = P == 0 ? 3 : P == 1 ? 6 : 9;
-#pragma unroll
-        for (int m = 0; m < 9; ++m)
-            if (m < n) fa[m] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)(((ptp_[P][m] * a.mtiles + mt) * KC) * 64) * 16u, 0));
-        if (P == 0) {
-#pragma unroll
-            for (int m = 0; m < 3; ++m) fb[m] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)(((ptp_[0][m] * a.mtiles + mt) * KC + 1) * 64) * 16u, 0));
-        }
-    };
-    preload(MODE == 2 ? 0 : 2);
+    convt_preload<MODE == 2 ? 0 : 2>(fa, fb, wr, wl, frag0);
     __syncthreads();
 
     const int q = nt * 32 + j;
@@ -129,88 +254,14 @@ __global__ void __launch_bounds__(256, 3) k_convt_p(const ConvGArgs a) {
         // slots of the TH oldest rows.  (the element index is laundered per strip: its offsets are loop invariants that hipcc would
         // otherwise keep in registers across the whole strip loop)
         int pp0 = ppt; asm volatile("" : "+v"(pp0));
-        auto request_next = [&]() {
-            const int P0 = (r0 + TH + 1) * Win;
-#pragma unroll
-            for (int i = 0; i < NPF; ++i) pf[i] = fetch(P0 + pp0 + i * pstep, pp0 + i * pstep < SPX);
-        };
+        auto request_next = [&]() { ring_request(pf, fetch, (r0 + TH + 1) * Win, pp0, pstep, SPX); };
         if (busy) {
-            // Stride 2: two passes over the strip, one per output-row parity (3 taps -> parities (0,0) (0,1); 6 taps -> (1,0) (1,1)): 32
-            // accumulator registers live instead of 64, so three waves per SIMD fit.  Stride 1: one pass of nine taps (table row 2).
             auto run_pass = [&](auto PC) {
-                constexpr int P = decltype(PC)::value;      // table row: 0 / 1 = the two passes of the stride-2 layers, 2 = the stride-1 layer
-                constexpr int NMP = P == 0 ? 3 : P == 1 ? 6 : 9, NVP = P == 0 ? 2 : P == 1 ? 4 : 9, NAC = P == 2 ? 1 : 2;
-                constexpr int pvw[3][9] = {{0, 0, 1, 0, 0, 0, 0, 0, 0}, {0, 0, 1, 2, 2, 3, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};
-                constexpr int ptp[3][9] = {{4, 5, 3, 0, 0, 0, 0, 0, 0}, {7, 8, 6, 1, 2, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};
-                constexpr int pac[3][9] = {{0, 1, 1, 0, 0, 0, 0, 0, 0}, {0, 1, 1, 0, 1, 1, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-                f32x16 ac[NAC];
-#pragma unroll
-                for (int p = 0; p < NAC; ++p)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) ac[p][e] = bias;       // a lane owns one output channel: the bias is the accumulator's start value
-                // one contraction step: the strip views of block kc (requested a step earlier) against fragment set av; every
-                // fragment is re-requested for block kc + AD right behind the MFMAs that consumed it, every view for block kc + 1
-                // behind its last reader, so each wait leaves the newer requests in flight (a bulk request per step made hipcc
-                // wait for all of them in the middle of the step)
-                constexpr int vlast[3][9] = {{1, 2, 0, 0, 0, 0, 0, 0, 0}, {1, 2, 4, 5, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};      // last MFMA group that reads view v
-                // (pass 0 keeps two fragment sets, AD = 2 blocks ahead: its three groups are only 768 cycles; pass 1 refills one set, AD = 1)
-                constexpr int AD = P == 0 ? 2 : 1;
-                auto step = [&](float4 (&av)[NMP], float4 (&bv)[NVP], int kc) {
-#pragma unroll
-                    for (int m = 0; m < NMP; ++m) {
-                        const float4 b = bv[pvw[P][m]];
-                        f32x16& c = ac[pac[P][m]];
-                        c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, av[m].x, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, av[m].y, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, av[m].z, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, av[m].w, c, 0, 0, 0);
-                        if (kc + AD < KC) {
-                            const u32x4g v = __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)(((ptp[P][m] * a.mtiles + mt) * KC + kc + AD) * 64) * 16u, 0);
-                            av[m] = __builtin_bit_cast(float4, v);
-                        }
-#pragma unroll
-                        for (int v = 0; v < NVP; ++v)
-                            if (vlast[P][v] == m && kc + 1 < KC) bv[v] = cl_x[vb[v] + 2 * (kc + 1)];      // view v is free: block kc + 1 in place
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                };
-                float4 a0[NMP], a1[AD == 2 ? NMP : 1], bv[NVP];
-#pragma unroll
-                for (int m = 0; m < NMP; ++m) a0[m] = fa[m];                  // requested before the previous pass's epilogue / the strip barriers
-                if (AD == 2) {
-#pragma unroll
-                    for (int m = 0; m < NMP; ++m) a1[m % (AD == 2 ? NMP : 1)] = fb[m % 3];
-                }
-#pragma unroll
-                for (int v = 0; v < NVP; ++v) bv[v] = cl_x[vb[v]];
-                for (int kc = 0; kc < KC; kc += 2) {
-                    if (P >= 1 && kc + 2 >= KC && more) request_next();     // behind the strip's last fragment request
-                    __builtin_amdgcn_sched_barrier(0);
-                    step(a0, bv, kc);
-                    if constexpr (AD == 2) step(a1, bv, kc + 1); else step(a0, bv, kc + 1);
-                }
-                preload(P == 0 ? 1 : P == 1 ? 0 : 2);                          // the next pass's first fragments, ahead of this pass's stores
-                // epilogue: C/D layout column = lane & 31 (channel), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (pixel of the tile).
-                // Stores go through a buffer resource that covers exactly this image: a strip pixel outside it (a short last strip, the
-                // table's sentinel) has an out-of-range offset and is dropped by the hardware -- no branches around the stores.
-                if (co < a.Cout) {
-                    const unsigned sbase = (unsigned)(s * strip_floats + co) * 4u;
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int4 off = *reinterpret_cast<const int4*>(cl_off + nt * 32 + 8 * g4 + 4 * h);
-                        const unsigned offs[4] = {(unsigned)off.x, (unsigned)off.y, (unsigned)off.z, (unsigned)off.w};
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const unsigned o = offs[i] + sbase;
-#pragma unroll
-                            for (int pw = 0; pw < NAC; ++pw) {
-                                float v = ac[pw][4 * g4 + i];
-                                if (a.relu) v = fmaxf(v, 0.0f);
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr, o, P == 2 ? 0u : (unsigned)((P * a.Wout + pw) * a.ldo) * 4u, 0);
-                            }
-                        }
-                    }
-                }
+                constexpr int P = decltype(PC)::value;      // 0 / 1 = the two passes of the stride-2 layers, 2 = the stride-1 layer
+                f32x16 ac[CONVT_PASS[P].NAC];
+                convt_contract<P>(ac, bias, fa, fb, wr, wl, frag0, KC, vb, [&]() { if (P >= 1 && more) request_next(); });
+                convt_preload<P == 0 ? 1 : P == 1 ? 0 : 2>(fa, fb, wr, wl, frag0);      // the next pass's first fragments, ahead of this pass's stores
+                if (co < a.Cout) convt_store<P>(ac, yr, cl_off, nt, h, (unsigned)(s * strip_floats + co) * 4u, a.relu, a.Wout, a.ldo);
             };
             if constexpr (MODE == 2) {
                 run_pass(std::integral_constant<int, 0>{});
@@ -223,17 +274,7 @@ __global__ void __launch_bounds__(256, 3) k_convt_p(const ConvGArgs a) {
         }
         if (!more) break;
         __syncthreads();                                   // every wave is done reading the rows that are replaced
-        {
-            int nb = bs + (TH + 1) * Win;                  // slot of the first new pixel = slot of the oldest row
-            if (nb >= RPa) nb -= RPa;
-#pragma unroll
-            for (int i = 0; i < NPF; ++i) {
-                const int pp = pp0 + i * pstep;
-                int sl = nb + pp;
-                if (sl >= RPa) sl -= RPa;
-                if (pp < SPX) cl_x[sl * PS4 + c4] = pf[i];
-            }
-        }
+        ring_commit(pf, bs + (TH + 1) * Win, pp0, pstep, SPX, RPa, PS4, c4);      // slot of the first new pixel = slot of the oldest row
         bs += SPX;
         if (bs >= RPa) bs -= RPa;
         __syncthreads();
@@ -257,7 +298,7 @@ __global__ void __launch_bounds__(256, 3) k_convt_p(const ConvGArgs a) {
 template <int NPF>
 __global__ void __launch_bounds__(256, 2) k_convt_12(const ConvT12Args a) {
     __shared__ int cl_off[128];                      // per strip pixel: byte offset of its (first-parity) output pixel for r0 = 0
-    extern __shared__ float4 cl_x[];                 // [x ring RPa][y1 ring RYa][16 zero slots][1 dummy slot] x 17 float4
+    // cl_x: [x ring RPa][y1 ring RYa][16 zero slots][1 dummy slot] x 17 float4
     constexpr int KC = 8, C4 = 16, PS4 = 17, Cin = 64, MTL = 2;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -299,21 +340,14 @@ __global__ void __launch_bounds__(256, 2) k_convt_12(const ConvT12Args a) {
     const __amdgpu_buffer_rsrc_t wr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W1p) + mt * (KC * 256), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t wr2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W2p) + mt * (KC * 256), 0, 0x7fffffff, 0x00020000);
     const unsigned wl = (unsigned)lane * 16u;
-    // first weight fragments of the upcoming pass (see k_convt_p): table row 2 = the stride-1 pass (layer 1), rows 0 / 1 = the stride-2 passes (layer 2)
-    constexpr int ptp_[3][9] = {{4, 5, 3, 0, 0, 0, 0, 0, 0}, {7, 8, 6, 1, 2, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};
+    // pass 2 = the stride-1 pass (layer 1, W1p), passes 0 / 1 = the stride-2 passes (layer 2, W2p)
+    auto frag0 = [](int tap) -> int { return tap * MTL * KC; };
     float4 fa[9], fb[3];
-    auto preload = [&](int P) {
-        const int n = P == 0 ? 3 : P == 1 ? 6 : 9;
-        const __amdgpu_buffer_rsrc_t wr = P == 2 ? wr1 : wr2;
-#pragma unroll
-        for (int m = 0; m < 9; ++m)
-            if (m < n) fa[m] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)((ptp_[P][m] * MTL * KC) * 64) * 16u, 0));
-        if (P == 0) {
-#pragma unroll
-            for (int m = 0; m < 3; ++m) fb[m] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)((ptp_[0][m] * MTL * KC + 1) * 64) * 16u, 0));
-        }
-    };
-    preload(2);
+    auto preload = [&](auto PC) { convt_preload<decltype(PC)::value>(fa, fb, decltype(PC)::value == 2 ? wr1 : wr2, wl, frag0); };
+    constexpr std::integral_constant<int, 0> P0{};
+    constexpr std::integral_constant<int, 1> P1{};
+    constexpr std::integral_constant<int, 2> P2{};
+    preload(P2);
     __syncthreads();
 
     const int q = nt * 32 + j;
@@ -328,64 +362,15 @@ __global__ void __launch_bounds__(256, 2) k_convt_12(const ConvT12Args a) {
     float* const y1f = reinterpret_cast<float*>(cl_x);
     const int ydummy = (ZP + 16) * (PS4 * 4) + lane;   // float index of this lane's dummy slot (one more pixel slot behind the zero region)
 
-    // one pass over this wave's tile: the contraction of k_convt_p (fragment / view schedule unchanged)
     float4 pf[NPF];
     int pp0 = 0;
     int rA0 = 0; bool moreA = false;
-    auto request_next = [&]() {                        // the x rows rA0 + TH + 1 .. rA0 + 2 TH of round i + 1: one contiguous block of SPX pixels
-        const int P0 = (rA0 + TH + 1) * Win;
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) pf[i] = fetch(P0 + pp0 + i * pstep, pp0 + i * pstep < SPX);
-    };
-    auto run_pass = [&](auto PC, const int (&vb)[9], auto epilogue) {
+    // the x rows rA0 + TH + 1 .. rA0 + 2 TH of round i + 1: one contiguous block of SPX pixels
+    auto request_next = [&]() { ring_request(pf, fetch, (rA0 + TH + 1) * Win, pp0, pstep, SPX); };
+    auto run_pass = [&](auto PC, const int (&vb)[9], auto epilogue) {      // one pass over this wave's tile
         constexpr int P = decltype(PC)::value;
-        constexpr int NMP = P == 0 ? 3 : P == 1 ? 6 : 9, NVP = P == 0 ? 2 : P == 1 ? 4 : 9, NAC = P == 2 ? 1 : 2;
-        constexpr int pvw[3][9] = {{0, 0, 1, 0, 0, 0, 0, 0, 0}, {0, 0, 1, 2, 2, 3, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};
-        constexpr int ptp[3][9] = {{4, 5, 3, 0, 0, 0, 0, 0, 0}, {7, 8, 6, 1, 2, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};
-        constexpr int pac[3][9] = {{0, 1, 1, 0, 0, 0, 0, 0, 0}, {0, 1, 1, 0, 1, 1, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-        constexpr int vlast[3][9] = {{1, 2, 0, 0, 0, 0, 0, 0, 0}, {1, 2, 4, 5, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8}};
-        constexpr int AD = P == 0 ? 2 : 1;
-        const __amdgpu_buffer_rsrc_t wr = P == 2 ? wr1 : wr2;
-        const float bias = P == 2 ? bias1 : bias2;
-        f32x16 ac[NAC];
-#pragma unroll
-        for (int p = 0; p < NAC; ++p)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) ac[p][e] = bias;
-        auto step = [&](float4 (&av)[NMP], float4 (&bv)[NVP], int kc) {
-#pragma unroll
-            for (int m = 0; m < NMP; ++m) {
-                const float4 b = bv[pvw[P][m]];
-                f32x16& c = ac[pac[P][m]];
-                c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, av[m].x, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, av[m].y, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, av[m].z, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, av[m].w, c, 0, 0, 0);
-                if (kc + AD < KC) {
-                    const u32x4g v = __builtin_amdgcn_raw_buffer_load_b128(wr, wl, (unsigned)((ptp[P][m] * MTL * KC + kc + AD) * 64) * 16u, 0);
-                    av[m] = __builtin_bit_cast(float4, v);
-                }
-#pragma unroll
-                for (int v = 0; v < NVP; ++v)
-                    if (vlast[P][v] == m && kc + 1 < KC) bv[v] = cl_x[vb[v] + 2 * (kc + 1)];
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        float4 a0[NMP], a1[AD == 2 ? NMP : 1], bv[NVP];
-#pragma unroll
-        for (int m = 0; m < NMP; ++m) a0[m] = fa[m];
-        if (AD == 2) {
-#pragma unroll
-            for (int m = 0; m < NMP; ++m) a1[m % (AD == 2 ? NMP : 1)] = fb[m % 3];
-        }
-#pragma unroll
-        for (int v = 0; v < NVP; ++v) bv[v] = cl_x[vb[v]];
-        for (int kc = 0; kc < KC; kc += 2) {
-            if (P == 2 && kc + 2 >= KC && moreA) request_next();      // behind the layer-1 pass's last fragment request
-            __builtin_amdgcn_sched_barrier(0);
-            step(a0, bv, kc);
-            if constexpr (AD == 2) step(a1, bv, kc + 1); else step(a0, bv, kc + 1);
-        }
+        f32x16 ac[CONVT_PASS[P].NAC];
+        convt_contract<P>(ac, P == 2 ? bias1 : bias2, fa, fb, P == 2 ? wr1 : wr2, wl, frag0, std::integral_constant<int, KC>{}, vb, [&]() { if (P == 2 && moreA) request_next(); });
         epilogue(ac);
     };
 
@@ -409,8 +394,8 @@ __global__ void __launch_bounds__(256, 2) k_convt_12(const ConvT12Args a) {
                     vb[v] = (ok ? nat : ZP + (nat & 15)) * PS4 + h;
                 }
                 const int ybase = (YB + (i & 1) * SPX) * (PS4 * 4) + co;          // float index of (this half's pixel 0, channel co)
-                run_pass(std::integral_constant<int, 2>{}, vb, [&](f32x16 (&ac)[1]) {
-                    preload(0);                              // layer 2's first fragments, ahead of the ring writes
+                run_pass(P2, vb, [&](f32x16 (&ac)[1]) {
+                    preload(P0);                              // layer 2's first fragments, ahead of the ring writes
                     // C/D layout: column = lane & 31 (channel), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (pixel of the tile)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {            // (a pixel outside the strip goes to a dummy slot: an address select, not a branch per element)
@@ -420,23 +405,13 @@ __global__ void __launch_bounds__(256, 2) k_convt_12(const ConvT12Args a) {
                 });
             } else {
                 if (moreA) request_next();
-                preload(0);
+                preload(P0);
             }
         } else {
-            preload(0);
+            preload(P0);
         }
         __syncthreads();                                   // A(i)'s rows are in the y1 ring; nobody reads the x ring any more
-        if (moreA) {                                       // the x rows of A(i + 1) take the slots of the TH oldest rows
-            int nb = bs + (TH + 1) * Win;
-            if (nb >= RPa) nb -= RPa;
-#pragma unroll
-            for (int k = 0; k < NPF; ++k) {
-                const int pp = pp0 + k * pstep;
-                int sl = nb + pp;
-                if (sl >= RPa) sl -= RPa;
-                if (pp < SPX) cl_x[sl * PS4 + c4] = pf[k];
-            }
-        }
+        if (moreA) ring_commit(pf, bs + (TH + 1) * Win, pp0, pstep, SPX, RPa, PS4, c4);      // the x rows of A(i + 1) take the slots of the TH oldest rows
         bs += SPX;
         if (bs >= RPa) bs -= RPa;
         if (doB) {
@@ -455,29 +430,14 @@ __global__ void __launch_bounds__(256, 2) k_convt_12(const ConvT12Args a) {
                 }
 #pragma unroll
                 for (int v = 4; v < 9; ++v) vb[v] = vb[0];
-                auto store = [&](auto PC, auto& ac) {
-                    constexpr int P = decltype(PC)::value;
-                    const unsigned sbase = (unsigned)(s * strip_floats + co) * 4u;
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int4 off = *reinterpret_cast<const int4*>(cl_off + nt * 32 + 8 * g4 + 4 * h);
-                        const unsigned offs[4] = {(unsigned)off.x, (unsigned)off.y, (unsigned)off.z, (unsigned)off.w};
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const unsigned o = offs[k] + sbase;
-#pragma unroll
-                            for (int pw = 0; pw < 2; ++pw)
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fmaxf(ac[pw][4 * g4 + k], 0.0f)), yr, o, (unsigned)((P * Wout + pw) * 64) * 4u, 0);
-                        }
-                    }
-                };
-                run_pass(std::integral_constant<int, 0>{}, vb, [&](f32x16 (&ac)[2]) { preload(1); store(std::integral_constant<int, 0>{}, ac); });
-                run_pass(std::integral_constant<int, 1>{}, vb, [&](f32x16 (&ac)[2]) { preload(2); store(std::integral_constant<int, 1>{}, ac); });
+                const unsigned sbase = (unsigned)(s * strip_floats + co) * 4u;
+                run_pass(P0, vb, [&](f32x16 (&ac)[2]) { preload(P1); convt_store<0>(ac, yr, cl_off, nt, h, sbase, true, Wout, 64); });
+                run_pass(P1, vb, [&](f32x16 (&ac)[2]) { preload(P2); convt_store<1>(ac, yr, cl_off, nt, h, sbase, true, Wout, 64); });
             } else {
-                preload(2);
+                preload(P2);
             }
         } else {
-            preload(2);
+            preload(P2);
         }
         __syncthreads();                                   // B(i - 1) is done with the half A(i + 1) overwrites; the x ring is complete
     }

@@ -17,6 +17,26 @@
 
 namespace efe {
 
+// The ring row wrap and the store of a tile, shared by the per-layer kernel and the fused one (whose conv1 ring IS the conv2 input
+// ring of k_conv_e<2>: same slots, same de-interleaved columns).  The column slot (x & 1) ? WE + (x >> 1) : (x >> 1) and the tap
+// operand index base_of(t) stay written out in both kernels: as shared functions they changed the kernels' listings (other registers,
+// more s_nop, one VGPR less in k_conv_e<2, 16>; tools/isa_report.py --diff), as they stand every listing is the one before the merge.
+__device__ __forceinline__ int ring_row(int r, int NR) {         // r in [0, 3 NR) -> r mod NR
+    r = r >= NR ? r - NR : r;
+    return r >= NR ? r - NR : r;
+}
+// bias + ReLU of a lane's 16 channels as four float4: register e holds channel (e & 3) + 8 (e >> 2) + 4 h = quad 2 (e >> 2) + h of
+// the pixel, op points at quad h (of an NHWC pixel in global memory or of a ring slot in LDS)
+__device__ __forceinline__ void bias_relu_store(float4* op, const f32x16& acc, const float4 (&bq)[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float4 v;
+        v.x = fmaxf(acc[4 * g] + bq[g].x, 0.f); v.y = fmaxf(acc[4 * g + 1] + bq[g].y, 0.f);
+        v.z = fmaxf(acc[4 * g + 2] + bq[g].z, 0.f); v.w = fmaxf(acc[4 * g + 3] + bq[g].w, 0.f);
+        op[2 * g] = v;
+    }
+}
+
 template <int L, int NPF>
 __global__ void __launch_bounds__(256, 2) k_conv_e(const ConvEArgs a) {
     extern __shared__ __attribute__((aligned(16))) float4 sx[];        // [NR ring rows][Win slots][PS4]
@@ -41,10 +61,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_e(const ConvEArgs a) {
     };
     auto slot_of = [&](int pp, int rs) -> int {                  // pixel pp of a block of rows whose first row has ring slot rs
         const int row = (int)__umulhi((unsigned)pp, a.magicWin), x = pp - row * Win;
-        int r = rs + row;
-        r = r >= NR ? r - NR : r;
-        r = r >= NR ? r - NR : r;
-        return (r * Win + ((x & 1) ? WE + (x >> 1) : (x >> 1))) * PS4 + c4;
+        return (ring_row(rs + row, NR) * Win + ((x & 1) ? WE + (x >> 1) : (x >> 1))) * PS4 + c4;
     };
     // strip 0: input rows 0 .. 2 TY -> ring slots 0 .. NR - 1
     // (NPRO requests in flight together: the whole block for the shapes of BASELINE configs[4] -- batches of 4 were five HBM round trips
@@ -93,9 +110,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_e(const ConvEArgs a) {
             const bool pvx = q < nrows * Wout;
             auto base_of = [&](int t) -> int {          // LDS float4 index of tap t's operand for this lane's pixel
                 const int kh = t / 3, kw = t - 3 * kh;
-                int r = rs0 + 2 * (pvx ? yl : 0) + kh;
-                r = r >= NR ? r - NR : r;
-                r = r >= NR ? r - NR : r;
+                const int r = ring_row(rs0 + 2 * (pvx ? yl : 0) + kh, NR);
                 const int xx = pvx ? x : 0;
                 return (r * Win + (kw == 1 ? WE + xx : xx + (kw >> 1))) * PS4;
             };
@@ -113,14 +128,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_e(const ConvEArgs a) {
                 }, PackedWIdx{1, 4, 0});
             }
             if (pvx) {                                   // bias + ReLU; register e holds channel (e & 3) + 8 (e >> 2) + 4 h
-                float* op = dst + ((size_t)(y0 + yl) * Wout + x) * 32 + 4 * h;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float4 v;
-                    v.x = fmaxf(acc[4 * g] + bq[g].x, 0.f); v.y = fmaxf(acc[4 * g + 1] + bq[g].y, 0.f);
-                    v.z = fmaxf(acc[4 * g + 2] + bq[g].z, 0.f); v.w = fmaxf(acc[4 * g + 3] + bq[g].w, 0.f);
-                    *reinterpret_cast<float4*>(op + 8 * g) = v;
-                }
+                bias_relu_store(reinterpret_cast<float4*>(dst + ((size_t)(y0 + yl) * Wout + x) * 32 + 4 * h), acc, bq);
             }
         }
         if (!more) break;
@@ -216,17 +224,8 @@ __global__ void __launch_bounds__(256, 2) k_conv_e12(const ConvE12Args a) {
         const int p = T * 32 + j;
         if (p < npx) {                                  // bias + ReLU; register e holds channel (e & 3) + 8 (e >> 2) + 4 h = quad 2 (e >> 2) + h
             const int rk = (int)__umulhi((unsigned)p, a.magicW1), x = p - rk * W1;
-            int r = slot0 + rk;
-            r = r >= NR ? r - NR : r;
-            r = r >= NR ? r - NR : r;
-            float4* op = sx + (r * W1 + ((x & 1) ? WE + (x >> 1) : (x >> 1))) * PS4 + h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float4 o;
-                o.x = fmaxf(acc[4 * g] + bq1[g].x, 0.f); o.y = fmaxf(acc[4 * g + 1] + bq1[g].y, 0.f);
-                o.z = fmaxf(acc[4 * g + 2] + bq1[g].z, 0.f); o.w = fmaxf(acc[4 * g + 3] + bq1[g].w, 0.f);
-                op[2 * g] = o;
-            }
+            float4* op = sx + (ring_row(slot0 + rk, NR) * W1 + ((x & 1) ? WE + (x >> 1) : (x >> 1))) * PS4 + h;
+            bias_relu_store(op, acc, bq1);
         }
     };
     // The operands of ALL of a wave's tiles of a block (at most E12_ROUNDS: the ring holds <= 80 KB = 568 pixels = 18 tiles) are
@@ -267,9 +266,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_e12(const ConvE12Args a) {
             const bool pvx = q < nrows * W2;
             auto base_of = [&](int t) -> int {          // LDS float4 index of tap t's operand for this lane's pixel
                 const int kh = t / 3, kw = t - 3 * kh;
-                int r = rs0 + 2 * (pvx ? yl : 0) + kh;
-                r = r >= NR ? r - NR : r;
-                r = r >= NR ? r - NR : r;
+                const int r = ring_row(rs0 + 2 * (pvx ? yl : 0) + kh, NR);
                 const int xx = pvx ? x2 : 0;
                 return (r * W1 + (kw == 1 ? WE + xx : xx + (kw >> 1))) * PS4;
             };
@@ -278,14 +275,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_e12(const ConvE12Args a) {
                 wt = t; bs[0] = base_of(t); sw[0] = 0;
             }, PackedWIdx{1, 4, 0});
             if (pvx) {
-                float* op = dst + ((size_t)(y0 + yl) * W2 + x2) * 32 + 4 * h;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float4 v;
-                    v.x = fmaxf(acc[4 * g] + bq2[g].x, 0.f); v.y = fmaxf(acc[4 * g + 1] + bq2[g].y, 0.f);
-                    v.z = fmaxf(acc[4 * g + 2] + bq2[g].z, 0.f); v.w = fmaxf(acc[4 * g + 3] + bq2[g].w, 0.f);
-                    *reinterpret_cast<float4*>(op + 8 * g) = v;
-                }
+                bias_relu_store(reinterpret_cast<float4*>(dst + ((size_t)(y0 + yl) * W2 + x2) * 32 + 4 * h), acc, bq2);
             }
         }
         if (!more) break;

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Per-kernel register / spill / LDS figures of the BUILT engine library, read from the AMDGPU code-object metadata inside it
 (no recompilation): the gfx950 ELF images are cut out of the .hip_fatbin section and their NT_AMDGPU_METADATA note is printed by
-llvm-readelf.   python tools/isa_report.py [path/to/libefe_mi355x.so]"""
-import os, re, struct, subprocess, sys, tempfile
+llvm-readelf.   python tools/isa_report.py [path/to/libefe_mi355x.so]
+                python tools/isa_report.py --diff OLD.so NEW.so      (per kernel: identical listing, or what differs)"""
+import collections, os, re, struct, subprocess, sys, tempfile
 
 LLVM = '/opt/rocm/lib/llvm/bin'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,7 +76,48 @@ def disassembly(lib=DEFAULT_LIB):
     return {p: res[n] for p, n in zip(pretty, names)}
 
 
+def listing(text):
+    """the instructions of a kernel's listing with everything that depends on where the code sits taken out: addresses, encodings and
+    the symbol + offset form of branch targets (all in the trailing comment; the operand itself is a relative distance), label lines"""
+    out = []
+    for line in text.splitlines():
+        line = re.sub(r'\s+', ' ', line.split('//')[0]).strip()
+        if line and not re.fullmatch(r'(?:[0-9a-f]+ )?<[^>]+>:', line):
+            out.append(line)
+    return out
+
+
+def diff(old, new, out=sys.stdout):
+    """per kernel of either library: 'identical' (same normalised listing and metadata), else the metadata fields (old -> new where
+    they differ) and the per-mnemonic instruction counts that differ: a mnemonic that is not listed occurs equally often on both
+    sides.  -> number of kernels that are not identical"""
+    ko, kn, do, dn = kernels(old), kernels(new), disassembly(old), disassembly(new)
+    changed = 0
+    for k in sorted(set(ko) | set(kn)):
+        if k not in ko or k not in kn:
+            out.write(f'{k}: only in {"NEW" if k in kn else "OLD"}\n')
+            changed += 1
+            continue
+        lo, ln = listing(do.get(k, '')), listing(dn.get(k, ''))
+        if lo == ln and ko[k] == kn[k]:
+            out.write(f'{k}: identical ({len(lo)} instructions)\n')
+            continue
+        changed += 1
+        meta = [f'{f[1:]} {ko[k].get(f)}' + ('' if ko[k].get(f) == kn[k].get(f) else f' -> {kn[k].get(f)}') for f in FIELDS]
+        out.write(f'{k}: DIFFERS, {len(lo)} -> {len(ln)} instructions; metadata ' + ('equal' if ko[k] == kn[k] else 'DIFFERS') + ': ' + ', '.join(meta) + '\n')
+        co, cn = (collections.Counter(i.split()[0] for i in l) for l in (lo, ln))
+        for mn in sorted(set(co) | set(cn)):
+            if co[mn] != cn[mn]:
+                out.write(f'    {mn:40s} {co[mn]:6d} -> {cn[mn]:6d}\n')
+        if co == cn:
+            out.write('    (the same instructions in another order or with other operands)\n')
+    out.write(f'{changed} of {len(set(ko) | set(kn))} kernels differ\n')
+    return changed
+
+
 if __name__ == '__main__':
+    if len(sys.argv) == 4 and sys.argv[1] == '--diff':
+        sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
     ks = kernels(sys.argv[1] if len(sys.argv) > 1 else DEFAULT_LIB)
     print(f'{"kernel":44s} {"vgpr":>5s} {"agpr":>5s} {"sgpr":>5s} {"vspill":>6s} {"sspill":>6s} {"scratch":>7s} {"lds":>7s} {"wg":>5s}')
     for k in sorted(ks):
