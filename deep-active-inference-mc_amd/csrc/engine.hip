@@ -86,6 +86,7 @@ struct efe_ctx {
     int64_t mid_unfused = 0;       // option: 1 = layer-by-layer k_dense transition (A/B experiments)
     float *enc_w1 = nullptr, *enc_b1 = nullptr, *dec_wf = nullptr;
     float dec_bf = 0.f;
+    float* dect_raw = nullptr;     // po_net.13 / .15 / .17 / .19 unpacked, flat in parameters() order (kernels.h DT_*; part of wbufs): train_dec.hip reads it
     float* zeros = nullptr;
     std::vector<void*> owned;      // lives as long as the context
     std::vector<void*> wbufs;      // packed weights of the current commit (freed by the next one)
@@ -597,6 +598,17 @@ size_t plan_bytes(const efe_ctx* c, const CorePlan& p) { return arena_bytes(c, {
 struct RolloutPlan { size_t enc0, x, o8; };
 RolloutPlan rollout_plan(const efe_ctx* ctx, int64_t M) { return {(size_t)M * 32, (size_t)M * 16, ctx->generic ? (size_t)M * ctx->img_store : 0}; }
 size_t plan_bytes(const efe_ctx* c, const RolloutPlan& p) { return arena_bytes(c, {p.enc0, p.x, p.o8}); }
+
+// efe_dec_tail_grad (train_dec.hip): the stored activations and the gradients of one row group (C rows; y_l / po exist only when the caller
+// gives no output for them), nlogpo1 never (required output), and the partial-gradient slabs (none at G = 1: the gradient itself)
+struct DecTailPlan { int C, G; size_t y1, y2, y3, po, g4, g3, g2, g1, slabs; };
+DecTailPlan dec_tail_plan(int64_t M, bool own_y1, bool own_y2, bool own_y3, bool own_po) {
+    const size_t C = (size_t)std::min<int64_t>(DEC_TAIL_ROWS, M);
+    const int G = dec_tail_slabs((int)std::min<int64_t>(M, DEC_TAIL_SLABS));
+    return {(int)C, G, own_y1 ? C * DEC_TAIL_Y1 : 0, own_y2 ? C * DEC_TAIL_Y2 : 0, own_y3 ? C * DEC_TAIL_Y3 : 0, own_po ? C * 4096 : 0,
+            C * 4096, C * DEC_TAIL_Y3, C * DEC_TAIL_Y2, C * DEC_TAIL_Y1, G > 1 ? (size_t)G * DEC_TAIL_P : 0};
+}
+size_t plan_bytes(const efe_ctx* c, const DecTailPlan& p) { return arena_bytes(c, {p.y1, p.y2, p.y3, p.po, p.g4, p.g3, p.g2, p.g1, p.slabs}); }
 
 // the sums, nested as the calls are: run_decoder / run_encoder dispatch on the geometry, run_core runs D transitions and one pass of each
 size_t decoder_bytes(const efe_ctx* ctx, int64_t N) { return ctx->generic ? plan_bytes(ctx, dec_g_plan(ctx, N)) : plan_bytes(ctx, dec_plan(ctx, N)); }
@@ -1282,6 +1294,19 @@ static int pack_encoder(efe_ctx* ctx) {
 // decoder (torchmodel.py:106-128) behind its head: Linear(256, 64 B^2), three ConvTranspose2d ([Cin][Cout][kh][kw]) and the final convolution
 static int pack_decoder(efe_ctx* ctx) {
     const int C = ctx->chan, B = ctx->base;
+    ctx->dect_raw = nullptr;
+    if (C == 1 && ctx->res == 64) {     // the raw copy the backward of the ConvT tail reads (train_dec.hip), beside the packed forward forms
+        std::vector<float> flat;
+        for (int i = 0; i < 4; ++i) {
+            const LayerSpec s = i < 3 ? DEC_CT[i] : LayerSpec{"down.po_net.19", 1, 32};
+            const WB t = weight_and_bias(ctx, s.key, {s.in, s.out, 3, 3}, {s.out});
+            if (!t) return 1;
+            flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
+            flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
+        }
+        if (flat.size() != (size_t)DEC_TAIL_P) return ctx->fail("decoder tail: unexpected parameter count");
+        if (!(ctx->dect_raw = upload(ctx, flat))) return 1;
+    }
     {   // Unflatten(1, (64, B, B)) is channel-major c*B*B + p (torchmodel.py:119); the layer emits NHWC p*64 + c directly
         const std::vector<int> rowp = nhwc_perm(64, B * B);
         if (pack_linear(ctx, ctx->generic ? ctx->g_fc4 : ctx->dec_fc[3], LayerSpec{"down.po_net.9", B * B * 64, 256}, rowp.data())) return 1;
@@ -1323,6 +1348,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         for (void* p : ctx->wbufs) (void)hipFree(p);
         ctx->wbufs.clear();
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
+        ctx->dect_raw = nullptr;
     }
     ctx->committed = false;
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first
@@ -1571,6 +1597,9 @@ int mid_grad_args(efe_ctx* ctx, const float* s0, const float* pi0, const float* 
 
 int64_t efe_param_count(efe_ctx* ctx, const char* part) {
     Call call(ctx, Mode::host); if (!call) return 0;
+    // the decoder's ConvTranspose2d tail po_net.13 / .15 / .17 / .19: a gradient exists (efe_dec_tail_grad), no optimiser step yet, so it is
+    // no part of train_part()
+    if (part && !strcmp(part, "po_net_convt")) return DT_B3 + 32 + 32 * ctx->chan * 9 + ctx->chan;
     if (!train_part(ctx, part, "efe_param_count")) return 0;
     return !strcmp(part, "top") ? part_param_count(TOP_NL, top_layer, ctx->pi_dim) : part_param_count(MID_NL, mid_layer, ctx->pi_dim);
 }
@@ -1654,6 +1683,37 @@ int efe_train_mid(efe_ctx* ctx, const float* s0, const float* pi0, const float* 
     a.g = g.slabs; a.nslab = G; a.m = exp_avg; a.v = exp_avg_sq;    // the same ascending slab sum as k_slab_sum
     tp.dirty = true;
     launch_adam(a, P, st);
+    return call.finish();
+}
+
+// ---- backward of the reconstruction loss through the decoder's ConvTranspose2d tail (train_dec.hip) ----
+int efe_dec_tail_grad(efe_ctx* ctx, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
+                      float* grad, float* y1, float* y2, float* y3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (M <= 0) return ctx->fail("efe_dec_tail_grad: M must be >= 1");
+    if (!h4 || !o1 || !nlogpo1 || !grad) return ctx->fail("efe_dec_tail_grad: h4, o1, nlogpo1 and grad must be non-NULL");
+    if (ctx->chan != 1 || ctx->res != 64 || !ctx->dect_raw) return ctx->fail("efe_dec_tail_grad: built for the 1 x 64 x 64 geometry only");
+    if (ctx->mfma_bf16x3) return ctx->fail("efe_dec_tail_grad: not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+    if (!(scale >= 0.0f)) {
+        if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail("efe_dec_tail_grad: scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
+        scale = beta_o / (float)M;
+    }
+    const DecTailPlan p = dec_tail_plan(M, !y1, !y2, !y3, !po1);
+    float* s1 = ctx->allocT<float>(p.y1); float* s2 = ctx->allocT<float>(p.y2); float* s3 = ctx->allocT<float>(p.y3); float* sp = ctx->allocT<float>(p.po);
+    float* g4 = ctx->allocT<float>(p.g4); float* g3 = ctx->allocT<float>(p.g3); float* g2 = ctx->allocT<float>(p.g2); float* g1 = ctx->allocT<float>(p.g1);
+    float* slabs = p.G > 1 ? ctx->allocT<float>(p.slabs) : grad;
+    if (!s1 || !s2 || !s3 || !sp || !g4 || !g3 || !g2 || !g1 || !slabs) return 1;
+    for (int m0 = 0; m0 < M; m0 += p.C) {       // row groups: boundaries at multiples of DEC_TAIL_ROWS, a function of M alone
+        DecTailArgs a{};
+        a.w = ctx->dect_raw; a.h4 = h4 + (size_t)m0 * DEC_TAIL_Y1; a.o1 = o1 + (size_t)m0 * 4096;
+        a.y1 = y1 ? y1 + (size_t)m0 * DEC_TAIL_Y1 : s1; a.y2 = y2 ? y2 + (size_t)m0 * DEC_TAIL_Y2 : s2; a.y3 = y3 ? y3 + (size_t)m0 * DEC_TAIL_Y3 : s3;
+        a.po = po1 ? po1 + (size_t)m0 * 4096 : sp; a.nlogpo1 = nlogpo1 + m0;
+        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = d_h4 ? d_h4 + (size_t)m0 * DEC_TAIL_Y1 : nullptr;
+        a.slabs = slabs; a.rows = std::min(p.C, M - m0); a.G = p.G; a.first = m0 == 0; a.scale = scale;
+        launch_dec_tail_group(a, st);
+    }
+    if (p.G > 1) launch_slab_sum(slabs, p.G, DEC_TAIL_P, grad, st);
+    ctx->last_macs += (int64_t)M * 3 * 38928384;      // forward, data gradient, weight gradient of the four layers
     return call.finish();
 }
 

@@ -438,6 +438,28 @@ struct MidGradArgs {
 void launch_mid_grad(const MidGradArgs& a, hipStream_t st);
 int init_train_kernels();
 
+// ---- backward of the decoder's ConvTranspose2d tail po_net[12:] at 1 x 64 x 64 (train_dec.hip) -----------------------------
+// The parameters as one flat vector in parameters() order (13.weight, 13.bias, 15.weight, 15.bias, 17.weight, 17.bias, 19.weight, 19.bias),
+// each tensor row-major in the reference's shape ([Cin][Cout][3][3]): the layout of the raw device copy and of the gradient.
+constexpr int DT_W1 = 0, DT_B1 = DT_W1 + 64 * 64 * 9, DT_W2 = DT_B1 + 64, DT_B2 = DT_W2 + 64 * 64 * 9, DT_W3 = DT_B2 + 64,
+              DT_B3 = DT_W3 + 64 * 32 * 9, DT_W4 = DT_B3 + 32, DT_B4 = DT_W4 + 32 * 9, DEC_TAIL_P = DT_B4 + 1;      // 92 609
+constexpr int DEC_TAIL_SLABS = 32;       // partial-gradient slabs: row m adds to slab m mod G, G = dec_tail_slabs(M)
+constexpr int DEC_TAIL_ROWS = 64;        // rows per pass (a multiple of DEC_TAIL_SLABS): bounds the stored activations and gradients
+constexpr size_t DEC_TAIL_Y1 = 64 * 256, DEC_TAIL_Y2 = 64 * 1024, DEC_TAIL_Y3 = 32 * 4096;      // floats per row
+__host__ __device__ inline int dec_tail_slabs(int M) { return M < DEC_TAIL_SLABS ? M : DEC_TAIL_SLABS; }
+struct DecTailArgs {                     // one row group: every pointer is the group's first row
+    const float* w;                      // raw parameters [DEC_TAIL_P]
+    const float* h4; const float* o1;    // [rows][64][16][16], [rows][4096]
+    float *y1, *y2, *y3, *po;            // stored forward
+    float* nlogpo1;                      // [rows]
+    float *g4, *g3, *g2, *g1;            // dL / da_l
+    float* dh4;                          // nullable [rows][64][16][16]
+    float* slabs;                        // [G][DEC_TAIL_P]; first != 0: written, else added to
+    int rows, G, first;
+    float scale;
+};
+void launch_dec_tail_group(const DecTailArgs& a, hipStream_t st);
+
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);
 void launch_root_post(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,

@@ -458,6 +458,25 @@ std::tuple<Tensor, Tensor, Tensor> train_mid(int64_t h, const Tensor& s0_, const
     return {pm, pv, F};
 }
 
+// ---- backward of the decoder's ConvTranspose2d tail (csrc/train_dec.hip) ----
+// d (scale * sum nlogpo1) / d (po_net.13 .. 19, h4) -> (nlogpo1 [M], po1 [M,1,64,64], d_h4 [M,16384], grad [92609], y1, y2, y3); the
+// activations are empty tensors unless want_y; scale < 0: beta_o / M
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> dec_tail_grad(int64_t h, const Tensor& h4_, const Tensor& o1_, double scale, double beta_o,
+                                                                                  bool want_y) {
+    efe_ctx* c = CTX(h);
+    Tensor h4 = in(h4_, "h4"), o1 = in(o1_, "o1");
+    const int M = rows(h4, 16384, "h4");
+    TORCH_CHECK(o1.numel() == (int64_t)M * 4096, "efe: o1 must be [M, 1, 64, 64]");
+    const int64_t NP = efe_param_count(c, "po_net_convt");
+    auto op = h4.options();
+    const int64_t My = want_y ? M : 0;
+    Tensor nl = at::empty({M}, op), po = at::empty({M, 1, 64, 64}, op), dh = at::empty({M, 16384}, op), grad = at::empty({NP}, op);
+    Tensor y1 = at::empty({My, 64, 16, 16}, op), y2 = at::empty({My, 64, 32, 32}, op), y3 = at::empty({My, 32, 64, 64}, op);
+    ok(c, efe_dec_tail_grad(c, h4.data_ptr<float>(), o1.data_ptr<float>(), M, (float)scale, (float)beta_o, P(nl), P(po), P(dh), P(grad),
+                            want_y ? P(y1) : nullptr, want_y ? P(y2) : nullptr, want_y ? P(y3) : nullptr, stream_of(h4)));
+    return {nl, po, dh, grad, y1, y2, y3};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -481,6 +500,7 @@ TORCH_LIBRARY(efe, m) {
     m.def("train_top(int ctx, Tensor s, Tensor log_Ppi, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> Tensor");
     m.def("mid_grad(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset) -> (Tensor F_mid, Tensor ps1_mean, Tensor ps1_logvar, Tensor grad)");
     m.def("train_mid(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> (Tensor ps1_mean, Tensor ps1_logvar, Tensor F_mid)");
+    m.def("dec_tail_grad(int ctx, Tensor h4, Tensor o1, float scale, float beta_o, bool want_y) -> (Tensor nlogpo1, Tensor po1, Tensor d_h4, Tensor grad, Tensor y1, Tensor y2, Tensor y3)");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -504,4 +524,5 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("train_top", &train_top);
     m.impl("mid_grad", &mid_grad);
     m.impl("train_mid", &train_mid);
+    m.impl("dec_tail_grad", &dec_tail_grad);
 }

@@ -4,8 +4,10 @@ composition train.py:104-123 evaluates before its optimizer steps, in one engine
 
 No autograd graph is built.  The habit network and the transition network are trainable: `train_model_top` (torchloss.py:65-74) and
 `train_model_mid` (torchloss.py:76-88) are each one Adam step on the device (csrc/train.hip: backward + update in two launches, with a
-daimc_amd.Adam holding the state), and `grad_top` / `grad_mid` return the gradients.  `train_model_down` (the encoder / decoder) is not
-built, and a training loop is out of scope.  Every call dispatches through torch.ops.efe.* on the model's device; there is no CPU
+daimc_amd.Adam holding the state), and `grad_top` / `grad_mid` return the gradients.  `train_model_down` (torchloss.py:90-98, the encoder /
+decoder) is not built; its first piece is: `grad_decoder_convs` is the backward of the reconstruction term through the decoder's four
+ConvTranspose2d layers (po_net.13 / .15 / .17 / .19, csrc/train_dec.hip) down to the Unflatten's input.  The decoder's dense head, the
+encoder and their optimiser step are still missing, and a training loop is out of scope.  Every call dispatches through torch.ops.efe.* on the model's device; there is no CPU
 fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
@@ -199,3 +201,32 @@ def train_model_mid(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, opt
     mean, lv, _ = e.ops.train_mid(*args, ea, es, *hyper, optimizer._step)
     model_mid._stepped()
     return mean, lv
+
+
+DEC_CONVT_KEYS = tuple(f'po_net.{i}.{sfx}' for i in (13, 15, 17, 19) for sfx in ('weight', 'bias'))
+
+
+def grad_decoder_convs(model_down, h4, o1, *, scale=None, return_activations=False):
+    """Backward of L = scale * sum_r -log p(o1_r) through po_net[12:] (Unflatten, four ConvTranspose2d, ReLUs, sigmoid; torchmodel.py:119-127,
+    torchloss.py:62) -> (nlogpo1 [M], po1 [M,1,64,64], d_h4 [M,16384], {state_dict key: dL / d tensor}) and, with return_activations,
+    (y1, y2, y3), the stored post-ReLU activations (NCHW) whose sign is the backward gate.  h4 [M,16384] is what po_net[0:12] hands to the
+    Unflatten (reference order); scale None = beta_o / M, the decoder's share of F_down.mean().  The gradients are views of one flat tensor
+    in parameters() order.  1 x 64 x 64 models only."""
+    m = model_down._owner
+    if (m.colour_channels, m.resolution) != (1, 64):
+        raise ValueError(f'grad_decoder_convs: built for 1 x 64 x 64 models, this one is {m.colour_channels} x {m.resolution} x {m.resolution}')
+    e = m._ready()
+    h4 = e.tensor(h4, (-1, 16384))
+    M = h4.shape[0]
+    o1 = e.tensor(o1, (M, 1, 64, 64))
+    if scale is not None and not float(scale) >= 0.0:
+        raise ValueError('grad_decoder_convs: scale must be >= 0 (None = beta_o / M)')
+    nl, po1, d_h4, flat, y1, y2, y3 = e.ops.dec_tail_grad(e.h, h4, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o),
+                                                          bool(return_activations))
+    grads, off = {}, 0
+    for key in DEC_CONVT_KEYS:
+        t = model_down._sd[key]
+        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
+        off += t.numel()
+    out = (nl, po1, d_h4, grads)
+    return out + ((y1, y2, y3),) if return_activations else out

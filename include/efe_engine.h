@@ -350,6 +350,27 @@ int efe_train_mid(efe_ctx*, const float* s0, const float* pi0, const float* qs1_
                   const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, float* exp_avg, float* exp_avg_sq,
                   const efe_adam_params* hp, void* stream);
 
+/* ---- backward of the reconstruction loss through the decoder's ConvTranspose2d tail (csrc/train_dec.hip; additive to ABI 6) --------------
+ * The first piece of train_model_down (src/torchloss.py:90-98): the four ConvTranspose2d layers po_net.13 / .15 / .17 / .19 with their
+ * ReLUs, the sigmoid and the binary cross entropy of compute_loss_down (torchloss.py:62), at the 1 x 64 x 64 geometry.  No dropout lies
+ * behind the Unflatten, so the call takes no noise keys.
+ *   h4 [M,16384]   : what po_net[0:12] hands to the Unflatten, the reference's order (64, 16, 16) channel-major
+ *   o1 [M,1,64,64] : the observed image
+ *   scale, beta_o  : the loss is L = scale * sum_r nlogpo1_r.  scale >= 0 is used as given; a NEGATIVE scale means beta_o / M, the
+ *                    decoder's share of F_down.mean() (gamma and beta_s touch only the KL terms, which do not reach po_net)
+ *   nlogpo1 [M]    : -log p(o1), k_fe_down's expression and reduction order: bit-identical however rows are grouped (required)
+ *   po1 [M,4096], d_h4 [M,16384] = dL / dh4 (no gate: the ReLU and dropout in front belong to the dense head), and the stored
+ *   activations y1 [M,64,16,16], y2 [M,64,32,32], y3 [M,32,64,64] (NCHW, after the ReLU): optional, NULL = not wanted
+ *   grad [P]       : dL / d parameters, P = efe_param_count("po_net_convt") = 92 609, flat in parameters() order (13.weight, 13.bias,
+ *                    15.weight, 15.bias, 17.weight, 17.bias, 19.weight, 19.bias), each tensor row-major in the reference's shape (required)
+ * A fixed-order sum that depends on M alone: twice the same bits; the per-row outputs do not depend on the other
+ * rows of the call.  Scratch comes from the context's arena (rows are processed in groups of 64: at most 113 MB of activations and
+ * gradients, and 32 partial gradients of 370 KB).  Returns 1 with a message that names the function for M <= 0, a NULL required pointer, a
+ * context of another geometry, or a split-operand option (mfma_bf16x3 / mfma_f16x2) being on.  There is no optimiser step for this part
+ * yet: efe_adam_step and efe_get_weights refuse the name. */
+int efe_dec_tail_grad(efe_ctx*, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
+                      float* grad, float* y1, float* y2, float* y3, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
