@@ -86,7 +86,8 @@ struct efe_ctx {
     int64_t mid_unfused = 0;       // option: 1 = layer-by-layer k_dense transition (A/B experiments)
     float *enc_w1 = nullptr, *enc_b1 = nullptr, *dec_wf = nullptr;
     float dec_bf = 0.f;
-    float* dect_raw = nullptr;     // po_net.13 / .15 / .17 / .19 unpacked, flat in parameters() order (kernels.h DT_*; part of wbufs): train_dec.hip reads it
+    float* dec_raw = nullptr;      // the whole po_net unpacked, flat in parameters() order (kernels.h DH_*, then DT_*; part of wbufs): train_dec_head.hip reads it
+    float* dect_raw = nullptr;     // its tail po_net.13 / .15 / .17 / .19 (= dec_raw + DEC_HEAD_P): train_dec.hip reads it
     float* zeros = nullptr;
     std::vector<void*> owned;      // lives as long as the context
     std::vector<void*> wbufs;      // packed weights of the current commit (freed by the next one)
@@ -609,6 +610,16 @@ DecTailPlan dec_tail_plan(int64_t M, bool own_y1, bool own_y2, bool own_y3, bool
             C * 4096, C * DEC_TAIL_Y3, C * DEC_TAIL_Y2, C * DEC_TAIL_Y1, G > 1 ? (size_t)G * DEC_TAIL_P : 0};
 }
 size_t plan_bytes(const efe_ctx* c, const DecTailPlan& p) { return arena_bytes(c, {p.y1, p.y2, p.y3, p.po, p.g4, p.g3, p.g2, p.g1, p.slabs}); }
+
+// efe_dec_grad (train_dec_head.hip) on top of the tail's plan: the head's stored activations of one row group (those the caller gives no
+// output for), d_h4 (gated in place to layer 3's gradient), the 64 segment partials of d_h3, and the slabs of layers 0..2 (none at G = 1)
+struct DecHeadPlan { int C, G; size_t h1, h2, h3, h4, dh4, part, slabs; };
+DecHeadPlan dec_head_plan(int64_t M, bool own_h1, bool own_h2, bool own_h3, bool own_h4) {
+    const size_t C = (size_t)std::min<int64_t>(DEC_TAIL_ROWS, M);
+    const int G = dec_head_slabs((int)std::min<int64_t>(M, 16 * DEC_HEAD_SLABS));
+    return {(int)C, G, own_h1 ? C * 256 : 0, own_h2 ? C * 256 : 0, own_h3 ? C * 256 : 0, own_h4 ? C * DEC_TAIL_Y1 : 0, C * DEC_TAIL_Y1,
+            (size_t)DEC_HEAD_SEGS * C * 256, G > 1 ? (size_t)G * DEC_HEAD_SMALL_P : 0};
+}
 
 // the sums, nested as the calls are: run_decoder / run_encoder dispatch on the geometry, run_core runs D transitions and one pass of each
 size_t decoder_bytes(const efe_ctx* ctx, int64_t N) { return ctx->generic ? plan_bytes(ctx, dec_g_plan(ctx, N)) : plan_bytes(ctx, dec_plan(ctx, N)); }
@@ -1294,9 +1305,17 @@ static int pack_encoder(efe_ctx* ctx) {
 // decoder (torchmodel.py:106-128) behind its head: Linear(256, 64 B^2), three ConvTranspose2d ([Cin][Cout][kh][kw]) and the final convolution
 static int pack_decoder(efe_ctx* ctx) {
     const int C = ctx->chan, B = ctx->base;
-    ctx->dect_raw = nullptr;
-    if (C == 1 && ctx->res == 64) {     // the raw copy the backward of the ConvT tail reads (train_dec.hip), beside the packed forward forms
+    ctx->dec_raw = ctx->dect_raw = nullptr;
+    if (C == 1 && ctx->res == 64) {     // the raw copy the backward passes read (train_dec_head.hip, train_dec.hip), beside the packed forward forms
         std::vector<float> flat;
+        for (int i = 0; i < 4; ++i) {
+            const LayerSpec s = i < 3 ? DEC_HEAD[i] : LayerSpec{"down.po_net.9", 16384, 256};
+            const WB t = weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
+            if (!t) return 1;
+            flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
+            flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
+        }
+        if (flat.size() != (size_t)DEC_HEAD_P) return ctx->fail("decoder head: unexpected parameter count");
         for (int i = 0; i < 4; ++i) {
             const LayerSpec s = i < 3 ? DEC_CT[i] : LayerSpec{"down.po_net.19", 1, 32};
             const WB t = weight_and_bias(ctx, s.key, {s.in, s.out, 3, 3}, {s.out});
@@ -1304,8 +1323,9 @@ static int pack_decoder(efe_ctx* ctx) {
             flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
             flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
         }
-        if (flat.size() != (size_t)DEC_TAIL_P) return ctx->fail("decoder tail: unexpected parameter count");
-        if (!(ctx->dect_raw = upload(ctx, flat))) return 1;
+        if (flat.size() != (size_t)DEC_P) return ctx->fail("decoder tail: unexpected parameter count");
+        if (!(ctx->dec_raw = upload(ctx, flat))) return 1;
+        ctx->dect_raw = ctx->dec_raw + DEC_HEAD_P;
     }
     {   // Unflatten(1, (64, B, B)) is channel-major c*B*B + p (torchmodel.py:119); the layer emits NHWC p*64 + c directly
         const std::vector<int> rowp = nhwc_perm(64, B * B);
@@ -1348,7 +1368,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         for (void* p : ctx->wbufs) (void)hipFree(p);
         ctx->wbufs.clear();
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
-        ctx->dect_raw = nullptr;
+        ctx->dec_raw = ctx->dect_raw = nullptr;
     }
     ctx->committed = false;
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first
@@ -1600,6 +1620,8 @@ int64_t efe_param_count(efe_ctx* ctx, const char* part) {
     // the decoder's ConvTranspose2d tail po_net.13 / .15 / .17 / .19: a gradient exists (efe_dec_tail_grad), no optimiser step yet, so it is
     // no part of train_part()
     if (part && !strcmp(part, "po_net_convt")) return DT_B3 + 32 + 32 * ctx->chan * 9 + ctx->chan;
+    // the whole decoder (efe_dec_grad), likewise without an optimiser step
+    if (part && !strcmp(part, "po_net")) return DH_W3 + (int64_t)64 * ctx->base * ctx->base * 257 + DT_B3 + 32 + 32 * ctx->chan * 9 + ctx->chan;
     if (!train_part(ctx, part, "efe_param_count")) return 0;
     return !strcmp(part, "top") ? part_param_count(TOP_NL, top_layer, ctx->pi_dim) : part_param_count(MID_NL, mid_layer, ctx->pi_dim);
 }
@@ -1714,6 +1736,54 @@ int efe_dec_tail_grad(efe_ctx* ctx, const float* h4, const float* o1, int M, flo
     }
     if (p.G > 1) launch_slab_sum(slabs, p.G, DEC_TAIL_P, grad, st);
     ctx->last_macs += (int64_t)M * 3 * 38928384;      // forward, data gradient, weight gradient of the four layers
+    return call.finish();
+}
+
+// ---- backward of the reconstruction loss through the whole decoder: dense head (train_dec_head.hip) + ConvT tail (train_dec.hip) ----
+int efe_dec_grad(efe_ctx* ctx, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
+                 float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (M <= 0) return ctx->fail("efe_dec_grad: M must be >= 1");
+    if (!s || !o1 || !nz || !nlogpo1 || !grad) return ctx->fail("efe_dec_grad: s, o1, nz, nlogpo1 and grad must be non-NULL");
+    if (ctx->chan != 1 || ctx->res != 64 || !ctx->dec_raw) return ctx->fail("efe_dec_grad: built for the 1 x 64 x 64 geometry only");
+    if (ctx->mfma_bf16x3) return ctx->fail("efe_dec_grad: not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+    if (!(scale >= 0.0f)) {
+        if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail("efe_dec_grad: scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
+        scale = beta_o / (float)M;
+    }
+    const DecTailPlan p = dec_tail_plan(M, !y1, !y2, !y3, !po1);
+    const DecHeadPlan hp = dec_head_plan(M, !h1, !h2, !h3, !h4);
+    float* s1 = ctx->allocT<float>(p.y1); float* s2 = ctx->allocT<float>(p.y2); float* s3 = ctx->allocT<float>(p.y3); float* sp = ctx->allocT<float>(p.po);
+    float* g4 = ctx->allocT<float>(p.g4); float* g3 = ctx->allocT<float>(p.g3); float* g2 = ctx->allocT<float>(p.g2); float* g1 = ctx->allocT<float>(p.g1);
+    float* tgrad = grad + DEC_HEAD_P;           // the tail's gradient, laid out as efe_dec_tail_grad's
+    float* tslabs = p.G > 1 ? ctx->allocT<float>(p.slabs) : tgrad;
+    float* a1 = ctx->allocT<float>(hp.h1); float* a2 = ctx->allocT<float>(hp.h2); float* a3 = ctx->allocT<float>(hp.h3); float* a4 = ctx->allocT<float>(hp.h4);
+    float* dh4 = ctx->allocT<float>(hp.dh4); float* part = ctx->allocT<float>(hp.part);
+    float* hslabs = hp.G > 1 ? ctx->allocT<float>(hp.slabs) : grad;
+    if (!s1 || !s2 || !s3 || !sp || !g4 || !g3 || !g2 || !g1 || !tslabs || !a1 || !a2 || !a3 || !a4 || !dh4 || !part || !hslabs) return 1;
+    for (int m0 = 0; m0 < M; m0 += p.C) {       // row groups: boundaries at multiples of DEC_TAIL_ROWS, a function of M alone
+        const int rows = std::min(p.C, M - m0);
+        DecHeadArgs h{};
+        h.w = ctx->dec_raw; h.s = s + (size_t)m0 * S_DIM;
+        h.h1 = h1 ? h1 + (size_t)m0 * 256 : a1; h.h2 = h2 ? h2 + (size_t)m0 * 256 : a2; h.h3 = h3 ? h3 + (size_t)m0 * 256 : a3;
+        h.h4 = h4 ? h4 + (size_t)m0 * DEC_TAIL_Y1 : a4;
+        h.g4 = dh4; h.part = part; h.ds = d_s ? d_s + (size_t)m0 * S_DIM : nullptr; h.grad = grad; h.slabs = hslabs;
+        h.rows = rows; h.first = m0 == 0;
+        h.k0 = (uint32_t)nz->seed; h.k1 = (uint32_t)(nz->seed >> 32); h.row0 = nz->row_offset + (uint32_t)m0;
+        h.stream = stream_id(nz->pass, nz->sample); h.stage = nz->stage;
+        launch_dec_head_fwd(h, st);
+        DecTailArgs a{};
+        a.w = ctx->dect_raw; a.h4 = h.h4; a.o1 = o1 + (size_t)m0 * 4096;
+        a.y1 = y1 ? y1 + (size_t)m0 * DEC_TAIL_Y1 : s1; a.y2 = y2 ? y2 + (size_t)m0 * DEC_TAIL_Y2 : s2; a.y3 = y3 ? y3 + (size_t)m0 * DEC_TAIL_Y3 : s3;
+        a.po = po1 ? po1 + (size_t)m0 * 4096 : sp; a.nlogpo1 = nlogpo1 + m0;
+        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = dh4;
+        a.slabs = tslabs; a.rows = rows; a.G = p.G; a.first = m0 == 0; a.scale = scale;
+        launch_dec_tail_group(a, st);
+        launch_dec_head_bwd(h, st);
+    }
+    if (p.G > 1) launch_slab_sum(tslabs, p.G, DEC_TAIL_P, tgrad, st);
+    if (hp.G > 1) launch_slab_sum(hslabs, hp.G, DEC_HEAD_SMALL_P, grad, st);
+    ctx->last_macs += (int64_t)M * 3 * (38928384 + 4328960);      // forward, data gradient, weight gradient of the eight layers
     return call.finish();
 }
 

@@ -460,6 +460,30 @@ struct DecTailArgs {                     // one row group: every pointer is the 
 };
 void launch_dec_tail_group(const DecTailArgs& a, hipStream_t st);
 
+// ---- backward of the decoder's dense head po_net[0:12] at 1 x 64 x 64 (train_dec_head.hip) ---------------------------------
+// The whole po_net as one flat vector in parameters() order: 0.weight [256][10], 0.bias, 3.weight [256][256], 3.bias, 6.weight, 6.bias,
+// 9.weight [16384][256], 9.bias, then the tail's DEC_TAIL_P (DT_* offsets behind DEC_HEAD_P): the raw device copy and the gradient.
+constexpr int DH_W0 = 0, DH_B0 = DH_W0 + 256 * 10, DH_W1 = DH_B0 + 256, DH_B1 = DH_W1 + 256 * 256, DH_W2 = DH_B1 + 256, DH_B2 = DH_W2 + 256 * 256,
+              DEC_HEAD_SMALL_P = DH_B2 + 256,                                     // 134 400: one partial-gradient slab of layers 0..2
+              DH_W3 = DEC_HEAD_SMALL_P, DH_B3 = DH_W3 + 16384 * 256, DEC_HEAD_P = DH_B3 + 16384, DEC_P = DEC_HEAD_P + DEC_TAIL_P;      // 4 345 088, 4 437 697
+constexpr int DEC_HEAD_SLABS = 4;        // slabs of layers 0..2: 16-row tile t adds to slab t mod G, G = dec_head_slabs(M) (four tiles per row group)
+constexpr int DEC_HEAD_SEGS = 64;        // K segments (256 features each) of d_h3 = g4 W4
+__host__ __device__ inline int dec_head_slabs(int M) { const int t = (M + 15) / 16; return t < DEC_HEAD_SLABS ? t : DEC_HEAD_SLABS; }
+struct DecHeadArgs {                     // one row group (at most DEC_TAIL_ROWS rows): every row pointer is the group's first row
+    const float* w;                      // raw parameters [DEC_P]
+    const float* s;                      // [rows][10]
+    float *h1, *h2, *h3, *h4;            // stored forward, after the mask: [rows][256] x 3, [rows][16384] (reference order c 256 + p)
+    float* g4;                           // in: d_h4 [rows][16384] of the tail; gated in place to dL / da of layer 3
+    float* part;                         // [DEC_HEAD_SEGS][rows][256] partial sums of g4 W4
+    float* ds;                           // nullable [rows][10]
+    float* grad;                         // the caller's gradient [DEC_P]: 9.weight / 9.bias are written (first) or added to in place
+    float* slabs;                        // [G][DEC_HEAD_SMALL_P]; first != 0: written, else added to
+    int rows, first;
+    uint32_t k0, k1, row0, stream, stage;        // Philox key, global row of the group's row 0, stream_id(pass, sample), stage
+};
+void launch_dec_head_fwd(const DecHeadArgs& a, hipStream_t st);       // s -> h1 .. h4
+void launch_dec_head_bwd(const DecHeadArgs& a, hipStream_t st);       // d_h4 -> the head's gradients and d_s
+
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);
 void launch_root_post(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,

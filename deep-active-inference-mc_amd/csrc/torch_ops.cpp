@@ -477,6 +477,29 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> dec_tail_grad
     return {nl, po, dh, grad, y1, y2, y3};
 }
 
+// ---- backward of the whole decoder (csrc/train_dec_head.hip + csrc/train_dec.hip) ----
+// d (scale * sum nlogpo1) / d (po_net, s) -> (nlogpo1 [M], po1 [M,1,64,64], d_s [M,10], grad [4437697], h1, h2, h3, h4, y1, y2, y3); the
+// activations are empty tensors unless want_act; scale < 0: beta_o / M
+std::vector<Tensor> dec_grad(int64_t h, const Tensor& s_, const Tensor& o1_, double scale, double beta_o, int64_t seed, int64_t stage, int64_t pass,
+                             int64_t sample, int64_t row_offset, bool want_act) {
+    efe_ctx* c = CTX(h);
+    Tensor s = in(s_, "s"), o1 = in(o1_, "o1");
+    const int M = rows(s, 10, "s");
+    TORCH_CHECK(o1.numel() == (int64_t)M * 4096, "efe: o1 must be [M, 1, 64, 64]");
+    const int64_t NP = efe_param_count(c, "po_net");
+    TORCH_CHECK(NP > 0, "efe engine: ", efe_last_error(c));
+    const efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    auto op = s.options();
+    const int64_t Ma = want_act ? M : 0;
+    Tensor nl = at::empty({M}, op), po = at::empty({M, 1, 64, 64}, op), ds = at::empty({M, 10}, op), grad = at::empty({NP}, op);
+    Tensor h1 = at::empty({Ma, 256}, op), h2 = at::empty({Ma, 256}, op), h3 = at::empty({Ma, 256}, op), h4 = at::empty({Ma, 16384}, op);
+    Tensor y1 = at::empty({Ma, 64, 16, 16}, op), y2 = at::empty({Ma, 64, 32, 32}, op), y3 = at::empty({Ma, 32, 64, 64}, op);
+    auto A = [&](Tensor& t) { return want_act ? P(t) : nullptr; };
+    ok(c, efe_dec_grad(c, s.data_ptr<float>(), o1.data_ptr<float>(), M, (float)scale, (float)beta_o, &nz, P(nl), P(po), P(ds), P(grad),
+                       A(h1), A(h2), A(h3), A(h4), A(y1), A(y2), A(y3), stream_of(s)));
+    return {nl, po, ds, grad, h1, h2, h3, h4, y1, y2, y3};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -501,6 +524,7 @@ TORCH_LIBRARY(efe, m) {
     m.def("mid_grad(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset) -> (Tensor F_mid, Tensor ps1_mean, Tensor ps1_logvar, Tensor grad)");
     m.def("train_mid(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> (Tensor ps1_mean, Tensor ps1_logvar, Tensor F_mid)");
     m.def("dec_tail_grad(int ctx, Tensor h4, Tensor o1, float scale, float beta_o, bool want_y) -> (Tensor nlogpo1, Tensor po1, Tensor d_h4, Tensor grad, Tensor y1, Tensor y2, Tensor y3)");
+    m.def("dec_grad(int ctx, Tensor s, Tensor o1, float scale, float beta_o, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -525,4 +549,5 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("mid_grad", &mid_grad);
     m.impl("train_mid", &train_mid);
     m.impl("dec_tail_grad", &dec_tail_grad);
+    m.impl("dec_grad", &dec_grad);
 }

@@ -5,10 +5,12 @@ composition train.py:104-123 evaluates before its optimizer steps, in one engine
 No autograd graph is built.  The habit network and the transition network are trainable: `train_model_top` (torchloss.py:65-74) and
 `train_model_mid` (torchloss.py:76-88) are each one Adam step on the device (csrc/train.hip: backward + update in two launches, with a
 daimc_amd.Adam holding the state), and `grad_top` / `grad_mid` return the gradients.  `train_model_down` (torchloss.py:90-98, the encoder /
-decoder) is not built; its first piece is: `grad_decoder_convs` is the backward of the reconstruction term through the decoder's four
-ConvTranspose2d layers (po_net.13 / .15 / .17 / .19, csrc/train_dec.hip) down to the Unflatten's input.  The decoder's dense head, the
-encoder and their optimiser step are still missing, and a training loop is out of scope.  Every call dispatches through torch.ops.efe.* on the model's device; there is no CPU
-fallback.
+decoder) is not built; its decoder half is: `grad_decoder` is the gradient of the reconstruction term with respect to every parameter of
+po_net and to s in one engine call -- the dense head po_net.0 / .3 / .6 / .9 evaluated for training with the forward decoder's four
+dropout masks (csrc/train_dec_head.hip), then the four ConvTranspose2d layers (po_net.13 / .15 / .17 / .19, csrc/train_dec.hip), which
+`grad_decoder_convs` also runs on their own from a given Unflatten input.  The optimiser step for po_net, the encoder's backward and
+train_model_down itself are still missing, and a training loop is out of scope.  Every call dispatches through torch.ops.efe.* on the
+model's device; there is no CPU fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
 encoder, FE_T for the transition + sample, FE_DOWN for compute_loss_down's encoder + sample + decoder), one stage per call, rows keyed
@@ -230,3 +232,35 @@ def grad_decoder_convs(model_down, h4, o1, *, scale=None, return_activations=Fal
         off += t.numel()
     out = (nl, po1, d_h4, grads)
     return out + ((y1, y2, y3),) if return_activations else out
+
+
+DEC_HEAD_KEYS = tuple(f'po_net.{i}.{sfx}' for i in (0, 3, 6, 9) for sfx in ('weight', 'bias'))
+
+
+def grad_decoder(model_down, s, o1, *, scale=None, stage=None, pass_=PASS_FE_DOWN, sample=0, row_offset=None, return_activations=False):
+    """Backward of L = scale * sum_r -log p(o1_r) through the whole decoder po_net (torchmodel.py:106-128, torchloss.py:62) -> (nlogpo1 [M],
+    po1 [M,1,64,64], d_s [M,10], {state_dict key: dL / d tensor}) and, with return_activations, (h1, h2, h3, h4, y1, y2, y3): the stored
+    activations after ReLU and dropout mask (h1..h3 [M,256], h4 [M,16384] in the Unflatten's order; y1..y3 NCHW), whose sign is the
+    backward gate.  The four dropout masks are those `model_down.decoder(s, stage=, pass_=, sample=, row_offset=)` draws, so po1 agrees
+    with it to rounding.  scale None = beta_o / M, the decoder's share of F_down.mean().  The gradients are views of one flat tensor over
+    the 16 po_net.* keys in parameters() order.  1 x 64 x 64 models only."""
+    m = model_down._owner
+    if (m.colour_channels, m.resolution) != (1, 64):
+        raise ValueError(f'grad_decoder: built for 1 x 64 x 64 models, this one is {m.colour_channels} x {m.resolution} x {m.resolution}')
+    if scale is not None and not float(scale) >= 0.0:
+        raise ValueError('grad_decoder: scale must be >= 0 (None = beta_o / M)')
+    e = m._ready()
+    s = e.tensor(s, (-1, m.s_dim))
+    M = s.shape[0]
+    o1 = e.tensor(o1, (M, 1, 64, 64))
+    nz = m._noise(stage, pass_, sample, row_offset)
+    out = e.ops.dec_grad(e.h, s, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o), m._seed64(), nz.stage, pass_, sample,
+                         nz.row_offset, bool(return_activations))
+    nl, po1, d_s, flat = out[:4]
+    grads, off = {}, 0
+    for key in DEC_HEAD_KEYS + DEC_CONVT_KEYS:
+        t = model_down._sd[key]
+        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
+        off += t.numel()
+    res = (nl, po1, d_s, grads)
+    return res + (tuple(out[4:]),) if return_activations else res

@@ -371,6 +371,30 @@ int efe_train_mid(efe_ctx*, const float* s0, const float* pi0, const float* qs1_
 int efe_dec_tail_grad(efe_ctx*, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
                       float* grad, float* y1, float* y2, float* y3, void* stream);
 
+/* ---- backward of the reconstruction loss through the whole decoder (csrc/train_dec_head.hip + csrc/train_dec.hip; additive to ABI 6) ------
+ * The decoder's part of train_model_down (src/torchloss.py:90-98): po_net's dense head (Linear 10-256-256-256-16384, each with ReLU and
+ * Dropout(0.5), torchmodel.py:107-118) evaluated for training, the ConvTranspose2d tail exactly as efe_dec_tail_grad runs it, and the
+ * backward of both, at the 1 x 64 x 64 geometry.
+ *   s [M,10]       : the decoder's input
+ *   o1, scale, beta_o, nlogpo1, po1, y1..y3 : as efe_dec_tail_grad
+ *   nz             : the keys of the four dropout masks: the FORWARD decoder's masks draw for draw (tag TAG_DEC + layer, global row
+ *                    row_offset + r, stream_id(pass, sample), stage; the 16 384-feature mask keyed by the NHWC feature p 64 + c as in
+ *                    efe_decoder), so efe_decoder with the same efe_noise decodes the same network: po1 agrees to rounding, not bit for
+ *                    bit (another summation order).  The backward gate is read off the stored activation, 2 [h > 0].
+ *   d_s [M,10] = dL / ds, and the stored activations after the mask h1, h2, h3 [M,256], h4 [M,16384] (the Unflatten's input, reference
+ *   order c 256 + p): optional, NULL = not wanted
+ *   grad [P]       : dL / d parameters, P = efe_param_count("po_net") = 4 437 697, flat in parameters() order (0.weight, 0.bias, 3.weight,
+ *                    3.bias, 6.weight, 6.bias, 9.weight, 9.bias, then the tail's eight tensors exactly as efe_dec_tail_grad lays them out),
+ *                    each tensor row-major in the reference's shape (required, as is nlogpo1)
+ * A fixed-order sum that depends on M alone: twice the same bits; po1, nlogpo1, d_s, h1..h4 and y1..y3 of a row
+ * depend on that row and its global row id only.  The tail's outputs are bit-identical to efe_dec_tail_grad on the returned h4.  Scratch
+ * comes from the context's arena (rows are processed in groups of 64: the tail's scratch, plus at most 13 MB for the head and four
+ * partial gradients of 538 KB).  Returns 1 with a message that names the function for M <= 0, a NULL required pointer, a context of
+ * another geometry, or a split-operand option (mfma_bf16x3 / mfma_f16x2) being on.  There is no optimiser step for this part yet:
+ * efe_adam_step and efe_get_weights refuse the name "po_net". */
+int efe_dec_grad(efe_ctx*, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
+                 float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
