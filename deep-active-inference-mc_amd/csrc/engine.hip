@@ -1593,6 +1593,10 @@ int adam_args(efe_ctx* ctx, const TrainPart& tp, const efe_adam_params* hp, Adam
     a.bc2_sqrt = (float)std::sqrt(bc2); a.step_size = (float)(hp->lr / bc1); a.eps = (float)hp->eps;
     return 0;
 }
+// the Philox fields of a training call; row = the first row of the call's row group
+TrainKey train_key(const efe_noise* nz, uint32_t row = 0) {
+    return TrainKey{(uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), nz->row_offset + row, stream_id(nz->pass, nz->sample), nz->stage};
+}
 // the arguments of k_mid_grad after efe_loss_mid's checks (params: omega per row or scalar; nz: the keys of every dropout mask)
 // (arrays_ok: the entry point's own arrays -- the gradient, or both moments -- are non-NULL)
 int mid_grad_args(efe_ctx* ctx, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M, const efe_fe_params* params,
@@ -1609,8 +1613,22 @@ int mid_grad_args(efe_ctx* ctx, const float* s0, const float* pi0, const float* 
     a.F_mid = F_mid ? F_mid : ctx->allocT<float>((size_t)M);
     if (!a.p1_mean || !a.p1_lv || !a.F_mid) return 1;
     a.M = M; a.A = ctx->pi_dim; a.S = S_DIM; a.inv_M = 1.0f / (float)M;
-    a.k0 = (uint32_t)nz->seed; a.k1 = (uint32_t)(nz->seed >> 32); a.row_offset = nz->row_offset;
-    a.stream = stream_id(nz->pass, nz->sample); a.stage = nz->stage;
+    a.key = train_key(nz);
+    return 0;
+}
+// the tail of a gradient call (adam == nullptr) or of a training step over G partial-gradient slabs: launch(slabs) runs the backward
+// kernel; then the slabs are summed into `grad` (G == 1: the one slab IS grad), or k_adam forms the gradient by the same ascending sum
+extern "C++" template <class Launch>      // (a template inside the C ABI block)
+int grad_or_step(efe_ctx* ctx, TrainPart& tp, int G, float* grad, AdamArgs* adam, hipStream_t st, Launch launch) {
+    const int P = tp.net.P;
+    float* slabs = (!adam && G == 1) ? grad : ctx->allocT<float>((size_t)G * P);
+    if (!slabs) return 1;
+    launch(slabs);
+    if (adam) {
+        adam->g = slabs; adam->nslab = G;
+        tp.dirty = true;
+        launch_adam(*adam, P, st);
+    } else if (G > 1) launch_slab_sum(slabs, G, P, grad, st);
     return 0;
 }
 }  // namespace
@@ -1637,12 +1655,9 @@ int efe_get_weights(efe_ctx* ctx, const char* part, float* dst, int64_t n, void*
 int efe_top_grad(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, float* kl_pi, float* grad, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (!s || !log_Ppi || !grad || M < 1) return ctx->fail("efe_top_grad: bad arguments (s, log_Ppi and grad must be non-NULL, M >= 1)");
-    const TrainPart& tp = ctx->top_train;
-    const int G = train_slabs(M), P = tp.net.P;
-    float* slabs = G == 1 ? grad : ctx->allocT<float>((size_t)G * P);
-    if (!slabs) return 1;
-    launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
-    if (G > 1) launch_slab_sum(slabs, G, P, grad, st);
+    TrainPart& tp = ctx->top_train;
+    if (grad_or_step(ctx, tp, train_slabs(M), grad, nullptr, st, [&](float* slabs) {
+            launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st); })) return 1;
     return call.finish();
 }
 
@@ -1666,13 +1681,9 @@ int efe_train_top(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, flo
     TrainPart& tp = ctx->top_train;
     AdamArgs a{};
     if (adam_args(ctx, tp, hp, a, "efe_train_top")) return 1;
-    const int G = train_slabs(M), P = tp.net.P;
-    float* slabs = ctx->allocT<float>((size_t)G * P);
-    if (!slabs) return 1;
-    launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st);
-    a.g = slabs; a.nslab = G; a.m = exp_avg; a.v = exp_avg_sq;      // k_adam forms the gradient by the same ascending slab sum as k_slab_sum
-    tp.dirty = true;
-    launch_adam(a, P, st);
+    a.m = exp_avg; a.v = exp_avg_sq;
+    if (grad_or_step(ctx, tp, train_slabs(M), nullptr, &a, st, [&](float* slabs) {
+            launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st); })) return 1;
     return call.finish();
 }
 
@@ -1681,11 +1692,7 @@ int efe_mid_grad(efe_ctx* ctx, const float* s0, const float* pi0, const float* q
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     MidGradArgs g{};
     if (mid_grad_args(ctx, s0, pi0, qs1_mean, qs1_logvar, M, params, nz, ps1_mean, ps1_logvar, F_mid, grad != nullptr, g, "efe_mid_grad")) return 1;
-    const int G = train_mid_slabs(M), P = ctx->mid_train.net.P;
-    g.slabs = G == 1 ? grad : ctx->allocT<float>((size_t)G * P);
-    if (!g.slabs) return 1;
-    launch_mid_grad(g, st);
-    if (G > 1) launch_slab_sum(g.slabs, G, P, grad, st);
+    if (grad_or_step(ctx, ctx->mid_train, train_mid_slabs(M), grad, nullptr, st, [&](float* slabs) { g.slabs = slabs; launch_mid_grad(g, st); })) return 1;
     return call.finish();
 }
 
@@ -1698,92 +1705,83 @@ int efe_train_mid(efe_ctx* ctx, const float* s0, const float* pi0, const float* 
     TrainPart& tp = ctx->mid_train;
     AdamArgs a{};
     if (adam_args(ctx, tp, hp, a, "efe_train_mid")) return 1;
-    const int G = train_mid_slabs(M), P = tp.net.P;
-    g.slabs = ctx->allocT<float>((size_t)G * P);
-    if (!g.slabs) return 1;
-    launch_mid_grad(g, st);
-    a.g = g.slabs; a.nslab = G; a.m = exp_avg; a.v = exp_avg_sq;    // the same ascending slab sum as k_slab_sum
-    tp.dirty = true;
-    launch_adam(a, P, st);
+    a.m = exp_avg; a.v = exp_avg_sq;
+    if (grad_or_step(ctx, tp, train_mid_slabs(M), nullptr, &a, st, [&](float* slabs) { g.slabs = slabs; launch_mid_grad(g, st); })) return 1;
     return call.finish();
 }
 
-// ---- backward of the reconstruction loss through the decoder's ConvTranspose2d tail (train_dec.hip) ----
-int efe_dec_tail_grad(efe_ctx* ctx, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
-                      float* grad, float* y1, float* y2, float* y3, void* stream) {
-    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    if (M <= 0) return ctx->fail("efe_dec_tail_grad: M must be >= 1");
-    if (!h4 || !o1 || !nlogpo1 || !grad) return ctx->fail("efe_dec_tail_grad: h4, o1, nlogpo1 and grad must be non-NULL");
-    if (ctx->chan != 1 || ctx->res != 64 || !ctx->dect_raw) return ctx->fail("efe_dec_tail_grad: built for the 1 x 64 x 64 geometry only");
-    if (ctx->mfma_bf16x3) return ctx->fail("efe_dec_tail_grad: not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+// ---- backward of the reconstruction loss through the decoder: ConvT tail (train_dec.hip), optionally behind the dense head (train_dec_head.hip) ----
+namespace {
+// the dense head's side of the call: its input, the keys of its four dropout masks, its outputs (all nullable but s and nz)
+struct DecHeadIO { const float* s; const efe_noise* nz; float* d_s; float *h1, *h2, *h3, *h4; };
+
+// hd == nullptr: the tail alone, from the caller's h4 to the caller's d_h4 (nullable), grad [DEC_TAIL_P]; else grad [DEC_P] and h4 / d_h4 unused
+int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4, float* d_h4, const float* o1, int M, float scale, float beta_o,
+             float* nlogpo1, float* po1, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
+    const std::string w(who);
+    if (M <= 0) return ctx->fail(w + ": M must be >= 1");
+    if (!(hd ? hd->s && hd->nz : h4 != nullptr) || !o1 || !nlogpo1 || !grad)
+        return ctx->fail(w + (hd ? ": s, o1, nz, nlogpo1 and grad must be non-NULL" : ": h4, o1, nlogpo1 and grad must be non-NULL"));
+    if (ctx->chan != 1 || ctx->res != 64 || !(hd ? ctx->dec_raw : ctx->dect_raw)) return ctx->fail(w + ": built for the 1 x 64 x 64 geometry only");
+    if (ctx->mfma_bf16x3) return ctx->fail(w + ": not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
     if (!(scale >= 0.0f)) {
-        if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail("efe_dec_tail_grad: scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
+        if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail(w + ": scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
         scale = beta_o / (float)M;
     }
     const DecTailPlan p = dec_tail_plan(M, !y1, !y2, !y3, !po1);
     float* s1 = ctx->allocT<float>(p.y1); float* s2 = ctx->allocT<float>(p.y2); float* s3 = ctx->allocT<float>(p.y3); float* sp = ctx->allocT<float>(p.po);
     float* g4 = ctx->allocT<float>(p.g4); float* g3 = ctx->allocT<float>(p.g3); float* g2 = ctx->allocT<float>(p.g2); float* g1 = ctx->allocT<float>(p.g1);
-    float* slabs = p.G > 1 ? ctx->allocT<float>(p.slabs) : grad;
-    if (!s1 || !s2 || !s3 || !sp || !g4 || !g3 || !g2 || !g1 || !slabs) return 1;
-    for (int m0 = 0; m0 < M; m0 += p.C) {       // row groups: boundaries at multiples of DEC_TAIL_ROWS, a function of M alone
-        DecTailArgs a{};
-        a.w = ctx->dect_raw; a.h4 = h4 + (size_t)m0 * DEC_TAIL_Y1; a.o1 = o1 + (size_t)m0 * 4096;
-        a.y1 = y1 ? y1 + (size_t)m0 * DEC_TAIL_Y1 : s1; a.y2 = y2 ? y2 + (size_t)m0 * DEC_TAIL_Y2 : s2; a.y3 = y3 ? y3 + (size_t)m0 * DEC_TAIL_Y3 : s3;
-        a.po = po1 ? po1 + (size_t)m0 * 4096 : sp; a.nlogpo1 = nlogpo1 + m0;
-        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = d_h4 ? d_h4 + (size_t)m0 * DEC_TAIL_Y1 : nullptr;
-        a.slabs = slabs; a.rows = std::min(p.C, M - m0); a.G = p.G; a.first = m0 == 0; a.scale = scale;
-        launch_dec_tail_group(a, st);
-    }
-    if (p.G > 1) launch_slab_sum(slabs, p.G, DEC_TAIL_P, grad, st);
-    ctx->last_macs += (int64_t)M * 3 * 38928384;      // forward, data gradient, weight gradient of the four layers
-    return call.finish();
-}
-
-// ---- backward of the reconstruction loss through the whole decoder: dense head (train_dec_head.hip) + ConvT tail (train_dec.hip) ----
-int efe_dec_grad(efe_ctx* ctx, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
-                 float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream) {
-    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    if (M <= 0) return ctx->fail("efe_dec_grad: M must be >= 1");
-    if (!s || !o1 || !nz || !nlogpo1 || !grad) return ctx->fail("efe_dec_grad: s, o1, nz, nlogpo1 and grad must be non-NULL");
-    if (ctx->chan != 1 || ctx->res != 64 || !ctx->dec_raw) return ctx->fail("efe_dec_grad: built for the 1 x 64 x 64 geometry only");
-    if (ctx->mfma_bf16x3) return ctx->fail("efe_dec_grad: not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
-    if (!(scale >= 0.0f)) {
-        if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail("efe_dec_grad: scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
-        scale = beta_o / (float)M;
-    }
-    const DecTailPlan p = dec_tail_plan(M, !y1, !y2, !y3, !po1);
-    const DecHeadPlan hp = dec_head_plan(M, !h1, !h2, !h3, !h4);
-    float* s1 = ctx->allocT<float>(p.y1); float* s2 = ctx->allocT<float>(p.y2); float* s3 = ctx->allocT<float>(p.y3); float* sp = ctx->allocT<float>(p.po);
-    float* g4 = ctx->allocT<float>(p.g4); float* g3 = ctx->allocT<float>(p.g3); float* g2 = ctx->allocT<float>(p.g2); float* g1 = ctx->allocT<float>(p.g1);
-    float* tgrad = grad + DEC_HEAD_P;           // the tail's gradient, laid out as efe_dec_tail_grad's
+    float* tgrad = hd ? grad + DEC_HEAD_P : grad;           // the tail's gradient
     float* tslabs = p.G > 1 ? ctx->allocT<float>(p.slabs) : tgrad;
-    float* a1 = ctx->allocT<float>(hp.h1); float* a2 = ctx->allocT<float>(hp.h2); float* a3 = ctx->allocT<float>(hp.h3); float* a4 = ctx->allocT<float>(hp.h4);
-    float* dh4 = ctx->allocT<float>(hp.dh4); float* part = ctx->allocT<float>(hp.part);
-    float* hslabs = hp.G > 1 ? ctx->allocT<float>(hp.slabs) : grad;
-    if (!s1 || !s2 || !s3 || !sp || !g4 || !g3 || !g2 || !g1 || !tslabs || !a1 || !a2 || !a3 || !a4 || !dh4 || !part || !hslabs) return 1;
+    if (!s1 || !s2 || !s3 || !sp || !g4 || !g3 || !g2 || !g1 || !tslabs) return 1;
+    DecHeadPlan hp{};
+    float *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr, *dh4 = nullptr, *part = nullptr, *hslabs = nullptr;
+    if (hd) {
+        hp = dec_head_plan(M, !hd->h1, !hd->h2, !hd->h3, !hd->h4);
+        a1 = ctx->allocT<float>(hp.h1); a2 = ctx->allocT<float>(hp.h2); a3 = ctx->allocT<float>(hp.h3); a4 = ctx->allocT<float>(hp.h4);
+        dh4 = ctx->allocT<float>(hp.dh4); part = ctx->allocT<float>(hp.part);
+        hslabs = hp.G > 1 ? ctx->allocT<float>(hp.slabs) : grad;
+        if (!a1 || !a2 || !a3 || !a4 || !dh4 || !part || !hslabs) return 1;
+    }
     for (int m0 = 0; m0 < M; m0 += p.C) {       // row groups: boundaries at multiples of DEC_TAIL_ROWS, a function of M alone
         const int rows = std::min(p.C, M - m0);
         DecHeadArgs h{};
-        h.w = ctx->dec_raw; h.s = s + (size_t)m0 * S_DIM;
-        h.h1 = h1 ? h1 + (size_t)m0 * 256 : a1; h.h2 = h2 ? h2 + (size_t)m0 * 256 : a2; h.h3 = h3 ? h3 + (size_t)m0 * 256 : a3;
-        h.h4 = h4 ? h4 + (size_t)m0 * DEC_TAIL_Y1 : a4;
-        h.g4 = dh4; h.part = part; h.ds = d_s ? d_s + (size_t)m0 * S_DIM : nullptr; h.grad = grad; h.slabs = hslabs;
-        h.rows = rows; h.first = m0 == 0;
-        h.k0 = (uint32_t)nz->seed; h.k1 = (uint32_t)(nz->seed >> 32); h.row0 = nz->row_offset + (uint32_t)m0;
-        h.stream = stream_id(nz->pass, nz->sample); h.stage = nz->stage;
-        launch_dec_head_fwd(h, st);
+        if (hd) {
+            h.w = ctx->dec_raw; h.s = hd->s + (size_t)m0 * S_DIM;
+            h.h1 = hd->h1 ? hd->h1 + (size_t)m0 * 256 : a1; h.h2 = hd->h2 ? hd->h2 + (size_t)m0 * 256 : a2; h.h3 = hd->h3 ? hd->h3 + (size_t)m0 * 256 : a3;
+            h.h4 = hd->h4 ? hd->h4 + (size_t)m0 * DEC_TAIL_Y1 : a4;
+            h.g4 = dh4; h.part = part; h.ds = hd->d_s ? hd->d_s + (size_t)m0 * S_DIM : nullptr; h.grad = grad; h.slabs = hslabs;
+            h.rows = rows; h.first = m0 == 0; h.key = train_key(hd->nz, (uint32_t)m0);
+            launch_dec_head_fwd(h, st);
+        }
         DecTailArgs a{};
-        a.w = ctx->dect_raw; a.h4 = h.h4; a.o1 = o1 + (size_t)m0 * 4096;
+        a.w = ctx->dect_raw; a.h4 = hd ? h.h4 : h4 + (size_t)m0 * DEC_TAIL_Y1; a.o1 = o1 + (size_t)m0 * 4096;
         a.y1 = y1 ? y1 + (size_t)m0 * DEC_TAIL_Y1 : s1; a.y2 = y2 ? y2 + (size_t)m0 * DEC_TAIL_Y2 : s2; a.y3 = y3 ? y3 + (size_t)m0 * DEC_TAIL_Y3 : s3;
         a.po = po1 ? po1 + (size_t)m0 * 4096 : sp; a.nlogpo1 = nlogpo1 + m0;
-        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = dh4;
+        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = hd ? dh4 : d_h4 ? d_h4 + (size_t)m0 * DEC_TAIL_Y1 : nullptr;
         a.slabs = tslabs; a.rows = rows; a.G = p.G; a.first = m0 == 0; a.scale = scale;
         launch_dec_tail_group(a, st);
-        launch_dec_head_bwd(h, st);
+        if (hd) launch_dec_head_bwd(h, st);
     }
     if (p.G > 1) launch_slab_sum(tslabs, p.G, DEC_TAIL_P, tgrad, st);
-    if (hp.G > 1) launch_slab_sum(hslabs, hp.G, DEC_HEAD_SMALL_P, grad, st);
-    ctx->last_macs += (int64_t)M * 3 * (38928384 + 4328960);      // forward, data gradient, weight gradient of the eight layers
+    if (hd && hp.G > 1) launch_slab_sum(hslabs, hp.G, DEC_HEAD_SMALL_P, grad, st);
+    ctx->last_macs += (int64_t)M * 3 * (38928384 + (hd ? 4328960 : 0));      // forward, data gradient, weight gradient of the four (eight) layers
+    return 0;
+}
+}  // namespace
+
+int efe_dec_tail_grad(efe_ctx* ctx, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
+                      float* grad, float* y1, float* y2, float* y3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (dec_grad(ctx, "efe_dec_tail_grad", nullptr, h4, d_h4, o1, M, scale, beta_o, nlogpo1, po1, grad, y1, y2, y3, st)) return 1;
+    return call.finish();
+}
+
+int efe_dec_grad(efe_ctx* ctx, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
+                 float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    const DecHeadIO hd{s, nz, d_s, h1, h2, h3, h4};
+    if (dec_grad(ctx, "efe_dec_grad", &hd, nullptr, nullptr, o1, M, scale, beta_o, nlogpo1, po1, grad, y1, y2, y3, st)) return 1;
     return call.finish();
 }
 

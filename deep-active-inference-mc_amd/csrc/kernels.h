@@ -399,6 +399,7 @@ struct TrainLayer {
 };
 struct TrainNet { int nl, P; float* master; TrainLayer L[TRAIN_MAX_LAYERS]; };
 __host__ __device__ inline int train_slabs(int M) { const int t = (M + 15) / 16; return t < TRAIN_MAX_SLABS ? t : TRAIN_MAX_SLABS; }
+struct TrainKey { uint32_t k0, k1, row0, stream, stage; };     // Philox fields of a training call: key, global row of row 0, stream_id(pass, sample), stage
 struct TopGradArgs {
     const TrainNet* net;                 // device pointer
     const float* s; const float* log_Ppi;       // [M][in of layer 0], [M][A]
@@ -433,7 +434,7 @@ struct MidGradArgs {
     float* slabs;                        // [train_mid_slabs(M)][P]
     int M, A, S;
     float inv_M;
-    uint32_t k0, k1, row_offset, stream, stage;  // Philox key, global row of row 0, stream_id(pass, sample), stage
+    TrainKey key;
 };
 void launch_mid_grad(const MidGradArgs& a, hipStream_t st);
 int init_train_kernels();
@@ -479,7 +480,7 @@ struct DecHeadArgs {                     // one row group (at most DEC_TAIL_ROWS
     float* grad;                         // the caller's gradient [DEC_P]: 9.weight / 9.bias are written (first) or added to in place
     float* slabs;                        // [G][DEC_HEAD_SMALL_P]; first != 0: written, else added to
     int rows, first;
-    uint32_t k0, k1, row0, stream, stage;        // Philox key, global row of the group's row 0, stream_id(pass, sample), stage
+    TrainKey key;                        // row0 = the global row of the group's row 0
 };
 void launch_dec_head_fwd(const DecHeadArgs& a, hipStream_t st);       // s -> h1 .. h4
 void launch_dec_head_bwd(const DecHeadArgs& a, hipStream_t st);       // d_h4 -> the head's gradients and d_s

@@ -2,40 +2,36 @@
 // (/root/reference/src/torchloss.py:65-74): one Adam step on F_top.mean(), F_top = sum_a Qpi (log(Qpi + 1e-20) - log_Ppi).
 //
 //   k_top_grad : forward + loss gradient + backward in ONE launch.  A workgroup (4 waves) takes 16-row tiles; the activations of every
-//                layer stay in LDS.  Every contraction is v_mfma_f32_16x16x4_f32 (exact fp32 fma chains); the operands are gathered
-//                from LDS and from the fp32 master copy of the weights (reference layout), so the transposed products of the backward
-//                pass need no second packed form.
+//                layer stay in LDS.  The operands are gathered from LDS and from the fp32 master copy of the weights (reference layout),
+//                so the transposed products of the backward pass need no second packed form.
 //                    forward   h_{l+1}[r][f] = act(sum_k W_l[f][k] h_l[r][k] + b_l[f])         K = layer input
 //                    loss      per row: softmax, log(q + 1e-20), kl_pi, dlogit_j = (1/M) Q_j (g_j - sum_a Q_a g_a),
 //                              g_a = (logQ_a - logP_a) + Q_a / (Q_a + 1e-20)                    fp32, contraction off
 //                    backward  dW_l[o][i] = sum_r d_l[r][o] h_l[r][i],  db_l[o] = sum_r d_l[r][o]   K = the 16 rows of the tile
 //                              d_{l-1}[r][i] = (sum_o d_l[r][o] W_l[o][i]) * [h_l[r][i] > 0]         K = layer output
-//                Rows >= M of the last tile have dlogit = 0 and inputs 0: they contribute exactly zero.
 //                The kernel walks a layer table (kernels.h TrainNet: widths, ReLU flag, dropout tag slot), not the habit net's sizes.
 //   k_slab_sum : gradient = the fixed ascending sum of the workgroups' partial gradients (no float atomics).
 //   k_adam     : one thread per parameter, torch.optim.Adam's default arithmetic; the new value goes to the fp32 master copy and to
 //                both packed forward copies (32x32x2 layer-wise form, 16x16x4 fused form) through closed-form index maps.
 //
-// Reduction-order contract (a function of M alone): T = ceil(M / 16) tiles, G = min(T, 64) workgroups.  Workgroup p walks tiles
-// p, p + G, p + 2G, ... in ascending order; a tile's contribution to an element is one MFMA chain over its rows 0..15 in ascending
-// order (bias: a sequential sum), added to the workgroup's slab element by the one thread that owns it; the gradient is
-// ((slab_0 + slab_1) + slab_2) + ... in ascending p.  Two identical calls give identical bits.
-//
 // Training of the transition network ModelMid.ps_net (torchmodel.py:41-52) by train_model_mid (torchloss.py:76-88): one Adam step on
 // F_mid.mean(), F_mid = sum_k kl(q(s1) | p(s1 | s0, pi)) with precision omega (torchutils.py:7-8):
 //     kl = 0.5 (lv2 - log w - lv1) + (exp(lv1) + (mu1 - mu2)^2) / den - 0.5,   den = 2 exp(lv2) / w
 //     d/dmu2 = -(1/M) 2 (mu1 - mu2) / den,   d/dlv2 = (1/M) (0.5 - (exp(lv1) + (mu1 - mu2)^2) / den)          fp32, contraction off
-//   k_mid_grad : k_top_grad's structure for 512-wide hidden layers with MC-dropout (LDS map, chain scheme and its own reduction-order
-//                contract, G = min(T, 8): at the kernel).  k_slab_sum and k_adam serve both nets through their layer tables.
-#include "kernels.h"
+//   k_mid_grad : the same passes for 512-wide hidden layers with MC-dropout.  k_slab_sum and k_adam serve both nets through their tables.
+//
+// The chain, tile, slab and gate rules are train_mlp.h's order contract.  Slabs: T = ceil(M / 16) tiles, G = min(T, 64) workgroups for
+// k_top_grad, min(T, TRAIN_MID_SLABS = 8) for k_mid_grad; workgroup p owns slab p and walks tiles p, p + G, p + 2G, ... ascending.
+// Both kernels keep bodies of their own, the ones they had before train_mlp.h: on its passes each measured slower than its own spread
+// allows, and as written here each compiles to the listing it had.
+#include "train_mlp.h"
 
 namespace efe {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace mlp;
 
 namespace {
 
-constexpr int TR = 16;                          // rows per tile
 constexpr int TLD = TRAIN_MAX_WIDTH + 4;        // LDS row stride in floats
 
 __device__ __forceinline__ float slab_sum(const float* g, int nslab, int P, int i) {
@@ -47,6 +43,8 @@ __device__ __forceinline__ float slab_sum(const float* g, int nslab, int P, int 
 
 }  // namespace
 
+// k_top_grad: act[l] plus a ping-pong dl in LDS; dW tiles dealt to the four waves one by one (on train_mlp.h's dw_pass, where a wave owns 16
+// outputs, it was 5 % slower at M = 4096).  Per element its dW / db chains are train_mlp.h's tile rule.
 __global__ void __launch_bounds__(256) k_top_grad(const TopGradArgs a) {
 #pragma clang fp contract(off)
     __shared__ float act[TRAIN_MAX_LAYERS][TR][TLD];      // act[l] = input of layer l
@@ -214,21 +212,16 @@ __global__ void __launch_bounds__(256) k_top_grad(const TopGradArgs a) {
 // ReLU + Dropout(0.5) with 512-wide Linears between, Linear(512, 20) = ps1_mean | ps1_logvar; loss = mean_r sum_k kl (header).
 //
 // LDS (dynamic, MID_LDS_BYTES = 102 656): X0 [16][20] the input tile | H1, H2, H3 [16][516] the post-mask activations (H_l = input of
-// layer l) | DO [16][36] the output tile (logits, then their gradient).  d_{l-1} OVERWRITES H_l in place once dW_l has consumed it: lane
-// (n, q) gates and writes the four elements it reads, and d_l itself sits in H_{l+1} (DO for the last layer).  One workgroup per CU.
+// layer l) | DO [16][36] the output tile (logits, then their gradient).  d_l sits in H_{l+1} (DO for the last layer).  One workgroup per CU.
 //
 // Dropout: the forward pass draws the keep mask of hidden layer li as k_trans_fused does (tag TAG_MID + li = TrainLayer::drop_tag, block
-// f >> 7, the call's row / stream / stage) and stores relu(a) * mask (kept value x 2).  The backward gate mask * [a > 0] is READ OFF the
-// stored activation, 2 * [h > 0]: no second Philox evaluation, and the two passes cannot key a mask differently.
+// f >> 7, the call's row / stream / stage) and stores relu(a) * mask (kept value x 2).
 //
-// Chains: a contraction over a layer's width (K up to 512) runs on SIXTEEN accumulators: 16-channel chunk c goes to accumulator c & 15
-// (four MFMAs = 16 terms per visit, 32 terms per accumulator at K = 512), combined by the fixed tree of tree16().  The forward pass reads
-// the packed 16x16x4 copy (one coalesced float4 per lane and chunk; MFMA step s contracts channels 16 c + 4 q + s), the transposed
-// product gathers W[o][i] from the master copy with the same chunk / step order over o.  dW is one 16-term chain over the tile's rows.
-// The forward order is not k_trans_fused's single chain: ps1_mean / ps1_logvar agree with efe_loss_mid to rounding, not bit for bit.
-//
-// Reduction-order contract (a function of M alone): T = ceil(M / 16) tiles, G = min(T, TRAIN_MID_SLABS = 8) workgroups, workgroup p walks
-// tiles p, p + G, ... ascending and adds each tile's chain to its slab element; gradient = ((slab_0 + slab_1) + slab_2) + ... ascending.
+// Chains: train_mlp.h's chain rule with SIXTEEN accumulators (32 terms per accumulator at K = 512), joined by tree16() = tree<16> of that
+// header, written out here (with the header's tree<16>, mask_block or contract in its place the kernel compiles to another listing, and
+// on contract / dprev_pass it measured 7.130 -> 7.165 ms at M = 1024 against a spread of 0.010 ms).  The forward pass reads the packed 16x16x4 copy
+// (one coalesced float4 per lane and chunk), the transposed product gathers W[o][i] from the master copy; dW is one 16-term chain per tile.  The forward order is not
+// k_trans_fused's single chain: ps1_mean / ps1_logvar agree with efe_loss_mid to rounding, not bit for bit.
 namespace {
 
 constexpr int MLD = TRAIN_MID_WIDTH + 4;          // row stride of H1..H3 (516 floats: rows 16-byte aligned, 16 rows on 64 distinct banks)
@@ -242,12 +235,6 @@ __device__ __forceinline__ f32x4 tree16(const f32x4 (&a)[16]) {
     const f32x4 b2 = (a[8] + a[9]) + (a[10] + a[11]), b3 = (a[12] + a[13]) + (a[14] + a[15]);
     return (b0 + b1) + (b2 + b3);
 }
-
-#define MFMA4(ACC, A0, A1, A2, A3, BV)                                     \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A0, (BV).x, ACC, 0, 0, 0);   \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A1, (BV).y, ACC, 0, 0, 0);   \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A2, (BV).z, ACC, 0, 0, 0);   \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A3, (BV).w, ACC, 0, 0, 0);
 
 }  // namespace
 
@@ -305,18 +292,16 @@ __global__ void __launch_bounds__(256, 1) k_mid_grad(const MidGradArgs a) {
                         if (c < KC) {
                             const float4 av = Wp[(size_t)c * 64];                                     // A(i = feature, k): W[f0 + n][16 c + 4 q + s]
                             const float4 bv = *reinterpret_cast<const float4*>(x + 16 * c);            // B(k, j = row):     x[n][16 c + 4 q + s]
-                            MFMA4(acc[j], av.x, av.y, av.z, av.w, bv)
+                            mfma4(acc[j], av.x, av.y, av.z, av.w, bv);
                         }
                     }
                 }
                 const f32x4 sum = tree16(acc);
                 uint32_t word = 0xFFFFFFFFu;
                 if (tag) {
-                    // the key words pass through vector registers HERE: as loop invariants their ten Philox round keys are hoisted into twenty
-                    // scalar registers for the whole kernel, which then spills scalars
-                    uint32_t k0 = a.k0, k1 = a.k1;
+                    uint32_t k0 = a.key.k0, k1 = a.key.k1;
                     asm volatile("" : "+v"(k0), "+v"(k1));
-                    const uint4 rnd = noise_words(k0, k1, tag, (uint32_t)(f0 >> 7), a.row_offset + (uint32_t)(r0 + n), a.stream, a.stage);
+                    const uint4 rnd = noise_words(k0, k1, tag, (uint32_t)(f0 >> 7), a.key.row0 + (uint32_t)(r0 + n), a.key.stream, a.key.stage);
                     const int wsel = (f0 >> 5) & 3;
                     word = wsel == 0 ? rnd.x : wsel == 1 ? rnd.y : wsel == 2 ? rnd.z : rnd.w;
                 }
@@ -430,7 +415,7 @@ __global__ void __launch_bounds__(256, 1) k_mid_grad(const MidGradArgs a) {
                                 float av[4];                                                           // A(i = input feature, k = o): W[o][i0 + n]; beyond O the
 #pragma unroll                                                                                                 // row index is clamped: d is zero there, the product exactly 0
                                 for (int s = 0; s < 4; ++s) av[s] = Wc[(size_t)min(o + s, O - 1) * K];
-                                MFMA4(acc[j], av[0], av[1], av[2], av[3], bv)
+                                mfma4(acc[j], av[0], av[1], av[2], av[3], bv);
                             }
                         }
                     }
@@ -449,7 +434,6 @@ __global__ void __launch_bounds__(256, 1) k_mid_grad(const MidGradArgs a) {
         }
     }
 }
-#undef MFMA4
 
 __global__ void __launch_bounds__(256) k_slab_sum(const float* slabs, int nslab, int P, float* grad) {
     const int i = blockIdx.x * 256 + threadIdx.x;

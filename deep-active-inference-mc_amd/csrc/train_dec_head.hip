@@ -8,8 +8,7 @@
 //
 // Dropout: the keep mask of layer li is the forward decoder's (k_head / k_fc4), draw for draw: tag TAG_DEC + li, block f >> 7, word
 // (f >> 5) & 3, bit f & 31, the call's row / stream / stage.  Layer 3's mask is indexed by the engine's NHWC feature f' = p 64 + c of the
-// reference feature c 256 + p (k_fc4 emits NHWC).  The backward gate keep * [a > 0] is READ OFF the stored activation, 2 [x > 0] (DESIGN
-// 7c): no second Philox evaluation.
+// reference feature c 256 + p (k_fc4 emits NHWC).
 //
 // Kernels (one row group of at most DEC_TAIL_ROWS = 64 rows per launch):
 //   k_dech_fwd   : layers 0..2, one workgroup per 16-row tile, activations in LDS and stored to h1..h3.
@@ -20,45 +19,30 @@
 //   k_dech_small : joins the partials (+ gate) and runs layers 2, 1, 0 backward over one 16-row tile in LDS; slab = tile of the group.
 //   k_slab_sum (train.hip) : gradient of layers 0..2 = ascending sum of the slabs.
 //
-// Chains (every contraction is v_mfma_f32_16x16x4_f32, contraction off in the VALU epilogues): a contraction over K = 256 features runs
-// on EIGHT accumulators: 16-feature chunk c goes to accumulator c & 7 (four MFMAs = 16 terms per visit, MFMA step s contracts features
-// 16 c + 4 q + s; 32 terms per accumulator), joined by tree8(): ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)).  Layer 0 (K = 10) is
-// one chunk.  The forward order is not k_head's or k_fc4's: po1 agrees with efe_decoder to rounding, not bit for bit.
+// Chains: train_mlp.h's with EIGHT accumulators over K = 256 features (32 terms per accumulator), tree<8> = ((a0 + a1) + (a2 + a3)) +
+// ((a4 + a5) + (a6 + a7)).  Layer 0 (K = 10) is one chunk.  The forward order is not k_head's or k_fc4's: po1 agrees with efe_decoder to
+// rounding, not bit for bit.
 //
-// Reduction-order contract of the head's gradient (a function of M alone; no float atomics; every element has ONE owning thread):
+// Reduction order of the head's gradient, on top of train_mlp.h's tile, slab and gate rules (every element has ONE owning thread):
 //   rows     : row group g = rows 64 g .. 64 g + 63, 16-row tile t = rows 16 t .. 16 t + 15; rows >= M contribute exact zeros.
 //   dW_3/db_3: per element and group, the tiles ascending: chunk = one 16-term MFMA chain over the tile's rows (db: a sequential sum),
 //              group = ((chunk_0 + chunk_1) + chunk_2) + chunk_3; gradient = ((group_0 + group_1) + ...) ascending, in place.
-//   d_h3     : per row (no cross-row term): segment = tree8 of eight 32-term chains; the 64 segments joined as tree8 of eight sequential
+//   d_h3     : per row (no cross-row term): segment = tree<8> of eight 32-term chains; the 64 segments joined as tree<8> of eight sequential
 //              sums of eight consecutive segments.
 //   layers 0..2: G = min(ceil(M / 16), DEC_HEAD_SLABS = 4) slabs of 134 400 floats; tile t adds its 16-term chain (db: sequential sum) to
 //              slab t mod 4, tiles ascending; gradient = ((slab_0 + slab_1) + slab_2) + slab_3.
 // Two identical calls give identical bits; h1..h4, d_s (and through the tail po1, nlogpo1) of a row depend on that row and its global
 // row id only.
-#include "kernels.h"
+#include "train_mlp.h"
 
 namespace efe {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace mlp;
 
 namespace {
 
-constexpr int TR = 16;             // rows per tile
 constexpr int HLD = 256 + 4;       // LDS row stride of a 256-wide activation
 constexpr int SLD = 16 + 4;        // ... of the input tile s (10 columns, zero up to 16)
-
-__device__ __forceinline__ f32x4 tree8(const f32x4 (&a)[8]) {
-#pragma clang fp contract(off)
-    return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-}
-
-#define MFMA4(ACC, A0, A1, A2, A3, BV)                                     \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A0, (BV).x, ACC, 0, 0, 0);   \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A1, (BV).y, ACC, 0, 0, 0);   \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A2, (BV).z, ACC, 0, 0, 0);   \
-    ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(A3, (BV).w, ACC, 0, 0, 0);
-
-__device__ __forceinline__ uint32_t pick(const uint4& r, int w) { return w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w; }
 
 }  // namespace
 
@@ -77,46 +61,29 @@ __global__ void __launch_bounds__(256) k_dech_fwd(const DecHeadArgs a) {
     __syncthreads();
 #pragma unroll 1
     for (int l = 0; l < 3; ++l) {
-        const float* W = a.w + (l == 0 ? DH_W0 : l == 1 ? DH_W1 : DH_W2);
-        const float* B = a.w + (l == 0 ? DH_B0 : l == 1 ? DH_B1 : DH_B2);
+        const gfloat* W = (const gfloat*)a.w + (l == 0 ? DH_W0 : l == 1 ? DH_W1 : DH_W2);
+        const gfloat* B = (const gfloat*)a.w + (l == 0 ? DH_B0 : l == 1 ? DH_B1 : DH_B2);
         float* hl = l == 0 ? a.h1 : l == 1 ? a.h2 : a.h3;
         const float* x = (l == 0 ? X0 + n * SLD : H + (l - 1) * TR * HLD + n * HLD) + 4 * q;
         float* y = H + l * TR * HLD + n * HLD;
 #pragma unroll 1
         for (int t = 4 * w; t < 4 * w + 4; ++t) {
             const int f0 = 16 * t;
-            f32x4 acc[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] = (f32x4)(0.f);
+            const auto ldb = [&](int c) { return *reinterpret_cast<const float4*>(x + 16 * c); };     // B(k, j = row): x[n][16 c + 4 q + s]
+            f32x4 sum;
             if (l == 0) {                     // K = 10: one chunk, zero beyond the layer's width
-                const float4 bv = *reinterpret_cast<const float4*>(x);                                  // B(k, j = row): x[n][4 q + s]
-                float av[4];                                                                            // A(i = feature, k): W[f0 + n][4 q + s]
+                sum = contract<8, 1>([&](int) {                                                     // A(i = feature, k): W[f0 + n][4 q + s]
+                    float av[4];
 #pragma unroll
-                for (int s = 0; s < 4; ++s) av[s] = 4 * q + s < 10 ? W[(size_t)(f0 + n) * 10 + 4 * q + s] : 0.0f;
-                MFMA4(acc[0], av[0], av[1], av[2], av[3], bv)
+                    for (int s = 0; s < 4; ++s) av[s] = 4 * q + s < 10 ? W[(size_t)(f0 + n) * 10 + 4 * q + s] : 0.0f;
+                    return make_float4(av[0], av[1], av[2], av[3]);
+                }, ldb);
             } else {
-                const float4* Wp = reinterpret_cast<const float4*>(W + (size_t)(f0 + n) * 256 + 4 * q);
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const float4 av = Wp[4 * c];                                                        // W[f0 + n][16 c + 4 q + s]
-                    const float4 bv = *reinterpret_cast<const float4*>(x + 16 * c);
-                    MFMA4(acc[c & 7], av.x, av.y, av.z, av.w, bv)
-                }
+                const float4* Wp = reinterpret_cast<const float4*>((const float*)W + (size_t)(f0 + n) * 256 + 4 * q);
+                sum = contract<8, 16>([&](int c) { return Wp[4 * c]; }, ldb);                       // W[f0 + n][16 c + 4 q + s]
             }
-            const f32x4 sum = tree8(acc);
-            // (the key words pass through vector registers: as loop invariants their Philox round keys are hoisted into scalar registers)
-            uint32_t k0 = a.k0, k1 = a.k1;
-            asm volatile("" : "+v"(k0), "+v"(k1));
-            const uint4 rnd = noise_words(k0, k1, TAG_DEC + (uint32_t)l, (uint32_t)(f0 >> 7), a.row0 + (uint32_t)row, a.stream, a.stage);
-            const uint32_t word = pick(rnd, (f0 >> 5) & 3);
-            float4 out;
-            float* o4 = &out.x;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int f = f0 + 4 * q + e;                                                           // D(i = 4 q + e, j = n)
-                const float v = fmaxf(sum[e] + B[f], 0.0f);
-                o4[e] = ((word >> (f & 31)) & 1u) ? v * 2.0f : 0.0f;
-            }
+            const uint32_t word = mask_word(mask_block(a.key, TAG_DEC + (uint32_t)l, (uint32_t)(f0 >> 7), (uint32_t)row), f0);
+            const float4 out = fwd_epilogue(sum, B, f0, q, 256, true, true, word);                      // D(i = 4 q + e, j = n)
             *reinterpret_cast<float4*>(y + f0 + 4 * q) = out;
             if (row < a.rows) *reinterpret_cast<float4*>(hl + (size_t)row * 256 + f0 + 4 * q) = out;
         }
@@ -144,29 +111,18 @@ __global__ void __launch_bounds__(256) k_dech_fc4(const DecHeadArgs a) {
         const int row = r0 + n;
         const bool ok = row < a.rows;
         const float* xp = a.h3 + (size_t)(ok ? row : 0) * 256 + 4 * q;
-        f32x4 acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = (f32x4)(0.f);
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        const f32x4 sum = contract<8, 16>([&](int c) { return av[c]; }, [&](int c) {
             float4 bv = *reinterpret_cast<const float4*>(xp + 16 * c);                                  // B(k, j = row): h3[row][16 c + 4 q + s]
             if (!ok) bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            MFMA4(acc[c & 7], av[c].x, av[c].y, av[c].z, av[c].w, bv)
-        }
-        const f32x4 sum = tree8(acc);
-        uint32_t k0 = a.k0, k1 = a.k1;
-        asm volatile("" : "+v"(k0), "+v"(k1));
-        const uint4 ra = noise_words(k0, k1, TAG_DEC + 3u, pb, a.row0 + (uint32_t)row, a.stream, a.stage);
-        const uint4 rb = noise_words(k0, k1, TAG_DEC + 3u, pb + 1u, a.row0 + (uint32_t)row, a.stream, a.stage);
+            return bv;
+        });
+        const uint4 ra = mask_block(a.key, TAG_DEC + 3u, pb, (uint32_t)row), rb = mask_block(a.key, TAG_DEC + 3u, pb + 1u, (uint32_t)row);
         const uint32_t keep[4] = {pick(ra, wc), pick(ra, wc + 2), pick(rb, wc), pick(rb, wc + 2)};
         const float b4[4] = {bias.x, bias.y, bias.z, bias.w};
         float4 out;
         float* o4 = &out.x;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float v = fmaxf(sum[e] + b4[e], 0.0f);
-            o4[e] = ((keep[e] >> bit) & 1u) ? v * 2.0f : 0.0f;
-        }
+        for (int e = 0; e < 4; ++e) o4[e] = relu_drop(sum[e] + b4[e], true, true, keep[e], bit);
         if (ok) *reinterpret_cast<float4*>(a.h4 + (size_t)row * 16384 + f0 + 4 * q) = out;
     }
 }
@@ -246,33 +202,25 @@ __global__ void __launch_bounds__(256) k_dech_dh3(const DecHeadArgs a) {
     const int k0 = 16 * __builtin_amdgcn_readfirstlane((int)(blockIdx.x & 3) * 4 + (int)(threadIdx.x >> 6));
     const int fs = seg * 256;
     const float* Wc = a.w + DH_W3 + (size_t)(fs + 4 * q) * 256 + k0 + n;
-    float av[16][4];                                                                                    // A(i = input, k = feature): W3[fs + 16 c + 4 q + s][k0 + n]
+    float4 av[16];                                                                                      // A(i = input, k = feature): W3[fs + 16 c + 4 q + s][k0 + n]
 #pragma unroll
-    for (int c = 0; c < 16; ++c)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) av[c][s] = Wc[(size_t)(16 * c + s) * 256];
+    for (int c = 0; c < 16; ++c) av[c] = make_float4(Wc[(size_t)(16 * c) * 256], Wc[(size_t)(16 * c + 1) * 256], Wc[(size_t)(16 * c + 2) * 256], Wc[(size_t)(16 * c + 3) * 256]);
 #pragma unroll 1
     for (int r0 = 0; r0 < a.rows; r0 += TR) {
         const int row = r0 + n;
         const bool ok = row < a.rows;
         const float* gp = a.g4 + (size_t)(ok ? row : 0) * 16384 + fs + 4 * q;
-        f32x4 acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = (f32x4)(0.f);
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        const f32x4 sum = contract<8, 16>([&](int c) { return av[c]; }, [&](int c) {              // D(i = input 4 q + e, j = row n)
             float4 bv = *reinterpret_cast<const float4*>(gp + 16 * c);                                  // B(k = feature, j = row)
             if (!ok) bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            MFMA4(acc[c & 7], av[c][0], av[c][1], av[c][2], av[c][3], bv)
-        }
-        const f32x4 sum = tree8(acc);                                                                   // D(i = input 4 q + e, j = row n)
+            return bv;
+        });
         if (ok) *reinterpret_cast<float4*>(a.part + ((size_t)seg * a.rows + row) * 256 + k0 + 4 * q) = make_float4(sum[0], sum[1], sum[2], sum[3]);
     }
 }
 
 // grid = ceil(rows / 16): one 16-row tile; slab = the tile's index in its row group
-// LDS: D = g_2 | H2 = x_2, then g_1 | H1 = x_1, then g_0 | X0 = s.  g_{l-1} OVERWRITES x_l in place once dW_l has consumed it (k_mid_grad's
-// scheme): lane (n, q) gates and writes the four elements it reads.
+// LDS: D = g_2 | H2 = x_2, then g_1 | H1 = x_1, then g_0 | X0 = s.
 __global__ void __launch_bounds__(256) k_dech_small(const DecHeadArgs a) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(16))) float X0[TR * SLD];
@@ -282,7 +230,7 @@ __global__ void __launch_bounds__(256) k_dech_small(const DecHeadArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, q = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r0 = blockIdx.x * TR, first = a.first;
-    float* slab = a.slabs + (size_t)blockIdx.x * DEC_HEAD_SMALL_P;
+    gfloat* slab = (gfloat*)a.slabs + (size_t)blockIdx.x * DEC_HEAD_SMALL_P;
     {
         const int r = tid >> 4, c = tid & 15;
         X0[r * SLD + c] = (r0 + r < a.rows && c < 10) ? a.s[(size_t)(r0 + r) * 10 + c] : 0.0f;
@@ -313,81 +261,25 @@ __global__ void __launch_bounds__(256) k_dech_small(const DecHeadArgs a) {
 #pragma unroll 1
     for (int l = 2; l >= 0; --l) {
         const int K = l == 0 ? 10 : 256;
-        const float* W = a.w + (l == 0 ? DH_W0 : l == 1 ? DH_W1 : DH_W2);
-        float* gW = slab + (l == 0 ? DH_W0 : l == 1 ? DH_W1 : DH_W2);
-        float* gB = slab + (l == 0 ? DH_B0 : l == 1 ? DH_B1 : DH_B2);
+        const gfloat* W = (const gfloat*)a.w + (l == 0 ? DH_W0 : l == 1 ? DH_W1 : DH_W2);
+        gfloat* gW = slab + (l == 0 ? DH_W0 : l == 1 ? DH_W1 : DH_W2);
+        gfloat* gB = slab + (l == 0 ? DH_B0 : l == 1 ? DH_B1 : DH_B2);
         const float* d = l == 2 ? D : l == 1 ? H2 : H1;            // g_l
         float* x = l == 2 ? H2 : l == 1 ? H1 : X0;                 // x_l
-        const int xs = l == 0 ? SLD : HLD, IT = l == 0 ? 1 : 16;
-#pragma unroll 1
-        for (int ot = w; ot < 16; ot += 4) {                       // dW[o][i] = sum_r g[r][o] x[r][i]: A(i = o, k = row) stays in registers over the i tiles
-            const int o0 = 16 * ot;
-            float av[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) av[c] = d[(4 * c + q) * HLD + o0 + n];
-#pragma unroll 2
-            for (int it = 0; it < IT; ++it) {
-                const int i0 = 16 * it;
-                f32x4 acc = (f32x4)(0.f);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], x[(4 * c + q) * xs + i0 + n], acc, 0, 0, 0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int o = o0 + 4 * q + e, i = i0 + n;      // D(i = 4 q + e, j = n)
-                    if (i < K) {
-                        float* p = gW + (size_t)o * K + i;
-                        *p = first ? acc[e] : *p + acc[e];
-                    }
-                }
-            }
-        }
-        {                                                          // db[o] = sum_r g[r][o], thread = o
-            float sm = d[tid];
-#pragma unroll
-            for (int r = 1; r < TR; ++r) sm = sm + d[r * HLD + tid];
-            gB[tid] = first ? sm : gB[tid] + sm;
-        }
+        const int xs = l == 0 ? SLD : HLD;
+        dw_pass(d, HLD, x, xs, 256, K, gW, first, w, n, q);
+        db_pass(d, HLD, 256, gB, first, tid);
         __syncthreads();                                           // dW_l has consumed x_l: it may now be overwritten
-        const float* dn = d + n * HLD + 4 * q;                     // B(k = o, j = row): g[n][16 c + 4 q + s]
-        if (l > 0) {                                               // g_{l-1}[r][i] = (sum_o g[r][o] W[o][i]) 2 [x[r][i] > 0], written over x_l[r][i]
-#pragma unroll 1
-            for (int t = 4 * w; t < 4 * w + 4; ++t) {
-                const int i0 = 16 * t;
-                const float* Wc = W + 4 * q * 256 + i0 + n;        // A(i = input, k = o): W[16 c + 4 q + s][i0 + n]
-                f32x4 acc[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] = (f32x4)(0.f);
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const float4 bv = *reinterpret_cast<const float4*>(dn + 16 * c);
-                    float av[4];
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) av[s] = Wc[(16 * c + s) * 256];
-                    MFMA4(acc[c & 7], av[0], av[1], av[2], av[3], bv)
-                }
-                const f32x4 sum = tree8(acc);
-                float* hp = x + n * HLD + i0 + 4 * q;
-                const float4 h = *reinterpret_cast<const float4*>(hp);
-                float4 g;
-                g.x = h.x > 0.0f ? 2.0f * sum[0] : 0.0f;
-                g.y = h.y > 0.0f ? 2.0f * sum[1] : 0.0f;
-                g.z = h.z > 0.0f ? 2.0f * sum[2] : 0.0f;
-                g.w = h.w > 0.0f ? 2.0f * sum[3] : 0.0f;
-                *reinterpret_cast<float4*>(hp) = g;
-            }
+        if (l > 0) {
+            dprev_pass<8, 16>(d, HLD, x, HLD, W, 256, 2.0f, true, w, n, q);
         } else if (w == 0 && a.ds) {                               // d_s[r][i] = sum_o g_0[r][o] W_0[o][i], no gate
-            f32x4 acc[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] = (f32x4)(0.f);
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const float4 bv = *reinterpret_cast<const float4*>(dn + 16 * c);
-                float av[4];
+            const float* dn = d + n * HLD + 4 * q;                 // B(k = o, j = row): g[n][16 c + 4 q + s]
+            const f32x4 sum = contract<8, 16>([&](int c) {
+                float av[4];                                       // A(i = input, k = o): W_0[16 c + 4 q + s][n]
 #pragma unroll
                 for (int s = 0; s < 4; ++s) av[s] = n < 10 ? W[(16 * c + 4 * q + s) * 10 + n] : 0.0f;
-                MFMA4(acc[c & 7], av[0], av[1], av[2], av[3], bv)
-            }
-            const f32x4 sum = tree8(acc);
+                return make_float4(av[0], av[1], av[2], av[3]);
+            }, [&](int c) { return *reinterpret_cast<const float4*>(dn + 16 * c); });
             if (r0 + n < a.rows)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -396,7 +288,6 @@ __global__ void __launch_bounds__(256) k_dech_small(const DecHeadArgs a) {
         __syncthreads();
     }
 }
-#undef MFMA4
 
 void launch_dec_head_fwd(const DecHeadArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_dech_fwd, dim3((a.rows + TR - 1) / TR), dim3(256), 0, st, a);

@@ -137,17 +137,23 @@ def free_energy(model, o0, o1, pi0, log_Ppi, *, omega=None, omega_params=OMEGA_P
     return FreeEnergy(*outs)
 
 
+def _views(flat, tensors, keys=None):
+    """views of the flat gradient `flat` per state_dict key: {key: flat[its span].reshape(its shape)}, keys in parameters() order"""
+    grads, off = {}, 0
+    for key in (tensors if keys is None else keys):
+        t = tensors[key]
+        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
+        off += t.numel()
+    return grads
+
+
 def grad_top(model_top, s, log_Ppi):
     """-> (kl_div_pi [M], {state_dict key: d mean(F_top) / d tensor}): what torchloss.py:69-72 leaves in .grad (views of one flat tensor)"""
     m = model_top._owner
     e = m._ready()
     s = e.tensor(s, (-1, m.s_dim))
     kl, flat = e.ops.top_grad(e.h, s, e.tensor(log_Ppi, (s.shape[0], m.pi_dim)))
-    grads, off = {}, 0
-    for key, t in model_top._sd_host.items():
-        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
-        off += t.numel()
-    return kl, grads
+    return kl, _views(flat, model_top._sd_host)
 
 
 def train_model_top(model_top, s, log_Ppi, optimizer):
@@ -183,11 +189,7 @@ def grad_mid(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, *, stage=N
     .grad (views of one flat tensor), with the dropout masks of (stage, pass_, sample, row_offset)"""
     _, _, args = _mid_inputs(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, stage, pass_, sample, row_offset)
     F, mean, lv, flat = model_mid._owner._engine.ops.mid_grad(*args)
-    grads, off = {}, 0
-    for key, t in model_mid._sd_host.items():
-        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
-        off += t.numel()
-    return F, mean, lv, grads
+    return F, mean, lv, _views(flat, model_mid._sd_host)
 
 
 def train_model_mid(model_mid, s0, qs1_mean, qs1_logvar, Ppi_sampled, omega, optimizer, *, stage=None, pass_=PASS_FE_T, sample=0,
@@ -225,12 +227,7 @@ def grad_decoder_convs(model_down, h4, o1, *, scale=None, return_activations=Fal
         raise ValueError('grad_decoder_convs: scale must be >= 0 (None = beta_o / M)')
     nl, po1, d_h4, flat, y1, y2, y3 = e.ops.dec_tail_grad(e.h, h4, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o),
                                                           bool(return_activations))
-    grads, off = {}, 0
-    for key in DEC_CONVT_KEYS:
-        t = model_down._sd[key]
-        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
-        off += t.numel()
-    out = (nl, po1, d_h4, grads)
+    out = (nl, po1, d_h4, _views(flat, model_down._sd, DEC_CONVT_KEYS))
     return out + ((y1, y2, y3),) if return_activations else out
 
 
@@ -257,10 +254,5 @@ def grad_decoder(model_down, s, o1, *, scale=None, stage=None, pass_=PASS_FE_DOW
     out = e.ops.dec_grad(e.h, s, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o), m._seed64(), nz.stage, pass_, sample,
                          nz.row_offset, bool(return_activations))
     nl, po1, d_s, flat = out[:4]
-    grads, off = {}, 0
-    for key in DEC_HEAD_KEYS + DEC_CONVT_KEYS:
-        t = model_down._sd[key]
-        grads[key] = flat[off:off + t.numel()].reshape(t.shape)
-        off += t.numel()
-    res = (nl, po1, d_s, grads)
+    res = (nl, po1, d_s, _views(flat, model_down._sd, DEC_HEAD_KEYS + DEC_CONVT_KEYS))
     return res + (tuple(out[4:]),) if return_activations else res

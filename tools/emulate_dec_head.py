@@ -1,8 +1,7 @@
 """CPU emulation of the fp32 summation orders of csrc/train_dec_head.hip, to check the fp64 rule of tests/test_fp64_parity.py on the gradient
 cases of tests/test_train_dec_head_gpu.py before a GPU run.  Every contraction of the head is emulated:
-  * over a layer's width (forward of the four layers, d_h3 per 256-feature segment, the data gradients of layers 2, 1, 0, d_s): eight
-    interleaved accumulators, 16-feature chunk c -> accumulator c & 7, within a chunk MFMA step s contracts features 16 c + 4 q + s,
-    q = 0..3 in turn; tree8 = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
+  * over a layer's width (forward of the four layers, d_h3 per 256-feature segment, the data gradients of layers 2, 1, 0, d_s): the chain
+    of csrc/train_mlp.h's order contract with NACC = 8, joined by its tree<8> (tree8 below);
   * d_h3's join of the 64 segments: tree8 of eight sequential sums of eight consecutive segments;
   * dW_3 / db_3: per 64-row group the 16-row tiles ascending, one 16-term chain (db: sequential sum) per tile, group = chunks added in
     ascending order, gradient = groups added in ascending order;

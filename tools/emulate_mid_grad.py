@@ -1,7 +1,7 @@
 """CPU emulation of k_mid_grad's fp32 summation order (csrc/train.hip), to check the fp64 rule of tests/test_fp64_parity.py on the gradient
 cases of tests/test_train_mid_gpu.py before a GPU run: sixteen interleaved accumulators per contraction over a layer's width (16-channel
 chunk c -> accumulator c & 15, within a chunk MFMA step s contracts channels 16 c + 4 q + s, q = 0..3 in turn), the fixed tree of
-tree16(), one 16-row chain per tile for dW, per-workgroup slabs (tiles p, p + G, ..., G = min(T, 8)) summed in ascending order.
+tree<16> of csrc/train_mlp.h (tree16 below), one 16-row chain per tile for dW, per-workgroup slabs (tiles p, p + G, ..., G = min(T, 8)) summed in ascending order.
 An fp32 fma is formed in float64 and rounded once more (a double rounding that moves a result by at most one ulp in rare ties); expf /
 logf are numpy's.  Prints every figure and the worst ratio e_eng / (e_32 + 2 ulp) (the rule allows 4).
 
