@@ -88,6 +88,7 @@ struct efe_ctx {
     float dec_bf = 0.f;
     float* dec_raw = nullptr;      // the whole po_net unpacked, flat in parameters() order (kernels.h DH_*, then DT_*; part of wbufs): train_dec_head.hip reads it
     float* dect_raw = nullptr;     // its tail po_net.13 / .15 / .17 / .19 (= dec_raw + DEC_HEAD_P): train_dec.hip reads it
+    float* enc_raw = nullptr;      // the whole qs_net unpacked, flat in parameters() order (kernels.h EQ_*; part of wbufs): train_enc.hip reads it
     float* zeros = nullptr;
     std::vector<void*> owned;      // lives as long as the context
     std::vector<void*> wbufs;      // packed weights of the current commit (freed by the next one)
@@ -1265,6 +1266,19 @@ static int pack_heads(efe_ctx* ctx) {
 // encoder (torchmodel.py:84-104): the convolution stack, then the head's first layer
 static int pack_encoder(efe_ctx* ctx) {
     const int C = ctx->chan, F = ctx->enc_hw[4] * ctx->enc_hw[4];
+    ctx->enc_raw = nullptr;
+    if (C == 1 && ctx->res == 64) {     // the raw copy the training forward and backward read (train_enc.hip), beside the packed forward forms
+        std::vector<float> flat;
+        for (int i = 0; i < 8; ++i) {
+            const LayerSpec s = i < 4 ? enc_conv_layer(i, C) : i == 4 ? LayerSpec{"down.qs_net.9", 256, F * 64} : ENC_HEAD[i - 5];
+            const WB t = i < 4 ? weight_and_bias(ctx, s.key, {s.out, s.in, 3, 3}, {s.out}) : weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
+            if (!t) return 1;
+            flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
+            flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
+        }
+        if (flat.size() != (size_t)ENC_P) return ctx->fail("encoder: unexpected parameter count");
+        if (!(ctx->enc_raw = upload(ctx, flat))) return 1;
+    }
     if (ctx->generic) {     // build-defined geometry: four k_conv_g layers ...
         for (int i = 0; i < 4; ++i) if (pack_conv(ctx, ctx->g_enc[i], enc_conv_layer(i, C), false)) return 1;
         // ... and layer 1 for the LDS-tiled kernel (generic_enc.hip): lane (co = lane & 31, h = lane >> 5) holds its two K operands of a tap
@@ -1368,7 +1382,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         for (void* p : ctx->wbufs) (void)hipFree(p);
         ctx->wbufs.clear();
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
-        ctx->dec_raw = ctx->dect_raw = nullptr;
+        ctx->dec_raw = ctx->dect_raw = ctx->enc_raw = nullptr;
     }
     ctx->committed = false;
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first
@@ -1640,6 +1654,11 @@ int64_t efe_param_count(efe_ctx* ctx, const char* part) {
     if (part && !strcmp(part, "po_net_convt")) return DT_B3 + 32 + 32 * ctx->chan * 9 + ctx->chan;
     // the whole decoder (efe_dec_grad), likewise without an optimiser step
     if (part && !strcmp(part, "po_net")) return DH_W3 + (int64_t)64 * ctx->base * ctx->base * 257 + DT_B3 + 32 + 32 * ctx->chan * 9 + ctx->chan;
+    // the encoder (efe_enc_grad) and all of ModelDown, qs_net then po_net (efe_down_grad), at the one geometry those calls are built for
+    if (part && (!strcmp(part, "qs_net") || !strcmp(part, "down"))) {
+        if (ctx->chan != 1 || ctx->res != 64) { ctx->fail("efe_param_count: \"qs_net\" and \"down\" are counted for the 1 x 64 x 64 geometry only"); return 0; }
+        return !strcmp(part, "qs_net") ? ENC_P : DOWN_P;
+    }
     if (!train_part(ctx, part, "efe_param_count")) return 0;
     return !strcmp(part, "top") ? part_param_count(TOP_NL, top_layer, ctx->pi_dim) : part_param_count(MID_NL, mid_layer, ctx->pi_dim);
 }
@@ -1715,9 +1734,28 @@ namespace {
 // the dense head's side of the call: its input, the keys of its four dropout masks, its outputs (all nullable but s and nz)
 struct DecHeadIO { const float* s; const efe_noise* nz; float* d_s; float *h1, *h2, *h3, *h4; };
 
+// The decoder's gradient as the row groups of one call: open() checks the arguments and takes the scratch, group(m0) queues the forward and
+// backward of rows [m0, m0 + rows(m0)), close() joins the slabs.  efe_dec_tail_grad, efe_dec_grad and efe_down_grad (which runs the
+// encoder's group around each of the decoder's) share it.
 // hd == nullptr: the tail alone, from the caller's h4 to the caller's d_h4 (nullable), grad [DEC_TAIL_P]; else grad [DEC_P] and h4 / d_h4 unused
-int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4, float* d_h4, const float* o1, int M, float scale, float beta_o,
-             float* nlogpo1, float* po1, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
+struct DecGrad {
+    efe_ctx* ctx; const DecHeadIO* hd; const float* h4; float* d_h4; const float* o1; int M; float scale;
+    float *nlogpo1, *po1, *grad, *y1, *y2, *y3;
+    hipStream_t st;
+    DecTailPlan p; DecHeadPlan hp{};
+    float *s1, *s2, *s3, *sp, *g4, *g3, *g2, *g1, *tgrad, *tslabs;
+    float *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr, *dh4 = nullptr, *part = nullptr, *hslabs = nullptr;
+    int open(efe_ctx* ctx_, const char* who, const DecHeadIO* hd_, const float* h4_, float* d_h4_, const float* o1_, int M_, float scale_, float beta_o,
+             float* nlogpo1_, float* po1_, float* grad_, float* y1_, float* y2_, float* y3_, hipStream_t st_);
+    int rows(int m0) const { return std::min(p.C, M - m0); }
+    const float* po_of(int m0) const { return po1 ? po1 + (size_t)m0 * 4096 : sp; }      // the images of the group that starts at row m0
+    void group(int m0);
+    void close();
+};
+int DecGrad::open(efe_ctx* ctx_, const char* who, const DecHeadIO* hd_, const float* h4_, float* d_h4_, const float* o1_, int M_, float scale_, float beta_o,
+                  float* nlogpo1_, float* po1_, float* grad_, float* y1_, float* y2_, float* y3_, hipStream_t st_) {
+    ctx = ctx_; hd = hd_; h4 = h4_; d_h4 = d_h4_; o1 = o1_; M = M_; scale = scale_;
+    nlogpo1 = nlogpo1_; po1 = po1_; grad = grad_; y1 = y1_; y2 = y2_; y3 = y3_; st = st_;
     const std::string w(who);
     if (M <= 0) return ctx->fail(w + ": M must be >= 1");
     if (!(hd ? hd->s && hd->nz : h4 != nullptr) || !o1 || !nlogpo1 || !grad)
@@ -1728,14 +1766,12 @@ int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4
         if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail(w + ": scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
         scale = beta_o / (float)M;
     }
-    const DecTailPlan p = dec_tail_plan(M, !y1, !y2, !y3, !po1);
-    float* s1 = ctx->allocT<float>(p.y1); float* s2 = ctx->allocT<float>(p.y2); float* s3 = ctx->allocT<float>(p.y3); float* sp = ctx->allocT<float>(p.po);
-    float* g4 = ctx->allocT<float>(p.g4); float* g3 = ctx->allocT<float>(p.g3); float* g2 = ctx->allocT<float>(p.g2); float* g1 = ctx->allocT<float>(p.g1);
-    float* tgrad = hd ? grad + DEC_HEAD_P : grad;           // the tail's gradient
-    float* tslabs = p.G > 1 ? ctx->allocT<float>(p.slabs) : tgrad;
+    p = dec_tail_plan(M, !y1, !y2, !y3, !po1);
+    s1 = ctx->allocT<float>(p.y1); s2 = ctx->allocT<float>(p.y2); s3 = ctx->allocT<float>(p.y3); sp = ctx->allocT<float>(p.po);
+    g4 = ctx->allocT<float>(p.g4); g3 = ctx->allocT<float>(p.g3); g2 = ctx->allocT<float>(p.g2); g1 = ctx->allocT<float>(p.g1);
+    tgrad = hd ? grad + DEC_HEAD_P : grad;           // the tail's gradient
+    tslabs = p.G > 1 ? ctx->allocT<float>(p.slabs) : tgrad;
     if (!s1 || !s2 || !s3 || !sp || !g4 || !g3 || !g2 || !g1 || !tslabs) return 1;
-    DecHeadPlan hp{};
-    float *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr, *dh4 = nullptr, *part = nullptr, *hslabs = nullptr;
     if (hd) {
         hp = dec_head_plan(M, !hd->h1, !hd->h2, !hd->h3, !hd->h4);
         a1 = ctx->allocT<float>(hp.h1); a2 = ctx->allocT<float>(hp.h2); a3 = ctx->allocT<float>(hp.h3); a4 = ctx->allocT<float>(hp.h4);
@@ -1743,8 +1779,12 @@ int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4
         hslabs = hp.G > 1 ? ctx->allocT<float>(hp.slabs) : grad;
         if (!a1 || !a2 || !a3 || !a4 || !dh4 || !part || !hslabs) return 1;
     }
-    for (int m0 = 0; m0 < M; m0 += p.C) {       // row groups: boundaries at multiples of DEC_TAIL_ROWS, a function of M alone
-        const int rows = std::min(p.C, M - m0);
+    return 0;
+}
+// one row group: boundaries at multiples of DEC_TAIL_ROWS, a function of M alone
+void DecGrad::group(int m0) {
+    {
+        const int rows = this->rows(m0);
         DecHeadArgs h{};
         if (hd) {
             h.w = ctx->dec_raw; h.s = hd->s + (size_t)m0 * S_DIM;
@@ -1763,11 +1803,77 @@ int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4
         launch_dec_tail_group(a, st);
         if (hd) launch_dec_head_bwd(h, st);
     }
+}
+void DecGrad::close() {
     if (p.G > 1) launch_slab_sum(tslabs, p.G, DEC_TAIL_P, tgrad, st);
     if (hd && hp.G > 1) launch_slab_sum(hslabs, hp.G, DEC_HEAD_SMALL_P, grad, st);
     ctx->last_macs += (int64_t)M * 3 * (38928384 + (hd ? 4328960 : 0));      // forward, data gradient, weight gradient of the four (eight) layers
+}
+int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4, float* d_h4, const float* o1, int M, float scale, float beta_o,
+             float* nlogpo1, float* po1, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
+    DecGrad d;
+    if (d.open(ctx, who, hd, h4, d_h4, o1, M, scale, beta_o, nlogpo1, po1, grad, y1, y2, y3, st)) return 1;
+    for (int m0 = 0; m0 < M; m0 += d.p.C) d.group(m0);
+    d.close();
     return 0;
 }
+
+// ---- the encoder's training forward and backward (train_enc.hip) as the row groups of one call, the same way ---------------------------
+// the encoder's stored activations of one row group (those the caller gives no output for), the gradients at the four convolutions'
+// outputs, and the two sets of slabs (none at G = 1: the gradient itself)
+struct EncGradPlan { int C, GC, GH; size_t y1, y2, y3, y4, h1, h2, h3, g4, g3, g2, g1, cslabs, hslabs; };
+EncGradPlan enc_grad_plan(int64_t M, bool own_y1, bool own_y2, bool own_y3, bool own_y4, bool own_h1, bool own_h2, bool own_h3) {
+    const size_t C = (size_t)std::min<int64_t>(DEC_TAIL_ROWS, M);
+    const int GC = enc_conv_slabs((int)std::min<int64_t>(M, ENC_CONV_SLABS)), GH = enc_head_slabs((int)std::min<int64_t>(M, 16 * ENC_HEAD_SLABS));
+    return {(int)C, GC, GH, own_y1 ? C * ENC_Y1 : 0, own_y2 ? C * ENC_Y2 : 0, own_y3 ? C * ENC_Y3 : 0, own_y4 ? C * ENC_Y4 : 0,
+            own_h1 ? C * 256 : 0, own_h2 ? C * 256 : 0, own_h3 ? C * 256 : 0, C * ENC_Y4, C * ENC_Y3, C * ENC_Y2, C * ENC_Y1,
+            GC > 1 ? (size_t)GC * ENC_CONV_P : 0, GH > 1 ? (size_t)GH * ENC_HEAD_P : 0};
+}
+struct EncGrad {
+    efe_ctx* ctx; const float* o; const float *g_mean, *g_logvar; int M; const efe_noise* nz;
+    float *mean, *logvar, *grad, *y1, *y2, *y3, *y4, *h1, *h2, *h3;      // mean / logvar [M][10] are never scratch of one group: the caller's, or whole
+    hipStream_t st;
+    EncGradPlan p;
+    float *s1, *s2, *s3, *s4, *a1, *a2, *a3, *g4, *g3, *g2, *g1, *cslabs, *hslabs;
+    // g_mean / g_logvar may be given later (set them before the first bwd()): the composed call forms them per group
+    int open(efe_ctx* ctx_, const char* who, const float* o_, int M_, const efe_noise* nz_, float* mean_, float* logvar_, float* grad_,
+             float* y1_, float* y2_, float* y3_, float* y4_, float* h1_, float* h2_, float* h3_, hipStream_t st_) {
+        ctx = ctx_; o = o_; M = M_; nz = nz_; mean = mean_; logvar = logvar_; grad = grad_;
+        y1 = y1_; y2 = y2_; y3 = y3_; y4 = y4_; h1 = h1_; h2 = h2_; h3 = h3_; st = st_; g_mean = g_logvar = nullptr;
+        const std::string w(who);
+        if (ctx->chan != 1 || ctx->res != 64 || !ctx->enc_raw) return ctx->fail(w + ": built for the 1 x 64 x 64 geometry only");
+        if (ctx->mfma_bf16x3) return ctx->fail(w + ": not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+        p = enc_grad_plan(M, !y1, !y2, !y3, !y4, !h1, !h2, !h3);
+        s1 = ctx->allocT<float>(p.y1); s2 = ctx->allocT<float>(p.y2); s3 = ctx->allocT<float>(p.y3); s4 = ctx->allocT<float>(p.y4);
+        a1 = ctx->allocT<float>(p.h1); a2 = ctx->allocT<float>(p.h2); a3 = ctx->allocT<float>(p.h3);
+        g4 = ctx->allocT<float>(p.g4); g3 = ctx->allocT<float>(p.g3); g2 = ctx->allocT<float>(p.g2); g1 = ctx->allocT<float>(p.g1);
+        if (!mean) mean = ctx->allocT<float>((size_t)M * S_DIM);
+        if (!logvar) logvar = ctx->allocT<float>((size_t)M * S_DIM);
+        cslabs = p.GC > 1 ? ctx->allocT<float>(p.cslabs) : grad;
+        hslabs = p.GH > 1 ? ctx->allocT<float>(p.hslabs) : grad + ENC_CONV_P;
+        if (!s1 || !s2 || !s3 || !s4 || !a1 || !a2 || !a3 || !g4 || !g3 || !g2 || !g1 || !mean || !logvar || !cslabs || !hslabs) return 1;
+        return 0;
+    }
+    EncTrainArgs args(int m0) const {
+        EncTrainArgs a{};
+        a.w = ctx->enc_raw; a.o = o + (size_t)m0 * 4096;
+        a.y1 = y1 ? y1 + (size_t)m0 * ENC_Y1 : s1; a.y2 = y2 ? y2 + (size_t)m0 * ENC_Y2 : s2; a.y3 = y3 ? y3 + (size_t)m0 * ENC_Y3 : s3;
+        a.y4 = y4 ? y4 + (size_t)m0 * ENC_Y4 : s4;
+        a.h1 = h1 ? h1 + (size_t)m0 * 256 : a1; a.h2 = h2 ? h2 + (size_t)m0 * 256 : a2; a.h3 = h3 ? h3 + (size_t)m0 * 256 : a3;
+        a.mean = mean + (size_t)m0 * S_DIM; a.logvar = logvar + (size_t)m0 * S_DIM;
+        a.g_mean = g_mean ? g_mean + (size_t)m0 * S_DIM : nullptr; a.g_logvar = g_logvar ? g_logvar + (size_t)m0 * S_DIM : nullptr;
+        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.cslabs = cslabs; a.hslabs = hslabs;
+        a.rows = std::min(p.C, M - m0); a.GC = p.GC; a.first = m0 == 0; a.key = train_key(nz, (uint32_t)m0);
+        return a;
+    }
+    void fwd(int m0) { launch_enc_train_fwd(args(m0), st); }
+    void bwd(int m0) { launch_enc_train_bwd(args(m0), st); }
+    void close() {
+        if (p.GC > 1) launch_slab_sum(cslabs, p.GC, ENC_CONV_P, grad, st);
+        if (p.GH > 1) launch_slab_sum(hslabs, p.GH, ENC_HEAD_P, grad + ENC_CONV_P, st);
+        ctx->last_macs += (int64_t)M * 3 * 3868960;     // forward, data gradient, weight gradient: 276 768 + 2 073 600 + 903 168 + 331 776 conv, 283 648 dense
+    }
+};
 }  // namespace
 
 int efe_dec_tail_grad(efe_ctx* ctx, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
@@ -1782,6 +1888,67 @@ int efe_dec_grad(efe_ctx* ctx, const float* s, const float* o1, int M, float sca
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     const DecHeadIO hd{s, nz, d_s, h1, h2, h3, h4};
     if (dec_grad(ctx, "efe_dec_grad", &hd, nullptr, nullptr, o1, M, scale, beta_o, nlogpo1, po1, grad, y1, y2, y3, st)) return 1;
+    return call.finish();
+}
+
+int efe_enc_grad(efe_ctx* ctx, const float* o, const float* g_mean, const float* g_logvar, int M, const efe_noise* nz, float* mean, float* logvar,
+                 float* grad, float* y1, float* y2, float* y3, float* y4, float* h1, float* h2, float* h3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (M <= 0) return ctx->fail("efe_enc_grad: M must be >= 1");
+    if (!o || !g_mean || !g_logvar || !nz || !grad) return ctx->fail("efe_enc_grad: o, g_mean, g_logvar, nz and grad must be non-NULL");
+    EncGrad e;
+    if (e.open(ctx, "efe_enc_grad", o, M, nz, mean, logvar, grad, y1, y2, y3, y4, h1, h2, h3, st)) return 1;
+    e.g_mean = g_mean; e.g_logvar = g_logvar;
+    for (int m0 = 0; m0 < M; m0 += e.p.C) { e.fwd(m0); e.bwd(m0); }
+    e.close();
+    return call.finish();
+}
+
+int efe_down_grad(efe_ctx* ctx, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (M <= 0) return ctx->fail("efe_down_grad: M must be >= 1");
+    if (!o1 || !ps1_mean || !ps1_logvar || !nz || !out || !grad)
+        return ctx->fail("efe_down_grad: o1, ps1_mean, ps1_logvar, params, nz, out and grad must be non-NULL");
+    if (fe_params(ctx, params, false, "efe_down_grad")) return 1;
+    if (!out->F_down) return ctx->fail("efe_down_grad: out->F_down is required");
+    EncGrad e;
+    if (e.open(ctx, "efe_down_grad", o1, M, nz, out->qs1_mean, out->qs1_logvar, grad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return 1;
+    float* qs1 = out->qs1 ? out->qs1 : ctx->allocT<float>((size_t)M * S_DIM);
+    float* d_s = ctx->allocT<float>((size_t)M * S_DIM);
+    float* nl = out->nlogpo1 ? out->nlogpo1 : ctx->allocT<float>((size_t)M);
+    float* gm = g_mean ? g_mean : ctx->allocT<float>((size_t)M * S_DIM);
+    float* gv = g_logvar ? g_logvar : ctx->allocT<float>((size_t)M * S_DIM);
+    if (!qs1 || !d_s || !nl || !gm || !gv) return 1;
+    e.g_mean = gm; e.g_logvar = gv;
+    const DecHeadIO hd{qs1, nz, d_s, nullptr, nullptr, nullptr, nullptr};
+    DecGrad d;
+    if (d.open(ctx, "efe_down_grad", &hd, nullptr, nullptr, o1, M, -1.0f, params->beta_o, nl, out->po1, grad + ENC_P, nullptr, nullptr, nullptr, st)) return 1;
+    const float* omega = params->omega_mode == EFE_OMEGA_ARRAY ? params->omega : nullptr;
+    // F_down and its terms: k_fe_down's expressions on the training forward's po1, mean and logvar (nlogpo1 is the decoder group's own)
+    efe_fe_out fo{};
+    fo.F_down = out->F_down; fo.kl_s = out->kl_s; fo.kl_naive = out->kl_naive;
+    FeArgs fa = fe_down_args(ctx, M, o1, e.mean, ps1_mean, ps1_logvar, S_DIM, params, omega, &fo);
+    fa.q1_mean = e.mean; fa.q1_lv = e.logvar; fa.q1_ld = S_DIM;
+    const uint32_t k0 = (uint32_t)nz->seed, k1 = (uint32_t)(nz->seed >> 32);
+    for (int m0 = 0; m0 < M; m0 += e.p.C) {         // (both plans cut the rows at multiples of DEC_TAIL_ROWS)
+        const int rows = d.rows(m0);
+        const size_t r10 = (size_t)m0 * S_DIM;
+        e.fwd(m0);
+        launch_reparam(e.mean + r10, e.logvar + r10, eps ? eps + r10 : nullptr, qs1 + r10, rows, S_DIM, k0, k1, nz->pass, nz->sample, nz->stage,
+                       nz->row_offset + (uint32_t)m0, st);
+        d.group(m0);
+        launch_fe_down(fa, d.po_of(m0), m0, rows, st);
+        DownLatentArgs la{};
+        la.d_s = d_s + r10; la.mean = e.mean + r10; la.logvar = e.logvar + r10; la.p1_mean = ps1_mean + r10; la.p1_lv = ps1_logvar + r10;
+        la.eps_inj = eps ? eps + r10 : nullptr; la.omega_in = omega ? omega + m0 : nullptr; la.omega_scalar = params->omega_scalar;
+        la.gamma = params->gamma; la.beta_s = params->beta_s; la.Mf = (float)M;
+        la.g_mean = gm + r10; la.g_logvar = gv + r10; la.rows = rows; la.key = train_key(nz, (uint32_t)m0);
+        launch_down_latent(la, st);
+        e.bwd(m0);
+    }
+    d.close();
+    e.close();
     return call.finish();
 }
 

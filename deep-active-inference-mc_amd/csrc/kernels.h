@@ -485,6 +485,47 @@ struct DecHeadArgs {                     // one row group (at most DEC_TAIL_ROWS
 void launch_dec_head_fwd(const DecHeadArgs& a, hipStream_t st);       // s -> h1 .. h4
 void launch_dec_head_bwd(const DecHeadArgs& a, hipStream_t st);       // d_h4 -> the head's gradients and d_s
 
+// ---- training forward and backward of the encoder qs_net at 1 x 64 x 64 (train_enc.hip) -----------------------------------------
+// The whole qs_net as one flat vector in parameters() order: 0.weight [32][1][3][3], 0.bias, 2.weight [32][32][3][3], 2.bias, 4.weight
+// [64][32][3][3], 4.bias, 6.weight [64][64][3][3], 6.bias, 9.weight [256][576], 9.bias, 12.weight [256][256], 12.bias, 15.weight, 15.bias,
+// 18.weight [20][256], 18.bias: the raw device copy and the gradient.  The convolutions come first (ENC_CONV_P), the dense head behind.
+constexpr int EQ_W1 = 0, EQ_B1 = EQ_W1 + 32 * 9, EQ_W2 = EQ_B1 + 32, EQ_B2 = EQ_W2 + 32 * 32 * 9, EQ_W3 = EQ_B2 + 32, EQ_B3 = EQ_W3 + 64 * 32 * 9,
+              EQ_W4 = EQ_B3 + 64, EQ_B4 = EQ_W4 + 64 * 64 * 9, ENC_CONV_P = EQ_B4 + 64,                                  // 64 992
+              EQ_W9 = ENC_CONV_P, EQ_B9 = EQ_W9 + 256 * 576, EQ_W12 = EQ_B9 + 256, EQ_B12 = EQ_W12 + 256 * 256, EQ_W15 = EQ_B12 + 256,
+              EQ_B15 = EQ_W15 + 256 * 256, EQ_W18 = EQ_B15 + 256, EQ_B18 = EQ_W18 + 20 * 256, ENC_P = EQ_B18 + 20,        // 349 428
+              ENC_HEAD_P = ENC_P - ENC_CONV_P, DOWN_P = ENC_P + DEC_P;                                                   // 284 436, 4 787 125
+constexpr size_t ENC_Y1 = 32 * 961, ENC_Y2 = 32 * 225, ENC_Y3 = 64 * 49, ENC_Y4 = 64 * 9;      // floats per row of the stored activations
+constexpr int ENC_CONV_SLABS = 32;       // slabs of the convolutions' gradient: row m adds to slab m mod G, G = enc_conv_slabs(M)
+constexpr int ENC_HEAD_SLABS = 4;        // slabs of the dense head's: 16-row tile t adds to slab t mod G, G = enc_head_slabs(M)
+__host__ __device__ inline int enc_conv_slabs(int M) { return M < ENC_CONV_SLABS ? M : ENC_CONV_SLABS; }
+__host__ __device__ inline int enc_head_slabs(int M) { const int t = (M + 15) / 16; return t < ENC_HEAD_SLABS ? t : ENC_HEAD_SLABS; }
+struct EncTrainArgs {                    // one row group (at most DEC_TAIL_ROWS rows): every row pointer is the group's first row
+    const float* w;                      // raw parameters [ENC_P]
+    const float* o;                      // [rows][64][64]
+    float *y1, *y2, *y3, *y4;            // stored forward: relu outputs [rows][32][31][31], [32][15][15], [64][7][7], [64][3][3] (NCHW)
+    float *h1, *h2, *h3;                 // ... of the head, after the mask [rows][256]
+    float *mean, *logvar;                // [rows][10]
+    const float *g_mean, *g_logvar;      // backward: the upstream pair [rows][10]
+    float *g4, *g3, *g2, *g1;            // dL / da of the four convolutions, shaped as y4 .. y1
+    float* cslabs;                       // [GC][ENC_CONV_P]; first != 0: written, else added to
+    float* hslabs;                       // [GH][ENC_HEAD_P]
+    int rows, GC, first;
+    TrainKey key;                        // row0 = the global row of the group's row 0
+};
+void launch_enc_train_fwd(const EncTrainArgs& a, hipStream_t st);     // o -> y1 .. y4, h1 .. h3, mean, logvar
+void launch_enc_train_bwd(const EncTrainArgs& a, hipStream_t st);     // (g_mean, g_logvar) -> the slabs of every parameter's gradient
+// d mean(F_down) / d (qs1_mean, qs1_logvar) of one row group: the decoder's d_s through the sample plus the two KL terms of compute_loss_down
+struct DownLatentArgs {
+    const float *d_s, *mean, *logvar, *p1_mean, *p1_lv;      // [rows][10] each
+    const float* eps_inj;                // nullable [rows][10]: else the draw of (TAG_EPS, key)
+    const float* omega_in; float omega_scalar;      // omega_in nullable [rows]
+    float gamma, beta_s, Mf;             // Mf = the rows of the whole call (the mean's divisor)
+    float *g_mean, *g_logvar;            // [rows][10]
+    int rows;
+    TrainKey key;
+};
+void launch_down_latent(const DownLatentArgs& a, hipStream_t st);
+
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);
 void launch_root_post(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,

@@ -500,6 +500,54 @@ std::vector<Tensor> dec_grad(int64_t h, const Tensor& s_, const Tensor& o1_, dou
     return {nl, po, ds, grad, h1, h2, h3, h4, y1, y2, y3};
 }
 
+// ---- backward of the encoder (csrc/train_enc.hip) ----
+// the vector-Jacobian product of qs_net for (g_mean, g_logvar) -> (mean [M,10], logvar [M,10], grad [349428], y1, y2, y3, y4, h1, h2, h3); the
+// activations are empty tensors unless want_act
+std::vector<Tensor> enc_grad(int64_t h, const Tensor& o_, const Tensor& gm_, const Tensor& gv_, int64_t seed, int64_t stage, int64_t pass, int64_t sample,
+                             int64_t row_offset, bool want_act) {
+    efe_ctx* c = CTX(h);
+    Tensor o = in(o_, "o"), gm = in(gm_, "d_mean"), gv = in(gv_, "d_logvar");
+    const int M = rows(o, 4096, "o");
+    TORCH_CHECK(gm.numel() == (int64_t)M * 10 && gv.numel() == (int64_t)M * 10, "efe: d_mean and d_logvar must be [M, 10]");
+    const int64_t NP = efe_param_count(c, "qs_net");
+    TORCH_CHECK(NP > 0, "efe engine: ", efe_last_error(c));
+    const efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    auto op = o.options();
+    const int64_t Ma = want_act ? M : 0;
+    Tensor mean = at::empty({M, 10}, op), lv = at::empty({M, 10}, op), grad = at::empty({NP}, op);
+    Tensor y1 = at::empty({Ma, 32, 31, 31}, op), y2 = at::empty({Ma, 32, 15, 15}, op), y3 = at::empty({Ma, 64, 7, 7}, op), y4 = at::empty({Ma, 64, 3, 3}, op);
+    Tensor h1 = at::empty({Ma, 256}, op), h2 = at::empty({Ma, 256}, op), h3 = at::empty({Ma, 256}, op);
+    auto A = [&](Tensor& t) { return want_act ? P(t) : nullptr; };
+    ok(c, efe_enc_grad(c, o.data_ptr<float>(), gm.data_ptr<float>(), gv.data_ptr<float>(), M, &nz, P(mean), P(lv), P(grad), A(y1), A(y2), A(y3), A(y4),
+                       A(h1), A(h2), A(h3), stream_of(o)));
+    return {mean, lv, grad, y1, y2, y3, y4, h1, h2, h3};
+}
+
+// ---- gradient of F_down for all of ModelDown (csrc/train_enc.hip + the decoder's two files) ----
+// -> (F_down [M], nlogpo1 [M], kl_s [M], kl_naive [M], po1 [M,1,64,64], qs1, qs1_mean, qs1_logvar [M,10], g_mean, g_logvar [M,10], grad [4787125])
+std::vector<Tensor> down_grad(int64_t h, const Tensor& o1_, const Tensor& pm_, const Tensor& pv_, double gamma, double beta_s, double beta_o, int64_t omega_mode,
+                              const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample, int64_t row_offset,
+                              const OptT& eps) {
+    efe_ctx* c = CTX(h);
+    Tensor o1 = in(o1_, "o1"), pm = in(pm_, "ps1_mean"), pv = in(pv_, "ps1_logvar"), ok_, ek;
+    const int M = rows(o1, 4096, "o1");
+    TORCH_CHECK(pm.numel() == (int64_t)M * 10 && pv.numel() == (int64_t)M * 10, "efe: ps1_mean and ps1_logvar must be [M, 10]");
+    const int64_t NP = efe_param_count(c, "down");
+    TORCH_CHECK(NP > 0, "efe engine: ", efe_last_error(c));
+    efe_fe_params p = fe_params(gamma, beta_s, beta_o, omega_mode, omega, ok_, omega_scalar, M);
+    auto op = o1.options();
+    Tensor F = at::empty({M}, op), nl = at::empty({M}, op), kls = at::empty({M}, op), kln = at::empty({M}, op), po1 = at::empty({M, 1, 64, 64}, op);
+    Tensor qs1 = at::empty({M, 10}, op), qm = at::empty({M, 10}, op), qv = at::empty({M, 10}, op), gm = at::empty({M, 10}, op), gv = at::empty({M, 10}, op);
+    Tensor grad = at::empty({NP}, op);
+    efe_fe_out out{};
+    out.F_down = P(F); out.nlogpo1 = P(nl); out.kl_s = P(kls); out.kl_naive = P(kln); out.po1 = P(po1); out.qs1 = P(qs1);
+    out.qs1_mean = P(qm); out.qs1_logvar = P(qv);
+    efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    ok(c, efe_down_grad(c, o1.data_ptr<float>(), pm.data_ptr<float>(), pv.data_ptr<float>(), M, &p, &nz, optp(eps, ek, "eps", (int64_t)M * 10), &out,
+                        P(gm), P(gv), P(grad), stream_of(o1)));
+    return {F, nl, kls, kln, po1, qs1, qm, qv, gm, gv, grad};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -525,6 +573,8 @@ TORCH_LIBRARY(efe, m) {
     m.def("train_mid(int ctx, Tensor s0, Tensor Ppi_sampled, Tensor qs1_mean, Tensor qs1_logvar, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> (Tensor ps1_mean, Tensor ps1_logvar, Tensor F_mid)");
     m.def("dec_tail_grad(int ctx, Tensor h4, Tensor o1, float scale, float beta_o, bool want_y) -> (Tensor nlogpo1, Tensor po1, Tensor d_h4, Tensor grad, Tensor y1, Tensor y2, Tensor y3)");
     m.def("dec_grad(int ctx, Tensor s, Tensor o1, float scale, float beta_o, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
+    m.def("enc_grad(int ctx, Tensor o, Tensor d_mean, Tensor d_logvar, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
+    m.def("down_grad(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -550,4 +600,6 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("train_mid", &train_mid);
     m.impl("dec_tail_grad", &dec_tail_grad);
     m.impl("dec_grad", &dec_grad);
+    m.impl("enc_grad", &enc_grad);
+    m.impl("down_grad", &down_grad);
 }

@@ -134,10 +134,11 @@ __device__ __forceinline__ void db_pass(const float* d, int dld, int O, gfloat* 
 }
 
 // d_prev[r][i] = (sum_o d[r][o] W[o][i]) * keep [x[r][i] > 0], written over x[r][i]; W [O][K] row-major, K a multiple of 16.  Each wave
-// takes a contiguous quarter of the input tiles; O = 16 NC
-template <int NACC, int NC>
+// takes a contiguous quarter of the input tiles; O = 16 NC, or (BOUND) O < 16 NC rows of W: the features from O on feed exact zeros, never
+// what lies behind W (d holds zeros there as well)
+template <int NACC, int NC, bool BOUND = false>
 __device__ __forceinline__ void dprev_pass(const float* d, int dld, float* x, int xld, const gfloat* W, int K, float keep, bool relu,
-                                           int w, int n, int q) {
+                                           int w, int n, int q, int O = 16 * NC) {
 #pragma clang fp contract(off)
     const int IT = (K + 15) / 16, tpw = (IT + 3) / 4, t1 = min(IT, (w + 1) * tpw);
     const float* dn = d + n * dld + 4 * q;                             // B(k = o, j = row): d[n][16 c + 4 q + s]
@@ -150,7 +151,13 @@ __device__ __forceinline__ void dprev_pass(const float* d, int dld, float* x, in
                 const int o = 16 * c + 4 * q;
                 float av[4];
 #pragma unroll
-                for (int s = 0; s < 4; ++s) av[s] = Wc[(size_t)(o + s) * K];
+                for (int s = 0; s < 4; ++s) {
+                    if constexpr (BOUND) {
+                        const bool in = o + s < O;
+                        const float v = Wc[(size_t)(in ? o + s : 0) * K];
+                        av[s] = in ? v : 0.0f;
+                    } else av[s] = Wc[(size_t)(o + s) * K];
+                }
                 return make_float4(av[0], av[1], av[2], av[3]);
             },
             [&](int c) { return *reinterpret_cast<const float4*>(dn + 16 * c); });

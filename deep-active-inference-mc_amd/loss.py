@@ -5,12 +5,16 @@ composition train.py:104-123 evaluates before its optimizer steps, in one engine
 No autograd graph is built.  The habit network and the transition network are trainable: `train_model_top` (torchloss.py:65-74) and
 `train_model_mid` (torchloss.py:76-88) are each one Adam step on the device (csrc/train.hip: backward + update in two launches, with a
 daimc_amd.Adam holding the state), and `grad_top` / `grad_mid` return the gradients.  `train_model_down` (torchloss.py:90-98, the encoder /
-decoder) is not built; its decoder half is: `grad_decoder` is the gradient of the reconstruction term with respect to every parameter of
-po_net and to s in one engine call -- the dense head po_net.0 / .3 / .6 / .9 evaluated for training with the forward decoder's four
-dropout masks (csrc/train_dec_head.hip), then the four ConvTranspose2d layers (po_net.13 / .15 / .17 / .19, csrc/train_dec.hip), which
-`grad_decoder_convs` also runs on their own from a given Unflatten input.  The optimiser step for po_net, the encoder's backward and
-train_model_down itself are still missing, and a training loop is out of scope.  Every call dispatches through torch.ops.efe.* on the
-model's device; there is no CPU fallback.
+decoder) is built up to the gradient: `grad_down` returns F_down and d mean(F_down) / d every parameter of ModelDown (qs_net, then
+po_net: the order an Adam over model_down.parameters() sees) in one engine call -- per 64-row group the encoder evaluated for training
+with the forward encoder's three dropout masks (csrc/train_enc.hip), the sample, the decoder's forward and backward, the gradient of the
+reconstruction and KL terms at the latent, and the encoder's backward.  Its pieces run on their own: `grad_encoder` is the encoder's
+vector-Jacobian product for a given upstream pair, `grad_decoder` the gradient of the reconstruction term with respect to every
+parameter of po_net and to s -- the dense head po_net.0 / .3 / .6 / .9 evaluated for training with the forward decoder's four dropout
+masks (csrc/train_dec_head.hip), then the four ConvTranspose2d layers (po_net.13 / .15 / .17 / .19, csrc/train_dec.hip), which
+`grad_decoder_convs` also runs from a given Unflatten input.  The optimiser step for ModelDown (with the repack of the forward forms of
+po_net and the encoder trunk on the device) and train_model_down itself are still missing, and a training loop is out of scope.  Every
+call dispatches through torch.ops.efe.* on the model's device; there is no CPU fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
 encoder, FE_T for the transition + sample, FE_DOWN for compute_loss_down's encoder + sample + decoder), one stage per call, rows keyed
@@ -256,3 +260,50 @@ def grad_decoder(model_down, s, o1, *, scale=None, stage=None, pass_=PASS_FE_DOW
     nl, po1, d_s, flat = out[:4]
     res = (nl, po1, d_s, _views(flat, model_down._sd, DEC_HEAD_KEYS + DEC_CONVT_KEYS))
     return res + (tuple(out[4:]),) if return_activations else res
+
+
+ENC_KEYS = tuple(f'qs_net.{i}.{sfx}' for i in (0, 2, 4, 6, 9, 12, 15, 18) for sfx in ('weight', 'bias'))
+
+
+def _down_model(model_down, who):
+    m = model_down._owner
+    if (m.colour_channels, m.resolution) != (1, 64):
+        raise ValueError(f'{who}: built for 1 x 64 x 64 models, this one is {m.colour_channels} x {m.resolution} x {m.resolution}')
+    return m, m._ready()
+
+
+def grad_encoder(model_down, o, d_mean, d_logvar, *, stage=None, pass_=PASS_FE_DOWN, sample=0, row_offset=None, return_activations=False):
+    """The encoder qs_net (torchmodel.py:84-104) evaluated for training and its vector-Jacobian product for the upstream pair d_mean,
+    d_logvar [M,10] -> (qs_mean [M,10], qs_logvar [M,10], {state_dict key: sum_r d_mean_r . d qs_mean_r / d tensor + d_logvar_r . d qs_logvar_r
+    / d tensor}) and, with return_activations, (y1, y2, y3, y4, h1, h2, h3): the stored activations (y1..y4 NCHW after the ReLU, h1..h3
+    [M,256] after ReLU and dropout mask), whose sign is the backward gate.  The three dropout masks are those `model_down.encoder(o, stage=,
+    pass_=, sample=, row_offset=)` draws, so qs_mean / qs_logvar agree with it to rounding.  The gradients are views of one flat tensor
+    over the 16 qs_net.* keys in parameters() order.  1 x 64 x 64 models only."""
+    m, e = _down_model(model_down, 'grad_encoder')
+    o = e.tensor(o, (-1, 1, 64, 64))
+    M = o.shape[0]
+    nz = m._noise(stage, pass_, sample, row_offset)
+    out = e.ops.enc_grad(e.h, o, e.tensor(d_mean, (M, m.s_dim)), e.tensor(d_logvar, (M, m.s_dim)), m._seed64(), nz.stage, pass_, sample,
+                         nz.row_offset, bool(return_activations))
+    res = (out[0], out[1], _views(out[2], model_down._sd, ENC_KEYS))
+    return res + (tuple(out[3:]),) if return_activations else res
+
+
+def grad_down(model_down, o1, ps1_mean, ps1_logvar, omega, *, stage=None, pass_=PASS_FE_DOWN, sample=0, eps=None, row_offset=None,
+              return_upstream=False):
+    """train_model_down (torchloss.py:90-98) up to the gradient -> (F_down [M], (nlogpo1, kl_div_s, kl_div_s_naive) [M] each, po1 [M,1,64,64],
+    qs1, qs1_mean, qs1_logvar [M,10], {state_dict key: d mean(F_down) / d tensor}) and, with return_upstream, (g_mean, g_logvar) [M,10]: the
+    gradient at the encoder's outputs.  The gradients are views of one flat tensor over all 32 keys of model_down in parameters() order
+    (qs_net, then po_net).  ps1_mean, ps1_logvar and omega are constants, as the reference detaches them; gamma / beta_s / beta_o are the
+    owning ActiveInferenceModel's, as in compute_loss_down, whose keys (stage, pass_, sample, row_offset, eps) this call shares: F_down and
+    its terms agree with it to rounding.  1 x 64 x 64 models only."""
+    m, e = _down_model(model_down, 'grad_down')
+    o1 = e.tensor(o1, (-1, 1, 64, 64))
+    M = o1.shape[0]
+    mode, om, sc = _omega(e, omega, M)
+    nz = m._noise(stage, pass_, sample, row_offset)
+    F, nl, kls, kln, po1, qs1, qm, qv, gm, gv, flat = e.ops.down_grad(
+        e.h, o1, e.tensor(ps1_mean, (M, m.s_dim)), e.tensor(ps1_logvar, (M, m.s_dim)), _f32(m.gamma), _f32(m.beta_s), _f32(m.beta_o),
+        mode, om, sc, m._seed64(), nz.stage, pass_, sample, nz.row_offset, _eps(m, e, eps, M, pass_, sample, nz.stage, row_offset))
+    res = (F, (nl, kls, kln), po1, qs1, qm, qv, _views(flat, model_down._sd, ENC_KEYS + DEC_HEAD_KEYS + DEC_CONVT_KEYS))
+    return res + ((gm, gv),) if return_upstream else res

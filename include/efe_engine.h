@@ -395,6 +395,40 @@ int efe_dec_tail_grad(efe_ctx*, const float* h4, const float* o1, int M, float s
 int efe_dec_grad(efe_ctx*, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
                  float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream);
 
+/* ---- gradient of F_down for all of ModelDown (csrc/train_enc.hip with the two decoder files; additive to ABI 6) --------------------------
+ * train_model_down (src/torchloss.py:90-98) up to the gradient, at the 1 x 64 x 64 geometry: the encoder qs_net evaluated for training
+ * (four stride-2 convolutions, Linear 576-256-256-256-20 with ReLU and Dropout(0.5) behind the first three, torchmodel.py:84-104, with
+ * qs_net.9.weight [256][576]) and its backward, and the composed call that adds the sample, the decoder and the KL terms.
+ * efe_param_count("qs_net") = 349 428 (0.weight, 0.bias, 2.*, 4.*, 6.*, 9.*, 12.*, 15.*, 18.*: parameters() order, each tensor row-major
+ * in the reference's shape); efe_param_count("down") = 349 428 + 4 437 697 = 4 787 125, qs_net first, then po_net as efe_dec_grad lays it
+ * out: the order torch.optim.Adam(model_down.parameters()) sees.  There is no optimiser step for these parts yet: efe_adam_step and
+ * efe_get_weights refuse both names.
+ *   efe_enc_grad  : the vector-Jacobian product of the encoder for the upstream pair g_mean, g_logvar [M,10]:
+ *                   grad [349 428] = sum_r g_mean_r . d mean_r / d parameters + g_logvar_r . d logvar_r / d parameters.
+ *                   o [M,1,64,64], g_mean, g_logvar, nz and grad are required.  nz keys the three dropout masks: the FORWARD encoder's,
+ *                   draw for draw (tag TAG_ENC + layer, global row row_offset + r, stream_id(pass, sample), stage), so efe_encoder with the
+ *                   same efe_noise encodes the same network: mean / logvar [M,10] agree with it to rounding, not bit for bit.  Optional
+ *                   outputs (NULL = not wanted): mean, logvar, the stored activations y1 [M,32,31,31], y2 [M,32,15,15], y3 [M,64,7,7],
+ *                   y4 [M,64,3,3] (NCHW, after the ReLU) and h1, h2, h3 [M,256] (after the mask), whose sign is the backward gate.
+ *   efe_down_grad : F_down and grad [4 787 125] = d mean(F_down) / d every parameter of ModelDown.  Per 64-row group: the encoder's
+ *                   training forward (o1 -> qs1_mean, qs1_logvar), qs1 = eps exp(qs1_logvar / 2) + qs1_mean (eps [M,10] injected, or
+ *                   NULL: efe_loss_down's draw under TAG_EPS), efe_dec_grad's group at scale beta_o / M, the gradient of the loss at the
+ *                   latent (g_mean, g_logvar [M,10], optional outputs; ps1_mean, ps1_logvar and omega are constants, as the reference
+ *                   detaches them), and the encoder's backward.  params: gamma, beta_s, beta_o and omega_mode EFE_OMEGA_ARRAY or
+ *                   EFE_OMEGA_SCALAR (EFE_OMEGA_DERIVED is refused).  out: F_down is required; nlogpo1, kl_s, kl_naive, po1, qs1,
+ *                   qs1_mean, qs1_logvar are optional, the other fields are not read.  F_down and its terms are efe_loss_down's
+ *                   expressions evaluated on the training forward, so they agree with efe_loss_down to rounding.  The po_net gradient,
+ *                   po1 and nlogpo1 are bit-identical to efe_dec_grad(qs1, o1, scale < 0), the qs_net gradient to efe_enc_grad on the
+ *                   returned upstream pair.
+ * Both are fixed-order sums that depend on M alone: twice the same bits; the per-row outputs depend on that row and
+ * its global row id only.  Scratch comes from the context's arena (on top of efe_dec_grad's: at most 21 MB of encoder activations and
+ * gradients per group, 32 partial gradients of 260 KB and four of 1.1 MB).  Both return 1 with a message that names the function for
+ * M <= 0, a NULL required pointer, a context of another geometry, or a split-operand option (mfma_bf16x3 / mfma_f16x2) being on. */
+int efe_enc_grad(efe_ctx*, const float* o, const float* g_mean, const float* g_logvar, int M, const efe_noise* nz, float* mean, float* logvar,
+                 float* grad, float* y1, float* y2, float* y3, float* y4, float* h1, float* h2, float* h3, void* stream);
+int efe_down_grad(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
