@@ -15,7 +15,8 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_calculate_g_rows', 'efe_simulate_rows', 'efe_mcts_step',
            'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down',
            'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top',
-           'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad']
+           'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
+           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights']
 ABI_VERSION = 6
 
 
@@ -160,5 +161,8 @@ def load():
     lib.efe_dec_grad.argtypes = [p, f32p, f32p, i, C.c_float, C.c_float, C.POINTER(EfeNoise)] + [f32p] * 11 + [p]; lib.efe_dec_grad.restype = i
     lib.efe_enc_grad.argtypes = [p, f32p, f32p, f32p, i, nzp] + [f32p] * 10 + [p]; lib.efe_enc_grad.restype = i
     lib.efe_down_grad.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, f32p, f32p, f32p, p]; lib.efe_down_grad.restype = i
+    lib.efe_train_down.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, f32p, f32p, ap, p]; lib.efe_train_down.restype = i
+    lib.efe_down_adam_step.argtypes = [p, f32p, f32p, f32p, ap, p]; lib.efe_down_adam_step.restype = i
+    lib.efe_down_get_weights.argtypes = [p, f32p, C.c_int64, p]; lib.efe_down_get_weights.restype = i
     _lib = lib
     return lib

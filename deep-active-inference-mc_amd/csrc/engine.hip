@@ -86,9 +86,16 @@ struct efe_ctx {
     int64_t mid_unfused = 0;       // option: 1 = layer-by-layer k_dense transition (A/B experiments)
     float *enc_w1 = nullptr, *enc_b1 = nullptr, *dec_wf = nullptr;
     float dec_bf = 0.f;
-    float* dec_raw = nullptr;      // the whole po_net unpacked, flat in parameters() order (kernels.h DH_*, then DT_*; part of wbufs): train_dec_head.hip reads it
+    float* dec_raw = nullptr;      // the whole po_net unpacked, flat in parameters() order (kernels.h DH_*, then DT_*): train_dec_head.hip reads it
     float* dect_raw = nullptr;     // its tail po_net.13 / .15 / .17 / .19 (= dec_raw + DEC_HEAD_P): train_dec.hip reads it
-    float* enc_raw = nullptr;      // the whole qs_net unpacked, flat in parameters() order (kernels.h EQ_*; part of wbufs): train_enc.hip reads it
+    float* enc_raw = nullptr;      // the whole qs_net unpacked, flat in parameters() order (kernels.h EQ_*): train_enc.hip reads it
+    // ModelDown's master copy at 1 x 64 x 64 (owned: it outlives a re-commit, as TrainPart::master): [DOWN_P], qs_net then po_net, so
+    // enc_raw = down_master and dec_raw = down_master + ENC_P.  An optimiser step (train_down.hip) writes it and rebuilds every packed form
+    // of the table down_repack (device; one entry per packed buffer of pack_heads / pack_encoder / pack_decoder, built at commit).
+    // down_dirty: the device copy is newer than raw["down.*"] (refresh_down_host).  dec_bf_stale: and newer than the host scalar dec_bf.
+    float* down_master = nullptr;
+    RepackDesc* down_repack = nullptr; int down_repack_n = 0, down_repack_blocks = 0;
+    bool down_dirty = false, dec_bf_stale = false;
     float* zeros = nullptr;
     std::vector<void*> owned;      // lives as long as the context
     std::vector<void*> wbufs;      // packed weights of the current commit (freed by the next one)
@@ -194,6 +201,16 @@ T* upload(efe_ctx* ctx, const std::vector<T>& v) {
     return d;
 }
 
+// a span of ModelDown's master copy (owned, allocated at the first commit of a 1 x 64 x 64 context): floats [off, off + v.size())
+float* upload_master(efe_ctx* ctx, const std::vector<float>& v, size_t off) {
+    if (!ctx->down_master) {
+        if (hipMalloc((void**)&ctx->down_master, (size_t)DOWN_P * 4) != hipSuccess) { ctx->err = "master copy: hipMalloc failed"; return nullptr; }
+        ctx->owned.push_back(ctx->down_master);
+    }
+    if (hipMemcpy(ctx->down_master + off, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "master copy: hipMemcpy failed"; return nullptr; }
+    return ctx->down_master + off;
+}
+
 const HostTensor* need(efe_ctx* ctx, const std::string& key, std::initializer_list<int64_t> shape) {
     auto it = ctx->raw.find(key);
     if (it == ctx->raw.end()) { ctx->err = "missing weight " + key; return nullptr; }
@@ -248,37 +265,20 @@ std::vector<float> convt_s2_f22_weights(const float* W, int cin, int cout) {
     for (int wr = 0; wr < 4; ++wr)
         for (int wc = 0; wc < 4; ++wc)
             for (int co = 0; co < cout; ++co)
-                for (int ci = 0; ci < cin; ++ci) {
-                    const float* k = W + ((size_t)ci * cout + co) * 9;
-                    double s = 0;
-                    for (int kh = 0; kh < 3; ++kh)
-                        for (int kw = 0; kw < 3; ++kw) s += (double)(f22_cw(wr, kh) * f22_cw(wc, kw)) * (double)k[kh * 3 + kw];
-                    U[((size_t)(4 * wr + wc) * cout + co) * cin + ci] = (float)s;
-                }
+                for (int ci = 0; ci < cin; ++ci)
+                    U[((size_t)(4 * wr + wc) * cout + co) * cin + ci] = f22_u_elem(W + ((size_t)ci * cout + co) * 9, wr, wc);
     return U;
 }
 // Winograd F(2x2, 3x3) weights of a stride-1 ConvTranspose2d(cin, cout, 3, s1, p1) (decoder.hip wino_l1): U[4 a + b][co][ci] = (G g G^T)[a][b]
 // in fp64, rounded once; g[u][v] = W[ci][co][2 - u][2 - v] (the correlation form of the stride-1 transposed conv)
 std::vector<float> convt_s1_wino_weights(const float* W, int cin, int cout) {
-    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    // G = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}} (kernels.h wino_g; wino_u_elem forms one element, as the device repack does)
     std::vector<float> U((size_t)16 * cout * cin);
     for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            const float* k = W + ((size_t)ci * cout + co) * 9;
-            double Gg[4][3];
+        for (int ci = 0; ci < cin; ++ci)
             for (int a = 0; a < 4; ++a)
-                for (int v = 0; v < 3; ++v) {
-                    double s = 0;
-                    for (int u = 0; u < 3; ++u) s += Gm[a][u] * (double)k[(2 - u) * 3 + (2 - v)];
-                    Gg[a][v] = s;
-                }
-            for (int a = 0; a < 4; ++a)
-                for (int b = 0; b < 4; ++b) {
-                    double s = 0;
-                    for (int v = 0; v < 3; ++v) s += Gg[a][v] * Gm[b][v];
-                    U[((size_t)(a * 4 + b) * cout + co) * cin + ci] = (float)s;
-                }
-        }
+                for (int b = 0; b < 4; ++b)
+                    U[((size_t)(a * 4 + b) * cout + co) * cin + ci] = wino_u_elem(W + ((size_t)ci * cout + co) * 9, a, b);
     return U;
 }
 // 16 matrices U [cout][64] for v_mfma_f32_16x16x4_f32: [U][16-channel tile ct][chunk kc][lane][s] = U[16 ct + (lane & 15)][16 kc + 4 (lane >> 4) + s]
@@ -424,6 +424,86 @@ int refresh_train_host(efe_ctx* ctx, TrainPart& tp) {
         b.assign(flat.begin() + L.b_off, flat.begin() + L.b_off + L.out);
     }
     tp.dirty = false;
+    return 0;
+}
+
+// ... and the same for ModelDown's master copy (efe_train_down / efe_down_adam_step): all 32 tensors of raw["down.*"], in parameters() order
+const char* const DOWN_KEYS[16] = {"down.qs_net.0", "down.qs_net.2", "down.qs_net.4", "down.qs_net.6", "down.qs_net.9", "down.qs_net.12", "down.qs_net.15",
+                                   "down.qs_net.18", "down.po_net.0", "down.po_net.3", "down.po_net.6", "down.po_net.9", "down.po_net.13", "down.po_net.15",
+                                   "down.po_net.17", "down.po_net.19"};
+int refresh_down_host(efe_ctx* ctx) {
+    if (!ctx->down_dirty) return 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<float> flat((size_t)DOWN_P);
+    HIPCHK(hipMemcpy(flat.data(), ctx->down_master, flat.size() * 4, hipMemcpyDeviceToHost));
+    size_t off = 0;
+    for (const char* key : DOWN_KEYS)
+        for (const char* sfx : {".weight", ".bias"}) {
+            auto it = ctx->raw.find(std::string(key) + sfx);
+            if (it == ctx->raw.end() || off + it->second.data.size() > flat.size()) return ctx->fail(std::string("master copy: no host tensor to refresh for ") + key + sfx);
+            std::vector<float>& d = it->second.data;
+            d.assign(flat.begin() + off, flat.begin() + off + d.size());
+            off += d.size();
+        }
+    if (off != flat.size()) return ctx->fail("master copy: the host tensors do not add up to the parameter count");
+    ctx->dec_bf = flat.back(); ctx->dec_bf_stale = false;
+    ctx->down_dirty = false;
+    return 0;
+}
+
+// the table k_repack_down works from (train_down.hip): one entry per packed buffer and bias table that pack_heads, pack_encoder and
+// pack_decoder fill on the 1 x 64 x 64 path, with the buffers of THIS commit; its kinds name the packers they invert
+int build_down_repack(efe_ctx* ctx) {
+    std::vector<RepackDesc> t;
+    int blocks = 0;
+    auto add = [&](float* dst, int src, int kind, int n, int out, int in, int KC, int mtiles, int row_ch = 0, int row_pos = 0, int col_ch = 0, int col_pos = 0) {
+        RepackDesc d{};
+        d.dst = dst; d.src = src; d.kind = kind; d.n = n; d.block0 = blocks; d.out = out; d.in = in; d.KC = KC; d.mtiles = mtiles;
+        d.row_ch = row_ch; d.row_pos = row_pos; d.col_ch = col_ch; d.col_pos = col_pos;
+        d.vec = (kind == RP_DENSE32 || kind == RP_DENSE16) && !col_ch && src % 4 == 0 && in % (kind == RP_DENSE32 ? 8 : 16) == 0;
+        d.swizzle = kind == RP_DENSE32 && d.vec && KC % 4 == 0;
+        blocks += (n + 255) / 256;
+        t.push_back(d);
+    };
+    auto bias = [&](float* dst, int src, int out, int n, int row_ch = 0, int row_pos = 0) { add(dst, src, RP_BIAS, n, out, 0, 0, 0, row_ch, row_pos); };
+    auto dense32 = [&](const Layer& L, int w, int b, int out, int in, int row_ch = 0, int row_pos = 0, int col_ch = 0, int col_pos = 0) {
+        add(L.Wp, w, RP_DENSE32, L.mtiles * (L.cin / 8) * 64, out, in, L.cin / 8, L.mtiles, row_ch, row_pos, col_ch, col_pos);
+        bias(L.bias, b, out, L.mtiles * 32, row_ch, row_pos);
+    };
+    auto dense16 = [&](const MlpW& net, int layer, int w, int b, int out, int in, int col_ch = 0, int col_pos = 0) {
+        const int mtiles = (out + 15) / 16, KC = (in + 15) / 16;
+        add(const_cast<float*>(reinterpret_cast<const float*>(net.w[layer])), w, RP_DENSE16, mtiles * KC * 64, out, in, KC, mtiles, 0, 0, col_ch, col_pos);
+        bias(const_cast<float*>(net.b[layer]), b, out, mtiles * 16);
+    };
+    const int D = ENC_P, T = ENC_P + DEC_HEAD_P;      // po_net and its ConvT tail inside the master copy
+    // pack_heads
+    const int dh[3][4] = {{DH_W0, DH_B0, 256, 10}, {DH_W1, DH_B1, 256, 256}, {DH_W2, DH_B2, 256, 256}};
+    const int eh[3][4] = {{EQ_W12, EQ_B12, 256, 256}, {EQ_W15, EQ_B15, 256, 256}, {EQ_W18, EQ_B18, 20, 256}};
+    for (int i = 0; i < 3; ++i) {
+        dense32(ctx->dec_fc[i], D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]); dense16(ctx->dec16, i, D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]);
+        dense32(ctx->enc_fc[i + 1], eh[i][0], eh[i][1], eh[i][2], eh[i][3]); dense16(ctx->enc16, i + 1, eh[i][0], eh[i][1], eh[i][2], eh[i][3]);
+    }
+    // pack_encoder: conv1 on the VALU, conv2 / conv3 as nine taps of the 32x32x2 form, conv4 in the 16x16x4 form, the head's first layer (columns NHWC)
+    add(ctx->enc_w1, EQ_W1, RP_TAP32, 288, 32, 1, 0, 0); bias(ctx->enc_b1, EQ_B1, 32, 32);
+    add(ctx->enc_conv[0].Wp, EQ_W2, RP_CONV32, 9 * 1 * 4 * 64, 32, 32, 4, 1); bias(ctx->enc_conv[0].bias, EQ_B2, 32, 32);
+    add(ctx->enc_conv[1].Wp, EQ_W3, RP_CONV32, 9 * 2 * 4 * 64, 64, 32, 4, 2); bias(ctx->enc_conv[1].bias, EQ_B3, 64, 64);
+    add(ctx->enc_conv[2].Wp, EQ_W4, RP_CONV16, 9 * 4 * 4 * 64, 64, 64, 4, 4); bias(ctx->enc_conv[2].bias, EQ_B4, 64, 64);
+    dense32(ctx->enc_fc[0], EQ_W9, EQ_B9, 256, 576, 0, 0, 64, 9); dense16(ctx->enc16, 0, EQ_W9, EQ_B9, 256, 576, 64, 9);
+    // pack_decoder: Linear(256, 16384) with its rows NHWC, the Winograd and F(2, 2) matrices, the final convolution (its bias: ctx->dec_bf)
+    dense32(ctx->dec_fc[3], D + DH_W3, D + DH_B3, 16384, 256, 64, 256);
+    add(ctx->dec_ct[0].Wp, T + DT_W1, RP_WINO, 16 * 2 * 8 * 64, 64, 64, 8, 2); bias(ctx->dec_ct[0].bias, T + DT_B1, 64, 64);
+    add(ctx->dec_ct[1].Wp, T + DT_W2, RP_F22, 16 * 4 * 4 * 64, 64, 64, 4, 4); bias(ctx->dec_ct[1].bias, T + DT_B2, 64, 64);
+    add(ctx->dec_ct[2].Wp, T + DT_W3, RP_F22, 16 * 2 * 4 * 64, 32, 64, 4, 2); bias(ctx->dec_ct[2].bias, T + DT_B3, 32, 32);
+    add(ctx->dec_wf, T + DT_W4, RP_TAP32, 288, 32, 1, 0, 0);
+    constexpr size_t CAP = 64;
+    if (t.size() > CAP) return ctx->fail("repack table: more entries than its buffer holds");
+    for (const RepackDesc& d : t) if (!d.dst) return ctx->fail("repack table: a packed buffer is missing");
+    if (!ctx->down_repack) {
+        HIPCHK(hipMalloc((void**)&ctx->down_repack, CAP * sizeof(RepackDesc))); ctx->owned.push_back(ctx->down_repack);
+    }
+    HIPCHK(hipMemcpy(ctx->down_repack, t.data(), t.size() * sizeof(RepackDesc), hipMemcpyHostToDevice));
+    ctx->down_repack_n = (int)t.size(); ctx->down_repack_blocks = blocks;
     return 0;
 }
 
@@ -766,6 +846,16 @@ int run_encoder_g(efe_ctx* ctx, const float* o8, int N, const NoiseCfg& nc, floa
 int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const NoiseCfg& nc, int reward0, int store0,
                 float* val /*[N], or [N][4] quarter sums when dec_split(ctx, N)*/, float* po_store, hipStream_t st) {
     if (ctx->generic) return run_decoder_g(ctx, dec_in, N, nc, reward0, store0, val, po_store, st);
+    // po_net.19.bias goes to k_dec_b4 by value: after a device-side optimiser step (efe_train_down / efe_down_adam_step) the host scalar is
+    // stale, and the first decoder pass behind the step fetches the 4 bytes on its own stream, once
+    if (ctx->dec_bf_stale) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return ctx->fail("decoder: the first pass after an optimiser step of ModelDown synchronises its stream once and cannot be captured");
+        if (hipMemcpyAsync(&ctx->dec_bf, ctx->down_master + DOWN_P - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return ctx->fail("decoder: fetching po_net.19.bias after an optimiser step failed");
+        ctx->dec_bf_stale = false;
+    }
     const DecPlan p = dec_plan(ctx, N);
     const bool split = p.split;
     // mfma_f16x2 marks a row / image whose activation overflowed fp16 with +inf, and only its own split kernels turn that into a NaN
@@ -960,6 +1050,9 @@ CtxRegistry<efe_ctx>& registry() { static auto* r = new CtxRegistry<efe_ctx>(des
 // failure, kernels maybe queued -- records done_ev behind `st`'s work, so that the next call, on any stream, can order its arena reuse behind it.
 // false: a refused handle (return code 1, efe_last_error explains) or a failed start (its message in ctx->err).
 enum class Mode { host, device, scratch };
+// what efe_last_error says of a handle that is not live, on this thread: the plain message, or (Call::refused) the one that names the entry
+// point which was just handed it; every new call scope puts the plain one back
+thread_local std::string tl_stale_msg;
 struct Call {
     CtxRegistry<efe_ctx>::Admission adm;
     efe_ctx* const ctx;
@@ -967,7 +1060,12 @@ struct Call {
     hipStream_t st;
     bool ok = false, record = false;
     Call(efe_ctx* c, Mode mode, hipStream_t stream = nullptr)
-        : adm(registry().admit(c)), ctx(adm.ctx.get()), dev(ctx ? ctx->device : -1), st(stream) { ok = ctx && !start(mode); }
+        : adm(registry().admit(c)), ctx(adm.ctx.get()), dev(ctx ? ctx->device : -1), st(stream) { tl_stale_msg.clear(); ok = ctx && !start(mode); }
+    // the return value of an entry point whose scope did not open: 1; a refused handle's message names the entry point
+    int refused(const char* who) const {
+        if (!ctx) tl_stale_msg = std::string(who) + ": stale or invalid context handle";
+        return 1;
+    }
     int start(Mode mode) {
         if (mode == Mode::scratch && !ctx->committed) return ctx->fail("weights not committed");
         if (mode != Mode::host && hipSetDevice(ctx->device) != hipSuccess) return ctx->fail("hipSetDevice failed");
@@ -1148,13 +1246,18 @@ int efe_get_device(efe_ctx* ctx, int* device, char* pci_bus_id, int pci_bus_id_l
     return 0;
 }
 
-const char* efe_last_error(efe_ctx* ctx) { return !ctx ? "null context" : registry().alive(ctx) ? ctx->err.c_str() : "stale or invalid context handle"; }
+const char* efe_last_error(efe_ctx* ctx) {
+    if (!ctx) return "null context";
+    if (registry().alive(ctx)) return ctx->err.c_str();
+    return tl_stale_msg.empty() ? "stale or invalid context handle" : tl_stale_msg.c_str();
+}
 
 int efe_set_weight(efe_ctx* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim) {
     if (!key || !data_host || !shape || ndim < 1 || ndim > 4) return 1;
     Call call(ctx, Mode::host); if (!call) return 1;
     for (TrainPart* tp : {&ctx->top_train, &ctx->mid_train})       // the other tensors of a trained part keep what was learnt
         if (tp->dirty && !strncmp(key, tp->prefix, strlen(tp->prefix)) && refresh_train_host(ctx, *tp)) return 1;
+    if (ctx->down_dirty && !strncmp(key, "down.", 5) && refresh_down_host(ctx)) return 1;
     HostTensor t;
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
@@ -1190,9 +1293,12 @@ int efe_set_option(efe_ctx* ctx, const char* name, int64_t value) {
         if (mode && ctx->generic) return ctx->fail(std::string(name) + ": the experiment covers the Dynamic-dSprites geometry only");
         // (packed from ctx->raw only while raw IS the committed set -- efe_set_weight clears `committed`, the next commit packs the planes
         // with everything else; the option is on only after every plane exists: a failure part-way leaves the experiment off, not half-enabled)
+        // A device-side step of ModelDown has made raw["down.*"] older than the master copy and has invalidated the planes (down_step clears
+        // split_packed): the host tensors follow the master copy first, so the planes are those of the trained weights.
         if (mode && ctx->committed && ctx->split_packed != mode) {
             HIPCHK(hipSetDevice(ctx->device));
             HIPCHK(hipDeviceSynchronize());             // work that still reads the other mode's planes
+            if (refresh_down_host(ctx)) return 1;
             if (pack_fc4_b3(ctx, mode)) { ctx->mfma_bf16x3 = 0; return 1; }
         }
         ctx->mfma_bf16x3 = mode;
@@ -1277,7 +1383,7 @@ static int pack_encoder(efe_ctx* ctx) {
             flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
         }
         if (flat.size() != (size_t)ENC_P) return ctx->fail("encoder: unexpected parameter count");
-        if (!(ctx->enc_raw = upload(ctx, flat))) return 1;
+        if (!(ctx->enc_raw = upload_master(ctx, flat, 0))) return 1;
     }
     if (ctx->generic) {     // build-defined geometry: four k_conv_g layers ...
         for (int i = 0; i < 4; ++i) if (pack_conv(ctx, ctx->g_enc[i], enc_conv_layer(i, C), false)) return 1;
@@ -1338,7 +1444,7 @@ static int pack_decoder(efe_ctx* ctx) {
             flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
         }
         if (flat.size() != (size_t)DEC_P) return ctx->fail("decoder tail: unexpected parameter count");
-        if (!(ctx->dec_raw = upload(ctx, flat))) return 1;
+        if (!(ctx->dec_raw = upload_master(ctx, flat, ENC_P))) return 1;
         ctx->dect_raw = ctx->dec_raw + DEC_HEAD_P;
     }
     {   // Unflatten(1, (64, B, B)) is channel-major c*B*B + p (torchmodel.py:119); the layer emits NHWC p*64 + c directly
@@ -1370,7 +1476,7 @@ static int pack_decoder(efe_ctx* ctx) {
     std::vector<float> wf(288);                         // [tap][ci]
     for (int t = 0; t < 9; ++t) for (int ci = 0; ci < 32; ++ci) wf[t * 32 + ci] = tf.W()[ci * 9 + t];
     if (!(ctx->dec_wf = upload(ctx, wf))) return 1;
-    ctx->dec_bf = tf.B()[0];
+    ctx->dec_bf = tf.B()[0]; ctx->dec_bf_stale = false;
     return 0;
 }
 
@@ -1386,8 +1492,10 @@ int efe_commit_weights(efe_ctx* ctx) {
     }
     ctx->committed = false;
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first
-    if (refresh_train_host(ctx, ctx->top_train) || refresh_train_host(ctx, ctx->mid_train)) return 1;
+    if (refresh_train_host(ctx, ctx->top_train) || refresh_train_host(ctx, ctx->mid_train) || refresh_down_host(ctx)) return 1;
     if (pack_top(ctx) || pack_mid(ctx) || pack_heads(ctx) || pack_encoder(ctx) || pack_decoder(ctx)) return 1;
+    ctx->down_repack_n = 0;
+    if (!ctx->generic && ctx->enc_raw && ctx->dec_raw && build_down_repack(ctx)) return 1;
     // the host copies stay: a caller may update a single tensor with efe_set_weight and commit again
     ctx->committed = true;
     return 0;
@@ -1597,12 +1705,13 @@ TrainPart* train_part(efe_ctx* ctx, const char* part, const char* who) {
     ctx->fail(std::string(who) + ": part must be \"top\" (habit net) or \"ps_net\" (transition net), the trainable parts");
     return nullptr;
 }
-int adam_args(efe_ctx* ctx, const TrainPart& tp, const efe_adam_params* hp, AdamArgs& a, const char* who) {
+// (tp == nullptr: the scalars alone, for ModelDown's step, which has no layer table)
+int adam_args(efe_ctx* ctx, const TrainPart* tp, const efe_adam_params* hp, AdamArgs& a, const char* who) {
     if (!hp || hp->step < 1 || !(hp->lr >= 0.0) || !(hp->beta1 >= 0.0 && hp->beta1 < 1.0) || !(hp->beta2 >= 0.0 && hp->beta2 < 1.0) || !(hp->eps >= 0.0))
         return ctx->fail(std::string(who) + ": bad hyper-parameters (step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0)");
     // torch.optim.Adam's scalars, in double as Python computes them, rounded once
     const double bc1 = 1.0 - std::pow(hp->beta1, (double)hp->step), bc2 = 1.0 - std::pow(hp->beta2, (double)hp->step);
-    a.net = tp.net_dev;
+    a.net = tp ? tp->net_dev : nullptr;
     a.omb1 = (float)(1.0 - hp->beta1); a.b2 = (float)hp->beta2; a.omb2 = (float)(1.0 - hp->beta2);
     a.bc2_sqrt = (float)std::sqrt(bc2); a.step_size = (float)(hp->lr / bc1); a.eps = (float)hp->eps;
     return 0;
@@ -1685,7 +1794,7 @@ int efe_adam_step(efe_ctx* ctx, const char* part, const float* grad, float* exp_
     if (!grad || !exp_avg || !exp_avg_sq) return ctx->fail("efe_adam_step: grad, exp_avg and exp_avg_sq must be non-NULL");
     TrainPart* tp = train_part(ctx, part, "efe_adam_step"); if (!tp) return 1;
     AdamArgs a{};
-    if (adam_args(ctx, *tp, hp, a, "efe_adam_step")) return 1;
+    if (adam_args(ctx, tp, hp, a, "efe_adam_step")) return 1;
     a.g = grad; a.nslab = 1; a.m = exp_avg; a.v = exp_avg_sq;
     tp->dirty = true;
     launch_adam(a, tp->net.P, st);
@@ -1699,7 +1808,7 @@ int efe_train_top(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, flo
         return ctx->fail("efe_train_top: bad arguments (s, log_Ppi, exp_avg and exp_avg_sq must be non-NULL, M >= 1)");
     TrainPart& tp = ctx->top_train;
     AdamArgs a{};
-    if (adam_args(ctx, tp, hp, a, "efe_train_top")) return 1;
+    if (adam_args(ctx, &tp, hp, a, "efe_train_top")) return 1;
     a.m = exp_avg; a.v = exp_avg_sq;
     if (grad_or_step(ctx, tp, train_slabs(M), nullptr, &a, st, [&](float* slabs) {
             launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st); })) return 1;
@@ -1723,7 +1832,7 @@ int efe_train_mid(efe_ctx* ctx, const float* s0, const float* pi0, const float* 
     if (mid_grad_args(ctx, s0, pi0, qs1_mean, qs1_logvar, M, params, nz, ps1_mean, ps1_logvar, F_mid, exp_avg && exp_avg_sq, g, "efe_train_mid")) return 1;
     TrainPart& tp = ctx->mid_train;
     AdamArgs a{};
-    if (adam_args(ctx, tp, hp, a, "efe_train_mid")) return 1;
+    if (adam_args(ctx, &tp, hp, a, "efe_train_mid")) return 1;
     a.m = exp_avg; a.v = exp_avg_sq;
     if (grad_or_step(ctx, tp, train_mid_slabs(M), nullptr, &a, st, [&](float* slabs) { g.slabs = slabs; launch_mid_grad(g, st); })) return 1;
     return call.finish();
@@ -1904,16 +2013,19 @@ int efe_enc_grad(efe_ctx* ctx, const float* o, const float* g_mean, const float*
     return call.finish();
 }
 
-int efe_down_grad(efe_ctx* ctx, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
-                  const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream) {
-    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    if (M <= 0) return ctx->fail("efe_down_grad: M must be >= 1");
+namespace {
+// efe_down_grad inside its call scope, for efe_train_down too (`who` names the entry point in the messages; grad: the caller's array, or the
+// training call's scratch).  Every refusal comes before the first launch.
+int down_grad_run(efe_ctx* ctx, const char* who, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, hipStream_t st) {
+    const std::string w(who);
+    if (M <= 0) return ctx->fail(w + ": M must be >= 1");
     if (!o1 || !ps1_mean || !ps1_logvar || !nz || !out || !grad)
-        return ctx->fail("efe_down_grad: o1, ps1_mean, ps1_logvar, params, nz, out and grad must be non-NULL");
-    if (fe_params(ctx, params, false, "efe_down_grad")) return 1;
-    if (!out->F_down) return ctx->fail("efe_down_grad: out->F_down is required");
+        return ctx->fail(w + ": o1, ps1_mean, ps1_logvar, params, nz, out and grad must be non-NULL");
+    if (fe_params(ctx, params, false, who)) return 1;
+    if (!out->F_down) return ctx->fail(w + ": out->F_down is required");
     EncGrad e;
-    if (e.open(ctx, "efe_down_grad", o1, M, nz, out->qs1_mean, out->qs1_logvar, grad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return 1;
+    if (e.open(ctx, who, o1, M, nz, out->qs1_mean, out->qs1_logvar, grad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return 1;
     float* qs1 = out->qs1 ? out->qs1 : ctx->allocT<float>((size_t)M * S_DIM);
     float* d_s = ctx->allocT<float>((size_t)M * S_DIM);
     float* nl = out->nlogpo1 ? out->nlogpo1 : ctx->allocT<float>((size_t)M);
@@ -1923,7 +2035,7 @@ int efe_down_grad(efe_ctx* ctx, const float* o1, const float* ps1_mean, const fl
     e.g_mean = gm; e.g_logvar = gv;
     const DecHeadIO hd{qs1, nz, d_s, nullptr, nullptr, nullptr, nullptr};
     DecGrad d;
-    if (d.open(ctx, "efe_down_grad", &hd, nullptr, nullptr, o1, M, -1.0f, params->beta_o, nl, out->po1, grad + ENC_P, nullptr, nullptr, nullptr, st)) return 1;
+    if (d.open(ctx, who, &hd, nullptr, nullptr, o1, M, -1.0f, params->beta_o, nl, out->po1, grad + ENC_P, nullptr, nullptr, nullptr, st)) return 1;
     const float* omega = params->omega_mode == EFE_OMEGA_ARRAY ? params->omega : nullptr;
     // F_down and its terms: k_fe_down's expressions on the training forward's po1, mean and logvar (nlogpo1 is the decoder group's own)
     efe_fe_out fo{};
@@ -1949,6 +2061,66 @@ int efe_down_grad(efe_ctx* ctx, const float* o1, const float* ps1_mean, const fl
     }
     d.close();
     e.close();
+    return 0;
+}
+
+// ModelDown's optimiser step (train_down.hip): the 1 x 64 x 64 geometry, exact fp32 planes only, sane hyper-parameters
+int down_step_args(efe_ctx* ctx, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, DownAdamArgs& a, const char* who) {
+    const std::string w(who);
+    if (!exp_avg || !exp_avg_sq) return ctx->fail(w + ": exp_avg and exp_avg_sq must be non-NULL");
+    if (ctx->chan != 1 || ctx->res != 64 || !ctx->down_master || !ctx->down_repack_n) return ctx->fail(w + ": built for the 1 x 64 x 64 geometry only");
+    if (ctx->mfma_bf16x3) return ctx->fail(w + ": not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+    AdamArgs s{};
+    if (adam_args(ctx, nullptr, hp, s, who)) return 1;
+    a.m = exp_avg; a.v = exp_avg_sq; a.w = ctx->down_master; a.P = DOWN_P;
+    a.omb1 = s.omb1; a.b2 = s.b2; a.omb2 = s.omb2; a.bc2_sqrt = s.bc2_sqrt; a.step_size = s.step_size; a.eps = s.eps;
+    return 0;
+}
+// the update, then every packed forward form from the new raw copy; the host tensors and the host's copy of po_net.19.bias are stale from here,
+// and so are split-operand planes left from a time the option was on (it is off now: down_step_args): marked unpacked, so that turning
+// the option on again packs them from the trained weights (efe_set_option)
+void down_step(efe_ctx* ctx, const DownAdamArgs& a, hipStream_t st) {
+    ctx->down_dirty = true; ctx->dec_bf_stale = true; ctx->split_packed = 0;
+    launch_adam_down(a, st);
+    launch_repack_down(ctx->down_repack, ctx->down_repack_n, ctx->down_repack_blocks, ctx->down_master, st);
+}
+}  // namespace
+
+int efe_down_grad(efe_ctx* ctx, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                  const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (down_grad_run(ctx, "efe_down_grad", o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, g_mean, g_logvar, grad, st)) return 1;
+    return call.finish();
+}
+
+int efe_train_down(efe_ctx* ctx, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                   const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_train_down");
+    DownAdamArgs a{};
+    if (down_step_args(ctx, exp_avg, exp_avg_sq, hp, a, "efe_train_down")) return 1;
+    float* grad = ctx->allocT<float>((size_t)DOWN_P);
+    if (!grad) return 1;
+    if (down_grad_run(ctx, "efe_train_down", o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, nullptr, nullptr, grad, st)) return 1;
+    a.g = grad;
+    down_step(ctx, a, st);
+    return call.finish();
+}
+
+int efe_down_adam_step(efe_ctx* ctx, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_down_adam_step");
+    if (!grad) return ctx->fail("efe_down_adam_step: grad must be non-NULL");
+    DownAdamArgs a{};
+    if (down_step_args(ctx, exp_avg, exp_avg_sq, hp, a, "efe_down_adam_step")) return 1;
+    a.g = grad;
+    down_step(ctx, a, st);
+    return call.finish();
+}
+
+int efe_down_get_weights(efe_ctx* ctx, float* dst, int64_t n, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_down_get_weights");
+    if (ctx->chan != 1 || ctx->res != 64 || !ctx->down_master) return ctx->fail("efe_down_get_weights: built for the 1 x 64 x 64 geometry only");
+    if (!dst || n != DOWN_P) return ctx->fail("efe_down_get_weights: dst must hold efe_param_count(\"down\") floats");
+    HIPCHK(hipMemcpyAsync(dst, ctx->down_master, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return call.finish();
 }
 

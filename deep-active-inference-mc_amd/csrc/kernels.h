@@ -126,6 +126,30 @@ __host__ __device__ constexpr int f22_wt(int p) { return p < 2 ? 0 : p - 1; }
 __host__ __device__ constexpr int f22_o0(int p) { return p < 2 ? 0 : (p < 4 ? 1 : 3); }
 __host__ __device__ constexpr int f22_o1(int p) { return p == 1 ? 2 : (p == 3 ? 3 : -1); }
 __host__ __device__ constexpr int f22_cw(int wt, int k) { return wt == 0 ? (k == 1) : wt == 1 ? (k == 2) : wt == 2 ? (k != 1) : (k == 0); }
+// One element of the transformed weights, shared by the host packers (engine.hip convt_s2_f22_weights / convt_s1_wino_weights) and the
+// device repack (train_down.hip): k = the nine taps W[ci][co][.][.] of one (ci, co) pair; fp64 in this order, rounded once.
+//   F(2, 2), stride-2 ConvT: U[4 wr + wc] = sum_{kh, kw} f22_cw(wr, kh) f22_cw(wc, kw) k[kh][kw]
+__host__ __device__ inline float f22_u_elem(const float* k, int wr, int wc) {
+#pragma clang fp contract(off)
+    double s = 0;
+    for (int kh = 0; kh < 3; ++kh)
+        for (int kw = 0; kw < 3; ++kw) s += (double)(f22_cw(wr, kh) * f22_cw(wc, kw)) * (double)k[kh * 3 + kw];
+    return (float)s;
+}
+//   Winograd F(2x2, 3x3), stride-1 ConvT: U[4 a + b] = (G g G^T)[a][b], g[u][v] = k[2 - u][2 - v], G = wino_g
+__host__ __device__ constexpr double wino_g(int a, int u) { return a == 0 ? (u == 0 ? 1.0 : 0.0) : a == 1 ? 0.5 : a == 2 ? (u == 1 ? -0.5 : 0.5) : (u == 2 ? 1.0 : 0.0); }
+__host__ __device__ inline float wino_u_elem(const float* k, int a, int b) {
+#pragma clang fp contract(off)
+    double Gg[3];
+    for (int v = 0; v < 3; ++v) {
+        double s = 0;
+        for (int u = 0; u < 3; ++u) s += wino_g(a, u) * (double)k[(2 - u) * 3 + (2 - v)];
+        Gg[v] = s;
+    }
+    double s = 0;
+    for (int v = 0; v < 3; ++v) s += Gg[v] * wino_g(b, v);
+    return (float)s;
+}
 
 struct DecBArgs {
     const float* y2;
@@ -418,6 +442,18 @@ struct AdamArgs {
     float bc2_sqrt, step_size, eps;      // sqrt(1 - beta2^t), lr / (1 - beta1^t)
 };
 void launch_adam(const AdamArgs& a, int P, hipStream_t st);
+// torch.optim.Adam, default flags (no amsgrad, no weight decay, not maximize), one element, in this order:
+//   m = m + (1 - b1) (g - m);  v = b2 v + (1 - b2) g g;  denom = sqrt(v) / sqrt(1 - b2^t) + eps;  w = w + (-(lr / (1 - b1^t)) m) / denom
+// Contraction off, division and square root correctly rounded; the bias corrections come from the host (double, rounded once).  Shared by
+// k_adam (train.hip) and k_adam_down (train_down.hip).
+__device__ __forceinline__ void adam_update(float g, float& m, float& v, float& wv, float omb1, float b2, float omb2, float bc2_sqrt, float step_size,
+                                            float eps) {
+#pragma clang fp contract(off)
+    m = m + omb1 * (g - m);
+    v = b2 * v + (omb2 * g) * g;
+    const float denom = __fdiv_rn(__fsqrt_rn(v), bc2_sqrt) + eps;
+    wv = wv + __fdiv_rn(-step_size * m, denom);        // addcdiv_(m, denom, value = -step_size): (value * m) / denom
+}
 // the transition net ModelMid.ps_net (k_mid_grad): hidden layers up to TRAIN_MID_WIDTH wide, each ReLU + MC-dropout; one partial-gradient
 // slab is 2.17 MB (P = 543 252 at pi_dim 4), so the workgroup count has a cap of its own
 constexpr int TRAIN_MID_WIDTH = 512;     // widest hidden activation k_mid_grad keeps in LDS
@@ -525,6 +561,35 @@ struct DownLatentArgs {
     TrainKey key;
 };
 void launch_down_latent(const DownLatentArgs& a, hipStream_t st);
+
+// ---- the optimiser step of ModelDown at 1 x 64 x 64 (train_down.hip): Adam over the flat [DOWN_P] vector, then the packed forms again ------
+struct DownAdamArgs {
+    const float* g;                      // gradient [P], already slab-summed
+    float *m, *v, *w;                    // exp_avg, exp_avg_sq, the raw master copy [P]
+    int P;
+    float omb1, b2, omb2, bc2_sqrt, step_size, eps;      // as AdamArgs
+};
+void launch_adam_down(const DownAdamArgs& a, hipStream_t st);
+// One packed buffer of the forward paths as k_repack_down rebuilds it from the raw copy: the inverse of the host packer named per kind
+// (engine.hip).  n = owning threads: destination floats (RP_BIAS, RP_TAP32) or destination float4s (the fragment forms).
+enum RepackKind {
+    RP_BIAS,        // bias padded with zeros to n (upload_layer / pack_linear16), rows optionally permuted
+    RP_TAP32,       // [tap][32] of a [32][9] tensor: the encoder's conv1, the decoder's final convolution
+    RP_DENSE32,     // pack_linear -> upload_packed: 32x32x2 fragment order, rows / columns optionally permuted
+    RP_DENSE16,     // pack_linear16: 16x16x4 fragment order, columns optionally permuted
+    RP_CONV32,      // pack_conv (Conv2d): nine taps of the 32x32x2 form
+    RP_CONV16,      // the encoder's conv4 in the 16x16x4 form
+    RP_WINO,        // convt_s1_wino_weights as 16 taps of the 32x32x2 form
+    RP_F22          // pack_u16x16x4(convt_s2_f22_weights)
+};
+struct RepackDesc {
+    float* dst; int src;                 // the packed buffer; offset of the source tensor in the raw copy
+    int kind, n, block0;                 // RepackKind; owning threads; the first workgroup of this entry (256 threads each)
+    int out, in, KC, mtiles;             // the tensor's rows / columns (Cout / Cin); K chunks and row tiles of the packed form
+    int row_ch, row_pos, col_ch, col_pos;      // nhwc_perm(channels, positions) of the rows / columns (channels 0: none)
+    int vec, swizzle;                    // a lane's four source floats are one aligned float4; the 128-B-segment thread order (train_down.hip)
+};
+void launch_repack_down(const RepackDesc* table, int n, int blocks, const float* w, hipStream_t st);
 
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);

@@ -548,6 +548,39 @@ std::vector<Tensor> down_grad(int64_t h, const Tensor& o1_, const Tensor& pm_, c
     return {F, nl, kls, kln, po1, qs1, qm, qv, gm, gv, grad};
 }
 
+// train_model_down, torchloss.py:90-98 (csrc/train_down.hip behind the gradient) -> (F_down, nlogpo1, kl_s, kl_naive [M]) of the weights before the step
+std::vector<Tensor> train_down(int64_t h, const Tensor& o1_, const Tensor& pm_, const Tensor& pv_, double gamma, double beta_s, double beta_o, int64_t omega_mode,
+                               const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample, int64_t row_offset,
+                               const OptT& eps, Tensor exp_avg, Tensor exp_avg_sq, double lr, double beta1, double beta2, double aeps, int64_t step) {
+    efe_ctx* c = CTX(h);
+    Tensor o1 = in(o1_, "o1"), pm = in(pm_, "ps1_mean"), pv = in(pv_, "ps1_logvar"), ok_, ek;
+    const int M = rows(o1, 4096, "o1");
+    TORCH_CHECK(pm.numel() == (int64_t)M * 10 && pv.numel() == (int64_t)M * 10, "efe: ps1_mean and ps1_logvar must be [M, 10]");
+    const int64_t NP = efe_param_count(c, "down");
+    TORCH_CHECK(NP > 0, "efe engine: ", efe_last_error(c));
+    efe_fe_params p = fe_params(gamma, beta_s, beta_o, omega_mode, omega, ok_, omega_scalar, M);
+    auto op = o1.options();
+    Tensor F = at::empty({M}, op), nl = at::empty({M}, op), kls = at::empty({M}, op), kln = at::empty({M}, op);
+    efe_fe_out out{};
+    out.F_down = P(F); out.nlogpo1 = P(nl); out.kl_s = P(kls); out.kl_naive = P(kln);
+    efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    const efe_adam_params hp = adam_params(lr, beta1, beta2, aeps, step);
+    ok(c, efe_train_down(c, o1.data_ptr<float>(), pm.data_ptr<float>(), pv.data_ptr<float>(), M, &p, &nz, optp(eps, ek, "eps", (int64_t)M * 10), &out,
+                         state(exp_avg, "exp_avg", NP), state(exp_avg_sq, "exp_avg_sq", NP), &hp, stream_of(o1)));
+    return {F, nl, kls, kln};
+}
+
+// torch.optim.Adam.step() of ModelDown with the caller's gradient and state, and the packed forward forms rebuilt
+void down_adam_step(int64_t h, const Tensor& grad_, Tensor exp_avg, Tensor exp_avg_sq, double lr, double beta1, double beta2, double eps, int64_t step) {
+    efe_ctx* c = CTX(h);
+    const int64_t NP = efe_param_count(c, "down");
+    TORCH_CHECK(NP > 0, "efe engine: ", efe_last_error(c));
+    Tensor grad = in(grad_, "grad");
+    TORCH_CHECK(grad.numel() == NP, "efe: grad has ", grad.numel(), " elements, ModelDown has ", NP, " parameters");
+    const efe_adam_params hp = adam_params(lr, beta1, beta2, eps, step);
+    ok(c, efe_down_adam_step(c, grad.data_ptr<float>(), state(exp_avg, "exp_avg", NP), state(exp_avg_sq, "exp_avg_sq", NP), &hp, stream_of(grad)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -575,6 +608,8 @@ TORCH_LIBRARY(efe, m) {
     m.def("dec_grad(int ctx, Tensor s, Tensor o1, float scale, float beta_o, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
     m.def("enc_grad(int ctx, Tensor o, Tensor d_mean, Tensor d_logvar, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
     m.def("down_grad(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> Tensor[]");
+    m.def("train_down(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float adam_eps, int step) -> Tensor[]");
+    m.def("down_adam_step(int ctx, Tensor grad, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -602,4 +637,6 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("dec_grad", &dec_grad);
     m.impl("enc_grad", &enc_grad);
     m.impl("down_grad", &down_grad);
+    m.impl("train_down", &train_down);
+    m.impl("down_adam_step", &down_adam_step);
 }

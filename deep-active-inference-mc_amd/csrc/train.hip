@@ -440,9 +440,8 @@ __global__ void __launch_bounds__(256) k_slab_sum(const float* slabs, int nslab,
     if (i < P) grad[i] = slab_sum(slabs, nslab, P, i);
 }
 
-// torch.optim.Adam, default flags (no amsgrad, no weight decay, not maximize), per element and in this order:
-//   m = m + (1 - b1) (g - m);  v = b2 v + (1 - b2) g g;  denom = sqrt(v) / sqrt(1 - b2^t) + eps;  w = w + (-(lr / (1 - b1^t)) m) / denom
-// Contraction off, division and square root correctly rounded; the bias corrections come from the host (double, rounded once).
+// torch.optim.Adam, default flags (no amsgrad, no weight decay, not maximize), per element: kernels.h adam_update (shared with
+// train_down.hip's k_adam_down), then the element's two packed forward copies.
 __global__ void __launch_bounds__(256) k_adam(const AdamArgs a) {
 #pragma clang fp contract(off)
     const TrainNet& net = *a.net;
@@ -450,10 +449,7 @@ __global__ void __launch_bounds__(256) k_adam(const AdamArgs a) {
     if (i >= P) return;
     const float g = slab_sum(a.g, a.nslab, P, i);
     float m = a.m[i], v = a.v[i], wv = net.master[i];
-    m = m + a.omb1 * (g - m);
-    v = a.b2 * v + (a.omb2 * g) * g;
-    const float denom = __fdiv_rn(__fsqrt_rn(v), a.bc2_sqrt) + a.eps;
-    wv = wv + __fdiv_rn(-a.step_size * m, denom);        // addcdiv_(m, denom, value = -step_size): (value * m) / denom
+    adam_update(g, m, v, wv, a.omb1, a.b2, a.omb2, a.bc2_sqrt, a.step_size, a.eps);
     a.m[i] = m; a.v[i] = v; net.master[i] = wv;
     // the packed forward copies: inverses of upload_packed ([mtile 32][kc 8][lane = co % 32 + 32 (ci % 8 / 4)][ci % 4]) and
     // pack_linear16 ([mtile 16][kc 16][lane = co % 16 + 16 (ci % 16 / 4)][ci % 4]) of engine.hip

@@ -5,15 +5,15 @@ composition train.py:104-123 evaluates before its optimizer steps, in one engine
 No autograd graph is built.  The habit network and the transition network are trainable: `train_model_top` (torchloss.py:65-74) and
 `train_model_mid` (torchloss.py:76-88) are each one Adam step on the device (csrc/train.hip: backward + update in two launches, with a
 daimc_amd.Adam holding the state), and `grad_top` / `grad_mid` return the gradients.  `train_model_down` (torchloss.py:90-98, the encoder /
-decoder) is built up to the gradient: `grad_down` returns F_down and d mean(F_down) / d every parameter of ModelDown (qs_net, then
+decoder, 1 x 64 x 64 models) is one engine call too: the gradient, Adam over the 4 787 125 parameters, and every packed forward form of
+po_net and the encoder rebuilt on the device (csrc/train_down.hip).  `grad_down` returns F_down and d mean(F_down) / d every parameter of ModelDown (qs_net, then
 po_net: the order an Adam over model_down.parameters() sees) in one engine call -- per 64-row group the encoder evaluated for training
 with the forward encoder's three dropout masks (csrc/train_enc.hip), the sample, the decoder's forward and backward, the gradient of the
 reconstruction and KL terms at the latent, and the encoder's backward.  Its pieces run on their own: `grad_encoder` is the encoder's
 vector-Jacobian product for a given upstream pair, `grad_decoder` the gradient of the reconstruction term with respect to every
 parameter of po_net and to s -- the dense head po_net.0 / .3 / .6 / .9 evaluated for training with the forward decoder's four dropout
 masks (csrc/train_dec_head.hip), then the four ConvTranspose2d layers (po_net.13 / .15 / .17 / .19, csrc/train_dec.hip), which
-`grad_decoder_convs` also runs from a given Unflatten input.  The optimiser step for ModelDown (with the repack of the forward forms of
-po_net and the encoder trunk on the device) and train_model_down itself are still missing, and a training loop is out of scope.  Every
+`grad_decoder_convs` also runs from a given Unflatten input.  A training loop on the device is out of scope.  Every
 call dispatches through torch.ops.efe.* on the model's device; there is no CPU fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
@@ -231,7 +231,7 @@ def grad_decoder_convs(model_down, h4, o1, *, scale=None, return_activations=Fal
         raise ValueError('grad_decoder_convs: scale must be >= 0 (None = beta_o / M)')
     nl, po1, d_h4, flat, y1, y2, y3 = e.ops.dec_tail_grad(e.h, h4, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o),
                                                           bool(return_activations))
-    out = (nl, po1, d_h4, _views(flat, model_down._sd, DEC_CONVT_KEYS))
+    out = (nl, po1, d_h4, _views(flat, model_down._sd_host, DEC_CONVT_KEYS))
     return out + ((y1, y2, y3),) if return_activations else out
 
 
@@ -258,7 +258,7 @@ def grad_decoder(model_down, s, o1, *, scale=None, stage=None, pass_=PASS_FE_DOW
     out = e.ops.dec_grad(e.h, s, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o), m._seed64(), nz.stage, pass_, sample,
                          nz.row_offset, bool(return_activations))
     nl, po1, d_s, flat = out[:4]
-    res = (nl, po1, d_s, _views(flat, model_down._sd, DEC_HEAD_KEYS + DEC_CONVT_KEYS))
+    res = (nl, po1, d_s, _views(flat, model_down._sd_host, DEC_HEAD_KEYS + DEC_CONVT_KEYS))
     return res + (tuple(out[4:]),) if return_activations else res
 
 
@@ -285,7 +285,7 @@ def grad_encoder(model_down, o, d_mean, d_logvar, *, stage=None, pass_=PASS_FE_D
     nz = m._noise(stage, pass_, sample, row_offset)
     out = e.ops.enc_grad(e.h, o, e.tensor(d_mean, (M, m.s_dim)), e.tensor(d_logvar, (M, m.s_dim)), m._seed64(), nz.stage, pass_, sample,
                          nz.row_offset, bool(return_activations))
-    res = (out[0], out[1], _views(out[2], model_down._sd, ENC_KEYS))
+    res = (out[0], out[1], _views(out[2], model_down._sd_host, ENC_KEYS))
     return res + (tuple(out[3:]),) if return_activations else res
 
 
@@ -305,5 +305,29 @@ def grad_down(model_down, o1, ps1_mean, ps1_logvar, omega, *, stage=None, pass_=
     F, nl, kls, kln, po1, qs1, qm, qv, gm, gv, flat = e.ops.down_grad(
         e.h, o1, e.tensor(ps1_mean, (M, m.s_dim)), e.tensor(ps1_logvar, (M, m.s_dim)), _f32(m.gamma), _f32(m.beta_s), _f32(m.beta_o),
         mode, om, sc, m._seed64(), nz.stage, pass_, sample, nz.row_offset, _eps(m, e, eps, M, pass_, sample, nz.stage, row_offset))
-    res = (F, (nl, kls, kln), po1, qs1, qm, qv, _views(flat, model_down._sd, ENC_KEYS + DEC_HEAD_KEYS + DEC_CONVT_KEYS))
+    res = (F, (nl, kls, kln), po1, qs1, qm, qv, _views(flat, model_down._sd_host, ENC_KEYS + DEC_HEAD_KEYS + DEC_CONVT_KEYS))
     return res + ((gm, gv),) if return_upstream else res
+
+
+def train_model_down(model_down, o1, ps1_mean, ps1_logvar, omega, optimizer, *, stage=None, pass_=PASS_FE_DOWN, sample=0, eps=None,
+                     row_offset=None):
+    """torchloss.py:90-98: one optimiser step of the encoder and decoder on F_down.mean() -> (F_down [M], (nlogpo1, kl_div_s, kl_div_s_naive)
+    [M] each) of the weights before the step.  One engine call (efe_train_down): grad_down's row groups, Adam over all 32 tensors, and
+    every packed forward form rebuilt on the device, with no host synchronisation.  optimizer: a daimc_amd.Adam over this model_down.
+    Bit-identical to grad_down followed by optimizer.step(grads).  1 x 64 x 64 models only."""
+    if getattr(optimizer, '_module', None) is not model_down:
+        raise ValueError('train_model_down: optimizer must be a daimc_amd.Adam over this model_down')
+    m, e = _down_model(model_down, 'train_model_down')
+    o1 = e.tensor(o1, (-1, 1, 64, 64))
+    M = o1.shape[0]
+    mode, om, sc = _omega(e, omega, M)
+    nz = m._noise(stage, pass_, sample, row_offset)
+    ea, es = optimizer._buffers()
+    hyper = optimizer._hyper()
+    F, nl, kls, kln = e.ops.train_down(
+        e.h, o1, e.tensor(ps1_mean, (M, m.s_dim)), e.tensor(ps1_logvar, (M, m.s_dim)), _f32(m.gamma), _f32(m.beta_s), _f32(m.beta_o),
+        mode, om, sc, m._seed64(), nz.stage, pass_, sample, nz.row_offset, _eps(m, e, eps, M, pass_, sample, nz.stage, row_offset),
+        ea, es, *hyper, optimizer._step + 1)
+    optimizer._step += 1
+    model_down._stepped()
+    return F, (nl, kls, kln)

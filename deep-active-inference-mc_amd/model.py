@@ -170,6 +170,9 @@ class _TrainableModule(_Module):
         self._sd_host = sd
         self._device_newer = False
 
+    def _get_weights(self, e, part, buf, P):
+        return e.lib.efe_get_weights(e.ctx, part, _ptr(buf), P, e.stream())
+
     def _download(self):
         """efe_get_weights: the device master copy (flat, parameters() order) -> the host state_dict"""
         e = self._owner._engine
@@ -177,7 +180,7 @@ class _TrainableModule(_Module):
         P = int(e.lib.efe_param_count(e.ctx, part))
         buf = e.empty(P)
         with torch.cuda.device(e.device):
-            e.check(e.lib.efe_get_weights(e.ctx, part, _ptr(buf), P, e.stream()))
+            e.check(self._get_weights(e, part, buf, P))
             flat = buf.cpu()
         new, off = {}, 0
         for key, t in self._sd_host.items():
@@ -241,9 +244,15 @@ class ModelMid(_TrainableModule):
         return mean, logvar
 
 
-class ModelDown(_Module):
+class ModelDown(_TrainableModule):
     """torchmodel.py:69-146 (resolution 64, 1 colour channel; the first encoder Linear takes the 576
-    features the conv trunk actually emits -- SURVEY appendix C)."""
+    features the conv trunk actually emits -- SURVEY appendix C).  Encoder and decoder are trainable on the device at 1 x 64 x 64
+    (loss.train_model_down); the optimiser step has C entry points of its own (efe_down_adam_step / efe_down_get_weights: it also
+    rebuilds the packed forward forms), so the string-part calls still refuse "down"."""
+    _train_part = 'down'
+
+    def _get_weights(self, e, part, buf, P):
+        return e.lib.efe_down_get_weights(e.ctx, _ptr(buf), P, e.stream())
 
     def __init__(self, owner):
         super().__init__(owner, 'down')
@@ -499,7 +508,8 @@ class ActiveInferenceModel:
 
     def _load_optimizers(self, folder_chp):
         """optimizers.pkl -> {name: daimc_amd.Adam} for every entry over a part the engine trains: one group of six parameters is the
-        habit net's, of eight the transition net's (entries of other parts stay in the file).  The reference's own loader
+        habit net's, of eight the transition net's, of 32 the encoder / decoder's (1 x 64 x 64 models; entries of other parts stay in the
+        file).  The reference's own loader
         (torchmodel.py:197-203) reads the pickle twice and always lands in its bare `except`, i.e. it restarts every optimiser; this one
         restores them."""
         path = f'{folder_chp}/optimizers.pkl'
@@ -508,7 +518,8 @@ class ActiveInferenceModel:
         from .optim import Adam
         with open(path, 'rb') as ff:
             saved = pickle.load(ff)
-        by_count = {len(mod._sd_host): mod for mod in (self.model_top, self.model_mid)}
+        mods = (self.model_top, self.model_mid) + ((self.model_down,) if (self.colour_channels, self.resolution) == (1, 64) else ())
+        by_count = {len(mod._sd_host): mod for mod in mods}
         out = {}
         for name, sd in saved.items():
             groups = sd.get('param_groups', [])

@@ -1,9 +1,11 @@
 """daimc_amd.Adam: torch.optim.Adam (default flags: no amsgrad, no weight decay) for the parts of the model the engine trains on the
-device: the habit network ModelTop.qpi_net (six parameters, C ABI part "top") and the transition network ModelMid.ps_net (eight
-parameters, part "ps_net").  One optimiser holds one part.  The update runs in csrc/train.hip (k_adam) on the engine's master copy of
-the weights; this class holds the part's name, the optimiser state (exp_avg, exp_avg_sq: flat device tensors in parameters() order) and
-the step count, and speaks torch.optim.Adam's state_dict format for the part's parameters, so state moves both ways between the two.
-The encoder / decoder (train_model_down) is not trainable on the engine."""
+device: the habit network ModelTop.qpi_net (six parameters, C ABI part "top"), the transition network ModelMid.ps_net (eight
+parameters, part "ps_net") and, at 1 x 64 x 64, the encoder / decoder ModelDown (32 parameters, 4 787 125 elements).  One optimiser
+holds one part.  The update runs on the engine's master copy of the weights: csrc/train.hip (k_adam, which also refreshes the two packed
+copies of the small nets) or, for ModelDown, csrc/train_down.hip (k_adam_down, then k_repack_down rebuilds every packed forward form;
+efe_down_adam_step).  This class holds the part's name, the optimiser state (exp_avg, exp_avg_sq: flat device tensors in parameters()
+order) and the step count, and speaks torch.optim.Adam's state_dict format for the part's parameters, so state moves both ways between
+the two."""
 import torch
 
 from .model import _TrainableModule
@@ -18,10 +20,14 @@ class Adam:
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         mod = params if isinstance(params, _TrainableModule) else getattr(params, 'module', None)
         if not isinstance(mod, _TrainableModule):
-            raise TypeError('daimc_amd.Adam takes model.model_top, model.model_mid or the parameters() of one of them (the habit net and '
-                            'the transition net are the trainable parts)')
+            raise TypeError('daimc_amd.Adam takes model.model_top, model.model_mid, model.model_down or the parameters() of one of them '
+                            '(the trainable parts)')
+        own = mod._owner
+        if mod._train_part == 'down' and (own.colour_channels, own.resolution) != (1, 64):
+            raise ValueError(f'daimc_amd.Adam: ModelDown is trainable on the engine at 1 x 64 x 64 only, this model is '
+                             f'{own.colour_channels} x {own.resolution} x {own.resolution}')
         self._module = mod
-        self._part = mod._train_part                # the part's name in the C ABI: "top" / "ps_net"
+        self._part = mod._train_part                # the part's name in the C ABI: "top" / "ps_net"; "down": the step's own entry point
         self._shapes = [tuple(t.shape) for t in mod._sd_host.values()]
         self._numel = [int(torch.Size(s).numel()) for s in self._shapes]
         group = _torch_group()
@@ -48,15 +54,20 @@ class Adam:
         """no-op: the engine never accumulates gradients"""
 
     def step(self, grad):
-        """one update with the caller's gradient: the dict loss.grad_top / grad_mid returns, or the flat [P] tensor (parameters() order)"""
+        """one update with the caller's gradient: the dict loss.grad_top / grad_mid / grad_down returns, or the flat [P] tensor
+        (parameters() order)"""
         m = self._module._owner
         e = m._ready()
         if isinstance(grad, dict):
             grad = torch.cat([e.tensor(grad[k]).reshape(-1) for k in self._module._sd_host])
         grad = e.tensor(grad).reshape(-1)
         ea, es = self._buffers()
+        hyper = self._hyper()
+        if self._part == 'down':
+            e.ops.down_adam_step(e.h, grad, ea, es, *hyper, self._step + 1)
+        else:
+            e.ops.adam_step(e.h, self._part, grad, ea, es, *hyper, self._step + 1)
         self._step += 1
-        e.ops.adam_step(e.h, self._part, grad, ea, es, *self._hyper(), self._step)
         self._module._stepped()
 
     def state_dict(self):

@@ -401,8 +401,8 @@ int efe_dec_grad(efe_ctx*, const float* s, const float* o1, int M, float scale, 
  * qs_net.9.weight [256][576]) and its backward, and the composed call that adds the sample, the decoder and the KL terms.
  * efe_param_count("qs_net") = 349 428 (0.weight, 0.bias, 2.*, 4.*, 6.*, 9.*, 12.*, 15.*, 18.*: parameters() order, each tensor row-major
  * in the reference's shape); efe_param_count("down") = 349 428 + 4 437 697 = 4 787 125, qs_net first, then po_net as efe_dec_grad lays it
- * out: the order torch.optim.Adam(model_down.parameters()) sees.  There is no optimiser step for these parts yet: efe_adam_step and
- * efe_get_weights refuse both names.
+ * out: the order torch.optim.Adam(model_down.parameters()) sees.  efe_adam_step and efe_get_weights refuse both names: the optimiser
+ * step of "down" has functions of its own (efe_train_down, efe_down_adam_step, efe_down_get_weights below).
  *   efe_enc_grad  : the vector-Jacobian product of the encoder for the upstream pair g_mean, g_logvar [M,10]:
  *                   grad [349 428] = sum_r g_mean_r . d mean_r / d parameters + g_logvar_r . d logvar_r / d parameters.
  *                   o [M,1,64,64], g_mean, g_logvar, nz and grad are required.  nz keys the three dropout masks: the FORWARD encoder's,
@@ -428,6 +428,30 @@ int efe_enc_grad(efe_ctx*, const float* o, const float* g_mean, const float* g_l
                  float* grad, float* y1, float* y2, float* y3, float* y4, float* h1, float* h2, float* h3, void* stream);
 int efe_down_grad(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
                   const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream);
+
+/* ---- the optimiser step of ModelDown: train_model_down (csrc/train_down.hip; additive to ABI 6) -------------------------------------------
+ * torch.optim.Adam's default update over the flat [4 787 125] parameter vector of ModelDown (the order of efe_down_grad's gradient), at the
+ * 1 x 64 x 64 geometry.  The engine owns a master copy of these parameters that survives efe_commit_weights; the step writes it and then
+ * rebuilds, on the device, every packed form the forward paths read (fragment orders, tap tables, the Winograd and F(2, 2) matrices, padded
+ * bias tables): each holds exactly what a fresh commit of the new weights would have packed.  A later efe_set_weight of a "down." tensor or
+ * efe_commit_weights first brings the host tensors up to date (one synchronisation), so a trained part is never reverted.  The first decoder
+ * pass behind a step fetches po_net.19.bias (4 bytes, handed to its kernel by value) on its own stream and synchronises that stream once; it
+ * cannot be captured into a graph, and a graph captured BEFORE a step holds the old bias by value: re-capture graphs after a step of ModelDown.
+ * A step also invalidates split-operand planes left from an earlier mfma_bf16x3 / mfma_f16x2: turning the option on after a step first brings
+ * the host tensors up to date and packs the planes from the trained weights.  For a handle that is not live these three return 1 and
+ * efe_last_error names the function ("<function>: stale or invalid context handle") until the thread's next call.
+ * The string-part calls keep refusing these parts: efe_adam_step / efe_get_weights know nothing of a repack; these are separate functions.
+ *   efe_train_down      : efe_down_grad's groups, the update and the repack queued on the stream, no host synchronisation; bit-identical to
+ *                         efe_down_grad followed by efe_down_adam_step.  out (as efe_down_grad's) reports the weights BEFORE the step.
+ *   efe_down_adam_step  : update and repack from the caller's gradient [4 787 125]; exp_avg / exp_avg_sq [4 787 125] are the caller's state.
+ *   efe_down_get_weights: the master copy -> dst (device), n == efe_param_count("down"), ordered on the stream.
+ * Each returns 1 with a message that names the function for a NULL required pointer, M <= 0, hp NULL or hp->step < 1 (or other bad
+ * hyper-parameters), EFE_OMEGA_DERIVED, a context of another geometry, or a split-operand option (mfma_bf16x3 / mfma_f16x2) being on; a
+ * refused call changes no weight and no optimiser state.  Scratch (the gradient, on top of efe_down_grad's) comes from the context's arena. */
+int efe_train_down(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                   const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
+int efe_down_adam_step(efe_ctx*, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
+int efe_down_get_weights(efe_ctx*, float* dst, int64_t n, void* stream);
 
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);

@@ -10,9 +10,15 @@ after --warmup calls, reported as milliseconds per call (median / min / max of -
   encoder   : torch.ops.efe.enc_grad alone (training forward and backward of qs_net for a given upstream pair)
   autograd  : the reference's own path on the same GPU -- qs_net and po_net built HERE from torch.nn layers (qs_net.9 = Linear(576, 256),
               Dropout(0.5) in train mode), compute_loss_down's expressions (torchloss.py:39-63) and F.mean().backward()
+  train     : torch.ops.efe.train_down -- `down`, then Adam over the 4 787 125 parameters and the repack of every packed forward form
+              (csrc/train_down.hip), at lr 1e-5 with the step count running
+  adam_step : torch.ops.efe.down_adam_step alone on a fixed gradient: k_adam_down + k_repack_down.  Its cost does not depend on M; the
+              record carries the byte count of the two kernels (STEP_BYTES below) and the rate achieved against it
+The two step legs are skipped (and `down` still timed) on a build without the ops: the parent commit, timed in the same session with
+--tag parent --no-autograd.
 No speed ratio is a gate.
 
-Usage:  python tools/train_down_bench.py [--sizes 50,1024] [--steps 20] [--warmup 3] [--write] [--out path.json]
+Usage:  python tools/train_down_bench.py [--sizes 50,1024] [--steps 20] [--warmup 3] [--tag name] [--write] [--out path.json]
 """
 import argparse
 import json
@@ -25,6 +31,18 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, 'profiles', 'train_down_bench.json')
+
+
+def step_bytes():
+    """bytes the optimiser step moves at the least: k_adam_down reads gradient, both moments and the weight and writes the last three
+    (7 x 4 P); k_repack_down reads the raw copy once (the small Linears, packed in two forms, twice) and writes every packed buffer"""
+    P = 4787125
+    dense = [(256, 16), (256, 256), (256, 256), (256, 256), (256, 256), (32, 256), (256, 576)]      # rows x padded K of the layers packed in both dense forms
+    packed = 2 * sum(r * k + r for r, k in dense)
+    packed += 288 + 32 + 9 * (32 * 32 + 64 * 32 + 64 * 64) + 32 + 64 + 64                         # the encoder's convolutions
+    packed += 16384 * 256 + 16384 + 16 * (64 * 64 + 64 * 64 + 32 * 64) + 64 + 64 + 32 + 288         # po_net.9, the Winograd / F(2,2) matrices, the final taps
+    twice = sum(r * k + r for r, k in dense)
+    return {'adam': 7 * 4 * P, 'repack_read': 4 * (P + twice), 'repack_write': 4 * packed, 'total': 4 * (8 * P + twice + packed)}
 
 
 def inputs(seed, M):
@@ -69,6 +87,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--no-autograd', action='store_true')
+    ap.add_argument('--tag', default='', help='a name for this build in the record (e.g. parent)')
     ap.add_argument('--write', action='store_true')
     ap.add_argument('--out', default=OUT)
     args = ap.parse_args()
@@ -79,7 +98,7 @@ def main():
     w = synth.make_weights(1234, 1.15)
     gamma, beta_s, beta_o = 0.5, 1.0, 1.0
     res = {'metric': 'down_grad_ms_per_call', 'steps': args.steps, 'warmup': args.warmup, 'repeats': args.repeats,
-           'device': torch.cuda.get_device_name(0), 'legs': {}}
+           'device': torch.cuda.get_device_name(0), 'tag': args.tag, 'step_bytes': step_bytes(), 'legs': {}}
     m = daimc_amd.ActiveInferenceModel(10, 4, gamma, beta_s, beta_o, device='cuda:0', seed=1, init_weights=False)
     m.load_flat_weights(w)
     e = m._ready()
@@ -108,9 +127,25 @@ def main():
                 F.mean().backward()
                 return F
             legs['autograd'] = autograd_call
+        if hasattr(e.lib, 'efe_train_down'):
+            NP = 4787125
+            ea, es, g = torch.zeros(NP, device='cuda:0'), torch.zeros(NP, device='cuda:0'), 1e-3 * torch.randn(NP, device='cuda:0')
+            step = [0]
+
+            def train_call():
+                step[0] += 1
+                return e.ops.train_down(e.h, o1, pm, pv, gamma, beta_s, beta_o, 0, om, 1.0, 1, 3, 12, 0, 0, None, ea, es, 1e-5, 0.9, 0.999, 1e-8, step[0])
+
+            def step_call():
+                step[0] += 1
+                e.ops.down_adam_step(e.h, g, ea, es, 1e-5, 0.9, 0.999, 1e-8, step[0])
+            legs['train'] = train_call
+            legs['adam_step'] = step_call
         for name, fn in legs.items():
             t = sorted(window_ms(fn, args.steps, args.warmup) for _ in range(args.repeats))
             res['legs'][f'{name}_M{M}'] = {'ms_per_call_median': t[len(t) // 2], 'ms_per_call_min': t[0], 'ms_per_call_max': t[-1]}
+            if name == 'adam_step':
+                res['legs'][f'{name}_M{M}']['achieved_TB_per_s'] = res['step_bytes']['total'] / (t[len(t) // 2] * 1e-3) / 1e12
     line = json.dumps(res)
     if args.write:
         with open(args.out, 'w') as fh:
