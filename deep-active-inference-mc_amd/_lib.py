@@ -16,7 +16,7 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down',
            'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top',
            'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
-           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights']
+           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step']
 ABI_VERSION = 6
 
 
@@ -49,6 +49,24 @@ class EfeAdamParams(C.Structure):
 
 class EfeFeOut(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in FE_OUT_FIELDS]
+
+
+# efe_train_step (include/efe_engine.h): its inputs, one part's optimiser state + hyper-parameters, its outputs
+EFE_STEP_MEANS = 8
+STEP_MEANS_FIELDS = ('kl_pi', 'omega', 'F_mid', 'F_down', 'nlogpo1', 'kl_s', 'kl_naive', 'omega_std')
+STEP_OUT_FIELDS = ('kl_pi', 'omega', 'qs0', 'F_mid', 'ps1_mean', 'ps1_logvar', 'F_down', 'nlogpo1', 'kl_s', 'kl_naive', 'means')
+
+
+class EfeStepIn(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ('o0', 'o1', 'pi0', 'log_Ppi', 'eps')]
+
+
+class EfeStepAdam(C.Structure):
+    _fields_ = [('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p), ('hp', EfeAdamParams)]
+
+
+class EfeStepOut(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in STEP_OUT_FIELDS]
 
 
 _lib = None
@@ -164,5 +182,7 @@ def load():
     lib.efe_train_down.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, f32p, f32p, ap, p]; lib.efe_train_down.restype = i
     lib.efe_down_adam_step.argtypes = [p, f32p, f32p, f32p, ap, p]; lib.efe_down_adam_step.restype = i
     lib.efe_down_get_weights.argtypes = [p, f32p, C.c_int64, p]; lib.efe_down_get_weights.restype = i
+    sap = C.POINTER(EfeStepAdam)
+    lib.efe_train_step.argtypes = [p, C.POINTER(EfeStepIn), i, fpp, nzp, sap, sap, sap, C.POINTER(EfeStepOut), p]; lib.efe_train_step.restype = i
     _lib = lib
     return lib

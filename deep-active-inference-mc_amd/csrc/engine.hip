@@ -1801,17 +1801,25 @@ int efe_adam_step(efe_ctx* ctx, const char* part, const float* grad, float* exp_
     return call.finish();
 }
 
+namespace {
+// efe_train_top inside its call scope, for efe_train_step too (`who` names the entry point in the messages).  Every refusal comes before the launch.
+int train_top_run(efe_ctx* ctx, const char* who, const float* s, const float* log_Ppi, int M, float* kl_pi, float* exp_avg, float* exp_avg_sq,
+                  const efe_adam_params* hp, hipStream_t st) {
+    if (!s || !log_Ppi || !exp_avg || !exp_avg_sq || M < 1)
+        return ctx->fail(std::string(who) + ": bad arguments (s, log_Ppi, exp_avg and exp_avg_sq must be non-NULL, M >= 1)");
+    TrainPart& tp = ctx->top_train;
+    AdamArgs a{};
+    if (adam_args(ctx, &tp, hp, a, who)) return 1;
+    a.m = exp_avg; a.v = exp_avg_sq;
+    return grad_or_step(ctx, tp, train_slabs(M), nullptr, &a, st, [&](float* slabs) {
+        launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st); });
+}
+}  // namespace
+
 int efe_train_top(efe_ctx* ctx, const float* s, const float* log_Ppi, int M, float* kl_pi, float* exp_avg, float* exp_avg_sq,
                   const efe_adam_params* hp, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    if (!s || !log_Ppi || !exp_avg || !exp_avg_sq || M < 1)
-        return ctx->fail("efe_train_top: bad arguments (s, log_Ppi, exp_avg and exp_avg_sq must be non-NULL, M >= 1)");
-    TrainPart& tp = ctx->top_train;
-    AdamArgs a{};
-    if (adam_args(ctx, &tp, hp, a, "efe_train_top")) return 1;
-    a.m = exp_avg; a.v = exp_avg_sq;
-    if (grad_or_step(ctx, tp, train_slabs(M), nullptr, &a, st, [&](float* slabs) {
-            launch_top_grad(TopGradArgs{tp.net_dev, s, log_Ppi, kl_pi, slabs, M, ctx->pi_dim, 1.0f / (float)M}, st); })) return 1;
+    if (train_top_run(ctx, "efe_train_top", s, log_Ppi, M, kl_pi, exp_avg, exp_avg_sq, hp, st)) return 1;
     return call.finish();
 }
 
@@ -1824,17 +1832,26 @@ int efe_mid_grad(efe_ctx* ctx, const float* s0, const float* pi0, const float* q
     return call.finish();
 }
 
+namespace {
+// efe_train_mid inside its call scope, for efe_train_step too.  Every refusal comes before the launch.
+int train_mid_run(efe_ctx* ctx, const char* who, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M,
+                  const efe_fe_params* params, const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, float* exp_avg, float* exp_avg_sq,
+                  const efe_adam_params* hp, hipStream_t st) {
+    MidGradArgs g{};
+    if (mid_grad_args(ctx, s0, pi0, qs1_mean, qs1_logvar, M, params, nz, ps1_mean, ps1_logvar, F_mid, exp_avg && exp_avg_sq, g, who)) return 1;
+    TrainPart& tp = ctx->mid_train;
+    AdamArgs a{};
+    if (adam_args(ctx, &tp, hp, a, who)) return 1;
+    a.m = exp_avg; a.v = exp_avg_sq;
+    return grad_or_step(ctx, tp, train_mid_slabs(M), nullptr, &a, st, [&](float* slabs) { g.slabs = slabs; launch_mid_grad(g, st); });
+}
+}  // namespace
+
 int efe_train_mid(efe_ctx* ctx, const float* s0, const float* pi0, const float* qs1_mean, const float* qs1_logvar, int M, const efe_fe_params* params,
                   const efe_noise* nz, float* ps1_mean, float* ps1_logvar, float* F_mid, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp,
                   void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    MidGradArgs g{};
-    if (mid_grad_args(ctx, s0, pi0, qs1_mean, qs1_logvar, M, params, nz, ps1_mean, ps1_logvar, F_mid, exp_avg && exp_avg_sq, g, "efe_train_mid")) return 1;
-    TrainPart& tp = ctx->mid_train;
-    AdamArgs a{};
-    if (adam_args(ctx, &tp, hp, a, "efe_train_mid")) return 1;
-    a.m = exp_avg; a.v = exp_avg_sq;
-    if (grad_or_step(ctx, tp, train_mid_slabs(M), nullptr, &a, st, [&](float* slabs) { g.slabs = slabs; launch_mid_grad(g, st); })) return 1;
+    if (train_mid_run(ctx, "efe_train_mid", s0, pi0, qs1_mean, qs1_logvar, M, params, nz, ps1_mean, ps1_logvar, F_mid, exp_avg, exp_avg_sq, hp, st)) return 1;
     return call.finish();
 }
 
@@ -2093,16 +2110,101 @@ int efe_down_grad(efe_ctx* ctx, const float* o1, const float* ps1_mean, const fl
     return call.finish();
 }
 
+namespace {
+// efe_train_down inside its call scope, for efe_train_step too.  Every refusal comes before the first launch.
+int train_down_run(efe_ctx* ctx, const char* who, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                   const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, hipStream_t st) {
+    DownAdamArgs a{};
+    if (down_step_args(ctx, exp_avg, exp_avg_sq, hp, a, who)) return 1;
+    float* grad = ctx->allocT<float>((size_t)DOWN_P);
+    if (!grad) return 1;
+    if (down_grad_run(ctx, who, o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, nullptr, nullptr, grad, st)) return 1;
+    a.g = grad;
+    down_step(ctx, a, st);
+    return 0;
+}
+}  // namespace
+
 int efe_train_down(efe_ctx* ctx, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
                    const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_train_down");
-    DownAdamArgs a{};
-    if (down_step_args(ctx, exp_avg, exp_avg_sq, hp, a, "efe_train_down")) return 1;
-    float* grad = ctx->allocT<float>((size_t)DOWN_P);
-    if (!grad) return 1;
-    if (down_grad_run(ctx, "efe_train_down", o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, nullptr, nullptr, grad, st)) return 1;
-    a.g = grad;
-    down_step(ctx, a, st);
+    if (train_down_run(ctx, "efe_train_down", o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, exp_avg, exp_avg_sq, hp, st)) return 1;
+    return call.finish();
+}
+
+// ---- one whole training step (train.py:111-126): the three run functions behind the two encoder passes, omega formed on the device ---------
+int efe_train_step(efe_ctx* ctx, const efe_step_in* in, int M, const efe_fe_params* params, const efe_noise* nz, const efe_step_adam* top,
+                   const efe_step_adam* mid, const efe_step_adam* down, const efe_step_out* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_train_step");
+    const char* who = "efe_train_step";
+    // every refusal before the first launch: what the run functions below would refuse, checked for all three parts up front
+    if (M < 1) return ctx->fail("efe_train_step: M must be >= 1");
+    if (!in || !in->o0 || !in->o1 || !in->pi0 || !in->log_Ppi || !nz || !out || !out->kl_pi || !out->F_down)
+        return ctx->fail("efe_train_step: in (o0, o1, pi0, log_Ppi), params, nz and out (kl_pi, F_down) must be non-NULL");
+    if (!top || !mid || !down || !top->exp_avg || !top->exp_avg_sq || !mid->exp_avg || !mid->exp_avg_sq || !down->exp_avg || !down->exp_avg_sq)
+        return ctx->fail("efe_train_step: top, mid and down with their exp_avg and exp_avg_sq must be non-NULL");
+    if (fe_params(ctx, params, true, who)) return 1;
+    {
+        AdamArgs a{}; DownAdamArgs d{};
+        if (adam_args(ctx, &ctx->top_train, &top->hp, a, "efe_train_step (top)") || adam_args(ctx, &ctx->mid_train, &mid->hp, a, "efe_train_step (mid)")) return 1;
+        if (down_step_args(ctx, down->exp_avg, down->exp_avg_sq, &down->hp, d, "efe_train_step (down)")) return 1;      // (geometry, split-operand options)
+        if (!ctx->enc_raw || !ctx->dec_raw) return ctx->fail("efe_train_step (down): built for the 1 x 64 x 64 geometry only");
+    }
+    const uint32_t k0 = (uint32_t)nz->seed, k1 = (uint32_t)(nz->seed >> 32);
+    const float* eps_q0 = in->eps;
+    const float* eps_d = in->eps ? in->eps + (size_t)2 * M * S_DIM : nullptr;
+    // what outlives a part: the arrays the caller does not want stand in scratch; each part's own scratch is handed back behind it (the
+    // stream orders the parts, as it orders fe_down's chunks)
+    auto own = [&](float* p, size_t n) { return p ? p : ctx->allocT<float>(n); };
+    float* qs0 = own(out->qs0, (size_t)M * S_DIM);
+    float* omega = own(out->omega, (size_t)M);
+    float* qm = ctx->allocT<float>((size_t)M * S_DIM);
+    float* qv = ctx->allocT<float>((size_t)M * S_DIM);
+    float* pm = own(out->ps1_mean, (size_t)M * S_DIM);
+    float* pv = own(out->ps1_logvar, (size_t)M * S_DIM);
+    float* F_mid = own(out->F_mid, (size_t)M);
+    float* nl = out->means ? own(out->nlogpo1, (size_t)M) : out->nlogpo1;
+    float* kls = out->means ? own(out->kl_s, (size_t)M) : out->kl_s;
+    float* kln = out->means ? own(out->kl_naive, (size_t)M) : out->kl_naive;
+    if (!qs0 || !omega || !qm || !qv || !pm || !pv || !F_mid || (out->means && (!nl || !kls || !kln))) return 1;
+    const Arena::Mark mark = ctx->arena.mark();
+    efe_noise pz = *nz; pz.sample = 0;
+    // 1. qs0 = encoder_with_sample(o0): efe_encoder under PASS_FE_Q0
+    {
+        float* enc = ctx->allocT<float>((size_t)M * 32);
+        if (!enc) return 1;
+        if (run_encoder(ctx, in->o0, M, pass_noise(nz, PASS_FE_Q0, 0, M), enc, st)) return 1;
+        launch_root_post(enc, nullptr, eps_q0, nullptr, qs0, M, 0, k0, k1, PASS_FE_Q0, 0, nz->stage, nz->row_offset, ctx->pi_dim, st);
+    }
+    // 2. the habit net's step
+    if (train_top_run(ctx, "efe_train_step (top)", qs0, in->log_Ppi, M, out->kl_pi, top->exp_avg, top->exp_avg_sq, &top->hp, st)) return 1;
+    ctx->arena.rewind(mark);
+    // 3. omega: compute_omega(kl_pi) of this call, or the caller's
+    {
+        FeArgs a{};
+        a.M = M; a.kl_pi = out->kl_pi;
+        fe_omega(a, params); a.omega_out = omega;
+        launch_step_omega(a, st);
+    }
+    efe_fe_params pw = *params;
+    pw.omega_mode = EFE_OMEGA_ARRAY; pw.omega = omega;
+    // 4. qs1_mean, qs1_logvar = encoder(o1): efe_encoder under PASS_FE_Q1
+    {
+        float* enc = ctx->allocT<float>((size_t)M * 32);
+        if (!enc) return 1;
+        if (run_encoder(ctx, in->o1, M, pass_noise(nz, PASS_FE_Q1, 0, M), enc, st)) return 1;
+        launch_split_enc(enc, qm, qv, M, st);
+    }
+    // 5. the transition net's step
+    pz.pass = PASS_FE_T;
+    if (train_mid_run(ctx, "efe_train_step (mid)", qs0, in->pi0, qm, qv, M, &pw, &pz, pm, pv, F_mid, mid->exp_avg, mid->exp_avg_sq, &mid->hp, st)) return 1;
+    ctx->arena.rewind(mark);
+    // 6. ModelDown's step
+    pz.pass = PASS_FE_DOWN;
+    efe_fe_out fo{};
+    fo.F_down = out->F_down; fo.nlogpo1 = nl; fo.kl_s = kls; fo.kl_naive = kln;
+    if (train_down_run(ctx, "efe_train_step (down)", in->o1, pm, pv, M, &pw, &pz, eps_d, &fo, down->exp_avg, down->exp_avg_sq, &down->hp, st)) return 1;
+    if (out->means) launch_step_means(StepMeansArgs{{out->kl_pi, omega, F_mid, out->F_down, nl, kls, kln}, out->means, M}, st);
     return call.finish();
 }
 

@@ -405,6 +405,12 @@ struct FeArgs {
 };
 void launch_fe_top_mid(const FeArgs& a, hipStream_t st);
 void launch_fe_down(const FeArgs& a, const float* po, int m0, int rows, hipStream_t st);     // rows [m0, m0 + rows); po = their images
+// the training step's tails (loss.hip): omega_out[r] = row omega of kl_pi[r] (FeArgs: M, kl_pi, the omega fields, omega_out), and the
+// step's statistics: means[q] = mean of x[q] [M] for q < 7 (kl_pi, omega, F_mid, F_down, nlogpo1, kl_s, kl_naive), means[7] = std of x[1]
+constexpr int STEP_MEANS = 8;          // = EFE_STEP_MEANS (include/efe_engine.h)
+struct StepMeansArgs { const float* x[STEP_MEANS - 1]; float* means; int M; };
+void launch_step_omega(const FeArgs& a, hipStream_t st);
+void launch_step_means(const StepMeansArgs& a, hipStream_t st);
 
 // ---- training of the small MLPs (train.hip): backward + Adam over a layer table -----------------------------------
 // A trainable part is a chain of Linear layers described by a DEVICE-RESIDENT table (built at efe_commit_weights): widths, the ReLU flag

@@ -5,6 +5,8 @@
 //                  given as a scalar, or compute_omega(kl_pi, a, b, c, d)), and the transition KL of compute_loss_mid (F_mid).
 //   k_fe_down    : one workgroup of 256 threads per row.  The Bernoulli log-likelihood of o1 under the decoder's stored image po1, summed
 //                  over C*H*W in a FIXED order, the two KL vectors of compute_loss_down and the gamma-branch combination F_down.
+//   k_step_omega, k_step_means : the two tails of the training step (efe_train_step): compute_omega per row between the habit net's step
+//                  and the transition net's, and the eight batch statistics a training loop logs (described where they are defined).
 //
 // Every expression follows the reference's torch expression in the same fp32 operation order, contraction off:
 //   kl(mu1, lv1, mu2, lv2, w) = 0.5 * ((lv2 - log w) - lv1) + (exp lv1 + (mu1 - mu2)^2) / ((2 exp lv2) / w) - 0.5   (torchutils.py:7-8)
@@ -40,6 +42,58 @@ __device__ __forceinline__ float row_omega(const FeArgs& a, int r, float kl_pi) 
 }
 
 }  // namespace
+
+// ---- the training step's two tails (efe_train_step) --------------------------------------------------------------------------------
+// k_step_omega : one thread per row.  omega[r] = row_omega(a, r, kl_pi[r]): the expression k_fe_top_mid evaluates (mode 2), or the
+//                caller's omega copied to the output (modes 0 / 1).  Reads a.kl_pi, writes a.omega_out; no other field of FeArgs.
+__global__ void __launch_bounds__(128) k_step_omega(const FeArgs a) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.M) return;
+    a.omega_out[r] = row_omega(a, r, a.omega_mode == 2 ? a.kl_pi[r] : 0.0f);
+}
+
+namespace {
+// the sum of f(x[r]) over r < M in the order the contract below states; every thread of the 256-thread workgroup gets the result
+template <class F>
+__device__ __forceinline__ float step_block_sum(const float* x, int M, float* ws, F f) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    float acc = 0.0f;
+    for (int r = tid; r < M; r += 256) acc = acc + f(x[r]);
+    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+    __syncthreads();                    // (ws may still be read from the previous sum)
+    if ((tid & 63) == 0) ws[tid >> 6] = acc;
+    __syncthreads();
+    return ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+}  // namespace
+
+// k_step_means : EFE_STEP_MEANS = 8 workgroups of 256 threads, one per quantity.  Workgroup q < 7 writes means[q] = the batch mean of
+//                a.x[q] [M]; workgroup 7 writes the unbiased standard deviation of a.x[1] (omega), torch.std's two passes: the mean, then
+//                the sum of squared deviations from it, divided by M - 1 (0 / 0 = NaN at M = 1, as torch.std gives).
+// Reduction-order contract (a function of M alone): thread t adds rows t, t + 256, ... in ascending order into an fp32 accumulator that
+// starts at 0; the 64 lanes of a wave are combined by an xor butterfly (offsets 32, 16, ..., 1) and the four wave sums as
+// ((w0 + w1) + w2) + w3; one correctly rounded division by (float)M (by (float)(M - 1) for the variance) and a correctly rounded square
+// root.  Contraction off, no atomics.  Memory-bound: 4 M bytes read per workgroup (8 M by the last one).
+__global__ void __launch_bounds__(256) k_step_means(const StepMeansArgs a) {
+#pragma clang fp contract(off)
+    __shared__ float ws[4];
+    const int q = blockIdx.x;
+    const float* x = a.x[q < 7 ? q : 1];
+    const float Mf = (float)a.M;
+    const float mean = __fdiv_rn(step_block_sum(x, a.M, ws, [](float v) { return v; }), Mf);
+    if (q < 7) {
+        if (threadIdx.x == 0) a.means[q] = mean;
+        return;
+    }
+    const float ss = step_block_sum(x, a.M, ws, [mean](float v) {
+#pragma clang fp contract(off)
+        const float d = v - mean;
+        return d * d;
+    });
+    if (threadIdx.x == 0) a.means[7] = __fsqrt_rn(__fdiv_rn(ss, (float)(a.M - 1)));
+}
 
 __global__ void __launch_bounds__(128) k_fe_top_mid(const FeArgs a) {
 #pragma clang fp contract(off)
@@ -120,6 +174,13 @@ __global__ void __launch_bounds__(256) k_fe_down(const FeArgs a, const float* po
     if (a.nlogpo1) a.nlogpo1[r] = -logpo1;
     if (a.kl_s) a.kl_s[r] = kls;
     if (a.kl_naive) a.kl_naive[r] = kln;
+}
+
+void launch_step_omega(const FeArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_step_omega, dim3((a.M + 127) / 128), dim3(128), 0, st, a);
+}
+void launch_step_means(const StepMeansArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_step_means, dim3(STEP_MEANS), dim3(256), 0, st, a);
 }
 
 void launch_fe_top_mid(const FeArgs& a, hipStream_t st) {

@@ -581,6 +581,39 @@ void down_adam_step(int64_t h, const Tensor& grad_, Tensor exp_avg, Tensor exp_a
     ok(c, efe_down_adam_step(c, grad.data_ptr<float>(), state(exp_avg, "exp_avg", NP), state(exp_avg_sq, "exp_avg_sq", NP), &hp, stream_of(grad)));
 }
 
+// one whole training step, train.py:111-126 (efe_train_step) -> (kl_pi, omega, qs0, F_mid, ps1_mean, ps1_logvar, F_down, nlogpo1, kl_s, kl_naive); means
+// [EFE_STEP_MEANS] and the six state vectors are written in place.  hyper = (lr, beta1, beta2, eps) of the top, mid and down optimisers
+// (12 numbers), steps = their three step numbers
+std::vector<Tensor> train_step(int64_t h, const Tensor& o0_, const Tensor& o1_, const Tensor& pi0_, const Tensor& lp_, double gamma, double beta_s,
+                               double beta_o, int64_t omega_mode, const OptT& omega, double omega_scalar, double a, double b, double cc, double d,
+                               int64_t seed, int64_t stage, int64_t row_offset, const OptT& eps, Tensor top_m, Tensor top_v, Tensor mid_m, Tensor mid_v,
+                               Tensor down_m, Tensor down_v, c10::ArrayRef<double> hyper, at::IntArrayRef steps, Tensor means) {
+    efe_ctx* c = CTX(h);
+    Tensor o0 = in(o0_, "o0"), o1 = in(o1_, "o1"), pi0 = in(pi0_, "pi0"), lp = in(lp_, "log_Ppi"), ok_, ek;
+    const Geo g = geo(c);
+    TORCH_CHECK(g.C == 1 && g.R == 64, "efe engine: efe_train_step: built for the 1 x 64 x 64 geometry only");
+    const int M = rows(o0, 4096, "o0");
+    TORCH_CHECK(o1.numel() == (int64_t)M * 4096, "efe: o1 must have the shape of o0");
+    TORCH_CHECK(pi0.numel() == (int64_t)M * g.A && lp.numel() == (int64_t)M * g.A, "efe: pi0 and log_Ppi must be [M, pi_dim]");
+    TORCH_CHECK(hyper.size() == 12 && steps.size() == 3, "efe: train_step takes 12 hyper-parameters and 3 step numbers");
+    efe_fe_params p = fe_params(gamma, beta_s, beta_o, omega_mode, omega, ok_, omega_scalar, M);
+    p.a = (float)a; p.b = (float)b; p.c = (float)cc; p.d = (float)d;
+    const int64_t Pt = efe_param_count(c, "top"), Pm = efe_param_count(c, "ps_net"), Pd = efe_param_count(c, "down");
+    TORCH_CHECK(Pt > 0 && Pm > 0 && Pd > 0, "efe engine: ", efe_last_error(c));
+    efe_step_adam at_{state(top_m, "top exp_avg", Pt), state(top_v, "top exp_avg_sq", Pt), adam_params(hyper[0], hyper[1], hyper[2], hyper[3], steps[0])};
+    efe_step_adam am_{state(mid_m, "mid exp_avg", Pm), state(mid_v, "mid exp_avg_sq", Pm), adam_params(hyper[4], hyper[5], hyper[6], hyper[7], steps[1])};
+    efe_step_adam ad_{state(down_m, "down exp_avg", Pd), state(down_v, "down exp_avg_sq", Pd), adam_params(hyper[8], hyper[9], hyper[10], hyper[11], steps[2])};
+    auto op = o0.options();
+    const int64_t S = g.s;
+    std::vector<Tensor> r = {at::empty({M}, op), at::empty({M}, op), at::empty({M, S}, op), at::empty({M}, op), at::empty({M, S}, op),
+                             at::empty({M, S}, op), at::empty({M}, op), at::empty({M}, op), at::empty({M}, op), at::empty({M}, op)};
+    efe_step_in si{o0.data_ptr<float>(), o1.data_ptr<float>(), pi0.data_ptr<float>(), lp.data_ptr<float>(), optp(eps, ek, "eps", (int64_t)3 * M * S)};
+    efe_step_out out{P(r[0]), P(r[1]), P(r[2]), P(r[3]), P(r[4]), P(r[5]), P(r[6]), P(r[7]), P(r[8]), P(r[9]), state(means, "means", EFE_STEP_MEANS)};
+    efe_noise nz = noise(seed, stage, 0, 0, row_offset);
+    ok(c, efe_train_step(c, &si, M, &p, &nz, &at_, &am_, &ad_, &out, stream_of(o0)));
+    return r;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -609,6 +642,7 @@ TORCH_LIBRARY(efe, m) {
     m.def("enc_grad(int ctx, Tensor o, Tensor d_mean, Tensor d_logvar, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
     m.def("down_grad(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> Tensor[]");
     m.def("train_down(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float adam_eps, int step) -> Tensor[]");
+    m.def("train_step(int ctx, Tensor o0, Tensor o1, Tensor pi0, Tensor log_Ppi, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, float a, float b, float c, float d, int seed, int stage, int row_offset, Tensor? eps, Tensor(a!) top_exp_avg, Tensor(b!) top_exp_avg_sq, Tensor(c!) mid_exp_avg, Tensor(d!) mid_exp_avg_sq, Tensor(e!) down_exp_avg, Tensor(f!) down_exp_avg_sq, float[] hyper, int[] steps, Tensor(g!) means) -> Tensor[]");
     m.def("down_adam_step(int ctx, Tensor grad, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> ()");
 }
 
@@ -638,5 +672,6 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("enc_grad", &enc_grad);
     m.impl("down_grad", &down_grad);
     m.impl("train_down", &train_down);
+    m.impl("train_step", &train_step);
     m.impl("down_adam_step", &down_adam_step);
 }

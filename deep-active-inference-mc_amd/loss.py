@@ -13,7 +13,10 @@ reconstruction and KL terms at the latent, and the encoder's backward.  Its piec
 vector-Jacobian product for a given upstream pair, `grad_decoder` the gradient of the reconstruction term with respect to every
 parameter of po_net and to s -- the dense head po_net.0 / .3 / .6 / .9 evaluated for training with the forward decoder's four dropout
 masks (csrc/train_dec_head.hip), then the four ConvTranspose2d layers (po_net.13 / .15 / .17 / .19, csrc/train_dec.hip), which
-`grad_decoder_convs` also runs from a given Unflatten input.  A training loop on the device is out of scope.  Every
+`grad_decoder_convs` also runs from a given Unflatten input.  `train_step` is the loop body of train.py:111-126 as ONE engine call
+(efe_train_step): the o0 encoder + sample, the habit net's step, compute_omega of its kl_pi on the device, the o1 encoder, the transition
+net's step and ModelDown's step, bit-identical to those public calls issued one after another, plus the batch means a loop logs
+(`TrainStep.means`) without a synchronisation; daimc_amd.train.Trainer drives it.  Every
 call dispatches through torch.ops.efe.* on the model's device; there is no CPU fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
@@ -39,6 +42,8 @@ from . import _lib
 from .model import PASS_FE_Q0, PASS_FE_Q1, PASS_FE_T, PASS_FE_DOWN
 
 FreeEnergy = collections.namedtuple('FreeEnergy', _lib.FE_OUT_FIELDS)
+TrainStep = collections.namedtuple('TrainStep', _lib.STEP_OUT_FIELDS)
+STEP_MEANS_FIELDS = _lib.STEP_MEANS_FIELDS      # what TrainStep.means [8] holds, in order
 OMEGA_PARAMS = (1.0, 25.0, 5.0, 1.5)        # train.py:29-32 (var_a, var_b, var_c, var_d)
 
 
@@ -331,3 +336,59 @@ def train_model_down(model_down, o1, ps1_mean, ps1_logvar, omega, optimizer, *, 
     optimizer._step += 1
     model_down._stepped()
     return F, (nl, kls, kln)
+
+
+def _step_optimizers(model, optimizers):
+    """the reference's optimizers dict -> (top, mid, down) daimc_amd.Adam, each over this model's part"""
+    out = []
+    for name, mod in (('top', model.model_top), ('mid', model.model_mid), ('down', model.model_down)):
+        if not hasattr(optimizers, 'get') or optimizers.get(name) is None:
+            raise ValueError(f"train_step: optimizers has no entry '{name}' (expected {{'top': Adam(model.model_top), 'mid': "
+                             "Adam(model.model_mid), 'down': Adam(model.model_down)}})")
+        if getattr(optimizers[name], '_module', None) is not mod:
+            raise ValueError(f"train_step: optimizers['{name}'] must be a daimc_amd.Adam over this model's model_{name}")
+        out.append(optimizers[name])
+    return out
+
+
+def train_step(model, o0, o1, pi0, log_Ppi, optimizers, *, omega=None, omega_params=OMEGA_PARAMS, stage=None, row_offset=None, eps=None,
+               means=None):
+    """The loop body of train.py:111-126 as one engine call (efe_train_step) -> TrainStep (fields: _lib.STEP_OUT_FIELDS): qs0 =
+    encoder_with_sample(o0), train_model_top, omega, encoder(o1), train_model_mid, train_model_down, all at ONE stage under the passes
+    PASS_FE_Q0 / _Q1 / _T / _DOWN, with no host synchronisation.  Bit-identical to those public calls issued one after another at that
+    stage with this call's per-row omega.  Every output is of the weights before the step.
+    optimizers: {'top': Adam(model.model_top), 'mid': Adam(model.model_mid), 'down': Adam(model.model_down)} (daimc_amd.Adam).
+    omega: None = compute_omega(kl_pi, *omega_params) of this call on the device (train.py:118), a number, or M values.
+    eps: optional injected normals [3, M, s_dim] as free_energy lays them out (plane 0: the FE_Q0 sample, plane 2: the FE_DOWN sample,
+    plane 1 is not read).  means: optional [8] device tensor written in place (STEP_MEANS_FIELDS: the batch means of kl_pi, omega, F_mid,
+    F_down, nlogpo1, kl_s, kl_naive and the unbiased standard deviation of omega); one is allocated otherwise.  1 x 64 x 64 models only."""
+    if (model.colour_channels, model.resolution) != (1, 64):        # (first: no Adam over model_down exists at another geometry)
+        raise ValueError(f'train_step: built for 1 x 64 x 64 models, this one is {model.colour_channels} x {model.resolution} x {model.resolution}')
+    opts = _step_optimizers(model, optimizers)
+    e = model._ready()
+    o0 = e.tensor(o0, (-1, 1, 64, 64))
+    M = o0.shape[0]
+    o1 = e.tensor(o1, (M, 1, 64, 64))
+    if omega is None:
+        mode, om, sc = _lib.EFE_OMEGA_DERIVED, None, 1.0
+    else:
+        mode, om, sc = _omega(e, omega, M)
+    a, b, c, d = (_f32(v) for v in omega_params)
+    if means is None:
+        means = e.empty(_lib.EFE_STEP_MEANS)
+    elif not (isinstance(means, torch.Tensor) and means.device == e.device and means.dtype == torch.float32 and means.is_contiguous()
+              and means.numel() == _lib.EFE_STEP_MEANS):
+        raise ValueError(f'train_step: means must be a contiguous float32 tensor of {_lib.EFE_STEP_MEANS} elements on the model device')
+    hyper = [v for o in opts for v in o._hyper()]
+    state = [t for o in opts for t in o._buffers()]
+    pi0, log_Ppi = e.tensor(pi0, (M, model.pi_dim)), e.tensor(log_Ppi, (M, model.pi_dim))
+    nz = model._noise(stage, 0, 0, row_offset)
+    if eps is None and model.eps_source is not None:
+        eps = np.stack([model._src_eps(M, model.s_dim, p, 0, nz.stage, row_offset) for p in (PASS_FE_Q0, PASS_FE_T, PASS_FE_DOWN)], 0)
+    eps_t = e.tensor(eps, (3, M, model.s_dim)) if eps is not None else None
+    outs = e.ops.train_step(e.h, o0, o1, pi0, log_Ppi, _f32(model.gamma), _f32(model.beta_s), _f32(model.beta_o), mode, om, sc, a, b, c, d,
+                            model._seed64(), nz.stage, nz.row_offset, eps_t, *state, hyper, [o._step + 1 for o in opts], means)
+    for o in opts:
+        o._step += 1
+        o._module._stepped()
+    return TrainStep(*outs, means)

@@ -453,6 +453,42 @@ int efe_train_down(efe_ctx*, const float* o1, const float* ps1_mean, const float
 int efe_down_adam_step(efe_ctx*, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
 int efe_down_get_weights(efe_ctx*, float* dst, int64_t n, void* stream);
 
+/* ---- one whole training step: the loop body of the reference's train.py:111-126 (additive to ABI 6) --------------------------------------
+ * One call, one call scope, everything queued on `stream`, no host synchronisation.  At the 1 x 64 x 64 geometry, in this order:
+ *   1. qs0 = encoder_with_sample(o0)                              pass PASS_FE_Q0 (9):  encoder masks + normals (eps plane 0)
+ *   2. the habit net's step (efe_train_top)                       -> kl_pi [M] of the weights before the step
+ *   3. omega [M]: params->omega_mode EFE_OMEGA_DERIVED = compute_omega(kl_pi, a, b, c, d) on the device (train.py:118), the expression
+ *      efe_free_energy evaluates; EFE_OMEGA_ARRAY / EFE_OMEGA_SCALAR: the caller's omega, copied to out->omega
+ *   4. qs1_mean, qs1_logvar = encoder(o1)                         pass PASS_FE_Q1 (10): encoder masks
+ *   5. the transition net's step (efe_train_mid)                  pass PASS_FE_T (11):  -> ps1_mean, ps1_logvar, F_mid before the step
+ *   6. ModelDown's step (efe_train_down)                          pass PASS_FE_DOWN (12), eps plane 2: -> F_down, nlogpo1, kl_s, kl_naive
+ * One stage (nz->stage) per call; nz->pass / nz->sample are not read; rows are keyed by global row nz->row_offset + r.
+ * in->eps: NULL, or injected normals [3][M][s_dim] laid out as efe_free_energy's: plane 0 is the FE_Q0 sample, plane 2 the FE_DOWN
+ * sample, plane 1 is not read (the training call draws no transition normals).
+ * Each part brings its optimiser state and hyper-parameters (efe_step_adam; hp.step = that part's step number, 1 for its first step).
+ * CONTRACT: bit-identical to efe_encoder(PASS_FE_Q0), efe_train_top, efe_encoder(PASS_FE_Q1), efe_train_mid(omega), efe_train_down(omega)
+ * issued one after another with the same seed, stage and row_offset and the per-row omega of step 3: every output, the three master
+ * copies, every packed forward form and all six state vectors.  The call runs those entry points' own launch sequences and adds no
+ * summation of its own, so a step with derived omega equals a step given its own out->omega as EFE_OMEGA_ARRAY.
+ * out->means (optional, EFE_STEP_MEANS floats): the batch means of kl_pi, omega, F_mid, F_down, nlogpo1, kl_s, kl_naive, then the
+ * unbiased standard deviation of omega (train.py:158-159; NaN at M = 1, as torch.std) -- a fixed-order reduction that depends on M alone
+ * (csrc/loss.hip k_step_means), so a loop can log its losses without synchronising every step.
+ * Required: in and its o0, o1, pi0, log_Ppi; params; nz; top, mid, down with both state vectors; out with kl_pi and F_down.  Every
+ * refusal comes before the first launch -- M < 1, a NULL required pointer, an unknown omega_mode or EFE_OMEGA_ARRAY without
+ * params->omega, a geometry other than 1 x 64 x 64, a split-operand option (mfma_bf16x3 / mfma_f16x2) being on, hyper-parameters
+ * efe_adam_step would refuse for any part -- with a message that names efe_train_step; a refused step changes no weight and no state.
+ * Scratch comes from the context's arena (the three parts reuse it one after another). */
+enum { EFE_STEP_MEANS = 8 };
+typedef struct efe_step_in { const float* o0; const float* o1 /*[M,1,64,64]*/; const float* pi0; const float* log_Ppi /*[M,A]*/; const float* eps; } efe_step_in;
+typedef struct efe_step_adam { float* exp_avg; float* exp_avg_sq; efe_adam_params hp; } efe_step_adam;
+/* [M] unless stated; NULL = not wanted, except kl_pi and F_down */
+typedef struct efe_step_out {
+    float* kl_pi; float* omega; float* qs0 /*[M,s]*/; float* F_mid; float* ps1_mean /*[M,s]*/; float* ps1_logvar /*[M,s]*/;
+    float* F_down; float* nlogpo1; float* kl_s; float* kl_naive; float* means /*[EFE_STEP_MEANS]*/;
+} efe_step_out;
+int efe_train_step(efe_ctx*, const efe_step_in* in, int M, const efe_fe_params* params, const efe_noise* nz, const efe_step_adam* top,
+                   const efe_step_adam* mid, const efe_step_adam* down, const efe_step_out* out, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
