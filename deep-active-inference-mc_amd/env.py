@@ -14,6 +14,9 @@ from . import _lib
 from .model import _Engine, _ptr
 
 
+MIN_BANK_IMAGES = 3581
+
+
 def synthetic_sprite_bank(n=3581):
     """deterministic binary sprites, one filled box per index (same rule as oracle/env_oracle.py::sprite_bank)"""
     imgs = torch.zeros(n, 64, 64, dtype=torch.uint8)
@@ -28,14 +31,19 @@ def synthetic_sprite_bank(n=3581):
 class Game:
     def __init__(self, games_no, *, model=None, device=None, imgs=None, seed=0, game_offset=0, init_stage=None):
         self.games_no = int(games_no)
+        bank = synthetic_sprite_bank() if imgs is None else torch.as_tensor(imgs)
+        bank = bank.reshape(-1, 64, 64)
+        # the index rule dot(s[:6], [1,3,6,40,32,32]) reaches 2*3 + 5*6 + 39*40 + 31*32 + 31*32 = 3580; the reference raises on a shorter
+        # bank at the first such frame, and k_env_render's clamp to the last image is memory safety only, not a rule of the game
+        if bank.shape[0] < MIN_BANK_IMAGES:
+            raise ValueError(f'sprite bank has {bank.shape[0]} images; the image index reaches {MIN_BANK_IMAGES - 1}, so at least {MIN_BANK_IMAGES} are needed')
         if model is not None:
             self._engine = model._engine
         else:
             idx = torch.device(device).index or 0 if device is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
             self._engine = _Engine(idx)
         self.device = self._engine.device
-        bank = synthetic_sprite_bank() if imgs is None else torch.as_tensor(imgs)
-        self.imgs = bank.reshape(-1, 64, 64).to(device=self.device, dtype=torch.uint8).contiguous()
+        self.imgs = bank.to(device=self.device, dtype=torch.uint8).contiguous()
         self.s_sizes = torch.tensor([1, 3, 6, 40, 32, 32])
         self.s_bases = torch.tensor([1, 3, 6, 40, 32, 32])
         self.s_dim = 7

@@ -13,37 +13,40 @@ BASES = np.array([1, 3, 6, 40, 32, 32], dtype=np.float32)
 
 
 def env_u(seed, game, stage, blk):
+    """uniform of draw `blk` (latent 0..5, 6 = accumulated reward, 7 = last_r) for one game, or for an array of games at once"""
     k0, k1 = PX._key(seed)
     # game (= game_offset + e) and stage modulo 2^32: the engine's uint32 arithmetic (k_env_*)
-    x0, _, _, _ = PX.philox4x32_10(np.uint64(blk) | (np.uint64(TAG_ENV) << np.uint64(16)), np.uint64(PX.u32(game)),
+    g = np.uint64(PX.u32(game)) if np.ndim(game) == 0 else np.asarray(game, dtype=np.uint64) & PX.MASK32
+    x0, _, _, _ = PX.philox4x32_10(np.uint64(blk) | (np.uint64(TAG_ENV) << np.uint64(16)), g,
                                    np.uint64(PX.stream_id(PASS_ENV, 0)), np.uint64(PX.u32(stage)), k0, k1)
     return PX._u01(np.asarray(x0, dtype=np.uint32))
 
 
 def env_randint(seed, game, stage, latent):
+    """torch.randint(size) of one latent: int(u * size) in fp32, clamped to size - 1 (u rounds to 1.0 for the largest 24-bit word).
+    `game` may be an array."""
     size = SIZES[latent]
-    v = int(np.float32(env_u(seed, game, stage, latent)) * np.float32(size))
-    return min(v, size - 1)
+    v = (np.float32(env_u(seed, game, stage, latent)) * np.float32(size)).astype(np.int64)
+    return np.minimum(v, size - 1) if np.ndim(game) else min(int(v), size - 1)
 
 
 def reset(seed, n_games, stage, game_offset=0):
     s = np.zeros((n_games, 7), dtype=np.float32)
-    last_r = np.zeros(n_games, dtype=np.float32)
-    for e in range(n_games):
-        g = game_offset + e
-        for k in range(6):
-            s[e, k] = env_randint(seed, g, stage, k)
-        s[e, 6] = np.float32(-10.0) + np.float32(env_u(seed, g, stage, 6)) * np.float32(20.0)
-        last_r[e] = np.float32(-1.0) + np.float32(env_u(seed, g, stage, 7)) * np.float32(2.0)
-    return s, last_r
+    g = game_offset + np.arange(n_games, dtype=np.uint64)
+    for k in range(6):
+        s[:, k] = env_randint(seed, g, stage, k)
+    # the product is rounded to fp32 before the add, as torch does (-10 + rand * 20, :74-75)
+    s[:, 6] = np.float32(-10.0) + (env_u(seed, g, stage, 6) * np.float32(20.0)).astype(np.float32)
+    last_r = np.float32(-1.0) + (env_u(seed, g, stage, 7) * np.float32(2.0)).astype(np.float32)
+    return s, last_r.astype(np.float32)
 
 
 def new_image_all(seed, s, stage, game_offset=0):
     """new_image_all (:83-88), in place: fresh latents for every game; the accumulated reward (slot 6) is carried over.
     What the reference constructor calls (:21) on a zero state: reward 0, last_r 0."""
-    for e in range(len(s)):
-        for k in range(6):
-            s[e, k] = env_randint(seed, game_offset + e, stage, k)
+    g = game_offset + np.arange(len(s), dtype=np.uint64)
+    for k in range(6):
+        s[:, k] = env_randint(seed, g, stage, k)
     return s
 
 
@@ -99,6 +102,21 @@ def render(s, last_r, imgs):
             raise ValueError(f'Error: Reward: {r}')
         out[e] = img
     return out
+
+
+SWEEP_R = (0.0, 1.0, -1.0, 0.5, -0.37, 1e-30, -1e-30)
+
+
+def sweep_grid():
+    """the exhaustive one-step grid of tests/golden/env_sweep.npz: game i is the i-th element of shape {0,1,2} x x 0..31 x y 0..31 x
+    action 0..3 (action fastest); scale, orientation, accumulated reward and last_r cycle with periods 6, 40, 11 and 7 (7 and 11 are
+    coprime with every grid period, so each action, x and shape meets every last_r).  -> (s [G,7], last_r [G], actions [G])"""
+    i = np.arange(3 * 32 * 32 * 4)
+    s = np.zeros((len(i), 7), dtype=np.float32)
+    s[:, 1], s[:, 4], s[:, 5] = i // 4096, (i // 128) % 32, (i // 4) % 32
+    s[:, 2], s[:, 3] = (5 * i) % 6, (7 * i) % 40
+    s[:, 6] = np.float32(-3.25) + (i % 11).astype(np.float32)
+    return s, np.array(SWEEP_R, dtype=np.float32)[i % 7], (i % 4).astype(np.int64)
 
 
 def sprite_bank(n=3581):

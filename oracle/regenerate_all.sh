@@ -8,6 +8,7 @@ export PYTHONDONTWRITEBYTECODE=1
 python -m oracle.make_golden            # networks, calculate_G*, rollouts, simulate, planners (injected Philox noise)
 python -m oracle.make_golden_deep       # planners at benchmark depth, upstream-intent reward
 python -m oracle.make_golden_env        # environment (Game) capture
+python -m oracle.make_golden_env --sweep   # ... and one step from every (shape, x, y, action), a long trajectory, the clamped draw
 python -m oracle.make_golden_invalid    # bare-except fallback of mcts_step_simulate
 python -m oracle.make_golden_thr        # the planner's early stops at benchmark depth (thresholds 0.5 / 0.4)
 python -m oracle.make_golden_defaults   # the reference planner at MCTS_Params() defaults (300 repeats) and with simulation_repeats = 2
