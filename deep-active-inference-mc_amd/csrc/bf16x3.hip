@@ -85,7 +85,7 @@ __device__ __forceinline__ void split3_pk(float x0, float x1, uint32_t& hi, uint
 //          an activation below 2^-3 loses at most 2^-25 absolutely -- and must stay below 65 504: a larger one is DETECTED where it is
 //          split and the row / image poisoned (SchH2::overflow below): loud, never silently wrong.  Operand representation error 2^-22 relative: tools/f16_split_check.py.
 //          The poison (+inf rows / images) is read only by these kernels, which end it in a NaN sum: an exact-fp32 kernel behind k_fc4_b3 or
-//          k_dec_a_b3 could turn it into a finite image (relu_bits maps -inf and a negative-signed NaN to 0), so engine.hip run_decoder keeps
+//          k_dec_a_b3 could turn it into a finite image (a ReLU maps -inf to 0), so engine.hip run_decoder keeps
 //          the whole chain split under this scheme -- small launches (k_dec_a_s / quarter sums) take k_fc4, b3_convt3 = 0 is not honoured.
 // Plane 0 = hi.  PA / PB: the weight / activation plane of product pr, small terms first.
 // ---------------------------------------------------------------------------------------------------------
@@ -280,7 +280,7 @@ __global__ void __launch_bounds__(512, 1) k_fc4_b3(const GemmArgs a) {
                         v[2] = acc[mt][nt][4 * g4 + 2] + bb.z; v[3] = acc[mt][nt][4 * g4 + 3] + bb.w;
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = ((word >> ((co + e) & 31)) & 1u) ? fmaxf(v[e], 0.f) * 2.0f : 0.0f;
+                    for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]) * keep2(((word >> ((co + e) & 31)) & 1u));
                     if (SC::SCALED && rbad) v[0] = v[1] = v[2] = v[3] = __builtin_inff();      // an input of this row did not fit fp16: the row is poisoned (k_dec_a_b3 passes it on)
                     *reinterpret_cast<float4*>(yp + co) = make_float4(v[0], v[1], v[2], v[3]);
                 }
@@ -473,8 +473,8 @@ __global__ void __launch_bounds__(512 / NTW, 1) k_dec_a_b3(const DecAArgs a) {
                     for (int g4 = 0; g4 < 4; ++g4)
                     {
                         const float u = SC::SCALED ? a.w1s_inv : 1.0f;      // (fp16 split: the weight scale is undone before the activation is split again)
-                        put_planes(px, mt * 32 + 8 * g4 + 4 * g, SC::SCALED ? relu_bits(acc[mt][nt][4 * g4 + 0]) * u : relu_bits(acc[mt][nt][4 * g4 + 0]), SC::SCALED ? relu_bits(acc[mt][nt][4 * g4 + 1]) * u : relu_bits(acc[mt][nt][4 * g4 + 1]),
-                                   SC::SCALED ? relu_bits(acc[mt][nt][4 * g4 + 2]) * u : relu_bits(acc[mt][nt][4 * g4 + 2]), SC::SCALED ? relu_bits(acc[mt][nt][4 * g4 + 3]) * u : relu_bits(acc[mt][nt][4 * g4 + 3]));
+                        put_planes(px, mt * 32 + 8 * g4 + 4 * g, SC::SCALED ? relu_nan(acc[mt][nt][4 * g4 + 0]) * u : relu_nan(acc[mt][nt][4 * g4 + 0]), SC::SCALED ? relu_nan(acc[mt][nt][4 * g4 + 1]) * u : relu_nan(acc[mt][nt][4 * g4 + 1]),
+                                   SC::SCALED ? relu_nan(acc[mt][nt][4 * g4 + 2]) * u : relu_nan(acc[mt][nt][4 * g4 + 2]), SC::SCALED ? relu_nan(acc[mt][nt][4 * g4 + 3]) * u : relu_nan(acc[mt][nt][4 * g4 + 3]));
                     }
             }
             if (SC::SCALED && ovf) { sovf[fpar] = 1; ovf = 0; }
@@ -510,8 +510,8 @@ __global__ void __launch_bounds__(512 / NTW, 1) k_dec_a_b3(const DecAArgs a) {
 #pragma unroll
                         for (int g4 = 0; g4 < 4; ++g4) {
                             float4 v;
-                            v.x = relu_bits(acc[mt][nt][4 * g4 + 0]); v.y = relu_bits(acc[mt][nt][4 * g4 + 1]);
-                            v.z = relu_bits(acc[mt][nt][4 * g4 + 2]); v.w = relu_bits(acc[mt][nt][4 * g4 + 3]);
+                            v.x = relu_nan(acc[mt][nt][4 * g4 + 0]); v.y = relu_nan(acc[mt][nt][4 * g4 + 1]);
+                            v.z = relu_nan(acc[mt][nt][4 * g4 + 2]); v.w = relu_nan(acc[mt][nt][4 * g4 + 3]);
                             if (SC::SCALED) { v.x *= a.w2s_inv; v.y *= a.w2s_inv; v.z *= a.w2s_inv; v.w *= a.w2s_inv; }
                             if (SC::SCALED && ibad) v.x = v.y = v.z = v.w = __builtin_inff();      // x4 or y1 did not fit fp16: the image is poisoned (k_dec_b_b3 turns it into a NaN sum)
                             yp[(mt * 4 + g4) * 512] = v;
@@ -778,7 +778,7 @@ __global__ void __launch_bounds__(512, 1) k_dec_b_b3(const DecBArgs a) {
             {
                 f32x4 Tq[2][3];
 #pragma unroll
-                for (int e = 0; e < 16; ++e) { acc[0][e] = relu_bits(acc[0][e]); acc[1][e] = relu_bits(acc[1][e]); }
+                for (int e = 0; e < 16; ++e) { acc[0][e] = relu_nan(acc[0][e]); acc[1][e] = relu_nan(acc[1][e]); }
 #pragma unroll
                 for (int pw = 0; pw < 2; ++pw)
 #pragma unroll

@@ -285,8 +285,8 @@ __device__ __forceinline__ void f22_l2_store(f32x4 (&acc)[16], const __amdgpu_bu
             u32x4 lo, hi;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const unsigned x0 = __builtin_bit_cast(unsigned, relu_bits(acc[4 * orow + c][e]));
-                const unsigned x1 = __builtin_bit_cast(unsigned, relu_bits(acc[4 * orow + c + 2][e]));
+                const unsigned x0 = __builtin_bit_cast(unsigned, relu_nan(acc[4 * orow + c][e]));
+                const unsigned x1 = __builtin_bit_cast(unsigned, relu_nan(acc[4 * orow + c + 2][e]));
                 const auto sw = __builtin_amdgcn_permlane32_swap(x0, x1, false, false);
                 lo[e] = sw[0]; hi[e] = sw[1];
             }
@@ -378,8 +378,8 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const f32x16& o = l1o[rc >> 1][rc & 1];
                     float4 v;
-                    v.x = relu_bits(o[4 * g4 + 0]); v.y = relu_bits(o[4 * g4 + 1]);
-                    v.z = relu_bits(o[4 * g4 + 2]); v.w = relu_bits(o[4 * g4 + 3]);
+                    v.x = relu_nan(o[4 * g4 + 0]); v.y = relu_nan(o[4 * g4 + 1]);
+                    v.z = relu_nan(o[4 * g4 + 2]); v.w = relu_nan(o[4 * g4 + 3]);
                     sm[pix * DA_PS + l1mt * 8 + 2 * g4 + h] = v;
                 }
             }
@@ -501,8 +501,8 @@ __global__ void __launch_bounds__(256, 2) k_dec_a_s(const DecAArgs a) {
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 float4 v;
-                v.x = relu_bits(o[0][c][4 * g4 + 0]); v.y = relu_bits(o[0][c][4 * g4 + 1]);
-                v.z = relu_bits(o[0][c][4 * g4 + 2]); v.w = relu_bits(o[0][c][4 * g4 + 3]);
+                v.x = relu_nan(o[0][c][4 * g4 + 0]); v.y = relu_nan(o[0][c][4 * g4 + 1]);
+                v.z = relu_nan(o[0][c][4 * g4 + 2]); v.w = relu_nan(o[0][c][4 * g4 + 3]);
                 sl1[((ly + 1 + r) * 16 + lx + 1 + c) * DA_PS + mt * 8 + 2 * g4 + h] = v;
             }
     }
@@ -790,7 +790,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
 #pragma unroll
             for (int oc = 0; oc < 4; ++oc)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[4 * orow + oc][e] = relu_bits(acc[4 * orow + oc][e]);
+                for (int e = 0; e < 4; ++e) acc[4 * orow + oc][e] = relu_nan(acc[4 * orow + oc][e]);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -944,7 +944,7 @@ __global__ void __launch_bounds__(256, 2) k_fc4(const GemmArgs a) {
                     float v[4] = {acc[mt][nt][4 * g4 + 0] + bb.x, acc[mt][nt][4 * g4 + 1] + bb.y,
                                   acc[mt][nt][4 * g4 + 2] + bb.z, acc[mt][nt][4 * g4 + 3] + bb.w};
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = ((word >> ((co + e) & 31)) & 1u) ? fmaxf(v[e], 0.f) * 2.0f : 0.0f;
+                    for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]) * keep2(((word >> ((co + e) & 31)) & 1u));
                     *reinterpret_cast<float4*>(yp + co) = make_float4(v[0], v[1], v[2], v[3]);
                 }
         }

@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(256, EFE_ENC_WAVES) k_enc_trunk(const EncArgs 
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) bx[nt][e] = relu_bits(bx[nt][e]);
+                    for (int e = 0; e < 16; ++e) bx[nt][e] = relu_nan(bx[nt][e]);
             };
             auto shl = [&](f32x16 (&bx)[2], int kc) {
 #pragma unroll
@@ -162,8 +162,8 @@ __global__ void __launch_bounds__(256, EFE_ENC_WAVES) k_enc_trunk(const EncArgs 
                     const int c4 = 2 * g4 + h;
                     const float4 bb = sm4[EN_B2 / 4 + c4];
                     float4 v;
-                    v.x = fmaxf(acc[nt][4 * g4 + 0] + bb.x, 0.f); v.y = fmaxf(acc[nt][4 * g4 + 1] + bb.y, 0.f);
-                    v.z = fmaxf(acc[nt][4 * g4 + 2] + bb.z, 0.f); v.w = fmaxf(acc[nt][4 * g4 + 3] + bb.w, 0.f);
+                    v.x = relu_nan(acc[nt][4 * g4 + 0] + bb.x); v.y = relu_nan(acc[nt][4 * g4 + 1] + bb.y);
+                    v.z = relu_nan(acc[nt][4 * g4 + 2] + bb.z); v.w = relu_nan(acc[nt][4 * g4 + 3] + bb.w);
                     sm4[EN_C2 / 4 + m[nt] * EN_P2 + c4] = v;
                 }
             }
@@ -192,8 +192,8 @@ __global__ void __launch_bounds__(256, EFE_ENC_WAVES) k_enc_trunk(const EncArgs 
                     const int c4 = mt * 8 + 2 * g4 + h;
                     const float4 bb = sm4[EN_B3 / 4 + c4];
                     float4 v;
-                    v.x = fmaxf(acc[0][0][4 * g4 + 0] + bb.x, 0.f); v.y = fmaxf(acc[0][0][4 * g4 + 1] + bb.y, 0.f);
-                    v.z = fmaxf(acc[0][0][4 * g4 + 2] + bb.z, 0.f); v.w = fmaxf(acc[0][0][4 * g4 + 3] + bb.w, 0.f);
+                    v.x = relu_nan(acc[0][0][4 * g4 + 0] + bb.x); v.y = relu_nan(acc[0][0][4 * g4 + 1] + bb.y);
+                    v.z = relu_nan(acc[0][0][4 * g4 + 2] + bb.z); v.w = relu_nan(acc[0][0][4 * g4 + 3] + bb.w);
                     sm4[EN_C3 / 4 + m * EN_P3 + c4] = v;
                 }
             }
@@ -237,8 +237,8 @@ __global__ void __launch_bounds__(256, EFE_ENC_WAVES) k_enc_trunk(const EncArgs 
                 const int c4 = w * 4 + q;
                 const float4 bb = sm4[EN_B4 / 4 + c4];
                 float4 v;
-                v.x = fmaxf(c0[0] + c1[0] + bb.x, 0.f); v.y = fmaxf(c0[1] + c1[1] + bb.y, 0.f);
-                v.z = fmaxf(c0[2] + c1[2] + bb.z, 0.f); v.w = fmaxf(c0[3] + c1[3] + bb.w, 0.f);
+                v.x = relu_nan(c0[0] + c1[0] + bb.x); v.y = relu_nan(c0[1] + c1[1] + bb.y);
+                v.z = relu_nan(c0[2] + c1[2] + bb.z); v.w = relu_nan(c0[3] + c1[3] + bb.w);
                 reinterpret_cast<float4*>(a.out + (size_t)img * 576 + px * 64)[c4] = v;
             }
         }

@@ -859,7 +859,7 @@ int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const Nois
     const DecPlan p = dec_plan(ctx, N);
     const bool split = p.split;
     // mfma_f16x2 marks a row / image whose activation overflowed fp16 with +inf, and only its own split kernels turn that into a NaN
-    // sum: an exact-fp32 consumer (k_dec_a_s / k_dec_a / k_dec_b4) can make a finite wrong image of it (inf - inf = NaN, and relu_bits
+    // sum: an exact-fp32 consumer (k_dec_a_s / k_dec_a / k_dec_b4) can make a finite wrong image of it (inf - inf = NaN, and a ReLU
     // maps a negative-signed NaN or -inf to 0).  So under that mode the chain is split from k_fc4_b3 to k_dec_b_b3 or not at all: small
     // launches keep k_fc4 too, and ConvT3 always runs on k_dec_b_b3 (b3_convt3 = 0 applies to mfma_bf16x3, which cannot overflow).
     const bool f16 = ctx->mfma_bf16x3 == 2;

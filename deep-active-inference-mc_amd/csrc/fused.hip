@@ -101,13 +101,13 @@ __device__ __forceinline__ void hidden16(const float4* __restrict__ Wp, const fl
         float v[4] = {acc[mt][0] + bq[mt].x, acc[mt][1] + bq[mt].y, acc[mt][2] + bq[mt].z, acc[mt][3] + bq[mt].w};
         if (RELU) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+            for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
         }
         if (DROP) {
             const int wsel = (f >> 5) & 3;
             const uint32_t word = wsel == 0 ? rnd.x : wsel == 1 ? rnd.y : wsel == 2 ? rnd.z : rnd.w;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = ((word >> ((f + e) & 31)) & 1u) ? v[e] * 2.0f : 0.0f;
+            for (int e = 0; e < 4; ++e) v[e] = v[e] * keep2(((word >> ((f + e) & 31)) & 1u));
         }
         act_out[aswz(n, 4 * (mt0 + mt) + q)] = make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -170,14 +170,14 @@ __device__ __forceinline__ float4 hidden16_slice(const float4* __restrict__ Wp, 
     float v[4] = {acc[0][0] + bq.x, acc[0][1] + bq.y, acc[0][2] + bq.z, acc[0][3] + bq.w};
     if (RELU) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+        for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
     }
     if (DROP) {
         const uint4 rnd = noise_words(k0, k1, tag, (uint32_t)(f >> 7), rk.row, rk.stream, rk.stage);
         const int wsel = (f >> 5) & 3;
         const uint32_t word = wsel == 0 ? rnd.x : wsel == 1 ? rnd.y : wsel == 2 ? rnd.z : rnd.w;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = ((word >> ((f + e) & 31)) & 1u) ? v[e] * 2.0f : 0.0f;
+        for (int e = 0; e < 4; ++e) v[e] = v[e] * keep2(((word >> ((f + e) & 31)) & 1u));
     }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
@@ -521,7 +521,7 @@ __device__ __forceinline__ void head_layer(const float4* __restrict__ Wp, const 
                 const int wsel = (f >> 5) & 3;
                 const uint32_t word = wsel == 0 ? rnd.x : wsel == 1 ? rnd.y : wsel == 2 ? rnd.z : rnd.w;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = ((word >> ((f + e) & 31)) & 1u) ? fmaxf(v[e], 0.0f) * 2.0f : 0.0f;
+                for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]) * keep2(((word >> ((f + e) & 31)) & 1u));
             }
             act_out[aswz64(16 * nb + n, 4 * (mt0 + mt) + q)] = make_float4(v[0], v[1], v[2], v[3]);
         }

@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(256) k_conv_g(const ConvGArgs a) {
                                   acc[mt][nt][4 * g4 + 3] + bb.w};
                     if (a.relu) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+                        for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
                     }
                     *reinterpret_cast<float4*>(yp + co) = make_float4(v[0], v[1], v[2], v[3]);
                 }

@@ -157,7 +157,7 @@ __device__ __forceinline__ void convt_store(const f32x16 (&ac)[CONVT_PASS[P].NAC
 #pragma unroll
             for (int pw = 0; pw < CONVT_PASS[P].NAC; ++pw) {
                 float v = ac[pw][4 * g4 + i];
-                if (relu) v = fmaxf(v, 0.0f);
+                if (relu) v = relu_nan(v);
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr, o, P == 2 ? 0u : (unsigned)((P * Wout + pw) * ldo) * 4u, 0);
             }
         }
@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(256, 2) k_convt_12(const ConvT12Args a) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {            // (a pixel outside the strip goes to a dummy slot: an address select, not a branch per element)
                         const int qa = nt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                        y1f[qa < nq ? ybase + qa * (PS4 * 4) : ydummy] = fmaxf(ac[0][e], 0.0f);
+                        y1f[qa < nq ? ybase + qa * (PS4 * 4) : ydummy] = relu_nan(ac[0][e]);
                     }
                 });
             } else {
@@ -869,7 +869,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_bg(const DecBGArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             // ---- ReLU + tap contraction of output rows 2 y: T = Wt x relu(acc) (two column parities)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) { acc[0][e] = relu_bits(acc[0][e]); acc[1][e] = relu_bits(acc[1][e]); T0[e] = 0.f; T1[e] = 0.f; }
+            for (int e = 0; e < 16; ++e) { acc[0][e] = relu_nan(acc[0][e]); acc[1][e] = relu_nan(acc[1][e]); T0[e] = 0.f; T1[e] = 0.f; }
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 T0 = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[e], acc[0][e], T0, 0, 0, 0);
@@ -904,7 +904,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_bg(const DecBGArgs a) {
         ring_addr(0, hpa, epa);
         int nb = bs + RP; nb = nb >= RPa ? nb - RPa : nb;       // uniform: slot of pixel (r0 + TH + 1, 0)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[2][e] = relu_bits(acc[2][e]); acc[3][e] = relu_bits(acc[3][e]); U0[e] = 0.f; U1[e] = 0.f; }
+        for (int e = 0; e < 16; ++e) { acc[2][e] = relu_nan(acc[2][e]); acc[3][e] = relu_nan(acc[3][e]); U0[e] = 0.f; U1[e] = 0.f; }
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
 #pragma unroll

@@ -31,8 +31,8 @@ __device__ __forceinline__ void bias_relu_store(float4* op, const f32x16& acc, c
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         float4 v;
-        v.x = fmaxf(acc[4 * g] + bq[g].x, 0.f); v.y = fmaxf(acc[4 * g + 1] + bq[g].y, 0.f);
-        v.z = fmaxf(acc[4 * g + 2] + bq[g].z, 0.f); v.w = fmaxf(acc[4 * g + 3] + bq[g].w, 0.f);
+        v.x = relu_nan(acc[4 * g] + bq[g].x); v.y = relu_nan(acc[4 * g + 1] + bq[g].y);
+        v.z = relu_nan(acc[4 * g + 2] + bq[g].z); v.w = relu_nan(acc[4 * g + 3] + bq[g].w);
         op[2 * g] = v;
     }
 }

@@ -63,6 +63,28 @@ __device__ __forceinline__ bool row_live(const RowMask& k, int m) {
     return k.mask[k.ids ? k.ids[slot] : slot] != 0;
 }
 
+// Non-finite propagation ("Non-finite values"): the forms every layer epilogue and backward gate is written in.
+//   relu_nan : torch's relu -- max(x, 0) that RETURNS a NaN x of either sign (fmaxf returns 0 for it, a signed-integer maximum of the bit
+//              pattern 0 for a negative-signed one).  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950; -0 gives +0, finite values and
+//              +inf keep every bit.
+//   keep2    : the factor of a dropout mask, 2 for a kept unit and 0 for a dropped one.  The mask MULTIPLIES (h * mask, as F.dropout
+//              does): a dropped NaN or inf unit stays NaN, which a select (keep ? 2 h : 0) would turn into 0.
+//   gate_open: torch's threshold_backward zeroes the upstream gradient only where the stored activation is <= 0, so a NaN activation lets it
+//              through (a > 0 test would zero it).
+//   gated    : the gradient t behind a ReLU (and, `masked`, a dropout mask whose factor t already carries), read off the ONE stored
+//              activation h = relu(x) [* mask].  Open gate: t.  Closed without a mask: exactly 0, as threshold_backward gives.  Closed behind a
+//              mask, h = 0 is an inactive unit (torch: 0) or an active dropped one (torch: t * 0, NaN for a non-finite t) and the stored value
+//              cannot tell which: t - t serves both -- +0 for every finite t (the same bits as the select), NaN for a non-finite one.  That
+//              is a superset of torch's NaN set, inside rows whose upstream gradient is not finite already.
+__device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
+__device__ __forceinline__ float keep2(bool keep) { return keep ? 2.0f : 0.0f; }
+__device__ __forceinline__ bool gate_open(float a) { return !(a <= 0.0f); }
+__device__ __forceinline__ float gated(float h, float t, bool relu, bool masked) {
+#pragma clang fp contract(off)
+    if (!relu || gate_open(h)) return t;
+    return masked ? t - t : 0.0f;
+}
+
 // One pixel's term of the reward log-likelihood log_bernoulli(x = pr, p = target) (/root/reference/src/torchutils.py:30-37):
 //   intent 0: what the shipped port computes -- on NCHW input the target broadcasts to 1 for image rows oh < H / 2 and 0 below, and
 //             every pixel counts (pinned by the oracle);

@@ -155,13 +155,13 @@ __global__ void __launch_bounds__(256) k_dense(const GemmArgs a) {
                                   acc[mt][nt][4 * g4 + 2] + bb.z, acc[mt][nt][4 * g4 + 3] + bb.w};
                     if (a.relu) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+                        for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
                     }
                     if (a.dropout) {
                         const uint32_t word = ((co >> 5) & 3) == 0 ? rnd.x : ((co >> 5) & 3) == 1 ? rnd.y
                                             : ((co >> 5) & 3) == 2 ? rnd.z : rnd.w;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = ((word >> ((co + e) & 31)) & 1u) ? v[e] * 2.0f : 0.0f;
+                        for (int e = 0; e < 4; ++e) v[e] = v[e] * keep2(((word >> ((co + e) & 31)) & 1u));
                     }
                     *reinterpret_cast<float4*>(a.Y + yoff + co) = make_float4(v[0], v[1], v[2], v[3]);
                 }

@@ -62,11 +62,8 @@ __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
     return r;
 }
 
-// max(x, 0) for fp32 as a signed-integer max of the bit pattern: negative floats (and -0, -NaN) are negative integers.
-__device__ __forceinline__ float relu_bits(float x) {
-    const int b = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
+// (the epilogues' ReLU is kernels.h's relu_nan: the signed-integer maximum of the bit pattern that stood here kept a positive-signed NaN
+//  and turned a negative-signed one into 0)
 
 // sigmoid and natural log on the hardware transcendental instructions alone (v_exp_f32 = 2^x, v_rcp_f32, v_log_f32 = log2 x: 1 ulp each).
 // __expf / __logf add a denormal-range rescue (compare + ldexp + select per call) that these call sites do not need: the log arguments

@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) k_top_grad(const TopGradArgs a) {
                 for (int e = 0; e < 4; ++e) {
                     const int f = f0 + 4 * q + e;
                     float v = acc[e] + B[f < O ? f : 0];
-                    if (relu) v = fmaxf(v, 0.0f);
+                    if (relu) v = relu_nan(v);
                     // (the habit net has no dropout: L.drop_tag is 0 in its table; k_mid_grad below is the kernel for layers that carry one)
                     y[n][f] = f < O ? v : 0.0f;
                 }
@@ -197,7 +197,7 @@ __global__ void __launch_bounds__(256) k_top_grad(const TopGradArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int f = i0 + 4 * q + e;
-                        dn[n][f] = (f < K && (!relu || x[n][f] > 0.0f)) ? acc[e] : 0.0f;
+                        dn[n][f] = (f < K && (!relu || gate_open(x[n][f]))) ? acc[e] : 0.0f;
                     }
                 }
                 cur ^= 1;
@@ -311,8 +311,8 @@ __global__ void __launch_bounds__(256, 1) k_mid_grad(const MidGradArgs a) {
                 for (int e = 0; e < 4; ++e) {
                     const int f = f0 + 4 * q + e;
                     float v = sum[e] + B[f < O ? f : 0];
-                    if (relu) v = fmaxf(v, 0.0f);
-                    if (tag) v = ((word >> (f & 31)) & 1u) ? v * 2.0f : 0.0f;
+                    if (relu) v = relu_nan(v);
+                    if (tag) v = v * keep2(((word >> (f & 31)) & 1u));
                     o4[e] = f < O ? v : 0.0f;
                 }
                 *reinterpret_cast<float4*>(y + f0 + 4 * q) = out;
@@ -423,10 +423,10 @@ __global__ void __launch_bounds__(256, 1) k_mid_grad(const MidGradArgs a) {
                     float* hp = x + n * xs + i0 + 4 * q;
                     const float4 h = *reinterpret_cast<const float4*>(hp);
                     float4 g;
-                    g.x = (!Lp.relu || h.x > 0.0f) ? keep * sum[0] : 0.0f;
-                    g.y = (!Lp.relu || h.y > 0.0f) ? keep * sum[1] : 0.0f;
-                    g.z = (!Lp.relu || h.z > 0.0f) ? keep * sum[2] : 0.0f;
-                    g.w = (!Lp.relu || h.w > 0.0f) ? keep * sum[3] : 0.0f;
+                    g.x = gated(h.x, keep * sum[0], Lp.relu, keep != 1.0f);
+                    g.y = gated(h.y, keep * sum[1], Lp.relu, keep != 1.0f);
+                    g.z = gated(h.z, keep * sum[2], Lp.relu, keep != 1.0f);
+                    g.w = gated(h.w, keep * sum[3], Lp.relu, keep != 1.0f);
                     *reinterpret_cast<float4*>(hp) = g;
                 }
             }

@@ -134,10 +134,10 @@ __global__ void __launch_bounds__(256) k_dect_tap(const float* __restrict__ src,
             float v = total[t][e];
             if (BWD) {
                 const size_t idx = (((size_t)r * CI + oc) * HIN + vy) * HIN + vx;
-                if (gate) v = gate[idx] > 0.0f ? v : 0.0f;
+                if (gate) v = gate_open(gate[idx]) ? v : 0.0f;
                 dst[idx] = v;
             } else {
-                v = fmaxf(v + bias[oc], 0.0f);
+                v = relu_nan(v + bias[oc]);
                 dst[(((size_t)r * CO + oc) * HOUT + (S * vy + py)) * HOUT + (S * vx + px)] = v;
             }
         }
@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(256) k_dect_dx4(const float* __restrict__ g4, 
 #pragma unroll
         for (int t = 0; t < 9; ++t) c = fmaf(gv[t], w4[ci * 9 + t], c);          // (an out-of-range term is an exact + 0)
         const size_t idx = ((size_t)r * 32 + ci) * 4096 + pix;
-        g3[idx] = y3[idx] > 0.0f ? c : 0.0f;
+        g3[idx] = gate_open(y3[idx]) ? c : 0.0f;
     }
 }
 

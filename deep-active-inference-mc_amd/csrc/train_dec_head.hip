@@ -134,10 +134,10 @@ __global__ void __launch_bounds__(256) k_dech_gate(const float* __restrict__ h4,
     if (i >= n4) return;
     const float4 h = reinterpret_cast<const float4*>(h4)[i];
     float4 v = reinterpret_cast<float4*>(g)[i];
-    v.x = h.x > 0.0f ? 2.0f * v.x : 0.0f;
-    v.y = h.y > 0.0f ? 2.0f * v.y : 0.0f;
-    v.z = h.z > 0.0f ? 2.0f * v.z : 0.0f;
-    v.w = h.w > 0.0f ? 2.0f * v.w : 0.0f;
+    v.x = gated(h.x, 2.0f * v.x, true, true);
+    v.y = gated(h.y, 2.0f * v.y, true, true);
+    v.z = gated(h.z, 2.0f * v.z, true, true);
+    v.w = gated(h.w, 2.0f * v.w, true, true);
     reinterpret_cast<float4*>(g)[i] = v;
 }
 
@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(256) k_dech_small(const DecHeadArgs a) {
                 j8[j] = sm;
             }
             const float sum = ((j8[0] + j8[1]) + (j8[2] + j8[3])) + ((j8[4] + j8[5]) + (j8[6] + j8[7]));
-            g = a.h3[(size_t)row * 256 + k] > 0.0f ? 2.0f * sum : 0.0f;
+            g = gated(a.h3[(size_t)row * 256 + k], 2.0f * sum, true, true);
             x2 = a.h2[(size_t)row * 256 + k];
             x1 = a.h1[(size_t)row * 256 + k];
         }

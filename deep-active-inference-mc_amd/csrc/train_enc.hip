@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) k_enc_conv1(const float* __restrict__ o, 
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) c = fmaf(x[ky * 64 + kx], wp[3 * ky + kx], c);
-    y1[i] = fmaxf(c + w[EQ_B1 + co], 0.0f);
+    y1[i] = relu_nan(c + w[EQ_B1 + co]);
 }
 
 // layers 2..4: x [rows][CI][HIN][HIN] -> y = relu(conv + bias) [rows][CO][HOUT][HOUT], HOUT = (HIN - 1) / 2
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256) k_enc_conv(const float* __restrict__ x, c
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int co = co0 + 4 * q + e;                                               // D(i = 4 q + e, j = n)
-        y[((size_t)r * CO + co) * HW + pos] = fmaxf(total[e] + bias[co], 0.0f);
+        y[((size_t)r * CO + co) * HW + pos] = relu_nan(total[e] + bias[co]);
     }
 }
 
@@ -428,7 +428,7 @@ __global__ void __launch_bounds__(256) k_enc_dx(const float* __restrict__ g, con
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const size_t idx = ((size_t)r * CI + ci0 + 4 * q + e) * HIN * HIN + iy * HIN + ix;      // D(i = 4 q + e, j = n)
-        dx[idx] = gate[idx] > 0.0f ? total[e] : 0.0f;
+        dx[idx] = gate_open(gate[idx]) ? total[e] : 0.0f;
     }
 }
 

@@ -58,8 +58,8 @@ __device__ __forceinline__ uint32_t mask_word(const uint4& r, int f0) { return p
 // ReLU and mask of one pre-activation: the stored value is relu(v) * keep * 2
 __device__ __forceinline__ float relu_drop(float v, bool relu, bool drop, uint32_t word, int bit) {
 #pragma clang fp contract(off)
-    if (relu) v = fmaxf(v, 0.0f);
-    if (drop) v = ((word >> bit) & 1u) ? v * 2.0f : 0.0f;
+    if (relu) v = relu_nan(v);
+    if (drop) v = v * keep2(((word >> bit) & 1u));
     return v;
 }
 
@@ -164,10 +164,10 @@ __device__ __forceinline__ void dprev_pass(const float* d, int dld, float* x, in
         float* hp = x + n * xld + i0 + 4 * q;
         const float4 h = *reinterpret_cast<const float4*>(hp);
         float4 g;
-        g.x = (!relu || h.x > 0.0f) ? keep * sum[0] : 0.0f;
-        g.y = (!relu || h.y > 0.0f) ? keep * sum[1] : 0.0f;
-        g.z = (!relu || h.z > 0.0f) ? keep * sum[2] : 0.0f;
-        g.w = (!relu || h.w > 0.0f) ? keep * sum[3] : 0.0f;
+        g.x = gated(h.x, keep * sum[0], relu, keep != 1.0f);
+        g.y = gated(h.y, keep * sum[1], relu, keep != 1.0f);
+        g.z = gated(h.z, keep * sum[2], relu, keep != 1.0f);
+        g.w = gated(h.w, keep * sum[3], relu, keep != 1.0f);
         *reinterpret_cast<float4*>(hp) = g;
     }
 }

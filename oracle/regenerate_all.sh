@@ -10,7 +10,8 @@ python -m oracle.make_golden_deep       # planners at benchmark depth, upstream-
 python -m oracle.make_golden_env        # environment (Game) capture
 python -m oracle.make_golden_env --sweep   # ... and one step from every (shape, x, y, action), a long trajectory, the clamped draw
 python -m oracle.make_golden_invalid    # bare-except fallback of mcts_step_simulate
-python -m oracle.make_golden_thr        # the planner's early stops at benchmark depth (thresholds 0.5 / 0.4)
+python -m oracle.make_golden_nonfinite  # isnan / isinf masks of the four networks with one non-finite input or weight element
+python -m oracle.make_golden_thr     # the planner's early stops at benchmark depth (thresholds 0.5 / 0.4)
 python -m oracle.make_golden_defaults   # the reference planner at MCTS_Params() defaults (300 repeats) and with simulation_repeats = 2
 python -m oracle.make_golden_stats      # SAMPLES of the unpatched reference under torch's own generator (statistical pin)
 python -m oracle.make_golden_stats_planner   # ... and 512 whole planner decisions under that generator

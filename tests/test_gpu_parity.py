@@ -1598,6 +1598,33 @@ def test_fp16_split_overflow_is_loud(weights_cache):
     np.testing.assert_allclose(got[~bad], ref[~bad], rtol=1e-5, atol=4e-6)      # ... and every image that did not is still right
 
 
+@pytest.mark.parametrize('dec_split', [1, 0])
+def test_fp16_split_overflow_at_a_small_launch(weights_cache, dec_split):
+    """the same overflow weights at N = 100, a launch of at most 128 images.  With the default dec_split such a launch keeps the exact fp32
+    chain under mfma_f16x2 (engine.hip run_decoder: an fp32 consumer could make a finite wrong image of the split kernels' overflow mark):
+    every image is finite and within the file's sigmoid tolerance of the exact fp32 result.  With dec_split = 0 it runs the split kernels:
+    some image is not finite, and no image is finite and outside that tolerance."""
+    import daimc_amd
+    w = dict(weights_cache(1234, 1.15))
+    w['down.po_net.9.weight'] = w['down.po_net.9.weight'] * np.float32(1.0e6)
+    w['down.po_net.13.weight'] = w['down.po_net.13.weight'] * np.float32(1.0e-6)
+    m = daimc_amd.ActiveInferenceModel(10, 4, 0.0, 1.0, 1.0, device='cuda:0', seed=5, init_weights=False)
+    m.load_flat_weights(w)
+    s = PX.uniform_fill(13, (100, 10), 401, -1.5, 1.5)
+    ref = c(m.model_down.decoder(s, stage=2, pass_=PX.PASS_D1))
+    assert np.isfinite(ref).all()
+    m.set_option('dec_split', dec_split)
+    m.set_option('mfma_f16x2', 1)
+    got = c(m.model_down.decoder(s, stage=2, pass_=PX.PASS_D1))
+    bad = ~np.isfinite(got).all(axis=(1, 2, 3))
+    print(f'dec_split {dec_split}: {int(bad.sum())} of 100 images not finite; max |got - ref| over the finite ones {np.abs(got[~bad] - ref[~bad]).max(initial=0.0):.3e}')
+    if dec_split:
+        assert not bad.any()
+    else:
+        assert bad.any()
+    np.testing.assert_allclose(got[~bad], ref[~bad], rtol=1e-5, atol=4e-6)
+
+
 def test_split_operands_are_off_by_default_and_refused_on_other_geometries(models):
     import daimc_amd
     m = models(1234, 1.15, 3)

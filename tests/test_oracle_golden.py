@@ -130,6 +130,30 @@ def test_simulate_invalid_posterior_vs_reference(golden, weights_cache):
         assert np.array_equal(q.numpy(), g['Qpi'])
 
 
+def test_nonfinite_masks_vs_reference(golden):
+    """where the reference puts NaN and inf when one input or one weight element of a network is not finite (oracle/make_golden_nonfinite.py:
+    +NaN, -NaN, +inf, -inf in a state row / an observation pixel, a NaN weight in the decoder's last dense layer and behind the transition's
+    first dropout mask): the fp32 oracle reproduces both masks of every case exactly, and none of them is empty -- the evidence that the
+    oracle is a valid reference of non-finite propagation for the engine (tests/test_nonfinite_gpu.py)"""
+    from oracle import nonfinite as NF
+    g = golden('nonfinite_ref')
+    assert (int(g['wseed']), float(g['gain']), int(g['nseed']), int(g['stage']), int(g['rows'])) == (NF.WSEED, NF.GAIN, NF.NSEED, NF.STAGE, NF.M)
+    cases = NF.cases()
+    assert {k[:-5] for k in g if k.endswith('__nan')} == set(cases) and len(cases) == 4 * 4 + 2
+    with torch.no_grad():
+        for case, (net, weights, frames, s, pi) in cases.items():
+            out = NF.run_net(NF.oracle_calls(EO.OracleModel(weights, EO.PhiloxNoise(NF.NSEED))), net, frames, s, pi)
+            assert out.shape == (NF.M, int(g[case + '__n'])), case
+            ref_nan = np.unpackbits(g[case + '__nan'])[:out.size].astype(bool).reshape(out.shape)
+            ref_inf = np.unpackbits(g[case + '__inf'])[:out.size].astype(bool).reshape(out.shape)
+            assert np.array_equal(np.isnan(out), ref_nan), case
+            assert np.array_equal(np.isinf(out), ref_inf), case
+            bad = ~np.isfinite(out).all(axis=1)
+            assert bad.any(), case
+            if case not in NF.WEIGHT_CASES:                 # an input case: the poisoned row and no other
+                assert np.flatnonzero(bad).tolist() == [NF.BAD_ROW], case
+
+
 def test_convtranspose_subpixel_restatement():
     """independent numpy restatement of ConvTranspose2d(k3,s2,p1,op1) in the 4-parity form the HIP kernel
     uses against torch's conv_transpose2d."""
