@@ -15,3 +15,5 @@ from .loss import free_energy, FreeEnergy, train_step, TrainStep  # noqa: F401
 from .optim import Adam  # noqa: F401
 from . import train  # noqa: F401
 from .train import Trainer  # noqa: F401
+from . import agent  # noqa: F401
+from .agent import AgentRunner, AgentState, run_agent  # noqa: F401

@@ -16,13 +16,22 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down',
            'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top',
            'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
-           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step']
+           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step',
+           'efe_encoder_rows', 'efe_rollout_rows', 'efe_agent_need', 'efe_agent_choose', 'efe_agent_enqueue', 'efe_agent_act']
 ABI_VERSION = 6
 
 
 class EfeMctsTree(C.Structure):
     _fields_ = [('W', C.c_void_p), ('N', C.c_void_p), ('Qpi', C.c_void_p), ('child', C.c_void_p), ('S', C.c_void_p),
                 ('E', C.c_int32), ('cap', C.c_int32), ('A', C.c_int32), ('s_dim', C.c_int32)]
+
+
+class EfeAgent(C.Structure):
+    _fields_ = [('queue', C.c_void_p), ('head', C.c_void_p), ('len', C.c_void_p), ('crossings', C.c_void_p), ('reward_sum', C.c_void_p),
+                ('E', C.c_int32), ('cap', C.c_int32)]
+
+
+EFE_AGENT_AI, EFE_AGENT_T1, EFE_AGENT_T12, EFE_AGENT_PROBS = 0, 1, 2, 3
 
 
 class EfeNoise(C.Structure):
@@ -184,5 +193,12 @@ def load():
     lib.efe_down_get_weights.argtypes = [p, f32p, C.c_int64, p]; lib.efe_down_get_weights.restype = i
     sap = C.POINTER(EfeStepAdam)
     lib.efe_train_step.argtypes = [p, C.POINTER(EfeStepIn), i, fpp, nzp, sap, sap, sap, C.POINTER(EfeStepOut), p]; lib.efe_train_step.restype = i
+    lib.efe_encoder_rows.argtypes = [p, f32p, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_encoder_rows.restype = i
+    lib.efe_rollout_rows.argtypes = [p, f32p, f32p, i, i, i, i, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_rollout_rows.restype = i
+    agp = C.POINTER(EfeAgent)
+    lib.efe_agent_need.argtypes = [p, agp, p, p, p]; lib.efe_agent_need.restype = i
+    lib.efe_agent_choose.argtypes = [p, agp, p, i, i, f32p, f32p, f32p, i, C.c_float, i, nzp, f32p, p, f32p, p]; lib.efe_agent_choose.restype = i
+    lib.efe_agent_enqueue.argtypes = [p, agp, p, i, p, p, i, i, p]; lib.efe_agent_enqueue.restype = i
+    lib.efe_agent_act.argtypes = [p, agp, f32p, f32p, nzp, p, p]; lib.efe_agent_act.restype = i
     _lib = lib
     return lib

@@ -1,0 +1,240 @@
+"""The agent of the reference's test_demo.py on the device, batched over games: observe a frame, choose an action sequence by one of the
+paper's methods, execute it tick by tick in Dynamic-dSprites, drop the rest of the sequence when a reward is collected, start a new round
+every `round_ticks` ticks and report the score every `report_ticks` ticks (test_demo.py:118-204).
+
+The per-game control state (the action queue `executing_steps`, the reward crossings and the sum of the rewards received) lives in device
+arrays behind `efe_agent` of the C ABI; `AgentState` binds its four kernels (csrc/agent.hip) and `AgentRunner` is the loop.  Only the games
+whose queue is empty decide on a tick, as a compacted call whose noise follows the game (Rows: efe_encoder_rows / efe_rollout_rows)."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .model import Rows, _ptr
+
+MODES = {'ai': _lib.EFE_AGENT_AI, 't1': _lib.EFE_AGENT_T1, 't12': _lib.EFE_AGENT_T12, 'probs': _lib.EFE_AGENT_PROBS}
+METHODS = ('habit', 'ai', 't1', 't12', 'mcts')
+TAG_AGENT = 0x70
+
+
+def _i32(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+class AgentState:
+    """Device arrays of `efe_agent` for E games: queue [E, cap] int32 with head [E] and len [E], crossings [E] int32, reward_sum [E] float32.
+    The queue of game g is queue[g, head[g] : head[g] + len[g]]; head is 0 whenever len is 0."""
+
+    def __init__(self, engine, games_no, cap):
+        self._engine = engine
+        self.E, self.cap = int(games_no), int(cap)
+        dev = engine.device
+        self.queue = torch.zeros(max(self.E, 0), max(self.cap, 0), dtype=torch.int32, device=dev)
+        self.head = torch.zeros(max(self.E, 0), dtype=torch.int32, device=dev)
+        self.len = torch.zeros(max(self.E, 0), dtype=torch.int32, device=dev)
+        self.crossings = torch.zeros(max(self.E, 0), dtype=torch.int32, device=dev)
+        self.reward_sum = torch.zeros(max(self.E, 0), dtype=torch.float32, device=dev)
+        self.ids = torch.zeros(max(self.E, 1), dtype=torch.int32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._bind()
+
+    def _bind(self):
+        """(re)builds the efe_agent struct from the tensors this object holds"""
+        self._struct = _lib.EfeAgent(self.queue.data_ptr(), self.head.data_ptr(), self.len.data_ptr(), self.crossings.data_ptr(),
+                                     self.reward_sum.data_ptr(), self.E, self.cap)
+
+    def _call(self, fn, *args):
+        e = self._engine
+        e.check(fn(e.ctx, C.byref(self._struct), *args, e.stream()))
+
+    def clear(self):
+        """empties every queue (test_demo.py:129); crossings and reward sums are kept"""
+        self.len.zero_()
+        self.head.zero_()
+
+    def need(self):
+        """-> (ids [E] int32, count [1] int32), both on the device: ids[:count] are the games whose queue is empty, ascending"""
+        self._call(self._engine.lib.efe_agent_need, _i32(self.ids), _i32(self.count))
+        return self.ids, self.count
+
+    def choose(self, ids, mode, *, sum_G=None, sum_terms=None, probs=None, steps=1, temperature=1.0, repeat=1, seed=0, stage=0,
+               game_offset=0, u=None, want_u=False):
+        """efe_agent_choose for the deciding games `ids` (int32 device tensor [n]) -> choice [n] int32 (-1: the decision failed and the queue
+        stays empty), or (choice, u) with want_u.  mode: 'ai' (sum_G [4n]), 't1' / 't12' (sum_terms [3, 4n]), 'probs' (probs [n, 4])."""
+        if mode not in MODES:
+            raise ValueError(f'unknown mode {mode!r}: one of {sorted(MODES)}')
+        e = self._engine
+        n = int(ids.numel())
+        sum_G, sum_terms, probs = self._f32(sum_G, 4 * n, 'sum_G'), self._f32(sum_terms, 12 * n, 'sum_terms'), self._f32(probs, 4 * n, 'probs')
+        u_t = self._f32(u, n, 'u')
+        choice = torch.empty(n, dtype=torch.int32, device=e.device)
+        u_out = torch.empty(n, dtype=torch.float32, device=e.device) if want_u else None
+        if n == 0:                                                   # no game decides (empty tensors have no address to hand over)
+            return (choice, u_out) if want_u else choice
+        nz = _lib.EfeNoise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage) & 0xFFFFFFFF, 0, 0, int(game_offset) & 0xFFFFFFFF)
+        self._call(e.lib.efe_agent_choose, _i32(ids), n, MODES[mode], _ptr(sum_G), _ptr(sum_terms), _ptr(probs), int(steps),
+                   C.c_float(float(temperature)), int(repeat), C.byref(nz), _ptr(u_t), _i32(choice), _ptr(u_out))
+        return (choice, u_out) if want_u else choice
+
+    def _f32(self, t, numel, name):
+        """an optional input as a contiguous float32 device tensor of `numel` elements"""
+        if t is None:
+            return None
+        t = self._engine.tensor(t)
+        if t.numel() != numel:
+            raise ValueError(f'{name} has {t.numel()} elements, expected {numel}')
+        return t
+
+    def enqueue(self, ids, actions, lengths, jumps=1):
+        """efe_agent_enqueue: the queue of game ids[i] becomes actions[i, :lengths[i]], each action `jumps` times"""
+        e = self._engine
+        n = int(ids.numel())
+        if n == 0:                                                   # nothing to queue (the engine accepts n = 0 and launches nothing)
+            return
+        a = torch.as_tensor(actions).to(device=e.device, dtype=torch.int32).reshape(n, -1).contiguous()
+        ln = torch.as_tensor(lengths).to(device=e.device, dtype=torch.int32).reshape(n).contiguous()
+        self._call(e.lib.efe_agent_enqueue, _i32(ids), n, _i32(a), _i32(ln), int(a.shape[1]), int(jumps))
+
+    def act(self, games, stage, want_changed=False):
+        """efe_agent_act on `games` (a daimc_amd.Game of the same size): one tick for every game with a non-empty queue"""
+        e = self._engine
+        if games.games_no != self.E:
+            raise ValueError(f'the agent state holds {self.E} games, the environment {games.games_no}')
+        changed = torch.empty(self.E, dtype=torch.int32, device=e.device) if want_changed else None
+        nz = _lib.EfeNoise(games.seed, int(stage) & 0xFFFFFFFF, 9, 0, games.game_offset)
+        self._call(e.lib.efe_agent_act, _ptr(games.current_s), _ptr(games.last_r), C.byref(nz), _i32(changed))
+        return changed.bool() if want_changed else None
+
+
+def default_samples(method):
+    """test_demo.py:70-77"""
+    return 10 if method in ('t1', 't12', 'ai', 'habit') else 1
+
+
+class AgentRunner:
+    """test_demo.py's loop for every game of `games` at once.
+
+    Start (test_demo.py:51-52): randomize_environment_all, then the score column is set to 0.  Tick t, in the order of :118-204:
+      1. t % report_ticks == 0 and t > 0: every game's s[6] is recorded as a round score and set to 0
+      2. t % round_ticks == 0: randomize_environment_all with the score column put back, all queues cleared
+      3. efe_agent_need; the decision for the deciding games only; efe_agent_act
+    Decisions (the deciding games' frames are rendered from their gathered state rows):
+      habit          : encoder(rows=ids) -> encode_s -> choose('probs'), the action `steps` times
+      ai / t1 / t12  : batched calculate_G_4_repeated(rows=ids, steps, samples, calc_mean) -> choose, the action steps * jumps times
+      mcts           : active_inference_mcts_batch on the deciding frames -> enqueue(path, jumps)
+
+    Noise: every draw's stage is a function of the tick alone and its row a function of the game's global index g = games.game_offset + e:
+      environment    : seed games.seed; start = stage 0, the reset of tick t = stage 1 + 2 t, its act = stage 2 + 2 t; row g
+      model          : seed model.seed; the decision of tick t starts at stage t * steps (a rollout takes `steps` stages); rows 4 g .. 4 g + 3
+                       for the rollouts, row g for the habit encoder
+      action uniform : seed model.seed, tag 0x70, stage t, row g
+    (all modulo 2^32).  The trajectory of a game is therefore the same whether it runs alone (game_offset = g) or inside any batch -- for
+    habit, ai, t1 and t12.  NOT for mcts: the planner keys an episode by its slot among the deciding games and takes its stages from the
+    model's own counter, so an mcts trajectory depends on which other games decide on the same tick.
+
+    Host traffic per tick: one 4-byte read-back (the number of deciding games), plus the render validity flag on ticks where a game decides
+    (mcts: plus the planner's own read-backs).  run() fetches everything else once at its end."""
+
+    def __init__(self, model, games, method, *, steps=7, jumps=5, temperature=1.0, samples=None, calc_mean=False, mcts_params=None,
+                 round_ticks=100, report_ticks=1000):
+        if method not in METHODS:
+            raise ValueError(f'unknown method {method!r}: one of {METHODS}')
+        self.model, self.games, self.method = model, games, method
+        self.steps, self.jumps, self.temperature = int(steps), int(jumps), float(temperature)
+        self.samples = default_samples(method) if samples is None else int(samples)
+        self.calc_mean, self.round_ticks, self.report_ticks = bool(calc_mean), int(round_ticks), int(report_ticks)
+        if self.steps < 1 or self.jumps < 1 or self.round_ticks < 1 or self.report_ticks < 1:
+            raise ValueError('steps, jumps, round_ticks and report_ticks must be >= 1')
+        if games.device != model.device:
+            raise ValueError('the games and the model must live on the same device')
+        cap = self.steps * self.jumps
+        if method == 'mcts':
+            from .mcts import MCTS_Params
+            self.mcts_params = mcts_params if mcts_params is not None else MCTS_Params()
+            cap = max(cap, (self.mcts_params.repeats + 2) * self.jumps)
+        self.state = AgentState(model._ready(), games.games_no, cap)
+        self.t = 0
+        self.decisions = 0
+        self.scores = []
+        self._failed = torch.zeros(1, dtype=torch.int32, device=model.device)
+
+    # ---- one tick ----------------------------------------------------------------------------------------------------------------------
+    def _frames(self, ids):
+        """[n,1,64,64] frames of the games `ids` (s_to_o on their gathered state rows)"""
+        g, e = self.games, self.model._ready()
+        n = int(ids.numel())
+        s = g.current_s.index_select(0, ids).contiguous()
+        r = g.last_r.index_select(0, ids).contiguous()
+        frames = torch.empty(n, 1, 64, 64, device=g.device)
+        err = torch.empty(n, dtype=torch.int32, device=g.device)
+        e.check(e.lib.efe_env_render(e.ctx, _ptr(s), _ptr(r), C.c_void_p(g.imgs.data_ptr()), g.imgs.shape[0], _ptr(frames),
+                                     C.c_void_p(err.data_ptr()), n, e.stream()))
+        if bool(err.any()):
+            raise ValueError(f'Error: Reward: {r[err.bool()][0].item()}')              # game_environment.py:53
+        return frames
+
+    def _decide(self, ids, t):
+        m, g, st = self.model, self.games, self.state
+        n, E = int(ids.numel()), g.games_no
+        frames = self._frames(ids)
+        stage = (t * self.steps) & 0xFFFFFFFF
+        key = dict(seed=m.seed, stage=t, game_offset=g.game_offset)
+        if self.method == 'habit':
+            mean, _ = m.model_down.encoder(frames, stage=stage, row_offset=g.game_offset & 0xFFFFFFFF, rows=Rows(ids=ids, rows_per_entry=1, n_total=E))
+            _, Qpi, _ = m.model_top.encode_s(mean)
+            choice = st.choose(ids, 'probs', probs=Qpi, steps=self.steps, temperature=self.temperature, repeat=self.steps, **key)
+        elif self.method == 'mcts':
+            from .mcts import active_inference_mcts_batch
+            out, _ = active_inference_mcts_batch(m, frames, self.mcts_params, o_shape=(1, 64, 64), episode_offset=g.game_offset)
+            paths = [list(o[0]) for o in out]
+            L = max(1, max(len(p) for p in paths))
+            acts = np.zeros((n, L), dtype=np.int32)
+            for i, p in enumerate(paths):
+                acts[i, :len(p)] = p
+            st.enqueue(ids, acts, np.array([len(p) for p in paths], dtype=np.int32), self.jumps)
+            return
+        else:
+            sum_G, sum_terms, _ = m.calculate_G_4_repeated(frames.repeat_interleave(4, dim=0), steps=self.steps, calc_mean=self.calc_mean,
+                                                           samples=self.samples, stage=stage, row_offset=(4 * g.game_offset) & 0xFFFFFFFF,
+                                                           rows=Rows(ids=ids, rows_per_entry=4, n_total=E))
+            choice = st.choose(ids, self.method, sum_G=sum_G, sum_terms=torch.stack(sum_terms), steps=self.steps,
+                               temperature=self.temperature, repeat=self.steps * self.jumps, **key)
+        self._failed += (choice < 0).any().to(torch.int32)
+
+    def tick(self):
+        g, st, t = self.games, self.state, self.t
+        if t == 0:                                                   # test_demo.py:51-52
+            g.randomize_environment_all(stage=0)
+            g.current_s[:, 6] = 0.0
+        if t % self.report_ticks == 0 and t > 0:                     # :121-124
+            self.scores.append(g.current_s[:, 6].clone())
+            g.current_s[:, 6] = 0.0
+        if t % self.round_ticks == 0:                                # :125-129
+            score = g.current_s[:, 6].clone()
+            g.randomize_environment_all(stage=(1 + 2 * t) & 0xFFFFFFFF)
+            g.current_s[:, 6] = score
+            st.clear()
+        ids, count = st.need()
+        n = int(count.item())                                        # the tick's one read-back
+        if n:
+            self.decisions += n
+            self._decide(ids[:n], t)
+        st.act(g, stage=(2 + 2 * t) & 0xFFFFFFFF)
+        self.t = t + 1
+
+    def run(self, ticks):
+        """`ticks` more ticks -> dict: round_scores [reports so far, E], crossings [E], reward_sum [E], state [E, 7], last_r [E] (numpy,
+        fetched once here), ticks, decisions (game decisions made) and failed_ticks (ticks in which a decision failed)"""
+        for _ in range(int(ticks)):
+            self.tick()
+        g, st = self.games, self.state
+        scores = torch.stack(self.scores).cpu().numpy() if self.scores else np.zeros((0, g.games_no), dtype=np.float32)
+        return {'round_scores': scores, 'crossings': st.crossings.cpu().numpy(), 'reward_sum': st.reward_sum.cpu().numpy(),
+                'state': g.current_s.cpu().numpy(), 'last_r': g.last_r.cpu().numpy(), 'ticks': self.t, 'decisions': self.decisions,
+                'failed_ticks': int(self._failed.item())}
+
+
+def run_agent(model, games, method, ticks, **kw):
+    """AgentRunner(model, games, method, **kw).run(ticks)"""
+    return AgentRunner(model, games, method, **kw).run(ticks)

@@ -1532,6 +1532,68 @@ int efe_env_render(efe_ctx* ctx, const float* state, const float* last_r, const 
     return call.finish();
 }
 
+// ---- agent control state (csrc/agent.hip): every refusal comes before the first launch and names its entry point ----
+static int agent_state(efe_ctx* ctx, const char* fn, const efe_agent* ag, AgentState& o) {
+    if (!ag) return ctx->fail(std::string(fn) + ": agent is NULL");
+    if (ag->E < 1) return ctx->fail(std::string(fn) + ": E < 1");
+    if (ag->cap < 1) return ctx->fail(std::string(fn) + ": cap < 1");
+    if (!ag->queue || !ag->head || !ag->len || !ag->crossings || !ag->reward_sum) return ctx->fail(std::string(fn) + ": a NULL array in efe_agent");
+    o = AgentState{ag->queue, ag->head, ag->len, ag->crossings, ag->reward_sum, ag->E, ag->cap};
+    return 0;
+}
+
+int efe_agent_need(efe_ctx* ctx, const efe_agent* agent, int32_t* ids, int32_t* count, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentState a; if (agent_state(ctx, "efe_agent_need", agent, a)) return 1;
+    if (!ids || !count) return ctx->fail("efe_agent_need: ids or count is NULL");
+    launch_agent_need(a, ids, count, (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_choose(efe_ctx* ctx, const efe_agent* agent, const int32_t* ids, int n, int mode, const float* sum_G, const float* sum_terms,
+                     const float* probs, int steps, float temperature, int repeat, const efe_noise* nz, const float* u, int32_t* choice,
+                     float* u_out, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentState a; if (agent_state(ctx, "efe_agent_choose", agent, a)) return 1;
+    if (n < 0 || n > a.E) return ctx->fail("efe_agent_choose: n < 0 or n > E");
+    if (mode != EFE_AGENT_AI && mode != EFE_AGENT_T1 && mode != EFE_AGENT_T12 && mode != EFE_AGENT_PROBS)
+        return ctx->fail("efe_agent_choose: unknown mode " + std::to_string(mode));
+    if (steps < 1) return ctx->fail("efe_agent_choose: steps < 1");
+    if (!(temperature > 0.0f) || std::isinf(temperature)) return ctx->fail("efe_agent_choose: the temperature must be finite and positive");
+    if (repeat < 1) return ctx->fail("efe_agent_choose: repeat < 1");
+    if (repeat > a.cap) return ctx->fail("efe_agent_choose: the queue capacity " + std::to_string(a.cap) + " is smaller than repeat = " + std::to_string(repeat));
+    if (!ids || !choice) return ctx->fail("efe_agent_choose: ids or choice is NULL");
+    if (!nz && !u) return ctx->fail("efe_agent_choose: neither efe_noise nor injected uniforms");
+    if (mode == EFE_AGENT_AI && !sum_G) return ctx->fail("efe_agent_choose: mode ai needs sum_G");
+    if ((mode == EFE_AGENT_T1 || mode == EFE_AGENT_T12) && !sum_terms) return ctx->fail("efe_agent_choose: modes t1 and t12 need sum_terms");
+    if (mode == EFE_AGENT_PROBS && !probs) return ctx->fail("efe_agent_choose: mode probs needs probs");
+    const uint64_t seed = nz ? nz->seed : 0;
+    launch_agent_choose(a, ids, n, mode, sum_G, sum_terms, probs, steps, temperature, repeat, (uint32_t)seed, (uint32_t)(seed >> 32),
+                        nz ? nz->stage : 0u, nz ? nz->row_offset : 0u, u, choice, u_out, (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_enqueue(efe_ctx* ctx, const efe_agent* agent, const int32_t* ids, int n, const int32_t* actions, const int32_t* lengths, int L,
+                      int jumps, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentState a; if (agent_state(ctx, "efe_agent_enqueue", agent, a)) return 1;
+    if (n < 0 || n > a.E) return ctx->fail("efe_agent_enqueue: n < 0 or n > E");
+    if (L < 1 || jumps < 1) return ctx->fail("efe_agent_enqueue: L < 1 or jumps < 1");
+    if ((int64_t)L * jumps > a.cap)
+        return ctx->fail("efe_agent_enqueue: the queue capacity " + std::to_string(a.cap) + " is smaller than L * jumps = " + std::to_string((int64_t)L * jumps));
+    if (!ids || !actions || !lengths) return ctx->fail("efe_agent_enqueue: ids, actions or lengths is NULL");
+    launch_agent_enqueue(a, ids, n, actions, lengths, L, jumps, (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_act(efe_ctx* ctx, const efe_agent* agent, float* state, float* last_r, const efe_noise* nz, int32_t* round_changed, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentState a; if (agent_state(ctx, "efe_agent_act", agent, a)) return 1;
+    if (!state || !last_r || !nz) return ctx->fail("efe_agent_act: state, last_r or efe_noise is NULL");
+    launch_agent_act(a, state, last_r, round_changed, (uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), nz->stage, nz->row_offset, (hipStream_t)stream);
+    return call.finish();
+}
+
 int efe_mcts_select(efe_ctx* ctx, const efe_mcts_tree* tree, const uint8_t* active, float C, int use_prior, int max_depth,
                     int32_t* path_nodes, int32_t* path_act, int32_t* path_len, int32_t* leaf, float* leaf_s, float* leaf_s_rep,
                     void* stream) {
@@ -1648,22 +1710,13 @@ int efe_decoder(efe_ctx* ctx, const float* s, int M, const efe_noise* nz, float*
     return call.finish();
 }
 
+// the bodies of efe_encoder[_rows] and efe_rollout[_rows] (behind row_set, below); `who` = the entry point the caller used
+static int encoder_call(efe_ctx* ctx, const char* who, const float* o, int M, const efe_noise* nz, const float* eps, const efe_rows* rows, float* s,
+                        float* mean, float* logvar, void* stream);
+static int rollout_call(efe_ctx* ctx, const char* who, const float* o, const float* pi, int M, int steps, int samples, int calc_mean, int per_stage_mean,
+                        const efe_noise* nz, const float* eps, const efe_rows* rows, float* sum_G, float* sum_terms, float* po1, void* stream);
 int efe_encoder(efe_ctx* ctx, const float* o, int M, const efe_noise* nz, const float* eps, float* s, float* mean, float* logvar, void* stream) {
-    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    if (!o || !nz || M < 1) return ctx->fail("efe_encoder: bad arguments");
-    float* enc = ctx->allocT<float>((size_t)M * 32);
-    if (!enc) return 1;
-    const NoiseCfg nc = pass_noise(nz, nz->pass, nz->sample, M);
-    if (ctx->generic) {
-        float* o8 = ctx->allocT<float>((size_t)M * ctx->img_store);
-        if (!o8) return 1;
-        launch_to_nhwc4(o, o8, M, ctx->res * ctx->res, ctx->chan, st);
-        o = o8;
-    }
-    if (run_encoder(ctx, o, M, nc, enc, st)) return 1;
-    launch_split_enc(enc, mean, logvar, M, st);
-    if (s) launch_root_post(enc, nullptr, eps, nullptr, s, M, 0, nc.k0, nc.k1, nz->pass, nz->sample, nz->stage, nz->row_offset, ctx->pi_dim, st);
-    return call.finish();
+    return encoder_call(ctx, "efe_encoder", o, M, nz, eps, nullptr, s, mean, logvar, stream);
 }
 
 int efe_habit(efe_ctx* ctx, const float* s, int M, float* logits, float* q, float* logq, void* stream) {
@@ -2397,10 +2450,55 @@ int efe_calculate_g_rows(efe_ctx* ctx, const float* s0, const float* pi0, int M,
     return call.finish();
 }
 
+// the noise of the single-group pass (pass, sample) of a call over the row set rs (rows == NULL: exactly pass_noise)
+static NoiseCfg pass_noise_rows(const efe_noise* nz, uint32_t pass, uint32_t sample, int M, const efe_rows* rows, const RowSet& rs) {
+    if (!rows) return pass_noise(nz, pass, sample, M);
+    return make_noise((uint32_t)nz->seed, (uint32_t)(nz->seed >> 32), M, nz->row_offset, GroupMap{1, 1, {pass, 0, 0}, nz->stage, sample}, rs.ids, rs.div, rs.mask);
+}
+
+// `who`: the entry point the caller used; every refusal names it
+static int encoder_call(efe_ctx* ctx, const char* who, const float* o, int M, const efe_noise* nz, const float* eps, const efe_rows* rows, float* s,
+                        float* mean, float* logvar, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
+    if (!o || !nz || M < 1) return ctx->fail(std::string(who) + ": bad arguments");
+    if (rows && ctx->generic) return ctx->fail("efe_encoder_rows: a row set needs the 1 x 64 x 64 geometry (the generic-geometry path has no row form)");
+    RowSet rs;
+    if (row_set(ctx, rows, M, 0, rs, "efe_encoder_rows", st)) return 1;
+    float* enc = ctx->allocT<float>((size_t)M * 32);
+    if (!enc) return 1;
+    const NoiseCfg nc = pass_noise_rows(nz, nz->pass, nz->sample, M, rows, rs);
+    if (ctx->generic) {
+        float* o8 = ctx->allocT<float>((size_t)M * ctx->img_store);
+        if (!o8) return 1;
+        launch_to_nhwc4(o, o8, M, ctx->res * ctx->res, ctx->chan, st);
+        o = o8;
+    }
+    if (run_encoder(ctx, o, M, nc, enc, st)) return 1;
+    launch_split_enc(enc, mean, logvar, M, st);
+    if (s) launch_root_post_rows(enc, nullptr, eps, nullptr, s, M, 0, nc.k0, nc.k1, nz->pass, nz->sample, nz->stage, nz->row_offset, ctx->pi_dim, rs.ids, rs.div, st);
+    return call.finish();
+}
+int efe_encoder_rows(efe_ctx* ctx, const float* o, int M, const efe_noise* nz, const float* eps, const efe_rows* rows, float* s, float* mean,
+                     float* logvar, void* stream) {
+    return encoder_call(ctx, "efe_encoder_rows", o, M, nz, eps, rows, s, mean, logvar, stream);
+}
+
 int efe_rollout(efe_ctx* ctx, const float* o, const float* pi, int M, int steps, int samples, int calc_mean, int per_stage_mean,
                 const efe_noise* nz, const float* eps, float* sum_G, float* sum_terms, float* po1, void* stream) {
+    return rollout_call(ctx, "efe_rollout", o, pi, M, steps, samples, calc_mean, per_stage_mean, nz, eps, nullptr, sum_G, sum_terms, po1, stream);
+}
+int efe_rollout_rows(efe_ctx* ctx, const float* o, const float* pi, int M, int steps, int samples, int calc_mean, int per_stage_mean,
+                     const efe_noise* nz, const float* eps, const efe_rows* rows, float* sum_G, float* sum_terms, float* po1, void* stream) {
+    return rollout_call(ctx, "efe_rollout_rows", o, pi, M, steps, samples, calc_mean, per_stage_mean, nz, eps, rows, sum_G, sum_terms, po1, stream);
+}
+
+static int rollout_call(efe_ctx* ctx, const char* who, const float* o, const float* pi, int M, int steps, int samples, int calc_mean, int per_stage_mean,
+                        const efe_noise* nz, const float* eps, const efe_rows* rows, float* sum_G, float* sum_terms, float* po1, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
-    if (!o || !pi || !nz || !sum_G || M < 1 || steps < 1 || samples < 1 || samples > 65535) return ctx->fail("efe_rollout: bad arguments");
+    if (!o || !pi || !nz || !sum_G || M < 1 || steps < 1 || samples < 1 || samples > 65535) return ctx->fail(std::string(who) + ": bad arguments");
+    if (rows && ctx->generic) return ctx->fail("efe_rollout_rows: a row set needs the 1 x 64 x 64 geometry (the generic-geometry path has no row form)");
+    RowSet rs;
+    if (row_set(ctx, rows, M, 0, rs, "efe_rollout_rows", st)) return 1;
     const uint32_t k0 = (uint32_t)nz->seed, k1 = (uint32_t)(nz->seed >> 32);
     const RolloutPlan plan = rollout_plan(ctx, M);
     float* enc0 = ctx->allocT<float>(plan.enc0);
@@ -2413,8 +2511,8 @@ int efe_rollout(efe_ctx* ctx, const float* o, const float* pi, int M, int steps,
             launch_to_nhwc4(o, o8, M, ctx->res * ctx->res, ctx->chan, st);
             o = o8;
         }
-        if (run_encoder(ctx, o, M, pass_noise(nz, PASS_ROOT, 0, M), enc0, st)) return 1;
-        launch_root_post(enc0, pi, eps, x, nullptr, M, calc_mean ? 1 : 0, k0, k1, PASS_ROOT, 0, nz->stage, nz->row_offset, ctx->pi_dim, st);
+        if (run_encoder(ctx, o, M, pass_noise_rows(nz, PASS_ROOT, 0, M, rows, rs), enc0, st)) return 1;
+        launch_root_post_rows(enc0, pi, eps, x, nullptr, M, calc_mean ? 1 : 0, k0, k1, PASS_ROOT, 0, nz->stage, nz->row_offset, ctx->pi_dim, rs.ids, rs.div, st);
     }
     const int mean_mode = (per_stage_mean && calc_mean) ? 1 : 0;
     CoreIO io{};
@@ -2422,6 +2520,7 @@ int efe_rollout(efe_ctx* ctx, const float* o, const float* pi, int M, int steps,
     io.k0 = k0; io.k1 = k1; io.stage0 = nz->stage; io.row_offset = nz->row_offset;
     io.eps = eps ? eps + (size_t)M * 10 : nullptr;
     io.G = sum_G; io.terms = sum_terms; io.po1 = po1;
+    io.mask = rs.mask; io.ids = rs.ids; io.mask_div = rs.div;
     if (run_core(ctx, io, st)) return 1;
     return call.finish();
 }

@@ -623,6 +623,9 @@ void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim,
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);
 void launch_root_post(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,
                       uint32_t k0, uint32_t k1, uint32_t pass, uint32_t sample, uint32_t stage, uint32_t row_offset, int pi_dim, hipStream_t st);
+void launch_root_post_rows(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,
+                           uint32_t k0, uint32_t k1, uint32_t pass, uint32_t sample, uint32_t stage, uint32_t row_offset, int pi_dim,
+                           const int32_t* ids, int ids_div, hipStream_t st);      // ids == nullptr: launch_root_post
 void launch_split_enc(const float* enc, float* mean, float* logvar, int R, hipStream_t st);
 void launch_softmax4(const float* logits32, float* logits, float* q, float* logq, int R, int n, hipStream_t st);
 void launch_mean_rows(const float* G, float* out, int E, int T, hipStream_t st);
@@ -638,5 +641,48 @@ void launch_env_new_image(float* state, int E, uint32_t k0, uint32_t k1, uint32_
 void launch_env_reset(float* state, float* last_r, int E, uint32_t k0, uint32_t k1, uint32_t stage, uint32_t game_offset, hipStream_t st);
 void launch_env_render(const float* state, const float* last_r, const unsigned char* imgs, long n_imgs, float* frames, int* err,
                        int E, hipStream_t st);
+
+// ---- Dynamic-dSprites environment: what k_env_* (kernels.hip) and k_agent_act (agent.hip) share --------------------------------------
+enum : uint32_t { TAG_ENV = 0x60, PASS_ENV = 9 };
+__device__ __forceinline__ int env_randint(uint32_t k0, uint32_t k1, uint32_t game, uint32_t stage, int latent, int size) {
+    const float u = u01(noise_words(k0, k1, TAG_ENV, (uint32_t)latent, game, stream_id(PASS_ENV, 0), stage).x);
+    const int v = (int)(u * (float)size);
+    return v < size ? v : size - 1;
+}
+// ONE tick of pi_to_action (game_environment.py:113-169) for one game: tick, move, and on a crossing the reward and new_image.
+// s = the game's 7 state floats, r = its last_r (kept in a register by the caller); -> the round finished
+__device__ __forceinline__ bool env_tick_move(float* s, float& r, int pi, uint32_t k0, uint32_t k1, uint32_t game, uint32_t stage) {
+    bool changed = false;
+    r *= 0.95f;                                                   // tick
+    if (pi == 0) {                                                // up
+        s[5] += 1.0f;
+        if (s[5] >= 32.0f) {
+            const float x = s[4];
+            if (s[1] < 0.5f) r = (x > 15.0f) ? (15.0f - x) / 16.0f : (16.0f - x) / 16.0f;      // square
+            else             r = (x > 15.0f) ? (x - 15.0f) / 16.0f : (x - 16.0f) / 16.0f;      // ellipse / heart
+            const int sizes[6] = {1, 3, 6, 40, 32, 32};
+            for (int k = 0; k < 6; ++k) s[k] = (float)env_randint(k0, k1, game, stage, k, sizes[k]);
+            // port quirk, replicated because the oracle pins it: new_image() holds the accumulated reward as a tensor VIEW,
+            // overwrites the row with a fresh sample (slot 6 = 0) and writes the view back -> the reward restarts at 0
+            s[6] = 0.0f;
+            changed = true;
+        }
+    } else if (pi == 1) { if (s[5] > 0.0f) s[5] -= 1.0f; }       // down
+    else if (pi == 2) { if (s[4] < 31.0f) s[4] += 1.0f; }         // left
+    else if (pi == 3) { if (s[4] > 0.0f) s[4] -= 1.0f; }          // right
+    return changed;
+}
+
+// ---- agent control state (csrc/agent.hip; efe_agent of the C ABI) -------------------------------------------------------------------
+struct AgentState { int32_t* queue; int32_t* head; int32_t* len; int32_t* crossings; float* reward_sum; int E, cap; };
+enum : uint32_t { TAG_AGENT = 0x70 };                                // the action uniform of efe_agent_choose: word 0 of (TAG_AGENT, game, stream 0, stage)
+enum { AGENT_AI = 0, AGENT_T1 = 1, AGENT_T12 = 2, AGENT_PROBS = 3 };
+void launch_agent_need(const AgentState& a, int32_t* ids, int32_t* count, hipStream_t st);
+void launch_agent_choose(const AgentState& a, const int32_t* ids, int n, int mode, const float* sum_G, const float* sum_terms, const float* probs,
+                         int steps, float temperature, int repeat, uint32_t k0, uint32_t k1, uint32_t stage, uint32_t game_offset, const float* u,
+                         int32_t* choice, float* u_out, hipStream_t st);
+void launch_agent_enqueue(const AgentState& a, const int32_t* ids, int n, const int32_t* actions, const int32_t* lengths, int L, int jumps, hipStream_t st);
+void launch_agent_act(const AgentState& a, float* state, float* last_r, int32_t* round_changed, uint32_t k0, uint32_t k1, uint32_t stage,
+                      uint32_t game_offset, hipStream_t st);
 
 }  // namespace efe

@@ -369,6 +369,37 @@ void launch_root_post(const float* enc, const float* pi, const float* eps_inj, f
                        k0, k1, pass, sample, stage, row_offset, pi_dim);
 }
 
+// the same over a row set (efe_rows.ids: efe_encoder_rows / efe_rollout_rows): the normals of row r are those of its global row
+// global_row(ids, ids_div, r, row_offset).  A kernel of its own, so that k_root_post's code stays what it was.
+__global__ void __launch_bounds__(256) k_root_post_rows(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,
+                                 uint32_t k0, uint32_t k1, uint32_t pass, uint32_t sample, uint32_t stage, uint32_t row_offset, int pi_dim,
+                                 const int32_t* ids, int ids_div) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = gid >> 4, k = gid & 15;
+    if (r >= R) return;
+    float v = 0.f;
+    if (k < pi_dim) v = pi ? pi[(size_t)r * pi_dim + k] : 0.f;
+    else if (k < pi_dim + 10) {
+        const int kk = k - pi_dim;
+        const float mean = enc[(size_t)r * 32 + kk], lv = enc[(size_t)r * 32 + 10 + kk];
+        if (use_mean) v = mean;
+        else {
+            const float eps = eps_inj ? eps_inj[(size_t)r * 10 + kk]
+                                      : normal_elem(k0, k1, global_row(ids, ids_div, r, row_offset), stream_id(pass, sample), stage, kk);
+            v = eps * expf(lv * 0.5f) + mean;
+        }
+        if (s_out) s_out[(size_t)r * 10 + kk] = v;
+    }
+    if (x) x[gid] = v;
+}
+void launch_root_post_rows(const float* enc, const float* pi, const float* eps_inj, float* x, float* s_out, int R, int use_mean,
+                           uint32_t k0, uint32_t k1, uint32_t pass, uint32_t sample, uint32_t stage, uint32_t row_offset, int pi_dim,
+                           const int32_t* ids, int ids_div, hipStream_t st) {
+    if (!ids) return launch_root_post(enc, pi, eps_inj, x, s_out, R, use_mean, k0, k1, pass, sample, stage, row_offset, pi_dim, st);
+    hipLaunchKernelGGL(k_root_post_rows, dim3((R * 16 + 255) / 256), dim3(256), 0, st, enc, pi, eps_inj, x, s_out, R, use_mean,
+                       k0, k1, pass, sample, stage, row_offset, pi_dim, ids, ids_div);
+}
+
 __global__ void k_split_enc(const float* enc, float* mean, float* logvar, int R) {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= R * 10) return;
@@ -481,13 +512,7 @@ void launch_reparam(const float* mean, const float* logvar, const float* eps_inj
 // pi_to_action (:154-169), new_image (:84-87) with the latent resampling drawn from Philox, and
 // randomize_environment_all (:72-75).  State s[7] = (colour, shape, scale, orientation, x, y, reward).
 // ---------------------------------------------------------------------------------------------
-enum : uint32_t { TAG_ENV = 0x60, PASS_ENV = 9 };
-__device__ __forceinline__ int env_randint(uint32_t k0, uint32_t k1, uint32_t game, uint32_t stage, int latent, int size) {
-    const float u = u01(noise_words(k0, k1, TAG_ENV, (uint32_t)latent, game, stream_id(PASS_ENV, 0), stage).x);
-    const int v = (int)(u * (float)size);
-    return v < size ? v : size - 1;
-}
-
+// (TAG_ENV, env_randint and the one-tick move env_tick_move live in kernels.h: csrc/agent.hip takes the same tick)
 __global__ void k_env_step(float* state, float* last_r, const int* actions, int* round_changed, int E, int repeats,
                            uint32_t k0, uint32_t k1, uint32_t stage, uint32_t game_offset) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -496,25 +521,7 @@ __global__ void k_env_step(float* state, float* last_r, const int* actions, int*
     float r = last_r[e];
     const int pi = actions[e];
     bool changed = false;
-    for (int i = 0; i < repeats && !changed; ++i) {
-        r *= 0.95f;                                                   // tick
-        if (pi == 0) {                                                // up
-            s[5] += 1.0f;
-            if (s[5] >= 32.0f) {
-                const float x = s[4];
-                if (s[1] < 0.5f) r = (x > 15.0f) ? (15.0f - x) / 16.0f : (16.0f - x) / 16.0f;      // square
-                else             r = (x > 15.0f) ? (x - 15.0f) / 16.0f : (x - 16.0f) / 16.0f;      // ellipse / heart
-                const int sizes[6] = {1, 3, 6, 40, 32, 32};
-                for (int k = 0; k < 6; ++k) s[k] = (float)env_randint(k0, k1, game_offset + e, stage, k, sizes[k]);
-                // port quirk, replicated because the oracle pins it: new_image() holds the accumulated reward as a tensor VIEW,
-                // overwrites the row with a fresh sample (slot 6 = 0) and writes the view back -> the reward restarts at 0
-                s[6] = 0.0f;
-                changed = true;
-            }
-        } else if (pi == 1) { if (s[5] > 0.0f) s[5] -= 1.0f; }       // down
-        else if (pi == 2) { if (s[4] < 31.0f) s[4] += 1.0f; }         // left
-        else if (pi == 3) { if (s[4] > 0.0f) s[4] -= 1.0f; }          // right
-    }
+    for (int i = 0; i < repeats && !changed; ++i) changed = env_tick_move(s, r, pi, k0, k1, game_offset + e, stage);
     last_r[e] = r;
     if (round_changed) round_changed[e] = changed ? 1 : 0;
 }

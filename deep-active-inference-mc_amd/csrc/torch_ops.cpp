@@ -141,6 +141,24 @@ std::tuple<Tensor, Tensor, Tensor> encoder(int64_t h, const Tensor& o_, int64_t 
     return {s, mean, lv};
 }
 
+// the same over a row set (efe_encoder_rows): noise follows the entry id
+std::tuple<Tensor, Tensor, Tensor> encoder_rows(int64_t h, const Tensor& o_, int64_t seed, int64_t stage, int64_t pass, int64_t sample,
+                                                int64_t row_offset, const OptT& eps, bool want_s, const OptT& mask, const OptT& ids,
+                                                int64_t rows_per_entry, int64_t n_total) {
+    efe_ctx* c = CTX(h);
+    Tensor o = in(o_, "o"), ek;
+    const int M = rows(o, geo(c).img(), "o");
+    Tensor s = want_s ? at::empty({M, 10}, o.options()) : at::empty({0}, o.options());
+    Tensor mean = at::empty({M, 10}, o.options()), lv = at::empty({M, 10}, o.options());
+    efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    RowsArg ra;
+    TORCH_CHECK(rows_per_entry < 1 || M % rows_per_entry == 0, "efe: rows_per_entry must divide the row count");
+    rows_arg(ra, mask, ids, rows_per_entry, rows_per_entry >= 1 ? M / rows_per_entry : M, n_total);
+    ok(c, efe_encoder_rows(c, o.data_ptr<float>(), M, &nz, optp(eps, ek, "eps", (int64_t)M * 10), ra.ptr, want_s ? s.data_ptr<float>() : nullptr,
+                           mean.data_ptr<float>(), lv.data_ptr<float>(), stream_of(o)));
+    return {s, mean, lv};
+}
+
 // ModelTop.encode_s, torchmodel.py:27-31
 std::tuple<Tensor, Tensor, Tensor> habit(int64_t h, const Tensor& s_) {
     efe_ctx* c = CTX(h);
@@ -192,6 +210,29 @@ std::tuple<Tensor, Tensor, Tensor> rollout(int64_t h, const Tensor& o_, const Te
     ok(c, efe_rollout(c, o.data_ptr<float>(), pi.data_ptr<float>(), M, (int)steps, (int)samples, calc_mean ? 1 : 0, per_stage_mean ? 1 : 0, &nz,
                       optp(eps, ek, "eps", (int64_t)M * 10 + steps * 3 * S * M * 10), G.data_ptr<float>(), terms.data_ptr<float>(),
                       po1.data_ptr<float>(), stream_of(o)));
+    return {G, terms, po1};
+}
+
+// the same over a row set (efe_rollout_rows): the rollouts of a compacted subset of the entries, noise keyed by the entry id
+std::tuple<Tensor, Tensor, Tensor> rollout_rows(int64_t h, const Tensor& o_, const Tensor& pi_, int64_t steps, int64_t samples, bool calc_mean,
+                                                bool per_stage_mean, int64_t seed, int64_t stage, int64_t row_offset, const OptT& eps,
+                                                const OptT& mask, const OptT& ids, int64_t rows_per_entry, int64_t n_total) {
+    efe_ctx* c = CTX(h);
+    Tensor o = in(o_, "o"), pi = in(pi_, "pi"), ek;
+    const Geo gq = geo(c);
+    const int M = rows(o, gq.img(), "o");
+    TORCH_CHECK(pi.numel() == (int64_t)M * gq.A, "efe: o and pi must have the same number of rows");
+    TORCH_CHECK(steps >= 1 && samples >= 1 && samples <= 65535, "efe engine: steps and samples must be >= 1");
+    const int64_t S = (per_stage_mean && calc_mean) ? 1 : samples;
+    auto op = o.options();
+    Tensor G = at::empty({M}, op), terms = at::empty({3, M}, op), po1 = at::empty({M, gq.C, gq.R, gq.R}, op);
+    efe_noise nz = noise(seed, stage, 0, 0, row_offset);
+    RowsArg ra;
+    TORCH_CHECK(rows_per_entry < 1 || M % rows_per_entry == 0, "efe: rows_per_entry must divide the row count");
+    rows_arg(ra, mask, ids, rows_per_entry, rows_per_entry >= 1 ? M / rows_per_entry : M, n_total);
+    ok(c, efe_rollout_rows(c, o.data_ptr<float>(), pi.data_ptr<float>(), M, (int)steps, (int)samples, calc_mean ? 1 : 0, per_stage_mean ? 1 : 0, &nz,
+                           optp(eps, ek, "eps", (int64_t)M * 10 + steps * 3 * S * M * 10), ra.ptr, G.data_ptr<float>(), terms.data_ptr<float>(),
+                           po1.data_ptr<float>(), stream_of(o)));
     return {G, terms, po1};
 }
 
@@ -620,6 +661,8 @@ TORCH_LIBRARY(efe, m) {
     m.def("transition(int ctx, Tensor pi, Tensor s0, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> (Tensor ps1, Tensor mean, Tensor logvar)");
     m.def("decoder(int ctx, Tensor s, int seed, int stage, int pass_id, int sample, int row_offset) -> Tensor");
     m.def("encoder(int ctx, Tensor o, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps, bool want_s) -> (Tensor s, Tensor mean, Tensor logvar)");
+    m.def("encoder_rows(int ctx, Tensor o, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps, bool want_s, Tensor? mask=None, Tensor? ids=None, int rows_per_entry=1, int n_total=0) -> (Tensor s, Tensor mean, Tensor logvar)");
+    m.def("rollout_rows(int ctx, Tensor o, Tensor pi, int steps, int samples, bool calc_mean, bool per_stage_mean, int seed, int stage, int row_offset, Tensor? eps, Tensor? mask=None, Tensor? ids=None, int rows_per_entry=1, int n_total=0) -> (Tensor sum_G, Tensor sum_terms, Tensor po1)");
     m.def("habit(int ctx, Tensor s) -> (Tensor logits, Tensor q, Tensor logq)");
     m.def("calculate_g(int ctx, Tensor s0, Tensor pi0, int samples, bool mean_mode, int seed, int stage, int row_offset, Tensor? eps, Tensor? mask=None, Tensor? ids=None, int rows_per_entry=1, int n_total=0) -> (Tensor G, Tensor terms, Tensor ps1, Tensor ps1_mean, Tensor po1, Tensor t2parts)");
     m.def("rollout(int ctx, Tensor o, Tensor pi, int steps, int samples, bool calc_mean, bool per_stage_mean, int seed, int stage, int row_offset, Tensor? eps) -> (Tensor sum_G, Tensor sum_terms, Tensor po1)");
@@ -650,6 +693,8 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("transition", &transition);
     m.impl("decoder", &decoder);
     m.impl("encoder", &encoder);
+    m.impl("encoder_rows", &encoder_rows);
+    m.impl("rollout_rows", &rollout_rows);
     m.impl("habit", &habit);
     m.impl("calculate_g", &calculate_g);
     m.impl("rollout", &rollout);

@@ -263,16 +263,24 @@ class ModelDown(_TrainableModule):
         """torchmodel.py:130-132; the normals come from the model's Philox stream (one stage per call)"""
         return self._owner._reparameterize(mean, logvar, **kw)
 
-    def encoder_with_sample(self, o, stage=None, pass_=PASS_E1, sample=0, eps=None, row_offset=None, _want_s=True):
+    def encoder_with_sample(self, o, stage=None, pass_=PASS_E1, sample=0, eps=None, row_offset=None, _want_s=True, rows=None):
+        """torchmodel.py:143-146; rows: optional Rows -- the call holds a subset of the entries of a larger batch and draws their noise
+        (dropout masks and normals keyed by the entry id, efe_encoder_rows), so it returns the bits the full call returns for those rows"""
         m = self._owner
         e = m._ready()
         o = e.tensor(o, (-1, m.colour_channels, m.resolution, m.resolution))
         M = o.shape[0]
         nz = m._noise(stage, pass_, sample, row_offset)
         if eps is None and _want_s and m.eps_source is not None:
-            eps = m._src_eps(M, 10, pass_, sample, nz.stage, row_offset)
+            hr = rows.host_rows(rows.rows_per_entry) if rows is not None else None
+            eps = m._src_eps(M, 10, pass_, sample, nz.stage, row_offset) if hr is None else \
+                m._src_eps(int(hr.max()) + 1, 10, pass_, sample, nz.stage, row_offset)[hr]
         eps_t = e.tensor(eps, (M, 10)) if eps is not None else None
-        s, mean, logvar = e.ops.encoder(e.h, o, m._seed64(), nz.stage, pass_, sample, nz.row_offset, eps_t, bool(_want_s))
+        if rows is None:
+            s, mean, logvar = e.ops.encoder(e.h, o, m._seed64(), nz.stage, pass_, sample, nz.row_offset, eps_t, bool(_want_s))
+        else:
+            s, mean, logvar = e.ops.encoder_rows(e.h, o, m._seed64(), nz.stage, pass_, sample, nz.row_offset, eps_t, bool(_want_s),
+                                                 rows.mask, rows.ids, rows.rows_per_entry, rows.n_total)
         return (s if _want_s else None), mean, logvar
 
     def encoder(self, o, **kw):
@@ -618,7 +626,7 @@ class ActiveInferenceModel:
         """torchmodel.py:302-327 -> (G, terms, ps1_mean, po1)"""
         return self.calculate_G(s0, pi0, 1, stage=stage, eps=eps, row_offset=row_offset, _mean_mode=True, _parts=_parts, rows=rows)
 
-    def _rollout(self, o, pi, steps, calc_mean, samples, per_stage_mean, stage, eps, row_offset):
+    def _rollout(self, o, pi, steps, calc_mean, samples, per_stage_mean, stage, eps, row_offset, rows=None):
         e = self._ready()
         o = e.tensor(o, (-1, self.colour_channels, self.resolution, self.resolution)); pi = e.tensor(pi, (-1, self.pi_dim))
         M = o.shape[0]
@@ -630,29 +638,46 @@ class ActiveInferenceModel:
         nz = self._noise(self._take_stage(stage, steps), 0, 0, row_offset)
         S_eff = 1 if (per_stage_mean and calc_mean) else samples
         if eps is None and self.eps_source is not None:
-            parts = [self._src_eps(M, 10, PASS_ROOT, 0, nz.stage, row_offset).reshape(-1)]
-            parts += [self._src_eps_calcG(M, S_eff, nz.stage + t, row_offset).reshape(-1) for t in range(steps)]
+            hr = rows.host_rows(rows.rows_per_entry) if rows is not None else None
+            if hr is None:
+                parts = [self._src_eps(M, 10, PASS_ROOT, 0, nz.stage, row_offset).reshape(-1)]
+                parts += [self._src_eps_calcG(M, S_eff, nz.stage + t, row_offset).reshape(-1) for t in range(steps)]
+            else:                                               # a compacted call: the normals of the rows it holds
+                n = int(hr.max()) + 1
+                parts = [self._src_eps(n, 10, PASS_ROOT, 0, nz.stage, row_offset)[hr].reshape(-1)]
+                parts += [self._src_eps_calcG(n, S_eff, nz.stage + t, row_offset)[:, hr].reshape(-1) for t in range(steps)]
             eps = np.concatenate(parts)
         eps_t = e.tensor(eps).reshape(-1) if eps is not None else None
         if eps_t is not None and eps_t.numel() != M * 10 + steps * 3 * S_eff * M * 10:
             raise ValueError(f'eps has {eps_t.numel()} elements, efe_rollout expects M*10 + steps*3*S*M*10 = '
                              f'{M * 10 + steps * 3 * S_eff * M * 10}')
-        sum_G, sum_terms, po1 = e.ops.rollout(e.h, o, pi, steps, samples, bool(calc_mean), bool(per_stage_mean), self._seed64(), nz.stage,
-                                              nz.row_offset, eps_t)
+        if rows is None:
+            sum_G, sum_terms, po1 = e.ops.rollout(e.h, o, pi, steps, samples, bool(calc_mean), bool(per_stage_mean), self._seed64(), nz.stage,
+                                                  nz.row_offset, eps_t)
+        else:
+            sum_G, sum_terms, po1 = e.ops.rollout_rows(e.h, o, pi, steps, samples, bool(calc_mean), bool(per_stage_mean), self._seed64(),
+                                                       nz.stage, nz.row_offset, eps_t, rows.mask, rows.ids, rows.rows_per_entry, rows.n_total)
         return sum_G, [sum_terms[0], sum_terms[1], sum_terms[2]], po1
 
-    def calculate_G_repeated(self, o, pi, steps=1, calc_mean=False, samples=10, *, stage=None, eps=None, row_offset=None):
-        """torchmodel.py:227-245 -> (sum_G, sum_terms, po1); one row = one EFE rollout."""
-        return self._rollout(o, pi, steps, calc_mean, samples, False, stage, eps, row_offset)
+    def calculate_G_repeated(self, o, pi, steps=1, calc_mean=False, samples=10, *, stage=None, eps=None, row_offset=None, rows=None):
+        """torchmodel.py:227-245 -> (sum_G, sum_terms, po1); one row = one EFE rollout.  rows: optional Rows (efe_rollout_rows): the call
+        holds a subset of the entries of a larger batch and draws their noise, so it returns the bits the full call returns for those rows."""
+        return self._rollout(o, pi, steps, calc_mean, samples, False, stage, eps, row_offset, rows)
 
-    def calculate_G_4_repeated(self, o, steps=1, calc_mean=False, samples=10, *, stage=None, eps=None, row_offset=None):
-        """torchmodel.py:247-268 (4 rows, pi = eye(4); calc_mean switches every stage to calculate_G_mean)"""
+    def calculate_G_4_repeated(self, o, steps=1, calc_mean=False, samples=10, *, stage=None, eps=None, row_offset=None, rows=None):
+        """torchmodel.py:247-268 (4 rows, pi = eye(4); calc_mean switches every stage to calculate_G_mean).
+        With rows = Rows(rows_per_entry=4, ...) the call is BATCHED: o is [4n,1,64,64], four copies of the frame of each of n entries
+        (the games that decide on this tick), pi = eye(4) per entry; outputs are [4n] in the call's row order."""
         if self.pi_dim != 4:
             raise ValueError('calculate_G_4_repeated is hard-wired to 4 actions (pi_one_hot, torchmodel.py:251-252)')
         o = self._engine.tensor(o, (-1, self.colour_channels, self.resolution, self.resolution))
-        if o.shape[0] != 4:
-            raise ValueError('calculate_G_4_repeated expects 4 rows (torchmodel.py:251-252)')
-        return self._rollout(o, self.pi_one_hot, steps, calc_mean, samples, True, stage, eps, row_offset)
+        if rows is None:
+            if o.shape[0] != 4:
+                raise ValueError('calculate_G_4_repeated expects 4 rows (torchmodel.py:251-252)')
+            return self._rollout(o, self.pi_one_hot, steps, calc_mean, samples, True, stage, eps, row_offset)
+        if rows.rows_per_entry != 4 or o.shape[0] < 4 or o.shape[0] % 4:
+            raise ValueError('batched calculate_G_4_repeated expects [4n,1,64,64] frames and Rows(rows_per_entry=4)')
+        return self._rollout(o, self.pi_one_hot.repeat(o.shape[0] // 4, 1), steps, calc_mean, samples, True, stage, eps, row_offset, rows)
 
     def calculate_G_given_trajectory(self, s0_traj, ps1_traj, ps1_mean_traj, ps1_logvar_traj, pi0_traj, *, stage=None,
                                      eps=None, row_offset=None):

@@ -150,6 +150,12 @@ int efe_decoder(efe_ctx*, const float* s /*[M,10]*/, int M, const efe_noise* nz,
 /* ModelDown.encoder / encoder_with_sample, torchmodel.py:134-137,143-146.  s may be NULL. */
 int efe_encoder(efe_ctx*, const float* o /*[M,1,64,64]*/, int M, const efe_noise* nz, const float* eps,
                 float* s, float* mean, float* logvar, void* stream);
+/* the same over the row set `rows` (1 x 64 x 64 geometry only; entry = rows_per_entry consecutive rows): row r of the call draws the noise of
+ * global row ids[r / rows_per_entry] * rows_per_entry + r % rows_per_entry (+ nz->row_offset) -- the dense head's dropout masks and the
+ * sample's normals -- so a compacted call returns the bits the full call returns for those rows; the trunk skips dead entries of `mask`
+ * (their outputs are unspecified).  o, eps and the outputs are in the call's (compact) row order.  rows == NULL: efe_encoder. */
+int efe_encoder_rows(efe_ctx*, const float* o /*[M,1,64,64]*/, int M, const efe_noise* nz, const float* eps, const efe_rows* rows,
+                     float* s, float* mean, float* logvar, void* stream);
 /* ModelTop.encode_s, torchmodel.py:27-31 (no dropout). */
 int efe_habit(efe_ctx*, const float* s /*[M,10]*/, int M, float* logits, float* q, float* logq, void* stream);
 
@@ -184,6 +190,15 @@ int efe_calculate_g_rows(efe_ctx*, const float* s0, const float* pi0, int M, int
 int efe_rollout(efe_ctx*, const float* o, const float* pi, int M, int steps, int samples, int calc_mean,
                 int per_stage_mean, const efe_noise* nz, const float* eps,
                 float* sum_G, float* sum_terms, float* po1, void* stream);
+
+/* the same over the row set `rows` (1 x 64 x 64 geometry only): every draw of the call -- the root encoder's dropout, the root
+ * reparameterisation and every stage of the core -- is keyed by the entry id as in efe_calculate_g_rows, so the rollouts of a compacted
+ * subset (the games that decide on this tick, rows_per_entry = 4) are bit-identical to those rows of the full call; dead entries of `mask`
+ * are skipped by the per-image kernels (outputs unspecified).  o, pi, eps and the outputs are in the call's row order.  rows == NULL:
+ * efe_rollout. */
+int efe_rollout_rows(efe_ctx*, const float* o, const float* pi, int M, int steps, int samples, int calc_mean,
+                     int per_stage_mean, const efe_noise* nz, const float* eps, const efe_rows* rows,
+                     float* sum_G, float* sum_terms, float* po1, void* stream);
 
 /* calculate_G_given_trajectory (torchmodel.py:329-352): rows are trajectory steps. G[T]. */
 int efe_trajectory(efe_ctx*, const float* s0_traj, const float* ps1_traj, const float* ps1_mean_traj,
@@ -222,6 +237,45 @@ int efe_env_step(efe_ctx*, float* state, float* last_r, const int32_t* actions, 
                  int32_t* round_changed, void* stream);
 int efe_env_render(efe_ctx*, const float* state, const float* last_r, const uint8_t* imgs, int64_t n_imgs, float* frames,
                    int32_t* err, int E, void* stream);
+
+/* ---- per-game control state of the observe-plan-act loop (csrc/agent.hip; additive to ABI 6; /root/reference/test_demo.py:118-204) ------
+ * All pointers are DEVICE arrays owned by the caller: queue [E][cap] int32 (test_demo.py's executing_steps; the queue of game g is
+ * queue[g][head[g] .. head[g] + len[g])), head [E], len [E], crossings [E] (reward crossings so far) and reward_sum [E] (the rewards
+ * received, added in tick order -- new_image restarts state slot 6 at 0 on every crossing, so the score the reference prints is not
+ * the task reward).  Zero-filled arrays are the initial state; zeroing len (and head) clears every queue.  The kernels keep head == 0
+ * whenever len == 0 and write a new queue from slot 0.  One thread per game; no engine weights are involved.
+ *   efe_agent_need   : ids[0 .. *count) = the games whose queue is empty (:131), ASCENDING, *count (one device word) their number; a
+ *                      function of `len` alone (no atomics).  ids has room for E entries; those at and beyond *count are not written.
+ *   efe_agent_choose : the draw of :152-184 for the n deciding games ids[0 .. n): row i of the inputs belongs to game ids[i].
+ *                      mode EFE_AGENT_AI : x = -(sum_G / steps)                             sum_G [4n]
+ *                           EFE_AGENT_T1 : x = sum_terms[0] / steps                         sum_terms [3][4n]
+ *                           EFE_AGENT_T12: x = sum_terms[0] / steps - sum_terms[1] / steps
+ *                      p = exp(x / temperature) / sum, fp32, summed left to right, NO max-subtraction; EFE_AGENT_PROBS: p = probs [n][4].
+ *                      The draw is np.random.choice's: cdf = cumsum(p) / cumsum(p)[3], the first edge above u; at u == 1.0 (which the
+ *                      engine's 24-bit uniform can round to) the last action with p > 0.  u = u[i] when injected, else word 0 of the Philox
+ *                      counter (tag 0x70, global game nz->row_offset + ids[i], stream 0, nz->stage); u_out [n] (NULL ok) receives it.
+ *                      If any p is NaN, infinite or negative (exp overflow: inf / inf; all four underflow: 0 / 0) choice[i] = -1 and the
+ *                      queue stays empty (the reference's `except: "Not executing anything"`): the game neither moves nor ticks this
+ *                      tick and decides again on the next.  Otherwise the queue is choice[i] `repeat` times (steps * jumps for ai / t1 /
+ *                      t12, steps for the habit method, :181-184).
+ *   efe_agent_enqueue: queue of game ids[i] = actions[i][0 .. lengths[i]) (int32 [n][L], values 0..3; lengths clamped to [0, L]), each
+ *                      action `jumps` times (the planner's path, :167-170).
+ *   efe_agent_act    : one tick (:189-204).  A game with a non-empty queue takes its head action for exactly one tick of pi_to_action:
+ *                      state, last_r and a crossing's new latents are bit-identical to efe_env_step(repeats = 1) at the same efe_noise
+ *                      (seed, stage, row_offset = global index of game 0).  A crossing clears the queue, adds 1 to crossings and the
+ *                      reward to reward_sum; otherwise the head advances.  A game with an empty queue is left untouched: no move, no
+ *                      last_r *= 0.95.  round_changed [E] may be NULL.
+ * Each call returns 1 with a message that names it, and launches nothing, for E < 1, n < 0 (or n > E), a cap smaller than the queue the
+ * call would write, steps < 1, a temperature that is not finite and positive, an unknown mode, or a NULL required pointer. */
+typedef struct efe_agent { int32_t* queue; int32_t* head; int32_t* len; int32_t* crossings; float* reward_sum; int32_t E, cap; } efe_agent;
+typedef enum { EFE_AGENT_AI = 0, EFE_AGENT_T1 = 1, EFE_AGENT_T12 = 2, EFE_AGENT_PROBS = 3 } efe_agent_mode;
+int efe_agent_need(efe_ctx*, const efe_agent* agent, int32_t* ids, int32_t* count, void* stream);
+int efe_agent_choose(efe_ctx*, const efe_agent* agent, const int32_t* ids, int n, int mode, const float* sum_G, const float* sum_terms,
+                     const float* probs, int steps, float temperature, int repeat, const efe_noise* nz, const float* u, int32_t* choice,
+                     float* u_out, void* stream);
+int efe_agent_enqueue(efe_ctx*, const efe_agent* agent, const int32_t* ids, int n, const int32_t* actions, const int32_t* lengths, int L,
+                      int jumps, void* stream);
+int efe_agent_act(efe_ctx*, const efe_agent* agent, float* state, float* last_r, const efe_noise* nz, int32_t* round_changed, void* stream);
 
 /* ---- device-resident tree of the lock-step MCTS planner (counterpart of Node / active_inference_mcts, src/mcts.py:11-195) ----
  * All pointers are device pointers owned by the caller.  tree = { W, N, Qpi [E][cap][A] floats, child [E][cap][A] int32

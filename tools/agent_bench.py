@@ -1,0 +1,96 @@
+"""Throughput of the agent loop (daimc_amd.agent.AgentRunner), recorded in profiles/agent_bench.json -- a measurement, not a gate.
+
+    python tools/agent_bench.py [--ticks 120] [--games 1 64 1024] [--parent PATH_TO_A_BUILT_PARENT_CHECKOUT] [--out profiles/agent_bench.json]
+
+Per method (habit, ai at steps 7, samples 10) and number of games: game-ticks per second of an unsynchronised run (wall time over
+`--ticks` ticks after a warm-up run of the same length on the same model), and the share of wall time spent in decisions, taken from a
+second run whose decisions are bracketed by device synchronisations (so that run is slower and only its ratio is used).  Freshly
+initialised weights and the synthetic sprite bank: the figures are about the loop, not about an agent's skill.
+With --parent, `bench.py --gpus 1 --steps 20 --warmup 5` is run three times each from this checkout and from the parent's, alternating,
+and both sets of result lines are recorded: no existing kernel changes, so the two should sit inside each other's spread."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def timed_runner():
+    """AgentRunner whose decisions are bracketed by device synchronisations; .spent = seconds inside decisions"""
+    import torch
+    import daimc_amd
+
+    class TimedRunner(daimc_amd.AgentRunner):
+        spent = 0.0
+
+        def _decide(self, ids, t):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            super()._decide(ids, t)
+            torch.cuda.synchronize()
+            self.spent += time.perf_counter() - t0
+    return TimedRunner
+
+
+def one(model, method, E, ticks, timed_decisions):
+    """-> (wall seconds of `ticks` ticks, seconds inside decisions (0 unless timed), run()'s result)"""
+    import torch
+    import daimc_amd
+    games = daimc_amd.Game(E, model=model, seed=1)
+    cls = timed_runner() if timed_decisions else daimc_amd.AgentRunner
+    runner = cls(model, games, method, steps=7, jumps=5, samples=10)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = runner.run(ticks)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    return wall, getattr(runner, 'spent', 0.0), res
+
+
+def bench_line(path):
+    r = subprocess.run([sys.executable, os.path.join(path, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5'], capture_output=True,
+                       text=True, cwd=path, timeout=900)
+    if r.returncode != 0:
+        return {'error': r.stderr[-400:]}
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--ticks', type=int, default=120)
+    ap.add_argument('--games', type=int, nargs='+', default=[1, 64, 1024])
+    ap.add_argument('--parent', default=None)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'agent_bench.json'))
+    args = ap.parse_args(argv)
+    import daimc_amd
+    model = daimc_amd.ActiveInferenceModel(10, 4, 1.0, 1.0, 1.0, device='cuda:0', seed=0)
+    rows = []
+    for method in ('habit', 'ai'):
+        for E in args.games:
+            one(model, method, E, args.ticks, False)                                      # warm-up: arena growth, planner buffers
+            wall, _, res = one(model, method, E, args.ticks, False)
+            wall_s, spent, _ = one(model, method, E, args.ticks, True)
+            row = {'method': method, 'games': E, 'ticks': args.ticks, 'steps': 7, 'jumps': 5, 'samples': 10, 'wall_s': wall,
+                   'game_ticks_per_s': E * args.ticks / wall, 'decisions': res['decisions'], 'failed_ticks': res['failed_ticks'],
+                   'decision_share_of_wall': spent / wall_s, 'synchronised_wall_s': wall_s}
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    out = {'what': 'AgentRunner throughput, freshly initialised weights, synthetic sprite bank', 'loop': rows}
+    if args.parent:
+        out['bench'] = {'this': [], 'parent': []}
+        for _ in range(3):
+            out['bench']['this'].append(bench_line(ROOT))
+            out['bench']['parent'].append(bench_line(os.path.abspath(args.parent)))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(out, fh, indent=1)
+    print('wrote', args.out)
+
+
+if __name__ == '__main__':
+    main()
