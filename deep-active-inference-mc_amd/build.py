@@ -10,8 +10,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ['csrc/kernels.hip', 'csrc/decoder.hip', 'csrc/encoder.hip', 'csrc/mcts.hip', 'csrc/agent.hip', 'csrc/fused.hip', 'csrc/generic.hip', 'csrc/generic_dec.hip', 'csrc/generic_enc.hip', 'csrc/bf16x3.hip', 'csrc/loss.hip', 'csrc/train.hip', 'csrc/train_dec.hip', 'csrc/train_dec_head.hip', 'csrc/train_enc.hip', 'csrc/train_down.hip', 'csrc/engine.hip']
-HEADERS = ['csrc/kernels.h', 'csrc/philox.h', 'csrc/mfma_pipe.h', 'csrc/train_mlp.h', 'csrc/ctx_registry.h', '../include/efe_engine.h']
+SOURCES = ['csrc/kernels.hip', 'csrc/decoder.hip', 'csrc/encoder.hip', 'csrc/mcts.hip', 'csrc/agent.hip', 'csrc/fused.hip', 'csrc/generic.hip', 'csrc/generic_dec.hip', 'csrc/generic_enc.hip', 'csrc/bf16x3.hip', 'csrc/loss.hip', 'csrc/train.hip', 'csrc/train_dec.hip', 'csrc/train_dec_head.hip', 'csrc/train_enc.hip', 'csrc/train_down.hip',
+           'csrc/engine_ctx.hip', 'csrc/engine_weights.hip', 'csrc/engine_forward.hip', 'csrc/engine_efe.hip', 'csrc/engine_control.hip', 'csrc/engine_loss.hip', 'csrc/engine_train.hip']
+HEADERS = ['csrc/kernels.h', 'csrc/philox.h', 'csrc/mfma_pipe.h', 'csrc/train_mlp.h', 'csrc/ctx_registry.h', 'csrc/engine.h', '../include/efe_engine.h']
 LIB = os.path.join(HERE, 'libefe_mi355x.so')
 OPS_SOURCES = ['csrc/torch_ops.cpp']
 OPS_LIB = os.path.join(HERE, 'libefe_torch_ops.so')
@@ -20,13 +21,20 @@ OPS_LIB = os.path.join(HERE, 'libefe_torch_ops.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', '-Wno-pass-failed', '-Wl,-soname,libefe_mi355x.so']
 
 
+def _listed(f):
+    """path of a listed source or header; a listed file that does not exist is an error (skipped, a typo in SOURCES would give a
+    library that links, loads and lacks entry points)"""
+    path = os.path.join(HERE, f)
+    if not os.path.isfile(path):
+        raise RuntimeError(f'build.py lists {f}, which does not exist ({path})')
+    return path
+
+
 def source_digest(files=None):
     """sha256 over the engine sources and headers (names + contents), first 16 hex digits"""
     h = hashlib.sha256()
     for f in (files or SOURCES + HEADERS):
-        path = os.path.join(HERE, f)
-        if not os.path.exists(path):
-            continue
+        path = _listed(f)
         h.update(f.encode())
         with open(path, 'rb') as fh:
             h.update(fh.read())
@@ -82,7 +90,7 @@ def _compile_objects(hipcc, srcs, verbose):
 def build(force=False, verbose=False):
     if force or needs_build():
         hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-        srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
+        srcs = [_listed(s) for s in SOURCES]
         if force:
             import shutil
             shutil.rmtree(os.path.join(HERE, 'build'), ignore_errors=True)     # --force: every object from source

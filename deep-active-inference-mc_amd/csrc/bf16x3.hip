@@ -85,7 +85,7 @@ __device__ __forceinline__ void split3_pk(float x0, float x1, uint32_t& hi, uint
 //          an activation below 2^-3 loses at most 2^-25 absolutely -- and must stay below 65 504: a larger one is DETECTED where it is
 //          split and the row / image poisoned (SchH2::overflow below): loud, never silently wrong.  Operand representation error 2^-22 relative: tools/f16_split_check.py.
 //          The poison (+inf rows / images) is read only by these kernels, which end it in a NaN sum: an exact-fp32 kernel behind k_fc4_b3 or
-//          k_dec_a_b3 could turn it into a finite image (a ReLU maps -inf to 0), so engine.hip run_decoder keeps
+//          k_dec_a_b3 could turn it into a finite image (a ReLU maps -inf to 0), so engine_forward.hip run_decoder keeps
 //          the whole chain split under this scheme -- small launches (k_dec_a_s / quarter sums) take k_fc4, b3_convt3 = 0 is not honoured.
 // Plane 0 = hi.  PA / PB: the weight / activation plane of product pr, small terms first.
 // ---------------------------------------------------------------------------------------------------------

@@ -27,9 +27,9 @@ namespace efe {
 // five products instead of six:
 //     P1 = d0 g1 -> 0    P2 = d1 g1 -> 0, 2    P3 = d0 g2 -> 1    P4 = d1 (g0 + g2) -> 1, 3    P5 = d2 g0 -> 3
 // In 2D (the outer product of this table with itself) a 2 x 2 input block needs 25 products instead of 36: 9 views d_a (x) d_b and 16
-// weight matrices U = w_r (x) w_c, w in {g1, g2, g0 + g2, g0}, formed in fp64 at commit time and rounded once (engine.hip).  The 9
+// weight matrices U = w_r (x) w_c, w in {g1, g2, g0 + g2, g0}, formed in fp64 at commit time and rounded once (engine_weights.hip).  The 9
 // products with one output in both dimensions chain straight into that output; the other 16 run in a short-lived accumulator that is
-// then added into its 2 or 4 outputs.  (The 1D table f22_* is in kernels.h: engine.hip forms the weights from it.)
+// then added into its 2 or 4 outputs.  (The 1D table f22_* is in kernels.h: engine_weights.hip forms the weights from it.)
 //
 // compile-time loop: f(std::integral_constant<int, 0>{}) .. f(std::integral_constant<int, N - 1>{})
 template <class F, int... I> __device__ __forceinline__ void static_for_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -85,7 +85,7 @@ constexpr int DA_BIAS = 273 * DA_PS;       // float4 index of the two bias vecto
 // Layer 1 (ConvTranspose2d(64,64,3,s1,p1) = a 3x3 correlation with the flipped kernel g, pad 1) by Winograd F(2x2, 3x3) (Lavin):
 //   output tile (ty, tx) = pixels (2ty + r, 2tx + c), r, c in {0, 1}; input tile d[i][jj] = x[2ty - 1 + i][2tx - 1 + jj] (zero outside)
 //   xi = (a, b) in 4 x 4:  V_xi = (B^T d B)[a][b],  M_xi[co][tile] = sum_ci U_xi[co][ci] V_xi[ci][tile],  out[r][c] = bias + sum_xi AT[r][a] AT[c][b] M_xi
-// U = G g G^T is formed in fp64 at commit time and rounded once (engine.hip), packed like a 16-tap conv: [xi][2 tiles][8 chunks][64 lanes][4].
+// U = G g G^T is formed in fp64 at commit time and rounded once (engine_weights.hip), packed like a 16-tap conv: [xi][2 tiles][8 chunks][64 lanes][4].
 // Each row of B^T has two non-zero entries, the first +1: row a of B^T d is d[wino_i0(a)] + wino_s1(a) d[wino_i1(a)], so a B fragment is four LDS reads
 // and three fp32 adds per component (a signed add is written as fma(+-1, x, y): exactly y +- x).  16 xi-GEMMs of 32 MFMAs per 32-channel x
 // 32-tile block replace the 9 x 32 of the direct form.  The output transform runs in ascending xi = 4a + b, one signed add per non-zero AT
@@ -203,7 +203,7 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
 // xb + (16 i + jj) DA_PS; column 2 of row i at c2[i]; row 2, column jj < 2, at r2 + jj DA_PS (the callers point x_2 beyond the last
 // row / column at zero pixels).  With the lane order n = 8 (block row & 1) + block column the lanes that one ds_read_b128 pass serves
 // ({0-3, 12-15} of a lane group and {4-11} of the next: pixels at a stride of two, quads at distance one) hit 16 distinct bank quads.
-// U: packed [16 matrices][4 channel tiles][4 chunks][64 lanes][4] (engine.hip); wr: the resource based at this channel tile; dn: distance
+// U: packed [16 matrices][4 channel tiles][4 chunks][64 lanes][4] (engine_weights.hip); wr: the resource based at this channel tile; dn: distance
 // to the tile contracted next (0 or 1), whose first fragments are requested behind this tile's last ones.  aq: the fragments of the
 // tile's first F22_PD steps on entry (f22_l2_first), of the next tile's on exit.
 // ---------------------------------------------------------------------------------------------------------
@@ -623,7 +623,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     // the image's y2 through a buffer resource over exactly its 256 KiB: a row below the image is requested at an out-of-range offset
     // and the hardware returns zeros (the halo row of the last strip)
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.y2) + (size_t)img * (32 * 32 * 64), 0, 32 * 32 * 64 * 4, 0x00020000);
-    // packed U fragments [16 matrices][2 channel halves][4 chunks][64 lanes] (engine.hip): the channel half is folded into the base
+    // packed U fragments [16 matrices][2 channel halves][4 chunks][64 lanes] (engine_weights.hip): the channel half is folded into the base
     const __amdgpu_buffer_rsrc_t wr = wrsrc(a.w3 + (size_t)hf * 4 * 64 * 4);
     const unsigned ln = (unsigned)lane * 16u;
     auto wf = [&](int m, int kc) -> f32x4 { return __builtin_bit_cast(f32x4, wfrag(wr, ln, (size_t)(m * 8 + kc) * 64)); };

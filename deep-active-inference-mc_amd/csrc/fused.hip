@@ -187,7 +187,7 @@ __device__ __forceinline__ float4 hidden16_slice(const float4* __restrict__ Wp, 
 // raises the group's STICKY flag (sync[2], agent scope) before it goes on -- i.e. before it publishes any further slice or arrival -- and
 // the writer reads the flag behind its last gather (k_sim_chain's epilogue): whichever workgroup saw the timeout, at whichever exchange,
 // the writer poisons every output of the launch.  The words re-arm themselves at the end of a launch; after a call that failed the
-// engine zeroes them on the stream before the next split launch (engine.hip, sim_sync_dirty), so a launch that was cut short cannot
+// engine zeroes them on the stream before the next split launch (engine_efe.hip, sim_sync_dirty), so a launch that was cut short cannot
 // leave the next one's barriers open.
 template <int NWG>
 __device__ __forceinline__ void xchg_gather(const float* xbuf, int* sync, int target, float4* act_out, int tid, int* bad) {

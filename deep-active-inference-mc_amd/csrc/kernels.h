@@ -128,7 +128,7 @@ struct GemmArgs {
 struct DecAArgs {
     const float* x4; float* y2;
     const float* w1; const float* b1;   // Winograd F(2x2,3x3) weights packed [16 xi][2][8][64][4] (decoder.hip wino_l1), bias [64]
-    const float* w2; const float* b2;   // F(2, 2) weights packed [16 U][4 channel tiles][4 chunks][64][4] (engine.hip; decoder.hip f22_l2), bias [64]
+    const float* w2; const float* b2;   // F(2, 2) weights packed [16 U][4 channel tiles][4 chunks][64][4] (engine_weights.hip; decoder.hip f22_l2), bias [64]
     int rows;
     RowMask live;
     int parts;            // 1 = persistent, one image per workgroup pass; 8 = small launches, an image over eight workgroups (k_dec_a_s)
@@ -148,7 +148,7 @@ __host__ __device__ constexpr int f22_wt(int p) { return p < 2 ? 0 : p - 1; }
 __host__ __device__ constexpr int f22_o0(int p) { return p < 2 ? 0 : (p < 4 ? 1 : 3); }
 __host__ __device__ constexpr int f22_o1(int p) { return p == 1 ? 2 : (p == 3 ? 3 : -1); }
 __host__ __device__ constexpr int f22_cw(int wt, int k) { return wt == 0 ? (k == 1) : wt == 1 ? (k == 2) : wt == 2 ? (k != 1) : (k == 0); }
-// One element of the transformed weights, shared by the host packers (engine.hip convt_s2_f22_weights / convt_s1_wino_weights) and the
+// One element of the transformed weights, shared by the host packers (engine_weights.hip convt_s2_f22_weights / convt_s1_wino_weights) and the
 // device repack (train_down.hip): k = the nine taps W[ci][co][.][.] of one (ci, co) pair; fp64 in this order, rounded once.
 //   F(2, 2), stride-2 ConvT: U[4 wr + wc] = sum_{kh, kw} f22_cw(wr, kh) f22_cw(wc, kw) k[kh][kw]
 __host__ __device__ inline float f22_u_elem(const float* k, int wr, int wc) {
@@ -175,7 +175,7 @@ __host__ __device__ inline float wino_u_elem(const float* k, int a, int b) {
 
 struct DecBArgs {
     const float* y2;
-    const float* w3; const float* b3;   // F(2, 2) weights packed [16 U][2 channel halves][4 chunks][64][4] (engine.hip), bias [32]
+    const float* w3; const float* b3;   // F(2, 2) weights packed [16 U][2 channel halves][4 chunks][64][4] (engine_weights.hip), bias [32]
     const float* w4; float b4;          // [9 taps][32 ch], scalar bias
     int rows;             // decoder rows (images) in this launch
     RowMask live;
@@ -599,7 +599,7 @@ struct DownAdamArgs {
 };
 void launch_adam_down(const DownAdamArgs& a, hipStream_t st);
 // One packed buffer of the forward paths as k_repack_down rebuilds it from the raw copy: the inverse of the host packer named per kind
-// (engine.hip).  n = owning threads: destination floats (RP_BIAS, RP_TAP32) or destination float4s (the fragment forms).
+// (engine_weights.hip).  n = owning threads: destination floats (RP_BIAS, RP_TAP32) or destination float4s (the fragment forms).
 enum RepackKind {
     RP_BIAS,        // bias padded with zeros to n (upload_layer / pack_linear16), rows optionally permuted
     RP_TAP32,       // [tap][32] of a [32][9] tensor: the encoder's conv1, the decoder's final convolution

@@ -452,7 +452,7 @@ __global__ void __launch_bounds__(256) k_adam(const AdamArgs a) {
     adam_update(g, m, v, wv, a.omb1, a.b2, a.omb2, a.bc2_sqrt, a.step_size, a.eps);
     a.m[i] = m; a.v[i] = v; net.master[i] = wv;
     // the packed forward copies: inverses of upload_packed ([mtile 32][kc 8][lane = co % 32 + 32 (ci % 8 / 4)][ci % 4]) and
-    // pack_linear16 ([mtile 16][kc 16][lane = co % 16 + 16 (ci % 16 / 4)][ci % 4]) of engine.hip
+    // pack_linear16 ([mtile 16][kc 16][lane = co % 16 + 16 (ci % 16 / 4)][ci % 4]) of engine_weights.hip
     for (int l = 0; l < net.nl; ++l) {
         const TrainLayer& L = net.L[l];
         const int e = i - L.w_off, b = i - L.b_off;

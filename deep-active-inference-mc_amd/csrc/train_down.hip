@@ -8,7 +8,7 @@
 //                   exp_avg_sq and the raw master copy only.
 //   k_repack_down : a gather.  One thread owns one destination float4 (weights: one lane's four consecutive K elements of an MFMA
 //                   fragment) or one destination float (bias tables, zero padding included), computes its source index in the raw copy as
-//                   the inverse of the host packer that fills the buffer at efe_commit_weights (engine.hip pack_heads / pack_encoder /
+//                   the inverse of the host packer that fills the buffer at efe_commit_weights (engine_weights.hip pack_heads / pack_encoder /
 //                   pack_decoder) and stores.  The buffers are listed in a device-resident table of RepackDesc (built at commit); a
 //                   workgroup finds its entry by the first-block prefix.  The transformed forms (Winograd F(2x2,3x3) of po_net.13, F(2,2)
 //                   of po_net.15 / .17) call the host's own per-element functions (kernels.h wino_u_elem / f22_u_elem: fp64, the host's
@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(256) k_adam_down(const DownAdamArgs a) {
 }
 
 // source row / column of a permuted Linear: the NHWC index p * channels + c of the kernels -> torch's channel-major c * positions + p
-// (engine.hip nhwc_perm)
+// (engine_weights.hip nhwc_perm)
 __device__ __forceinline__ int perm_of(int i, int channels, int positions) { return channels ? (i % channels) * positions + i / channels : i; }
 
 __global__ void __launch_bounds__(256) k_repack_down(const RepackDesc* __restrict__ table, int n, const float* __restrict__ w) {

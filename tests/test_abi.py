@@ -94,6 +94,19 @@ def test_stale_library_is_refused(tmp_path, monkeypatch):
         _lib.load()
 
 
+def test_build_lists_match_csrc():
+    """build.py's lists and csrc/ name the same files: a listed file that does not exist is a typo (build() refuses it), and a .hip or
+    .h file that no list names would be left out of the library, or out of the digest that marks a binary stale"""
+    import glob
+    from daimc_amd import build
+    for f in build.SOURCES + build.HEADERS + build.OPS_SOURCES:
+        assert os.path.isfile(os.path.join(build.HERE, f)), f'build.py lists {f}, which does not exist'
+    in_csrc = lambda ext: sorted('csrc/' + os.path.basename(p) for p in glob.glob(os.path.join(build.HERE, 'csrc', '*' + ext)))
+    assert in_csrc('.hip') == sorted(build.SOURCES)
+    assert in_csrc('.h') == sorted(h for h in build.HEADERS if h.startswith('csrc/'))
+    assert len(set(build.SOURCES)) == len(build.SOURCES) and len(set(build.HEADERS)) == len(build.HEADERS)
+
+
 def test_bench_refuses_more_ranks_than_devices():
     """`python bench.py --gpus N` without a launcher environment starts its own N ranks -- one per GPU; with fewer visible HIP devices
     than ranks it stops with a message (exit code 2) instead of stacking ranks on one device (--share-device is the explicit

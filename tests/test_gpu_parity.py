@@ -1601,7 +1601,7 @@ def test_fp16_split_overflow_is_loud(weights_cache):
 @pytest.mark.parametrize('dec_split', [1, 0])
 def test_fp16_split_overflow_at_a_small_launch(weights_cache, dec_split):
     """the same overflow weights at N = 100, a launch of at most 128 images.  With the default dec_split such a launch keeps the exact fp32
-    chain under mfma_f16x2 (engine.hip run_decoder: an fp32 consumer could make a finite wrong image of the split kernels' overflow mark):
+    chain under mfma_f16x2 (engine_forward.hip run_decoder: an fp32 consumer could make a finite wrong image of the split kernels' overflow mark):
     every image is finite and within the file's sigmoid tolerance of the exact fp32 result.  With dec_split = 0 it runs the split kernels:
     some image is not finite, and no image is finite and outside that tolerance."""
     import daimc_amd

@@ -21,7 +21,7 @@ Sites -> tests:
   k_root_post (kernels.hip:359)                  test_site_normals_rollout_root
   k_reparam (kernels.hip:469)                    test_device_normals_vs_mirror
   k_sim_chain (fused.hip:355/380/398)            test_simulate*, test_device_uniforms_bit_equal, test_site_normals_simulate
-  pass_noise (engine.hip)                        test_free_energy
+  pass_noise (engine_forward.hip)                test_free_energy
   k_env_* (kernels.hip:486/545/546)              test_environment
   generic launchers (GemmArgs filled separately) test_generic_geometry
 

@@ -6,7 +6,7 @@ masks and the objective are the same at each step.  The batch sizes are the smal
 gradient is the slab), 3 (one row group), 65 (two row groups, one ragged), and the reference's 50 in the composition test.
 
 The repack test compares the trained model with a FRESH model built by the host packers from the downloaded weights, bit for bit, on every
-reader of the packed forms that engine.hip's launch code has at 1 x 64 x 64 (DESIGN.md section 7g lists the forms against these calls):
+reader of the packed forms that engine_forward.hip's launch code has at 1 x 64 x 64 (DESIGN.md section 7g lists the forms against these calls):
     encoder / encoder_with_sample        k_enc_trunk (enc_w1, enc_b1, conv2 / conv3 taps, conv4 16x16x4), k_head (enc16) or, head_unfused,
                                          k_dense (enc_fc 32x32x2, the first layer's columns NHWC)
     decoder                              k_head (dec16) or k_dense (dec_fc), k_fc4 (po_net.9, rows NHWC), k_dec_a_s / k_dec_a (Winograd of
