@@ -17,7 +17,8 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top',
            'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
            'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step',
-           'efe_encoder_rows', 'efe_rollout_rows', 'efe_agent_need', 'efe_agent_choose', 'efe_agent_enqueue', 'efe_agent_act']
+           'efe_encoder_rows', 'efe_rollout_rows', 'efe_agent_need', 'efe_agent_choose', 'efe_agent_enqueue', 'efe_agent_act',
+           'efe_agent_mcts_root', 'efe_agent_mcts_enqueue']
 ABI_VERSION = 6
 
 
@@ -200,5 +201,7 @@ def load():
     lib.efe_agent_choose.argtypes = [p, agp, p, i, i, f32p, f32p, f32p, i, C.c_float, i, nzp, f32p, p, f32p, p]; lib.efe_agent_choose.restype = i
     lib.efe_agent_enqueue.argtypes = [p, agp, p, i, p, p, i, i, p]; lib.efe_agent_enqueue.restype = i
     lib.efe_agent_act.argtypes = [p, agp, f32p, f32p, nzp, p, p]; lib.efe_agent_act.restype = i
+    lib.efe_agent_mcts_root.argtypes = [p, agp, p, i, f32p, i, i, C.c_float, i, i, nzp, f32p, p, p, p, f32p, p]; lib.efe_agent_mcts_root.restype = i
+    lib.efe_agent_mcts_enqueue.argtypes = [p, agp, C.POINTER(EfeMctsTree), p, i, p, i, i, p, p, p]; lib.efe_agent_mcts_enqueue.restype = i
     _lib = lib
     return lib

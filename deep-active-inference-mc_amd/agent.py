@@ -3,7 +3,8 @@ paper's methods, execute it tick by tick in Dynamic-dSprites, drop the rest of t
 every `round_ticks` ticks and report the score every `report_ticks` ticks (test_demo.py:118-204).
 
 The per-game control state (the action queue `executing_steps`, the reward crossings and the sum of the rewards received) lives in device
-arrays behind `efe_agent` of the C ABI; `AgentState` binds its four kernels (csrc/agent.hip) and `AgentRunner` is the loop.  Only the games
+arrays behind `efe_agent` of the C ABI; `AgentState` binds its four kernels (csrc/agent.hip) and the two ends of an mcts decision
+(csrc/agent_mcts.hip: the habit shortcut's draw, and the walk, trim and queueing of the planned path), and `AgentRunner` is the loop.  Only the games
 whose queue is empty decide on a tick, as a compacted call whose noise follows the game (Rows: efe_encoder_rows / efe_rollout_rows)."""
 import ctypes as C
 
@@ -96,6 +97,43 @@ class AgentState:
         ln = torch.as_tensor(lengths).to(device=e.device, dtype=torch.int32).reshape(n).contiguous()
         self._call(e.lib.efe_agent_enqueue, _i32(ids), n, _i32(a), _i32(ln), int(a.shape[1]), int(jumps))
 
+    def mcts_root(self, ids, Qpi, active, decided, *, use_habit, threshold, max_depth, jumps=1, seed=0, stage=0, game_offset=0, u=None,
+                  want_u=False):
+        """efe_agent_mcts_root: the beginning of an mcts decision for the deciding games `ids` (int32 device tensor [n]; slot i plans for game
+        ids[i]).  Qpi [n, A] is the habit posterior of the root states; `active` and `decided` (uint8 device tensors, [>= n]) are written:
+        the planner's liveness mask and what mcts_enqueue skips.  -> choice [n] int32: the habit shortcut's action (its queue is written,
+        `jumps` times), -1 for a Qpi that is no distribution (empty queue, decided), -2 where the planner goes on; or (choice, u) with want_u.
+        stage is the tick: the uniform has the key of choose()'s."""
+        e = self._engine
+        n = int(ids.numel())
+        choice = torch.empty(n, dtype=torch.int32, device=e.device)
+        u_out = torch.empty(n, dtype=torch.float32, device=e.device) if want_u else None
+        if n == 0:
+            return (choice, u_out) if want_u else choice
+        Qpi = e.tensor(Qpi)
+        if Qpi.dim() != 2 or Qpi.shape[0] != n:
+            raise ValueError(f'Qpi has shape {tuple(Qpi.shape)}, expected ({n}, pi_dim)')
+        for t, nm in ((active, 'active'), (decided, 'decided')):
+            if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.numel() < n:
+                raise ValueError(f'{nm}: a contiguous uint8 device tensor of at least {n} entries is required')
+        u_t = self._f32(u, n, 'u')
+        nz = _lib.EfeNoise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage) & 0xFFFFFFFF, 0, 0, int(game_offset) & 0xFFFFFFFF)
+        self._call(e.lib.efe_agent_mcts_root, _i32(ids), n, _ptr(Qpi), int(Qpi.shape[1]), 1 if use_habit else 0, C.c_float(float(threshold)),
+                   int(max_depth), int(jumps), C.byref(nz), _ptr(u_t), _i32(active), _i32(decided), _i32(choice), _ptr(u_out))
+        return (choice, u_out) if want_u else choice
+
+    def mcts_enqueue(self, ids, tree, decided, max_depth, jumps=1, want_path=False):
+        """efe_agent_mcts_enqueue: for every slot i with decided[i] == 0 the queue of game ids[i] becomes the trimmed most-visited path of tree
+        slot i (`tree`: an _lib.EfeMctsTree, e.g. BatchedMCTS.tree_of(n)), each action `jumps` times.  want_path -> (path [n, max_depth] int32,
+        path_len [n] int32) on the device, pre-filled with -1 (decided slots and entries beyond the length are not written)."""
+        e = self._engine
+        n = int(ids.numel())
+        path = torch.full((n, max(int(max_depth), 1)), -1, dtype=torch.int32, device=e.device) if want_path else None
+        plen = torch.full((n,), -1, dtype=torch.int32, device=e.device) if want_path else None
+        if n:
+            self._call(e.lib.efe_agent_mcts_enqueue, C.byref(tree), _i32(ids), n, _i32(decided), int(max_depth), int(jumps), _i32(path), _i32(plen))
+        return (path, plen) if want_path else None
+
     def act(self, games, stage, want_changed=False):
         """efe_agent_act on `games` (a daimc_amd.Game of the same size): one tick for every game with a non-empty queue"""
         e = self._engine
@@ -122,22 +160,31 @@ class AgentRunner:
     Decisions (the deciding games' frames are rendered from their gathered state rows):
       habit          : encoder(rows=ids) -> encode_s -> choose('probs'), the action `steps` times
       ai / t1 / t12  : batched calculate_G_4_repeated(rows=ids, steps, samples, calc_mean) -> choose, the action steps * jumps times
-      mcts           : active_inference_mcts_batch on the deciding frames -> enqueue(path, jumps)
+      mcts           : active_inference_mcts_batch on the deciding frames -> enqueue(path, jumps); with keyed_planner = True one id-keyed
+                       planner for all the games (BatchedMCTS(keyed=True)): root encoder(rows=ids) -> encode_s -> mcts_root (the habit
+                       shortcut's draw, on the device) -> the planner's iterations -> mcts_enqueue (walk, trim and queue, on the device)
 
     Noise: every draw's stage is a function of the tick alone and its row a function of the game's global index g = games.game_offset + e:
       environment    : seed games.seed; start = stage 0, the reset of tick t = stage 1 + 2 t, its act = stage 2 + 2 t; row g
       model          : seed model.seed; the decision of tick t starts at stage t * steps (a rollout takes `steps` stages); rows 4 g .. 4 g + 3
                        for the rollouts, row g for the habit encoder
       action uniform : seed model.seed, tag 0x70, stage t, row g
+      keyed planner  : seed model.seed; the decision of tick t starts at stage t * P, P = 2 + repeats * (1 + simulation_repeats): root encoder
+                       t P, root expansion t P + 1, expansion of iteration r  t P + 2 + r (1 + simulation_repeats), its simulation k that
+                       + 1 + k; row g for the encoder and the simulations, rows A g .. A g + A - 1 for the expansions; the habit shortcut's
+                       action uniform is the one above (tag 0x70, stage t, row g)
     (all modulo 2^32).  The trajectory of a game is therefore the same whether it runs alone (game_offset = g) or inside any batch -- for
-    habit, ai, t1 and t12.  NOT for mcts: the planner keys an episode by its slot among the deciding games and takes its stages from the
-    model's own counter, so an mcts trajectory depends on which other games decide on the same tick.
+    habit, ai, t1 and t12, and for mcts with keyed_planner = True.  NOT for mcts with the default slot planner (keyed_planner = False, kept
+    as the default for now; the keyed planner is meant to replace it): that planner keys an episode by its slot among the deciding games and
+    takes its stages from the model's own counter, so the trajectory depends on which other games decide on the same tick, and its habit
+    shortcut draws from the host's global generator.
 
     Host traffic per tick: one 4-byte read-back (the number of deciding games), plus the render validity flag on ticks where a game decides
-    (mcts: plus the planner's own read-backs).  run() fetches everything else once at its end."""
+    (mcts: plus the planner's own read-backs -- keyed: only its lagged stop snapshot, one pinned copy per iteration that the host reads two
+    iterations later).  run() fetches everything else once at its end."""
 
     def __init__(self, model, games, method, *, steps=7, jumps=5, temperature=1.0, samples=None, calc_mean=False, mcts_params=None,
-                 round_ticks=100, report_ticks=1000):
+                 round_ticks=100, report_ticks=1000, keyed_planner=False):
         if method not in METHODS:
             raise ValueError(f'unknown method {method!r}: one of {METHODS}')
         self.model, self.games, self.method = model, games, method
@@ -153,7 +200,13 @@ class AgentRunner:
             from .mcts import MCTS_Params
             self.mcts_params = mcts_params if mcts_params is not None else MCTS_Params()
             cap = max(cap, (self.mcts_params.repeats + 2) * self.jumps)
+        self.keyed_planner = bool(keyed_planner) and method == 'mcts'      # (the other methods key every draw by the game as they are)
         self.state = AgentState(model._ready(), games.games_no, cap)
+        if self.keyed_planner:
+            from .mcts import BatchedMCTS
+            # ONE planner for all the games, reused by every decision; the decision of tick t starts at stage t * P
+            self.planner = BatchedMCTS(model, games.games_no, self.mcts_params, keyed=True)
+            self.stages_per_decision = BatchedMCTS.stages_per_decision(self.mcts_params)
         self.t = 0
         self.decisions = 0
         self.scores = []
@@ -184,6 +237,15 @@ class AgentRunner:
             mean, _ = m.model_down.encoder(frames, stage=stage, row_offset=g.game_offset & 0xFFFFFFFF, rows=Rows(ids=ids, rows_per_entry=1, n_total=E))
             _, Qpi, _ = m.model_top.encode_s(mean)
             choice = st.choose(ids, 'probs', probs=Qpi, steps=self.steps, temperature=self.temperature, repeat=self.steps, **key)
+        elif self.keyed_planner:
+            pl, p = self.planner, self.planner.p
+            Qpi = pl.begin_keyed(frames, ids, g.game_offset, (t * self.stages_per_decision) & 0xFFFFFFFF, o_shape=(1, 64, 64))
+            choice = st.mcts_root(ids, Qpi, pl.active, pl.decided, use_habit=p.use_habit, threshold=p.threshold, max_depth=pl.max_depth,
+                                  jumps=self.jumps, **key)
+            pl.plan_keyed()
+            st.mcts_enqueue(ids, pl.tree_of(n), pl.decided, pl.max_depth, self.jumps)
+            self._failed += (choice == -1).any().to(torch.int32)
+            return
         elif self.method == 'mcts':
             from .mcts import active_inference_mcts_batch
             out, _ = active_inference_mcts_batch(m, frames, self.mcts_params, o_shape=(1, 64, 64), episode_offset=g.game_offset)

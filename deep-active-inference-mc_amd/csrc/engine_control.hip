@@ -108,6 +108,47 @@ int efe_agent_act(efe_ctx* ctx, const efe_agent* agent, float* state, float* las
     return call.finish();
 }
 
+int efe_agent_mcts_root(efe_ctx* ctx, const efe_agent* agent, const int32_t* ids, int n, const float* Qpi, int A, int use_habit, float threshold,
+                        int max_depth, int jumps, const efe_noise* nz, const float* u, uint8_t* active, uint8_t* decided, int32_t* choice,
+                        float* u_out, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentState a; if (agent_state(ctx, "efe_agent_mcts_root", agent, a)) return 1;
+    if (n < 0 || n > a.E) return ctx->fail("efe_agent_mcts_root: n < 0 or n > E");
+    if (A != 3 && A != 4) return ctx->fail("efe_agent_mcts_root: A = " + std::to_string(A) + ", the path trimming is defined for 3 and 4 actions");
+    if (jumps < 1) return ctx->fail("efe_agent_mcts_root: jumps < 1");
+    if (max_depth < 1) return ctx->fail("efe_agent_mcts_root: max_depth < 1");
+    if ((int64_t)max_depth * jumps > a.cap)
+        return ctx->fail("efe_agent_mcts_root: the queue capacity " + std::to_string(a.cap) + " is smaller than max_depth * jumps = " +
+                         std::to_string((int64_t)max_depth * jumps) + ", the longest queue this decision could write");
+    if (!ids || !Qpi || !active || !decided || !choice) return ctx->fail("efe_agent_mcts_root: ids, Qpi, active, decided or choice is NULL");
+    if (!nz && !u) return ctx->fail("efe_agent_mcts_root: neither efe_noise nor injected uniforms");
+    const uint64_t seed = nz ? nz->seed : 0;
+    launch_agent_mcts_root(a, ids, n, Qpi, A, use_habit ? 1 : 0, threshold, jumps, (uint32_t)seed, (uint32_t)(seed >> 32), nz ? nz->stage : 0u,
+                           nz ? nz->row_offset : 0u, u, active, decided, choice, u_out, (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_mcts_enqueue(efe_ctx* ctx, const efe_agent* agent, const efe_mcts_tree* tree, const int32_t* ids, int n, const uint8_t* decided,
+                           int max_depth, int jumps, int32_t* path_out, int32_t* path_len_out, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentState a; if (agent_state(ctx, "efe_agent_mcts_enqueue", agent, a)) return 1;
+    if (n < 0 || n > a.E) return ctx->fail("efe_agent_mcts_enqueue: n < 0 or n > E");
+    if (!tree) return ctx->fail("efe_agent_mcts_enqueue: tree is NULL");
+    if (tree->A != 3 && tree->A != 4)
+        return ctx->fail("efe_agent_mcts_enqueue: A = " + std::to_string(tree->A) + ", the path trimming is defined for 3 and 4 actions");
+    if (!tree->N || !tree->child) return ctx->fail("efe_agent_mcts_enqueue: N or child of the tree is NULL");
+    if (tree->cap < 1 || n > tree->E) return ctx->fail("efe_agent_mcts_enqueue: the tree has cap < 1 or fewer than n slots");
+    if (jumps < 1) return ctx->fail("efe_agent_mcts_enqueue: jumps < 1");
+    if (max_depth < 1) return ctx->fail("efe_agent_mcts_enqueue: max_depth < 1");
+    if ((int64_t)max_depth * jumps > a.cap)
+        return ctx->fail("efe_agent_mcts_enqueue: the queue capacity " + std::to_string(a.cap) + " is smaller than max_depth * jumps = " +
+                         std::to_string((int64_t)max_depth * jumps) + ", the longest queue this call could write");
+    if (!ids || !decided) return ctx->fail("efe_agent_mcts_enqueue: ids or decided is NULL");
+    const MctsTree t{tree->W, tree->N, tree->Qpi, tree->child, tree->S, tree->E, tree->cap, tree->A, tree->s_dim};
+    launch_agent_mcts_enqueue(a, t, ids, n, decided, max_depth, jumps, path_out, path_len_out, (hipStream_t)stream);
+    return call.finish();
+}
+
 int efe_mcts_select(efe_ctx* ctx, const efe_mcts_tree* tree, const uint8_t* active, float C, int use_prior, int max_depth,
                     int32_t* path_nodes, int32_t* path_act, int32_t* path_len, int32_t* leaf, float* leaf_s, float* leaf_s_rep,
                     void* stream) {

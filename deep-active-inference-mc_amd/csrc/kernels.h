@@ -256,6 +256,15 @@ struct MctsTree {
     float* S;                         // [E][cap][s_dim] latent state of every node
     int E, cap, A, s_dim;
 };
+__device__ __forceinline__ int argmax_nan_first(const float* v, int n) {          // torch.argmax: NaN is the maximum, first index wins
+    int best = 0;
+    for (int i = 1; i < n; ++i) {
+        const bool nb = v[best] != v[best], ni = v[i] != v[i];
+        if (nb) continue;
+        if (ni || v[i] > v[best]) best = i;
+    }
+    return best;
+}
 void launch_mcts_select(const MctsTree& t, const uint8_t* active, float C, int use_prior, int max_depth, int32_t* path_nodes,
                         int32_t* path_act, int32_t* path_len, int32_t* leaf, float* leaf_s, float* leaf_s_rep, hipStream_t st);
 void launch_mcts_expand(const MctsTree& t, int32_t* n_nodes, const int32_t* nodes, const uint8_t* mask, const float* G,
@@ -684,5 +693,11 @@ void launch_agent_choose(const AgentState& a, const int32_t* ids, int n, int mod
 void launch_agent_enqueue(const AgentState& a, const int32_t* ids, int n, const int32_t* actions, const int32_t* lengths, int L, int jumps, hipStream_t st);
 void launch_agent_act(const AgentState& a, float* state, float* last_r, int32_t* round_changed, uint32_t k0, uint32_t k1, uint32_t stage,
                       uint32_t game_offset, hipStream_t st);
+// the two ends of an mcts decision (csrc/agent_mcts.hip): one thread per deciding slot i of game ids[i]; n < 1 launches nothing
+void launch_agent_mcts_root(const AgentState& a, const int32_t* ids, int n, const float* Qpi, int A, int use_habit, float threshold, int jumps,
+                            uint32_t k0, uint32_t k1, uint32_t stage, uint32_t game_offset, const float* u, uint8_t* active, uint8_t* decided,
+                            int32_t* choice, float* u_out, hipStream_t st);
+void launch_agent_mcts_enqueue(const AgentState& a, const MctsTree& t, const int32_t* ids, int n, const uint8_t* decided, int max_depth, int jumps,
+                               int32_t* path_out, int32_t* path_len_out, hipStream_t st);
 
 }  // namespace efe

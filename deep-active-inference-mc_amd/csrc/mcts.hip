@@ -12,15 +12,7 @@ namespace efe {
 // keeps hipcc from contracting  a * b + c  into an fma (the reference rounds the product first)
 __device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
 
-__device__ __forceinline__ int argmax_nan_first(const float* v, int n) {          // torch.argmax: NaN is the maximum, first index wins
-    int best = 0;
-    for (int i = 1; i < n; ++i) {
-        const bool nb = v[best] != v[best], ni = v[i] != v[i];
-        if (nb) continue;
-        if (ni || v[i] > v[best]) best = i;
-    }
-    return best;
-}
+// (argmax_nan_first -- torch.argmax: NaN is the maximum, first index wins -- lives in kernels.h: csrc/agent_mcts.hip walks the tree by it too)
 
 // Tree-policy walk of ONE episode (mcts.py:49-62).  A level costs ONE memory latency: the W / N / Qpi / child rows of the current node are
 // requested together, and "the node just reached has no children" (mcts.py:56) is read off the child row that the next level loads anyway.

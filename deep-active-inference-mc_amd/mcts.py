@@ -227,9 +227,23 @@ class BatchedMCTS:
     children, node states) are device-resident [E, nodes, pi_dim] arrays; selection, expansion bookkeeping, back-propagation
     and the early-stop test are one-thread-per-episode kernels behind the C ABI (`efe_mcts_*`, csrc/mcts.hip), so an
     iteration is a stream of launches with no host round trip between the engine calls.  The host only reads the number of
-    still-active episodes (one int per iteration) and, at the end, the history needed for the reference's return tuple."""
+    still-active episodes (one int per iteration) and, at the end, the history needed for the reference's return tuple.
 
-    def __init__(self, model, n_episodes, params, episode_offset=0):
+    keyed = True is the agent loop's form (daimc_amd.agent.AgentRunner(keyed_planner=True)): ONE planner sized for all E games of a Game,
+    reused for every decision.  A decision runs in the first n SLOTS for the n <= E deciding games `ids` (the device tensor of
+    efe_agent_need, never a host list): the tree arrays stay slot-indexed, every engine call gets Rows(ids = the game of each live slot,
+    n_total = E) and row_offset = game_offset * rows_per_entry, so a draw is keyed by the game's global index g = game_offset + id (encoder
+    and simulation: row g; expansions: rows A g + a) and by stages that are a function of `stage0` alone:
+        root encoder stage0, root expansion stage0 + 1, expansion of iteration r stage0 + 2 + r (1 + simulation_repeats), its simulation k
+        that + 1 + k
+    -- the order in which the slot planner consumes the model's counter, which a keyed decision neither reads nor advances.  What a game
+    plans is therefore the same alone and inside any batch.  The engine reads the liveness mask at the game id, the tree kernels write it at
+    the slot: `active_g` is the game-indexed copy, refreshed on the device behind every kernel that writes `active`.  No history is kept
+    (H_* are two-row rings: efe_mcts_step needs the previous iteration's rows only) and nothing is downloaded at the end; the lagged stop
+    snapshot is the planner's only host traffic.  begin_keyed / plan_keyed are the two halves of a decision, with efe_agent_mcts_root
+    between them and efe_agent_mcts_enqueue behind them (csrc/agent_mcts.hip)."""
+
+    def __init__(self, model, n_episodes, params, episode_offset=0, keyed=False):
         import ctypes as C
         import weakref
         from . import _lib
@@ -247,6 +261,9 @@ class BatchedMCTS:
                           'iterations directly (INTEGRATION.md section 4)', RuntimeWarning, stacklevel=3)
         self.pi_dim = A = model.pi_dim
         self.ep0 = int(episode_offset)
+        self.keyed = bool(keyed)
+        # slots in use, the global index of entry 0 and the game of every slot: a keyed decision sets them (begin_keyed)
+        self.n, self.ro, self._gid = self.E, self.ep0, None
         self.cap = cap = 1 + A * (params.repeats + 2)
         self.max_depth = params.repeats + 2
         E, dev = self.E, model.device
@@ -258,10 +275,10 @@ class BatchedMCTS:
         self.n_nodes = torch.ones(E, dtype=torch.int32, device=dev)
         self._tree = _lib.EfeMctsTree(self.W.data_ptr(), self.N.data_ptr(), self.Qpi.data_ptr(), self.child.data_ptr(),
                                       self.S.data_ptr(), E, cap, A, model.s_dim)
-        self._C = C
+        self._C, self._tree_now = C, self._tree
         self.pi_hot = (model.pi_one_hot if A == 4 else model.pi_one_hot_3).repeat(E, 1)
         # per-iteration scratch + history (device)
-        R = max(1, params.repeats)
+        R = 2 if self.keyed else max(1, params.repeats)             # (keyed: rings of two rows, no history)
         self.path_nodes = torch.zeros(E, self.max_depth, dtype=torch.int32, device=dev)
         self.H_act = torch.zeros(R, E, self.max_depth, dtype=torch.int32, device=dev)
         self.H_len = torch.zeros(R, E, dtype=torch.int32, device=dev)
@@ -273,9 +290,13 @@ class BatchedMCTS:
         self.sims = torch.zeros(max(1, params.simulation_repeats), E, device=dev)
         self.stop_at = torch.full((E,), -1, dtype=torch.int32, device=dev)
         self.n_active = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.n_active_it = torch.zeros(R + 1, dtype=torch.int32, device=dev)       # efe_mcts_step: one word per iteration
+        self.n_active_it = torch.zeros(max(1, params.repeats) + 1, dtype=torch.int32, device=dev)       # efe_mcts_step: one word per iteration
         self.q0 = torch.zeros(E, A, device=dev)
         self.active = torch.zeros(E, dtype=torch.uint8, device=dev)
+        if self.keyed:
+            self.active_g = torch.zeros(E, dtype=torch.uint8, device=dev)      # `active` by game id, as the engine reads efe_rows.mask
+            self.decided = torch.zeros(E, dtype=torch.uint8, device=dev)       # efe_agent_mcts_root -> efe_agent_mcts_enqueue
+            self._sims_buf, self._trees = self.sims.view(-1), {}
         self.root_nodes = torch.zeros(E, dtype=torch.int32, device=dev)
         # expansion / simulation results of a COMPACTED call (only the live episodes, efe_rows.ids) are scattered into these full-size rows
         self.G_full = torch.zeros(E * A, device=dev)
@@ -302,7 +323,7 @@ class BatchedMCTS:
 
     def _call(self, fn, *args):
         e = self.model._ready()
-        e.check(fn(e.ctx, self._C.byref(self._tree), *args, e.stream()))
+        e.check(fn(e.ctx, self._C.byref(self._tree_now), *args, e.stream()))      # (_tree_now: all E slots, or the first n of a keyed decision)
 
     @staticmethod
     def _p(t):
@@ -315,6 +336,8 @@ class BatchedMCTS:
         from .model import Rows
         if mask is None and self._ids is None:
             return None
+        if mask is not None and self._gid is not None:
+            mask = self.active_g                                     # (keyed: the engine reads the mask at the game id)
         # one Rows object per (mask, rows_per_entry) and compaction: built where the batch is compacted, reused by every call until the next one
         key = (None if mask is None else mask.data_ptr(), rows_per_entry)
         r = self._rows_cache.get(key)
@@ -323,10 +346,14 @@ class BatchedMCTS:
             r = self._rows_cache[key] = Rows(mask=mask, ids=ids, rows_per_entry=rows_per_entry, ids_host=ids_host, n_total=self.E)
         return r
 
+    def _entries(self):
+        """entries of the engine calls as they stand: the slots in use, or the live ones since the last compaction"""
+        return self.n if self._ids is None or self._ids[2] is None else int(self._ids[2].numel())
+
     def _compact(self, n_live):
         """gather the live episodes into a dense batch for the following iterations (called where the host has just read the active count:
         no extra synchronisation; the lagged check uses _compact_host).  The dense layers, which cannot skip single rows, shrink too."""
-        cur = self.E if self._ids is None else len(self._ids[1])
+        cur = self._entries()
         if n_live <= 0 or n_live > (1.0 - float(getattr(self.p, 'compact_min_dead', 0.03))) * cur:
             return
         idx = torch.nonzero(self.active).flatten()
@@ -335,7 +362,7 @@ class BatchedMCTS:
 
     def _compact_host(self, snap, n_live):
         """the same from a host snapshot of `active` (the lagged check): no device synchronisation at all"""
-        cur = self.E if self._ids is None else len(self._ids[1])
+        cur = self._entries()
         if n_live <= 0 or n_live > (1.0 - float(getattr(self.p, 'compact_min_dead', 0.03))) * cur:
             return
         ids = np.flatnonzero(snap)
@@ -343,6 +370,10 @@ class BatchedMCTS:
         stage = self.h_ids[self._h_ids_k]                                                   # source would synchronise the whole stream)
         stage[:len(ids)] = torch.from_numpy(ids)
         idx = stage[:len(ids)].to(self.active.device, non_blocking=True)
+        if self._gid is not None:                                    # keyed: the live SLOTS idx, and the games they belong to for the engine
+            self._ids = (self._gid[0].index_select(0, idx), None, idx)
+            self._rows_cache = {}
+            return
         self._ids = (idx.to(torch.int32).contiguous(), ids.tolist(), idx)
         self._rows_cache = {}
 
@@ -350,19 +381,20 @@ class BatchedMCTS:
         """ONE engine call over E x pi_dim rows (Node.expand, mcts.py:64-86); tree bookkeeping only where mask[e].  defer: the bookkeeping
         (W -= G, N += 1, children, their states) is left to the NEXT efe_mcts_step launch -> returns the (G, ps_next) tensors it needs"""
         m, p_, A = self.model, self._p, self.pi_dim
-        ro = self.ep0 * A
+        ro = (self.ro * A) & 0xFFFFFFFF
         rows = self._rows(mask if use_mask else None, A)
         pi_hot = self.pi_hot
-        if self._ids is not None:
-            idx = self._ids[2]
-            states_rep = states_rep.view(self.E, A, -1).index_select(0, idx).reshape(idx.numel() * A, -1)
+        idx = self._ids[2] if self._ids is not None else None        # the live slots of a compacted batch
+        if idx is not None:
+            states_rep = states_rep.view(-1, A, states_rep.shape[-1]).index_select(0, idx).reshape(idx.numel() * A, -1)
             pi_hot = self.pi_hot[:idx.numel() * A]
+        elif self.n != self.E:                                       # (keyed: the first n slots)
+            states_rep, pi_hot = states_rep[:self.n * A], self.pi_hot[:self.n * A]
         if self.p.use_means:
             G, _, ps_next, _ = m.calculate_G_mean(states_rep, pi_hot, row_offset=ro, stage=stage, rows=rows)
         else:
             G, _, ps_next, _, _ = m.calculate_G(states_rep, pi_hot, samples=getattr(self.p, 'samples', 1), row_offset=ro, stage=stage, rows=rows)
-        if self._ids is not None:
-            idx = self._ids[2]
+        if idx is not None:
             self.G_full.view(self.E, A).index_copy_(0, idx, G.view(-1, A))
             self.ps_full.view(self.E, A, -1).index_copy_(0, idx, ps_next.view(idx.numel(), A, -1))
             G, ps_next = self.G_full, self.ps_full
@@ -377,18 +409,19 @@ class BatchedMCTS:
         iteration and an un-compacted batch the engine's own output tensors are handed to the back-propagation: self._sim_out, no copies)"""
         p = self.p
         rows = self._rows(mask, 1)
-        leaf_s = self.leaf_s if self._ids is None else self.leaf_s.index_select(0, self._ids[2])
+        idx = self._ids[2] if self._ids is not None else None        # the live slots of a compacted batch
+        leaf_s = self.leaf_s.index_select(0, idx) if idx is not None else self.leaf_s if self.n == self.E else self.leaf_s[:self.n]
         self._sim_out = None
         for r in range(p.simulation_repeats):
-            G, _, q0 = model.simulate_batch(leaf_s, p.simulation_depth, use_means=False, row_offset=self.ep0, stage=stage_of(r), rows=rows)
-            if direct and p.simulation_repeats == 1 and self._ids is None:
+            G, _, q0 = model.simulate_batch(leaf_s, p.simulation_depth, use_means=False, row_offset=self.ro & 0xFFFFFFFF, stage=stage_of(r), rows=rows)
+            if direct and p.simulation_repeats == 1 and idx is None:
                 self._sim_out = (G, q0)          # (kept until the next iteration's simulation, which starts behind this one's back-propagation)
-            elif self._ids is None:
+            elif idx is None:
                 self.sims[r].copy_(G)
-                self.q0.copy_(q0)
+                (self.q0 if self.n == self.E else self.q0[:self.n]).copy_(q0)
             else:
-                self.sims[r].index_copy_(0, self._ids[2], G)
-                self.q0.index_copy_(0, self._ids[2], q0)
+                self.sims[r].index_copy_(0, idx, G)
+                self.q0.index_copy_(0, idx, q0)
 
     def action_selection(self, e, N=None, child=None):
         N = self.N.cpu().numpy() if N is None else np.asarray(N)
@@ -407,7 +440,69 @@ class BatchedMCTS:
         self.W.zero_(); self.N.zero_(); self.Qpi.zero_()
         self.child.fill_(-1); self.n_nodes.fill_(1); self.stop_at.fill_(-1)
 
+    # ---- a keyed decision (the agent loop): begin_keyed -> efe_agent_mcts_root -> plan_keyed -> efe_agent_mcts_enqueue ----------------------
+    def tree_of(self, n):
+        """the efe_mcts_tree of the first n slots (the arrays are slot-major: a prefix of them is a smaller tree)"""
+        t = self._trees.get(n)
+        if t is None:
+            from . import _lib
+            t = self._trees[n] = _lib.EfeMctsTree(self.W.data_ptr(), self.N.data_ptr(), self.Qpi.data_ptr(), self.child.data_ptr(),
+                                                  self.S.data_ptr(), n, self.cap, self.pi_dim, self.model.s_dim)
+        return t
+
+    def _refresh_active_g(self):
+        """active (by slot) -> active_g (by game id), on the device; entries of games that do not decide are stale and never read"""
+        self.active_g.index_copy_(0, self._gid[1], self.active[:self.n])
+
+    def begin_keyed(self, frames, ids, game_offset, stage0, o_shape=(64, 64, 1)):
+        """The first half of a decision for the games `ids` (int32 device tensor [n], ascending as efe_agent_need writes them) whose
+        frames are `frames` [n, ...]: fresh trees in the first n slots, the root encoder (stage0, row game_offset + id) and the habit
+        posterior -> Qpi [n, pi_dim].  efe_agent_mcts_root then writes self.active[:n] and self.decided[:n], and plan_keyed goes on."""
+        if not self.keyed:
+            raise RuntimeError('begin_keyed needs BatchedMCTS(..., keyed=True)')
+        from .model import Rows
+        m, A = self.model, self.pi_dim
+        n = int(ids.numel())
+        if n < 1 or n > self.E:
+            raise ValueError(f'{n} deciding games for a planner of {self.E}')
+        self.n, self.ro, self._gid = n, int(game_offset), (ids, ids.long())
+        self.stage0 = int(stage0) & 0xFFFFFFFF
+        self.W[:n].zero_(); self.N[:n].zero_(); self.Qpi[:n].zero_()
+        self.child[:n].fill_(-1); self.n_nodes[:n].fill_(1); self.stop_at[:n].fill_(-1)
+        self.sims = self._sims_buf[:max(1, self.p.simulation_repeats) * n].view(-1, n)          # [simulations][slots]: the tree kernels' layout
+        self._ids, self._rows_cache = (ids, None, None), {}
+        qs0_mean, _ = m.model_down.encoder(_frames_nchw(m, frames, n, o_shape), stage=self.stage0, row_offset=self.ro & 0xFFFFFFFF,
+                                           rows=Rows(ids=ids, rows_per_entry=1, n_total=self.E))
+        self.S[:n, 0] = qs0_mean
+        q_root = m.model_top.encode_s(qs0_mean)[1]
+        self.Qpi[:n, 0] = q_root
+        return q_root
+
+    def plan_keyed(self):
+        """The second half: root expansion and the iterations of the slots efe_agent_mcts_root left active.  Nothing is read back but the
+        lagged stop snapshot; the trees stay on the device for efe_agent_mcts_enqueue."""
+        p = self.p
+        prev = torch.get_num_threads()
+        torch.set_num_threads(1)
+        if self.overlap:
+            self.sim_model = self.model.cached_replica()       # same object unless the weights changed; refreshed noise settings
+        try:
+            self._refresh_active_g()
+            skip = bool(getattr(p, 'skip_stopped', True))
+            st_root, st0 = (self.stage0 + 1) & 0xFFFFFFFF, (self.stage0 + 2) & 0xFFFFFFFF
+            return self._iterate(self.tree_of(self.n), st_root, st0, skip, skip and bool(getattr(p, 'compact_stopped', True)))
+        finally:
+            torch.set_num_threads(prev)
+
+    @staticmethod
+    def stages_per_decision(params):
+        """P = 2 + repeats * (1 + simulation_repeats): the stages a decision reserves (root encoder, root expansion, then per iteration
+        the expansion and each simulation); the decision of tick t starts at stage t * P mod 2^32"""
+        return 2 + int(params.repeats) * (1 + int(params.simulation_repeats))
+
     def run(self, frames, o_shape=(64, 64, 1)):
+        if self.keyed:
+            raise RuntimeError('a keyed planner runs a decision through begin_keyed / plan_keyed (daimc_amd.agent.AgentRunner)')
         # the little host-side work left (habit shortcut, final path read-out) uses tiny tensors: one intra-op thread
         prev = torch.get_num_threads()
         torch.set_num_threads(1)
@@ -451,7 +546,14 @@ class BatchedMCTS:
         self._ids, self._rows_cache = None, {}
         if compact and not bool(active_h.all()):
             self._compact(int(active_h.sum()))
-        self._expand(self.root_nodes, active, self.S[:, 0].repeat_interleave(A, dim=0).contiguous(), stage=st_root, use_mask=skip)
+        return self._finish(res, self._iterate(self._tree, st_root, st0, skip, compact))
+
+    def _iterate(self, tree, st_root, st0, skip, compact):
+        """root expansion and the planning iterations of the first self.n slots (`tree`: the efe_mcts_tree of those slots) -> iterations run"""
+        m, E, p, A, p_ = self.model, self.E, self.p, self.pi_dim, self._p
+        lib = m._engine.lib
+        active, per_it, self._tree_now = self.active, 1 + p.simulation_repeats, tree
+        self._expand(self.root_nodes, active, self.S[:self.n, 0].repeat_interleave(A, dim=0).contiguous(), stage=st_root, use_mask=skip)
         n_iter = 0
         # The per-episode early stop (mcts.py:176) is applied on the device every iteration (stopped episodes are masked out of
         # every tree update); the host only needs to know when ALL episodes have stopped, to end the loop early.  It looks at
@@ -463,10 +565,11 @@ class BatchedMCTS:
         # stop, selection -- per episode in the reference's order (mcts.py:176-191).  The active count of iteration r lands in its own
         # zero-initialised word (no memset launch); the last iteration's back-propagation follows the loop.
         self.n_active_it.zero_()
+        H = (lambda r: r & 1) if self.keyed else (lambda r: r)       # the history row of iteration r (keyed: a ring of two)
         # (one episode too, since round 6: reading the active count in every iteration -- a device synchronisation -- cost 12 % of a
         # one-episode iteration, the lagged snapshot 2 %; the price is up to LAG masked iterations behind the stop.  lagged_single = False:
         # the immediate read)
-        lagged = bool(getattr(p, 'lagged_check', True)) and (E > 1 or bool(getattr(p, 'lagged_single', True)))
+        lagged = self.keyed or (bool(getattr(p, 'lagged_check', True)) and (E > 1 or bool(getattr(p, 'lagged_single', True))))
         LAG = 2
         pending = None                                   # (iteration, sims, q0) whose back-propagation is still to run
         for repeat in range(p.repeats):
@@ -474,13 +577,16 @@ class BatchedMCTS:
                 prev, pexp = (None, None, None, 1, None, None, None), (None, None, None)
             else:
                 pr, sims_t, q0_t, G_t, ps_t = pending
-                prev = (p_(self.H_act[pr]), p_(self.H_len[pr]), p_(sims_t), int(p.simulation_repeats), p_(q0_t), p_(self.H_g[pr]), p_(self.H_active[pr]))
+                prev = (p_(self.H_act[H(pr)]), p_(self.H_len[H(pr)]), p_(sims_t), int(p.simulation_repeats), p_(q0_t), p_(self.H_g[H(pr)]),
+                        p_(self.H_active[H(pr)]))
                 pexp = (p_(self.n_nodes), p_(G_t), p_(ps_t))          # the previous leaf's expansion bookkeeping rides in the same launch
             self._call(lib.efe_mcts_step, prev[0], prev[1], prev[2], prev[3], prev[4], prev[5], prev[6], p_(active), p_(self.stop_at), repeat,
                        float(p.threshold), p_(self.n_active_it[repeat:]), float(p.C), 1 if p.using_prior_for_exploration else 0, self.max_depth,
-                       p_(self.path_nodes), p_(self.H_act[repeat]), p_(self.H_len[repeat]), p_(self.leaf), p_(self.leaf_s), p_(self.leaf_rep),
+                       p_(self.path_nodes), p_(self.H_act[H(repeat)]), p_(self.H_len[H(repeat)]), p_(self.leaf), p_(self.leaf_s), p_(self.leaf_rep),
                        pexp[0], pexp[1], pexp[2])
             pending = None
+            if self._gid is not None:
+                self._refresh_active_g()
             if can_stop and E == 1 and not lagged:        # one episode: stop the loop in the iteration the episode stops in
                 if int(self.n_active_it[repeat].item()) == 0:
                     break
@@ -490,12 +596,12 @@ class BatchedMCTS:
                 # iterations of work stay queued: the GPU never drains, unlike a read of the current count).  From that snapshot it
                 # ends the loop and re-compacts the batch (episodes stopped since then are in the batch but masked).
                 slot = repeat % len(self.ev_snap)
-                self.h_active[slot].copy_(active, non_blocking=True)
+                (self.h_active[slot] if self.n == E else self.h_active[slot, :self.n]).copy_(active if self.n == E else active[:self.n], non_blocking=True)
                 self.ev_snap[slot].record(torch.cuda.current_stream(m.device))
                 if repeat >= LAG:
                     ls = (repeat - LAG) % len(self.ev_snap)
                     self.ev_snap[ls].synchronize()
-                    snap = self.h_active[ls].numpy()
+                    snap = self.h_active[ls, :self.n].numpy()
                     n_live = int(snap.sum())
                     if n_live == 0:
                         break
@@ -525,8 +631,13 @@ class BatchedMCTS:
         if pending is not None:
             pr, sims_t, q0_t, G_t, ps_t = pending
             self._call(lib.efe_mcts_expand, p_(self.n_nodes), p_(self.leaf), p_(active), p_(G_t), p_(ps_t))
-            self._call(lib.efe_mcts_backprop, p_(self.path_nodes), p_(self.H_act[pr]), p_(self.H_len[pr]), p_(self.leaf), p_(active),
-                       p_(sims_t), int(p.simulation_repeats), p_(q0_t), self.max_depth, p_(self.H_g[pr]), p_(self.H_active[pr]))
+            self._call(lib.efe_mcts_backprop, p_(self.path_nodes), p_(self.H_act[H(pr)]), p_(self.H_len[H(pr)]), p_(self.leaf), p_(active),
+                       p_(sims_t), int(p.simulation_repeats), p_(q0_t), self.max_depth, p_(self.H_g[H(pr)]), p_(self.H_active[H(pr)]))
+        return n_iter
+
+    def _finish(self, res, n_iter):
+        """the reference's return tuples of the slot planner, from the history of the n_iter iterations that ran"""
+        E, p = self.E, self.p
         # read the history back once, then plain Python lists on the host: per-element torch indexing here cost ~30 ms per 64-episode
         # decision, per-element numpy indexing 2.6 ms (during which the GPU has nothing queued); whole-array tolist() + list slicing 1.0 ms
         H_act, H_len = self.H_act[:n_iter].cpu().numpy(), self.H_len[:n_iter].cpu().numpy()

@@ -308,6 +308,39 @@ int efe_mcts_backprop(efe_ctx*, const efe_mcts_tree* tree, const int32_t* path_n
 int efe_mcts_stop(efe_ctx*, const efe_mcts_tree* tree, uint8_t* active, int32_t* stop_at, int repeat, float threshold,
                   int32_t* n_active, void* stream);
 
+/* ---- the two ends of an `mcts` decision of the agent loop (csrc/agent_mcts.hip; additive to ABI 6) ---------------------------------------
+ * The n deciding games ids[0 .. n) (efe_agent_need) plan in the first n SLOTS of a planner's tree: every array below that is not part of
+ * efe_agent is indexed by the slot i, the queue by the game ids[i].  One thread per slot, fp32, sums left to right.
+ *   efe_agent_mcts_root   : the beginning of the decision (/root/reference/src/mcts.py:166-170).  Qpi [n][A] is the habit posterior of the root
+ *                           state, A = 3 or 4; thr = max(Qpi) - mean(Qpi).
+ *                             a Qpi row with a NaN, an infinite or a negative entry: choice[i] = -1, the queue stays empty, decided[i] = 1,
+ *                               active[i] = 0 (efe_agent_choose's failure rule, whatever use_habit says);
+ *                             use_habit != 0 and thr > threshold: choice[i] = a draw from Qpi by EFE_AGENT_PROBS's rule (cdf = cumsum / its
+ *                               last entry, the first edge above u; u == 1.0: the last action with p > 0), the queue of game ids[i] becomes
+ *                               that action `jumps` times (head 0), decided[i] = 1, active[i] = 0;
+ *                             otherwise choice[i] = -2, the queue is not touched, decided[i] = 0, active[i] = 1: the planner goes on.
+ *                           u = u[i] when injected, else word 0 of the Philox counter (tag 0x70, global game nz->row_offset + ids[i], stream 0,
+ *                           nz->stage) -- the key of efe_agent_choose's uniform, so nz->stage is the tick; u_out [n] (NULL ok) receives it.
+ *                           `active` is the planner's liveness mask (efe_mcts_step), `decided` is what efe_agent_mcts_enqueue skips.
+ *   efe_agent_mcts_enqueue: the end (Node.action_selection, mcts.py:98-128, and test_demo.py:167-170).  For every slot with decided[i] == 0:
+ *                           from node 0 of tree slot i, the argmax of N (NaN first, then the first index on ties) down to the first node
+ *                           whose child[.][0] < 0; the visited actions trimmed as the reference trims them (a pair of opposite actions --
+ *                           A = 4: 0/1 and 2/3, A = 3: 1/2 -- is dropped, and the last visited action is never emitted unless a pair consumed
+ *                           it); the queue of game ids[i] becomes the trimmed path, each action `jumps` times, from slot 0 with head = 0.  A
+ *                           path that trims to nothing leaves the queue empty: the game decides again on the next tick.  path_out
+ *                           [n][max_depth] and path_len_out [n] (both NULL ok) receive the trimmed path; entries at and beyond the length
+ *                           are not written.  Slots with decided[i] != 0 are not touched, in no array.  Of the tree only N, child, E (>= n),
+ *                           cap and A are read.  The walk is cut after max_depth actions (the planner's is repeats + 2, above any depth its
+ *                           tree can reach), so at most max_depth - 1 actions are queued.
+ * Both return 1 with a message that names the call, and launch nothing, for E < 1, n outside [0, E], A other than 3 and 4, jumps < 1,
+ * max_depth < 1, a queue capacity below max_depth * jumps (the longest queue the decision could write: refused where the decision begins,
+ * not after the planning), or a NULL required pointer (root: neither nz nor u). */
+int efe_agent_mcts_root(efe_ctx*, const efe_agent* agent, const int32_t* ids, int n, const float* Qpi /*[n][A]*/, int A, int use_habit,
+                        float threshold, int max_depth, int jumps, const efe_noise* nz, const float* u, uint8_t* active, uint8_t* decided,
+                        int32_t* choice, float* u_out, void* stream);
+int efe_agent_mcts_enqueue(efe_ctx*, const efe_agent* agent, const efe_mcts_tree* tree, const int32_t* ids, int n, const uint8_t* decided,
+                           int max_depth, int jumps, int32_t* path_out, int32_t* path_len_out, void* stream);
+
 
 /* ---- training-side free energy, forward only (additive to ABI 6; /root/reference/src/torchloss.py, train.py:104-123) ----------------
  * efe_free_energy evaluates what one training step of train.py computes before its optimizer steps, for M rows:

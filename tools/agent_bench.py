@@ -1,11 +1,17 @@
 """Throughput of the agent loop (daimc_amd.agent.AgentRunner), recorded in profiles/agent_bench.json -- a measurement, not a gate.
 
-    python tools/agent_bench.py [--ticks 120] [--games 1 64 1024] [--parent PATH_TO_A_BUILT_PARENT_CHECKOUT] [--out profiles/agent_bench.json]
+    python tools/agent_bench.py [--ticks 120] [--games 1 64 1024] [--method habit ai mcts] [--mcts-ticks 20]
+                                [--parent PATH_TO_A_BUILT_PARENT_CHECKOUT] [--out profiles/agent_bench.json]
 
 Per method (habit, ai at steps 7, samples 10) and number of games: game-ticks per second of an unsynchronised run (wall time over
 `--ticks` ticks after a warm-up run of the same length on the same model), and the share of wall time spent in decisions, taken from a
 second run whose decisions are bracketed by device synchronisations (so that run is slower and only its ratio is used).  Freshly
 initialised weights and the synthetic sprite bank: the figures are about the loop, not about an agent's skill.
+--method mcts measures the planner in BOTH of its modes -- the slot planner (the default of AgentRunner) and the id-keyed one
+(keyed_planner = True) -- at the reference's demo settings (`MCTS_Params()` untouched, jumps 5) over `--mcts-ticks` ticks: per number of
+games one warm-up run per mode, then three unsynchronised runs per mode, ALTERNATING between the modes; per mode the median game-ticks/s and
+decisions/s, the spread of the three, and the decision share from one synchronised run.  An existing --out file keeps the rows of the
+(method, games) pairs this call does not measure.
 With --parent, `bench.py --gpus 1 --steps 20 --warmup 5` is run three times each from this checkout and from the parent's, alternating,
 and both sets of result lines are recorded: no existing kernel changes, so the two should sit inside each other's spread."""
 import argparse
@@ -37,19 +43,43 @@ def timed_runner():
     return TimedRunner
 
 
-def one(model, method, E, ticks, timed_decisions):
+def one(model, method, E, ticks, timed_decisions, keyed=False):
     """-> (wall seconds of `ticks` ticks, seconds inside decisions (0 unless timed), run()'s result)"""
     import torch
     import daimc_amd
     games = daimc_amd.Game(E, model=model, seed=1)
     cls = timed_runner() if timed_decisions else daimc_amd.AgentRunner
-    runner = cls(model, games, method, steps=7, jumps=5, samples=10)
+    runner = cls(model, games, method, steps=7, jumps=5, samples=10, keyed_planner=keyed)          # mcts: MCTS_Params() as they come
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     res = runner.run(ticks)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     return wall, getattr(runner, 'spent', 0.0), res
+
+
+def mcts_rows(model, E, ticks, runs=3):
+    """the slot and the keyed planner at E games, `runs` alternating unsynchronised runs each -> one row per mode"""
+    modes = (('slot', False), ('keyed', True))
+    for _, keyed in modes:
+        one(model, 'mcts', E, ticks, False, keyed)                                        # warm-up: planner buffers, replica context, arena
+    walls, results = {m: [] for m, _ in modes}, {}
+    for _ in range(runs):
+        for mode, keyed in modes:
+            wall, _, res = one(model, 'mcts', E, ticks, False, keyed)
+            walls[mode].append(wall)
+            results[mode] = res
+    rows = []
+    for mode, keyed in modes:
+        wall_s, spent, _ = one(model, 'mcts', E, ticks, True, keyed)
+        w, res = sorted(walls[mode]), results[mode]
+        med = w[len(w) // 2]
+        rows.append({'method': 'mcts', 'planner': mode, 'games': E, 'ticks': ticks, 'jumps': 5, 'params': 'MCTS_Params() defaults',
+                     'wall_s': walls[mode], 'wall_median_s': med, 'game_ticks_per_s': E * ticks / med,
+                     'game_ticks_per_s_min_max': [E * ticks / w[-1], E * ticks / w[0]], 'decisions': res['decisions'],
+                     'decisions_per_s': res['decisions'] / med, 'failed_ticks': res['failed_ticks'],
+                     'decision_share_of_wall': spent / wall_s, 'synchronised_wall_s': wall_s})
+    return rows
 
 
 def bench_line(path):
@@ -64,13 +94,19 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--ticks', type=int, default=120)
     ap.add_argument('--games', type=int, nargs='+', default=[1, 64, 1024])
+    ap.add_argument('--method', nargs='+', default=['habit', 'ai', 'mcts'], choices=['habit', 'ai', 'mcts'])
+    ap.add_argument('--mcts-ticks', type=int, default=20)
     ap.add_argument('--parent', default=None)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'agent_bench.json'))
     args = ap.parse_args(argv)
     import daimc_amd
     model = daimc_amd.ActiveInferenceModel(10, 4, 1.0, 1.0, 1.0, device='cuda:0', seed=0)
     rows = []
-    for method in ('habit', 'ai'):
+    for E in args.games if 'mcts' in args.method else ():
+        for row in mcts_rows(model, E, args.mcts_ticks):
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    for method in [m for m in ('habit', 'ai') if m in args.method]:
         for E in args.games:
             one(model, method, E, args.ticks, False)                                      # warm-up: arena growth, planner buffers
             wall, _, res = one(model, method, E, args.ticks, False)
@@ -81,6 +117,12 @@ def main(argv=None):
             print(json.dumps(row), flush=True)
             rows.append(row)
     out = {'what': 'AgentRunner throughput, freshly initialised weights, synthetic sprite bank', 'loop': rows}
+    if os.path.isfile(args.out):                                                          # keep what this call did not measure
+        with open(args.out) as fh:
+            old = json.load(fh)
+        out['loop'] += [r for r in old.get('loop', []) if r.get('method') not in args.method or r.get('games') not in args.games]
+        if 'bench' in old and not args.parent:
+            out['bench'] = old['bench']
     if args.parent:
         out['bench'] = {'this': [], 'parent': []}
         for _ in range(3):

@@ -32,6 +32,8 @@ def parser():
     ap.add_argument('-threshold', '--threshold', type=float, default=0.5, help='MCTS: threshold to decide early')
     ap.add_argument('-depth', '--depth', type=int, default=3, help='MCTS: simulation depth')
     ap.add_argument('-no_habit', '--no_habit', action='store_true', help='MCTS: as test_demo.py, the flag is handed to params.use_habit')
+    ap.add_argument('--keyed-planner', action='store_true',
+                    help='MCTS: one id-keyed planner for all games (a game plays the same trajectory alone and in any batch; no host draw)')
     ap.add_argument('--games', type=int, default=1, help='games run at once (test_demo.py: 1)')
     ap.add_argument('--sprites', default=None, metavar='PATH', help='dSprites images; default: the synthetic sprite bank')
     ap.add_argument('--seed', type=int, default=0)
@@ -61,7 +63,7 @@ def main(argv=None):
     params.use_habit = args.no_habit
     games = daimc_amd.Game(args.games, model=model, imgs=sprites(args.sprites), seed=args.seed)
     runner = daimc_amd.AgentRunner(model, games, args.method, steps=args.steps, jumps=args.jumps, temperature=args.temperature,
-                                   calc_mean=args.mean, mcts_params=params)
+                                   calc_mean=args.mean, mcts_params=params, keyed_planner=args.keyed_planner)
     start = time.time()
     res, printed, done = None, 0, 0
     while done < args.duration:
@@ -76,7 +78,7 @@ def main(argv=None):
             start = time.time()
     if res is None:
         res = runner.run(0)
-    summary = {'method': args.method, 'games': args.games, 'ticks': res['ticks'], 'steps': args.steps, 'jumps': args.jumps,
+    summary = {'method': args.method, 'keyed_planner': runner.keyed_planner, 'games': args.games, 'ticks': res['ticks'], 'steps': args.steps, 'jumps': args.jumps,
                'temperature': args.temperature, 'mean': args.mean, 'samples': runner.samples, 'decisions': res['decisions'],
                'failed_ticks': res['failed_ticks'], 'round_scores': res['round_scores'].tolist(), 'crossings': res['crossings'].tolist(),
                'reward_sum': res['reward_sum'].tolist()}
