@@ -16,7 +16,7 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down',
            'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top',
            'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
-           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step',
+           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step', 'efe_eval_stats',
            'efe_encoder_rows', 'efe_rollout_rows', 'efe_agent_need', 'efe_agent_choose', 'efe_agent_enqueue', 'efe_agent_act',
            'efe_agent_mcts_root', 'efe_agent_mcts_enqueue']
 ABI_VERSION = 6
@@ -65,6 +65,16 @@ class EfeFeOut(C.Structure):
 EFE_STEP_MEANS = 8
 STEP_MEANS_FIELDS = ('kl_pi', 'omega', 'F_mid', 'F_down', 'nlogpo1', 'kl_s', 'kl_naive', 'omega_std')
 STEP_OUT_FIELDS = ('kl_pi', 'omega', 'qs0', 'F_mid', 'ps1_mean', 'ps1_logvar', 'F_down', 'nlogpo1', 'kl_s', 'kl_naive', 'means')
+
+
+# efe_eval_stats (include/efe_engine.h): the row of the epoch report, its input arrays in struct order, then Mr
+EFE_EVAL_STATS, EFE_EVAL_MAX_ROWS = 98, 8192
+EVAL_IN_FIELDS = ('F_top', 'F_mid', 'F_down', 'nlogpo1', 'kl_s', 'kl_naive', 'kl_pi', 'kl_s_anal', 'kl_naive_anal', 'kl_pi_anal', 'qs1', 's0',
+                  'S_real', 'o1_r', 'po1_r')
+
+
+class EfeEvalIn(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in EVAL_IN_FIELDS] + [('Mr', C.c_int32)]
 
 
 class EfeStepIn(C.Structure):
@@ -194,6 +204,7 @@ def load():
     lib.efe_down_get_weights.argtypes = [p, f32p, C.c_int64, p]; lib.efe_down_get_weights.restype = i
     sap = C.POINTER(EfeStepAdam)
     lib.efe_train_step.argtypes = [p, C.POINTER(EfeStepIn), i, fpp, nzp, sap, sap, sap, C.POINTER(EfeStepOut), p]; lib.efe_train_step.restype = i
+    lib.efe_eval_stats.argtypes = [p, C.POINTER(EfeEvalIn), i, f32p, p]; lib.efe_eval_stats.restype = i
     lib.efe_encoder_rows.argtypes = [p, f32p, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_encoder_rows.restype = i
     lib.efe_rollout_rows.argtypes = [p, f32p, f32p, i, i, i, i, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_rollout_rows.restype = i
     agp = C.POINTER(EfeAgent)

@@ -5,7 +5,7 @@
 //   engine_forward.hip  launch helpers, scratch plans, the forward runners (run_mid ... run_core)
 //   engine_efe.hip      network-level and EFE-level entry points
 //   engine_control.hip  environment, agent and MCTS entry points
-//   engine_loss.hip     the training-side free energy
+//   engine_loss.hip     the training-side free energy, the epoch report (efe_eval_stats)
 //   engine_train.hip    gradients, optimiser steps, efe_train_step
 #pragma once
 #include <hip/hip_runtime.h>

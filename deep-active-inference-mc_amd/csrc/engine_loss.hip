@@ -1,5 +1,6 @@
 // Host side of the engine, the training-side free energy (loss.hip): F_top, F_mid and F_down of the reference's compute_loss_* as
-// entry points, and the helpers that the gradient calls of engine_train.hip share with them.
+// entry points, and the helpers that the gradient calls of engine_train.hip share with them; and the epoch report (eval.hip), which
+// reduces their per-row outputs into one row of statistics.
 #include "engine.h"
 
 namespace efe {
@@ -190,6 +191,35 @@ int efe_loss_down(efe_ctx* ctx, const float* o1, const float* ps1_mean, const fl
     const FeArgs d = fe_down_args(ctx, M, o1, enc, ps1_mean, ps1_logvar, S_DIM, params,
                                   params->omega_mode == EFE_OMEGA_ARRAY ? params->omega : nullptr, out);
     if (fe_down(ctx, dec_in, M, nc, d, out->po1, st)) return 1;
+    return call.finish();
+}
+
+// ---- the epoch report (eval.hip) ----------------------------------------------------------------------
+// Reads the caller's arrays and writes the caller's row: no scratch, no weights, so the scope is Mode::device.  Every refusal comes before
+// the launch.
+int efe_eval_stats(efe_ctx* ctx, const efe_eval_in* in, int M, float* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::device, st); if (!call) return call.refused("efe_eval_stats");
+    if (!in || !out) return ctx->fail("efe_eval_stats: in and out must be non-NULL");
+    if (M < 1) return ctx->fail("efe_eval_stats: M must be >= 1");
+    if (M > EFE_EVAL_MAX_ROWS) return ctx->fail("efe_eval_stats: M = " + std::to_string(M) + " is above the cap of " + std::to_string((int)EFE_EVAL_MAX_ROWS) + " rows");
+    const float* fe[10] = {in->F_top, in->F_mid, in->F_down, in->nlogpo1, in->kl_s, in->kl_naive, in->kl_pi, in->kl_s_anal, in->kl_naive_anal, in->kl_pi_anal};
+    int n_fe = 0;
+    for (const float* p : fe) n_fe += p ? 1 : 0;
+    if (n_fe != 0 && n_fe != 10)
+        return ctx->fail("efe_eval_stats: partial FE group (" + std::to_string(n_fe) + " of its 10 arrays given: F_top, F_mid, F_down, nlogpo1, kl_s, kl_naive, kl_pi, kl_s_anal, kl_naive_anal, kl_pi_anal)");
+    if (!in->s0 != !in->S_real) return ctx->fail("efe_eval_stats: partial RHO group (s0 and S_real go together)");
+    const bool r_any = in->o1_r || in->po1_r;
+    if (r_any && (!in->o1_r || !in->po1_r || in->Mr < 1)) return ctx->fail("efe_eval_stats: partial R group (o1_r, po1_r and Mr >= 1 go together)");
+    if (r_any && in->Mr > EFE_EVAL_MAX_ROWS) return ctx->fail("efe_eval_stats: Mr = " + std::to_string(in->Mr) + " is above the cap of " + std::to_string((int)EFE_EVAL_MAX_ROWS) + " rows");
+    if (!n_fe && !in->qs1 && !in->s0 && !r_any) return ctx->fail("efe_eval_stats: no input group (FE, TC, RHO or R) given");
+    if (n_fe && ctx->pi_dim != 4) return ctx->fail("efe_eval_stats: the row layout holds kl_div_pi_anal [4], this context has pi_dim " + std::to_string(ctx->pi_dim));
+    if (r_any && (ctx->chan != 1 || ctx->res != 64)) return ctx->fail("efe_eval_stats: mse_r reads 1 x 64 x 64 images");
+    EvalArgs a{};
+    for (int k = 0; k < 7; ++k) a.row[k] = fe[k];
+    a.kl_s_anal = in->kl_s_anal; a.kl_naive_anal = in->kl_naive_anal; a.kl_pi_anal = in->kl_pi_anal;
+    a.qs1 = in->qs1; a.s0 = in->s0; a.S_real = in->S_real; a.o1_r = in->o1_r; a.po1_r = in->po1_r;
+    a.M = M; a.Mr = r_any ? in->Mr : 0; a.A = ctx->pi_dim; a.out = out;
+    launch_eval_stats(a, st);
     return call.finish();
 }
 

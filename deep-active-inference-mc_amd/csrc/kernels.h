@@ -442,6 +442,21 @@ constexpr int STEP_MEANS = 8;          // = EFE_STEP_MEANS (include/efe_engine.h
 struct StepMeansArgs { const float* x[STEP_MEANS - 1]; float* means; int M; };
 void launch_step_omega(const FeArgs& a, hipStream_t st);
 void launch_step_means(const StepMeansArgs& a, hipStream_t st);
+// the epoch report (eval.hip): one row of EVAL_STATS floats from the per-row arrays of an evaluation batch; a group whose first pointer
+// is null is absent and its fields are written as NaN (layout and groups: include/efe_engine.h efe_eval_stats)
+constexpr int EVAL_STATS = 98;         // = EFE_EVAL_STATS
+constexpr int EVAL_MAX_ROWS = 8192;    // = EFE_EVAL_MAX_ROWS: one column of floats in LDS (32 KiB), 4 M^4 < 2^63
+constexpr int EVAL_FACTORS = 6;        // columns of S_real
+struct EvalArgs {
+    const float* row[7];               // FE: F_top, F_mid, F_down, nlogpo1, kl_s, kl_naive, kl_pi [M]
+    const float* kl_s_anal; const float* kl_naive_anal; const float* kl_pi_anal;      // [M][10], [M][10], [M][A]
+    const float* qs1;                  // TC: [M][10]
+    const float* s0; const float* S_real;      // RHO: [M][10], [M][EVAL_FACTORS]
+    const float* o1_r; const float* po1_r;     // R: [Mr][4096] NCHW, C = 1
+    int M, Mr, A;
+    float* out;                        // [EVAL_STATS]
+};
+void launch_eval_stats(const EvalArgs& a, hipStream_t st);
 
 // ---- training of the small MLPs (train.hip): backward + Adam over a layer table -----------------------------------
 // A trainable part is a chain of Linear layers described by a DEVICE-RESIDENT table (built at efe_commit_weights): widths, the ReLU flag

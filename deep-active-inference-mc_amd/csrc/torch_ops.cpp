@@ -655,6 +655,35 @@ std::vector<Tensor> train_step(int64_t h, const Tensor& o0_, const Tensor& o1_, 
     return r;
 }
 
+// the epoch report, train.py:136-187 (efe_eval_stats): batch statistics of an evaluation batch into out [EFE_EVAL_STATS], written in place.
+// A group is given whole or not at all; the engine refuses anything else (and M outside [1, EFE_EVAL_MAX_ROWS]) before it launches, so
+// the sizes are checked here only where the engine would go on to read them.
+void eval_stats(int64_t h, const OptT& F_top, const OptT& F_mid, const OptT& F_down, const OptT& nlogpo1, const OptT& kl_s, const OptT& kl_naive,
+                const OptT& kl_pi, const OptT& kl_s_anal, const OptT& kl_naive_anal, const OptT& kl_pi_anal, const OptT& qs1, const OptT& s0,
+                const OptT& S_real, const OptT& o1_r, const OptT& po1_r, int64_t M, int64_t Mr, Tensor out) {
+    efe_ctx* c = CTX(h);
+    TORCH_CHECK(M >= INT32_MIN && M <= INT32_MAX && Mr >= INT32_MIN && Mr <= INT32_MAX, "efe engine: efe_eval_stats: M / Mr out of range");
+    const Geo g = geo(c);
+    const bool sized = M >= 1 && M <= EFE_EVAL_MAX_ROWS, rsized = Mr >= 1 && Mr <= EFE_EVAL_MAX_ROWS;
+    Tensor keep[15];
+    auto arg = [&](const OptT& t, int slot, const char* name, int64_t rows_, int64_t width, bool check) -> const float* {
+        if (!t.has_value() || !t->defined()) return nullptr;
+        keep[slot] = in(*t, name);
+        TORCH_CHECK(!check || keep[slot].numel() == rows_ * width, "efe engine: efe_eval_stats: ", name, " has ", keep[slot].numel(), " elements, expected ",
+                    rows_, " x ", width);
+        return keep[slot].data_ptr<float>();
+    };
+    efe_eval_in ei{};
+    ei.F_top = arg(F_top, 0, "F_top", M, 1, sized); ei.F_mid = arg(F_mid, 1, "F_mid", M, 1, sized); ei.F_down = arg(F_down, 2, "F_down", M, 1, sized);
+    ei.nlogpo1 = arg(nlogpo1, 3, "nlogpo1", M, 1, sized); ei.kl_s = arg(kl_s, 4, "kl_s", M, 1, sized); ei.kl_naive = arg(kl_naive, 5, "kl_naive", M, 1, sized);
+    ei.kl_pi = arg(kl_pi, 6, "kl_pi", M, 1, sized); ei.kl_s_anal = arg(kl_s_anal, 7, "kl_s_anal", M, g.s, sized);
+    ei.kl_naive_anal = arg(kl_naive_anal, 8, "kl_naive_anal", M, g.s, sized); ei.kl_pi_anal = arg(kl_pi_anal, 9, "kl_pi_anal", M, g.A, sized);
+    ei.qs1 = arg(qs1, 10, "qs1", M, g.s, sized); ei.s0 = arg(s0, 11, "s0", M, g.s, sized); ei.S_real = arg(S_real, 12, "S_real", M, 6, sized);
+    ei.o1_r = arg(o1_r, 13, "o1_r", Mr, 4096, rsized); ei.po1_r = arg(po1_r, 14, "po1_r", Mr, 4096, rsized);
+    ei.Mr = (int)Mr;
+    ok(c, efe_eval_stats(c, &ei, (int)M, state(out, "out", EFE_EVAL_STATS), stream_of(out)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -686,6 +715,7 @@ TORCH_LIBRARY(efe, m) {
     m.def("down_grad(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> Tensor[]");
     m.def("train_down(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float adam_eps, int step) -> Tensor[]");
     m.def("train_step(int ctx, Tensor o0, Tensor o1, Tensor pi0, Tensor log_Ppi, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, float a, float b, float c, float d, int seed, int stage, int row_offset, Tensor? eps, Tensor(a!) top_exp_avg, Tensor(b!) top_exp_avg_sq, Tensor(c!) mid_exp_avg, Tensor(d!) mid_exp_avg_sq, Tensor(e!) down_exp_avg, Tensor(f!) down_exp_avg_sq, float[] hyper, int[] steps, Tensor(g!) means) -> Tensor[]");
+    m.def("eval_stats(int ctx, Tensor? F_top, Tensor? F_mid, Tensor? F_down, Tensor? nlogpo1, Tensor? kl_s, Tensor? kl_naive, Tensor? kl_pi, Tensor? kl_s_anal, Tensor? kl_naive_anal, Tensor? kl_pi_anal, Tensor? qs1, Tensor? s0, Tensor? S_real, Tensor? o1_r, Tensor? po1_r, int M, int Mr, Tensor(a!) out) -> ()");
     m.def("down_adam_step(int ctx, Tensor grad, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> ()");
 }
 
@@ -718,5 +748,6 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("down_grad", &down_grad);
     m.impl("train_down", &train_down);
     m.impl("train_step", &train_step);
+    m.impl("eval_stats", &eval_stats);
     m.impl("down_adam_step", &down_adam_step);
 }

@@ -16,7 +16,9 @@ masks (csrc/train_dec_head.hip), then the four ConvTranspose2d layers (po_net.13
 `grad_decoder_convs` also runs from a given Unflatten input.  `train_step` is the loop body of train.py:111-126 as ONE engine call
 (efe_train_step): the o0 encoder + sample, the habit net's step, compute_omega of its kl_pi on the device, the o1 encoder, the transition
 net's step and ModelDown's step, bit-identical to those public calls issued one after another, plus the batch means a loop logs
-(`TrainStep.means`) without a synchronisation; daimc_amd.train.Trainer drives it.  Every
+(`TrainStep.means`) without a synchronisation; daimc_amd.train.Trainer drives it.  `eval_stats` reduces what an epoch's evaluation logs
+(train.py:136-187: means, order statistics, TC, the reward-transition error of `compare_reward`, Spearman correlations of the latents
+with the true factors) into one device row (efe_eval_stats, csrc/eval.hip).  Every
 call dispatches through torch.ops.efe.* on the model's device; there is no CPU fallback.
 
 Noise: each loss draws its masks / normals under its own pass id (model.PASS_FE_*: FE_Q0 for the o0 encoder + sample, FE_Q1 for the o1
@@ -392,3 +394,59 @@ def train_step(model, o0, o1, pi0, log_Ppi, optimizers, *, omega=None, omega_par
         o._step += 1
         o._module._stepped()
     return TrainStep(*outs, means)
+
+
+# ---- the epoch report (efe_eval_stats, csrc/eval.hip): the statistics train.py:136-187 appends to `stats`, one device row ---------------
+EVAL_FE_ARRAYS = ('F_top', 'F_mid', 'F_down', 'nlogpo1', 'kl_s', 'kl_naive', 'kl_pi', 'kl_s_anal', 'kl_naive_anal', 'kl_pi_anal')
+# name -> slice of the [98] row (include/efe_engine.h efe_eval_stats); spearman is [10][6] row-major
+EVAL_STATS_FIELDS = {
+    'F': slice(0, 1), 'F_top': slice(1, 2), 'F_mid': slice(2, 3), 'F_down': slice(3, 4), 'mse_o': slice(4, 5), 'kl_div_s': slice(5, 6),
+    'kl_div_s_naive': slice(6, 7), 'kl_div_pi': slice(7, 8), 'kl_div_pi_min': slice(8, 9), 'kl_div_pi_max': slice(9, 10),
+    'kl_div_pi_med': slice(10, 11), 'kl_div_pi_std': slice(11, 12), 'TC': slice(12, 13), 'mse_r': slice(13, 14),
+    'kl_div_s_anal': slice(14, 24), 'kl_div_s_naive_anal': slice(24, 34), 'kl_div_pi_anal': slice(34, 38), 'spearman': slice(38, 98),
+}
+EVAL_FACTORS = ('shape', 'scale', 'orientation', 'posX', 'posY', 'reward')      # the columns of S_real, and of spearman's rows
+_stats_engines = {}
+
+
+def _stats_engine(device):
+    """an engine context of `device` for calls that read no weights (one per device, made on first use)"""
+    from .model import _Engine
+    idx = torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    if idx not in _stats_engines:
+        _stats_engines[idx] = _Engine(idx)
+    return _stats_engines[idx]
+
+
+def eval_stats(fe=None, S_real=None, reward=None, out=None, *, engine=None):
+    """The batch statistics of an evaluation batch, reduced on the device in one engine call (efe_eval_stats) with no synchronisation ->
+    the [98] float32 device row EVAL_STATS_FIELDS names.  Inputs come in four groups, each whole or absent; an absent group's fields
+    are NaN:
+      fe      : a FreeEnergy (or any object / mapping with some of its fields): its ten loss arrays (EVAL_FE_ARRAYS) give the means, the
+                order statistics of kl_pi and the column means; its qs1 gives TC; its s0 goes with S_real
+      S_real  : [M, 6] true factors of the rows of fe.s0 (util.make_batch_dsprites_random) -> spearman
+      reward  : (o1, po1), [Mr, 1, 64, 64] each -> mse_r (compare_reward)
+    out: an optional contiguous float32 [98] device tensor (or view) written in place.  engine: the engine context to run on (a model's
+    `_ready()`); by default one per device that holds no weights.  At most 8192 rows per group."""
+    get = (lambda k: fe.get(k)) if hasattr(fe, 'get') else (lambda k: getattr(fe, k, None))
+    vals = [get(k) for k in EVAL_FE_ARRAYS] + [get('qs1'), get('s0') if S_real is not None else None, S_real]      # (s0 is read with S_real only)
+    vals += list(reward) if reward is not None else [None, None]
+    if all(v is None for v in vals):
+        raise RuntimeError('efe_eval_stats: no input group (FE, TC, RHO or R) given')
+    e = engine
+    if e is None:           # the device of the first device tensor among the arguments, else the current one
+        e = _stats_engine(next((t.device for t in [out] + vals if isinstance(t, torch.Tensor) and t.is_cuda), 'cuda'))
+    arrs = [None if v is None else e.tensor(v) for v in vals]
+    Mr = next((t.shape[0] if t.dim() else 1 for t in arrs[13:] if t is not None), 0)
+    M = next((t.shape[0] if t.dim() else 1 for t in arrs[:13] if t is not None), Mr)      # (the R group alone: M is not read, and must be >= 1)
+    if out is None:
+        out = e.empty(_lib.EFE_EVAL_STATS)
+    e.ops.eval_stats(e.h, *arrs, M, Mr, out)
+    return out
+
+
+def compare_reward(o1, po1, *, engine=None):
+    """src/util.py:82-85 on the device: the mean squared error of the prediction po1 against o1 over the reward bar (image rows 0..2),
+    both [M, 1, 64, 64] (NCHW; the reference slices its NHWC arrays as [:, 0:3, 0:64, :]) -> a 0-d device tensor"""
+    return eval_stats(reward=(o1, po1), engine=engine)[EVAL_STATS_FIELDS['mse_r']].reshape(())

@@ -1,7 +1,8 @@
 """The training loop of the reference (its train.py) on the device: `Trainer` drives `loss.train_step` (one engine call per round:
 train.py:111-126) with the batched environment (env.Game) and the planner side of the batch builder
 (util.make_batch_dsprites_active_inference), applies the gamma schedule (train.py:101-102) and runs the evaluation block
-(train.py:136-173) through `loss.free_energy`.  tools/train_loop.py is the command line over it.
+(train.py:136-173) through `loss.free_energy`; `Trainer.report` is that block and the reward-transition test (train.py:181-186) reduced
+on the device (loss.eval_stats) and downloaded once.  tools/train_loop.py is the command line over it.
 
 What a round reads back: nothing of the model's.  `train_step` queues its kernels and writes that round's eight batch statistics
 (loss.STEP_MEANS_FIELDS) into one row of a [rounds, 8] device tensor; `epoch()` downloads that tensor once, after the last round.  (The
@@ -13,7 +14,9 @@ Deviations from the reference, each documented where it applies:
     keeps gamma, beta_s and beta_o there as Python floats, so that no step has to fetch a 0-d device tensor.  The schedule itself is the
     reference's fp32 arithmetic (a float32 tensor += a Python float), see `next_gamma`.
   * the dSprites archive does not ship: the games run on whatever sprite bank they were built with (env.synthetic_sprite_bank by default).
-  * no plots (generate_traversals, reconstructions_plot, stats_plot) and no reward-transition test (train.py:177-187)."""
+  * no plots (generate_traversals, reconstructions_plot, stats_plot).  `Trainer.report` produces every number of the epoch report on the
+    device (loss.eval_stats), the reward-transition test (train.py:181-186) and the Spearman correlations of generate_traversals.py:36-46
+    included; their p-values and the mutual_info_regression scores of that script (a randomised estimator) are not computed."""
 import numpy as np
 import torch
 
@@ -28,6 +31,7 @@ EPOCH_KEYS = loss.STEP_MEANS_FIELDS[:7] + ('omega_last', 'omega_std_last')
 EVAL_KEYS = ('F', 'F_top', 'F_mid', 'F_down', 'mse_o', 'kl_div_s', 'kl_div_s_anal', 'kl_div_s_naive', 'kl_div_s_naive_anal', 'omega', 'omega_std',
              'kl_div_pi', 'kl_div_pi_min', 'kl_div_pi_max', 'kl_div_pi_med', 'kl_div_pi_std', 'kl_div_pi_anal', 'var_beta_s', 'var_gamma',
              'var_beta_o', 'var_a', 'var_b', 'var_c', 'var_d', 'TC')
+REPORT_KEYS = EVAL_KEYS + ('mse_r', 'spearman')         # what Trainer.report adds: the reward-transition test and the latent-to-factor correlations
 
 
 def next_gamma(gamma, epoch, gamma_rate=0.01, gamma_max=0.8, gamma_delay=30):
@@ -140,3 +144,37 @@ class Trainer:
             'var_beta_s': float(m.beta_s), 'var_gamma': float(m.gamma), 'var_beta_o': float(m.beta_o), 'var_a': a, 'var_b': b, 'var_c': c,
             'var_d': d, 'TC': float(total_correlation(fe.qs1.cpu().numpy())),
         }
+
+    def report(self, game_test, *, reward_deepness=1):
+        """The whole per-epoch report, train.py:136-187 without the plots, with ONE download -> {REPORT_KEYS}: EVAL_KEYS as `evaluate` gives
+        them, `mse_r` (the reward-transition test, train.py:181-186) and `spearman` [10, 6] (the correlation of every latent of the o0
+        sample with every true factor, loss.EVAL_FACTORS: generate_traversals.py:36-46 without the p-values).  On `game_test`: the
+        evaluation batch with its true latents, free_energy at omega = var_a / 2 + var_d, the reward-transition batch pushed through
+        imagine_future_from_o, and loss.eval_stats over all of it; the last training round's omega mean / std join the row on the device.
+        (The environment's own validity checks still look at one flag per call.)"""
+        m = self.model
+        a, b, c, d = self.omega_params
+        e = m._ready()
+        o0, o1, pi0, S0_real, _ = util.make_batch_dsprites_random(game_test, self.repeats, self.generator)
+        pi0 = e.tensor(pi0, (-1, m.pi_dim))
+        fe = loss.free_energy(m, o0, o1, pi0, torch.log(pi0 + 1e-15), omega=a / 2.0 + d, omega_params=self.omega_params)
+        r0, r1, rpi = util.make_batch_dsprites_random_reward_transitions(game_test, deepness=reward_deepness, repeats=self.repeats)
+        po1 = m.imagine_future_from_o(r0, rpi)
+        n = loss._lib.EFE_EVAL_STATS
+        row = torch.full((n + 2,), float('nan'), dtype=torch.float32, device=m.device)
+        loss.eval_stats(fe, S0_real, (r1, po1), out=row[:n], engine=e)
+        if self.rounds_done:
+            row[n:] = self.means[self.rounds_done - 1][1::6]      # omega, omega_std (STEP_MEANS_FIELDS 1 and 7)
+        h = row.cpu().numpy()
+        f = {k: h[s] for k, s in loss.EVAL_STATS_FIELDS.items()}
+        var = {'var_beta_s': float(m.beta_s), 'var_gamma': float(m.gamma), 'var_beta_o': float(m.beta_o), 'var_a': a, 'var_b': b, 'var_c': c,
+               'var_d': d, 'omega': float(h[n]), 'omega_std': float(h[n + 1])}
+        out = {}
+        for k in REPORT_KEYS:
+            if k in var:
+                out[k] = var[k]
+            elif k == 'spearman':
+                out[k] = f[k].reshape(m.s_dim, len(loss.EVAL_FACTORS)).copy()
+            else:
+                out[k] = f[k].copy() if f[k].size > 1 else float(f[k][0])
+        return out

@@ -44,3 +44,45 @@ def make_batch_dsprites_active_inference(games, model, deepness=10, samples=5, c
     games.pi_to_action_all(pi0.argmax(dim=1), repeats=repeats)
     o1 = games.current_frame_all()
     return o0, o1, pi0, log_Ppi
+
+
+def _s_real(games):
+    """src/util.py:15-16 for every game: current_s[:, 1:] with last_r in its last column -> [games, 6] (shape, scale, orientation, posX, posY,
+    last_r), a fresh device tensor"""
+    S = games.current_s[:, 1:7].clone()
+    S[:, 5] = games.last_r
+    return S
+
+
+def make_batch_dsprites_random(games, repeats, generator=None):
+    """The reference's make_batch_dsprites_random (src/util.py:6-25) with the batched device environment, one transition per game: randomise, observe, act on an action
+    drawn from a random categorical, observe again -> (o0, o1 [games,1,64,64], pi0 one-hot [games,4], S0_real, S1_real [games,6]) as device
+    tensors.  S0_real is the true state before the action, S1_real the one after it.  The draws are exactly train.make_batch_random's: a
+    twin Game and a twin generator give the same o0, o1 and pi0."""
+    import torch
+    games.randomize_environment_all()
+    o0 = games.current_frame_nchw()
+    S0_real = _s_real(games)
+    Ppi = torch.rand(games.games_no, 4, device=games.device, generator=generator)
+    choice = torch.multinomial(Ppi / Ppi.sum(1, keepdim=True), 1, generator=generator).squeeze(1)
+    games.pi_to_action_all(choice, repeats=repeats)
+    pi0 = torch.zeros(games.games_no, 4, device=games.device)
+    pi0[torch.arange(games.games_no, device=games.device), choice] = 1.0
+    return o0, games.current_frame_nchw(), pi0, S0_real, _s_real(games)
+
+
+def make_batch_dsprites_random_reward_transitions(games, deepness=1, repeats=1):
+    """The reference's make_batch_dsprites_random_reward_transitions (src/util.py:27-44) with the batched device environment: every game is randomised and put right below the top edge
+    (posY = 31), observed, moved `up` `deepness` times (`repeats` steps each: the first one crosses and ends the round) and observed
+    again -> (o0, o1 [games,1,64,64], pi_one_hot [games,4] with column 0 set) as device tensors: the batch that shows whether the
+    transition network has learnt what crossing does to the reward bar (loss.compare_reward)."""
+    import torch
+    games.randomize_environment_all()
+    games.current_s[:, 5] = 31.0
+    o0 = games.current_frame_nchw()
+    up = torch.zeros(games.games_no, dtype=torch.int32, device=games.device)
+    for _ in range(int(deepness)):
+        games.pi_to_action_all(up, repeats=repeats)
+    pi_one_hot = torch.zeros(games.games_no, 4, device=games.device)
+    pi_one_hot[:, 0] = 1.0
+    return o0, games.current_frame_nchw(), pi_one_hot

@@ -576,6 +576,42 @@ typedef struct efe_step_out {
 int efe_train_step(efe_ctx*, const efe_step_in* in, int M, const efe_fe_params* params, const efe_noise* nz, const efe_step_adam* top,
                    const efe_step_adam* mid, const efe_step_adam* down, const efe_step_out* out, void* stream);
 
+/* ---- the epoch report: batch statistics of an evaluation batch (csrc/eval.hip; additive to ABI 6) -----------------------------------------
+ * What the reference's train.py:136-187 appends to `stats` once an epoch, reduced on the device into ONE row of EFE_EVAL_STATS floats, in
+ * one call scope with no host synchronisation and no scratch.  Row layout (s_dim 10, pi_dim 4, 6 true factors):
+ *    0      F                  mean over rows of (F_down[r] + F_mid[r]) + F_top[r], the fp32 per-row sum in that order (train.py:149)
+ *    1-6    F_top, F_mid, F_down, mse_o (= mean nlogpo1), kl_div_s, kl_div_s_naive                                batch means
+ *    7-11   kl_div_pi mean, min, max, med, std: min / max / med return an input element, med is torch.median's lower median (the element
+ *           of sorted rank (M - 1) / 2), std is unbiased, two passes as efe_train_step's omega_std, NaN at M = 1
+ *    12     TC                 total correlation of a Gaussian fitted to qs1 (torchutils.py:40-42): (sum_k log cov_kk - log det cov) / 2, the
+ *                              covariance with divisor M - 1, both terms from one Cholesky factor, all in fp64, rounded once to fp32.  A
+ *                              non-positive pivot (a constant latent) or M <= 10 gives NaN, where numpy's slogdet route gives inf or a huge number
+ *    13     mse_r              compare_reward (src/util.py:82-85): mean of (o1 - po1)^2 over image rows 0..2 of NCHW [Mr,1,64,64]
+ *    14-23, 24-33, 34-37       kl_div_s_anal [10], kl_div_s_naive_anal [10], kl_div_pi_anal [4]                       column means
+ *    38-97  spearman [10][6]   signed Spearman rho of s0[:, i] against S_real[:, j] (columns: shape, scale, orientation, posX, posY, reward),
+ *                              ties at their average rank, from doubled integer ranks summed in int64 and ONE fp64 quotient: exactly what
+ *                              the rank formula gives.  A constant column gives 0 / 0 = NaN, as scipy does
+ * Inputs come in four groups, each all-or-nothing; an absent group leaves its fields NaN:
+ *    FE  : F_top, F_mid, F_down, nlogpo1, kl_s, kl_naive, kl_pi [M]; kl_s_anal, kl_naive_anal [M,10]; kl_pi_anal [M,4]   -> 0-11, 14-37
+ *    TC  : qs1 [M,10]                                                                                                    -> 12
+ *    RHO : s0 [M,10], S_real [M,6]                                                                                       -> 38-97
+ *    R   : o1_r, po1_r [Mr,1,64,64], Mr >= 1                                                                             -> 13
+ * Every mean, the std and mse_r follow k_step_means' order contract (a function of the element count alone): thread t of a 256-thread
+ * workgroup adds elements t, t + 256, ... in ascending order, xor butterfly over the wave (offsets 32 ... 1), ((w0 + w1) + w2) + w3, one
+ * correctly rounded division.  Non-finite values: every field is NaN exactly where numpy / torch on the same arrays give NaN (min, max
+ * and med propagate a NaN explicitly, a NaN in either column makes that rho NaN); a field that does not read a poisoned array keeps its bits.
+ * Returns 1 with a message that names efe_eval_stats, before the first launch and writing nothing, for: in or out NULL, no group at all, a
+ * partial group, M < 1, M > EFE_EVAL_MAX_ROWS, Mr > EFE_EVAL_MAX_ROWS (the cap: one column of M floats in LDS, 4 M^4 < 2^63). */
+enum { EFE_EVAL_STATS = 98, EFE_EVAL_MAX_ROWS = 8192 };
+typedef struct efe_eval_in {
+    const float* F_top; const float* F_mid; const float* F_down; const float* nlogpo1; const float* kl_s; const float* kl_naive; const float* kl_pi;
+    const float* kl_s_anal; const float* kl_naive_anal; const float* kl_pi_anal;      /* FE */
+    const float* qs1;                                                                 /* TC */
+    const float* s0; const float* S_real;                                             /* RHO */
+    const float* o1_r; const float* po1_r; int Mr;                                    /* R */
+} efe_eval_in;
+int efe_eval_stats(efe_ctx*, const efe_eval_in* in, int M, float* out /*[EFE_EVAL_STATS]*/, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 
