@@ -12,7 +12,7 @@ from .util import (softmax_multi_with_log, plan_actions_batch, make_batch_dsprit
 from .env import Game, synthetic_sprite_bank  # noqa: F401
 from .parallel import episode_shard, gather_action_posteriors  # noqa: F401
 from . import loss  # noqa: F401
-from .loss import free_energy, FreeEnergy, train_step, TrainStep, eval_stats, compare_reward  # noqa: F401
+from .loss import free_energy, FreeEnergy, train_step, TrainStep, eval_stats, compare_reward, eval_mutual_info  # noqa: F401
 from .optim import Adam  # noqa: F401
 from . import train  # noqa: F401
 from .train import Trainer  # noqa: F401

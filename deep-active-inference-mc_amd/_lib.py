@@ -18,7 +18,7 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
            'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step', 'efe_eval_stats',
            'efe_encoder_rows', 'efe_rollout_rows', 'efe_agent_need', 'efe_agent_choose', 'efe_agent_enqueue', 'efe_agent_act',
-           'efe_agent_mcts_root', 'efe_agent_mcts_enqueue']
+           'efe_agent_mcts_root', 'efe_agent_mcts_enqueue', 'efe_eval_mi']
 ABI_VERSION = 6
 
 
@@ -75,6 +75,16 @@ EVAL_IN_FIELDS = ('F_top', 'F_mid', 'F_down', 'nlogpo1', 'kl_s', 'kl_naive', 'kl
 
 class EfeEvalIn(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in EVAL_IN_FIELDS] + [('Mr', C.c_int32)]
+
+
+# efe_eval_mi (include/efe_engine.h): the [60] table of mutual-information scores, latent-major
+EFE_EVAL_MI, EFE_EVAL_MI_MAX_NEIGHBORS = 60, 4
+EVAL_MI_IN_FIELDS = ('s0', 'S_real', 'noise', 'n_neighbors', 'seed', 'stage')
+
+
+class EfeEvalMiIn(C.Structure):
+    _fields_ = [('s0', C.c_void_p), ('S_real', C.c_void_p), ('noise', C.c_void_p), ('n_neighbors', C.c_int32), ('seed', C.c_uint64),
+                ('stage', C.c_uint32)]
 
 
 class EfeStepIn(C.Structure):
@@ -205,6 +215,7 @@ def load():
     sap = C.POINTER(EfeStepAdam)
     lib.efe_train_step.argtypes = [p, C.POINTER(EfeStepIn), i, fpp, nzp, sap, sap, sap, C.POINTER(EfeStepOut), p]; lib.efe_train_step.restype = i
     lib.efe_eval_stats.argtypes = [p, C.POINTER(EfeEvalIn), i, f32p, p]; lib.efe_eval_stats.restype = i
+    lib.efe_eval_mi.argtypes = [p, C.POINTER(EfeEvalMiIn), i, f32p, p, p]; lib.efe_eval_mi.restype = i
     lib.efe_encoder_rows.argtypes = [p, f32p, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_encoder_rows.restype = i
     lib.efe_rollout_rows.argtypes = [p, f32p, f32p, i, i, i, i, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_rollout_rows.restype = i
     agp = C.POINTER(EfeAgent)

@@ -143,6 +143,7 @@ struct efe_ctx {
     bool arch_gfx950 = false;      // hipDeviceProp_t.gcnArchName starts with gfx950 (checked at creation)
     int64_t sim_split = 1;         // simulations of <= 16 episodes: the chain kernel on eight workgroups per 8 episodes (k_sim_chain<8>); 0 = one workgroup (A/B, bit-identical)
     bool sim_sync_dirty = false;   // the last split launch's call did not complete on the host: zero sim_sync before the next one
+    double* mi_ws = nullptr;       // efe_eval_mi's column statistics and per-slice partial sums [EVAL_MI_WS], then its digamma table [EVAL_MI_PSI] (owned)
     float* sim_xch = nullptr; int* sim_sync = nullptr;      // its exchange buffer and arrival counters / sticky timeout flag (owned; zeroed at creation, and on the stream when sim_sync_dirty; otherwise, after an in-kernel timeout too, the kernel's epilogue re-arms them)
     int64_t check_rows = 0;        // development: range-check efe_rows.ids on the host before every _rows call
     int64_t last_macs = 0;
@@ -258,7 +259,8 @@ bool capturing(hipStream_t st);
 // call still in flight on ANOTHER stream finishes first (same stream: stream order guarantees it), and every exit after that -- success or
 // failure, kernels maybe queued -- records done_ev behind `st`'s work, so that the next call, on any stream, can order its arena reuse behind it.
 // false: a refused handle (return code 1, efe_last_error explains) or a failed start (its message in ctx->err).
-enum class Mode { host, device, scratch };
+// ordered: scratch's ordering for a call that reads no weights and works in a buffer the context owns (efe_eval_mi: ctx->mi_ws).
+enum class Mode { host, device, scratch, ordered };
 // what efe_last_error says of a handle that is not live, on this thread: the plain message, or (Call::refused) the one that names the entry
 // point which was just handed it; every new call scope puts the plain one back
 extern thread_local std::string tl_stale_msg;      // (engine_ctx.hip)
@@ -278,7 +280,7 @@ struct Call {
     int start(Mode mode) {
         if (mode == Mode::scratch && !ctx->committed) return ctx->fail("weights not committed");
         if (mode != Mode::host && hipSetDevice(ctx->device) != hipSuccess) return ctx->fail("hipSetDevice failed");
-        if (mode != Mode::scratch) return 0;
+        if (mode == Mode::host || mode == Mode::device) return 0;
         if (ctx->have_last && ctx->last_stream != st && !capturing(st) && hipStreamWaitEvent(st, ctx->done_ev, 0) != hipSuccess)
             return ctx->fail("hipStreamWaitEvent failed");
         ctx->arena.reset();

@@ -111,6 +111,13 @@ int efe_create_cfg(efe_ctx** out, int device, int s_dim, int pi_dim, int channel
         ctx->owned.push_back(ctx->sim_sync);
         if (hipMemset(ctx->sim_sync, 0, sb) != hipSuccess) { release_ctx(ctx); return 4; }
     }
+    {   // efe_eval_mi (eval_mi.hip): its workspace, and behind it the digamma table
+        if (hipMalloc((void**)&ctx->mi_ws, (EVAL_MI_WS + EVAL_MI_PSI) * sizeof(double)) != hipSuccess) { release_ctx(ctx); return 4; }
+        ctx->owned.push_back(ctx->mi_ws);
+        std::vector<double> psi(EVAL_MI_PSI);
+        eval_mi_psi_table(psi.data());
+        if (hipMemcpy(ctx->mi_ws + EVAL_MI_WS, psi.data(), psi.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { release_ctx(ctx); return 4; }
+    }
     registry().insert(ctx);
     *out = ctx;
     return 0;

@@ -223,4 +223,24 @@ int efe_eval_stats(efe_ctx* ctx, const efe_eval_in* in, int M, float* out, void*
     return call.finish();
 }
 
+// The mutual-information table (eval_mi.hip).  It reads the caller's arrays and no weights, and keeps its 32 column statistics and its
+// per-slice partial sums in ctx->mi_ws, so the scope is Mode::ordered: a call on another stream waits for the previous one.  Every refusal
+// comes before the launch.
+int efe_eval_mi(efe_ctx* ctx, const efe_eval_mi_in* in, int M, float* out, int32_t* counts, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::ordered, st); if (!call) return call.refused("efe_eval_mi");
+    if (!in || !out) return ctx->fail("efe_eval_mi: in and out must be non-NULL");
+    if (!in->s0 || !in->S_real) return ctx->fail("efe_eval_mi: in->s0 and in->S_real must be non-NULL");
+    if (in->n_neighbors < 1 || in->n_neighbors > EFE_EVAL_MI_MAX_NEIGHBORS)
+        return ctx->fail("efe_eval_mi: n_neighbors = " + std::to_string(in->n_neighbors) + " is outside 1 .. " + std::to_string((int)EFE_EVAL_MI_MAX_NEIGHBORS));
+    if (M < in->n_neighbors + 1)
+        return ctx->fail("efe_eval_mi: M = " + std::to_string(M) + " rows hold no " + std::to_string(in->n_neighbors) + " neighbours of a point (M must be >= n_neighbors + 1)");
+    if (M > EFE_EVAL_MAX_ROWS) return ctx->fail("efe_eval_mi: M = " + std::to_string(M) + " is above the cap of " + std::to_string((int)EFE_EVAL_MAX_ROWS) + " rows");
+    EvalMiArgs a{};
+    a.s0 = in->s0; a.S_real = in->S_real; a.noise = in->noise; a.M = M; a.k = in->n_neighbors;
+    a.k0 = (uint32_t)in->seed; a.k1 = (uint32_t)(in->seed >> 32); a.stage = in->stage;
+    a.ws = ctx->mi_ws; a.psi = ctx->mi_ws + EVAL_MI_WS; a.out = out; a.counts = counts;
+    launch_eval_mi(a, st);
+    return call.finish();
+}
+
 }  // extern "C"

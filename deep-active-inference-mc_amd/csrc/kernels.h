@@ -457,6 +457,25 @@ struct EvalArgs {
     float* out;                        // [EVAL_STATS]
 };
 void launch_eval_stats(const EvalArgs& a, hipStream_t st);
+// the mutual information of every latent with every true factor (eval.hip, efe_eval_mi): the KSG k-nearest-neighbour estimator in fp64
+constexpr int EVAL_MI = 60;            // = EFE_EVAL_MI: pairs, latent-major
+constexpr int EVAL_MI_MAX_K = 4;       // = EFE_EVAL_MI_MAX_NEIGHBORS
+constexpr int EVAL_MI_POINTS = 256;    // points of one workgroup of the pair sweep = its j tile = its threads
+constexpr int EVAL_MI_SLICES = EVAL_MAX_ROWS / EVAL_MI_POINTS;      // workgroups of one pair at the row cap
+constexpr size_t EVAL_MI_WS = 32 + (size_t)EVAL_MI * EVAL_MI_SLICES * 2;      // doubles: column statistics, then the per-slice partial sums
+constexpr int EVAL_MI_PSI = EVAL_MAX_ROWS + 2;      // entries of the digamma table: the integers 0 .. 8193
+struct EvalMiArgs {
+    const float* s0; const float* S_real;      // [M][10], [M][EVAL_FACTORS]
+    const double* noise;               // [EVAL_MI][2][M], or null: drawn under TAG_MI from (k0, k1), row j, stream_id(pair, which), stage
+    int M, k;
+    uint32_t k0, k1, stage;
+    double* ws;                        // [EVAL_MI_WS]
+    const double* psi;                 // [EVAL_MI_PSI]: digamma at the integers (eval_mi_psi_table)
+    float* out;                        // [EVAL_MI]
+    int32_t* counts;                   // null, or [EVAL_MI][2][M]
+};
+void launch_eval_mi(const EvalMiArgs& a, hipStream_t st);
+void eval_mi_psi_table(double* t);     // host: fills t[EVAL_MI_PSI]
 
 // ---- training of the small MLPs (train.hip): backward + Adam over a layer table -----------------------------------
 // A trainable part is a chain of Linear layers described by a DEVICE-RESIDENT table (built at efe_commit_weights): widths, the ReLU flag

@@ -23,7 +23,8 @@
 
 namespace efe {
 
-enum : uint32_t { TAG_MID = 0x10, TAG_DEC = 0x20, TAG_ENC = 0x30, TAG_EPS = 0x40, TAG_ACT = 0x50 };
+enum : uint32_t { TAG_MID = 0x10, TAG_DEC = 0x20, TAG_ENC = 0x30, TAG_EPS = 0x40, TAG_ACT = 0x50,
+                  TAG_MI = 0x80 };      // (0x60 and 0x70: TAG_ENV, TAG_AGENT of kernels.h) the tie-breaking jitter of efe_eval_mi (eval_mi.hip)
 enum : uint32_t { PASS_T1 = 0, PASS_D1 = 1, PASS_E1 = 2, PASS_T2 = 3, PASS_D2A = 4, PASS_D2B = 5,
                   PASS_ROOT = 6, PASS_HABIT = 7, PASS_SIM = 8,
                   // forward free energy of a training step (efe_free_energy, loss.hip): o0 encoder + normals, o1 encoder, transition +
@@ -56,9 +57,10 @@ __device__ __forceinline__ float u01(uint32_t x) {
     return ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f;   // 2^-24, result in (0,1)
 }
 
-// element k (0..) of the normal vector of one row
-__device__ __forceinline__ float normal_elem(uint32_t k0, uint32_t k1, uint32_t row, uint32_t stream, uint32_t stage, int k) {
-    const uint4 w = noise_words(k0, k1, TAG_EPS, (uint32_t)(k >> 2), row, stream, stage);
+// element k (0..) of the normal vector of one row, under the draw site's tag
+__device__ __forceinline__ float normal_elem(uint32_t k0, uint32_t k1, uint32_t row, uint32_t stream, uint32_t stage, int k,
+                                             uint32_t tag = TAG_EPS) {
+    const uint4 w = noise_words(k0, k1, tag, (uint32_t)(k >> 2), row, stream, stage);
     const int lane = k & 3;
     const uint32_t a = (lane & 2) ? w.z : w.x;
     const uint32_t b = (lane & 2) ? w.w : w.y;

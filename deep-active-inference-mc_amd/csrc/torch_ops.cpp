@@ -684,6 +684,41 @@ void eval_stats(int64_t h, const OptT& F_top, const OptT& F_mid, const OptT& F_d
     ok(c, efe_eval_stats(c, &ei, (int)M, state(out, "out", EFE_EVAL_STATS), stream_of(out)));
 }
 
+// the mutual information of every latent with every true factor (efe_eval_mi) into out [EFE_EVAL_MI], written in place; noise: float64
+// [EFE_EVAL_MI, 2, M] or none (device noise from seed and stage); counts: int32 [EFE_EVAL_MI, 2, M] or none.  The engine refuses
+// n_neighbors and M out of range before it launches, so the sizes are checked here only where it would go on to read them.
+void eval_mi(int64_t h, const Tensor& s0_, const Tensor& S_real_, const OptT& noise, int64_t n_neighbors, int64_t seed, int64_t stage, Tensor out,
+             const OptT& counts) {
+    efe_ctx* c = CTX(h);
+    Tensor s0 = in(s0_, "s0"), S = in(S_real_, "S_real"), nk;
+    const int64_t M = s0.dim() ? s0.size(0) : 1;
+    TORCH_CHECK(M <= INT32_MAX && n_neighbors >= INT32_MIN && n_neighbors <= INT32_MAX, "efe engine: efe_eval_mi: M / n_neighbors out of range");
+    const bool sized = M >= 1 && M <= EFE_EVAL_MAX_ROWS;
+    auto dev_ok = [&](const Tensor& t, const char* name, at::ScalarType ty, const char* tyname) {
+        TORCH_CHECK(t.is_cuda(), "efe: ", name, " must be a HIP device tensor (there is no CPU fallback)");
+        TORCH_CHECK((int)t.device().index() == tl_ctx_device, "efe: ", name, " is on device ", (int)t.device().index(), ", the engine context lives on device ", tl_ctx_device);
+        TORCH_CHECK(t.scalar_type() == ty, "efe: ", name, " must be ", tyname);
+    };
+    TORCH_CHECK(!sized || (s0.numel() == M * 10 && S.numel() == M * 6), "efe engine: efe_eval_mi: s0 / S_real have ", s0.numel(), " / ", S.numel(),
+                " elements, expected ", M, " x 10 and ", M, " x 6");
+    efe_eval_mi_in mi{};
+    mi.s0 = s0.data_ptr<float>(); mi.S_real = S.data_ptr<float>();
+    if (noise.has_value() && noise->defined()) {
+        dev_ok(*noise, "noise", at::kDouble, "float64");
+        nk = noise->contiguous();
+        TORCH_CHECK(!sized || nk.numel() == (int64_t)EFE_EVAL_MI * 2 * M, "efe engine: efe_eval_mi: noise has ", nk.numel(), " elements, expected 60 x 2 x ", M);
+        mi.noise = nk.data_ptr<double>();
+    }
+    mi.n_neighbors = (int)n_neighbors; mi.seed = (uint64_t)seed; mi.stage = (uint32_t)stage;
+    int32_t* cp = nullptr;
+    if (counts.has_value() && counts->defined()) {
+        dev_ok(*counts, "counts", at::kInt, "int32");
+        TORCH_CHECK(counts->is_contiguous() && (!sized || counts->numel() == (int64_t)EFE_EVAL_MI * 2 * M), "efe engine: efe_eval_mi: counts must be a contiguous int32 tensor of 60 x 2 x ", M, " elements");
+        cp = counts->data_ptr<int32_t>();
+    }
+    ok(c, efe_eval_mi(c, &mi, (int)M, state(out, "out", EFE_EVAL_MI), cp, stream_of(out)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(efe, m) {
@@ -717,6 +752,7 @@ TORCH_LIBRARY(efe, m) {
     m.def("train_step(int ctx, Tensor o0, Tensor o1, Tensor pi0, Tensor log_Ppi, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, float a, float b, float c, float d, int seed, int stage, int row_offset, Tensor? eps, Tensor(a!) top_exp_avg, Tensor(b!) top_exp_avg_sq, Tensor(c!) mid_exp_avg, Tensor(d!) mid_exp_avg_sq, Tensor(e!) down_exp_avg, Tensor(f!) down_exp_avg_sq, float[] hyper, int[] steps, Tensor(g!) means) -> Tensor[]");
     m.def("eval_stats(int ctx, Tensor? F_top, Tensor? F_mid, Tensor? F_down, Tensor? nlogpo1, Tensor? kl_s, Tensor? kl_naive, Tensor? kl_pi, Tensor? kl_s_anal, Tensor? kl_naive_anal, Tensor? kl_pi_anal, Tensor? qs1, Tensor? s0, Tensor? S_real, Tensor? o1_r, Tensor? po1_r, int M, int Mr, Tensor(a!) out) -> ()");
     m.def("down_adam_step(int ctx, Tensor grad, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> ()");
+    m.def("eval_mi(int ctx, Tensor s0, Tensor S_real, Tensor? noise, int n_neighbors, int seed, int stage, Tensor(a!) out, Tensor(b!)? counts) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP device on ROCm builds of PyTorch
@@ -750,4 +786,5 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("train_step", &train_step);
     m.impl("eval_stats", &eval_stats);
     m.impl("down_adam_step", &down_adam_step);
+    m.impl("eval_mi", &eval_mi);
 }

@@ -446,6 +446,29 @@ def eval_stats(fe=None, S_real=None, reward=None, out=None, *, engine=None):
     return out
 
 
+def eval_mutual_info(s0, S_real, *, n_neighbors=3, noise=None, seed=0, stage=0, out=None, counts=None, engine=None):
+    """The mutual information of every latent column of s0 [M, 10] with every true factor of S_real [M, 6] (EVAL_FACTORS), the scores
+    sklearn.feature_selection.mutual_info_regression gives generate_traversals.py:36-46, in one engine call (efe_eval_mi,
+    csrc/eval_mi.hip) with no synchronisation -> a float32 [60] device tensor, latent-major like `spearman`.  The estimator is the one
+    scikit-learn defines for float64 columns (the reference hands it a float32 factor column, whose value is an
+    accident of that dtype and is not reproduced).
+      noise  : float64 [60, 2, M], pair-major, the latent's vector first: the standard normals of the tie-breaking jitter.  None: drawn on
+               the device from (seed, stage), and the result is a function of (s0, S_real, n_neighbors, seed, stage) alone.
+      out    : an optional contiguous float32 [60] device tensor (or view) written in place.
+      counts : an optional contiguous int32 [60, 2, M] device tensor: the marginal neighbour counts nx, ny of every point of every pair.
+    n_neighbors in 1 .. 4, n_neighbors < M <= 8192.  engine: as eval_stats."""
+    e = engine
+    if e is None:
+        e = _stats_engine(next((t.device for t in (s0, S_real, out) if isinstance(t, torch.Tensor) and t.is_cuda), 'cuda'))
+    s0, S_real = e.tensor(s0), e.tensor(S_real)
+    if noise is not None:
+        noise = torch.as_tensor(noise, dtype=torch.float64).to(s0.device).contiguous()
+    if out is None:
+        out = e.empty(_lib.EFE_EVAL_MI)
+    e.ops.eval_mi(e.h, s0, S_real, noise, int(n_neighbors), int(seed), int(stage), out, counts)
+    return out
+
+
 def compare_reward(o1, po1, *, engine=None):
     """src/util.py:82-85 on the device: the mean squared error of the prediction po1 against o1 over the reward bar (image rows 0..2),
     both [M, 1, 64, 64] (NCHW; the reference slices its NHWC arrays as [:, 0:3, 0:64, :]) -> a 0-d device tensor"""

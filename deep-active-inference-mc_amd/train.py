@@ -16,7 +16,9 @@ Deviations from the reference, each documented where it applies:
   * the dSprites archive does not ship: the games run on whatever sprite bank they were built with (env.synthetic_sprite_bank by default).
   * no plots (generate_traversals, reconstructions_plot, stats_plot).  `Trainer.report` produces every number of the epoch report on the
     device (loss.eval_stats), the reward-transition test (train.py:181-186) and the Spearman correlations of generate_traversals.py:36-46
-    included; their p-values and the mutual_info_regression scores of that script (a randomised estimator) are not computed."""
+    included, and with `mutual_info=True` that script's mutual_info_regression scores (loss.eval_mutual_info: the estimator as
+    scikit-learn defines it for float64 columns).  The Spearman p-values, which the reference computes and drops,
+    are not computed."""
 import numpy as np
 import torch
 
@@ -145,13 +147,15 @@ class Trainer:
             'var_d': d, 'TC': float(total_correlation(fe.qs1.cpu().numpy())),
         }
 
-    def report(self, game_test, *, reward_deepness=1):
+    def report(self, game_test, *, reward_deepness=1, mutual_info=False, n_neighbors=3):
         """The whole per-epoch report, train.py:136-187 without the plots, with ONE download -> {REPORT_KEYS}: EVAL_KEYS as `evaluate` gives
         them, `mse_r` (the reward-transition test, train.py:181-186) and `spearman` [10, 6] (the correlation of every latent of the o0
         sample with every true factor, loss.EVAL_FACTORS: generate_traversals.py:36-46 without the p-values).  On `game_test`: the
         evaluation batch with its true latents, free_energy at omega = var_a / 2 + var_d, the reward-transition batch pushed through
         imagine_future_from_o, and loss.eval_stats over all of it; the last training round's omega mean / std join the row on the device.
-        (The environment's own validity checks still look at one flag per call.)"""
+        (The environment's own validity checks still look at one flag per call.)  mutual_info=True adds the key `mutual_info` [10, 6]
+        behind `spearman`: loss.eval_mutual_info of the same s0 and true factors with device noise (seed: the model's, stage: the rounds
+        this trainer has run), written into the same device row, so it is still one download."""
         m = self.model
         a, b, c, d = self.omega_params
         e = m._ready()
@@ -161,10 +165,13 @@ class Trainer:
         r0, r1, rpi = util.make_batch_dsprites_random_reward_transitions(game_test, deepness=reward_deepness, repeats=self.repeats)
         po1 = m.imagine_future_from_o(r0, rpi)
         n = loss._lib.EFE_EVAL_STATS
-        row = torch.full((n + 2,), float('nan'), dtype=torch.float32, device=m.device)
+        n_mi = loss._lib.EFE_EVAL_MI if mutual_info else 0
+        row = torch.full((n + 2 + n_mi,), float('nan'), dtype=torch.float32, device=m.device)
         loss.eval_stats(fe, S0_real, (r1, po1), out=row[:n], engine=e)
         if self.rounds_done:
-            row[n:] = self.means[self.rounds_done - 1][1::6]      # omega, omega_std (STEP_MEANS_FIELDS 1 and 7)
+            row[n:n + 2] = self.means[self.rounds_done - 1][1::6]      # omega, omega_std (STEP_MEANS_FIELDS 1 and 7)
+        if mutual_info:
+            loss.eval_mutual_info(fe.s0, S0_real, n_neighbors=n_neighbors, seed=m.seed, stage=self.rounds_done, out=row[n + 2:], engine=e)
         h = row.cpu().numpy()
         f = {k: h[s] for k, s in loss.EVAL_STATS_FIELDS.items()}
         var = {'var_beta_s': float(m.beta_s), 'var_gamma': float(m.gamma), 'var_beta_o': float(m.beta_o), 'var_a': a, 'var_b': b, 'var_c': c,
@@ -177,4 +184,6 @@ class Trainer:
                 out[k] = f[k].reshape(m.s_dim, len(loss.EVAL_FACTORS)).copy()
             else:
                 out[k] = f[k].copy() if f[k].size > 1 else float(f[k][0])
+        if mutual_info:
+            out['mutual_info'] = h[n + 2:].reshape(m.s_dim, len(loss.EVAL_FACTORS)).copy()
         return out

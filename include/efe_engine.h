@@ -612,6 +612,30 @@ typedef struct efe_eval_in {
 } efe_eval_in;
 int efe_eval_stats(efe_ctx*, const efe_eval_in* in, int M, float* out /*[EFE_EVAL_STATS]*/, void* stream);
 
+/* ---- the epoch report: mutual information of latents and true factors (csrc/eval_mi.hip; additive to ABI 6) -------------------------------
+ * The second curve of the reference's traversal figure (graphs/generate_traversals.py:36-46): out[l * 6 + f] = the mutual information of
+ * latent column l of s0 [M][10] and factor column f of S_real [M][6], by the Kraskov-Stoegbauer-Grassberger k-nearest-neighbour estimator
+ * as scikit-learn's mutual_info_regression defines it for float64 columns, in one call scope with no host
+ * synchronisation.  Per pair, in fp64 with contraction off: each column is divided by its standard deviation (divisor M; 1 where it is
+ * below 10 * 2^-52) and gets the jitter (1e-10 * max(1, mean|v|)) * noise; r_i is the n_neighbors-th smallest Chebyshev distance of point i
+ * to another point, moved one fp64 step toward zero; nx_i, ny_i count the other points within r_i on each axis;
+ * MI = max(0, psi(M) + psi(n_neighbors) - mean psi(nx + 1) - mean psi(ny + 1)), rounded once to fp32.
+ *   noise  : [EFE_EVAL_MI][2][M] fp64, pair-major, the latent's vector first; or NULL: element 0 of the normal vector of counter
+ *            (TAG_MI = 0x80, row i, stream_id(pair, which), stage) under the key of `seed`, widened to double (which: 0 latent, 1 factor).
+ *            With device noise the result is a function of (s0, S_real, n_neighbors, seed, stage) alone.
+ *   counts : NULL, or int32 [EFE_EVAL_MI][2][M]: nx then ny of every pair.
+ * The sums behind the standard deviations and mean|v| follow efe_eval_stats' order contract with an fp64 accumulator; the last step has a
+ * fixed order too, with psi from a table of harmonic numbers (csrc/eval_mi.hip), so the result is the same bits on every run.  A pair whose latent
+ * column, factor column or noise holds a NaN or an infinity is NaN; the other pairs keep their bits.
+ * Returns 1 with a message that names efe_eval_mi, before the first launch and writing nothing, for: in, out, in->s0 or in->S_real NULL,
+ * n_neighbors outside 1 .. EFE_EVAL_MI_MAX_NEIGHBORS, M < n_neighbors + 1, M > EFE_EVAL_MAX_ROWS. */
+enum { EFE_EVAL_MI = 60, EFE_EVAL_MI_MAX_NEIGHBORS = 4 };
+typedef struct efe_eval_mi_in {
+    const float* s0; const float* S_real; const double* noise;
+    int n_neighbors; uint64_t seed; uint32_t stage;
+} efe_eval_mi_in;
+int efe_eval_mi(efe_ctx*, const efe_eval_mi_in* in, int M, float* out /*[EFE_EVAL_MI]*/, int32_t* counts, void* stream);
+
 /* introspection for benches: algorithmic MACs of the last EFE-level call (0 for a handle that is not live). */
 int64_t efe_last_call_macs(efe_ctx*);
 

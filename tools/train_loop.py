@@ -1,13 +1,14 @@
 """The training loop of the reference's train.py on the device: a command line over daimc_amd.train.Trainer.
 
-    python tools/train_loop.py --batch 50 --epochs 4 --rounds 100 --folder runs/a [--resume] [--sprites dsprites.npz] [--report]
+    python tools/train_loop.py --batch 50 --epochs 4 --rounds 100 --folder runs/a [--resume] [--sprites dsprites.npz] [--report | --report-mi]
 
 Per epoch: the gamma schedule, `rounds` training rounds (one engine call each, no read-back), the evaluation block on `--test-size`
 random transitions, one line in the reference's format, and a checkpoint (model.save_all: weights, stats, optimiser state) every second
 epoch, as train.py:128-129.  --sprites takes the dSprites archive (an .npz with `imgs`, or an .npy of [N,64,64] uint8); without it the
 games run on the synthetic sprite bank, because the archive does not ship.  There are no plots.  With --report the epoch evaluation is
 Trainer.report: the same numbers reduced on the device and downloaded once, and `stats` gains `mse_r` (the reward-transition test) and
-`spearman` (latent against true factor, [10, 6] per epoch); the printed line is the same."""
+`spearman` (latent against true factor, [10, 6] per epoch); the printed line is the same.  --report-mi is --report with `mutual_info` as
+well: the k-nearest-neighbour mutual information of every latent with every true factor ([10, 6] per epoch), in the same download."""
 import argparse
 import os
 import sys
@@ -29,6 +30,7 @@ def parser():
     ap.add_argument('--folder', default='train_run', help='the checkpoint lives in FOLDER/checkpoints')
     ap.add_argument('--sprites', default=None, metavar='PATH', help='dSprites images; default: the synthetic sprite bank')
     ap.add_argument('--report', action='store_true', help='evaluate through Trainer.report: one download per epoch, stats gain mse_r and spearman')
+    ap.add_argument('--report-mi', action='store_true', help='--report, and stats gain mutual_info: the KSG mutual information of every latent with every true factor')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', default='cuda:0')
     return ap
@@ -59,7 +61,8 @@ def main(argv=None):
     imgs = sprites(args.sprites)
     games = daimc_amd.Game(args.batch, model=model, imgs=imgs, seed=args.seed)
     game_test = daimc_amd.Game(args.test_size, model=model, imgs=imgs, seed=args.seed + 1)
-    keys = REPORT_KEYS if args.report else EVAL_KEYS
+    report = args.report or args.report_mi
+    keys = (REPORT_KEYS + (('mutual_info',) if args.report_mi else ())) if report else EVAL_KEYS
     stats, optimizers = ({k: [] for k in keys}, None)
     if args.resume:                                                                                      # train.py:76-83
         stats, optimizers = model.load_all(chp)
@@ -71,7 +74,7 @@ def main(argv=None):
     for epoch in range(len(stats['F']) + 1, args.epochs + 1):
         tr.begin_epoch(epoch)
         tr.epoch(args.rounds)
-        st = tr.report(game_test) if args.report else tr.evaluate(*make_batch_random(game_test, tr.repeats, gen))
+        st = tr.report(game_test, mutual_info=args.report_mi) if report else tr.evaluate(*make_batch_random(game_test, tr.repeats, gen))
         for k in keys:
             stats[k].append(st[k])
         if epoch % 2 == 0:                                                                               # train.py:128-129
