@@ -17,4 +17,4 @@ from .optim import Adam  # noqa: F401
 from . import train  # noqa: F401
 from .train import Trainer  # noqa: F401
 from . import agent  # noqa: F401
-from .agent import AgentRunner, AgentState, run_agent  # noqa: F401
+from .agent import AgentRunner, AgentState, AgentTrace, run_agent  # noqa: F401

@@ -18,7 +18,8 @@ EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'ef
            'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
            'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step', 'efe_eval_stats',
            'efe_encoder_rows', 'efe_rollout_rows', 'efe_agent_need', 'efe_agent_choose', 'efe_agent_enqueue', 'efe_agent_act',
-           'efe_agent_mcts_root', 'efe_agent_mcts_enqueue', 'efe_eval_mi']
+           'efe_agent_mcts_root', 'efe_agent_mcts_enqueue', 'efe_eval_mi',
+           'efe_agent_trace_tick', 'efe_agent_trace_decision', 'efe_agent_plan_mask', 'efe_agent_view']
 ABI_VERSION = 6
 
 
@@ -33,6 +34,14 @@ class EfeAgent(C.Structure):
 
 
 EFE_AGENT_AI, EFE_AGENT_T1, EFE_AGENT_T12, EFE_AGENT_PROBS = 0, 1, 2, 3
+EFE_AGENT_NONE = -1
+
+# efe_agent_trace (include/efe_engine.h): the arrays of the record in struct order, then T, E, Lp
+TRACE_FIELDS = ('state', 'last_r', 'action', 'queue_len', 'decided', 'choice', 'u', 'G', 'terms', 'probs', 'path', 'path_len')
+
+
+class EfeAgentTrace(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in TRACE_FIELDS] + [('T', C.c_int32), ('E', C.c_int32), ('Lp', C.c_int32)]
 
 
 class EfeNoise(C.Structure):
@@ -225,5 +234,10 @@ def load():
     lib.efe_agent_act.argtypes = [p, agp, f32p, f32p, nzp, p, p]; lib.efe_agent_act.restype = i
     lib.efe_agent_mcts_root.argtypes = [p, agp, p, i, f32p, i, i, C.c_float, i, i, nzp, f32p, p, p, p, f32p, p]; lib.efe_agent_mcts_root.restype = i
     lib.efe_agent_mcts_enqueue.argtypes = [p, agp, C.POINTER(EfeMctsTree), p, i, p, i, i, p, p, p]; lib.efe_agent_mcts_enqueue.restype = i
+    trp = C.POINTER(EfeAgentTrace)
+    lib.efe_agent_trace_tick.argtypes = [p, agp, trp, i, f32p, f32p, p]; lib.efe_agent_trace_tick.restype = i
+    lib.efe_agent_trace_decision.argtypes = [p, trp, i, p, i, i, p, f32p, f32p, f32p, f32p, i, C.c_float, p, p, i, p]; lib.efe_agent_trace_decision.restype = i
+    lib.efe_agent_plan_mask.argtypes = [p, p, i, i, f32p, p, p, p, i, i, i, i, i, f32p, p]; lib.efe_agent_plan_mask.restype = i
+    lib.efe_agent_view.argtypes = [p, f32p, f32p, p, i, i, p, p]; lib.efe_agent_view.restype = i
     _lib = lib
     return lib

@@ -62,22 +62,7 @@ __global__ void __launch_bounds__(128) k_agent_choose(const AgentState a, const 
     const int g = ids[i];
     if (g < 0 || g >= a.E) return;                                   // memory safety only: efe_agent_need writes ids in range
     float p[4];
-    if (mode == AGENT_PROBS) {
-        for (int k = 0; k < 4; ++k) p[k] = probs[(size_t)i * 4 + k];
-    } else {
-        const float fs = (float)steps;
-        float ex[4], sum = 0.f;
-        for (int k = 0; k < 4; ++k) {
-            const size_t r = (size_t)i * 4 + k;
-            float x;
-            if (mode == AGENT_AI) x = -(sum_G[r] / fs);
-            else if (mode == AGENT_T1) x = sum_terms[r] / fs;
-            else x = sum_terms[r] / fs - sum_terms[(size_t)n * 4 + r] / fs;
-            ex[k] = expf(x / temperature);
-            sum = (k == 0) ? ex[k] : sum + ex[k];
-        }
-        for (int k = 0; k < 4; ++k) p[k] = ex[k] / sum;
-    }
+    agent_probs(mode, i, n, sum_G, sum_terms, probs, steps, temperature, p);
     const float u = u_inj ? u_inj[i] : u01(noise_words(k0, k1, TAG_AGENT, 0u, game_offset + (uint32_t)g, 0u, stage).x);
     if (u_out) u_out[i] = u;
     bool ok = true;

@@ -1,5 +1,6 @@
 // Host side of the engine, control: the entry points of the Dynamic-dSprites environment (kernels.hip), the agent's control state
-// (agent.hip) and the planner's tree (mcts.hip).  None takes scratch: each checks its arguments and launches.
+// (agent.hip), the record of its run (agent_trace.hip) and the planner's tree (mcts.hip).  None takes scratch: each checks its arguments
+// and launches.
 #include "engine.h"
 
 namespace {
@@ -18,6 +19,20 @@ int agent_state(efe_ctx* ctx, const char* fn, const efe_agent* ag, AgentState& o
     if (ag->cap < 1) return ctx->fail(std::string(fn) + ": cap < 1");
     if (!ag->queue || !ag->head || !ag->len || !ag->crossings || !ag->reward_sum) return ctx->fail(std::string(fn) + ": a NULL array in efe_agent");
     o = AgentState{ag->queue, ag->head, ag->len, ag->crossings, ag->reward_sum, ag->E, ag->cap};
+    return 0;
+}
+
+// the record of an agent run (csrc/agent_trace.hip): every array is required, `row` must lie inside the record
+int agent_trace(efe_ctx* ctx, const char* fn, const efe_agent_trace* tr, int row, AgentTrace& o) {
+    if (!tr) return ctx->fail(std::string(fn) + ": trace is NULL");
+    if (tr->E < 1) return ctx->fail(std::string(fn) + ": E < 1");
+    if (tr->T < 1 || tr->Lp < 1) return ctx->fail(std::string(fn) + ": T < 1 or Lp < 1");
+    if (row < 0 || row >= tr->T) return ctx->fail(std::string(fn) + ": row " + std::to_string(row) + " is outside the record of " + std::to_string(tr->T) + " rows");
+    if (!tr->state || !tr->last_r || !tr->action || !tr->queue_len || !tr->decided || !tr->choice || !tr->u || !tr->G || !tr->terms || !tr->probs ||
+        !tr->path || !tr->path_len)
+        return ctx->fail(std::string(fn) + ": a NULL array in efe_agent_trace");
+    o = AgentTrace{tr->state, tr->last_r, tr->action, tr->queue_len, tr->decided, tr->choice, tr->u, tr->G, tr->terms, tr->probs, tr->path,
+                   tr->path_len, tr->T, tr->E, tr->Lp};
     return 0;
 }
 
@@ -146,6 +161,63 @@ int efe_agent_mcts_enqueue(efe_ctx* ctx, const efe_agent* agent, const efe_mcts_
     if (!ids || !decided) return ctx->fail("efe_agent_mcts_enqueue: ids or decided is NULL");
     const MctsTree t{tree->W, tree->N, tree->Qpi, tree->child, tree->S, tree->E, tree->cap, tree->A, tree->s_dim};
     launch_agent_mcts_enqueue(a, t, ids, n, decided, max_depth, jumps, path_out, path_len_out, (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_trace_tick(efe_ctx* ctx, const efe_agent* agent, const efe_agent_trace* trace, int row, const float* state, const float* last_r,
+                         void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentState a; if (agent_state(ctx, "efe_agent_trace_tick", agent, a)) return 1;
+    AgentTrace tr; if (agent_trace(ctx, "efe_agent_trace_tick", trace, row, tr)) return 1;
+    if (tr.E != a.E) return ctx->fail("efe_agent_trace_tick: the record holds " + std::to_string(tr.E) + " games, the agent " + std::to_string(a.E));
+    if (!state || !last_r) return ctx->fail("efe_agent_trace_tick: state or last_r is NULL");
+    launch_agent_trace_tick(a, tr, row, state, last_r, (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_trace_decision(efe_ctx* ctx, const efe_agent_trace* trace, int row, const int32_t* ids, int n, int mode, const int32_t* choice,
+                             const float* u, const float* sum_G, const float* sum_terms, const float* probs, int steps, float temperature,
+                             const int32_t* path, const int32_t* path_len, int path_stride, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    AgentTrace tr; if (agent_trace(ctx, "efe_agent_trace_decision", trace, row, tr)) return 1;
+    if (n < 0 || n > tr.E) return ctx->fail("efe_agent_trace_decision: n < 0 or n > E");
+    if (mode != EFE_AGENT_NONE && mode != EFE_AGENT_AI && mode != EFE_AGENT_T1 && mode != EFE_AGENT_T12 && mode != EFE_AGENT_PROBS)
+        return ctx->fail("efe_agent_trace_decision: unknown mode " + std::to_string(mode));
+    if (!ids) return ctx->fail("efe_agent_trace_decision: ids is NULL");
+    if (mode == EFE_AGENT_AI || mode == EFE_AGENT_T1 || mode == EFE_AGENT_T12) {
+        if (!sum_G || !sum_terms) return ctx->fail("efe_agent_trace_decision: modes ai, t1 and t12 need sum_G and sum_terms");
+        if (steps < 1) return ctx->fail("efe_agent_trace_decision: steps < 1");
+        if (!(temperature > 0.0f) || std::isinf(temperature)) return ctx->fail("efe_agent_trace_decision: the temperature must be finite and positive");
+    }
+    if (mode == EFE_AGENT_PROBS && !probs) return ctx->fail("efe_agent_trace_decision: mode probs needs probs");
+    if ((path != nullptr) != (path_len != nullptr)) return ctx->fail("efe_agent_trace_decision: path and path_len come together");
+    if (path && path_stride < 1) return ctx->fail("efe_agent_trace_decision: path_stride < 1");
+    launch_agent_trace_decision(tr, row, ids, n, mode, choice, u, sum_G, sum_terms, probs, steps, temperature, path, path_len, path_stride,
+                                (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_plan_mask(efe_ctx* ctx, const int32_t* ids, int n, int E, const float* state, const int32_t* H_act, const int32_t* H_len,
+                        const uint8_t* H_active, int n_iter, int h_slots, int max_depth, int jumps, int A, float* mask, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    if (E < 1) return ctx->fail("efe_agent_plan_mask: E < 1");
+    if (n < 0 || n > E) return ctx->fail("efe_agent_plan_mask: n < 0 or n > E");
+    if (A != 4) return ctx->fail("efe_agent_plan_mask: A = " + std::to_string(A) + ", the walk of the mask is defined for 4 actions");
+    if (jumps < 1) return ctx->fail("efe_agent_plan_mask: jumps < 1");
+    if (max_depth < 1 || n_iter < 0) return ctx->fail("efe_agent_plan_mask: max_depth < 1 or n_iter < 0");
+    if (n > h_slots) return ctx->fail("efe_agent_plan_mask: the history has fewer than n slots");
+    if (!ids || !state || !H_act || !H_len || !H_active || !mask) return ctx->fail("efe_agent_plan_mask: ids, state, a history array or mask is NULL");
+    launch_agent_plan_mask(ids, n, E, state, H_act, H_len, H_active, n_iter, h_slots, max_depth, jumps, mask, (hipStream_t)stream);
+    return call.finish();
+}
+
+int efe_agent_view(efe_ctx* ctx, const float* frames, const float* mask, const int32_t* ids, int n, int E, uint8_t* view, void* stream) {
+    Call call(ctx, Mode::device); if (!call) return 1;
+    if (E < 1) return ctx->fail("efe_agent_view: E < 1");
+    if (n < 0 || n > E) return ctx->fail("efe_agent_view: n < 0 or n > E");
+    if (!frames || !view) return ctx->fail("efe_agent_view: frames or view is NULL");
+    if (mask && !ids) return ctx->fail("efe_agent_view: a mask needs ids");
+    launch_agent_view(frames, mask, ids, n, E, view, (hipStream_t)stream);
     return call.finish();
 }
 

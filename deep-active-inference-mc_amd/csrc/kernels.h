@@ -720,6 +720,27 @@ __device__ __forceinline__ bool env_tick_move(float* s, float& r, int pi, uint32
 struct AgentState { int32_t* queue; int32_t* head; int32_t* len; int32_t* crossings; float* reward_sum; int E, cap; };
 enum : uint32_t { TAG_AGENT = 0x70 };                                // the action uniform of efe_agent_choose: word 0 of (TAG_AGENT, game, stream 0, stage)
 enum { AGENT_AI = 0, AGENT_T1 = 1, AGENT_T12 = 2, AGENT_PROBS = 3 };
+// The distribution an action is drawn from, for deciding game i of n (k_agent_choose draws from it, k_agent_trace_decision records it: one
+// function, so the record holds the bits the draw used).  fp32 in the order of test_demo.py:152-159; see k_agent_choose for the formulas.
+__device__ __forceinline__ void agent_probs(int mode, int i, int n, const float* sum_G, const float* sum_terms, const float* probs, int steps,
+                                            float temperature, float p[4]) {
+    if (mode == AGENT_PROBS) {
+        for (int k = 0; k < 4; ++k) p[k] = probs[(size_t)i * 4 + k];
+    } else {
+        const float fs = (float)steps;
+        float ex[4], sum = 0.f;
+        for (int k = 0; k < 4; ++k) {
+            const size_t r = (size_t)i * 4 + k;
+            float x;
+            if (mode == AGENT_AI) x = -(sum_G[r] / fs);
+            else if (mode == AGENT_T1) x = sum_terms[r] / fs;
+            else x = sum_terms[r] / fs - sum_terms[(size_t)n * 4 + r] / fs;
+            ex[k] = expf(x / temperature);
+            sum = (k == 0) ? ex[k] : sum + ex[k];
+        }
+        for (int k = 0; k < 4; ++k) p[k] = ex[k] / sum;
+    }
+}
 void launch_agent_need(const AgentState& a, int32_t* ids, int32_t* count, hipStream_t st);
 void launch_agent_choose(const AgentState& a, const int32_t* ids, int n, int mode, const float* sum_G, const float* sum_terms, const float* probs,
                          int steps, float temperature, int repeat, uint32_t k0, uint32_t k1, uint32_t stage, uint32_t game_offset, const float* u,
@@ -733,5 +754,16 @@ void launch_agent_mcts_root(const AgentState& a, const int32_t* ids, int n, cons
                             int32_t* choice, float* u_out, hipStream_t st);
 void launch_agent_mcts_enqueue(const AgentState& a, const MctsTree& t, const int32_t* ids, int n, const uint8_t* decided, int max_depth, int jumps,
                                int32_t* path_out, int32_t* path_len_out, hipStream_t st);
+// the record of an agent run (csrc/agent_trace.hip; efe_agent_trace of the C ABI): T rows (ticks) x E games, row-major
+struct AgentTrace { float* state; float* last_r; int32_t* action; int32_t* queue_len; uint8_t* decided; int32_t* choice; float* u; float* G;
+                    float* terms; float* probs; int32_t* path; int32_t* path_len; int T, E, Lp; };
+enum { AGENT_NONE = -1 };                                            // a decision without a recorded distribution (the slot planner's)
+void launch_agent_trace_tick(const AgentState& a, const AgentTrace& tr, int row, const float* state, const float* last_r, hipStream_t st);
+void launch_agent_trace_decision(const AgentTrace& tr, int row, const int32_t* ids, int n, int mode, const int32_t* choice, const float* u,
+                                 const float* sum_G, const float* sum_terms, const float* probs, int steps, float temperature,
+                                 const int32_t* path, const int32_t* path_len, int path_stride, hipStream_t st);
+void launch_agent_plan_mask(const int32_t* ids, int n, int E, const float* state, const int32_t* H_act, const int32_t* H_len,
+                            const uint8_t* H_active, int n_iter, int h_slots, int max_depth, int jumps, float* mask, hipStream_t st);
+void launch_agent_view(const float* frames, const float* mask, const int32_t* ids, int n, int E, uint8_t* view, hipStream_t st);
 
 }  // namespace efe

@@ -239,11 +239,13 @@ class BatchedMCTS:
     -- the order in which the slot planner consumes the model's counter, which a keyed decision neither reads nor advances.  What a game
     plans is therefore the same alone and inside any batch.  The engine reads the liveness mask at the game id, the tree kernels write it at
     the slot: `active_g` is the game-indexed copy, refreshed on the device behind every kernel that writes `active`.  No history is kept
-    (H_* are two-row rings: efe_mcts_step needs the previous iteration's rows only) and nothing is downloaded at the end; the lagged stop
-    snapshot is the planner's only host traffic.  begin_keyed / plan_keyed are the two halves of a decision, with efe_agent_mcts_root
-    between them and efe_agent_mcts_enqueue behind them (csrc/agent_mcts.hip)."""
+    (H_* are two-row rings: efe_mcts_step needs the previous iteration's rows only) unless history = True, which keeps all `repeats` rows of
+    a decision on the device as the slot planner does (a traced AgentRunner takes the plan mask from them: rows r < plan_keyed()'s return
+    value; repeats x E x (repeats + 2) x 4 bytes for H_act, 362 KB per game at MCTS_Params() defaults).  Nothing is downloaded at the end;
+    the lagged stop snapshot is the planner's only host traffic.  begin_keyed / plan_keyed are the two halves of a decision, with
+    efe_agent_mcts_root between them and efe_agent_mcts_enqueue behind them (csrc/agent_mcts.hip)."""
 
-    def __init__(self, model, n_episodes, params, episode_offset=0, keyed=False):
+    def __init__(self, model, n_episodes, params, episode_offset=0, keyed=False, history=False):
         import ctypes as C
         import weakref
         from . import _lib
@@ -262,6 +264,7 @@ class BatchedMCTS:
         self.pi_dim = A = model.pi_dim
         self.ep0 = int(episode_offset)
         self.keyed = bool(keyed)
+        self.history = bool(history) and self.keyed                 # (the slot planner keeps its history as it is)
         # slots in use, the global index of entry 0 and the game of every slot: a keyed decision sets them (begin_keyed)
         self.n, self.ro, self._gid = self.E, self.ep0, None
         self.cap = cap = 1 + A * (params.repeats + 2)
@@ -278,7 +281,7 @@ class BatchedMCTS:
         self._C, self._tree_now = C, self._tree
         self.pi_hot = (model.pi_one_hot if A == 4 else model.pi_one_hot_3).repeat(E, 1)
         # per-iteration scratch + history (device)
-        R = 2 if self.keyed else max(1, params.repeats)             # (keyed: rings of two rows, no history)
+        R = 2 if self.keyed and not self.history else max(1, params.repeats)        # (keyed: rings of two rows, unless history = True)
         self.path_nodes = torch.zeros(E, self.max_depth, dtype=torch.int32, device=dev)
         self.H_act = torch.zeros(R, E, self.max_depth, dtype=torch.int32, device=dev)
         self.H_len = torch.zeros(R, E, dtype=torch.int32, device=dev)
@@ -500,7 +503,9 @@ class BatchedMCTS:
         the expansion and each simulation); the decision of tick t starts at stage t * P mod 2^32"""
         return 2 + int(params.repeats) * (1 + int(params.simulation_repeats))
 
-    def run(self, frames, o_shape=(64, 64, 1)):
+    def run(self, frames, o_shape=(64, 64, 1), history_hook=None):
+        """history_hook(planner, n_iter): called once per decision while the history of its n_iter iterations (H_act, H_len, H_active, rows
+        r < n_iter) is on the device and before it is read back -- the agent loop takes the plan mask from it"""
         if self.keyed:
             raise RuntimeError('a keyed planner runs a decision through begin_keyed / plan_keyed (daimc_amd.agent.AgentRunner)')
         # the little host-side work left (habit shortcut, final path read-out) uses tiny tensors: one intra-op thread
@@ -509,11 +514,11 @@ class BatchedMCTS:
         if self.overlap:
             self.sim_model = self.model.cached_replica()       # same object unless the weights changed; refreshed noise settings
         try:
-            return self._run(frames, o_shape)
+            return self._run(frames, o_shape, history_hook)
         finally:
             torch.set_num_threads(prev)
 
-    def _run(self, frames, o_shape):
+    def _run(self, frames, o_shape, history_hook=None):
         m, E, p, A, p_ = self.model, self.E, self.p, self.pi_dim, self._p
         lib = m._engine.lib
         res = [None] * E
@@ -535,6 +540,8 @@ class BatchedMCTS:
         st_root = m._take_stage(None, 1)
         st0 = m._take_stage(None, p.repeats * per_it)
         if not bool(active_h.any()):        # every episode was decided by the habit shortcut (mcts.py:166-169): nothing to plan
+            if history_hook is not None:
+                history_hook(self, 0)
             return res
         self.active.copy_(active_h.to(torch.uint8))
         active = self.active
@@ -546,7 +553,10 @@ class BatchedMCTS:
         self._ids, self._rows_cache = None, {}
         if compact and not bool(active_h.all()):
             self._compact(int(active_h.sum()))
-        return self._finish(res, self._iterate(self._tree, st_root, st0, skip, compact))
+        n_iter = self._iterate(self._tree, st_root, st0, skip, compact)
+        if history_hook is not None:
+            history_hook(self, n_iter)
+        return self._finish(res, n_iter)
 
     def _iterate(self, tree, st_root, st0, skip, compact):
         """root expansion and the planning iterations of the first self.n slots (`tree`: the efe_mcts_tree of those slots) -> iterations run"""
@@ -565,7 +575,7 @@ class BatchedMCTS:
         # stop, selection -- per episode in the reference's order (mcts.py:176-191).  The active count of iteration r lands in its own
         # zero-initialised word (no memset launch); the last iteration's back-propagation follows the loop.
         self.n_active_it.zero_()
-        H = (lambda r: r & 1) if self.keyed else (lambda r: r)       # the history row of iteration r (keyed: a ring of two)
+        H = (lambda r: r & 1) if self.keyed and not self.history else (lambda r: r)       # the history row of iteration r (keyed: a ring of two)
         # (one episode too, since round 6: reading the active count in every iteration -- a device synchronisation -- cost 12 % of a
         # one-episode iteration, the lagged snapshot 2 %; the price is up to LAG masked iterations behind the stop.  lagged_single = False:
         # the immediate read)
@@ -685,9 +695,9 @@ class BatchedMCTS:
         return n / n.sum(dim=1, keepdim=True)
 
 
-def active_inference_mcts_batch(model, frames, params, o_shape=(64, 64, 1), episode_offset=0):
+def active_inference_mcts_batch(model, frames, params, o_shape=(64, 64, 1), episode_offset=0, history_hook=None):
     """E planning decisions in lock-step; returns a list of E tuples shaped like active_inference_mcts's result and
-    the [E, pi_dim] root visit distribution."""
+    the [E, pi_dim] root visit distribution.  history_hook: BatchedMCTS.run's."""
     frames = torch.as_tensor(frames)
     # planner objects (device buffers) are kept per (episodes, offset, parameters) on the model
     try:
@@ -705,5 +715,5 @@ def active_inference_mcts_batch(model, frames, params, o_shape=(64, 64, 1), epis
             cache[key] = planner
     else:
         planner.reset()
-    out = planner.run(frames, o_shape)
+    out = planner.run(frames, o_shape, history_hook)
     return out, planner.root_visit_distribution()

@@ -341,6 +341,46 @@ int efe_agent_mcts_root(efe_ctx*, const efe_agent* agent, const int32_t* ids, in
 int efe_agent_mcts_enqueue(efe_ctx*, const efe_agent* agent, const efe_mcts_tree* tree, const int32_t* ids, int n, const uint8_t* decided,
                            int max_depth, int jumps, int32_t* path_out, int32_t* path_len_out, void* stream);
 
+/* ---- the record of an agent run (csrc/agent_trace.hip; additive to ABI 6; what test_demo.py shows on every tick) -------------------------
+ * efe_agent_trace is T rows (ticks) x E games of DEVICE arrays owned by the caller, row-major: state [T][E][7], last_r [T][E], action,
+ * queue_len [T][E] int32, decided [T][E] uint8, choice [T][E] int32, u [T][E], G [T][E][4], terms [T][E][3][4], probs [T][E][4],
+ * path [T][E][Lp] int32, path_len [T][E] int32.  The caller allocates them pre-filled with "nothing happened" (NaN for the floats, -1 for
+ * action and choice, 0 for the rest): a call writes only what happened, nothing initialises a row.  None of these calls writes an array
+ * of efe_agent or of the environment; no engine weights are involved.
+ *   efe_agent_trace_tick    : row `row` of state / last_r = the environment now, action = the head of the queue (-1: the queue is empty
+ *                             and efe_agent_act will not move the game), queue_len = its length.  Called after the tick's decision and
+ *                             before its efe_agent_act.  (efe_agent_act's round_changed may point at a row of an [T][E] int32 array.)
+ *   efe_agent_trace_decision: for the n deciding games ids[0 .. n) (inputs by slot i, the record by game ids[i]): decided = 1; choice and u
+ *                             as given (NULL: the fill stays); mode EFE_AGENT_AI / T1 / T12: G = sum_G / steps, terms = (-sum_terms[0] /
+ *                             steps, sum_terms[1] / steps, sum_terms[2] / steps) (test_demo.py:152-155, one fp32 division each; both
+ *                             arrays are needed in all three modes) and probs = the p efe_agent_choose draws from in that mode, same bits;
+ *                             EFE_AGENT_PROBS: probs = probs [n][4]; EFE_AGENT_NONE: no distribution.  path [n][path_stride] and
+ *                             path_len [n] (both or neither): where path_len[i] >= 0, path_len is recorded as it is and the first
+ *                             min(path_len[i], Lp, path_stride) actions of the path.
+ *   efe_agent_plan_mask     : make_mask (test_demo.py:87-113) for the n deciding slots of an mcts decision into mask [E][32][32] at game
+ *                             ids[i].  The explored paths of slot i are the history rows r < n_iter with H_active[r][i] != 0, cut to
+ *                             H_len[r][i] (H_act [rows][h_slots][max_depth] int32, H_len [rows][h_slots] int32, H_active [rows][h_slots]
+ *                             uint8).  The walker starts at (tx, ty) = (int(state[g][5]), int(state[g][4])) CLAMPED to 0..31 and takes
+ *                             each action `jumps` times (0: tx + 1 if tx < 31, 1: tx - 1 if tx > 0, 2: ty + 1 if ty < 31, 3: ty - 1 if
+ *                             ty > 0); a move that happens adds 1 to count[tx][ty]; mask = float(count) / float(max count), and ALL ZEROS
+ *                             when nothing was counted (the reference divides 0 by 0).  Integer counters: independent of any order.
+ *   efe_agent_view          : view [n][64][64] uint8 from frames [n][64][64] (efe_env_render): rows 59..62 of column 31 set to 1.0,
+ *                             mask[ids[i]] (NULL: none) added onto rows and columns 16..47, then uint8(min(trunc(v * 255), 255)), NaN -> 0:
+ *                             SATURATING where the reference's astype(uint8) wraps.
+ * Each returns 1 with a message that names the call, and launches nothing, for E < 1, n outside [0, E], a row outside the record,
+ * jumps < 1, A != 4 (mask), an unknown mode, or a NULL required pointer. */
+typedef struct efe_agent_trace { float* state; float* last_r; int32_t* action; int32_t* queue_len; uint8_t* decided; int32_t* choice; float* u;
+                                 float* G; float* terms; float* probs; int32_t* path; int32_t* path_len; int32_t T, E, Lp; } efe_agent_trace;
+enum { EFE_AGENT_NONE = -1 };
+int efe_agent_trace_tick(efe_ctx*, const efe_agent* agent, const efe_agent_trace* trace, int row, const float* state, const float* last_r,
+                         void* stream);
+int efe_agent_trace_decision(efe_ctx*, const efe_agent_trace* trace, int row, const int32_t* ids, int n, int mode, const int32_t* choice,
+                             const float* u, const float* sum_G, const float* sum_terms, const float* probs, int steps, float temperature,
+                             const int32_t* path, const int32_t* path_len, int path_stride, void* stream);
+int efe_agent_plan_mask(efe_ctx*, const int32_t* ids, int n, int E, const float* state, const int32_t* H_act, const int32_t* H_len,
+                        const uint8_t* H_active, int n_iter, int h_slots, int max_depth, int jumps, int A, float* mask, void* stream);
+int efe_agent_view(efe_ctx*, const float* frames, const float* mask, const int32_t* ids, int n, int E, uint8_t* view, void* stream);
+
 
 /* ---- training-side free energy, forward only (additive to ABI 6; /root/reference/src/torchloss.py, train.py:104-123) ----------------
  * efe_free_energy evaluates what one training step of train.py computes before its optimizer steps, for M rows:

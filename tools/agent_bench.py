@@ -13,7 +13,14 @@ games one warm-up run per mode, then three unsynchronised runs per mode, ALTERNA
 decisions/s, the spread of the three, and the decision share from one synchronised run.  An existing --out file keeps the rows of the
 (method, games) pairs this call does not measure.
 With --parent, `bench.py --gpus 1 --steps 20 --warmup 5` is run three times each from this checkout and from the parent's, alternating,
-and both sets of result lines are recorded: no existing kernel changes, so the two should sit inside each other's spread."""
+and both sets of result lines are recorded: no existing kernel changes, so the two should sit inside each other's spread.
+
+    python tools/agent_bench.py --trace [--trace-frames 4] [--method ai mcts] [--games 1 64 1024] [--out profiles/agent_trace_bench.json]
+
+measures what recording a run costs (AgentRunner(trace=...)): per method (ai; mcts = the keyed planner) and number of games one warm-up run,
+then three unsynchronised runs each of the untraced loop, the loop with the log, and the loop with the log and the frames of the first
+--trace-frames games, ALTERNATING between the three; per variant the median game-ticks/s and the spread.  ai runs --ticks ticks, mcts
+--mcts-ticks.  The default --out is then profiles/agent_trace_bench.json."""
 import argparse
 import json
 import os
@@ -43,13 +50,14 @@ def timed_runner():
     return TimedRunner
 
 
-def one(model, method, E, ticks, timed_decisions, keyed=False):
+def one(model, method, E, ticks, timed_decisions, keyed=False, trace=None):
     """-> (wall seconds of `ticks` ticks, seconds inside decisions (0 unless timed), run()'s result)"""
     import torch
     import daimc_amd
     games = daimc_amd.Game(E, model=model, seed=1)
     cls = timed_runner() if timed_decisions else daimc_amd.AgentRunner
-    runner = cls(model, games, method, steps=7, jumps=5, samples=10, keyed_planner=keyed)          # mcts: MCTS_Params() as they come
+    kw = {} if trace is None else {'trace': trace}
+    runner = cls(model, games, method, steps=7, jumps=5, samples=10, keyed_planner=keyed, **kw)    # mcts: MCTS_Params() as they come
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     res = runner.run(ticks)
@@ -82,6 +90,26 @@ def mcts_rows(model, E, ticks, runs=3):
     return rows
 
 
+def trace_row(model, method, E, ticks, n_frames, runs=3):
+    """the untraced loop, the loop with the log, and with log + frames at E games: `runs` alternating unsynchronised runs each -> one row"""
+    import daimc_amd
+    keyed = method == 'mcts'
+    variants = {'untraced': lambda: None, 'log': lambda: daimc_amd.AgentTrace(),
+                'log_frames': lambda: daimc_amd.AgentTrace(frames=range(min(n_frames, E)))}
+    one(model, method, E, ticks, False, keyed, variants['log_frames']())                  # warm-up: arena, planner buffers, the record's allocation
+    walls = {v: [] for v in variants}
+    for _ in range(runs):
+        for v, make in variants.items():
+            walls[v].append(one(model, method, E, ticks, False, keyed, make())[0])
+    row = {'method': method, 'planner': 'keyed' if keyed else None, 'games': E, 'ticks': ticks, 'frames_of_games': min(n_frames, E)}
+    for v, w in walls.items():
+        w = sorted(w)
+        row[v] = {'wall_s': walls[v], 'game_ticks_per_s': E * ticks / w[len(w) // 2], 'game_ticks_per_s_min_max': [E * ticks / w[-1], E * ticks / w[0]]}
+    for v in ('log', 'log_frames'):
+        row[v]['relative_to_untraced'] = row[v]['game_ticks_per_s'] / row['untraced']['game_ticks_per_s']
+    return row
+
+
 def bench_line(path):
     r = subprocess.run([sys.executable, os.path.join(path, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5'], capture_output=True,
                        text=True, cwd=path, timeout=900)
@@ -97,10 +125,27 @@ def main(argv=None):
     ap.add_argument('--method', nargs='+', default=['habit', 'ai', 'mcts'], choices=['habit', 'ai', 'mcts'])
     ap.add_argument('--mcts-ticks', type=int, default=20)
     ap.add_argument('--parent', default=None)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'agent_bench.json'))
+    ap.add_argument('--trace', action='store_true', help='measure the cost of recording a run instead (AgentRunner(trace=...))')
+    ap.add_argument('--trace-frames', type=int, default=4, help='--trace: the first N games are filmed in the log + frames variant')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'agent_trace_bench.json' if args.trace else 'agent_bench.json')
     import daimc_amd
     model = daimc_amd.ActiveInferenceModel(10, 4, 1.0, 1.0, 1.0, device='cuda:0', seed=0)
+    if args.trace:
+        rows = []
+        for method in [m for m in ('ai', 'mcts') if m in args.method]:
+            for E in args.games:
+                row = trace_row(model, method, E, args.mcts_ticks if method == 'mcts' else args.ticks, args.trace_frames)
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            json.dump({'what': 'AgentRunner throughput untraced, with the log, and with log + frames; freshly initialised weights, '
+                               'synthetic sprite bank', 'trace': rows}, fh, indent=1)
+        print('wrote', args.out)
+        return
     rows = []
     for E in args.games if 'mcts' in args.method else ():
         for row in mcts_rows(model, E, args.mcts_ticks):

@@ -6,7 +6,10 @@ command line over daimc_amd.agent.AgentRunner.
 Every 1000 ticks it prints test_demo.py's line (`<t> ROUND SCORE: <score> t: <seconds>`, one per game); at the end it writes a JSON summary
 (round scores, reward crossings, the sum of the rewards received, decisions made).  --network takes the folder model.save_all wrote, or
 `random` for freshly initialised weights.  --sprites takes the dSprites archive (an .npz with `imgs`, or an .npy of [N,64,64] uint8);
-without it the games run on the synthetic sprite bank, because the archive does not ship."""
+without it the games run on the synthetic sprite bank, because the archive does not ship.
+--trace OUT.npz records the run (daimc_amd.AgentTrace: per tick and game the state, the executed action, G and its terms, the softmax the
+action was drawn from, the planned path) and writes the record's arrays; --trace-frames N adds the frames of the first N games (`view`,
+uint8, every --frame-every ticks) with the planner's heat mask laid over them."""
 import argparse
 import json
 import os
@@ -39,6 +42,9 @@ def parser():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--out', default='agent_run.json', help='the JSON summary')
+    ap.add_argument('--trace', default=None, metavar='OUT.npz', help='record the run and write the record here')
+    ap.add_argument('--trace-frames', type=int, default=0, metavar='N', help='with --trace: also the frames of the first N games')
+    ap.add_argument('--frame-every', type=int, default=1, metavar='K', help='with --trace-frames: one frame every K ticks')
     return ap
 
 
@@ -62,14 +68,19 @@ def main(argv=None):
     params.C, params.repeats, params.threshold, params.simulation_depth = args.C, args.repeats, args.threshold, args.depth
     params.use_habit = args.no_habit
     games = daimc_amd.Game(args.games, model=model, imgs=sprites(args.sprites), seed=args.seed)
+    trace = None
+    if args.trace:
+        trace = daimc_amd.AgentTrace(frames=range(min(args.trace_frames, args.games)) if args.trace_frames > 0 else None, frame_every=args.frame_every)
     runner = daimc_amd.AgentRunner(model, games, args.method, steps=args.steps, jumps=args.jumps, temperature=args.temperature,
-                                   calc_mean=args.mean, mcts_params=params, keyed_planner=args.keyed_planner)
+                                   calc_mean=args.mean, mcts_params=params, keyed_planner=args.keyed_planner, trace=trace)
+    if trace is not None:
+        trace.reserve(args.duration)                                                       # (the chunks below would otherwise grow it one by one)
     start = time.time()
     res, printed, done = None, 0, 0
     while done < args.duration:
         # a score is recorded at the START of tick 1000 k: the first chunk runs ticks 0 .. 1000, every later one the next 1000
         n = min(args.duration - done, runner.report_ticks + (1 if done == 0 else 0))
-        res = runner.run(n)
+        res = runner.run(n, fetch_trace=done + n >= args.duration)                        # the record is downloaded once, at the end
         done += n
         for row in res['round_scores'][printed:]:
             printed += 1
@@ -84,6 +95,10 @@ def main(argv=None):
                'reward_sum': res['reward_sum'].tolist()}
     with open(args.out, 'w') as fh:
         json.dump(summary, fh)
+    if args.trace:
+        import numpy as np
+        np.savez_compressed(args.trace, **res['trace'])
+        print('wrote', args.trace, '-', res['ticks'], 'rows')
     print('wrote', args.out, '- ticks', res['ticks'], 'decisions', res['decisions'], 'crossings', int(res['crossings'].sum()),
           'reward sum', float(res['reward_sum'].sum()))
 
