@@ -171,12 +171,14 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
 #pragma unroll
                     for (int q = 0; q < 4; ++q) raw[q] = sm[pb[q] + h];
                 }
+                prio_matrix();
                 __builtin_amdgcn_sched_barrier(0);      // keep the prefetch loads AHEAD of this chunk's MFMAs
                 f32x16& x = xacc;
                 x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, v.x, kc == 0 ? zero : x, 0, 0, 0);
                 x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, v.y, x, 0, 0, 0);
                 x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, v.z, x, 0, 0, 0);
                 x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, v.w, x, 0, 0, 0);
+                prio_nonmatrix();
             }
             // the xi's output transform (a second accumulator to overlap it with the next xi's MFMAs does not fit the register budget)
             otrans(a, b, xacc, mask);
@@ -244,6 +246,7 @@ __device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5],
         static_for<w3_nch(GP)>([&](auto c) { aq[ST % F22_PD][c] = f22_wfrag(wr, ln, ST + F22_PD < NST ? 0 : dn, w3_mat(w3_prod(GP, c)), KP); });
         if constexpr (ST + 1 < NST)
             static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
+        prio_matrix();
         __builtin_amdgcn_sched_barrier(0);             // keep the prefetch loads AHEAD of this step's MFMAs
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -258,6 +261,7 @@ __device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5],
                     tq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (KC == 0 && e == 0) ? zero4 : tq[c], 0, 0, 0);
                 }
             });
+        prio_nonmatrix();
         if constexpr (KC == 3)                         // the group's temporaries into their outputs, in chain order
             static_for<w3_nch(G)>([&](auto c) {
                 constexpr int PP = w3_prod(G, c);
@@ -662,27 +666,30 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     // oh = r - 1 + kh), the two channel halves added here; split into pieces for the deferred form
     constexpr int RWG = 2 * SR / NW;
     float gh[RWG][6], gpr[RWG];
-    // (ring slot of y3 row tr = slot hb0 of row r0y + (tr - r0y), wrapped: no division; a row outside the image reads any valid slot)
-    auto g_load = [&](int oh, int q, int r0y, int hb0) {
+    // The H ring as byte offsets: a ring row (both channel halves' three planes) is HROW bytes, and a slot offset moves forward by
+    // fewer than DB_YROWS rows at a time, so one unsigned minimum wraps it (o - HRING wraps around to a huge value unless o >= HRING).
+    constexpr unsigned HROW = 2 * 3 * 64 * sizeof(float), HRING = DB_YROWS * HROW;
+    auto ring_fwd = [&](unsigned o, unsigned rows) { o += rows * HROW; const unsigned t = o - HRING; return t < o ? t : o; };
+    const float* const sHl = sH + lane;
+    // go: ring byte offset of y3 row oh - 1 (the gather's lowest source row); row oh + 1 - kh is 2 - kh ring rows behind it.  gm: all
+    // ones where that source row is inside the image, else zero -- the row then contributes +0, whatever its slot holds.
+    unsigned gm[RWG][3];
+    auto g_load = [&](unsigned go, int q) {
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
-            const int tr = oh + 1 - kh;
-            const bool rv = tr >= 0 && tr <= 63;
-            int hs = hb0 + (tr - r0y);
-            hs = hs < 0 ? hs + DB_YROWS : hs;
-            hs = hs >= DB_YROWS ? hs - DB_YROWS : hs;
-            hs = rv ? hs : 0;
-            const float* hq = sH + ((hs * 2) * 3 + kh) * 64 + lane;
+            const float* hq = reinterpret_cast<const float*>(reinterpret_cast<const char*>(sHl) + (kh == 2 ? go : ring_fwd(go, 2 - kh))) + kh * 64;
             gh[q][2 * kh] = hq[0]; gh[q][2 * kh + 1] = hq[3 * 64];
         }
     };
-    auto g_sig = [&](int oh, int q) {
+    auto g_mask = [&](int oh, int q) {
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) gm[q][kh] = (unsigned)(oh + 1 - kh) <= 63u ? ~0u : 0u;
+    };
+    auto g_sig = [&](int q) {
         float val = a.b4;
 #pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int tr = oh + 1 - kh;
-            val = add1(val, (tr >= 0 && tr <= 63) ? add1(gh[q][2 * kh], gh[q][2 * kh + 1]) : 0.f);
-        }
+        for (int kh = 0; kh < 3; ++kh)
+            val = add1(val, __builtin_bit_cast(float, __builtin_bit_cast(unsigned, add1(gh[q][2 * kh], gh[q][2 * kh + 1])) & gm[q][kh]));
         // hardware exp2 / rcp / log2 (v_exp_f32, v_rcp_f32, v_log_f32: 1 ulp each) instead of the libm expansions: ~14 instead of ~60 VALU
         // instructions per pixel, each of which costs ~19 cycles of wave time beside the other wave's MFMA stream; the image stays within
         // 3e-7 of the libm form, the 4096-pixel sums within their own fp32 rounding (tests/test_gpu_parity.py tolerances unchanged)
@@ -709,18 +716,22 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
 
     // a quarter is complete: park the thread's partial sum (one LDS write; the reductions of all quarters run once, behind the last strip)
     auto fold = [&](int k) { sq[k * NTHR + tid] = part; part = 0.f; };
-    float* const sHw = sH + g * 64 + 4 * v;               // this lane's place in an H plane of its tap row
-    int hb = 0, hbp = 0;                                   // H-ring slots of y3 rows 2 SR s (this strip's first) and 2 SR (s - 1)
+    char* const sHw = reinterpret_cast<char*>(sH + hf * (3 * 64) + g * 64 + 4 * v);     // this lane's place in an H plane of its channel half and tap row
+    // The ring's schedule is fixed: the slot of y3 row 2 SR s (this strip's first) advances 2 SR mod DB_YROWS per strip from 0.  hbo is its
+    // byte offset; this wave's four write rows (4 u + orow ring rows on) and the six source rows of its deferred gather (rows
+    // -(2 SR) - 2 + w + {0, 1, 2, 4, 5, 6} of the previous strip, that is DB_YROWS - 2 SR - 2 + w + ... ring rows on) are wrapped additions from it.
+    unsigned hbo = 0;
+    const int tl = tid;
+    // staging: piece it is row it >> 1, pixel column 2 ((tl & 31) >> 1) + (it & 1), quad 2 (tl >> 5) + (tl & 1) -- one address register,
+    // the pieces at immediate offsets (the row below the image arrived as zeros)
+    f32x4* const sp = smv + ((tl & 31) >> 1) * (2 * DB_PS) + 2 * (tl >> 5) + (tl & 1);
     for (int s = s_lo; s < s_hi; ++s) {
-        // per-strip laundering of the thread index: stops hipcc hoisting the ~15 staging / prefetch addresses out of the strip loop
-        // (VGPR spills behind the 64 accumulators)
-        int tl = tid; asm volatile("" : "+v"(tl));
         const bool gq = parts == 1 ? true : s == 2 * qtr + 1;   // (uniform) the previous strip's rows are this workgroup's to gather
         const int oh0 = 2 * SR * (s - 1) - 1 + w, oh1 = oh0 + NW;         // this wave's two output rows of the previous strip
-        // stage the strip: piece it is row it >> 1, pixel column 2 ((tl & 31) >> 1) + (it & 1), quad 2 (tl >> 5) + (tl & 1) -- one address
-        // register, the pieces at immediate offsets (the row below the image arrived as zeros)
+        const unsigned go0 = ring_fwd(hbo, DB_YROWS - 2 * SR - 2 + w), go1 = ring_fwd(go0, NW);      // rows oh0 - 1, oh1 - 1
+        const unsigned hwo = ring_fwd(hbo, 4 * u);
+        g_mask(oh0, 0); g_mask(oh1, 1);
         {
-            f32x4* const sp = smv + ((tl & 31) >> 1) * (2 * DB_PS) + 2 * (tl >> 5) + (tl & 1);
 #pragma unroll
             for (int it = 0; it < NPF; ++it) sp[((it >> 1) * DB_RP + (it & 1)) * DB_PS] = pf[it];
         }
@@ -737,6 +748,20 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
         // ---- contraction, software-pipelined one step ahead: step ST = (group ST >> 2, chunk ST & 3), every index a compile-time constant
         f32x4 xr[9];
         static_for<9>([&](auto i) { if constexpr (w3_reads(0, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, 0); });
+        // group GG's temporaries into their outputs, in chain order
+        auto add_tmp = [&](auto gg) {
+            constexpr int GG = decltype(gg)::value;
+            static_for<w3_nch(GG)>([&](auto c) {
+                constexpr int PP = w3_prod(GG, c);
+                if constexpr (!w3_direct(PP))
+                    static_for<16>([&](auto o) {
+                        if constexpr (w3_hits(PP, o)) {
+                            if constexpr (w3_seen(GG, c, o)) acc[o] = add4(acc[o], tq[c]);
+                            else acc[o] = add4(bias4, tq[c]);
+                        }
+                    });
+            });
+        };
         static_for<NST>([&](auto stc) {
             constexpr int ST = decltype(stc)::value, G = ST >> 2, KC = ST & 3, GN = (ST + 1) >> 2, KN = (ST + 1) & 3;
             f32x4 vw[9], ac[5];
@@ -747,6 +772,14 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
                 static_for<w3_nch(GN)>([&](auto c) { aq[c] = wf(w3_mat(w3_prod(GN, c)), KN); });
                 static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
             }
+            // The previous group's temporaries are added HERE, behind this step's views and requests and in front of its MFMAs (the
+            // first that may touch those outputs again), not right behind the group's last MFMA: there every add waited out that
+            // MFMA's result latency in hazard wait states (the barrier keeps hipcc from moving them back up).
+            if constexpr (KC == 0 && ST > 0) {
+                __builtin_amdgcn_sched_barrier(0);
+                add_tmp(std::integral_constant<int, (ST > 0 ? G - 1 : 0)>{});
+            }
+            prio_matrix();
             __builtin_amdgcn_sched_barrier(0);         // keep the prefetch loads AHEAD of this step's MFMAs
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -761,51 +794,53 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
                         tq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (KC == 0 && e == 0) ? zero4 : tq[c], 0, 0, 0);
                     }
                 });
-            if constexpr (KC == 3)                         // the group's temporaries into their outputs, in chain order
-                static_for<w3_nch(G)>([&](auto c) {
-                    constexpr int PP = w3_prod(G, c);
-                    if constexpr (!w3_direct(PP))
-                        static_for<16>([&](auto o) {
-                            if constexpr (w3_hits(PP, o)) {
-                                if constexpr (w3_seen(G, c, o)) acc[o] = add4(acc[o], tq[c]);
-                                else acc[o] = add4(bias4, tq[c]);
-                            }
-                        });
-                });
+            prio_nonmatrix();
             // the previous strip's gather, a piece per step
             if (gq) {
-                if constexpr (ST == 0) { g_load(oh0, 0, 2 * SR * (s - 1), hbp); g_load(oh1, 1, 2 * SR * (s - 1), hbp); }
-                if constexpr (ST == 2) g_sig(oh0, 0);
+                if constexpr (ST == 0) { g_load(go0, 0); g_load(go1, 1); }
+                if constexpr (ST == 2) g_sig(0);
                 if constexpr (ST == 5) g_term(oh0, 0);
-                if constexpr (ST == 8) g_sig(oh1, 1);
+                if constexpr (ST == 8) g_sig(1);
                 if constexpr (ST == 11) g_term(oh1, 1);
             }
         });
         // ---- ReLU, then the 32 -> 1 conv as tap planes (4 v_mfma_f32_16x16x4_f32 per output position, the four columns' chains
         // interleaved) and the horizontal presums of this channel half, one y3 row at a time
         prefetch((s < NS - 1) ? s + 1 : NS - 1, tl);     // the next strip's input, behind this strip's last weight-fragment request
-#pragma unroll
-        for (int orow = 0; orow < 4; ++orow) {
-            f32x4 T[4];
+        // Skewed by one row: a row's MFMAs share their scheduling region with the NEXT row's ReLUs and the PREVIOUS row's presums, so
+        // that no instruction of the region waits for an MFMA result of the same region (a ReLU sunk in front of the MFMA that reads it
+        // costs two hazard wait states, a presum right behind its row's last MFMA ten).  The barrier keeps the ReLUs a block ahead.
+        auto relu_row = [&](int orow) {
 #pragma unroll
             for (int oc = 0; oc < 4; ++oc)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[4 * orow + oc][e] = relu_nan(acc[4 * orow + oc][e]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int oc = 0; oc < 4; ++oc)
-                    T[oc] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4a[e], acc[4 * orow + oc][e], e == 0 ? zero4 : T[oc], 0, 0, 0);
-            // T[oc][kw] = tap (kh = g, kw) at column 4 v + oc; H(c) = (T[kw 0] at c + 1 + T[kw 1] at c) + T[kw 2] at c - 1
+        };
+        // T[oc][kw] = tap (kh = g, kw) at column 4 v + oc; H(c) = (T[kw 0] at c + 1 + T[kw 1] at c) + T[kw 2] at c - 1
+        auto presum_row = [&](const f32x4 (&T)[4], int orow) {
             f32x4 hv;
             hv[0] = add1(add1(T[1][0], T[0][1]), dpp_shr1_zero(T[3][2]));
             hv[1] = add1(add1(T[2][0], T[1][1]), T[0][2]);
             hv[2] = add1(add1(T[3][0], T[2][1]), T[1][2]);
             hv[3] = add1(add1(dpp_shl1_zero(T[0][0]), T[3][1]), T[2][2]);
-            int hsw = hb + 4 * u + orow;                   // ring slot of this wave's y3 row 2 SR s + 4 u + orow
-            hsw = hsw >= DB_YROWS ? hsw - DB_YROWS : hsw;
-            if (g < 3) *reinterpret_cast<f32x4*>(sHw + (hsw * 2 + hf) * (3 * 64)) = hv;     // (the slot is uniform: a scalar offset to the lane's address)
+            // ring slot of this wave's y3 row 2 SR s + 4 u + orow (uniform: a scalar offset to the lane's address)
+            if (g < 3) *reinterpret_cast<f32x4*>(sHw + ring_fwd(hwo, orow)) = hv;
+        };
+        f32x4 T[2][4];
+        relu_row(0);
+#pragma unroll
+        for (int orow = 0; orow < 4; ++orow) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int oc = 0; oc < 4; ++oc)
+                    T[orow & 1][oc] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4a[e], acc[4 * orow + oc][e], e == 0 ? zero4 : T[orow & 1][oc], 0, 0, 0);
+            if (orow < 3) relu_row(orow + 1);
+            if (orow > 0) presum_row(T[(orow - 1) & 1], orow - 1);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        presum_row(T[1], 3);
         __syncthreads();
         if (gq) { g_store(oh0, 0); g_store(oh1, 1); }     // the deferred rows' pixels (stores behind the prefetch loads)
         if (parts == 1 && (s == 2 || s == 4 || s == 6)) fold(s / 2 - 1);       // quarter s / 2 - 1 is complete (its second gather ran inside this strip)
@@ -814,12 +849,11 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
             for (int q = 0; q <= RWG; ++q) {
                 if (q == RWG && (w != 0 || s != NS - 1)) break;
                 const int oh = 2 * SR * s - 1 + q * NW + w;
-                g_load(oh, 0, 2 * SR * s, hb); g_sig(oh, 0); g_term(oh, 0); g_store(oh, 0);
+                g_mask(oh, 0);
+                g_load(ring_fwd(ring_fwd(hbo, DB_YROWS - 2), q * NW + w), 0); g_sig(0); g_term(oh, 0); g_store(oh, 0);      // row oh - 1 = 2 SR s - 2 + ...
             }
         }
-        hbp = hb;
-        hb += 2 * SR;
-        hb = hb >= DB_YROWS ? hb - DB_YROWS : hb;
+        hbo = ring_fwd(hbo, 2 * SR);
     }
     fold(parts == 1 ? 3 : 0);
     __syncthreads();

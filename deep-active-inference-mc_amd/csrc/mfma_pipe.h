@@ -62,6 +62,15 @@ __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
     return r;
 }
 
+// Wave priority around the MFMA groups of the decoder contractions (k_dec_b4's strip loop, f22_l2, wino_l1).  A SIMD holds two waves of
+// these kernels; while one streams MFMAs (one issue slot per 32 or 64 cycles) a VALU instruction of the other costs ~19 cycles of wave time
+// against ~3 alone.  The non-matrix section of a step -- fragment and pixel requests, views, the temporaries' adds, the gather piece -- runs
+// at priority 1 and drops to 0 in front of the step's MFMA group: the section ends sooner, the partner's MFMA stream loses an issue slot
+// now and then, and the two waves are less often outside an MFMA group at the same time.  (The inverse polarity, priority on the MFMA
+// groups, measured no gain: profiles/HISTORY.md.)  s_setprio is scalar and ignores EXEC: call these from uniform code only.
+__device__ __forceinline__ void prio_nonmatrix() { __builtin_amdgcn_s_setprio(1); }
+__device__ __forceinline__ void prio_matrix() { __builtin_amdgcn_s_setprio(0); }
+
 // (the epilogues' ReLU is kernels.h's relu_nan: the signed-integer maximum of the bit pattern that stood here kept a positive-signed NaN
 //  and turned a negative-signed one into 0)
 
