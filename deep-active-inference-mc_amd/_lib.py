@@ -6,21 +6,16 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('EFE_LIB_PATH') or os.path.join(HERE, 'libefe_mi355x.so')    # override: A/B of kernel builds
 
-EXPORTS = ['efe_create', 'efe_destroy', 'efe_last_error', 'efe_abi_version', 'efe_set_weight', 'efe_commit_weights',
-           'efe_set_option', 'efe_transition', 'efe_decoder', 'efe_encoder', 'efe_habit', 'efe_calculate_g',
-           'efe_rollout', 'efe_trajectory', 'efe_simulate', 'efe_action_posterior', 'efe_last_call_macs',
-           'efe_prof_enable', 'efe_prof_classes', 'efe_prof_read', 'efe_env_reset', 'efe_env_step', 'efe_env_render',
-           'efe_check_reward', 'efe_reparameterize', 'efe_mcts_select', 'efe_mcts_expand', 'efe_mcts_backprop', 'efe_mcts_stop',
-           'efe_build_id', 'efe_reserve', 'efe_rollout_scratch_bytes', 'efe_arena_stats', 'efe_env_new_image', 'efe_create_cfg', 'efe_get_config', 'efe_get_device', 'efe_ctx_alive',
-           'efe_calculate_g_rows', 'efe_simulate_rows', 'efe_mcts_step',
-           'efe_free_energy', 'efe_loss_top', 'efe_loss_mid', 'efe_loss_down',
-           'efe_param_count', 'efe_get_weights', 'efe_top_grad', 'efe_adam_step', 'efe_train_top',
-           'efe_mid_grad', 'efe_train_mid', 'efe_dec_tail_grad', 'efe_dec_grad', 'efe_enc_grad', 'efe_down_grad',
-           'efe_train_down', 'efe_down_adam_step', 'efe_down_get_weights', 'efe_train_step', 'efe_eval_stats',
-           'efe_encoder_rows', 'efe_rollout_rows', 'efe_agent_need', 'efe_agent_choose', 'efe_agent_enqueue', 'efe_agent_act',
-           'efe_agent_mcts_root', 'efe_agent_mcts_enqueue', 'efe_eval_mi',
-           'efe_agent_trace_tick', 'efe_agent_trace_decision', 'efe_agent_plan_mask', 'efe_agent_view']
 ABI_VERSION = 6
+
+
+def ptr(t):
+    """the address of a tensor's data as the C ABI takes it; None is NULL"""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+class EfeRows(C.Structure):
+    _fields_ = [('mask', C.c_void_p), ('ids', C.c_void_p), ('rows_per_entry', C.c_int32), ('n_total', C.c_int32)]
 
 
 class EfeMctsTree(C.Structure):
@@ -88,12 +83,14 @@ class EfeEvalIn(C.Structure):
 
 # efe_eval_mi (include/efe_engine.h): the [60] table of mutual-information scores, latent-major
 EFE_EVAL_MI, EFE_EVAL_MI_MAX_NEIGHBORS = 60, 4
-EVAL_MI_IN_FIELDS = ('s0', 'S_real', 'noise', 'n_neighbors', 'seed', 'stage')
 
 
 class EfeEvalMiIn(C.Structure):
     _fields_ = [('s0', C.c_void_p), ('S_real', C.c_void_p), ('noise', C.c_void_p), ('n_neighbors', C.c_int32), ('seed', C.c_uint64),
                 ('stage', C.c_uint32)]
+
+
+EVAL_MI_IN_FIELDS = tuple(f for f, _ in EfeEvalMiIn._fields_)
 
 
 class EfeStepIn(C.Structure):
@@ -106,6 +103,102 @@ class EfeStepAdam(C.Structure):
 
 class EfeStepOut(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in STEP_OUT_FIELDS]
+
+
+# the struct of include/efe_engine.h each class above mirrors (tests/test_abi.py compiles the header and compares every size and offset)
+STRUCTS = {'efe_rows': EfeRows, 'efe_noise': EfeNoise, 'efe_agent': EfeAgent, 'efe_mcts_tree': EfeMctsTree, 'efe_agent_trace': EfeAgentTrace,
+           'efe_fe_params': EfeFeParams, 'efe_fe_out': EfeFeOut, 'efe_adam_params': EfeAdamParams, 'efe_step_in': EfeStepIn,
+           'efe_step_adam': EfeStepAdam, 'efe_step_out': EfeStepOut, 'efe_eval_in': EfeEvalIn, 'efe_eval_mi_in': EfeEvalMiIn}
+
+# Every prototype of include/efe_engine.h as name: (restype, argtypes), in the header's order; load() applies it and tests/test_abi.py holds
+# it to the header argument by argument.  _p: the context, the stream and every device or host array; a struct pointer is POINTER(its mirror).
+_p, _i, _f, _l, _s = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_char_p
+_nz, _rows, _ag, _tp, _tr = C.POINTER(EfeNoise), C.POINTER(EfeRows), C.POINTER(EfeAgent), C.POINTER(EfeMctsTree), C.POINTER(EfeAgentTrace)
+_fp, _fo, _ap, _sa = C.POINTER(EfeFeParams), C.POINTER(EfeFeOut), C.POINTER(EfeAdamParams), C.POINTER(EfeStepAdam)
+_ip, _lp = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+SIGNATURES = {
+    'efe_create': (_i, (C.POINTER(_p), _i)),
+    'efe_create_cfg': (_i, (C.POINTER(_p), _i, _i, _i, _i, _i)),
+    'efe_get_config': (_i, (_p, _ip, _ip, _ip, _ip)),
+    'efe_get_device': (_i, (_p, _ip, _s, _i)),
+    'efe_destroy': (None, (_p,)),
+    'efe_last_error': (_s, (_p,)),
+    'efe_ctx_alive': (_i, (_p,)),
+    'efe_abi_version': (_i, ()),
+    'efe_build_id': (_s, ()),
+    'efe_set_weight': (_i, (_p, _s, _p, _lp, _i)),
+    'efe_commit_weights': (_i, (_p,)),
+    'efe_set_option': (_i, (_p, _s, _l)),
+    'efe_reserve': (_i, (_p, _l)),
+    'efe_rollout_scratch_bytes': (_l, (_p, _i, _i, _i)),
+    'efe_arena_stats': (_i, (_p, _lp, _lp, _lp)),
+    'efe_transition': (_i, (_p, _p, _p, _i, _nz, _p, _p, _p, _p, _p)),
+    'efe_decoder': (_i, (_p, _p, _i, _nz, _p, _p)),
+    'efe_encoder': (_i, (_p, _p, _i, _nz, _p, _p, _p, _p, _p)),
+    'efe_encoder_rows': (_i, (_p, _p, _i, _nz, _p, _rows, _p, _p, _p, _p)),
+    'efe_habit': (_i, (_p, _p, _i, _p, _p, _p, _p)),
+    'efe_check_reward': (_i, (_p, _p, _i, _p, _p)),
+    'efe_reparameterize': (_i, (_p, _p, _p, _i, _i, _nz, _p, _p, _p)),
+    'efe_calculate_g': (_i, (_p, _p, _p, _i, _i, _i, _nz, _p, _p, _p, _p, _p, _p, _p, _p)),
+    'efe_calculate_g_rows': (_i, (_p, _p, _p, _i, _i, _i, _nz, _p, _rows, _p, _p, _p, _p, _p, _p, _p)),
+    'efe_rollout': (_i, (_p, _p, _p, _i, _i, _i, _i, _i, _nz, _p, _p, _p, _p, _p)),
+    'efe_rollout_rows': (_i, (_p, _p, _p, _i, _i, _i, _i, _i, _nz, _p, _rows, _p, _p, _p, _p)),
+    'efe_trajectory': (_i, (_p, _p, _p, _p, _p, _p, _i, _nz, _p, _p, _p)),
+    'efe_simulate': (_i, (_p, _p, _i, _i, _i, _nz, _p, _p, _p, _p, _p, _p)),
+    'efe_simulate_rows': (_i, (_p, _p, _i, _i, _i, _nz, _p, _p, _rows, _p, _p, _p, _p)),
+    'efe_action_posterior': (_i, (_p, _p, _i, _i, _f, _p, _p, _p)),
+    'efe_env_reset': (_i, (_p, _p, _p, _i, _nz, _p)),
+    'efe_env_new_image': (_i, (_p, _p, _i, _nz, _p)),
+    'efe_env_step': (_i, (_p, _p, _p, _p, _i, _i, _nz, _p, _p)),
+    'efe_env_render': (_i, (_p, _p, _p, _p, _l, _p, _p, _i, _p)),
+    'efe_agent_need': (_i, (_p, _ag, _p, _p, _p)),
+    'efe_agent_choose': (_i, (_p, _ag, _p, _i, _i, _p, _p, _p, _i, _f, _i, _nz, _p, _p, _p, _p)),
+    'efe_agent_enqueue': (_i, (_p, _ag, _p, _i, _p, _p, _i, _i, _p)),
+    'efe_agent_act': (_i, (_p, _ag, _p, _p, _nz, _p, _p)),
+    'efe_mcts_step': (_i, (_p, _tp, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _f, _p, _f, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p)),
+    'efe_mcts_select': (_i, (_p, _tp, _p, _f, _i, _i, _p, _p, _p, _p, _p, _p, _p)),
+    'efe_mcts_expand': (_i, (_p, _tp, _p, _p, _p, _p, _p, _p)),
+    'efe_mcts_backprop': (_i, (_p, _tp, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p)),
+    'efe_mcts_stop': (_i, (_p, _tp, _p, _p, _i, _f, _p, _p)),
+    'efe_agent_mcts_root': (_i, (_p, _ag, _p, _i, _p, _i, _i, _f, _i, _i, _nz, _p, _p, _p, _p, _p, _p)),
+    'efe_agent_mcts_enqueue': (_i, (_p, _ag, _tp, _p, _i, _p, _i, _i, _p, _p, _p)),
+    'efe_agent_trace_tick': (_i, (_p, _ag, _tr, _i, _p, _p, _p)),
+    'efe_agent_trace_decision': (_i, (_p, _tr, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _f, _p, _p, _i, _p)),
+    'efe_agent_plan_mask': (_i, (_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p)),
+    'efe_agent_view': (_i, (_p, _p, _p, _p, _i, _i, _p, _p)),
+    'efe_free_energy': (_i, (_p, _p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p)),
+    'efe_loss_top': (_i, (_p, _p, _p, _i, _fo, _p)),
+    'efe_loss_mid': (_i, (_p, _p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p)),
+    'efe_loss_down': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p)),
+    'efe_param_count': (_l, (_p, _s)),
+    'efe_get_weights': (_i, (_p, _s, _p, _l, _p)),
+    'efe_top_grad': (_i, (_p, _p, _p, _i, _p, _p, _p)),
+    'efe_adam_step': (_i, (_p, _s, _p, _p, _p, _ap, _p)),
+    'efe_train_top': (_i, (_p, _p, _p, _i, _p, _p, _p, _ap, _p)),
+    'efe_mid_grad': (_i, (_p, _p, _p, _p, _p, _i, _fp, _nz, _p, _p, _p, _p, _p)),
+    'efe_train_mid': (_i, (_p, _p, _p, _p, _p, _i, _fp, _nz, _p, _p, _p, _p, _p, _ap, _p)),
+    'efe_dec_tail_grad': (_i, (_p, _p, _p, _i, _f, _f) + (_p,) * 8),
+    'efe_dec_grad': (_i, (_p, _p, _p, _i, _f, _f, _nz) + (_p,) * 12),
+    'efe_enc_grad': (_i, (_p, _p, _p, _p, _i, _nz) + (_p,) * 11),
+    'efe_down_grad': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p, _p, _p, _p)),
+    'efe_train_down': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p, _p, _ap, _p)),
+    'efe_down_adam_step': (_i, (_p, _p, _p, _p, _ap, _p)),
+    'efe_down_get_weights': (_i, (_p, _p, _l, _p)),
+    'efe_train_step': (_i, (_p, C.POINTER(EfeStepIn), _i, _fp, _nz, _sa, _sa, _sa, C.POINTER(EfeStepOut), _p)),
+    'efe_eval_stats': (_i, (_p, C.POINTER(EfeEvalIn), _i, _p, _p)),
+    'efe_eval_mi': (_i, (_p, C.POINTER(EfeEvalMiIn), _i, _p, _p, _p)),
+    'efe_last_call_macs': (_l, (_p,)),
+    'efe_prof_enable': (_i, (_p, _i)),
+    'efe_prof_classes': (_i, ()),
+    'efe_prof_read': (_i, (_p, C.POINTER(C.c_double), _lp)),
+}
+EXPORTS = list(SIGNATURES)
+
+
+def _declare(lib, names):
+    for n in names:
+        fn = getattr(lib, n)
+        fn.restype, fn.argtypes = SIGNATURES[n]
 
 
 _lib = None
@@ -149,10 +242,9 @@ def load():
     # RTLD_GLOBAL + the library's SONAME (build.py): when libefe_torch_ops.so is loaded later, its DT_NEEDED libefe_mi355x.so resolves
     # to THIS copy even if EFE_LIB_PATH points somewhere else -- the context and every hot-path op then run the same build
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    lib.efe_abi_version.argtypes = []; lib.efe_abi_version.restype = C.c_int
+    _declare(lib, ('efe_abi_version', 'efe_build_id'))        # what the two checks below call; the rest once the library is known to be this ABI
     if lib.efe_abi_version() != ABI_VERSION:
         raise ImportError(f'{LIB_PATH}: ABI version {lib.efe_abi_version()} != {ABI_VERSION} (stale build: re-run build())')
-    lib.efe_build_id.argtypes = []; lib.efe_build_id.restype = C.c_char_p
     if not os.environ.get('EFE_LIB_PATH'):
         # a shipped binary must come from the sources next to it: compare the digest compiled into it
         from . import build as _build
@@ -160,84 +252,6 @@ def load():
         if want != have:
             raise ImportError(f'{LIB_PATH} is stale: built from sources {have}, the sources here are {want}; '
                               're-run `python -c "import __graft_entry__ as g; g.build()"`')
-    p, i, f32p = C.c_void_p, C.c_int, C.c_void_p
-    nzp = C.POINTER(EfeNoise)
-    lib.efe_create.argtypes = [C.POINTER(p), i]; lib.efe_create.restype = i
-    lib.efe_get_config.argtypes = [p, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]; lib.efe_get_config.restype = i
-    lib.efe_get_device.argtypes = [p, C.POINTER(i), C.c_char_p, i]; lib.efe_get_device.restype = i
-    lib.efe_create_cfg.argtypes = [C.POINTER(p), i, i, i, i, i]; lib.efe_create_cfg.restype = i
-    lib.efe_destroy.argtypes = [p]; lib.efe_destroy.restype = None
-    lib.efe_last_error.argtypes = [p]; lib.efe_last_error.restype = C.c_char_p
-    lib.efe_set_weight.argtypes = [p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), i]; lib.efe_set_weight.restype = i
-    lib.efe_commit_weights.argtypes = [p]; lib.efe_commit_weights.restype = i
-    lib.efe_set_option.argtypes = [p, C.c_char_p, C.c_int64]; lib.efe_set_option.restype = i
-    lib.efe_transition.argtypes = [p, f32p, f32p, i, nzp, f32p, f32p, f32p, f32p, p]; lib.efe_transition.restype = i
-    lib.efe_decoder.argtypes = [p, f32p, i, nzp, f32p, p]; lib.efe_decoder.restype = i
-    lib.efe_encoder.argtypes = [p, f32p, i, nzp, f32p, f32p, f32p, f32p, p]; lib.efe_encoder.restype = i
-    lib.efe_habit.argtypes = [p, f32p, i, f32p, f32p, f32p, p]; lib.efe_habit.restype = i
-    lib.efe_calculate_g.argtypes = [p, f32p, f32p, i, i, i, nzp, f32p, f32p, f32p, f32p, f32p, f32p, f32p, p]
-    lib.efe_calculate_g.restype = i
-    lib.efe_rollout.argtypes = [p, f32p, f32p, i, i, i, i, i, nzp, f32p, f32p, f32p, f32p, p]; lib.efe_rollout.restype = i
-    lib.efe_trajectory.argtypes = [p, f32p, f32p, f32p, f32p, f32p, i, nzp, f32p, f32p, p]; lib.efe_trajectory.restype = i
-    lib.efe_simulate.argtypes = [p, f32p, i, i, i, nzp, f32p, f32p, f32p, f32p, f32p, p]; lib.efe_simulate.restype = i
-    lib.efe_reserve.argtypes = [p, C.c_int64]; lib.efe_reserve.restype = i
-    lib.efe_ctx_alive.argtypes = [p]; lib.efe_ctx_alive.restype = i
-    lib.efe_rollout_scratch_bytes.argtypes = [p, i, i, i]; lib.efe_rollout_scratch_bytes.restype = C.c_int64
-    lib.efe_arena_stats.argtypes = [p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.efe_arena_stats.restype = i
-    lib.efe_env_new_image.argtypes = [p, f32p, i, nzp, p]; lib.efe_env_new_image.restype = i
-    lib.efe_action_posterior.argtypes = [p, f32p, i, i, C.c_float, f32p, f32p, p]; lib.efe_action_posterior.restype = i
-    lib.efe_last_call_macs.argtypes = [p]; lib.efe_last_call_macs.restype = C.c_int64
-    lib.efe_prof_enable.argtypes = [p, i]; lib.efe_prof_enable.restype = i
-    lib.efe_prof_classes.argtypes = []; lib.efe_prof_classes.restype = i
-    lib.efe_prof_read.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]; lib.efe_prof_read.restype = i
-    lib.efe_env_reset.argtypes = [p, f32p, f32p, i, nzp, p]; lib.efe_env_reset.restype = i
-    lib.efe_env_step.argtypes = [p, f32p, f32p, C.c_void_p, i, i, nzp, C.c_void_p, p]; lib.efe_env_step.restype = i
-    lib.efe_env_render.argtypes = [p, f32p, f32p, C.c_void_p, C.c_int64, f32p, C.c_void_p, i, p]; lib.efe_env_render.restype = i
-    lib.efe_check_reward.argtypes = [p, f32p, i, f32p, p]; lib.efe_check_reward.restype = i
-    lib.efe_reparameterize.argtypes = [p, f32p, f32p, i, i, nzp, f32p, f32p, p]; lib.efe_reparameterize.restype = i
-    tp = C.POINTER(EfeMctsTree)
-    lib.efe_mcts_select.argtypes = [p, tp, p, C.c_float, i, i, p, p, p, p, f32p, f32p, p]; lib.efe_mcts_select.restype = i
-    lib.efe_mcts_expand.argtypes = [p, tp, p, p, p, f32p, f32p, p]; lib.efe_mcts_expand.restype = i
-    lib.efe_mcts_backprop.argtypes = [p, tp, p, p, p, p, p, f32p, i, f32p, i, f32p, p, p]; lib.efe_mcts_backprop.restype = i
-    lib.efe_mcts_stop.argtypes = [p, tp, p, p, i, C.c_float, p, p]; lib.efe_mcts_stop.restype = i
-    lib.efe_mcts_step.argtypes = [p, tp, p, p, f32p, i, f32p, f32p, p, p, p, i, C.c_float, p, C.c_float, i, i, p, p, p, p, f32p, f32p, p, f32p, f32p, p]; lib.efe_mcts_step.restype = i
-    fpp, fop = C.POINTER(EfeFeParams), C.POINTER(EfeFeOut)
-    lib.efe_free_energy.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_free_energy.restype = i
-    lib.efe_loss_top.argtypes = [p, f32p, f32p, i, fop, p]; lib.efe_loss_top.restype = i
-    lib.efe_loss_mid.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_loss_mid.restype = i
-    lib.efe_loss_down.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, p]; lib.efe_loss_down.restype = i
-    ap = C.POINTER(EfeAdamParams)
-    lib.efe_param_count.argtypes = [p, C.c_char_p]; lib.efe_param_count.restype = C.c_int64
-    lib.efe_get_weights.argtypes = [p, C.c_char_p, f32p, C.c_int64, p]; lib.efe_get_weights.restype = i
-    lib.efe_top_grad.argtypes = [p, f32p, f32p, i, f32p, f32p, p]; lib.efe_top_grad.restype = i
-    lib.efe_adam_step.argtypes = [p, C.c_char_p, f32p, f32p, f32p, ap, p]; lib.efe_adam_step.restype = i
-    lib.efe_train_top.argtypes = [p, f32p, f32p, i, f32p, f32p, f32p, ap, p]; lib.efe_train_top.restype = i
-    lib.efe_mid_grad.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, f32p, f32p, f32p, p]; lib.efe_mid_grad.restype = i
-    lib.efe_train_mid.argtypes = [p, f32p, f32p, f32p, f32p, i, fpp, nzp, f32p, f32p, f32p, f32p, f32p, ap, p]; lib.efe_train_mid.restype = i
-    lib.efe_dec_tail_grad.argtypes = [p, f32p, f32p, i, C.c_float, C.c_float, f32p, f32p, f32p, f32p, f32p, f32p, f32p, p]; lib.efe_dec_tail_grad.restype = i
-    lib.efe_dec_grad.argtypes = [p, f32p, f32p, i, C.c_float, C.c_float, C.POINTER(EfeNoise)] + [f32p] * 11 + [p]; lib.efe_dec_grad.restype = i
-    lib.efe_enc_grad.argtypes = [p, f32p, f32p, f32p, i, nzp] + [f32p] * 10 + [p]; lib.efe_enc_grad.restype = i
-    lib.efe_down_grad.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, f32p, f32p, f32p, p]; lib.efe_down_grad.restype = i
-    lib.efe_train_down.argtypes = [p, f32p, f32p, f32p, i, fpp, nzp, f32p, fop, f32p, f32p, ap, p]; lib.efe_train_down.restype = i
-    lib.efe_down_adam_step.argtypes = [p, f32p, f32p, f32p, ap, p]; lib.efe_down_adam_step.restype = i
-    lib.efe_down_get_weights.argtypes = [p, f32p, C.c_int64, p]; lib.efe_down_get_weights.restype = i
-    sap = C.POINTER(EfeStepAdam)
-    lib.efe_train_step.argtypes = [p, C.POINTER(EfeStepIn), i, fpp, nzp, sap, sap, sap, C.POINTER(EfeStepOut), p]; lib.efe_train_step.restype = i
-    lib.efe_eval_stats.argtypes = [p, C.POINTER(EfeEvalIn), i, f32p, p]; lib.efe_eval_stats.restype = i
-    lib.efe_eval_mi.argtypes = [p, C.POINTER(EfeEvalMiIn), i, f32p, p, p]; lib.efe_eval_mi.restype = i
-    lib.efe_encoder_rows.argtypes = [p, f32p, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_encoder_rows.restype = i
-    lib.efe_rollout_rows.argtypes = [p, f32p, f32p, i, i, i, i, i, nzp, f32p, p, f32p, f32p, f32p, p]; lib.efe_rollout_rows.restype = i
-    agp = C.POINTER(EfeAgent)
-    lib.efe_agent_need.argtypes = [p, agp, p, p, p]; lib.efe_agent_need.restype = i
-    lib.efe_agent_choose.argtypes = [p, agp, p, i, i, f32p, f32p, f32p, i, C.c_float, i, nzp, f32p, p, f32p, p]; lib.efe_agent_choose.restype = i
-    lib.efe_agent_enqueue.argtypes = [p, agp, p, i, p, p, i, i, p]; lib.efe_agent_enqueue.restype = i
-    lib.efe_agent_act.argtypes = [p, agp, f32p, f32p, nzp, p, p]; lib.efe_agent_act.restype = i
-    lib.efe_agent_mcts_root.argtypes = [p, agp, p, i, f32p, i, i, C.c_float, i, i, nzp, f32p, p, p, p, f32p, p]; lib.efe_agent_mcts_root.restype = i
-    lib.efe_agent_mcts_enqueue.argtypes = [p, agp, C.POINTER(EfeMctsTree), p, i, p, i, i, p, p, p]; lib.efe_agent_mcts_enqueue.restype = i
-    trp = C.POINTER(EfeAgentTrace)
-    lib.efe_agent_trace_tick.argtypes = [p, agp, trp, i, f32p, f32p, p]; lib.efe_agent_trace_tick.restype = i
-    lib.efe_agent_trace_decision.argtypes = [p, trp, i, p, i, i, p, f32p, f32p, f32p, f32p, i, C.c_float, p, p, i, p]; lib.efe_agent_trace_decision.restype = i
-    lib.efe_agent_plan_mask.argtypes = [p, p, i, i, f32p, p, p, p, i, i, i, i, i, f32p, p]; lib.efe_agent_plan_mask.restype = i
-    lib.efe_agent_view.argtypes = [p, f32p, f32p, p, i, i, p, p]; lib.efe_agent_view.restype = i
+    _declare(lib, SIGNATURES)
     _lib = lib
     return lib

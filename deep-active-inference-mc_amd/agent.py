@@ -13,15 +13,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import Rows, _ptr
+from ._lib import ptr
+from .model import Rows
 
 MODES = {'ai': _lib.EFE_AGENT_AI, 't1': _lib.EFE_AGENT_T1, 't12': _lib.EFE_AGENT_T12, 'probs': _lib.EFE_AGENT_PROBS}
 METHODS = ('habit', 'ai', 't1', 't12', 'mcts')
 TAG_AGENT = 0x70
-
-
-def _i32(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class AgentState:
@@ -57,7 +54,7 @@ class AgentState:
 
     def need(self):
         """-> (ids [E] int32, count [1] int32), both on the device: ids[:count] are the games whose queue is empty, ascending"""
-        self._call(self._engine.lib.efe_agent_need, _i32(self.ids), _i32(self.count))
+        self._call(self._engine.lib.efe_agent_need, ptr(self.ids), ptr(self.count))
         return self.ids, self.count
 
     def choose(self, ids, mode, *, sum_G=None, sum_terms=None, probs=None, steps=1, temperature=1.0, repeat=1, seed=0, stage=0,
@@ -75,8 +72,8 @@ class AgentState:
         if n == 0:                                                   # no game decides (empty tensors have no address to hand over)
             return (choice, u_out) if want_u else choice
         nz = _lib.EfeNoise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage) & 0xFFFFFFFF, 0, 0, int(game_offset) & 0xFFFFFFFF)
-        self._call(e.lib.efe_agent_choose, _i32(ids), n, MODES[mode], _ptr(sum_G), _ptr(sum_terms), _ptr(probs), int(steps),
-                   C.c_float(float(temperature)), int(repeat), C.byref(nz), _ptr(u_t), _i32(choice), _ptr(u_out))
+        self._call(e.lib.efe_agent_choose, ptr(ids), n, MODES[mode], ptr(sum_G), ptr(sum_terms), ptr(probs), int(steps),
+                   C.c_float(float(temperature)), int(repeat), C.byref(nz), ptr(u_t), ptr(choice), ptr(u_out))
         return (choice, u_out) if want_u else choice
 
     def _f32(self, t, numel, name):
@@ -96,7 +93,7 @@ class AgentState:
             return
         a = torch.as_tensor(actions).to(device=e.device, dtype=torch.int32).reshape(n, -1).contiguous()
         ln = torch.as_tensor(lengths).to(device=e.device, dtype=torch.int32).reshape(n).contiguous()
-        self._call(e.lib.efe_agent_enqueue, _i32(ids), n, _i32(a), _i32(ln), int(a.shape[1]), int(jumps))
+        self._call(e.lib.efe_agent_enqueue, ptr(ids), n, ptr(a), ptr(ln), int(a.shape[1]), int(jumps))
 
     def mcts_root(self, ids, Qpi, active, decided, *, use_habit, threshold, max_depth, jumps=1, seed=0, stage=0, game_offset=0, u=None,
                   want_u=False):
@@ -119,8 +116,8 @@ class AgentState:
                 raise ValueError(f'{nm}: a contiguous uint8 device tensor of at least {n} entries is required')
         u_t = self._f32(u, n, 'u')
         nz = _lib.EfeNoise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stage) & 0xFFFFFFFF, 0, 0, int(game_offset) & 0xFFFFFFFF)
-        self._call(e.lib.efe_agent_mcts_root, _i32(ids), n, _ptr(Qpi), int(Qpi.shape[1]), 1 if use_habit else 0, C.c_float(float(threshold)),
-                   int(max_depth), int(jumps), C.byref(nz), _ptr(u_t), _i32(active), _i32(decided), _i32(choice), _ptr(u_out))
+        self._call(e.lib.efe_agent_mcts_root, ptr(ids), n, ptr(Qpi), int(Qpi.shape[1]), 1 if use_habit else 0, C.c_float(float(threshold)),
+                   int(max_depth), int(jumps), C.byref(nz), ptr(u_t), ptr(active), ptr(decided), ptr(choice), ptr(u_out))
         return (choice, u_out) if want_u else choice
 
     def mcts_enqueue(self, ids, tree, decided, max_depth, jumps=1, want_path=False):
@@ -132,7 +129,7 @@ class AgentState:
         path = torch.full((n, max(int(max_depth), 1)), -1, dtype=torch.int32, device=e.device) if want_path else None
         plen = torch.full((n,), -1, dtype=torch.int32, device=e.device) if want_path else None
         if n:
-            self._call(e.lib.efe_agent_mcts_enqueue, C.byref(tree), _i32(ids), n, _i32(decided), int(max_depth), int(jumps), _i32(path), _i32(plen))
+            self._call(e.lib.efe_agent_mcts_enqueue, C.byref(tree), ptr(ids), n, ptr(decided), int(max_depth), int(jumps), ptr(path), ptr(plen))
         return (path, plen) if want_path else None
 
     def act(self, games, stage, want_changed=False, changed_out=None):
@@ -143,7 +140,7 @@ class AgentState:
             raise ValueError(f'the agent state holds {self.E} games, the environment {games.games_no}')
         changed = changed_out if changed_out is not None else torch.empty(self.E, dtype=torch.int32, device=e.device) if want_changed else None
         nz = _lib.EfeNoise(games.seed, int(stage) & 0xFFFFFFFF, 9, 0, games.game_offset)
-        self._call(e.lib.efe_agent_act, _ptr(games.current_s), _ptr(games.last_r), C.byref(nz), _i32(changed))
+        self._call(e.lib.efe_agent_act, ptr(games.current_s), ptr(games.last_r), C.byref(nz), ptr(changed))
         return changed.bool() if want_changed else None
 
 
@@ -219,8 +216,8 @@ class AgentTrace:
     def record_tick(self, state, games, row):
         """efe_agent_trace_tick: state, last_r, action and queue_len of row `row` (after the decision, before act)"""
         e = self._engine
-        e.check(e.lib.efe_agent_trace_tick(e.ctx, C.byref(state._struct), C.byref(self._struct), int(row), _ptr(games.current_s),
-                                           _ptr(games.last_r), e.stream()))
+        e.check(e.lib.efe_agent_trace_tick(e.ctx, C.byref(state._struct), C.byref(self._struct), int(row), ptr(games.current_s),
+                                           ptr(games.last_r), e.stream()))
 
     def record_decision(self, row, ids, mode=None, *, choice=None, u=None, sum_G=None, sum_terms=None, probs=None, steps=1, temperature=1.0,
                         path=None, path_len=None):
@@ -238,9 +235,9 @@ class AgentTrace:
             if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous()):
                 raise ValueError(f'{nm}: a contiguous int32 device tensor is required')
         stride = int(path.shape[1]) if path is not None else 0
-        e.check(e.lib.efe_agent_trace_decision(e.ctx, C.byref(self._struct), int(row), _i32(ids), n, _lib.EFE_AGENT_NONE if mode is None else MODES[mode],
-                                               _i32(choice), _ptr(u), _ptr(sum_G), _ptr(sum_terms), _ptr(probs), int(steps),
-                                               C.c_float(float(temperature)), _i32(path), _i32(path_len), stride, e.stream()))
+        e.check(e.lib.efe_agent_trace_decision(e.ctx, C.byref(self._struct), int(row), ptr(ids), n, _lib.EFE_AGENT_NONE if mode is None else MODES[mode],
+                                               ptr(choice), ptr(u), ptr(sum_G), ptr(sum_terms), ptr(probs), int(steps),
+                                               C.c_float(float(temperature)), ptr(path), ptr(path_len), stride, e.stream()))
 
     def numpy(self, ticks):
         """the first `ticks` rows as numpy arrays (one download per field)"""
@@ -269,8 +266,8 @@ def plan_mask(engine, ids, state, H_act, H_len, H_active, n_iter, jumps, mask, p
         raise ValueError(f'state: a contiguous float32 tensor [{mask.shape[0]}, 7] is required')
     if ids.dtype != torch.int32 or not ids.is_contiguous() or n > H_act.shape[1]:
         raise ValueError('ids: a contiguous int32 tensor of at most as many entries as the history has slots is required')
-    engine.check(engine.lib.efe_agent_plan_mask(engine.ctx, _i32(ids), n, int(mask.shape[0]), _ptr(state), _i32(H_act), _i32(H_len), _i32(H_active),
-                                                int(n_iter), int(H_act.shape[1]), int(H_act.shape[2]), int(jumps), int(pi_dim), _ptr(mask),
+    engine.check(engine.lib.efe_agent_plan_mask(engine.ctx, ptr(ids), n, int(mask.shape[0]), ptr(state), ptr(H_act), ptr(H_len), ptr(H_active),
+                                                int(n_iter), int(H_act.shape[1]), int(H_act.shape[2]), int(jumps), int(pi_dim), ptr(mask),
                                                 engine.stream()))
 
 
@@ -298,7 +295,7 @@ def view_into(engine, frames, mask, ids, view):
         if ids is None or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.numel() != n:
             raise ValueError('ids: with a mask, a contiguous int32 tensor of one game per frame is required')
     E = int(mask.shape[0]) if mask is not None else n
-    engine.check(engine.lib.efe_agent_view(engine.ctx, _ptr(frames), _ptr(mask), _i32(ids), n, E, C.c_void_p(view.data_ptr()), engine.stream()))
+    engine.check(engine.lib.efe_agent_view(engine.ctx, ptr(frames), ptr(mask), ptr(ids), n, E, ptr(view), engine.stream()))
 
 
 def default_samples(method):
@@ -394,8 +391,7 @@ class AgentRunner:
         r = g.last_r.index_select(0, ids).contiguous()
         frames = torch.empty(n, 1, 64, 64, device=g.device)
         err = torch.empty(n, dtype=torch.int32, device=g.device)
-        e.check(e.lib.efe_env_render(e.ctx, _ptr(s), _ptr(r), C.c_void_p(g.imgs.data_ptr()), g.imgs.shape[0], _ptr(frames),
-                                     C.c_void_p(err.data_ptr()), n, e.stream()))
+        e.check(e.lib.efe_env_render(e.ctx, ptr(s), ptr(r), ptr(g.imgs), g.imgs.shape[0], ptr(frames), ptr(err), n, e.stream()))
         if bool(err.any()):
             raise ValueError(f'Error: Reward: {r[err.bool()][0].item()}')              # game_environment.py:53
         return frames
@@ -497,7 +493,7 @@ class AgentRunner:
         r = g.last_r.index_select(0, ids).contiguous()
         frames = torch.empty(n, 1, 64, 64, device=g.device)
         # (no validity flag: reading it would be a host round trip per frame; the tick's decision checks the rewards it renders)
-        e.check(e.lib.efe_env_render(e.ctx, _ptr(s), _ptr(r), C.c_void_p(g.imgs.data_ptr()), g.imgs.shape[0], _ptr(frames), C.c_void_p(0), n, e.stream()))
+        e.check(e.lib.efe_env_render(e.ctx, ptr(s), ptr(r), ptr(g.imgs), g.imgs.shape[0], ptr(frames), None, n, e.stream()))
         view_into(e, frames, self.plan_mask, ids if self.plan_mask is not None else None, tr.view[j])
 
     def run(self, ticks, fetch_trace=True):

@@ -11,7 +11,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .model import _Engine, _ptr
+from ._lib import ptr
+from .model import _Engine
 
 
 MIN_BANK_IMAGES = 3581
@@ -62,13 +63,13 @@ class Game:
         """game_environment.py:83-88: new latents for every game; accumulated reward and last_r are kept"""
         e = self._engine
         nz = self._nz(stage)
-        e.check(e.lib.efe_env_new_image(e.ctx, _ptr(self.current_s), self.games_no, C.byref(nz), e.stream()))
+        e.check(e.lib.efe_env_new_image(e.ctx, ptr(self.current_s), self.games_no, C.byref(nz), e.stream()))
 
     def randomize_environment_all(self, stage=None):
         """game_environment.py:72-75"""
         e = self._engine
         nz = self._nz(stage)
-        e.check(e.lib.efe_env_reset(e.ctx, _ptr(self.current_s), _ptr(self.last_r), self.games_no, C.byref(nz), e.stream()))
+        e.check(e.lib.efe_env_reset(e.ctx, ptr(self.current_s), ptr(self.last_r), self.games_no, C.byref(nz), e.stream()))
 
     def pi_to_action_all(self, actions, repeats=1, stage=None):
         """pi_to_action(actions[i], i, repeats) for every game (game_environment.py:154-169) -> round_changed [games] bool"""
@@ -78,8 +79,8 @@ class Game:
             raise ValueError('Invalid action')
         changed = torch.empty(self.games_no, dtype=torch.int32, device=self.device)
         nz = self._nz(stage)
-        e.check(e.lib.efe_env_step(e.ctx, _ptr(self.current_s), _ptr(self.last_r), C.c_void_p(a.data_ptr()), self.games_no, int(repeats),
-                                   C.byref(nz), C.c_void_p(changed.data_ptr()), e.stream()))
+        e.check(e.lib.efe_env_step(e.ctx, ptr(self.current_s), ptr(self.last_r), ptr(a), self.games_no, int(repeats),
+                                   C.byref(nz), ptr(changed), e.stream()))
         return changed.bool()
 
     def current_frame_nchw(self):
@@ -87,8 +88,8 @@ class Game:
         e = self._engine
         frames = torch.empty(self.games_no, 1, 64, 64, device=self.device)
         err = torch.empty(self.games_no, dtype=torch.int32, device=self.device)
-        e.check(e.lib.efe_env_render(e.ctx, _ptr(self.current_s), _ptr(self.last_r), C.c_void_p(self.imgs.data_ptr()), self.imgs.shape[0],
-                                     _ptr(frames), C.c_void_p(err.data_ptr()), self.games_no, e.stream()))
+        e.check(e.lib.efe_env_render(e.ctx, ptr(self.current_s), ptr(self.last_r), ptr(self.imgs), self.imgs.shape[0],
+                                     ptr(frames), ptr(err), self.games_no, e.stream()))
         if bool(err.any()):
             raise ValueError(f'Error: Reward: {self.last_r[err.bool()][0].item()}')      # game_environment.py:53
         return frames

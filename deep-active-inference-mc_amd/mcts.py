@@ -6,6 +6,8 @@ host-side bookkeeping (pi_dim floats per node); every network evaluation goes to
 import numpy as np
 import torch
 
+from ._lib import ptr
+
 _OPPOSITE = {4: {(0, 1), (1, 0), (2, 3), (3, 2)}, 3: {(1, 2), (2, 1)}}
 
 
@@ -328,11 +330,6 @@ class BatchedMCTS:
         e = self.model._ready()
         e.check(fn(e.ctx, self._C.byref(self._tree_now), *args, e.stream()))      # (_tree_now: all E slots, or the first n of a keyed decision)
 
-    @staticmethod
-    def _p(t):
-        import ctypes as C
-        return C.c_void_p(t.data_ptr())
-
     def _rows(self, mask, rows_per_entry):
         """the row set of an engine call of this iteration: the liveness mask (early-stopped / habit-decided episodes are skipped on the
         device) and, once episodes have been lost, only the live ones as a dense batch (self._ids, refreshed by _compact)"""
@@ -383,7 +380,7 @@ class BatchedMCTS:
     def _expand(self, nodes, mask, states_rep, stage=None, use_mask=True, defer=False):
         """ONE engine call over E x pi_dim rows (Node.expand, mcts.py:64-86); tree bookkeeping only where mask[e].  defer: the bookkeeping
         (W -= G, N += 1, children, their states) is left to the NEXT efe_mcts_step launch -> returns the (G, ps_next) tensors it needs"""
-        m, p_, A = self.model, self._p, self.pi_dim
+        m, p_, A = self.model, ptr, self.pi_dim
         ro = (self.ro * A) & 0xFFFFFFFF
         rows = self._rows(mask if use_mask else None, A)
         pi_hot = self.pi_hot
@@ -519,7 +516,7 @@ class BatchedMCTS:
             torch.set_num_threads(prev)
 
     def _run(self, frames, o_shape, history_hook=None):
-        m, E, p, A, p_ = self.model, self.E, self.p, self.pi_dim, self._p
+        m, E, p, A, p_ = self.model, self.E, self.p, self.pi_dim, ptr
         lib = m._engine.lib
         res = [None] * E
         qs0_mean, _ = m.model_down.encoder(_frames_nchw(m, frames, E, o_shape), row_offset=self.ep0)
@@ -560,7 +557,7 @@ class BatchedMCTS:
 
     def _iterate(self, tree, st_root, st0, skip, compact):
         """root expansion and the planning iterations of the first self.n slots (`tree`: the efe_mcts_tree of those slots) -> iterations run"""
-        m, E, p, A, p_ = self.model, self.E, self.p, self.pi_dim, self._p
+        m, E, p, A, p_ = self.model, self.E, self.p, self.pi_dim, ptr
         lib = m._engine.lib
         active, per_it, self._tree_now = self.active, 1 + p.simulation_repeats, tree
         self._expand(self.root_nodes, active, self.S[:self.n, 0].repeat_interleave(A, dim=0).contiguous(), stage=st_root, use_mask=skip)

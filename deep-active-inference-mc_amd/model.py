@@ -48,8 +48,7 @@ _SHAPES = layer_shapes()
 _CONVT = ('po_net.13', 'po_net.15', 'po_net.17', 'po_net.19')
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+_ptr = _lib.ptr      # (the name the tests import)
 
 
 class _Engine:
@@ -171,7 +170,7 @@ class _TrainableModule(_Module):
         self._device_newer = False
 
     def _get_weights(self, e, part, buf, P):
-        return e.lib.efe_get_weights(e.ctx, part, _ptr(buf), P, e.stream())
+        return e.lib.efe_get_weights(e.ctx, part, _lib.ptr(buf), P, e.stream())
 
     def _download(self):
         """efe_get_weights: the device master copy (flat, parameters() order) -> the host state_dict"""
@@ -252,7 +251,7 @@ class ModelDown(_TrainableModule):
     _train_part = 'down'
 
     def _get_weights(self, e, part, buf, P):
-        return e.lib.efe_down_get_weights(e.ctx, _ptr(buf), P, e.stream())
+        return e.lib.efe_down_get_weights(e.ctx, _lib.ptr(buf), P, e.stream())
 
     def __init__(self, owner):
         super().__init__(owner, 'down')
@@ -407,7 +406,7 @@ class ActiveInferenceModel:
             for part, mod in (('top', self.model_top), ('mid', self.model_mid), ('down', self.model_down)):
                 for key, t in mod._sd.items():
                     shape = (C.c_int64 * t.dim())(*t.shape)
-                    e.check(e.lib.efe_set_weight(e.ctx, f'{part}.{key}'.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()))
+                    e.check(e.lib.efe_set_weight(e.ctx, f'{part}.{key}'.encode(), _lib.ptr(t), shape, t.dim()))
             e.check(e.lib.efe_commit_weights(e.ctx))
             self._weights_dirty = False
         return e

@@ -152,6 +152,37 @@ def test_rows_none_is_the_existing_entry_point(model, frames):
     assert same(s_py, enc[0][0]) and same(m_py, enc[0][1])
 
 
+def test_ctypes_row_sets_equal_the_custom_ops(model):
+    """efe_calculate_g_rows and efe_simulate_rows through ctypes with an EfeRows (the binding's mirror of efe_rows) against ops.calculate_g
+    and ops.simulate given the same tensors: 3 entries compacted to ids [2, 0], n_total 3 -- the same C call twice, so the same bits"""
+    from daimc_amd import _lib
+    e, dev, p = model._ready(), model.device, _lib.ptr
+    gen = torch.Generator().manual_seed(5)
+    ids = torch.tensor([2, 0], dtype=torch.int32, device=dev)
+    mask = torch.ones(3, dtype=torch.uint8, device=dev)
+    nz = _lib.EfeNoise(model.seed, STAGE, 0, 0, OFFSET)
+    # calculate_G: 2 entries x pi_dim 4 rows, one sample
+    s0 = torch.randn(8, 10, generator=gen).to(dev)
+    pi0 = model.pi_one_hot.repeat(2, 1).contiguous()
+    want = e.ops.calculate_g(e.h, s0, pi0, 1, False, model._seed64(), STAGE, OFFSET, None, mask, ids, 4, 3)
+    rows = _lib.EfeRows(mask.data_ptr(), ids.data_ptr(), 4, 3)
+    got = [torch.empty_like(t) for t in want]                   # G, terms, ps1, ps1_mean, po1, t2parts
+    e.check(e.lib.efe_calculate_g_rows(e.ctx, p(s0), p(pi0), 8, 1, 0, C.byref(nz), None, C.byref(rows), *[p(t) for t in got], e.stream()))
+    assert same(got[0], want[0]) and same(got[1], want[1])
+    assert torch.isfinite(want[0]).all()
+    plain = [torch.empty_like(t) for t in want]                 # NULL: entries 0 and 1 of the batch, other noise
+    e.check(e.lib.efe_calculate_g_rows(e.ctx, p(s0), p(pi0), 8, 1, 0, C.byref(nz), None, None, *[p(t) for t in plain], e.stream()))
+    assert not same(plain[0], want[0])
+    # simulate: 2 of 3 episodes, depth 2
+    s = torch.randn(2, 10, generator=gen).to(dev)
+    want = e.ops.simulate(e.h, s, 2, False, model._seed64(), STAGE, OFFSET, None, None, None, ids, 3)
+    rows = _lib.EfeRows(None, ids.data_ptr(), 1, 3)
+    got = [torch.empty_like(t) for t in want]                   # G, pi0, Qpi0
+    e.check(e.lib.efe_simulate_rows(e.ctx, p(s), 2, 2, 0, C.byref(nz), None, None, C.byref(rows), *[p(t) for t in got], e.stream()))
+    assert same(got[0], want[0]) and same(got[1], want[1])
+    assert torch.isfinite(want[0]).all() and want[1].sum() == 4       # one-hot actions: 2 episodes x depth 2
+
+
 def test_refusals(model, frames):
     import daimc_amd
     import daimc_amd.model as M
