@@ -304,17 +304,43 @@ __device__ __forceinline__ void f22_l2_store(f32x4 (&acc)[16], const __amdgpu_bu
 
 // Four waves per image (256 VGPRs, 2 waves per SIMD).  Layer 1: 32 channels x 32 Winograd tiles per wave; layer 2: four passes of 16 channels
 // x 16 blocks (block rows 2 w, 2 w + 1) per wave.
-__global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
+// k_dec_ab: a by-value kernel argument read from the kernel-argument segment again (scalar loads), through a laundered pointer.  Both
+// bodies use about a hundred SGPRs on their own; the arguments of the one loaded once and kept through the other are SGPR spills.
+template <class T>
+__device__ __forceinline__ T karg_reload(const int kp_lo, const int kp_hi, const size_t offset) {      // kp_*: the segment's address, parked (vpark)
+    const unsigned long long base = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(kp_hi) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(kp_lo);
+    const __attribute__((address_space(4))) char* p = (const __attribute__((address_space(4))) char*)base + offset;
+    T t;
+    __builtin_memcpy(&t, reinterpret_cast<const __attribute__((address_space(4))) T*>(p), sizeof(T));      // (T's alignment: scalar loads)
+    return t;
+}
+
+// k_dec_ab: a uniform value parked in a vector register between its uses (vpark), read back as a scalar where it is needed (vscalar): both
+// bodies are short of SGPRs, not of VGPRs, and a scalar that lives through a whole image with two uses is better kept out of their way.
+__device__ __forceinline__ int vpark(int x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ int vscalar(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+// pieces lo .. hi - 1 of thread (wave w, lane index tl)'s 16 float4s of image pimg: buffer loads (uniform image base, one lane offset)
+__device__ __forceinline__ void dec_a_load_x4(f32x4 (&pf)[16], const float* x4, const int pimg, const int w, const int tl, const int lo, const int hi) {
+    const __amdgpu_buffer_rsrc_t xr = wrsrc(x4 + (size_t)pimg * 16384);
+#pragma unroll
+    for (int it = 0; it < 16; ++it)     // (it & 3: the load's immediate offset; three scalar offsets instead of fifteen)
+        if (it >= lo && it < hi) pf[it] = __builtin_bit_cast(f32x4, wfrag(xr, (unsigned)(w * 16384 + (tl & 63) * 16 + (it & 3) * 1024), (size_t)(it >> 2) * 256));
+}
+
+// The persistent image loop of k_dec_a, shared with k_dec_ab (FUSED), which carries every image on through k_dec_b4's body: there y2 goes to the
+// workgroup's own slot a.y2 + blockIdx.x * 64 Ki floats, tail(img, nimg, pf) runs behind a live image's y2 stores (it requests the next image's
+// x4 itself) and, as its LDS aliases this one's, the zero row is written again for every image.
+template <bool FUSED, class Tail>
+__device__ __forceinline__ void dec_a_loop(const DecAArgs& a_, float4* const sm, Tail&& tail, const int kp_lo = 0, const int kp_hi = 0) {
+    const DecAArgs& a = a_;
     constexpr int NTHR = 256;
     constexpr int NPH = 2048 / NTHR;                  // float4s per thread of each image half
     constexpr int NPE = 8;                            // float4s of the next image requested ahead of layer 2, the others behind its last contraction
-    extern __shared__ __attribute__((aligned(16))) float4 sm[];        // [273 pixels][DA_PS slots]; pixels 256 .. 272 = zeros
+    // sm: [273 pixels][DA_PS slots]; pixels 256 .. 272 = zeros
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    const float4* W1 = reinterpret_cast<const float4*>(a.w1);
-    const float4* W2 = reinterpret_cast<const float4*>(a.w2);
+    const int w_ = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     if ((int)blockIdx.x >= a.rows) return;
     // Image schedule: the first two images of a workgroup are static (blockIdx, blockIdx + grid), the rest are claimed from a
@@ -330,32 +356,46 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
     {
         const f32x4* X = reinterpret_cast<const f32x4*>(a.x4) + (size_t)blockIdx.x * 4096;
 #pragma unroll
-        for (int it = 0; it < 2 * NPH; ++it) pf[it] = X[w * 1024 + it * 64 + lane];      // wave w: pixels 64 w .. 64 w + 63 (16 KiB contiguous)
+        for (int it = 0; it < 2 * NPH; ++it) pf[it] = X[w_ * 1024 + it * 64 + lane];      // wave w: pixels 64 w .. 64 w + 63 (16 KiB contiguous)
     }
-    for (int i = tid; i < 17 * DA_PS; i += NTHR) sm[256 * DA_PS + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (!FUSED)
+        for (int i = tid; i < 17 * DA_PS; i += NTHR) sm[256 * DA_PS + i] = make_float4(0.f, 0.f, 0.f, 0.f);
     // biases live in LDS: a global bias load inside an epilogue forces s_waitcnt vmcnt(0), i.e. waits for every store
     // issued before it (vmcnt retires in order) and serialises the whole store stream
     if (tid < 16) sm[DA_BIAS + tid] = reinterpret_cast<const float4*>(a.b1)[tid];
     else if (tid < 32) sm[DA_BIAS + tid] = reinterpret_cast<const float4*>(a.b2)[tid - 16];
 
-    for (int img = blockIdx.x; img < a.rows;) {
+    const int rows_v = FUSED ? vpark(a_.rows) : 0, bx_v = FUSED ? vpark((int)blockIdx.x) : 0;
+    if constexpr (FUSED) nimg = vpark(nimg);
+    for (int img = FUSED ? vpark((int)blockIdx.x) : (int)blockIdx.x; (FUSED ? vscalar(img) : img) < (FUSED ? vscalar(rows_v) : a_.rows);) {
+        // (k_dec_ab: the arguments read again for every image, see karg_reload; they are the first member of its argument struct)
+        DecAArgs ai;
+        if constexpr (FUSED) ai = karg_reload<DecAArgs>(kp_lo, kp_hi, 0);
+        const DecAArgs& a = FUSED ? ai : a_;
+        const float4* W1 = reinterpret_cast<const float4*>(a.w1);
+        const float4* W2 = reinterpret_cast<const float4*>(a.w2);
         // stage the 16x16x64 input image (64 KiB) into the swizzled LDS layout
         // per-image laundering of the thread index: stops hipcc hoisting ~40 loop-invariant staging / prefetch addresses out of
         // the image loop, which pushed the kernel over 256 VGPRs (spill reloads carry s_waitcnt vmcnt(0): they serialised
         // the prefetch loads and waited for every outstanding y2 store)
         int tl_ = tid; asm volatile("" : "+v"(tl_));
         const int j = tl_ & 31, h = (tl_ >> 5) & 1;
+        const int w = FUSED ? __builtin_amdgcn_readfirstlane(tl_ >> 6) : w_;      // (k_dec_ab: no scalar multiple of it kept from image to image)
         // a dead row of the call (efe_rows.mask) keeps the schedule -- barriers, ticket, the next image's prefetch -- and skips the work
-        const bool live = row_live(a.live, img);
+        // (k_dec_ab: made a scalar, so that the branches on it are uniform ones -- under a lane mask, the next image's x4 requested in the
+        // dead branch would stay live through both bodies of the live one)
+        const bool live = FUSED ? __builtin_amdgcn_readfirstlane((int)row_live(a.live, vscalar(img))) != 0 : row_live(a.live, img);
         if (live) {   // pixel 64 w + 4 it + (lane >> 4), quad lane & 15: one address register, immediate offsets
             const int sbase = (64 * w + ((tl_ >> 4) & 3)) * DA_PS + (tl_ & 15);
 #pragma unroll
             for (int it = 0; it < 2 * NPH; ++it) smv[sbase + it * 4 * DA_PS] = pf[it];
         }
+        if constexpr (FUSED)
+            for (int i = tl_; i < 17 * DA_PS; i += NTHR) sm[256 * DA_PS + i] = make_float4(0.f, 0.f, 0.f, 0.f);
         __syncthreads();
-        const int nnimg = slot[0];                     // the image after nimg (written one iteration ago)
+        const int nnimg = slot[0];                   // the image after nimg (written one iteration ago)
         int ticket = 0;
-        if (tid == 0) ticket = 2 * (int)gridDim.x + atomicAdd(a.queue, 1);     // lands during the layer-1 contraction
+        if ((FUSED ? tl_ : tid) == 0) ticket = 2 * (int)gridDim.x + atomicAdd(a.queue, 1);     // lands during the layer-1 contraction
         // ---------------- layer 1 (Winograd F(2x2, 3x3), see wino_l1): wave w owns channels 32 (w >> 1) .. + 31 of the 32 tiles
         // 32 (w & 1) .. + 31 (tile n = 8 ty + tx: tile rows 4 (w & 1) .. + 3), lane j = tile
         const int l1mt = w >> 1, l1n = 32 * (w & 1) + j;
@@ -373,7 +413,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
                 return ((unsigned)y < 16u && (unsigned)x < 16u ? y * 16 + x : 256) * DA_PS;
             });
             __syncthreads();            // every wave is done reading the input image (and slot[0])
-            if (tid == 0) slot[0] = ticket;
+            if ((FUSED ? tl_ : tid) == 0) slot[0] = ticket;
             // bias + ReLU, written back IN PLACE as the input image of layer 2 (same padded layout)
 #pragma unroll
             for (int rc = 0; rc < 4; ++rc) {
@@ -389,7 +429,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
             }
         } else {
             __syncthreads();
-            if (tid == 0) slot[0] = ticket;
+            if ((FUSED ? tl_ : tid) == 0) slot[0] = ticket;
         }
         __syncthreads();
         // ---------------- layer 2 (stride 2) by F(2, 2), see f22_l2: wave w owns block rows 2 w, 2 w + 1 (lane n = 8 (row & 1) + block
@@ -408,37 +448,40 @@ __global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
             nb.r2 = nb.xb + 32 * DA_PS;                 // (block row 7: the zero row, at the banks of a real row)
             const unsigned ln = (unsigned)(t2_ & 63) * 16u;
             const unsigned yoff = (unsigned)(((32 * bu + 2 * bv + (g >> 1)) * 2 + (g & 1)) * 16);
-            const __amdgpu_buffer_rsrc_t yr = wrsrc(a.y2 + (size_t)__builtin_amdgcn_readfirstlane(img) * (32 * 32 * 64));   // (uniform: img comes from LDS)
+            const __amdgpu_buffer_rsrc_t yr = wrsrc(a.y2 + (size_t)(FUSED ? vscalar(bx_v) : __builtin_amdgcn_readfirstlane(img)) * (32 * 32 * 64));   // (uniform: img comes from LDS)
             // the next image: NPE float4s are requested ahead of the four passes, the others behind the last contraction (layer 1 has no
             // registers for any, a pass of layer 2 for half; the last tile's stores and the image barrier cover a part of that latency, the
             // CU's other workgroup the rest).  Buffer loads (uniform image base, one lane offset; the image is clamped on the last pass:
             // unconditional loads keep pf[] in registers)
             auto load_next = [&](const int lo, const int hi) {
                 const int pimg = __builtin_amdgcn_readfirstlane(nimg < a.rows ? nimg : img);
-                const __amdgpu_buffer_rsrc_t xr = wrsrc(a.x4 + (size_t)pimg * 16384);
-#pragma unroll
-                for (int it = 0; it < 2 * NPH; ++it)     // (it & 3: the load's immediate offset; three scalar offsets instead of fifteen)
-                    if (it >= lo && it < hi) pf[it] = __builtin_bit_cast(f32x4, wfrag(xr, (unsigned)(w * 16384 + (t2_ & 63) * 16 + (it & 3) * 1024), (size_t)(it >> 2) * 256));
+                dec_a_load_x4(pf, a.x4, pimg, w, t2_, lo, hi);
             };
             if (live) {
                 f32x4 aq[F22_PD][5], acc2[16];
                 f22_l2_first(aq, wrsrc(W2), 0, ln);
-                load_next(0, NPE);
+                if constexpr (!FUSED) load_next(0, NPE);
 #pragma unroll 1
                 for (int ct = 0; ct < 4; ++ct) {
                     const f32x4 bias4 = smv[DA_BIAS + 16 + 4 * ct + g];
                     f22_l2(acc2, aq, wrsrc(W2 + ct * 256), ct < 3 ? 1 : 0, ln, bias4, smv, nb);
                     if (ct < 3) f22_l2_store(acc2, yr, yoff, ct, true);
                 }
-                load_next(NPE, 2 * NPH);
+                if constexpr (!FUSED) load_next(NPE, 2 * NPH);
                 f22_l2_store(acc2, yr, yoff, 3, true);
+                if constexpr (FUSED) tail(img, nimg, pf);      // (in this branch: every path through the image then requests pf anew)
             } else {
                 load_next(0, 2 * NPH);
             }
         }
         __syncthreads();                // every wave is done reading layer-1's image before the next one overwrites it
-        img = nimg; nimg = nnimg;
+        img = nimg; nimg = FUSED ? vpark(nnimg) : nnimg;      // (k_dec_ab: the schedule lives in vector registers, read as scalars where used)
     }
+}
+
+__global__ void __launch_bounds__(256, 2) k_dec_a(const DecAArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float4 sm[];
+    dec_a_loop<false>(a, sm, [](int, int, f32x4 (&)[16]) {});
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -572,8 +615,13 @@ void launch_dec_a(const DecAArgs& a, hipStream_t st) {
 // CONTRACTION, in pieces between its MFMA groups (a wave's VALU instructions issue in the shadow of the other wave's MFMAs).  The H-plane
 // ring holds 4 SR + 2 rows so that the next strip's planes do not overwrite rows still being gathered; the next strip's input is requested
 // behind the contraction's last weight-fragment request; the images of the deferred rows are stored after the strip barrier.
-template <int PARTS>        // 1 = one workgroup per image, 4 = four (small launches)
-__global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
+// The body of one image (dec_b_image) is shared by k_dec_b4 and by k_dec_ab, which runs it behind k_dec_a's two layers in the same workgroup:
+//   sm: the dynamic LDS (input strip + H ring); sb3 [8], sq [4 x 256], sQ [4]: the bias, the parked partial sums and the quarter sums;
+//   y2img: the image's y2 (256 KiB); FUSED: sb3 is already loaded (k_dec_ab's tables outlive the image, the zero column and the tap operand
+//   do not: the strip area aliases k_dec_a's image and no register survives its layers).
+template <int PARTS, bool FUSED>        // PARTS: 1 = one workgroup per image, 4 = four (small launches)
+__device__ __forceinline__ void dec_b_image(const DecBArgs& a, float4* const sm, float4* const sb3, float* const sq, float* const sQ,
+                                            const int img, const int qtr, const float* const y2img) {
     constexpr int SR = 4, NW = 4, NTHR = 256;
     constexpr int DB_RP = 33;                         // staged pixels per row: 32 columns + a zero column
     constexpr int DB_PS = 17;                         // float4 slots per pixel: 16 channel quads + 1 pad
@@ -582,10 +630,10 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     constexpr int NPF = (SR + 1) * 512 / NTHR;        // 10 float4s of the input strip per thread
     constexpr int NS = 32 / SR;
     constexpr int NST = 24;                           // contraction steps: 6 groups x 4 chunks of 16 channels
-    extern __shared__ __attribute__((aligned(16))) float4 sm[];
     float* sH = reinterpret_cast<float*>(sm + DB_IN_F4);       // [ring row][channel half][kh][64 output columns]
-    __shared__ float4 sb3[8];
-    const int tid = threadIdx.x;
+    // (k_dec_ab: the thread index laundered per image, so that none of this body's lane constants is formed ahead of k_dec_a's layers)
+    int tid = threadIdx.x;
+    if constexpr (FUSED) asm volatile("" : "+v"(tid));
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, v = lane & 15;
@@ -597,9 +645,6 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     // eight strips (a.parts == 1) and four workgroups walking three each produce the same bits: results stay a function of the noise
     // keys alone, whatever the launch size.
     constexpr int parts = PARTS;
-    const int img = parts == 1 ? (int)blockIdx.x : (int)(blockIdx.x >> 2);
-    const int qtr = parts == 1 ? 0 : (int)(blockIdx.x & 3);
-    if (!row_live(a.live, img)) return;                // a dead row of the call (efe_rows.mask): workgroup-uniform
     const int s_lo = parts == 1 ? 0 : (qtr ? 2 * qtr - 1 : 0);          // first strip contracted (the halo strip of quarters 1..3)
     const int s_hi = parts == 1 ? NS : 2 * qtr + 2;
 
@@ -611,10 +656,13 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     const int mode = (gp == 0 && a.reward0) ? 1 : 0;
     const int slot = (gp == 0 && a.store0) ? gt * a.gm.S + gs : -1;
     float* po = (slot >= 0) ? a.po + ((size_t)slot * a.rows_per_group + r) * 4096 : nullptr;
+    // (k_dec_ab: the image's scalars that live to its end are kept in vector registers -- k_dec_a's loop state takes their SGPRs)
+    int mode_v = mode, mg_v = mg, ri_v = a.reward_intent;
+    float* valp = a.val;
+    if constexpr (FUSED) { asm volatile("" : "+v"(po)); asm volatile("" : "+v"(valp)); mode_v = vpark(mode_v); mg_v = vpark(mg_v); ri_v = vpark(ri_v); }
 
-    __shared__ float sq[4 * NTHR];       // [quarter][thread]: the threads' partial sums of a quarter, reduced once per image
-    __shared__ float sQ[4];
-    if (tid < 8) sb3[tid] = reinterpret_cast<const float4*>(a.b3)[tid];
+    // sq: [quarter][thread], the threads' partial sums of a quarter, reduced once per image
+    if constexpr (!FUSED) { if (tid < 8) sb3[tid] = reinterpret_cast<const float4*>(a.b3)[tid]; }
     if (tid < (SR + 1) * 16) sm[((tid >> 4) * DB_RP + 32) * DB_PS + (tid & 15)] = make_float4(0.f, 0.f, 0.f, 0.f);      // the zero column
     // A operand of the 32 -> 1 conv: lane (tap row i = lane & 15 = 4 kh + kw, K row g) holds w4[kh][kw][16 hf + 4 g + rr] in w4a[rr]
     f32x4 w4a;
@@ -626,7 +674,10 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
 
     // the image's y2 through a buffer resource over exactly its 256 KiB: a row below the image is requested at an out-of-range offset
     // and the hardware returns zeros (the halo row of the last strip)
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.y2) + (size_t)img * (32 * 32 * 64), 0, 32 * 32 * 64 * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(y2img), 0, 32 * 32 * 64 * 4, 0x00020000);
+    // (k_dec_ab: the slot's address parked in two vector registers, the resource formed again for every strip)
+    const unsigned long long y2a = (unsigned long long)y2img;
+    const int y2lo_v = FUSED ? vpark((int)(unsigned)y2a) : 0, y2hi_v = FUSED ? vpark((int)(unsigned)(y2a >> 32)) : 0;
     // packed U fragments [16 matrices][2 channel halves][4 chunks][64 lanes] (engine_weights.hip): the channel half is folded into the base
     const __amdgpu_buffer_rsrc_t wr = wrsrc(a.w3 + (size_t)hf * 4 * 64 * 4);
     const unsigned ln = (unsigned)lane * 16u;
@@ -640,6 +691,8 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     // position (row >> 1, (tl & 31) >> 1), channel group 8 (it & 1) + (tl >> 5), quad tl & 1 -- a lane offset, a constant per piece and
     // 1 KiB per strip (SR = 4 rows = two rows of positions).  Row 32 (the halo of strip 7) is out of range: the lanes' offsets get bit 31.
     auto prefetch = [&](int sn, int tl) {
+        const __amdgpu_buffer_rsrc_t xr = !FUSED ? xr_ : __builtin_amdgcn_make_buffer_rsrc(
+            reinterpret_cast<float*>(((unsigned long long)(unsigned)vscalar(y2hi_v) << 32) | (unsigned)vscalar(y2lo_v)), 0, 32 * 32 * 64 * 4, 0x00020000);
         const unsigned lo = (unsigned)(((tl >> 5) * 512 + (tl & 31)) * 16);
         const unsigned lh = lo | (sn == NS - 1 ? 0x80000000u : 0u);
 #pragma unroll
@@ -703,8 +756,8 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
         const float pr = gpr[q];
         const float l1 = hw_log(D1 - pr), l0 = hw_log(D0 + pr);
         const float te = __builtin_fmaf(pr - 1.0f, l1, -(pr * l0));          // -(1 - p) ln((1e-5 + 1) - p) - p ln(1e-5 + p)
-        const float tw = reward_term(pr, oh, lane, 64, 64, a.reward_intent);
-        const float t = mode == 0 ? te : tw;
+        const float tw = reward_term(pr, oh, lane, 64, 64, ri_v);
+        const float t = mode_v == 0 ? te : tw;
         part += oh >= 0 ? t : 0.0f;
     };
     auto g_store = [&](int oh, int q) {
@@ -806,7 +859,9 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
         });
         // ---- ReLU, then the 32 -> 1 conv as tap planes (4 v_mfma_f32_16x16x4_f32 per output position, the four columns' chains
         // interleaved) and the horizontal presums of this channel half, one y3 row at a time
-        prefetch((s < NS - 1) ? s + 1 : NS - 1, tl);     // the next strip's input, behind this strip's last weight-fragment request
+        // the next strip's input, behind this strip's last weight-fragment request (k_dec_b4 requests the last strip's own input again,
+        // which keeps pf[] unconditional; k_dec_ab does not: its slot is about to be written again)
+        if (!(FUSED && s == NS - 1)) prefetch((s < NS - 1) ? s + 1 : NS - 1, tl);
         // Skewed by one row: a row's MFMAs share their scheduling region with the NEXT row's ReLUs and the PREVIOUS row's presums, so
         // that no instruction of the region waits for an MFMA result of the same region (a ReLU sunk in front of the MFMA that reads it
         // costs two hazard wait states, a presum right behind its row's last MFMA ten).  The barrier keeps the ReLUs a block ahead.
@@ -867,16 +922,72 @@ __global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
     }
     __syncthreads();
     if (tid == 0) {
-        if (parts == 1) a.val[mg] = add1(add1(sQ[0], sQ[1]), add1(sQ[2], sQ[3]));
+        if (parts == 1) valp[mg_v] = add1(add1(sQ[0], sQ[1]), add1(sQ[2], sQ[3]));
         else a.valq[(size_t)mg * 4 + qtr] = sQ[0];          // summed in the same association by the consumer (k_terms)
     }
 }
 
+template <int PARTS>
+__global__ void __launch_bounds__(256, 2) k_dec_b4(const DecBArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float4 sm[];
+    __shared__ float4 sb3[8];
+    __shared__ float sq[4 * 256];
+    __shared__ float sQ[4];
+    const int img = PARTS == 1 ? (int)blockIdx.x : (int)(blockIdx.x >> 2);
+    const int qtr = PARTS == 1 ? 0 : (int)(blockIdx.x & 3);
+    if (!row_live(a.live, img)) return;                // a dead row of the call (efe_rows.mask): workgroup-uniform
+    dec_b_image<PARTS, false>(a, sm, sb3, sq, sQ, img, qtr, a.y2 + (size_t)img * (32 * 32 * 64));
+}
+
 constexpr size_t DB_LDS4D = ((5 * 33) * 17) * sizeof(float4) + 18 * 2 * 3 * 64 * sizeof(float);  // input strip (+ zero column) + H planes per channel half (4 SR + 2 rows)
+
+// ---------------------------------------------------------------------------------------------------------
+// k_dec_ab: k_dec_a and k_dec_b4<1> as ONE persistent launch (engine option dec_fuse_ab).  A workgroup takes its images as k_dec_a does
+// (two static, then tickets) and carries each one through both bodies: the two layers of dec_a_loop write y2 into the workgroup's own
+// 256 KiB slot (a.a.y2 + blockIdx.x * 64 Ki floats, today's layout), and dec_b_image walks its eight strips over that slot.  The hand-over
+// is a release / acquire at workgroup scope and nothing more: every wave retires its y2 stores (s_waitcnt vmcnt(0)), then the workgroup
+// barrier; the waves share one CU and one vector L1, so no cache is written back or invalidated, and no workgroup ever waits for
+// another (the ticket counter stays the only shared word).  Every output element sees the operations of the two kernels in the same order.
+// LDS: k_dec_a's region [0, DA_LDS_BYTES) with k_dec_b4's dynamic region aliased onto its image and zero row (the two layers' biases and the
+// ticket slot lie behind it and survive), then k_dec_b4's static arrays: 79 024 bytes, two workgroups per CU.  Per image the zero row
+// (dec_a_loop), the zero column and the tap operand (dec_b_image) are formed again; the ConvT3 bias is loaded once.
+// The next image's x4 is requested behind body b's reduction, the last point of the image: requested anywhere inside the last strip
+// (behind its contraction, its tap conv, its barrier or its gather) hipcc spills 89 - 140 VGPRs of it, although fewer than 200 are live
+// there.  The image barrier, the zero row and the CU's other workgroup cover the latency; no register holds x4 through a contraction.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int DAB_SB3 = DA_BIAS + 33, DAB_SQ = DAB_SB3 + 8, DAB_SQQ = DAB_SQ + 256;       // float4 indices behind k_dec_a's region
+constexpr size_t DAB_LDS_BYTES = (DAB_SQQ + 1) * sizeof(float4);
+static_assert(DB_LDS4D <= DA_BIAS * sizeof(float4), "k_dec_b4's strips and ring must not reach k_dec_a's biases and ticket slot");
+static_assert(DAB_LDS_BYTES <= 80 * 1024, "two workgroups of k_dec_ab per CU");
+__global__ void __launch_bounds__(256, 2) k_dec_ab(const DecABArgs a) {
+    __shared__ __attribute__((aligned(16))) float4 sm[DAB_SQQ + 1];      // static: every region's address is a constant of the instructions
+    float4* const sb3 = sm + DAB_SB3;
+    float* const sq = reinterpret_cast<float*>(sm + DAB_SQ);
+    float* const sQ = reinterpret_cast<float*>(sm + DAB_SQQ);
+    if (threadIdx.x < 8) sb3[threadIdx.x] = reinterpret_cast<const float4*>(a.b.b3)[threadIdx.x];      // (read behind the first image's barriers)
+    const unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    const int kp_lo = vpark((int)(unsigned)kp), kp_hi = vpark((int)(unsigned)(kp >> 32));      // (see karg_reload)
+    dec_a_loop<true>(a.a, sm, [&](const int img, const int nimg, f32x4 (&pf)[16]) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's y2 stores have reached the cache the workgroup shares ...
+        __syncthreads();                                        // ... and every wave's; layer 2 is done reading the image the strips alias
+        const DecBArgs b = karg_reload<DecBArgs>(kp_lo, kp_hi, __builtin_offsetof(DecABArgs, b));
+        dec_b_image<1, true>(b, sm, sb3, sq, sQ, __builtin_amdgcn_readfirstlane(img), 0, b.y2 + (size_t)vscalar(vpark((int)blockIdx.x)) * (32 * 32 * 64));
+        const DecAArgs an = karg_reload<DecAArgs>(kp_lo, kp_hi, 0);
+        int tl = threadIdx.x; asm volatile("" : "+v"(tl));
+        const int pimg = __builtin_amdgcn_readfirstlane(nimg < an.rows ? nimg : img);
+        dec_a_load_x4(pf, an.x4, pimg, __builtin_amdgcn_readfirstlane(tl >> 6), tl, 0, 16);
+    }, kp_lo, kp_hi);
+}
+
 int init_dec_b_kernels() {
     if (hipFuncSetAttribute((const void*)k_dec_b4<1>, hipFuncAttributeMaxDynamicSharedMemorySize, DB_LDS4D) != hipSuccess) return 1;
     if (hipFuncSetAttribute((const void*)k_dec_b4<4>, hipFuncAttributeMaxDynamicSharedMemorySize, DB_LDS4D) != hipSuccess) return 1;
     return 0;
+}
+
+int dec_ab_grid(int rows, int cap) { const int g = rows < 512 ? rows : 512; return cap > 0 && cap < g ? cap : g; }
+void launch_dec_ab(const DecABArgs& a, int grid_cap, hipStream_t st) {
+    hipLaunchKernelGGL(k_dec_ab, dim3(dec_ab_grid(a.a.rows, grid_cap)), dim3(256), 0, st, a);      // (its LDS is static)
 }
 
 void launch_dec_b(const DecBArgs& a, hipStream_t st) {

@@ -129,6 +129,9 @@ struct efe_ctx {
     int64_t enc_tiled = 2;         // generic path, encoder layers 1 and 2: 2 = one kernel, conv1 kept in LDS (k_conv_e12); 1 = LDS-tiled, one launch per layer
                                    // (k_conv_e); 0 = k_conv_g for every layer (A/B, parity of the fallbacks)
     int64_t dec_split = 1;         // dSprites path: decoder launches of <= 128 images run k_dec_b4 with four workgroups per image (0 = never: A/B)
+    int64_t dec_fuse_ab = 1;       // dSprites path, fp32 launches of > 128 images: 1 = k_dec_a and k_dec_b4 as one persistent launch, k_dec_ab, y2 in one 256 KiB slot
+                                   // per workgroup (engine_forward.hip dec_fused); 0 = two launches, y2 for every image of a launch group
+    int64_t dec_ab_grid = 0;       // cap of k_dec_ab's grid (0 = min(512, images)): lets a small launch give every workgroup several images (tests)
     int64_t fuse_final_g = 1;      // generic path: last two decoder layers in one kernel (k_dec_bg); 0 = separate launches (A/B, parity tests of k_final_g)
     // OPT-IN EXPERIMENTS (bf16x3.hip): the decoder's Linear(256, 16384) and three large ConvTranspose2d layers on the 16-bit matrix pipe with
     // split operands.  mfma_bf16x3 holds the MODE: 0 = off (exact fp32, the default), 1 = three bf16 planes / six products (option

@@ -159,6 +159,8 @@ int efe_set_option(efe_ctx* ctx, const char* name, int64_t value) {
     if (!strcmp(name, "enc_tiled")) { ctx->enc_tiled = value < 0 ? 0 : value > 2 ? 2 : value; return 0; }
     if (!strcmp(name, "fuse_final_g")) { ctx->fuse_final_g = value ? 1 : 0; return 0; }
     if (!strcmp(name, "dec_split")) { ctx->dec_split = value ? 1 : 0; return 0; }
+    if (!strcmp(name, "dec_fuse_ab")) { ctx->dec_fuse_ab = value ? 1 : 0; return 0; }
+    if (!strcmp(name, "dec_ab_grid")) { if (value < 0) return ctx->fail("dec_ab_grid < 0"); ctx->dec_ab_grid = value; return 0; }
     if (!strcmp(name, "dec_budget_g")) { if (value < (1 << 20)) return ctx->fail("dec_budget_g < 1 MiB"); ctx->dec_budget_g = value; return 0; }
     if (!strcmp(name, "dec_chunk_g")) { if (value < 1) return ctx->fail("dec_chunk_g < 1"); ctx->dec_chunk_g = value; return 0; }
     if (!strcmp(name, "poison")) { ctx->poison = value; return 0; }

@@ -111,10 +111,19 @@ size_t plan_bytes(const efe_ctx* c, const DecGPlan& p) { return arena_bytes(c, {
 // dSprites decoder: launches of at most this many images split every image over four workgroups in k_dec_b4 (per-image sums as quarters, valq)
 constexpr int DEC_SPLIT_MAX = 128;
 inline bool dec_split(const efe_ctx* ctx, int64_t N) { return !ctx->generic && ctx->dec_split && N <= DEC_SPLIT_MAX; }
-struct DecPlan { int C; bool split; size_t hA, hB, x4, y2, queues; };       // queues: one image-ticket counter (int) per k_dec_a launch
+// Option dec_fuse_ab: the large-launch fp32 kernels k_dec_a and k_dec_b4<1> as one persistent launch, k_dec_ab, whose workgroups keep y2 in
+// a slot of their own (DecPlan::grid slots of 256 KiB instead of one per image of a launch group).  A fused launch has no boundary between
+// the profiling classes dec_a_convT1_convT2 and dec_b_convT3_final_reduce: while either is being timed, the call runs the two launches.
+inline bool dec_fused(const efe_ctx* ctx, int64_t N) {
+    return !ctx->generic && ctx->dec_fuse_ab && !dec_split(ctx, N) && !ctx->mfma_bf16x3 && !(ctx->prof & ((1u << PROF_CT2) | (1u << PROF_CT3)));
+}
+struct DecPlan { int C; bool split, fused; int grid; size_t hA, hB, x4, y2, queues; };       // queues: one image-ticket counter (int) per k_dec_a / k_dec_ab launch
 DecPlan dec_plan(const efe_ctx* ctx, int64_t N) {
     const int64_t C = std::min<int64_t>(ctx->dec_chunk, N);
-    return {(int)C, dec_split(ctx, N), (size_t)N * 256, (size_t)N * 256, (size_t)C * 16384, (size_t)C * 65536, (size_t)((N + C - 1) / C)};
+    const bool fused = dec_fused(ctx, N);
+    const int grid = fused ? dec_ab_grid((int)C, (int)ctx->dec_ab_grid) : 0;
+    return {(int)C, dec_split(ctx, N), fused, grid, (size_t)N * 256, (size_t)N * 256, (size_t)C * 16384, (size_t)(fused ? grid : C) * 65536,
+            (size_t)((N + C - 1) / C)};
 }
 size_t plan_bytes(const efe_ctx* c, const DecPlan& p) { return arena_bytes(c, {p.hA, p.hB, p.x4, p.y2, p.queues}); }
 
@@ -319,7 +328,7 @@ int run_mid(efe_ctx* ctx, const float* X, int x_mod, int M, float* tr /*[M][32]*
 
 // ModelDown.po_net over N rows ([group][row] batch): the three small dense layers run once over all rows, then per
 // chunk: dense 256->16384 (+dropout) -> k_dec_a (two transposed convs through LDS) -> k_dec_b (third transposed conv,
-// final conv, sigmoid and the per-image reduction, all on chip).
+// final conv, sigmoid and the per-image reduction, all on chip); under dec_fuse_ab the last two as one launch, k_dec_ab (dec_fused).
 int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const NoiseCfg& nc, int reward0, int store0,
                 float* val /*[N], or [N][4] quarter sums when dec_split(ctx, N)*/, float* po_store, hipStream_t st) {
     if (ctx->generic) return run_decoder_g(ctx, dec_in, N, nc, reward0, store0, val, po_store, st);
@@ -355,6 +364,18 @@ int run_decoder(efe_ctx* ctx, const float* dec_in /*[N][16]*/, int N, const Nois
     for (int m0 = 0; m0 < N; m0 += C) {
         const int c = std::min(C, N - m0);
         fc(ctx, PROF_DEC_FC4, ctx->dec_fc[3], hA + (size_t)m0 * 256, 256, 0, x4, 16384, c, true, true, TAG_DEC + 3, nc, m0, st, fc4_16);
+        if (p.fused) {       // one launch: y2 stays in the workgroups' slots
+            DecABArgs ab{};
+            DecAArgs& da = ab.a; DecBArgs& db = ab.b;
+            da.x4 = x4; da.y2 = y2; da.w1 = ctx->dec_ct[0].Wp; da.b1 = ctx->dec_ct[0].bias; da.w2 = ctx->dec_ct[1].Wp;
+            da.b2 = ctx->dec_ct[1].bias; da.rows = c; da.live = live_of(nc, m0); da.queue = queues + m0 / C; da.parts = 1;
+            db.y2 = y2; db.w3 = ctx->dec_ct[2].Wp; db.b3 = ctx->dec_ct[2].bias; db.w4 = ctx->dec_wf; db.b4 = ctx->dec_bf;
+            db.rows = c; db.live = da.live; db.m0 = m0; db.rows_per_group = nc.rows_per_group; db.gm = nc.gm; db.reward0 = reward0; db.store0 = store0;
+            db.val = val; db.parts = 1; db.valq = nullptr; db.po = po_store; db.reward_intent = (int)ctx->reward_intent;
+            ProfSpan span(ctx, PROF_CT2, st);      // (never timed: see dec_fused)
+            launch_dec_ab(ab, (int)ctx->dec_ab_grid, st);
+            continue;
+        }
         DecAArgs da{};
         da.x4 = x4; da.y2 = y2; da.w1 = ctx->dec_ct[0].Wp; da.b1 = ctx->dec_ct[0].bias; da.w2 = ctx->dec_ct[1].Wp;
         da.b2 = ctx->dec_ct[1].bias; da.rows = c; da.live = live_of(nc, m0); da.queue = queues + m0 / C; da.parts = split ? 8 : 1;

@@ -214,6 +214,10 @@ float pack_convt3_split(int mode, const float* W_cicokk, uint16_t* dst);      //
 int init_bf16x3_kernels();
 void launch_dec_a(const DecAArgs& a, hipStream_t st);
 void launch_dec_b(const DecBArgs& a, hipStream_t st);
+// both stages in one persistent launch (k_dec_ab: parts 1 only): a.y2 = b.y2 is [grid][32 x 32 x 64], one slot per workgroup
+struct DecABArgs { DecAArgs a; DecBArgs b; };
+int dec_ab_grid(int rows, int cap);      // workgroups of a launch of `rows` images: min(512, rows), capped at `cap` when cap > 0
+void launch_dec_ab(const DecABArgs& a, int grid_cap, hipStream_t st);
 
 int launch_dense(int MT, int NT, const GemmArgs& a, hipStream_t st);   // 0 = launched, 1 = unsupported tile shape
 

@@ -88,7 +88,12 @@ int efe_commit_weights(efe_ctx* ctx);
  *                   kernel with conv1 kept in LDS (default), 1 = LDS-tiled, one launch per layer, 0 = the direct kernel for every layer; bit-identical),
  *                   "ct_fuse12" (generic path: the decoder's first two ConvTranspose layers in one kernel, layer 1's output kept in LDS, default 1,
  *                   bit-identical to 0), "mid_unfused" (layer-by-layer transition MLP), "head_unfused" (the decoder / encoder dense heads as
- *                   one k_dense launch per layer instead of one k_head launch per head; same masks, fp32 summation order differs).  None of them removes work:
+ *                   one k_dense launch per layer instead of one k_head launch per head; same masks, fp32 summation order differs),
+ *                   "dec_fuse_ab" (Dynamic dSprites, fp32 decoder launches of > 128 images: 1 = the two decoder tail kernels as one persistent
+ *                   launch whose workgroups keep the activation between them in a 256 KiB slot each, 128 MiB of scratch instead of 256 KiB per
+ *                   image of a launch group (default); 0 = two launches; bit-identical.  While efe_prof_enable times either decoder tail class
+ *                   the call runs the two launches: one launch has no boundary between the classes), "dec_ab_grid" (cap of that launch's grid,
+ *                   0 = min(512, images): lets a small launch give every workgroup several images; tests).  None of them removes work:
  *                   every setting computes the same quantities (fp32 summation order may differ where stated).
  *   experiment    : "mfma_bf16x3" (0 / 1, default 0; Dynamic-dSprites geometry only).  1 = the decoder's Linear(256, 16384) and its first two
  *                   ConvTranspose layers run on the bf16 matrix pipe with both operands split into three bf16 planes (six products per fp32
