@@ -180,7 +180,10 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
                 x = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, v.w, x, 0, 0, 0);
                 prio_nonmatrix();
             }
-            // the xi's output transform (a second accumulator to overlap it with the next xi's MFMAs does not fit the register budget)
+            // the xi's output transform, behind its last MFMA.  (A second accumulator, with this transform spread over the next xi's
+            // chunks, fits all three kernels -- 244 / 219 / 252 VGPRs, unchanged -- and was measured in k_dec_ab: the same cycles
+            // within the parent's own spread, profiles/r14_overlap_items.txt.  The drain is 16 x 64 cycles per image and the partner
+            // wave fills most of it; what layer 1 pays for is the number of non-matrix instructions: see wino_l1_rows.)
             otrans(a, b, xacc, mask);
         }
     };
@@ -193,6 +196,93 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
 #pragma unroll 1
         for (int a = a_lo; a < a_hi; ++a) xi_row(a, std::integral_constant<int, 1>{});
     }
+}
+// k_dec_ab's form of layer 1 (NR = 2, R0 = 0): the four xi (a, 0..3) of a row are contracted TOGETHER, chunk by chunk, into four
+// accumulators.  They share their row transform: per chunk the two input rows wino_i0(a), wino_i1(a) are read once for the tile's four
+// columns (8 LDS reads where four xi on their own take 16) and col[j] = d[i0][j] + s1 d[i1][j] is formed once (16 + 4 x 4 fmas where
+// they take 4 x 12); xi (a, b)'s fragment is col[j0] + t1 col[j1], which is (d00 + s1 d10) + t1 (d01 + s1 d11) as in wino_l1, operation
+// for operation.  Every xi-GEMM still runs over chunks 0..7 on its own accumulator and the output transforms follow in ascending xi at
+// the row's end, so an output element sees what it sees in wino_l1: the same bits.  The 48 more accumulator registers and 16 more of
+// raw pixels are there in k_dec_ab alone, whose next image is not in flight during layer 1 (k_dec_a: 244 VGPRs beside its prefetch).
+template <class Pix>
+__device__ __forceinline__ void wino_l1_rows(f32x16 (&out)[2][2], const float4* __restrict__ U, const float4* sm, const int h,
+                                             const int mt_, Pix pix) {
+    const unsigned ln = (threadIdx.x & 63u) * 16u;
+    const __amdgpu_buffer_rsrc_t ur = wrsrc(U);
+    int mt = mt_; asm volatile("" : "+s"(mt));              // (laundered per call, as in wino_l1)
+    auto ufrag = [&](int a, int b, int kc) { return wfrag(ur, ln, (size_t)(((4 * a + b) * 2 + mt) * 8 + kc) * 64); };
+    auto bases = [&](int a, int (&pb)[8]) {                 // d[i0][0..3], d[i1][0..3] of xi row a
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) { pb[jj] = pix(wino_i0(a), jj); pb[4 + jj] = pix(wino_i1(a), jj); }
+    };
+    float4 aq[4], raw[8];                                   // the A fragments (one chunk of the four xi ahead) and the raw pixels of the next chunk
+    int pb[8];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) aq[b] = ufrag(0, b, 0);
+    bases(0, pb);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) raw[q] = sm[pb[q] + h];
+    f32x16 xacc[4];
+    const f32x16 zero = {};
+    auto fma4 = [](float s, const float4& x, const float4& y) {          // y + s x per component (s = +-1: exactly y +- x)
+        return make_float4(__builtin_fmaf(s, x.x, y.x), __builtin_fmaf(s, x.y, y.y), __builtin_fmaf(s, x.z, y.z), __builtin_fmaf(s, x.w, y.w));
+    };
+    auto otrans = [&](int a, int b, const f32x16& m, auto mask) {       // (wino_l1's, for NR = 2, R0 = 0)
+        constexpr int MASK = decltype(mask)::value;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (!((MASK >> r) & 1)) continue;
+            const float car = wino_at(r, a);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const float cbc = wino_at(c, b);
+                if (cbc == 0.0f) continue;
+                const float cf = car * cbc;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) out[r][c][e] = __builtin_fmaf(cf, m[e], out[r][c][e]);
+            }
+        }
+    };
+    auto xi_row = [&](int a, auto mask) {
+        const float s1 = wino_s1(a);
+        const int an = a + 1 < 4 ? a + 1 : a;              // the next xi row (the last one re-reads its own fragments: never used)
+#pragma unroll
+        for (int kc = 0; kc < 8; ++kc) {
+            float4 av[4], col[4], v[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { av[b] = aq[b]; aq[b] = kc < 7 ? ufrag(a, b, kc + 1) : ufrag(an, b, 0); }
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) col[jj] = fma4(s1, raw[4 + jj], raw[jj]);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) v[b] = fma4(wino_s1(b), col[wino_i1(b)], col[wino_i0(b)]);
+            if (kc == 7) bases(an, pb);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) raw[q] = sm[pb[q] + (kc < 7 ? 2 * (kc + 1) : 0) + h];
+            prio_matrix();
+            __builtin_amdgcn_sched_barrier(0);              // keep the prefetch loads AHEAD of this chunk's MFMAs
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                f32x16& x = xacc[b];
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av[b].x, v[b].x, kc == 0 ? zero : x, 0, 0, 0);
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av[b].y, v[b].y, x, 0, 0, 0);
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av[b].z, v[b].z, x, 0, 0, 0);
+                x = __builtin_amdgcn_mfma_f32_32x32x2f32(av[b].w, v[b].w, x, 0, 0, 0);
+                if (b < 3) __builtin_amdgcn_sched_barrier(0);      // xi by xi (hipcc deals the four chains round-robin otherwise: every accumulator's last MFMA among the chunk's last four)
+            }
+            prio_nonmatrix();
+        }
+        // the row's transforms in ascending xi, each behind the one before it: xi (a, 0)'s accumulator has been complete for twelve
+        // MFMAs, and by the time xi (a, 3)'s is read its last MFMA has left the pipe (the barriers keep hipcc from starting at the far end)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            otrans(a, b, xacc[b], mask);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    xi_row(0, std::integral_constant<int, 1>{});           // a = 0: row 0 only; a = 1, 2: both; a = 3: row 1 only
+#pragma unroll 1
+    for (int a = 1; a < 3; ++a) xi_row(a, std::integral_constant<int, 3>{});
+    xi_row(3, std::integral_constant<int, 2>{});
 }
 // ---------------------------------------------------------------------------------------------------------
 // Layer 2 (ConvTranspose2d(64,64,3,s2,p1,op1)) by F(2, 2) (the table and the six-group schedule at the top of this file) on
@@ -220,6 +310,11 @@ __device__ __forceinline__ void f22_l2_first(f32x4 (&aq)[F22_PD][5], const __amd
         static_for<w3_nch(p >> 2)>([&](auto c) { aq[p][c] = f22_wfrag(wr, ln, dn, w3_mat(w3_prod(p >> 2, c)), p & 3); });
     });
 }
+// LATE (k_dec_ab): a group's temporaries are added a step later, behind the next step's views and requests and in front of its MFMAs
+// (the first that may touch those outputs again; the last group's behind the loop), as in k_dec_b4: right behind the group's last MFMA
+// every add waits out that MFMA's result latency.  k_dec_a and k_dec_a_s keep the adds where they were: beside their live prefetch
+// of the next image the later placement takes k_dec_a to 256 VGPRs and spills.  The order per output element is the same either way.
+template <bool LATE = false>
 __device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5], const __amdgpu_buffer_rsrc_t wr, const int dn,
                                        const unsigned ln, const f32x4 bias4, const f32x4* smv, const F22Nb& nb) {
     constexpr int NST = 24;                            // contraction steps: 6 groups x 4 chunks of 16 channels
@@ -235,6 +330,20 @@ __device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5],
     const f32x4 zero4 = {};
     f32x4 tq[5], xr[9];
     static_for<9>([&](auto i) { if constexpr (w3_reads(0, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, 0); });
+    // group GG's temporaries into their outputs, in chain order
+    auto add_tmp = [&](auto gg) {
+        constexpr int GG = decltype(gg)::value;
+        static_for<w3_nch(GG)>([&](auto c) {
+            constexpr int PP = w3_prod(GG, c);
+            if constexpr (!w3_direct(PP))
+                static_for<16>([&](auto o) {
+                    if constexpr (w3_hits(PP, o)) {
+                        if constexpr (w3_seen(GG, c, o)) acc[o] = acc[o] + tq[c];
+                        else acc[o] = bias4 + tq[c];
+                    }
+                });
+        });
+    };
     // software-pipelined one step ahead: step ST = (group ST >> 2, chunk ST & 3), every index a compile-time constant
     static_for<NST>([&](auto stc) {
         constexpr int ST = decltype(stc)::value, G = ST >> 2, KC = ST & 3, GN = (ST + 1) >> 2, KN = (ST + 1) & 3;
@@ -246,6 +355,10 @@ __device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5],
         static_for<w3_nch(GP)>([&](auto c) { aq[ST % F22_PD][c] = f22_wfrag(wr, ln, ST + F22_PD < NST ? 0 : dn, w3_mat(w3_prod(GP, c)), KP); });
         if constexpr (ST + 1 < NST)
             static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
+        if constexpr (LATE && KC == 0 && ST > 0) {     // (the barrier keeps hipcc from moving the adds back up)
+            __builtin_amdgcn_sched_barrier(0);
+            add_tmp(std::integral_constant<int, (ST > 0 ? G - 1 : 0)>{});
+        }
         prio_matrix();
         __builtin_amdgcn_sched_barrier(0);             // keep the prefetch loads AHEAD of this step's MFMAs
 #pragma unroll
@@ -262,18 +375,9 @@ __device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5],
                 }
             });
         prio_nonmatrix();
-        if constexpr (KC == 3)                         // the group's temporaries into their outputs, in chain order
-            static_for<w3_nch(G)>([&](auto c) {
-                constexpr int PP = w3_prod(G, c);
-                if constexpr (!w3_direct(PP))
-                    static_for<16>([&](auto o) {
-                        if constexpr (w3_hits(PP, o)) {
-                            if constexpr (w3_seen(G, c, o)) acc[o] = acc[o] + tq[c];
-                            else acc[o] = bias4 + tq[c];
-                        }
-                    });
-            });
+        if constexpr (!LATE && KC == 3) add_tmp(std::integral_constant<int, G>{});
     });
+    if constexpr (LATE) add_tmp(std::integral_constant<int, 5>{});
 }
 // ReLU + the tile's y2 stores.  y2 is [parity][8 channel groups][16 x 16 positions][8 channels]: outputs (orow, c) and (orow, c + 2) of a
 // block are neighbouring positions of one parity, and lane groups g, g ^ 1 are the two halves of one 8-channel group.  One
@@ -408,10 +512,12 @@ __device__ __forceinline__ void dec_a_loop(const DecAArgs& a_, float4* const sm,
 #pragma unroll
                 for (int rc = 0; rc < 4; ++rc) { l1o[rc >> 1][rc & 1][4 * g4] = bb.x; l1o[rc >> 1][rc & 1][4 * g4 + 1] = bb.y; l1o[rc >> 1][rc & 1][4 * g4 + 2] = bb.z; l1o[rc >> 1][rc & 1][4 * g4 + 3] = bb.w; }
             }
-            wino_l1<2, 0>(l1o, W1, sm, h, l1mt, [&](int i, int jj) {
+            auto l1pix = [&](int i, int jj) {
                 const int y = l1y + i, x = l1x + jj;
                 return ((unsigned)y < 16u && (unsigned)x < 16u ? y * 16 + x : 256) * DA_PS;
-            });
+            };
+            if constexpr (FUSED) wino_l1_rows(l1o, W1, sm, h, l1mt, l1pix);
+            else wino_l1<2, 0>(l1o, W1, sm, h, l1mt, l1pix);
             __syncthreads();            // every wave is done reading the input image (and slot[0])
             if ((FUSED ? tl_ : tid) == 0) slot[0] = ticket;
             // bias + ReLU, written back IN PLACE as the input image of layer 2 (same padded layout)
@@ -464,7 +570,7 @@ __device__ __forceinline__ void dec_a_loop(const DecAArgs& a_, float4* const sm,
 #pragma unroll 1
                 for (int ct = 0; ct < 4; ++ct) {
                     const f32x4 bias4 = smv[DA_BIAS + 16 + 4 * ct + g];
-                    f22_l2(acc2, aq, wrsrc(W2 + ct * 256), ct < 3 ? 1 : 0, ln, bias4, smv, nb);
+                    f22_l2<FUSED>(acc2, aq, wrsrc(W2 + ct * 256), ct < 3 ? 1 : 0, ln, bias4, smv, nb);
                     if (ct < 3) f22_l2_store(acc2, yr, yoff, ct, true);
                 }
                 if constexpr (!FUSED) load_next(NPE, 2 * NPH);
@@ -681,7 +787,11 @@ __device__ __forceinline__ void dec_b_image(const DecBArgs& a, float4* const sm,
     // packed U fragments [16 matrices][2 channel halves][4 chunks][64 lanes] (engine_weights.hip): the channel half is folded into the base
     const __amdgpu_buffer_rsrc_t wr = wrsrc(a.w3 + (size_t)hf * 4 * 64 * 4);
     const unsigned ln = (unsigned)lane * 16u;
-    auto wf = [&](int m, int kc) -> f32x4 { return __builtin_bit_cast(f32x4, wfrag(wr, ln, (size_t)(m * 8 + kc) * 64)); };
+    // (k_dec_ab: the chunk is the load's immediate offset, so that a scalar offset serves four fragments -- with one scalar per fragment
+    // hipcc keeps up to 25 of them through the strip loop and spills the gather masks' SGPRs)
+    auto wf = [&](int m, int kc) -> f32x4 {
+        return __builtin_bit_cast(f32x4, FUSED ? wfrag(wr, ln + (unsigned)kc * 1024u, (size_t)(m * 8) * 64) : wfrag(wr, ln, (size_t)(m * 8 + kc) * 64));
+    };
     const float D1 = 1.00001f, D0 = 0.00001f;
     float part = 0.f;
     f32x4 pf[NPF];
