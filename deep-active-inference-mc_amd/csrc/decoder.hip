@@ -72,6 +72,84 @@ __host__ __device__ constexpr bool w3_reads(int G, int r, int c) {   // input pi
     return false;
 }
 
+// The contraction of one tile, shared by both layers: 24 steps ST = (group ST >> 2, channel chunk ST & 3), every index a compile-time
+// constant, software-pipelined: a step forms its group's views from the raw neighbourhood xr, takes its A fragments out of the ring aq
+// (PD steps deep; filled for steps 0 .. PD - 1 on entry) and requests the fragments of step ST + PD and the pixels of step ST + 1 in
+// front of its own MFMAs (e outer, chain inner: every B value feeds 4 or 5 independent chains).
+//   wf(m, kc, next): the A fragment of matrix m, chunk kc; next: the step requested lies behind this tile (ST + PD >= 24).  WRAP: those
+//   steps are requested too (the next tile's first fragments: aq holds them on exit); otherwise the ring runs dry.
+//   px(i, jj, kc): pixel (i, jj) of the lane's 3 x 3 neighbourhood, the lane's quad of chunk kc.
+//   piece(stc): the caller's own non-matrix work of step stc, behind prio_nonmatrix().
+//   OPAQUE: views and temporaries go through sub4 / add4 (mfma_pipe.h: single-lane instructions) instead of the vector operators.
+//   LATE: a group's temporaries are added a step later, behind the next step's views and requests and in front of its MFMAs (the first
+//   that may touch those outputs again; the last group's behind the loop), not right behind the group's last MFMA: there every add waits
+//   out that MFMA's result latency in hazard wait states.  The order per output element is the same either way.
+template <int PD, bool LATE, bool OPAQUE, bool WRAP, class WF, class PX, class Piece>
+__device__ __forceinline__ void f22_contract(f32x4 (&acc)[16], f32x4 (&aq)[PD][5], const f32x4 bias4, WF wf, PX px, Piece piece) {
+    constexpr int NST = 24;                            // contraction steps: 6 groups x 4 chunks of 16 channels
+    auto sub = [](const f32x4 a, const f32x4 b) -> f32x4 { if constexpr (OPAQUE) return sub4(a, b); else return a - b; };
+    auto add = [](const f32x4 a, const f32x4 b) -> f32x4 { if constexpr (OPAQUE) return add4(a, b); else return a + b; };
+    // view (a, b) of the raw neighbourhood x[i][jj]: the columns first (x[i][0] - x[i][1] | x[i][1] | x[i][2] - x[i][1]), then the rows
+    // in the same form
+    auto view = [&](const f32x4 (&x)[9], int vi) -> f32x4 {
+        const int va = vi / 3, vb = vi % 3;
+        auto cv = [&](int i) -> f32x4 { return vb == 0 ? sub(x[3 * i], x[3 * i + 1]) : (vb == 1 ? x[3 * i + 1] : sub(x[3 * i + 2], x[3 * i + 1])); };
+        return va == 0 ? sub(cv(0), cv(1)) : (va == 1 ? cv(1) : sub(cv(2), cv(1)));
+    };
+    const f32x4 zero4 = {};
+    f32x4 tq[5], xr[9];
+    static_for<9>([&](auto i) { if constexpr (w3_reads(0, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, 0); });
+    // group GG's temporaries into their outputs, in chain order
+    auto add_tmp = [&](auto gg) {
+        constexpr int GG = decltype(gg)::value;
+        static_for<w3_nch(GG)>([&](auto c) {
+            constexpr int PP = w3_prod(GG, c);
+            if constexpr (!w3_direct(PP))
+                static_for<16>([&](auto o) {
+                    if constexpr (w3_hits(PP, o)) {
+                        if constexpr (w3_seen(GG, c, o)) acc[o] = add(acc[o], tq[c]);
+                        else acc[o] = add(bias4, tq[c]);
+                    }
+                });
+        });
+    };
+    static_for<NST>([&](auto stc) {
+        constexpr int ST = decltype(stc)::value, G = ST >> 2, KC = ST & 3, GN = (ST + 1) >> 2, KN = (ST + 1) & 3;
+        constexpr int SP = (ST + PD) % NST, GP = SP >> 2, KP = SP & 3;      // the step whose fragments are requested now
+        f32x4 vw[9], ac[5];
+        static_for<9>([&](auto vi) { if constexpr (w3_uses_view(G, vi)) vw[vi] = view(xr, vi); });
+#pragma unroll
+        for (int c = 0; c < 5; ++c) ac[c] = aq[ST % PD][c];
+        if constexpr (WRAP || ST + PD < NST)
+            static_for<w3_nch(GP)>([&](auto c) { aq[ST % PD][c] = wf(w3_mat(w3_prod(GP, c)), KP, ST + PD >= NST); });
+        if constexpr (ST + 1 < NST)
+            static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
+        if constexpr (LATE && KC == 0 && ST > 0) {     // (the barrier keeps hipcc from moving the adds back up)
+            __builtin_amdgcn_sched_barrier(0);
+            add_tmp(std::integral_constant<int, (ST > 0 ? G - 1 : 0)>{});
+        }
+        prio_matrix();
+        __builtin_amdgcn_sched_barrier(0);             // keep the prefetch loads AHEAD of this step's MFMAs
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            static_for<w3_nch(G)>([&](auto c) {
+                constexpr int PP = w3_prod(G, c);
+                const float b = vw[w3_view(PP)][e], av = ac[c][e];
+                if constexpr (w3_direct(PP)) {
+                    constexpr int O = 4 * f22_o0(PP / 5) + f22_o0(PP % 5);
+                    constexpr bool FIRST = KC == 0 && !w3_seen(G, c, O);
+                    acc[O] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (FIRST && e == 0) ? bias4 : acc[O], 0, 0, 0);
+                } else {
+                    tq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (KC == 0 && e == 0) ? zero4 : tq[c], 0, 0, 0);
+                }
+            });
+        prio_nonmatrix();
+        if constexpr (!LATE && KC == 3) add_tmp(std::integral_constant<int, G>{});
+        piece(stc);
+    });
+    if constexpr (LATE) add_tmp(std::integral_constant<int, 5>{});      // (empty today: group 5 has direct chains only)
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // k_dec_a: ConvTranspose2d(64,64,3,s1,p1)+ReLU then ConvTranspose2d(64,64,3,s2,p1,op1)+ReLU, one image per WG.
 // ---------------------------------------------------------------------------------------------------------
@@ -99,6 +177,28 @@ __host__ __device__ constexpr int wino_i1(int a) { return a == 0 ? 2 : (a == 1 ?
 __host__ __device__ constexpr float wino_s1(int a) { return a == 1 ? 1.0f : -1.0f; }
 __host__ __device__ constexpr float wino_at(int r, int a) { return r == 0 ? (a < 3 ? 1.0f : 0.0f) : (a == 0 ? 0.0f : (a == 1 ? 1.0f : -1.0f)); }   // AT = [[1,1,1,0],[0,1,-1,-1]]
 
+__device__ __forceinline__ float4 fma4(float s, const float4& x, const float4& y) {          // y + s x per component (s = +-1: exactly y +- x)
+    return make_float4(__builtin_fmaf(s, x.x, y.x), __builtin_fmaf(s, x.y, y.y), __builtin_fmaf(s, x.z, y.z), __builtin_fmaf(s, x.w, y.w));
+}
+// the transform of xi (a, b), whose GEMM is m, into the outputs
+// (MASK: the output rows whose AT[r][a] is non-zero for this a -- a constant, so that no update is conditional at run time:
+// hipcc turns a run-time skip into selects that hold every output twice)
+template <int NR, int R0, int MASK>
+__device__ __forceinline__ void wino_otrans(f32x16 (&out)[NR][2], const int a, const int b, const f32x16& m) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        if (!((MASK >> r) & 1)) continue;
+        const float car = wino_at(R0 + r, a);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float cbc = wino_at(c, b);
+            if (cbc == 0.0f) continue;
+            const float cf = car * cbc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) out[r][c][e] = __builtin_fmaf(cf, m[e], out[r][c][e]);
+        }
+    }
+}
 template <int NR, int R0, class Pix>
 __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __restrict__ U, const float4* sm, const int h,
                                         const int mt_, Pix pix) {
@@ -123,25 +223,6 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
     for (int q = 0; q < 4; ++q) raw[q] = sm[pb[q] + h];
     f32x16 xacc;
     const f32x16 zero = {};
-    // the transform of xi (a, b) into the outputs
-    // (MASK: the output rows whose AT[r][a] is non-zero for this a -- a constant, so that no update is conditional at run time:
-    // hipcc turns a run-time skip into selects that hold every output twice)
-    auto otrans = [&](int a, int b, const f32x16& m, auto mask) {
-        constexpr int MASK = decltype(mask)::value;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            if (!((MASK >> r) & 1)) continue;
-            const float car = wino_at(R0 + r, a);
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const float cbc = wino_at(c, b);
-                if (cbc == 0.0f) continue;
-                const float cf = car * cbc;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) out[r][c][e] = __builtin_fmaf(cf, m[e], out[r][c][e]);
-            }
-        }
-    };
     auto xi_row = [&](int a, auto mask) {               // the four xi (a, 0..3)
         const float s1 = wino_s1(a);
         const int an = a + 1 < a_hi ? a + 1 : a;        // the next xi row (the last one re-reads its own fragments: never used)
@@ -152,15 +233,9 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
             for (int kc = 0; kc < 8; ++kc) {
                 const float4 av = aq[kc % PD];
                 aq[kc % PD] = (b * 8 + kc + PD < 32) ? ufrag(a, (b * 8 + kc + PD) >> 3, (kc + PD) & 7) : ufrag(an, 0, (kc + PD) & 7);
-                // V fragment of this chunk: (d00 + s1 d10) + t1 (d01 + s1 d11), per component
-                float4 v;
-                {
-                    const float4 c0 = make_float4(__builtin_fmaf(s1, raw[2].x, raw[0].x), __builtin_fmaf(s1, raw[2].y, raw[0].y),
-                                                  __builtin_fmaf(s1, raw[2].z, raw[0].z), __builtin_fmaf(s1, raw[2].w, raw[0].w));
-                    const float4 c1 = make_float4(__builtin_fmaf(s1, raw[3].x, raw[1].x), __builtin_fmaf(s1, raw[3].y, raw[1].y),
-                                                  __builtin_fmaf(s1, raw[3].z, raw[1].z), __builtin_fmaf(s1, raw[3].w, raw[1].w));
-                    v = make_float4(__builtin_fmaf(t1, c1.x, c0.x), __builtin_fmaf(t1, c1.y, c0.y), __builtin_fmaf(t1, c1.z, c0.z), __builtin_fmaf(t1, c1.w, c0.w));
-                }
+                // V fragment of this chunk: (d00 + s1 d10) + t1 (d01 + s1 d11), per component (c0, then c1: nested calls are evaluated in another order)
+                const float4 c0 = fma4(s1, raw[2], raw[0]), c1 = fma4(s1, raw[3], raw[1]);
+                const float4 v = fma4(t1, c1, c0);
                 // the next chunk's input pixels (the next xi's first chunk behind the last one)
                 if (kc < 7) {
 #pragma unroll
@@ -184,7 +259,7 @@ __device__ __forceinline__ void wino_l1(f32x16 (&out)[NR][2], const float4* __re
             // chunks, fits all three kernels -- 244 / 219 / 252 VGPRs, unchanged -- and was measured in k_dec_ab: the same cycles
             // within the parent's own spread, profiles/r14_overlap_items.txt.  The drain is 16 x 64 cycles per image and the partner
             // wave fills most of it; what layer 1 pays for is the number of non-matrix instructions: see wino_l1_rows.)
-            otrans(a, b, xacc, mask);
+            wino_otrans<NR, R0, decltype(mask)::value>(out, a, b, xacc);
         }
     };
     if constexpr (NR == 2) {                            // a = 0: row 0 only; a = 1, 2: both; a = 3: row 1 only
@@ -224,25 +299,6 @@ __device__ __forceinline__ void wino_l1_rows(f32x16 (&out)[2][2], const float4* 
     for (int q = 0; q < 8; ++q) raw[q] = sm[pb[q] + h];
     f32x16 xacc[4];
     const f32x16 zero = {};
-    auto fma4 = [](float s, const float4& x, const float4& y) {          // y + s x per component (s = +-1: exactly y +- x)
-        return make_float4(__builtin_fmaf(s, x.x, y.x), __builtin_fmaf(s, x.y, y.y), __builtin_fmaf(s, x.z, y.z), __builtin_fmaf(s, x.w, y.w));
-    };
-    auto otrans = [&](int a, int b, const f32x16& m, auto mask) {       // (wino_l1's, for NR = 2, R0 = 0)
-        constexpr int MASK = decltype(mask)::value;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (!((MASK >> r) & 1)) continue;
-            const float car = wino_at(r, a);
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const float cbc = wino_at(c, b);
-                if (cbc == 0.0f) continue;
-                const float cf = car * cbc;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) out[r][c][e] = __builtin_fmaf(cf, m[e], out[r][c][e]);
-            }
-        }
-    };
     auto xi_row = [&](int a, auto mask) {
         const float s1 = wino_s1(a);
         const int an = a + 1 < 4 ? a + 1 : a;              // the next xi row (the last one re-reads its own fragments: never used)
@@ -275,7 +331,7 @@ __device__ __forceinline__ void wino_l1_rows(f32x16 (&out)[2][2], const float4* 
         // MFMAs, and by the time xi (a, 3)'s is read its last MFMA has left the pipe (the barriers keep hipcc from starting at the far end)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            otrans(a, b, xacc[b], mask);
+            wino_otrans<2, 0, decltype(mask)::value>(out, a, b, xacc[b]);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -300,6 +356,17 @@ __device__ __forceinline__ void wino_l1_rows(f32x16 (&out)[2][2], const float4* 
 // tile's first F22_PD steps on entry (f22_l2_first), of the next tile's on exit.
 // ---------------------------------------------------------------------------------------------------------
 struct F22Nb { int xb, c2[3], r2; };
+// the neighbourhood of the block at xb (the lane's quad included) in block column bv; zq: a zero pixel (quad included), the x_2 of the last
+// block column and of block row bu = 7 (an image with a row of zeros below it passes bu = 0: row 2 is then a row like any other)
+__device__ __forceinline__ F22Nb f22_nb(const int xb, const int zq, const int bv, const int bu) {
+    F22Nb nb;
+    nb.xb = xb;
+    nb.c2[0] = bv == 7 ? zq : xb + 2 * DA_PS;
+    nb.c2[1] = bv == 7 ? zq : xb + 18 * DA_PS;
+    nb.c2[2] = (bv == 7 || bu == 7) ? zq : xb + 34 * DA_PS;
+    nb.r2 = bu == 7 ? zq : xb + 32 * DA_PS;
+    return nb;
+}
 __device__ __forceinline__ f32x4 f22_wfrag(const __amdgpu_buffer_rsrc_t wr, const unsigned ln, int ct, int m, int kc) {
     return __builtin_bit_cast(f32x4, wfrag(wr, ln + (unsigned)kc * 1024u, (size_t)(m * 4 + ct) * 256));      // kc: the load's immediate offset
 }
@@ -310,74 +377,15 @@ __device__ __forceinline__ void f22_l2_first(f32x4 (&aq)[F22_PD][5], const __amd
         static_for<w3_nch(p >> 2)>([&](auto c) { aq[p][c] = f22_wfrag(wr, ln, dn, w3_mat(w3_prod(p >> 2, c)), p & 3); });
     });
 }
-// LATE (k_dec_ab): a group's temporaries are added a step later, behind the next step's views and requests and in front of its MFMAs
-// (the first that may touch those outputs again; the last group's behind the loop), as in k_dec_b4: right behind the group's last MFMA
-// every add waits out that MFMA's result latency.  k_dec_a and k_dec_a_s keep the adds where they were: beside their live prefetch
-// of the next image the later placement takes k_dec_a to 256 VGPRs and spills.  The order per output element is the same either way.
+// LATE: k_dec_ab alone.  k_dec_a and k_dec_a_s keep the adds behind the group's last MFMA: beside their live prefetch of the next
+// image the later placement takes k_dec_a to 256 VGPRs and spills.  Plain vector adds and subtracts (a measured choice).
 template <bool LATE = false>
 __device__ __forceinline__ void f22_l2(f32x4 (&acc)[16], f32x4 (&aq)[F22_PD][5], const __amdgpu_buffer_rsrc_t wr, const int dn,
                                        const unsigned ln, const f32x4 bias4, const f32x4* smv, const F22Nb& nb) {
-    constexpr int NST = 24;                            // contraction steps: 6 groups x 4 chunks of 16 channels
     auto px = [&](int i, int jj, int kc) -> f32x4 {
         return smv[(jj == 2 ? nb.c2[i] : (i == 2 ? nb.r2 + jj * DA_PS : nb.xb + (16 * i + jj) * DA_PS)) + 4 * kc];
     };
-    // view (a, b) of the raw neighbourhood x[i][jj]: the columns first (x[i][0] - x[i][1] | x[i][1] | x[i][2] - x[i][1]), then the rows
-    auto view = [&](const f32x4 (&x)[9], int vi) -> f32x4 {
-        const int va = vi / 3, vb = vi % 3;
-        auto cv = [&](int i) -> f32x4 { return vb == 0 ? x[3 * i] - x[3 * i + 1] : (vb == 1 ? x[3 * i + 1] : x[3 * i + 2] - x[3 * i + 1]); };
-        return va == 0 ? cv(0) - cv(1) : (va == 1 ? cv(1) : cv(2) - cv(1));
-    };
-    const f32x4 zero4 = {};
-    f32x4 tq[5], xr[9];
-    static_for<9>([&](auto i) { if constexpr (w3_reads(0, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, 0); });
-    // group GG's temporaries into their outputs, in chain order
-    auto add_tmp = [&](auto gg) {
-        constexpr int GG = decltype(gg)::value;
-        static_for<w3_nch(GG)>([&](auto c) {
-            constexpr int PP = w3_prod(GG, c);
-            if constexpr (!w3_direct(PP))
-                static_for<16>([&](auto o) {
-                    if constexpr (w3_hits(PP, o)) {
-                        if constexpr (w3_seen(GG, c, o)) acc[o] = acc[o] + tq[c];
-                        else acc[o] = bias4 + tq[c];
-                    }
-                });
-        });
-    };
-    // software-pipelined one step ahead: step ST = (group ST >> 2, chunk ST & 3), every index a compile-time constant
-    static_for<NST>([&](auto stc) {
-        constexpr int ST = decltype(stc)::value, G = ST >> 2, KC = ST & 3, GN = (ST + 1) >> 2, KN = (ST + 1) & 3;
-        constexpr int SP = (ST + F22_PD) % NST, GP = SP >> 2, KP = SP & 3;      // the step whose fragments are requested now
-        f32x4 vw[9], ac[5];
-        static_for<9>([&](auto vi) { if constexpr (w3_uses_view(G, vi)) vw[vi] = view(xr, vi); });
-#pragma unroll
-        for (int c = 0; c < 5; ++c) ac[c] = aq[ST % F22_PD][c];
-        static_for<w3_nch(GP)>([&](auto c) { aq[ST % F22_PD][c] = f22_wfrag(wr, ln, ST + F22_PD < NST ? 0 : dn, w3_mat(w3_prod(GP, c)), KP); });
-        if constexpr (ST + 1 < NST)
-            static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
-        if constexpr (LATE && KC == 0 && ST > 0) {     // (the barrier keeps hipcc from moving the adds back up)
-            __builtin_amdgcn_sched_barrier(0);
-            add_tmp(std::integral_constant<int, (ST > 0 ? G - 1 : 0)>{});
-        }
-        prio_matrix();
-        __builtin_amdgcn_sched_barrier(0);             // keep the prefetch loads AHEAD of this step's MFMAs
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            static_for<w3_nch(G)>([&](auto c) {
-                constexpr int PP = w3_prod(G, c);
-                const float b = vw[w3_view(PP)][e], av = ac[c][e];
-                if constexpr (w3_direct(PP)) {
-                    constexpr int O = 4 * f22_o0(PP / 5) + f22_o0(PP % 5);
-                    constexpr bool FIRST = KC == 0 && !w3_seen(G, c, O);
-                    acc[O] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (FIRST && e == 0) ? bias4 : acc[O], 0, 0, 0);
-                } else {
-                    tq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (KC == 0 && e == 0) ? zero4 : tq[c], 0, 0, 0);
-                }
-            });
-        prio_nonmatrix();
-        if constexpr (!LATE && KC == 3) add_tmp(std::integral_constant<int, G>{});
-    });
-    if constexpr (LATE) add_tmp(std::integral_constant<int, 5>{});
+    f22_contract<F22_PD, LATE, false, true>(acc, aq, bias4, [&](int m, int kc, bool next) { return f22_wfrag(wr, ln, next ? dn : 0, m, kc); }, px, [](auto) {});
 }
 // ReLU + the tile's y2 stores.  y2 is [parity][8 channel groups][16 x 16 positions][8 channels]: outputs (orow, c) and (orow, c + 2) of a
 // block are neighbouring positions of one parity, and lane groups g, g ^ 1 are the two halves of one 8-channel group.  One
@@ -545,13 +553,7 @@ __device__ __forceinline__ void dec_a_loop(const DecAArgs& a_, float4* const sm,
             int t2_ = tid; asm volatile("" : "+v"(t2_));
             const int n = t2_ & 15, g = (t2_ >> 4) & 3;
             const int bu = 2 * w + (n >> 3), bv = n & 7;
-            const int zq = 256 * DA_PS + g;
-            F22Nb nb;
-            nb.xb = (32 * bu + 2 * bv) * DA_PS + g;
-            nb.c2[0] = bv == 7 ? zq : nb.xb + 2 * DA_PS;
-            nb.c2[1] = bv == 7 ? zq : nb.xb + 18 * DA_PS;
-            nb.c2[2] = bv == 7 ? zq : nb.xb + 34 * DA_PS;
-            nb.r2 = nb.xb + 32 * DA_PS;                 // (block row 7: the zero row, at the banks of a real row)
+            const F22Nb nb = f22_nb((32 * bu + 2 * bv) * DA_PS + g, 256 * DA_PS + g, bv, 0);      // (0: block row 7 reads the zero row, at the banks of a real row)
             const unsigned ln = (unsigned)(t2_ & 63) * 16u;
             const unsigned yoff = (unsigned)(((32 * bu + 2 * bv + (g >> 1)) * 2 + (g & 1)) * 16);
             const __amdgpu_buffer_rsrc_t yr = wrsrc(a.y2 + (size_t)(FUSED ? vscalar(bx_v) : __builtin_amdgcn_readfirstlane(img)) * (32 * 32 * 64));   // (uniform: img comes from LDS)
@@ -664,13 +666,7 @@ __global__ void __launch_bounds__(256, 2) k_dec_a_s(const DecAArgs a) {
     // A block row has 8 blocks: lanes n >= 8 repeat the blocks of lanes n - 8 and are not stored (half of the MFMA tile is idle)
     {
         const int n = lane & 15, g = lane >> 4, bv = n & 7;
-        const int zq = DAS_L1 * DA_PS + g;
-        F22Nb nb;
-        nb.xb = 2 * bv * DA_PS + g;
-        nb.c2[0] = bv == 7 ? zq : nb.xb + 2 * DA_PS;
-        nb.c2[1] = bv == 7 ? zq : nb.xb + 18 * DA_PS;
-        nb.c2[2] = (bv == 7 || p == 7) ? zq : nb.xb + 34 * DA_PS;
-        nb.r2 = p == 7 ? zq : nb.xb + 32 * DA_PS;
+        const F22Nb nb = f22_nb(2 * bv * DA_PS + g, DAS_L1 * DA_PS + g, bv, p);
         const unsigned ln = (unsigned)lane * 16u;
         const unsigned yoff = (unsigned)(((32 * p + 2 * bv + (g >> 1)) * 2 + (g & 1)) * 16);
         const __amdgpu_buffer_rsrc_t yr = wrsrc(a.y2 + (size_t)img * (32 * 32 * 64));
@@ -735,7 +731,6 @@ __device__ __forceinline__ void dec_b_image(const DecBArgs& a, float4* const sm,
     constexpr int DB_YROWS = 4 * SR + 2;
     constexpr int NPF = (SR + 1) * 512 / NTHR;        // 10 float4s of the input strip per thread
     constexpr int NS = 32 / SR;
-    constexpr int NST = 24;                           // contraction steps: 6 groups x 4 chunks of 16 channels
     float* sH = reinterpret_cast<float*>(sm + DB_IN_F4);       // [ring row][channel half][kh][64 output columns]
     // (k_dec_ab: the thread index laundered per image, so that none of this body's lane constants is formed ahead of k_dec_a's layers)
     int tid = threadIdx.x;
@@ -789,7 +784,7 @@ __device__ __forceinline__ void dec_b_image(const DecBArgs& a, float4* const sm,
     const unsigned ln = (unsigned)lane * 16u;
     // (k_dec_ab: the chunk is the load's immediate offset, so that a scalar offset serves four fragments -- with one scalar per fragment
     // hipcc keeps up to 25 of them through the strip loop and spills the gather masks' SGPRs)
-    auto wf = [&](int m, int kc) -> f32x4 {
+    auto wf = [&](int m, int kc, bool) -> f32x4 {       // (f22_contract's form; no step requests another strip's fragments)
         return __builtin_bit_cast(f32x4, FUSED ? wfrag(wr, ln + (unsigned)kc * 1024u, (size_t)(m * 8) * 64) : wfrag(wr, ln, (size_t)(m * 8 + kc) * 64));
     };
     const float D1 = 1.00001f, D0 = 0.00001f;
@@ -817,13 +812,6 @@ __device__ __forceinline__ void dec_b_image(const DecBArgs& a, float4* const sm,
     // this lane's block neighbourhood: pixel (2u + i, 2v + jj), quad 4 kc + g at xb + (33 i + jj) * DB_PS + 4 kc (all immediates)
     const int xb = (2 * u * DB_RP + 2 * v) * DB_PS + g;
     auto px = [&](int i, int jj, int kc) -> f32x4 { return smv[xb + (i * DB_RP + jj) * DB_PS + 4 * kc]; };
-    // view (a, b) of the raw neighbourhood x[i][jj]: the columns first (c_b(i) = x[i][0] - x[i][1] | x[i][1] | x[i][2] - x[i][1]),
-    // then the rows in the same form
-    auto view = [&](const f32x4 (&x)[9], int vi) -> f32x4 {
-        const int va = vi / 3, vb = vi % 3;
-        auto cv = [&](int i) -> f32x4 { return vb == 0 ? sub4(x[3 * i], x[3 * i + 1]) : (vb == 1 ? x[3 * i + 1] : sub4(x[3 * i + 2], x[3 * i + 1])); };
-        return va == 0 ? sub4(cv(0), cv(1)) : (va == 1 ? cv(1) : sub4(cv(2), cv(1)));
-    };
 
     // ---- gather of output row oh (lane = column): out = b4 + H[0][oh + 1] + H[1][oh] + H[2][oh - 1] (source row r contributes to
     // oh = r - 1 + kh), the two channel halves added here; split into pieces for the deferred form
@@ -898,67 +886,20 @@ __device__ __forceinline__ void dec_b_image(const DecBArgs& a, float4* const sm,
 #pragma unroll
             for (int it = 0; it < NPF; ++it) sp[((it >> 1) * DB_RP + (it & 1)) * DB_PS] = pf[it];
         }
-        f32x4 aq[5];                                       // the strip's first weight fragments: in flight across the barrier
+        f32x4 aq[1][5];                                    // the strip's first weight fragments: in flight across the barrier
 #pragma unroll
-        for (int c = 0; c < w3_nch(0); ++c) aq[c] = wf(w3_mat(w3_prod(0, c)), 0);
+        for (int c = 0; c < w3_nch(0); ++c) aq[0][c] = wf(w3_mat(w3_prod(0, c)), 0, false);
         __syncthreads();
 
         // the accumulators start at the layer-3 bias (lane: channels 16 hf + 4 g + 0..3): the C operand of an output's first MFMA, or
         // the first addend of its first temporary
         const f32x4 bias4 = __builtin_bit_cast(f32x4, sb3[4 * hf + g]);
         const f32x4 zero4 = {};
-        f32x4 acc[16], tq[5];
-        // ---- contraction, software-pipelined one step ahead: step ST = (group ST >> 2, chunk ST & 3), every index a compile-time constant
-        f32x4 xr[9];
-        static_for<9>([&](auto i) { if constexpr (w3_reads(0, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, 0); });
-        // group GG's temporaries into their outputs, in chain order
-        auto add_tmp = [&](auto gg) {
-            constexpr int GG = decltype(gg)::value;
-            static_for<w3_nch(GG)>([&](auto c) {
-                constexpr int PP = w3_prod(GG, c);
-                if constexpr (!w3_direct(PP))
-                    static_for<16>([&](auto o) {
-                        if constexpr (w3_hits(PP, o)) {
-                            if constexpr (w3_seen(GG, c, o)) acc[o] = add4(acc[o], tq[c]);
-                            else acc[o] = add4(bias4, tq[c]);
-                        }
-                    });
-            });
-        };
-        static_for<NST>([&](auto stc) {
-            constexpr int ST = decltype(stc)::value, G = ST >> 2, KC = ST & 3, GN = (ST + 1) >> 2, KN = (ST + 1) & 3;
-            f32x4 vw[9], ac[5];
-            static_for<9>([&](auto vi) { if constexpr (w3_uses_view(G, vi)) vw[vi] = view(xr, vi); });
-#pragma unroll
-            for (int c = 0; c < 5; ++c) ac[c] = aq[c];
-            if constexpr (ST + 1 < NST) {
-                static_for<w3_nch(GN)>([&](auto c) { aq[c] = wf(w3_mat(w3_prod(GN, c)), KN); });
-                static_for<9>([&](auto i) { if constexpr (w3_reads(GN, i / 3, i % 3)) xr[i] = px(i / 3, i % 3, KN); });
-            }
-            // The previous group's temporaries are added HERE, behind this step's views and requests and in front of its MFMAs (the
-            // first that may touch those outputs again), not right behind the group's last MFMA: there every add waited out that
-            // MFMA's result latency in hazard wait states (the barrier keeps hipcc from moving them back up).
-            if constexpr (KC == 0 && ST > 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                add_tmp(std::integral_constant<int, (ST > 0 ? G - 1 : 0)>{});
-            }
-            prio_matrix();
-            __builtin_amdgcn_sched_barrier(0);         // keep the prefetch loads AHEAD of this step's MFMAs
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                static_for<w3_nch(G)>([&](auto c) {
-                    constexpr int PP = w3_prod(G, c);
-                    const float b = vw[w3_view(PP)][e], av = ac[c][e];
-                    if constexpr (w3_direct(PP)) {
-                        constexpr int O = 4 * f22_o0(PP / 5) + f22_o0(PP % 5);
-                        constexpr bool FIRST = KC == 0 && !w3_seen(G, c, O);
-                        acc[O] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (FIRST && e == 0) ? bias4 : acc[O], 0, 0, 0);
-                    } else {
-                        tq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b, (KC == 0 && e == 0) ? zero4 : tq[c], 0, 0, 0);
-                    }
-                });
-            prio_nonmatrix();
-            // the previous strip's gather, a piece per step
+        f32x4 acc[16];
+        // ---- contraction (f22_contract: the temporaries added a step later, single-lane adds; the fragment ring one step deep, and
+        // dry at the strip's end), with the previous strip's gather, a piece per step
+        f22_contract<1, true, true, false>(acc, aq, bias4, wf, px, [&](auto stc) {
+            constexpr int ST = decltype(stc)::value;
             if (gq) {
                 if constexpr (ST == 0) { g_load(go0, 0); g_load(go1, 1); }
                 if constexpr (ST == 2) g_sig(0);

@@ -1,7 +1,7 @@
 """The premise of layer 2 of k_dec_a / k_dec_a_s (decoder.hip f22_l2, kernels.h f22_*): ConvTranspose2d(64, 64, 3, s2, p1, op1) on the
 16 x 16 layer-1 image computed by per-parity minimal filtering F(2, 2) in fp32 -- 16 weight matrices formed in fp64 and rounded once,
 9 input views per 2 x 2 input block (x_2 = 0 beyond the last row / column), 25 products added into the block's 4 x 4 outputs -- is as
-accurate as the direct form.  Restated here in torch on the CPU in the kernel's association (the bias first; group by group, direct
+accurate as the direct form.  Restated in torch on the CPU (tests/f22_ref.py) in the kernel's association (the bias first; group by group, direct
 products chained into their output, the others added into theirs in chain order; torch contracts the 64 channels of a product in its
 own order): exact in fp64, and within the fp64 parity rule of the direct fp32 error on every weight family, before and after the ReLU
 (tests/test_fp64_parity.py: e <= ALPHA * e_32 + BETA ulp).  The maths is that of ConvT3 (tests/test_winograd_convt3.py) on 8 x 8 blocks."""
@@ -10,59 +10,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from f22_ref import GROUPS, OUTS, VIEW, WT, f22_convt
 from oracle import synth
 
 ALPHA, BETA = 4.0, 8.0
-# 1D products P1..P5: view (d0 = x0 - x1, d1 = x1, d2 = x2 - x1), weight (g1, g2, g0 + g2, g0), outputs of the block
-VIEW = [0, 1, 0, 1, 2]
-WT = [0, 0, 1, 2, 3]
-OUTS = [(0,), (0, 2), (1,), (1, 3), (3,)]
-CW = [[0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 0, 0]]            # tap coefficients of each weight
-# the schedule of f22_l2: groups of (row product, column product)
-GROUPS = [[(0, 0), (0, 2), (2, 0), (2, 2)], [(0, 1), (0, 3), (2, 1), (2, 3)], [(1, 0), (1, 2), (3, 0), (3, 2)],
-          [(1, 1), (1, 3), (3, 1), (3, 3)], [(1, 4), (3, 4), (4, 1), (4, 3), (4, 4)], [(0, 4), (2, 4), (4, 0), (4, 2)]]
-
-
-def f22_weights(W):
-    """W [Cin, Cout, 3, 3] -> U [4, 4, Cin, Cout] in fp64 (rounded by the caller): U[wr][wc] = sum cw[wr][kh] cw[wc][kw] W[..., kh, kw]"""
-    C = torch.tensor(CW, dtype=torch.float64)
-    return torch.einsum('ah,bw,iohw->abio', C, C, W.double())
-
-
-def f22_convt2(x, W, b, dtype):
-    """x [N, Cin, H, H] (H even), W [Cin, Cout, 3, 3], b [Cout] -> [N, Cout, 2H, 2H] in `dtype`, in f22_l2's order of operations"""
-    H = x.shape[-1]
-    U = f22_weights(W).to(dtype)
-    xp = F.pad(x.to(dtype), (0, 1, 0, 1))                                    # x[H] = 0 (row and column)
-    nb = xp.unfold(2, 3, 2).unfold(3, 3, 2)                                   # [N, Cin, H/2, H/2, 3, 3]: block (u, v), x[i][jj]
-
-    def cview(i, vb):
-        return (nb[..., i, 0] - nb[..., i, 1]) if vb == 0 else (nb[..., i, 1] if vb == 1 else nb[..., i, 2] - nb[..., i, 1])
-
-    def view(va, vb):
-        return (cview(0, vb) - cview(1, vb)) if va == 0 else (cview(1, vb) if va == 1 else cview(2, vb) - cview(1, vb))
-
-    out = [[None] * 4 for _ in range(4)]
-    bias = b.to(dtype).view(1, -1, 1, 1)
-
-    def add(r, c, m):
-        out[r][c] = (bias + m) if out[r][c] is None else out[r][c] + m
-
-    for grp in GROUPS:
-        temps = []
-        for pr, pc in grp:
-            M = torch.einsum('io,nihw->nohw', U[WT[pr], WT[pc]], view(VIEW[pr], VIEW[pc]))
-            if len(OUTS[pr]) == 1 and len(OUTS[pc]) == 1:                     # direct: chained into its output during the group
-                add(OUTS[pr][0], OUTS[pc][0], M)
-            else:
-                temps.append((pr, pc, M))
-        for pr, pc, M in temps:                                               # then the temporaries, in chain order
-            for r in OUTS[pr]:
-                for c in OUTS[pc]:
-                    add(r, c, M)
-    y = torch.stack([torch.stack(row, -1) for row in out], -2)                # [N, Cout, H/2, H/2, 4 (r), 4 (c)]
-    return y.permute(0, 1, 2, 4, 3, 5).reshape(x.shape[0], -1, 2 * H, 2 * H)
-
 
 def layer_input(weights, n, seed):
     """ConvT2 inputs of the family's regime: the decoder's post-ReLU ConvT1 activations for random latents (dropout-free, so scaled by 2 on half)"""
@@ -115,7 +66,7 @@ def test_f22_restatement_is_exact_in_fp64():
     assert x.shape[1:] == (64, 16, 16) and W.shape == (64, 64, 3, 3)
     x[:, :, -1, :] += 1.0; x[:, :, :, -1] += 1.0; x[:, :, 0, :] += 1.0; x[:, :, :, 0] += 1.0     # active last row / column: x2 = 0 matters
     ref = F.conv_transpose2d(x, W, b, stride=2, padding=1, output_padding=1)
-    got = f22_convt2(x, W, b, torch.float64)
+    got = f22_convt(x, W, b, torch.float64)
     assert got.shape == ref.shape == (4, 64, 32, 32)
     assert torch.allclose(got, ref, rtol=0, atol=1e-12 * float(ref.abs().max()))
 
@@ -127,7 +78,7 @@ def test_f22_fp32_error_is_within_the_fp64_rule(family):
     x = layer_input(w, 8, 5)
     ref = F.conv_transpose2d(x.double(), W.double(), b.double(), stride=2, padding=1, output_padding=1)
     direct = F.conv_transpose2d(x, W, b, stride=2, padding=1, output_padding=1).double()
-    f22 = f22_convt2(x, W, b, torch.float32).double()
+    f22 = f22_convt(x, W, b, torch.float32).double()
     e32 = float((direct - ref).abs().max())
     ef = float((f22 - ref).abs().max())
     ulp = float(np.spacing(np.float32(float(ref.abs().max()))))

@@ -2,7 +2,7 @@
 """Per-kernel register / spill / LDS figures of the BUILT engine library, read from the AMDGPU code-object metadata inside it
 (no recompilation): the gfx950 ELF images are cut out of the .hip_fatbin section and their NT_AMDGPU_METADATA note is printed by
 llvm-readelf.   python tools/isa_report.py [path/to/libefe_mi355x.so]
-                python tools/isa_report.py --diff OLD.so NEW.so      (per kernel: identical listing, or what differs)"""
+                python tools/isa_report.py --diff OLD.so NEW.so      (per kernel: identical listing, the same instruction sequence, or what differs)"""
 import collections, os, re, struct, subprocess, sys, tempfile
 
 LLVM = '/opt/rocm/lib/llvm/bin'
@@ -88,9 +88,10 @@ def listing(text):
 
 
 def diff(old, new, out=sys.stdout):
-    """per kernel of either library: 'identical' (same normalised listing and metadata), else the metadata fields (old -> new where
-    they differ) and the per-mnemonic instruction counts that differ: a mnemonic that is not listed occurs equally often on both
-    sides.  -> number of kernels that are not identical"""
+    """per kernel of either library: 'identical' (same normalised listing and metadata); 'same instruction sequence' (equal metadata
+    and the same mnemonic line for line: only operands differ); else the metadata fields (old -> new where they differ) and the
+    per-mnemonic instruction counts that differ: a mnemonic that is not listed occurs equally often on both sides.
+    -> number of kernels that are not identical"""
     ko, kn, do, dn = kernels(old), kernels(new), disassembly(old), disassembly(new)
     changed = 0
     for k in sorted(set(ko) | set(kn)):
@@ -103,6 +104,11 @@ def diff(old, new, out=sys.stdout):
             out.write(f'{k}: identical ({len(lo)} instructions)\n')
             continue
         changed += 1
+        if ko[k] == kn[k] and [i.split()[0] for i in lo] == [i.split()[0] for i in ln]:
+            nd = sum(a != b for a, b in zip(lo, ln))
+            out.write(f'{k}: same instruction sequence, {nd} of {len(lo)} lines differ in operands; metadata equal: '
+                      + ', '.join(f'{f[1:]} {ko[k].get(f)}' for f in FIELDS) + '\n')
+            continue
         meta = [f'{f[1:]} {ko[k].get(f)}' + ('' if ko[k].get(f) == kn[k].get(f) else f' -> {kn[k].get(f)}') for f in FIELDS]
         out.write(f'{k}: DIFFERS, {len(lo)} -> {len(ln)} instructions; metadata ' + ('equal' if ko[k] == kn[k] else 'DIFFERS') + ': ' + ', '.join(meta) + '\n')
         co, cn = (collections.Counter(i.split()[0] for i in l) for l in (lo, ln))
