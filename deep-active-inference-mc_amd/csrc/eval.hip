@@ -12,15 +12,15 @@
 //
 // No atomics, nothing passes between workgroups, every loop is counted by M (or Mr); LDS <= 32 KiB + 1 KiB per workgroup.
 //
-// Reduction-order contract of every mean, the std and mse_r (k_step_means' of loss.hip, restated here: a function of the element count N
-// alone): thread t adds elements t, t + 256, ... in ascending order into an fp32 accumulator that starts at 0; the 64 lanes of a wave are
-// combined by an xor butterfly (offsets 32, 16, ..., 1) and the four wave sums as ((w0 + w1) + w2) + w3; one correctly rounded division by
-// (float)N ((float)(M - 1) for the variance, then a correctly rounded square root).  Contraction off.
+// Reduction-order contract of every mean, the std and mse_r (a function of the element count N alone): block_sum.h's sum in fp32, then one
+// correctly rounded division by (float)N ((float)(M - 1) for the variance, then a correctly rounded square root).  Contraction off.
+// k_eval_tc's fp64 sums run through the same function.
 //
 // Non-finite values: the sums propagate them by arithmetic.  min / max / med and the ranks are comparisons, which a NaN fails silently: each
 // of them tests the bit pattern of what it stages and writes NaN when one was seen.  Integer sums and fp64 sums have no order contract to
 // keep: the integer ones are exact, the fp64 ones are rounded once to fp32 at the end.
 #include "kernels.h"
+#include "block_sum.h"
 
 namespace efe {
 
@@ -32,20 +32,6 @@ constexpr int EV_PER = EVAL_MAX_ROWS / EV_WIDE;       // elements a thread of a 
 
 __device__ __forceinline__ bool ev_isnan(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
 __device__ __forceinline__ float ev_nan() { return __uint_as_float(0x7fc00000u); }
-
-// the sum of f(i) over i < N in the contract's order; every thread of the 256-thread workgroup gets the result
-template <class F>
-__device__ __forceinline__ float eval_block_sum(int N, float* ws, F f) {
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x;
-    float acc = 0.0f;
-    for (int i = tid; i < N; i += 256) acc = acc + f(i);
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-    __syncthreads();                    // (ws may still be read from the previous sum)
-    if ((tid & 63) == 0) ws[tid >> 6] = acc;
-    __syncthreads();
-    return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
 
 // counts, for each of this thread's elements x[k] (k < EV_PER), the entries of col[0, M) below it and equal to it
 __device__ __forceinline__ void ev_count(const float* col, int M, const float (&x)[EV_PER], int (&less)[EV_PER], int (&eq)[EV_PER]) {
@@ -95,7 +81,7 @@ __global__ void __launch_bounds__(256) k_eval_means(const EvalArgs a) {
         if (a.o1_r) {
             const int N = a.Mr * 192;
             const float* o = a.o1_r; const float* p = a.po1_r;
-            const float s = eval_block_sum(N, ws, [o, p](int i) {
+            const float s = block_sum_of(N, ws, [o, p](int i) {
 #pragma clang fp contract(off)
                 const int r = i / 192, c = i - r * 192;
                 const float d = o[(size_t)r * 4096 + c] - p[(size_t)r * 4096 + c];
@@ -107,13 +93,13 @@ __global__ void __launch_bounds__(256) k_eval_means(const EvalArgs a) {
         const float Mf = (float)M;
         if (q == 0) {                   // F: (F_down + F_mid) + F_top per row (train.py:149)
             const float* ft = a.row[0]; const float* fm = a.row[1]; const float* fd = a.row[2];
-            res = __fdiv_rn(eval_block_sum(M, ws, [ft, fm, fd](int r) {
+            res = __fdiv_rn(block_sum_of(M, ws, [ft, fm, fd](int r) {
 #pragma clang fp contract(off)
                 return (fd[r] + fm[r]) + ft[r];
             }), Mf);
         } else if (q <= 7) {            // batch means; 7 = kl_pi
             const float* x = a.row[q - 1];
-            res = __fdiv_rn(eval_block_sum(M, ws, [x](int r) { return x[r]; }), Mf);
+            res = __fdiv_rn(block_sum_of(M, ws, [x](int r) { return x[r]; }), Mf);
         } else if (q == 8 || q == 9) {  // min / max of kl_pi: an input element, or NaN when one is there
             const float* x = a.row[6];
             const bool mx = q == 9;
@@ -136,8 +122,8 @@ __global__ void __launch_bounds__(256) k_eval_means(const EvalArgs a) {
             res = (wi[0] | wi[1] | wi[2] | wi[3]) ? ev_nan() : m;
         } else if (q == 11) {           // unbiased std of kl_pi: torch.std's two passes (k_step_means' omega_std)
             const float* x = a.row[6];
-            const float mean = __fdiv_rn(eval_block_sum(M, ws, [x](int r) { return x[r]; }), Mf);
-            const float ss = eval_block_sum(M, ws, [x, mean](int r) {
+            const float mean = __fdiv_rn(block_sum_of(M, ws, [x](int r) { return x[r]; }), Mf);
+            const float ss = block_sum_of(M, ws, [x, mean](int r) {
 #pragma clang fp contract(off)
                 const float d = x[r] - mean;
                 return d * d;
@@ -148,7 +134,7 @@ __global__ void __launch_bounds__(256) k_eval_means(const EvalArgs a) {
             if (q < 24) { x = a.kl_s_anal; ld = EV_S; k = q - 14; }
             else if (q < 34) { x = a.kl_naive_anal; ld = EV_S; k = q - 24; }
             else { x = a.kl_pi_anal; ld = a.A; k = q - 34; }
-            res = __fdiv_rn(eval_block_sum(M, ws, [x, ld, k](int r) { return x[(size_t)r * ld + k]; }), Mf);
+            res = __fdiv_rn(block_sum_of(M, ws, [x, ld, k](int r) { return x[(size_t)r * ld + k]; }), Mf);
         }
     }
     if (tid == 0) a.out[q] = res;
@@ -184,10 +170,10 @@ __global__ void __launch_bounds__(EV_WIDE) k_eval_median(const EvalArgs a) {
 __global__ void __launch_bounds__(256) k_eval_tc(const EvalArgs a) {
 #pragma clang fp contract(off)
     constexpr int NC = EV_S * (EV_S + 1) / 2;        // 55 entries of the lower triangle, (i, j <= i) at i (i + 1) / 2 + j
-    __shared__ double wsum[4][NC];
+    __shared__ double wsum[NC][4];
     __shared__ double mean[EV_S];
     __shared__ double C[EV_S][EV_S];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, M = a.M;
+    const int tid = threadIdx.x, M = a.M;
     const float* x = a.qs1;
     double acc[NC];
 #pragma unroll
@@ -197,12 +183,9 @@ __global__ void __launch_bounds__(256) k_eval_tc(const EvalArgs a) {
         for (int k = 0; k < EV_S; ++k) acc[k] = acc[k] + (double)x[(size_t)r * EV_S + k];
     }
 #pragma unroll
-    for (int k = 0; k < EV_S; ++k) {
-        for (int off = 32; off >= 1; off >>= 1) acc[k] = acc[k] + __shfl_xor(acc[k], off, 64);
-        if (lane == 0) wsum[wave][k] = acc[k];
-    }
+    for (int k = 0; k < EV_S; ++k) wave_sum_put(acc[k], wsum[k]);
     __syncthreads();
-    if (tid < EV_S) mean[tid] = (((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid]) / (double)M;
+    if (tid < EV_S) mean[tid] = wave_sums_join(wsum[tid]) / (double)M;
     __syncthreads();
     double mu[EV_S];
 #pragma unroll
@@ -220,16 +203,13 @@ __global__ void __launch_bounds__(256) k_eval_tc(const EvalArgs a) {
     }
     __syncthreads();                    // (wsum is read above)
 #pragma unroll
-    for (int e = 0; e < NC; ++e) {
-        for (int off = 32; off >= 1; off >>= 1) acc[e] = acc[e] + __shfl_xor(acc[e], off, 64);
-        if (lane == 0) wsum[wave][e] = acc[e];
-    }
+    for (int e = 0; e < NC; ++e) wave_sum_put(acc[e], wsum[e]);
     __syncthreads();
     if (tid < NC) {
         int i = 0;
         while ((i + 1) * (i + 2) / 2 <= tid) ++i;
         const int j = tid - i * (i + 1) / 2;
-        const double c = (((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid]) / (double)(M - 1);
+        const double c = wave_sums_join(wsum[tid]) / (double)(M - 1);
         C[i][j] = c; C[j][i] = c;
     }
     __syncthreads();
@@ -278,7 +258,7 @@ __global__ void __launch_bounds__(EV_WIDE) k_eval_rho(const EvalArgs a) {
     }
 #pragma unroll
     for (int e = 0; e < 5; ++e) {
-        for (int off = 32; off >= 1; off >>= 1) s[e] += __shfl_xor(s[e], off, 64);
+        s[e] = wave_sum(s[e]);          // (exact: integers)
         if ((tid & 63) == 0) wsum[tid >> 6][e] = s[e];
     }
     __syncthreads();

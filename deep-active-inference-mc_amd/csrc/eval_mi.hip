@@ -18,20 +18,19 @@
 // No atomics, nothing passes between workgroups of one kernel, every loop is counted by M; 4 KiB of LDS per workgroup of the sweep.
 //
 // Reduction-order contract of the three sums of steps 1 and 2 (the mean, the sum of squared deviations, the sum of |v / sigma|), a function
-// of M alone, eval.hip's eval_block_sum with an fp64 accumulator: thread t of 256 adds elements t, t + 256, ... in ascending order into an
-// accumulator that starts at 0; the 64 lanes of a wave are combined by an xor butterfly (offsets 32, 16, ..., 1) and the four wave sums as
-// ((w0 + w1) + w2) + w3; one correctly rounded division by (double)M, a correctly rounded square root.  A prepared value is the same
-// expression wherever it is formed (mi_point), so every workgroup of a pair sees the same bits.
+// of M alone: block_sum.h's sum with an fp64 accumulator, then one correctly rounded division by (double)M, a correctly rounded square
+// root.  A prepared value is the same expression wherever it is formed (mi_point), so every workgroup of a pair sees the same bits.
 //
 // Step 5 has an order as well, because it cancels to rounding noise where the true score is 0 (four rows, or a constant column): psi comes
 // from a table the context uploads once (eval_mi_psi_table: harmonic numbers by compensated summation, IEEE operations only); a slice's
-// 256 values of psi(nx + 1) (0 for a thread past M) go through the butterfly and ((w0 + w1) + w2) + w3; the slices are added in ascending
+// 256 values of psi(nx + 1) (0 for a thread past M) go through block_sum; the slices are added in ascending
 // order from 0; MI = ((psi(M) + psi(k)) - sx / M) - sy / M, then max(0, .) and one rounding to fp32.
 //
 // Non-finite values: a NaN or an infinity in a column makes its sigma NaN, one in the noise makes that prepared value non-finite; every
 // workgroup of a pair stages all of the pair's prepared values, tests their bit patterns and writes NaN partial sums when it saw one, so
 // the pair's score is NaN and no other pair reads anything of it.
 #include "kernels.h"
+#include "block_sum.h"
 
 namespace efe {
 
@@ -45,20 +44,6 @@ __device__ __forceinline__ bool mi_nonfinite(double v) {
     return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
 }
 __device__ __forceinline__ double mi_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// the sum of f(i) over i < N in the contract's order; every thread of the 256-thread workgroup gets the result
-template <class F>
-__device__ __forceinline__ double mi_block_sum(int N, double* ws, F f) {
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int i = tid; i < N; i += 256) acc = acc + f(i);
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-    __syncthreads();                    // (ws may still be read from the previous sum)
-    if ((tid & 63) == 0) ws[tid >> 6] = acc;
-    __syncthreads();
-    return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
 
 // what a sweep workgroup knows of its pair: the columns, their scales and jitter amplitudes, the noise
 struct MiPair {
@@ -87,15 +72,15 @@ __global__ void __launch_bounds__(256) k_mi_cols(const EvalMiArgs a) {
     const float* v = c < MI_S ? a.s0 + c : a.S_real + (c - MI_S);
     const int ld = c < MI_S ? MI_S : EVAL_FACTORS;
     const double Md = (double)M;
-    const double mean = mi_block_sum(M, ws, [v, ld](int i) { return (double)v[(size_t)i * ld]; }) / Md;
-    const double var = mi_block_sum(M, ws, [v, ld, mean](int i) {
+    const double mean = block_sum_of(M, ws, [v, ld](int i) { return (double)v[(size_t)i * ld]; }) / Md;
+    const double var = block_sum_of(M, ws, [v, ld, mean](int i) {
 #pragma clang fp contract(off)
         const double d = (double)v[(size_t)i * ld] - mean;
         return d * d;
     }) / Md;
     double sigma = sqrt(var);
     if (sigma < 10.0 * 2.220446049250313e-16) sigma = 1.0;      // (a NaN stays)
-    const double mabs = mi_block_sum(M, ws, [v, ld, sigma](int i) { return fabs((double)v[(size_t)i * ld] / sigma); }) / Md;
+    const double mabs = block_sum_of(M, ws, [v, ld, sigma](int i) { return fabs((double)v[(size_t)i * ld] / sigma); }) / Md;
     if (threadIdx.x == 0) {
         a.ws[2 * c] = sigma;
         a.ws[2 * c + 1] = 1e-10 * (mabs < 1.0 ? 1.0 : mabs);    // (a NaN stays)
@@ -106,7 +91,8 @@ template <int K>
 __global__ void __launch_bounds__(MI_T) k_mi_sweep(const EvalMiArgs a) {
 #pragma clang fp contract(off)
     __shared__ double2 tile[MI_T];
-    __shared__ double wsum[MI_T / 64][2];
+    __shared__ double ws[2][4];
+    static_assert(MI_T == 256, "block_sum.h's workgroup");
     const int tid = threadIdx.x, M = a.M, pair = blockIdx.y, slice = blockIdx.x;
     const int li = pair / EVAL_FACTORS, fj = pair - li * EVAL_FACTORS;
     MiPair p;
@@ -167,14 +153,13 @@ __global__ void __launch_bounds__(MI_T) k_mi_sweep(const EvalMiArgs a) {
         a.counts[(size_t)(2 * pair) * M + i] = cx;
         a.counts[(size_t)(2 * pair + 1) * M + i] = cy;
     }
-    double px = live ? a.psi[cx + 1] : 0.0, py = live ? a.psi[cy + 1] : 0.0;       // (cx + 1 in [0, M]: entry 0, a NaN, is a poisoned point's)
-    for (int off = 32; off >= 1; off >>= 1) { px = px + __shfl_xor(px, off, 64); py = py + __shfl_xor(py, off, 64); }
-    if ((tid & 63) == 0) { wsum[tid >> 6][0] = px; wsum[tid >> 6][1] = py; }
-    const bool anybad = __syncthreads_or(bad) != 0;
+    wave_sum_put(live ? a.psi[cx + 1] : 0.0, ws[0]);       // (cx + 1 in [0, M]: entry 0, a NaN, is a poisoned point's)
+    wave_sum_put(live ? a.psi[cy + 1] : 0.0, ws[1]);
+    const bool anybad = __syncthreads_or(bad) != 0;        // (and block_sum's barrier between its halves, for both sums)
     if (tid != 0) return;
     double* part = a.ws + 32 + ((size_t)pair * EVAL_MI_SLICES + slice) * 2;
-    part[0] = anybad ? mi_nan() : ((wsum[0][0] + wsum[1][0]) + wsum[2][0]) + wsum[3][0];
-    part[1] = anybad ? mi_nan() : ((wsum[0][1] + wsum[1][1]) + wsum[2][1]) + wsum[3][1];
+    part[0] = anybad ? mi_nan() : wave_sums_join(ws[0]);
+    part[1] = anybad ? mi_nan() : wave_sums_join(ws[1]);
 }
 
 __global__ void __launch_bounds__(64) k_mi_finish(const EvalMiArgs a) {

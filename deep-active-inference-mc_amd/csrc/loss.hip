@@ -14,10 +14,10 @@
 // kl_naive is kl with mu2 = lv2 = 0 (torch.exp(0.0) = 1 exactly).  Sums over s_dim are sequential in k.
 //
 // Reduction-order contract of the BCE sum (independent of launch size, chunking and image layout): the elements are indexed by their
-// NCHW position i = c*H*W + p; thread t of the row's workgroup adds i = t, t + 256, t + 512, ... in ascending order into an fp32
-// accumulator; the 64 lanes of a wave are then combined by an xor butterfly (offsets 32, 16, ..., 1) and the four wave sums as
-// ((w0 + w1) + w2) + w3.  Memory-bound: per row 4 bytes of po1 and 4 of o1 per pixel (32 KiB at 1 x 64 x 64).
+// NCHW position i = c*H*W + p and summed by the row's workgroup in block_sum.h's order over N = C*H*W, in fp32.
+// Memory-bound: per row 4 bytes of po1 and 4 of o1 per pixel (32 KiB at 1 x 64 x 64).
 #include "kernels.h"
+#include "block_sum.h"
 
 namespace efe {
 
@@ -53,43 +53,26 @@ __global__ void __launch_bounds__(128) k_step_omega(const FeArgs a) {
     a.omega_out[r] = row_omega(a, r, a.omega_mode == 2 ? a.kl_pi[r] : 0.0f);
 }
 
-namespace {
-// the sum of f(x[r]) over r < M in the order the contract below states; every thread of the 256-thread workgroup gets the result
-template <class F>
-__device__ __forceinline__ float step_block_sum(const float* x, int M, float* ws, F f) {
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x;
-    float acc = 0.0f;
-    for (int r = tid; r < M; r += 256) acc = acc + f(x[r]);
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-    __syncthreads();                    // (ws may still be read from the previous sum)
-    if ((tid & 63) == 0) ws[tid >> 6] = acc;
-    __syncthreads();
-    return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-}  // namespace
-
 // k_step_means : EFE_STEP_MEANS = 8 workgroups of 256 threads, one per quantity.  Workgroup q < 7 writes means[q] = the batch mean of
 //                a.x[q] [M]; workgroup 7 writes the unbiased standard deviation of a.x[1] (omega), torch.std's two passes: the mean, then
 //                the sum of squared deviations from it, divided by M - 1 (0 / 0 = NaN at M = 1, as torch.std gives).
-// Reduction-order contract (a function of M alone): thread t adds rows t, t + 256, ... in ascending order into an fp32 accumulator that
-// starts at 0; the 64 lanes of a wave are combined by an xor butterfly (offsets 32, 16, ..., 1) and the four wave sums as
-// ((w0 + w1) + w2) + w3; one correctly rounded division by (float)M (by (float)(M - 1) for the variance) and a correctly rounded square
-// root.  Contraction off, no atomics.  Memory-bound: 4 M bytes read per workgroup (8 M by the last one).
+// Reduction-order contract (a function of M alone): block_sum.h's sum over the M rows in fp32, then one correctly rounded division by
+// (float)M (by (float)(M - 1) for the variance) and a correctly rounded square root.  Contraction off, no atomics.  Memory-bound: 4 M
+// bytes read per workgroup (8 M by the last one).
 __global__ void __launch_bounds__(256) k_step_means(const StepMeansArgs a) {
 #pragma clang fp contract(off)
     __shared__ float ws[4];
     const int q = blockIdx.x;
     const float* x = a.x[q < 7 ? q : 1];
     const float Mf = (float)a.M;
-    const float mean = __fdiv_rn(step_block_sum(x, a.M, ws, [](float v) { return v; }), Mf);
+    const float mean = __fdiv_rn(block_sum_of(a.M, ws, [x](int r) { return x[r]; }), Mf);
     if (q < 7) {
         if (threadIdx.x == 0) a.means[q] = mean;
         return;
     }
-    const float ss = step_block_sum(x, a.M, ws, [mean](float v) {
+    const float ss = block_sum_of(a.M, ws, [x, mean](int r) {
 #pragma clang fp contract(off)
-        const float d = v - mean;
+        const float d = x[r] - mean;
         return d * d;
     });
     if (threadIdx.x == 0) a.means[7] = __fsqrt_rn(__fdiv_rn(ss, (float)(a.M - 1)));
@@ -129,30 +112,20 @@ __global__ void __launch_bounds__(128) k_fe_top_mid(const FeArgs a) {
 __global__ void __launch_bounds__(256) k_fe_down(const FeArgs a, const float* po, int m0) {
 #pragma clang fp contract(off)
     const int r = m0 + (int)blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float ws[4];
     const float D1 = 1.00001f, D0 = 0.00001f;
     const int HW = a.HW, n = a.C * HW;
     const float* x = a.o1 + (size_t)r * n;
     const float* p = po + (size_t)blockIdx.x * (a.nhwc4 ? (size_t)HW * GEN_IMG_LD : (size_t)n);
-    float acc = 0.0f;
-    auto bce = [&](float xv, float pr) {
+    auto bce = [=](float xv, float pr) {
 #pragma clang fp contract(off)
         return xv * logf(D0 + pr) + (1.0f - xv) * logf(D1 - pr);
     };
-    if (a.nhwc4) {          // the generic path's store: pixel-major, channels padded to four
-        for (int i = tid; i < n; i += 256) {
-            const int c = i / HW, q = i - c * HW;
-            acc = acc + bce(x[i], p[(size_t)q * GEN_IMG_LD + c]);
-        }
-    } else {
-        for (int i = tid; i < n; i += 256) acc = acc + bce(x[i], p[i]);
-    }
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-    __shared__ float ws[4];
-    if (lane == 0) ws[wave] = acc;
-    __syncthreads();
-    if (tid != 0) return;
-    const float logpo1 = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+    const float logpo1 = a.nhwc4 ? block_sum_of(n, ws, [=](int i) {          // the generic path's store: pixel-major, channels padded to four
+        const int c = i / HW, q = i - c * HW;
+        return bce(x[i], p[(size_t)q * GEN_IMG_LD + c]);
+    }) : block_sum_of(n, ws, [=](int i) { return bce(x[i], p[i]); });
+    if (threadIdx.x != 0) return;
     const float w = a.omega_mode == 0 ? a.omega_in[r] : a.omega_scalar;
     float kls = 0.0f, kln = 0.0f;
     for (int k = 0; k < S_DIM_FE; ++k) {

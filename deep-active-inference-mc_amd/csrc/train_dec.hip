@@ -16,12 +16,13 @@
 //                K = CO per tap, all 9 taps (tap (ky, kx) reads the output pixels of parity (ky - 1, kx - 1) mod S); epilogue: the gate
 //                [y_prev > 0] read off the stored activation (none for d_h4).
 //   k_dect_out : layer 4 forward (Cout = 1, VALU) + sigmoid -> po1.
-//   k_dect_loss: one workgroup per row: nlogpo1 in k_fe_down's expression and reduction order (loss.hip), and
+//   k_dect_loss: one workgroup per row: nlogpo1 in k_fe_down's expression (loss.hip) and block_sum.h's order over the 4096 pixels, and
 //                g4 = -scale (o / (1e-5 + p) - (1 - o) / ((1e-5 + 1) - p)) ((1 - p) p)      finite when p rounds to 0 or 1.
 //   k_dect_dx4 : g3 = (sum_tap g4[iy - 1 + ky][ix - 1 + kx] W4[ci][tap]) [y3 > 0]   (VALU, Cout = 1).
 //   k_dect_wgrad<S, CI, CO, HIN> : dW[ci][co][tap] = sum_{m, iy, ix} x[m][ci][iy][ix] g[m][co][S iy - 1 + ky][S ix - 1 + kx] (in-range terms):
-//                MFMA with K = the positions; one wave owns a 16 ci x 16 co tile for all nine taps.
-//   k_dect_w4  : the 288 weights of layer 4, one workgroup per (ci, slab).     k_dect_bias : db[co] = sum g, one workgroup per (co, slab).
+//                MFMA with K = the positions; one wave owns a 16 ci x 16 co tile for all nine taps (train_conv.h's wgrad_mfma).
+//   k_dect_w4  : the 288 weights of layer 4, one workgroup per (ci, slab) (train_conv.h's wgrad_valu).
+//   k_conv_bias: db[co] = sum g, one workgroup per (co, slab); defined here, launched by train_enc.hip too (launch_conv_bias).
 //   k_slab_sum (train.hip) : gradient = ascending sum of the slabs.
 //
 // Forward order (NOT efe_decoder's Winograd / F(2, 2) forms: the activations agree with it to rounding, not bit for bit): per output and
@@ -30,33 +31,15 @@
 // The data gradient uses the same scheme over the output channels.
 //
 // Reduction-order contract of the parameter gradient (a function of M alone, no float atomics): G = min(M, DEC_TAIL_SLABS = 32) slabs of
-// P = 92 609 floats; row m belongs to slab m mod G and to row group m / DEC_TAIL_ROWS (= 64, a multiple of G).  Per element and slab:
-//   chunk  : one MFMA chain over 32 consecutive positions of one image (8 MFMAs; layer 4 and the biases: per thread the positions
-//            t, t + 256, ... ascending, 16 terms of the image for w4, then the xor butterfly 32, 16, .., 1 and ((w0 + w1) + w2) + w3),
-//   image  : the chunks of an image added in ascending order,
-//   group  : the images of the slab inside one row group added in ascending order (at most 2),
-//   slab   : the row groups added in ascending order;        gradient = ((slab_0 + slab_1) + slab_2) + ...
-// Each (element, slab) has ONE owning thread.  Two identical calls give identical bits.  Per-row outputs (po1, nlogpo1, d_h4, y_l) are
+// P = 92 609 floats; row m belongs to slab m mod G and to row group m / DEC_TAIL_ROWS (= 64, a multiple of G: at most 2 images per slab
+// and group).  Chunk, image, group and slab order: train_conv.h (layer 4's weights: 16 terms of the image per thread and tap).
+// Two identical calls give identical bits.  Per-row outputs (po1, nlogpo1, d_h4, y_l) are
 // computed per row with no cross-row term: they do not depend on which other rows are in the call (given the same scale).
-#include "kernels.h"
+#include "train_conv.h"
 
 namespace efe {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-namespace {
-
-__device__ __forceinline__ float block_sum_256(float acc, float* ws /*[4]*/) {
-#pragma clang fp contract(off)
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    const float s = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-    __syncthreads();
-    return s;
-}
-
-}  // namespace
+using cgrad::f32x4;
 
 // src: forward = the layer's input [rows][CI][HIN][HIN]; backward = the output gradient [rows][CO][S HIN][S HIN]
 // dst: forward = relu(output) [rows][CO][S HIN][S HIN]; backward = the input gradient [rows][CI][HIN][HIN], gated by gate > 0 (same shape) if given
@@ -180,13 +163,12 @@ __global__ void __launch_bounds__(256) k_dect_loss(const float* __restrict__ po,
     const float* p = po + (size_t)r * 4096;
     const float* x = o1 + (size_t)r * 4096;
     float* g = g4 + (size_t)r * 4096;
-    float acc = 0.0f;
-    for (int i = tid; i < 4096; i += 256) {
+    const float s = block_sum_of(4096, ws, [=](int i) {
+#pragma clang fp contract(off)
         const float xv = x[i], pr = p[i];
-        acc = acc + (xv * logf(D0 + pr) + (1.0f - xv) * logf(D1 - pr));
         g[i] = (-scale * (xv / (D0 + pr) - (1.0f - xv) / (D1 - pr))) * ((1.0f - pr) * pr);
-    }
-    const float s = block_sum_256(acc, ws);
+        return xv * logf(D0 + pr) + (1.0f - xv) * logf(D1 - pr);
+    });
     if (tid == 0) nlogpo1[r] = -s;
 }
 
@@ -224,125 +206,59 @@ __global__ void __launch_bounds__(256) k_dect_wgrad(const float* __restrict__ x,
 #pragma clang fp contract(off)
     constexpr int HOUT = S * HIN, HW = HIN * HIN;
     static_assert(HIN % 16 == 0 && HW % 32 == 0 && (CI / 16) * (CO / 16) % 4 == 0, "whole tiles");
-    const int G = gridDim.y, p = blockIdx.y;
-    if (p >= rows) return;
-    const int lane = threadIdx.x & 63, n = lane & 15, q = lane >> 4;
+    const int n = threadIdx.x & 15;
     const int pair = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     const int ci0 = 16 * (pair / (CO / 16)), co0 = 16 * (pair % (CO / 16));
-    f32x4 acc_g[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) acc_g[t] = (f32x4)(0.f);
-#pragma unroll 1
-    for (int r = p; r < rows; r += G) {
-        const float* xr = x + ((size_t)r * CI + ci0 + n) * HW;            // A(i = ci = n, k = position)
-        const float* gr = g + ((size_t)r * CO + co0 + n) * HOUT * HOUT;   // B(k = position, j = co = n)
-        f32x4 acc_i[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) acc_i[t] = (f32x4)(0.f);
-#pragma unroll 1
-        for (int pos0 = 0; pos0 < HW; pos0 += 32) {
-            f32x4 ch[9];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) ch[t] = (f32x4)(0.f);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int pos = pos0 + 16 * h + 4 * q;                    // MFMA step s contracts positions pos + s of the four q groups
-                const int iy = pos / HIN, ix = pos % HIN;
-                const float4 xv = *reinterpret_cast<const float4*>(xr + pos);
-                const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    const int gy = S * iy - 1 + ky;
-                    const bool oky = gy >= 0 && gy < HOUT;
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-                            const int gx = S * (ix + s) - 1 + kx;
-                            const bool ok = oky && gx >= 0 && gx < HOUT;
-                            float bv = gr[ok ? gy * HOUT + gx : 0];
-                            bv = ok ? bv : 0.0f;
-                            ch[3 * ky + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[s], bv, ch[3 * ky + kx], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 9; ++t) acc_i[t] = acc_i[t] + ch[t];
-        }
-#pragma unroll
-        for (int t = 0; t < 9; ++t) acc_g[t] = acc_g[t] + acc_i[t];
-    }
-    float* slab = slab_w + (size_t)p * P;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float* d = slab + ((size_t)(ci0 + 4 * q + e) * CO + co0 + n) * 9 + t;          // D(i = 4 q + e, j = n)
-            *d = first ? acc_g[t][e] : *d + acc_g[t][e];
-        }
+    cgrad::wgrad_mfma<HW>(rows, ci0, co0, CO, slab_w + (size_t)blockIdx.y * P, first,
+        [=](int r, int pos) {                                             // A(i = ci = n, k = position)
+            return *reinterpret_cast<const float4*>(x + ((size_t)r * CI + ci0 + n) * HW + pos);
+        },
+        [=](int r, int pos, int ky, int kx) {                             // B(k = position, j = co = n)
+            const int gy = S * (pos / HIN) - 1 + ky, gx = S * (pos % HIN) - 1 + kx;
+            const bool ok = gy >= 0 && gy < HOUT && gx >= 0 && gx < HOUT;
+            const float bv = (g + ((size_t)r * CO + co0 + n) * HOUT * HOUT)[ok ? gy * HOUT + gx : 0];
+            return ok ? bv : 0.0f;
+        });
 }
 
 // layer 4's weights: dW4[ci][tap] = sum y3[m][ci][iy][ix] g4[m][iy - 1 + ky][ix - 1 + kx]; grid (32, G)
 __global__ void __launch_bounds__(256) k_dect_w4(const float* __restrict__ y3, const float* __restrict__ g4, float* __restrict__ slab_w,
                                                  int rows, int P, int first) {
 #pragma clang fp contract(off)
-    __shared__ float ws[4];
-    const int G = gridDim.y, p = blockIdx.y, ci = blockIdx.x, tid = threadIdx.x;
-    if (p >= rows) return;
-    float acc_g = 0.0f;          // thread t < 9 owns tap t
-#pragma unroll 1
-    for (int r = p; r < rows; r += G) {
-        const float* x = y3 + ((size_t)r * 32 + ci) * 4096;
+    const int ci = blockIdx.x;
+    cgrad::wgrad_valu(rows, 4096, slab_w + (size_t)blockIdx.y * P + ci * 9, first, [=](int r, int i, float& c, float (&t9)[9]) {
         const float* g = g4 + (size_t)r * 4096;
-        float a9[9];
+        const int iy = i >> 6, ix = i & 63;
+        c = y3[((size_t)r * 32 + ci) * 4096 + i];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) a9[t] = 0.0f;
-#pragma unroll 1
-        for (int i = tid; i < 4096; i += 256) {
-            const int iy = i >> 6, ix = i & 63;
-            const float xv = x[i];
+        for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int gy = iy - 1 + ky, gx = ix - 1 + kx;
-                    const bool ok = gy >= 0 && gy < 64 && gx >= 0 && gx < 64;
-                    float gv = g[ok ? gy * 64 + gx : 0];
-                    gv = ok ? gv : 0.0f;
-                    a9[3 * ky + kx] = fmaf(xv, gv, a9[3 * ky + kx]);
-                }
-        }
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const float s = block_sum_256(a9[t], ws);
-            if (tid == t) acc_g = acc_g + s;
-        }
-    }
-    if (tid < 9) {
-        float* d = slab_w + (size_t)p * P + ci * 9 + tid;
-        *d = first ? acc_g : *d + acc_g;
-    }
+            for (int kx = 0; kx < 3; ++kx) {
+                const int gy = iy - 1 + ky, gx = ix - 1 + kx;
+                const bool ok = gy >= 0 && gy < 64 && gx >= 0 && gx < 64;
+                const float gv = g[ok ? gy * 64 + gx : 0];
+                t9[3 * ky + kx] = ok ? gv : 0.0f;
+            }
+    });
 }
 
-// db[co] = sum_{m, pixels} g[m][co][.]; grid (CO, G)
-__global__ void __launch_bounds__(256) k_dect_bias(const float* __restrict__ g, int CO, int HW, float* __restrict__ slab_b, int rows, int P, int first) {
+// db[co] = sum_{m, positions} g[m][co][.]; grid (CO, G); slab p = slab_b + p P
+__global__ void __launch_bounds__(256) k_conv_bias(const float* __restrict__ g, int CO, int HW, float* __restrict__ slab_b, int rows, int P, int first) {
 #pragma clang fp contract(off)
     __shared__ float ws[4];
-    const int G = gridDim.y, p = blockIdx.y, co = blockIdx.x, tid = threadIdx.x;
+    const int G = gridDim.y, p = blockIdx.y, co = blockIdx.x;
     if (p >= rows) return;
     float acc_g = 0.0f;
 #pragma unroll 1
     for (int r = p; r < rows; r += G) {
         const float* gp = g + ((size_t)r * CO + co) * HW;
-        float a = 0.0f;
-        for (int i = tid; i < HW; i += 256) a = a + gp[i];
-        acc_g = acc_g + block_sum_256(a, ws);
+        acc_g = acc_g + block_sum_of(HW, ws, [gp](int i) { return gp[i]; });
     }
-    if (tid == 0) {
-        float* d = slab_b + (size_t)p * P + co;
-        *d = first ? acc_g : *d + acc_g;
-    }
+    if (threadIdx.x == 0) cgrad::slab_put(slab_b + (size_t)p * P + co, acc_g, first);
+}
+
+void launch_conv_bias(const float* g, int CO, int HW, float* slab_b, int rows, int G, int P, int first, hipStream_t st) {
+    hipLaunchKernelGGL(k_conv_bias, dim3(CO, G), dim3(256), 0, st, g, CO, HW, slab_b, rows, P, first);
 }
 
 namespace {
@@ -358,7 +274,7 @@ void wgrad(const float* x, const float* g, float* slab_w, int rows, int G, int f
     hipLaunchKernelGGL((k_dect_wgrad<S, CI, CO, HIN>), dim3((CI / 16) * (CO / 16) / 4, G), dim3(256), 0, st, x, g, slab_w, rows, DEC_TAIL_P, first);
 }
 void bias(const float* g, int CO, int HW, float* slab_b, int rows, int G, int first, hipStream_t st) {
-    hipLaunchKernelGGL(k_dect_bias, dim3(CO, G), dim3(256), 0, st, g, CO, HW, slab_b, rows, DEC_TAIL_P, first);
+    launch_conv_bias(g, CO, HW, slab_b, rows, G, DEC_TAIL_P, first, st);
 }
 
 }  // namespace

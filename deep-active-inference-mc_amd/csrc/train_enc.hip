@@ -24,8 +24,9 @@
 //   k_ench_bwd   : the head backward over one 16-row tile from the upstream pair (g_mean, g_logvar), built of train_mlp.h's passes; ends in
 //                  g4 = dL / da4 = (g_0 W9) [y4 > 0].  LDS 56 064 B: G3 | A | U, U = a 256-wide activation, then the 576-wide y4 tile.
 //   k_enc_wgrad<CI, CO, HIN> : dW[co][ci][tap] = sum_{m, oy, ox} g[m][co][oy][ox] x[m][ci][2 oy + ky][2 ox + kx], MFMA with K = the
-//                  positions; one wave owns a 16 co x 16 ci tile for all nine taps.
-//   k_enc_w1     : the 288 weights of layer 1, one workgroup per (co, slab) (VALU).      k_enc_bias : db[co] = sum g, per (co, slab).
+//                  positions; one wave owns a 16 co x 16 ci tile for all nine taps (train_conv.h's wgrad_mfma).
+//   k_enc_w1     : the 288 weights of layer 1, one workgroup per (co, slab) (train_conv.h's wgrad_valu).
+//   k_conv_bias (train_dec.hip, launch_conv_bias) : db[co] = sum g, per (co, slab).
 //   k_enc_dx<CI, CO, HIN>    : dx[ci][iy][ix] = (sum_{co, ky, kx : iy = 2 oy + ky, ix = 2 ox + kx} g[co][oy][ox] W[co][ci][ky][kx]) [x > 0]:
 //                  one wave = 16 input channels x 16 positions of ONE input parity class (iy & 1, ix & 1), which fixes the taps that reach
 //                  it (4, 2, 2 or 1 of the 9), K = the output channels per tap.  No gradient with respect to the image is formed.
@@ -42,15 +43,14 @@
 // thread; two identical calls give identical bits):
 //   rows     : row group g = rows 64 g .. 64 g + 63 (DEC_TAIL_ROWS, so that the composed call interleaves with the decoder's groups),
 //              16-row tile t = rows 16 t .. 16 t + 15; rows >= M contribute exact zeros.
-//   convs    : GC = min(M, ENC_CONV_SLABS = 32) slabs of ENC_CONV_P = 64 992 floats; row m belongs to slab m mod GC.  Per element and slab:
-//              chunk = one MFMA chain over 32 consecutive positions of one image (8 MFMAs; layer 1 and the biases: per thread the positions
-//              t, t + 256, .. ascending, then the xor butterfly 32, 16, .., 1 and ((w0 + w1) + w2) + w3); image = its chunks ascending;
-//              group = the images of the slab inside one row group ascending (at most 2); slab = the row groups ascending.
+//   convs    : GC = min(M, ENC_CONV_SLABS = 32) slabs of ENC_CONV_P = 64 992 floats; row m belongs to slab m mod GC (at most 2 images per
+//              slab and group).  Chunk, image, group and slab order: train_conv.h; the last chunk of an image is ragged.
 //   head     : GH = min(ceil(M / 16), ENC_HEAD_SLABS = 4) slabs of ENC_HEAD_P = 284 436 floats; tile t adds its 16-term chain (db: the
 //              sequential sum of its rows) to slab t mod 4, tiles ascending (train_mlp.h's tile and gate rules).
 //   gradient = ((slab_0 + slab_1) + slab_2) + ... ascending (k_slab_sum).
 // The per-row outputs (mean, logvar, y1..y4, h1..h3, g_mean, g_logvar) depend on that row and its global row id only.
 #include "train_mlp.h"
+#include "train_conv.h"
 
 namespace efe {
 
@@ -61,16 +61,6 @@ namespace {
 constexpr int HLD = 256 + 4;       // LDS row stride of a 256-wide activation
 constexpr int XLD = 576 + 4;       // ... of the y4 tile
 constexpr int GLD = 32 + 4;        // ... of the upstream tile (mean | logvar, zero from column 20)
-
-__device__ __forceinline__ float block_sum_256(float acc, float* ws /*[4]*/) {
-#pragma clang fp contract(off)
-    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    const float s = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-    __syncthreads();
-    return s;
-}
 
 // a [16][256] activation tile of the group into LDS, zero beyond the group's rows; thread = column
 __device__ __forceinline__ void load_tile256(float* dst, const float* src, int r0, int rows, int tid) {
@@ -270,116 +260,43 @@ __global__ void __launch_bounds__(256) k_enc_wgrad(const float* __restrict__ x, 
 #pragma clang fp contract(off)
     constexpr int HOUT = (HIN - 1) / 2, HW = HOUT * HOUT, XW = HIN * HIN;
     static_assert((CI / 16) * (CO / 16) % 4 == 0 && 2 * HOUT + 1 == HIN, "whole workgroups, odd extent");
-    const int G = gridDim.y, p = blockIdx.y;
-    if (p >= rows) return;
-    const int lane = threadIdx.x & 63, n = lane & 15, q = lane >> 4;
+    const int n = threadIdx.x & 15;
     const int pair = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     const int co0 = 16 * (pair / (CI / 16)), ci0 = 16 * (pair % (CI / 16));
-    f32x4 acc_g[9];
+    // a position >= HW of the ragged last chunk: zero into both operands, the address clamped to element 0 of the image
+    cgrad::wgrad_mfma<HW>(rows, co0, ci0, CI, slab_w + (size_t)blockIdx.y * ENC_CONV_P, first,
+        [=](int r, int pos) {                                             // A(i = co = n, k = position)
+            const float* gr = g + ((size_t)r * CO + co0 + n) * HW;
+            float av[4];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) acc_g[t] = (f32x4)(0.f);
-#pragma unroll 1
-    for (int r = p; r < rows; r += G) {
-        const float* gr = g + ((size_t)r * CO + co0 + n) * HW;            // A(i = co = n, k = position)
-        const float* xr = x + ((size_t)r * CI + ci0 + n) * XW;            // B(k = position, j = ci = n)
-        f32x4 acc_i[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) acc_i[t] = (f32x4)(0.f);
-#pragma unroll 1
-        for (int pos0 = 0; pos0 < HW; pos0 += 32) {
-            f32x4 ch[9];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) ch[t] = (f32x4)(0.f);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {                             // MFMA step s contracts positions pos0 + 16 h + 4 q + s of the four q groups
-                    const int pos = pos0 + 16 * h + 4 * q + s;
-                    const bool ok = pos < HW;
-                    const int pc = ok ? pos : 0, oy = pc / HOUT, ox = pc - oy * HOUT;
-                    float av = gr[pc];
-                    av = ok ? av : 0.0f;
-                    const float* xp = xr + (2 * oy) * HIN + 2 * ox;
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                        for (int kx = 0; kx < 3; ++kx) {
-                            float bv = xp[ky * HIN + kx];
-                            bv = ok ? bv : 0.0f;
-                            ch[3 * ky + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, ch[3 * ky + kx], 0, 0, 0);
-                        }
-                }
+            for (int s = 0; s < 4; ++s) {
+                const bool ok = pos + s < HW;
+                av[s] = gr[ok ? pos + s : 0];
+                av[s] = ok ? av[s] : 0.0f;
             }
-#pragma unroll
-            for (int t = 0; t < 9; ++t) acc_i[t] = acc_i[t] + ch[t];
-        }
-#pragma unroll
-        for (int t = 0; t < 9; ++t) acc_g[t] = acc_g[t] + acc_i[t];
-    }
-    float* slab = slab_w + (size_t)p * ENC_CONV_P;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float* d = slab + ((size_t)(co0 + 4 * q + e) * CI + ci0 + n) * 9 + t;            // D(i = 4 q + e, j = n)
-            *d = first ? acc_g[t][e] : *d + acc_g[t][e];
-        }
+            return make_float4(av[0], av[1], av[2], av[3]);
+        },
+        [=](int r, int pos, int ky, int kx) {                             // B(k = position, j = ci = n)
+            const bool ok = pos < HW;
+            const int pc = ok ? pos : 0, oy = pc / HOUT, ox = pc - oy * HOUT;
+            const float bv = (x + ((size_t)r * CI + ci0 + n) * XW)[(2 * oy + ky) * HIN + 2 * ox + kx];
+            return ok ? bv : 0.0f;
+        });
 }
 
 // layer 1's weights: dW1[co][tap] = sum g1[m][co][oy][ox] o[m][2 oy + ky][2 ox + kx]; grid (32, G)
 __global__ void __launch_bounds__(256) k_enc_w1(const float* __restrict__ o, const float* __restrict__ g1, float* __restrict__ slab_w, int rows, int first) {
 #pragma clang fp contract(off)
-    __shared__ float ws[4];
-    const int G = gridDim.y, p = blockIdx.y, co = blockIdx.x, tid = threadIdx.x;
-    if (p >= rows) return;
-    float acc_g = 0.0f;          // thread t < 9 owns tap t
-#pragma unroll 1
-    for (int r = p; r < rows; r += G) {
-        const float* x = o + (size_t)r * 4096;
-        const float* g = g1 + ((size_t)r * 32 + co) * 961;
-        float a9[9];
+    const int co = blockIdx.x;
+    cgrad::wgrad_valu(rows, 961, slab_w + (size_t)blockIdx.y * ENC_CONV_P + co * 9, first, [=](int r, int i, float& c, float (&t9)[9]) {
+        const int oy = i / 31, ox = i - oy * 31;
+        const float* xp = o + (size_t)r * 4096 + (2 * oy) * 64 + 2 * ox;
+        c = g1[((size_t)r * 32 + co) * 961 + i];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) a9[t] = 0.0f;
-#pragma unroll 1
-        for (int i = tid; i < 961; i += 256) {
-            const int oy = i / 31, ox = i - oy * 31;
-            const float gv = g[i];
-            const float* xp = x + (2 * oy) * 64 + 2 * ox;
+        for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) a9[3 * ky + kx] = fmaf(gv, xp[ky * 64 + kx], a9[3 * ky + kx]);
-        }
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const float s = block_sum_256(a9[t], ws);
-            if (tid == t) acc_g = acc_g + s;
-        }
-    }
-    if (tid < 9) {
-        float* d = slab_w + (size_t)p * ENC_CONV_P + co * 9 + tid;
-        *d = first ? acc_g : *d + acc_g;
-    }
-}
-
-// db[co] = sum_{m, positions} g[m][co][.]; grid (CO, G)
-__global__ void __launch_bounds__(256) k_enc_bias(const float* __restrict__ g, int CO, int HW, float* __restrict__ slab_b, int rows, int first) {
-#pragma clang fp contract(off)
-    __shared__ float ws[4];
-    const int G = gridDim.y, p = blockIdx.y, co = blockIdx.x, tid = threadIdx.x;
-    if (p >= rows) return;
-    float acc_g = 0.0f;
-#pragma unroll 1
-    for (int r = p; r < rows; r += G) {
-        const float* gp = g + ((size_t)r * CO + co) * HW;
-        float a = 0.0f;
-        for (int i = tid; i < HW; i += 256) a = a + gp[i];
-        acc_g = acc_g + block_sum_256(a, ws);
-    }
-    if (tid == 0) {
-        float* d = slab_b + (size_t)p * ENC_CONV_P + co;
-        *d = first ? acc_g : *d + acc_g;
-    }
+            for (int kx = 0; kx < 3; ++kx) t9[3 * ky + kx] = xp[ky * 64 + kx];
+    });
 }
 
 // g [rows][CO][HOUT][HOUT] -> dx [rows][CI][HIN][HIN], gated by gate > 0 (the layer's stored input, same shape)
@@ -475,7 +392,7 @@ void dgrad(const float* g, const float* W, const float* gate, float* dx, int row
     hipLaunchKernelGGL((k_enc_dx<CI, CO, HIN>), dim3((unsigned)((rows * per_row + 3) / 4)), dim3(256), 0, st, g, W, gate, dx, rows);
 }
 void bias(const float* g, int CO, int HW, float* slab_b, int rows, int G, int first, hipStream_t st) {
-    hipLaunchKernelGGL(k_enc_bias, dim3(CO, G), dim3(256), 0, st, g, CO, HW, slab_b, rows, first);
+    launch_conv_bias(g, CO, HW, slab_b, rows, G, ENC_CONV_P, first, st);
 }
 
 }  // namespace

@@ -2,7 +2,7 @@
 Kraskov-Stoegbauer-Grassberger k-nearest-neighbour estimator as scikit-learn's mutual_info_regression defines it for float64 columns,
 steps 1-5 of the definition in that file's header, by brute force.  A plain module, like eval_ref.py.
 
-The order of the sums is a parameter: 'numpy' (np.mean's pairwise sums) or 'device' (a replay of the kernels' contract: 256 strided fp64
+The order of the sums is a parameter: 'numpy' (np.mean's pairwise sums) or 'device' (a replay of csrc/block_sum.h's contract: 256 strided fp64
 accumulators, an xor butterfly over each wave of 64, ((w0 + w1) + w2) + w3; for step 5 one such sum per slice of 256 points, the slices in
 ascending order).  With 'device' the prepared columns are the bits the kernels form, so the neighbour counts can be compared exactly, and
 so is the score, also where it cancels to rounding noise (a true score of 0).  psi is the engine's table in both.  The sweep is chunked
@@ -19,7 +19,7 @@ def factor_columns(r, n):
 
 
 def device_sum(v):
-    """the sum of v in the kernels' order (mi_block_sum): a function of len(v) alone"""
+    """the sum of v in the kernels' order (csrc/block_sum.h's block_sum_of in fp64): a function of len(v) alone"""
     v = np.asarray(v, dtype=np.float64).reshape(-1)
     rows = -(-v.size // 256)
     pad = np.zeros(rows * 256)

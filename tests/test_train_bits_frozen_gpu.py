@@ -4,7 +4,11 @@ two decoder-gradient entry points were merged on the host.  That change leaves e
 a stored activation, a gradient, an updated weight or an Adam moment may move.  The shapes are the smallest that still reach a partial
 tile, a second workgroup, a second tile of one workgroup (the add path of the slabs), the padded pi_dim 3 geometry, a second 64-row group
 of the decoder and the decoder tail without its head (tools/make_train_bits.py lists them).  Arrays above 16 384 elements are held by the
-SHA-256 of their bytes and by every 4 099th element; the decoder's gradient is held per state_dict key."""
+SHA-256 of their bytes and by every 4 099th element; the decoder's gradient is held per state_dict key.
+The enc_*, down_m17 and step_m257 cases were written on the build of the commit BEFORE csrc/block_sum.h and csrc/train_conv.h existed
+(every older entry came out of that run array-equal): they hold the encoder's gradient and stored activations at one slab, at 32 slabs
+with a second image in slab 0 and at a second row group, grad_down's composition (k_fe_down beside k_dect_loss, both gradients in one
+array), and one whole training step with k_step_means' eight statistics and every trained weight and Adam moment."""
 import importlib.util
 import os
 

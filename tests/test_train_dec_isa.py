@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TAP = ['k_dect_tap<1, 64, 64, 16, false>', 'k_dect_tap<2, 64, 64, 16, false>', 'k_dect_tap<2, 64, 32, 32, false>',
        'k_dect_tap<1, 64, 64, 16, true>', 'k_dect_tap<2, 64, 64, 16, true>', 'k_dect_tap<2, 64, 32, 32, true>']
 WGRAD = ['k_dect_wgrad<1, 64, 64, 16>', 'k_dect_wgrad<2, 64, 64, 16>', 'k_dect_wgrad<2, 64, 32, 32>']
-VALU = ['k_dect_out', 'k_dect_loss', 'k_dect_dx4', 'k_dect_w4', 'k_dect_bias']
+VALU = ['k_dect_out', 'k_dect_loss', 'k_dect_dx4', 'k_dect_w4', 'k_conv_bias']
 
 
 @pytest.fixture(scope='module')

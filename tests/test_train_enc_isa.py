@@ -9,7 +9,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SHAPES = ('32, 32, 31', '32, 64, 15', '64, 64, 7')          # <CI, CO, HIN> of layers 2, 3, 4
-LDS = {'k_enc_conv1': 0, 'k_ench_fwd': 3 * 16 * 260 * 4, 'k_ench_bwd': (16 * 36 + 16 * 260 + 16 * 580) * 4, 'k_enc_w1': 16, 'k_enc_bias': 16,
+LDS = {'k_enc_conv1': 0, 'k_ench_fwd': 3 * 16 * 260 * 4, 'k_ench_bwd': (16 * 36 + 16 * 260 + 16 * 580) * 4, 'k_enc_w1': 16, 'k_conv_bias': 16,
        'k_down_latent': 0}
 LDS.update({f'{k}<{s}>': 0 for k in ('k_enc_conv', 'k_enc_wgrad', 'k_enc_dx') for s in SHAPES})
 

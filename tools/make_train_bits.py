@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Writes tests/golden/train_bits.npz: the outputs of the training calls under csrc/train_mlp.h's order contract (habit net, transition
-net, the decoder's dense head) and of the decoder-gradient host path, stored bit for bit, so that a change that claims to leave
+net, the decoder's dense head), of the decoder-gradient host path and of the calls under csrc/train_conv.h's and csrc/block_sum.h's (the
+encoder's gradient, grad_down, one whole training step), stored bit for bit, so that a change that claims to leave
 every sum's order alone can be held to it (tests/test_train_bits_frozen_gpu.py).
 
 Run it ONCE, on the GPU, on the build of the commit BEFORE the kernel change (the fixture tests new code against its parent, never
@@ -20,12 +21,21 @@ these kernels can still go wrong:
   dec_m1 / dec_m17 / dec_m65     loss.grad_decoder(return_activations=True), stage 5, row_offset 3: two tiles and two slabs; a second
                                  64-row group (first = 0 in k_dech_w4grad and in the slabs)
   dectail_m5                     loss.grad_decoder_convs on the first 5 rows of dec_m17's h4: the host path without the head
+  enc_m1 / enc_m33 / enc_m65     loss.grad_encoder(return_activations=True), stage 5, row_offset 3.  G = 1: the one slab is the gradient (the
+                                 `first` store alone) and the head has one ragged tile; 32 slabs, slab 0 walking a second image (the add
+                                 of the row loop) and a third, ragged 16-row head tile; a second 64-row group (first = 0: the
+                                 read-add-write path of the slabs in all three parameter-gradient passes)
+  down_m17                       loss.grad_down on device normals: k_dect_loss and k_fe_down on the same images, k_down_latent, the
+                                 encoder's and the decoder's gradient in one array
+  step_m257                      loss.train_step, one step, omega derived: k_step_means with a second strided add in thread 0 alone, and
+                                 every trained weight and Adam moment behind it
 
 Storage: an array of up to 16 384 elements is stored whole under '<case>.<name>'; a larger one as '<case>.<name>.sha256' (the digest of
 its little-endian float32 bytes) and '<case>.<name>.every4099' (elements 0, 4099, 8198, ... of the flattened array).  The decoder's
 gradient (4.4 M floats; 92 609 for the tail alone) is stored in that form per state_dict key, '<case>.grad.<key>.*', whatever the key's size,
 so that a failure names the layer.  (16 384, not 65 536: with the larger bound the seven habit-net vectors of 18 436 floats and dec_m1's
-y2 are stored whole and the file is 888 KB; with this one it is 182 KB, below MAX_BYTES, the 512 KiB the other training fixtures keep to.)"""
+y2 are stored whole and the file is 888 KB; with this one it was 182 KB, and is 364 KB with the enc_*, down_* and step_* cases, below
+MAX_BYTES, the 512 KiB the other training fixtures keep to.)"""
 import hashlib
 import os
 import sys
@@ -38,7 +48,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 DEFAULT_OUT = os.path.join(ROOT, 'tests', 'golden', 'train_bits.npz')
 CASES = ('top_m3', 'top_m17', 'top_m1025', 'top_pi3_m17', 'top_step_m17', 'mid_m3', 'mid_m17', 'mid_m129', 'mid_pi3_m17', 'mid_step_m17',
-         'dec_m1', 'dec_m17', 'dec_m65', 'dectail_m5')
+         'dec_m1', 'dec_m17', 'dec_m65', 'dectail_m5', 'enc_m1', 'enc_m33', 'enc_m65', 'down_m17', 'step_m257')
 WHOLE, STRIDE = 16384, 4099
 MAX_BYTES = 512 * 1024
 KEY = dict(stage=5, row_offset=3)
@@ -73,6 +83,26 @@ def _mid_batch(seed, M, A=4):
 def _dec_batch(seed, M):
     r = np.random.RandomState(seed)
     return r.randn(M, 10).astype(np.float32), (r.uniform(size=(M, 1, 64, 64)) < 0.1).astype(np.float32)
+
+
+def _enc_batch(seed, M):
+    r = np.random.RandomState(seed)
+    o = (r.uniform(size=(M, 1, 64, 64)) < 0.1).astype(np.float32)
+    return o, r.randn(M, 10).astype(np.float32), r.randn(M, 10).astype(np.float32)
+
+
+def _down_batch(seed, M):
+    r = np.random.RandomState(seed)
+    o1 = (r.uniform(size=(M, 1, 64, 64)) < 0.1).astype(np.float32)
+    return o1, r.randn(M, 10).astype(np.float32), (0.5 * r.randn(M, 10) - 1.0).astype(np.float32), r.uniform(1.5, 2.5, M).astype(np.float32)
+
+
+def _step_batch(seed, M, A=4):
+    r = np.random.RandomState(seed)
+    o0, o1 = ((r.uniform(size=(M, 1, 64, 64)) < 0.1).astype(np.float32) for _ in range(2))
+    z = (2.0 * r.randn(M, A)).astype(np.float64)
+    z -= z.max(1, keepdims=True)
+    return o0, o1, np.eye(A, dtype=np.float32)[r.randint(0, A, M)], (z - np.log(np.exp(z).sum(1, keepdims=True))).astype(np.float32)
 
 
 def _step(module, opt):
@@ -117,6 +147,23 @@ def run_cases(device='cuda:0'):
         if M == 17:
             nl, po1, d_h4, g = loss.grad_decoder_convs(m.model_down, d['h4'][:5], o1[:5])
             out['dectail_m5'] = {'nlogpo1': _c(nl), 'po1': _c(po1), 'd_h4': _c(d_h4), **{'grad.' + k: _c(v) for k, v in g.items()}}
+    for M in (1, 33, 65):
+        mean, lv, g, act = loss.grad_encoder(m.model_down, *_enc_batch(600 + M, M), return_activations=True, **KEY)
+        d = {'qs_mean': _c(mean), 'qs_logvar': _c(lv)}
+        d.update({n: _c(a) for n, a in zip(('y1', 'y2', 'y3', 'y4', 'h1', 'h2', 'h3'), act)})
+        d.update({'grad.' + k: _c(v) for k, v in g.items()})
+        out[f'enc_m{M}'] = d
+    F, (nl, kls, kln), po1, qs1, qm, qv, g, (gm, gv) = loss.grad_down(m.model_down, *_down_batch(717, 17), return_upstream=True, **KEY)
+    out['down_m17'] = {'F_down': _c(F), 'nlogpo1': _c(nl), 'kl_s': _c(kls), 'kl_naive': _c(kln), 'po1': _c(po1), 'qs1': _c(qs1),
+                       'qs1_mean': _c(qm), 'qs1_logvar': _c(qv), 'g_mean': _c(gm), 'g_logvar': _c(gv),
+                       **{'grad.' + k: _c(v) for k, v in g.items()}}
+    ms = model()
+    opts = {k: daimc_amd.Adam(getattr(ms, 'model_' + k), lr=1e-3) for k in ('top', 'mid', 'down')}
+    res = loss.train_step(ms, *_step_batch(1057, 257), opts, **KEY)
+    d = {k: _c(v) for k, v in res._asdict().items()}
+    for part, opt in opts.items():
+        d.update({f'{part}.{k}': v for k, v in _step(getattr(ms, 'model_' + part), opt).items()})
+    out['step_m257'] = d
     torch.cuda.synchronize()
     assert tuple(sorted(out)) == tuple(sorted(CASES))
     return out
