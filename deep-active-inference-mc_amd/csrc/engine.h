@@ -97,6 +97,8 @@ struct efe_ctx {
     float dec_bf = 0.f;
     float* dec_raw = nullptr;      // the whole po_net unpacked, flat in parameters() order (kernels.h DH_*, then DT_*): train_dec_head.hip reads it
     float* dect_raw = nullptr;     // its tail po_net.13 / .15 / .17 / .19 (= dec_raw + DEC_HEAD_P): train_dec.hip reads it
+    float* dect_raw_g = nullptr;   // the same tail at ANY geometry, [92 320 + 289 chan] (DecTailGeo): train_dec_g.hip reads it.  = dect_raw at 1 x 64 x 64
+                                   // (so that it follows ModelDown's optimiser steps), else a buffer of the current commit
     float* enc_raw = nullptr;      // the whole qs_net unpacked, flat in parameters() order (kernels.h EQ_*): train_enc.hip reads it
     // ModelDown's master copy at 1 x 64 x 64 (owned: it outlives a re-commit, as TrainPart::master): [DOWN_P], qs_net then po_net, so
     // enc_raw = down_master and dec_raw = down_master + ENC_P.  An optimiser step (train_down.hip) writes it and rebuilds every packed form

@@ -92,6 +92,21 @@ int train_mid_run(efe_ctx* ctx, const char* who, const float* s0, const float* p
 // the dense head's side of the call: its input, the keys of its four dropout masks, its outputs (all nullable but s and nz)
 struct DecHeadIO { const float* s; const efe_noise* nz; float* d_s; float *h1, *h2, *h3, *h4; };
 
+// what every decoder-gradient call refuses, in this order and before its first launch: M, the required pointers, the geometry, the
+// split-operand options, the scale (negative = beta_o / M, written back)
+int dec_grad_checks(efe_ctx* ctx, const char* who, int M, bool ptrs, const char* ptr_msg, bool geometry, float& scale, float beta_o) {
+    const std::string w(who);
+    if (M <= 0) return ctx->fail(w + ": M must be >= 1");
+    if (!ptrs) return ctx->fail(w + ptr_msg);
+    if (!geometry) return ctx->fail(w + ": built for the 1 x 64 x 64 geometry only");
+    if (ctx->mfma_bf16x3) return ctx->fail(w + ": not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+    if (!(scale >= 0.0f)) {
+        if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail(w + ": scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
+        scale = beta_o / (float)M;
+    }
+    return 0;
+}
+
 // The decoder's gradient as the row groups of one call: open() checks the arguments and takes the scratch, group(m0) queues the forward and
 // backward of rows [m0, m0 + rows(m0)), close() joins the slabs.  efe_dec_tail_grad, efe_dec_grad and efe_down_grad (which runs the
 // encoder's group around each of the decoder's) share it.
@@ -114,16 +129,9 @@ int DecGrad::open(efe_ctx* ctx_, const char* who, const DecHeadIO* hd_, const fl
                   float* nlogpo1_, float* po1_, float* grad_, float* y1_, float* y2_, float* y3_, hipStream_t st_) {
     ctx = ctx_; hd = hd_; h4 = h4_; d_h4 = d_h4_; o1 = o1_; M = M_; scale = scale_;
     nlogpo1 = nlogpo1_; po1 = po1_; grad = grad_; y1 = y1_; y2 = y2_; y3 = y3_; st = st_;
-    const std::string w(who);
-    if (M <= 0) return ctx->fail(w + ": M must be >= 1");
-    if (!(hd ? hd->s && hd->nz : h4 != nullptr) || !o1 || !nlogpo1 || !grad)
-        return ctx->fail(w + (hd ? ": s, o1, nz, nlogpo1 and grad must be non-NULL" : ": h4, o1, nlogpo1 and grad must be non-NULL"));
-    if (ctx->chan != 1 || ctx->res != 64 || !(hd ? ctx->dec_raw : ctx->dect_raw)) return ctx->fail(w + ": built for the 1 x 64 x 64 geometry only");
-    if (ctx->mfma_bf16x3) return ctx->fail(w + ": not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
-    if (!(scale >= 0.0f)) {
-        if (!(scale < 0.0f) || !std::isfinite(beta_o)) return ctx->fail(w + ": scale is NaN, or negative (= beta_o / M) with a non-finite beta_o");
-        scale = beta_o / (float)M;
-    }
+    const bool ptrs = (hd ? hd->s && hd->nz : h4 != nullptr) && o1 && nlogpo1 && grad;
+    if (dec_grad_checks(ctx, who, M, ptrs, hd ? ": s, o1, nz, nlogpo1 and grad must be non-NULL" : ": h4, o1, nlogpo1 and grad must be non-NULL",
+                        ctx->chan == 1 && ctx->res == 64 && (hd ? ctx->dec_raw : ctx->dect_raw), scale, beta_o)) return 1;
     p = dec_tail_plan(M, !y1, !y2, !y3, !po1);
     s1 = ctx->allocT<float>(p.y1); s2 = ctx->allocT<float>(p.y2); s3 = ctx->allocT<float>(p.y3); sp = ctx->allocT<float>(p.po);
     g4 = ctx->allocT<float>(p.g4); g3 = ctx->allocT<float>(p.g3); g2 = ctx->allocT<float>(p.g2); g1 = ctx->allocT<float>(p.g1);
@@ -173,6 +181,44 @@ int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4
     if (d.open(ctx, who, hd, h4, d_h4, o1, M, scale, beta_o, nlogpo1, po1, grad, y1, y2, y3, st)) return 1;
     for (int m0 = 0; m0 < M; m0 += d.p.C) d.group(m0);
     d.close();
+    return 0;
+}
+
+// efe_dec_tail_grad_g inside its call scope: the tail's gradient by train_dec_g.hip's run-time-geometry kernels, at every admitted geometry.
+// Row groups of geo.rows_per_pass() rows; scratch of one group from the arena: the activations the caller gives no output for, the four
+// gradients, and G slabs (none at G = 1: the gradient itself).
+int dec_tail_grad_g_run(efe_ctx* ctx, const char* who, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1,
+                        float* d_h4, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
+    // (a context without the raw tail cannot exist once committed: the geometry test of the shared checks stands for "the copy is there")
+    if (dec_grad_checks(ctx, who, M, h4 && o1 && nlogpo1 && grad, ": h4, o1, nlogpo1 and grad must be non-NULL", ctx->dect_raw_g != nullptr, scale, beta_o))
+        return 1;
+    const DecTailGeo geo{ctx->base, ctx->chan, ctx->last_s1 ? 1 : 2};
+    const int C = std::min(geo.rows_per_pass(), M), G = dec_tail_slabs(M), P = geo.P();
+    const size_t n = (size_t)C;
+    float* s1 = y1 ? nullptr : ctx->allocT<float>(n * geo.y1());
+    float* s2 = y2 ? nullptr : ctx->allocT<float>(n * geo.y2());
+    float* s3 = y3 ? nullptr : ctx->allocT<float>(n * geo.y3());
+    float* sp = po1 ? nullptr : ctx->allocT<float>(n * geo.img());
+    float* g4 = ctx->allocT<float>(n * geo.img());
+    float* g3 = ctx->allocT<float>(n * geo.y3());
+    float* g2 = ctx->allocT<float>(n * geo.y2());
+    float* g1 = ctx->allocT<float>(n * geo.y1());
+    float* slabs = G > 1 ? ctx->allocT<float>((size_t)G * P) : grad;
+    if ((!y1 && !s1) || (!y2 && !s2) || (!y3 && !s3) || (!po1 && !sp) || !g4 || !g3 || !g2 || !g1 || !slabs) return 1;
+    for (int m0 = 0; m0 < M; m0 += C) {
+        const size_t m = (size_t)m0;
+        DecTailGArgs a{};
+        a.geo = geo; a.w = ctx->dect_raw_g; a.h4 = h4 + m * geo.y1(); a.o1 = o1 + m * geo.img();
+        a.y1 = y1 ? y1 + m * geo.y1() : s1; a.y2 = y2 ? y2 + m * geo.y2() : s2; a.y3 = y3 ? y3 + m * geo.y3() : s3;
+        a.po = po1 ? po1 + m * geo.img() : sp; a.nlogpo1 = nlogpo1 + m0;
+        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = d_h4 ? d_h4 + m * geo.y1() : nullptr;
+        a.slabs = slabs; a.rows = std::min(C, M - m0); a.G = G; a.first = m0 == 0; a.scale = scale;
+        launch_dec_tail_g_group(a, st);
+    }
+    if (G > 1) launch_slab_sum(slabs, G, P, grad, st);
+    // forward, data gradient, weight gradient of the four layers: 2 x 36 864 B^2, 18 432 (2B)^2, 288 C R^2 multiply-adds each
+    const int64_t BB = (int64_t)geo.B * geo.B, RR = (int64_t)geo.R() * geo.R();
+    ctx->last_macs += (int64_t)M * 3 * (2 * 36864 * BB + 18432 * 4 * BB + 288 * geo.C * RR);
     return 0;
 }
 
@@ -396,6 +442,13 @@ int efe_dec_tail_grad(efe_ctx* ctx, const float* h4, const float* o1, int M, flo
                       float* grad, float* y1, float* y2, float* y3, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (dec_grad(ctx, "efe_dec_tail_grad", nullptr, h4, d_h4, o1, M, scale, beta_o, nlogpo1, po1, grad, y1, y2, y3, st)) return 1;
+    return call.finish();
+}
+
+int efe_dec_tail_grad_g(efe_ctx* ctx, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
+                        float* grad, float* y1, float* y2, float* y3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_dec_tail_grad_g");
+    if (dec_tail_grad_g_run(ctx, "efe_dec_tail_grad_g", h4, o1, M, scale, beta_o, nlogpo1, po1, d_h4, grad, y1, y2, y3, st)) return 1;
     return call.finish();
 }
 

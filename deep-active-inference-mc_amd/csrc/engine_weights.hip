@@ -379,7 +379,7 @@ int pack_encoder(efe_ctx* ctx) {
 // decoder (torchmodel.py:106-128) behind its head: Linear(256, 64 B^2), three ConvTranspose2d ([Cin][Cout][kh][kw]) and the final convolution
 int pack_decoder(efe_ctx* ctx) {
     const int C = ctx->chan, B = ctx->base;
-    ctx->dec_raw = ctx->dect_raw = nullptr;
+    ctx->dec_raw = ctx->dect_raw = ctx->dect_raw_g = nullptr;
     if (C == 1 && ctx->res == 64) {     // the raw copy the backward passes read (train_dec_head.hip, train_dec.hip), beside the packed forward forms
         std::vector<float> flat;
         for (int i = 0; i < 4; ++i) {
@@ -399,7 +399,18 @@ int pack_decoder(efe_ctx* ctx) {
         }
         if (flat.size() != (size_t)DEC_P) return ctx->fail("decoder tail: unexpected parameter count");
         if (!(ctx->dec_raw = upload_master(ctx, flat, ENC_P))) return 1;
-        ctx->dect_raw = ctx->dec_raw + DEC_HEAD_P;
+        ctx->dect_raw_g = ctx->dect_raw = ctx->dec_raw + DEC_HEAD_P;
+    } else {                            // any other geometry: the raw tail alone, for efe_dec_tail_grad_g (train_dec_g.hip)
+        std::vector<float> flat;
+        for (int i = 0; i < 4; ++i) {
+            const LayerSpec s = i < 3 ? DEC_CT[i] : LayerSpec{"down.po_net.19", C, 32};
+            const WB t = weight_and_bias(ctx, s.key, {s.in, s.out, 3, 3}, {s.out});
+            if (!t) return 1;
+            flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
+            flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
+        }
+        if (flat.size() != (size_t)DT_W4 + 289 * (size_t)C) return ctx->fail("decoder tail: unexpected parameter count");
+        if (!(ctx->dect_raw_g = upload(ctx, flat))) return 1;
     }
     {   // Unflatten(1, (64, B, B)) is channel-major c*B*B + p (torchmodel.py:119); the layer emits NHWC p*64 + c directly
         const std::vector<int> rowp = nhwc_perm(64, B * B);
@@ -526,7 +537,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         for (void* p : ctx->wbufs) (void)hipFree(p);
         ctx->wbufs.clear();
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
-        ctx->dec_raw = ctx->dect_raw = ctx->enc_raw = nullptr;
+        ctx->dec_raw = ctx->dect_raw = ctx->dect_raw_g = ctx->enc_raw = nullptr;
     }
     ctx->committed = false;
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first

@@ -572,6 +572,34 @@ struct DecTailArgs {                     // one row group: every pointer is the 
 };
 void launch_dec_tail_group(const DecTailArgs& a, hipStream_t st);
 
+// ---- the same backward at every admitted geometry (train_dec_g.hip): B = the decoder's base grid, C colour channels, S3 = layer 3's stride --
+// The flat vector keeps DT_W1 .. DT_B3; layer 4 is [32][C][3][3] then [C]: P = 92 320 + 289 C.
+struct DecTailGeo {
+    int B, C, S3;
+    __host__ __device__ int R() const { return S3 * 2 * B; }                       // the resolution
+    __host__ __device__ int w4() const { return DT_W4; }
+    __host__ __device__ int b4() const { return DT_W4 + 288 * C; }
+    __host__ __device__ int P() const { return DT_W4 + 289 * C; }
+    size_t y1() const { return (size_t)64 * B * B; }                               // floats per row
+    size_t y2() const { return (size_t)64 * 4 * B * B; }
+    size_t y3() const { return (size_t)32 * R() * R(); }
+    size_t img() const { return (size_t)C * R() * R(); }
+    int rows_per_pass() const { return B <= 16 ? 64 : 32; }                        // a multiple of DEC_TAIL_SLABS, a function of the geometry alone
+};
+struct DecTailGArgs {                    // one row group: every pointer is the group's first row
+    DecTailGeo geo;
+    const float* w;                      // raw parameters [P]
+    const float* h4; const float* o1;    // [rows][64][B][B], [rows][C][R][R]
+    float *y1, *y2, *y3, *po;            // stored forward
+    float* nlogpo1;                      // [rows]
+    float *g4, *g3, *g2, *g1;            // dL / da_l
+    float* dh4;                          // nullable [rows][64][B][B]
+    float* slabs;                        // [G][P]; first != 0: written, else added to
+    int rows, G, first;
+    float scale;
+};
+void launch_dec_tail_g_group(const DecTailGArgs& a, hipStream_t st);
+
 // ---- backward of the decoder's dense head po_net[0:12] at 1 x 64 x 64 (train_dec_head.hip) ---------------------------------
 // The whole po_net as one flat vector in parameters() order: 0.weight [256][10], 0.bias, 3.weight [256][256], 3.bias, 6.weight, 6.bias,
 // 9.weight [16384][256], 9.bias, then the tail's DEC_TAIL_P (DT_* offsets behind DEC_HEAD_P): the raw device copy and the gradient.

@@ -500,6 +500,25 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> dec_tail_grad
     return {nl, po, dh, grad, y1, y2, y3};
 }
 
+// ---- the same at every admitted geometry (csrc/train_dec_g.hip): sizes from the context ----
+// -> (nlogpo1 [M], po1 [M,C,R,R], d_h4 [M,64 B B], grad [92320 + 289 C], y1 [M,64,B,B], y2 [M,64,2B,2B], y3 [M,32,R,R])
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> dec_tail_grad_g(int64_t h, const Tensor& h4_, const Tensor& o1_, double scale, double beta_o,
+                                                                                    bool want_y) {
+    Ctx x(h);
+    Tensor h4 = x.f32(h4_, "h4"), o1 = x.f32(o1_, "o1");
+    const int64_t R = x.R, B = R == 32 ? 16 : R / 4, C = x.C;
+    const int M = rows(h4, 64 * B * B, "h4");
+    TORCH_CHECK(o1.numel() == (int64_t)M * x.img(), "efe: o1 must be [M, ", C, ", ", R, ", ", R, "]");
+    const int64_t NP = x.param_count("po_net_convt");
+    auto op = h4.options();
+    const int64_t My = want_y ? M : 0;
+    Tensor nl = at::empty({M}, op), po = at::empty({M, C, R, R}, op), dh = at::empty({M, 64 * B * B}, op), grad = at::empty({NP}, op);
+    Tensor y1 = at::empty({My, 64, B, B}, op), y2 = at::empty({My, 64, 2 * B, 2 * B}, op), y3 = at::empty({My, 32, R, R}, op);
+    auto A = [&](Tensor& t) { return want_y ? P(t) : nullptr; };
+    x.ok(efe_dec_tail_grad_g(x.c, P(h4), P(o1), M, (float)scale, (float)beta_o, P(nl), P(po), P(dh), P(grad), A(y1), A(y2), A(y3), x.stream()));
+    return {nl, po, dh, grad, y1, y2, y3};
+}
+
 // ---- backward of the whole decoder (csrc/train_dec_head.hip + csrc/train_dec.hip) ----
 // d (scale * sum nlogpo1) / d (po_net, s) -> (nlogpo1 [M], po1 [M,1,64,64], d_s [M,10], grad [4437697], h1, h2, h3, h4, y1, y2, y3); the
 // activations are empty tensors unless want_act; scale < 0: beta_o / M
@@ -741,4 +760,14 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
     m.impl("eval_stats", &eval_stats);
     m.impl("down_adam_step", &down_adam_step);
     m.impl("eval_mi", &eval_mi);
+}
+
+// torch.ops.efe_g.* : the entry points that take their geometry from the context.  A namespace of its own: the 31 schemas of torch.ops.efe
+// are pinned as a closed set (tests/test_abi.py), and these calls are additions beside them, not changes to them.
+TORCH_LIBRARY(efe_g, m) {
+    m.def("dec_tail_grad(int ctx, Tensor h4, Tensor o1, float scale, float beta_o, bool want_y) -> (Tensor nlogpo1, Tensor po1, Tensor d_h4, Tensor grad, Tensor y1, Tensor y2, Tensor y3)");
+}
+
+TORCH_LIBRARY_IMPL(efe_g, CUDA, m) {
+    m.impl("dec_tail_grad", &dec_tail_grad_g);
 }

@@ -34,10 +34,12 @@ __device__ __forceinline__ void slab_put(float* d, float v, int first) {
 
 // dW of one 16 x 16 channel tile (origins i0, j0 of W's first and second index, NJ = the extent of the second) for all nine taps, over
 // images of HW positions; slab = this workgroup's.  lda(r, pos) -> the lane's A values of positions pos .. pos + 3 of row r;
-// ldb(r, pos, ky, kx) -> its B value of position pos under tap (ky, kx).  A position >= HW of a ragged last chunk must give zero in both.
-// The call is the kernel's last statement.
-template <int HW, class LA, class LB>
-__device__ __forceinline__ void wgrad_mfma(int rows, int i0, int j0, int NJ, float* slab, int first, LA lda, LB ldb) {
+// ldb(r, where(pos), ky, kx) -> its B value of position pos under tap (ky, kx).  A position >= HW of a ragged last chunk must give zero in both.
+// The call is the kernel's last statement.  HW is a run-time value here (train_dec_g.hip: the geometry is the context's); wgrad_mfma<HW>
+// below is the same body with the extent known to the compiler.  where(pos) -> what ldb takes in place of the position, formed ONCE per
+// position for its nine taps (run-time extents: the position's row and column, which cost a division).
+template <class LA, class LB, class LW>
+__device__ __forceinline__ void wgrad_mfma_rt(int HW, int rows, int i0, int j0, int NJ, float* slab, int first, LA lda, LB ldb, LW where) {
 #pragma clang fp contract(off)
     const int G = gridDim.y, p = blockIdx.y;
     if (p >= rows) return;
@@ -61,12 +63,14 @@ __device__ __forceinline__ void wgrad_mfma(int rows, int i0, int j0, int NJ, flo
                 const float4 a4 = lda(r, pos);
                 const float av[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
+                for (int s = 0; s < 4; ++s) {
+                    const auto at = where(pos + s);
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx)
-                            ch[3 * ky + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], ldb(r, pos + s, ky, kx), ch[3 * ky + kx], 0, 0, 0);
+                            ch[3 * ky + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], ldb(r, at, ky, kx), ch[3 * ky + kx], 0, 0, 0);
+                }
             }
 #pragma unroll
             for (int t = 0; t < 9; ++t) acc_i[t] = acc_i[t] + ch[t];
@@ -78,6 +82,11 @@ __device__ __forceinline__ void wgrad_mfma(int rows, int i0, int j0, int NJ, flo
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int e = 0; e < 4; ++e) slab_put(slab + ((size_t)(i0 + 4 * q + e) * NJ + j0 + n) * 9 + t, acc_g[t][e], first);
+}
+
+template <int HW, class LA, class LB>
+__device__ __forceinline__ void wgrad_mfma(int rows, int i0, int j0, int NJ, float* slab, int first, LA lda, LB ldb) {
+    wgrad_mfma_rt(HW, rows, i0, j0, NJ, slab, first, lda, ldb, [](int pos) { return pos; });
 }
 
 // the nine weights of one channel pair on the VALU (a layer with one channel on one side): slab9 = their place in this workgroup's

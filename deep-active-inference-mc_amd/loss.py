@@ -242,6 +242,27 @@ def grad_decoder_convs(model_down, h4, o1, *, scale=None, return_activations=Fal
     return out + ((y1, y2, y3),) if return_activations else out
 
 
+def grad_decoder_convs_g(model_down, h4, o1, *, scale=None, return_activations=False):
+    """grad_decoder_convs at every admitted geometry (csrc/train_dec_g.hip, efe_dec_tail_grad_g): the sizes come from the model.  With
+    C colour channels, resolution R and B = R / 4 (16 at R = 32, where po_net.17 has stride 1): h4 [M, 64 B B], o1 [M,C,R,R] ->
+    (nlogpo1 [M], po1 [M,C,R,R], d_h4 [M, 64 B B], {state_dict key: dL / d tensor}) and, with return_activations, (y1 [M,64,B,B],
+    y2 [M,64,2B,2B], y3 [M,32,R,R]).  scale None = beta_o / M.  The gradients are views of one flat tensor over DEC_CONVT_KEYS in
+    parameters() order.  1 x 64 x 64 models run the same run-time-geometry kernels (grad_decoder_convs is then a cross-check)."""
+    m = model_down._owner
+    if scale is not None and not float(scale) >= 0.0:
+        raise ValueError('grad_decoder_convs_g: scale must be >= 0 (None = beta_o / M)')
+    e = m._ready()
+    C_, R = int(m.colour_channels), int(m.resolution)
+    B = 16 if R == 32 else R // 4
+    h4 = e.tensor(h4, (-1, 64 * B * B))
+    M = h4.shape[0]
+    o1 = e.tensor(o1, (M, C_, R, R))
+    nl, po1, d_h4, flat, y1, y2, y3 = torch.ops.efe_g.dec_tail_grad(e.h, h4, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o),
+                                                                    bool(return_activations))
+    out = (nl, po1, d_h4, _views(flat, model_down._sd_host, DEC_CONVT_KEYS))
+    return out + ((y1, y2, y3),) if return_activations else out
+
+
 DEC_HEAD_KEYS = tuple(f'po_net.{i}.{sfx}' for i in (0, 3, 6, 9) for sfx in ('weight', 'bias'))
 
 

@@ -503,6 +503,19 @@ int efe_train_mid(efe_ctx*, const float* s0, const float* pi0, const float* qs1_
 int efe_dec_tail_grad(efe_ctx*, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
                       float* grad, float* y1, float* y2, float* y3, void* stream);
 
+/* ---- the same backward at every admitted geometry (csrc/train_dec_g.hip; additive to ABI 6) ------------------------------------------------
+ * efe_dec_tail_grad's arguments and meaning with the sizes taken from the context (efe_create_cfg: C = 1..3 colour channels, resolution
+ * R = 32..128 in steps of 4; B = R / 4, or 16 at R = 32, where the third layer has stride 1):
+ *   h4, d_h4 [M, 64 B B]   o1, po1 [M,C,R,R]   y1 [M,64,B,B]   y2 [M,64,2B,2B]   y3 [M,32,R,R]   nlogpo1 [M]
+ *   grad [P], P = efe_param_count("po_net_convt") = 92 320 + 289 C, parameters() order (19.weight is [32][C][3][3], 19.bias [C])
+ * It runs kernels whose spatial sizes are run-time values at EVERY geometry, 1 x 64 x 64 included (there efe_dec_tail_grad's specialised
+ * kernels are a cross-check: both hold the fp64 rule; their bits are not promised equal).  Same refusals (every one before the first launch),
+ * same negative-scale rule, same per-row contract, same fixed-order sum (G = min(M, 32) slabs, row m in slab m mod G; DESIGN.md section
+ * 7d-g): twice the same bits.  nlogpo1 is the 256-thread ordered sum over the row's C R R NCHW terms.  Rows are processed in groups of 64
+ * (B <= 16) or 32 (B > 16): at most 231 MB of scratch activations and gradients at resolution 128, 99 MB at 3 x 84 x 84. */
+int efe_dec_tail_grad_g(efe_ctx*, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
+                        float* grad, float* y1, float* y2, float* y3, void* stream);
+
 /* ---- backward of the reconstruction loss through the whole decoder (csrc/train_dec_head.hip + csrc/train_dec.hip; additive to ABI 6) ------
  * The decoder's part of train_model_down (src/torchloss.py:90-98): po_net's dense head (Linear 10-256-256-256-16384, each with ReLU and
  * Dropout(0.5), torchmodel.py:107-118) evaluated for training, the ConvTranspose2d tail exactly as efe_dec_tail_grad runs it, and the
