@@ -99,6 +99,8 @@ struct efe_ctx {
     float* dect_raw = nullptr;     // its tail po_net.13 / .15 / .17 / .19 (= dec_raw + DEC_HEAD_P): train_dec.hip reads it
     float* dect_raw_g = nullptr;   // the same tail at ANY geometry, [92 320 + 289 chan] (DecTailGeo): train_dec_g.hip reads it.  = dect_raw at 1 x 64 x 64
                                    // (so that it follows ModelDown's optimiser steps), else a buffer of the current commit
+    float* dec_raw_g = nullptr;    // the whole po_net at ANY geometry, [134 400 + 257 * 64 base^2] (DecHeadGeo) then the tail: train_dec_head_g.hip
+                                   // reads it.  dect_raw_g = dec_raw_g + the head's size; = dec_raw at 1 x 64 x 64, else a buffer of the current commit
     float* enc_raw = nullptr;      // the whole qs_net unpacked, flat in parameters() order (kernels.h EQ_*): train_enc.hip reads it
     // ModelDown's master copy at 1 x 64 x 64 (owned: it outlives a re-commit, as TrainPart::master): [DOWN_P], qs_net then po_net, so
     // enc_raw = down_master and dec_raw = down_master + ENC_P.  An optimiser step (train_down.hip) writes it and rebuilds every packed form

@@ -184,17 +184,24 @@ int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4
     return 0;
 }
 
-// efe_dec_tail_grad_g inside its call scope: the tail's gradient by train_dec_g.hip's run-time-geometry kernels, at every admitted geometry.
-// Row groups of geo.rows_per_pass() rows; scratch of one group from the arena: the activations the caller gives no output for, the four
-// gradients, and G slabs (none at G = 1: the gradient itself).
-int dec_tail_grad_g_run(efe_ctx* ctx, const char* who, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1,
-                        float* d_h4, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
-    // (a context without the raw tail cannot exist once committed: the geometry test of the shared checks stands for "the copy is there")
-    if (dec_grad_checks(ctx, who, M, h4 && o1 && nlogpo1 && grad, ": h4, o1, nlogpo1 and grad must be non-NULL", ctx->dect_raw_g != nullptr, scale, beta_o))
+// efe_dec_tail_grad_g and efe_dec_grad_g inside their call scope: the decoder's gradient by the run-time-geometry kernels (train_dec_g.hip,
+// train_dec_head_g.hip), at every admitted geometry.  Row groups of geo.rows_per_pass() rows; scratch of one group from the arena: the
+// activations the caller gives no output for, the four gradients, and G slabs (none at G = 1: the gradient itself).
+// hd == nullptr: the tail alone, from the caller's h4 to the caller's d_h4 (nullable), grad [geo.P()].  Else the whole decoder, grad
+// [hg.P() + geo.P()], h4 / d_h4 unused: per group the head's forward, launch_dec_tail_g_group exactly as without the head (on the group's h4,
+// d_h4 to scratch), the head's backward; the head takes h1..h4 and d_h4 of one group and the S x rows x 256 partials of d_h3 as well.
+int dec_grad_g_run(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1,
+                   float* po1, float* d_h4, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
+    // (a context without the raw copy cannot exist once committed: the geometry test of the shared checks stands for "the copy is there")
+    const bool ptrs = (hd ? hd->s && hd->nz : h4 != nullptr) && o1 && nlogpo1 && grad;
+    if (dec_grad_checks(ctx, who, M, ptrs, hd ? ": s, o1, nz, nlogpo1 and grad must be non-NULL" : ": h4, o1, nlogpo1 and grad must be non-NULL",
+                        (hd ? ctx->dec_raw_g : ctx->dect_raw_g) != nullptr, scale, beta_o))
         return 1;
     const DecTailGeo geo{ctx->base, ctx->chan, ctx->last_s1 ? 1 : 2};
+    const DecHeadGeo hg{ctx->base};
     const int C = std::min(geo.rows_per_pass(), M), G = dec_tail_slabs(M), P = geo.P();
     const size_t n = (size_t)C;
+    float* tgrad = hd ? grad + hg.P() : grad;        // the tail's gradient
     float* s1 = y1 ? nullptr : ctx->allocT<float>(n * geo.y1());
     float* s2 = y2 ? nullptr : ctx->allocT<float>(n * geo.y2());
     float* s3 = y3 ? nullptr : ctx->allocT<float>(n * geo.y3());
@@ -203,22 +210,48 @@ int dec_tail_grad_g_run(efe_ctx* ctx, const char* who, const float* h4, const fl
     float* g3 = ctx->allocT<float>(n * geo.y3());
     float* g2 = ctx->allocT<float>(n * geo.y2());
     float* g1 = ctx->allocT<float>(n * geo.y1());
-    float* slabs = G > 1 ? ctx->allocT<float>((size_t)G * P) : grad;
+    float* slabs = G > 1 ? ctx->allocT<float>((size_t)G * P) : tgrad;
     if ((!y1 && !s1) || (!y2 && !s2) || (!y3 && !s3) || (!po1 && !sp) || !g4 || !g3 || !g2 || !g1 || !slabs) return 1;
+    const int GH = dec_head_slabs(M);
+    float *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr, *dh4 = nullptr, *part = nullptr, *hslabs = nullptr;
+    if (hd) {
+        if (!hd->h1) a1 = ctx->allocT<float>(n * 256);
+        if (!hd->h2) a2 = ctx->allocT<float>(n * 256);
+        if (!hd->h3) a3 = ctx->allocT<float>(n * 256);
+        if (!hd->h4) a4 = ctx->allocT<float>(n * geo.y1());
+        dh4 = ctx->allocT<float>(n * geo.y1());
+        part = ctx->allocT<float>((size_t)hg.segs() * n * 256);
+        hslabs = GH > 1 ? ctx->allocT<float>((size_t)GH * DEC_HEAD_SMALL_P) : grad;
+        if ((!hd->h1 && !a1) || (!hd->h2 && !a2) || (!hd->h3 && !a3) || (!hd->h4 && !a4) || !dh4 || !part || !hslabs) return 1;
+    }
     for (int m0 = 0; m0 < M; m0 += C) {
         const size_t m = (size_t)m0;
+        const int rows = std::min(C, M - m0);
+        DecHeadGArgs h{};
+        if (hd) {
+            h.geo = hg; h.w = ctx->dec_raw_g; h.s = hd->s + m * S_DIM;
+            h.h1 = hd->h1 ? hd->h1 + m * 256 : a1; h.h2 = hd->h2 ? hd->h2 + m * 256 : a2; h.h3 = hd->h3 ? hd->h3 + m * 256 : a3;
+            h.h4 = hd->h4 ? hd->h4 + m * geo.y1() : a4;
+            h.g4 = dh4; h.part = part; h.ds = hd->d_s ? hd->d_s + m * S_DIM : nullptr; h.grad = grad; h.slabs = hslabs;
+            h.rows = rows; h.first = m0 == 0; h.tile0 = m0 / 16; h.key = train_key(hd->nz, (uint32_t)m0);
+            launch_dec_head_g_fwd(h, st);
+        }
         DecTailGArgs a{};
-        a.geo = geo; a.w = ctx->dect_raw_g; a.h4 = h4 + m * geo.y1(); a.o1 = o1 + m * geo.img();
+        a.geo = geo; a.w = ctx->dect_raw_g; a.h4 = hd ? h.h4 : h4 + m * geo.y1(); a.o1 = o1 + m * geo.img();
         a.y1 = y1 ? y1 + m * geo.y1() : s1; a.y2 = y2 ? y2 + m * geo.y2() : s2; a.y3 = y3 ? y3 + m * geo.y3() : s3;
         a.po = po1 ? po1 + m * geo.img() : sp; a.nlogpo1 = nlogpo1 + m0;
-        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = d_h4 ? d_h4 + m * geo.y1() : nullptr;
-        a.slabs = slabs; a.rows = std::min(C, M - m0); a.G = G; a.first = m0 == 0; a.scale = scale;
+        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.dh4 = hd ? dh4 : d_h4 ? d_h4 + m * geo.y1() : nullptr;
+        a.slabs = slabs; a.rows = rows; a.G = G; a.first = m0 == 0; a.scale = scale;
         launch_dec_tail_g_group(a, st);
+        if (hd) launch_dec_head_g_bwd(h, st);
     }
-    if (G > 1) launch_slab_sum(slabs, G, P, grad, st);
-    // forward, data gradient, weight gradient of the four layers: 2 x 36 864 B^2, 18 432 (2B)^2, 288 C R^2 multiply-adds each
+    if (G > 1) launch_slab_sum(slabs, G, P, tgrad, st);
+    if (hd && GH > 1) launch_slab_sum(hslabs, GH, DEC_HEAD_SMALL_P, grad, st);
+    // forward, data gradient, weight gradient of the four layers: 2 x 36 864 B^2, 18 432 (2B)^2, 288 C R^2 multiply-adds each; of the head's
+    // four: 10 x 256, 2 x 256 x 256, 256 F
     const int64_t BB = (int64_t)geo.B * geo.B, RR = (int64_t)geo.R() * geo.R();
     ctx->last_macs += (int64_t)M * 3 * (2 * 36864 * BB + 18432 * 4 * BB + 288 * geo.C * RR);
+    if (hd) ctx->last_macs += (int64_t)M * 3 * (2560 + 131072 + 256 * (int64_t)hg.F());
     return 0;
 }
 
@@ -448,7 +481,7 @@ int efe_dec_tail_grad(efe_ctx* ctx, const float* h4, const float* o1, int M, flo
 int efe_dec_tail_grad_g(efe_ctx* ctx, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1, float* po1, float* d_h4,
                         float* grad, float* y1, float* y2, float* y3, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_dec_tail_grad_g");
-    if (dec_tail_grad_g_run(ctx, "efe_dec_tail_grad_g", h4, o1, M, scale, beta_o, nlogpo1, po1, d_h4, grad, y1, y2, y3, st)) return 1;
+    if (dec_grad_g_run(ctx, "efe_dec_tail_grad_g", nullptr, h4, o1, M, scale, beta_o, nlogpo1, po1, d_h4, grad, y1, y2, y3, st)) return 1;
     return call.finish();
 }
 
@@ -457,6 +490,14 @@ int efe_dec_grad(efe_ctx* ctx, const float* s, const float* o1, int M, float sca
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     const DecHeadIO hd{s, nz, d_s, h1, h2, h3, h4};
     if (dec_grad(ctx, "efe_dec_grad", &hd, nullptr, nullptr, o1, M, scale, beta_o, nlogpo1, po1, grad, y1, y2, y3, st)) return 1;
+    return call.finish();
+}
+
+int efe_dec_grad_g(efe_ctx* ctx, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
+                   float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_dec_grad_g");
+    const DecHeadIO hd{s, nz, d_s, h1, h2, h3, h4};
+    if (dec_grad_g_run(ctx, "efe_dec_grad_g", &hd, nullptr, o1, M, scale, beta_o, nlogpo1, po1, nullptr, grad, y1, y2, y3, st)) return 1;
     return call.finish();
 }
 

@@ -379,29 +379,20 @@ int pack_encoder(efe_ctx* ctx) {
 // decoder (torchmodel.py:106-128) behind its head: Linear(256, 64 B^2), three ConvTranspose2d ([Cin][Cout][kh][kw]) and the final convolution
 int pack_decoder(efe_ctx* ctx) {
     const int C = ctx->chan, B = ctx->base;
-    ctx->dec_raw = ctx->dect_raw = ctx->dect_raw_g = nullptr;
-    if (C == 1 && ctx->res == 64) {     // the raw copy the backward passes read (train_dec_head.hip, train_dec.hip), beside the packed forward forms
+    ctx->dec_raw = ctx->dect_raw = ctx->dec_raw_g = ctx->dect_raw_g = nullptr;
+    {   // the raw copy the backward passes read, beside the packed forward forms: the whole po_net flat in parameters() order
+        const DecHeadGeo hg{B};
+        const size_t tail = (size_t)DT_W4 + 289 * (size_t)C;
         std::vector<float> flat;
+        flat.reserve(hg.P() + tail);
         for (int i = 0; i < 4; ++i) {
-            const LayerSpec s = i < 3 ? DEC_HEAD[i] : LayerSpec{"down.po_net.9", 16384, 256};
+            const LayerSpec s = i < 3 ? DEC_HEAD[i] : LayerSpec{"down.po_net.9", hg.F(), 256};
             const WB t = weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
             if (!t) return 1;
             flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
             flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
         }
-        if (flat.size() != (size_t)DEC_HEAD_P) return ctx->fail("decoder head: unexpected parameter count");
-        for (int i = 0; i < 4; ++i) {
-            const LayerSpec s = i < 3 ? DEC_CT[i] : LayerSpec{"down.po_net.19", 1, 32};
-            const WB t = weight_and_bias(ctx, s.key, {s.in, s.out, 3, 3}, {s.out});
-            if (!t) return 1;
-            flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
-            flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
-        }
-        if (flat.size() != (size_t)DEC_P) return ctx->fail("decoder tail: unexpected parameter count");
-        if (!(ctx->dec_raw = upload_master(ctx, flat, ENC_P))) return 1;
-        ctx->dect_raw_g = ctx->dect_raw = ctx->dec_raw + DEC_HEAD_P;
-    } else {                            // any other geometry: the raw tail alone, for efe_dec_tail_grad_g (train_dec_g.hip)
-        std::vector<float> flat;
+        if (flat.size() != hg.P()) return ctx->fail("decoder head: unexpected parameter count");
         for (int i = 0; i < 4; ++i) {
             const LayerSpec s = i < 3 ? DEC_CT[i] : LayerSpec{"down.po_net.19", C, 32};
             const WB t = weight_and_bias(ctx, s.key, {s.in, s.out, 3, 3}, {s.out});
@@ -409,8 +400,13 @@ int pack_decoder(efe_ctx* ctx) {
             flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
             flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
         }
-        if (flat.size() != (size_t)DT_W4 + 289 * (size_t)C) return ctx->fail("decoder tail: unexpected parameter count");
-        if (!(ctx->dect_raw_g = upload(ctx, flat))) return 1;
+        if (flat.size() != hg.P() + tail) return ctx->fail("decoder tail: unexpected parameter count");
+        if (C == 1 && ctx->res == 64) {     // inside ModelDown's master vector, so that it follows an optimiser step (train_dec_head.hip, train_dec.hip)
+            if (!(ctx->dec_raw = upload_master(ctx, flat, ENC_P))) return 1;
+            ctx->dec_raw_g = ctx->dec_raw;
+            ctx->dect_raw = ctx->dec_raw + DEC_HEAD_P;
+        } else if (!(ctx->dec_raw_g = upload(ctx, flat))) return 1;      // any other geometry: a buffer of this commit (train_dec_head_g.hip, train_dec_g.hip)
+        ctx->dect_raw_g = ctx->dec_raw_g + hg.P();
     }
     {   // Unflatten(1, (64, B, B)) is channel-major c*B*B + p (torchmodel.py:119); the layer emits NHWC p*64 + c directly
         const std::vector<int> rowp = nhwc_perm(64, B * B);
@@ -537,7 +533,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         for (void* p : ctx->wbufs) (void)hipFree(p);
         ctx->wbufs.clear();
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
-        ctx->dec_raw = ctx->dect_raw = ctx->dect_raw_g = ctx->enc_raw = nullptr;
+        ctx->dec_raw = ctx->dect_raw = ctx->dec_raw_g = ctx->dect_raw_g = ctx->enc_raw = nullptr;
     }
     ctx->committed = false;
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first

@@ -623,6 +623,35 @@ struct DecHeadArgs {                     // one row group (at most DEC_TAIL_ROWS
 };
 void launch_dec_head_fwd(const DecHeadArgs& a, hipStream_t st);       // s -> h1 .. h4
 void launch_dec_head_bwd(const DecHeadArgs& a, hipStream_t st);       // d_h4 -> the head's gradients and d_s
+void launch_dec_head_fwd_small(const DecHeadArgs& a, hipStream_t st); // layers 0..2 alone (k_dech_fwd): s -> h1 .. h3, at any geometry
+void launch_dec_head_gate(const float* h4, float* g, size_t n, hipStream_t st);      // k_dech_gate over n elements (a multiple of 4)
+
+// ---- the same head at every admitted geometry (train_dec_head_g.hip): F = 64 B^2 features of po_net.9, from the context ---------------
+// The flat vector keeps DH_W0 .. DH_B2; 9.weight is [F][256] at DH_W3, 9.bias [F] behind it, then the tail's DecTailGeo::P() floats.
+struct DecHeadGeo {
+    int B;
+    __host__ __device__ int BB() const { return B * B; }                           // pixels of the base grid = features per channel
+    __host__ __device__ int F() const { return 64 * B * B; }                       // 5 184 .. 65 536, a multiple of 64
+    __host__ __device__ size_t b3() const { return (size_t)DH_W3 + (size_t)F() * 256; }
+    __host__ __device__ size_t P() const { return b3() + (size_t)F(); }            // 134 400 + 257 F
+    __host__ __device__ int segs() const { return (F() + 255) / 256; }             // K segments of d_h3 = g4 W3; the last holds 64 features at odd B
+};
+struct DecHeadGArgs {                    // one row group (DecTailGeo::rows_per_pass() rows at most): every row pointer is the group's first row
+    DecHeadGeo geo;
+    const float* w;                      // raw parameters [geo.P() + the tail's]
+    const float* s;                      // [rows][10]
+    float *h1, *h2, *h3, *h4;            // stored forward, after the mask: [rows][256] x 3, [rows][F] (reference order c B^2 + p)
+    float* g4;                           // in: d_h4 [rows][F] of the tail; gated in place to dL / da of layer 3
+    float* part;                         // [geo.segs()][rows][256] partial sums of g4 W3; k_dechg_join leaves g_2 [rows][256] in plane 0
+    float* ds;                           // nullable [rows][10]
+    float* grad;                         // the caller's gradient: 9.weight / 9.bias are written (first) or added to in place
+    float* slabs;                        // [G][DEC_HEAD_SMALL_P]; a tile writes its slab if it is the slab's first, else adds to it
+    int rows, first;                     // first: the call's first row group
+    int tile0;                           // global index of the group's first 16-row tile: tile t of the call goes to slab t mod DEC_HEAD_SLABS
+    TrainKey key;                        // row0 = the global row of the group's row 0
+};
+void launch_dec_head_g_fwd(const DecHeadGArgs& a, hipStream_t st);    // s -> h1 .. h4
+void launch_dec_head_g_bwd(const DecHeadGArgs& a, hipStream_t st);    // d_h4 -> the head's gradients and d_s
 
 // ---- training forward and backward of the encoder qs_net at 1 x 64 x 64 (train_enc.hip) -----------------------------------------
 // The whole qs_net as one flat vector in parameters() order: 0.weight [32][1][3][3], 0.bias, 2.weight [32][32][3][3], 2.bias, 4.weight

@@ -541,6 +541,28 @@ std::vector<Tensor> dec_grad(int64_t h, const Tensor& s_, const Tensor& o1_, dou
     return {nl, po, ds, grad, h1, h2, h3, h4, y1, y2, y3};
 }
 
+// ---- the same at every admitted geometry (csrc/train_dec_head_g.hip + csrc/train_dec_g.hip): sizes from the context ----
+// -> (nlogpo1 [M], po1 [M,C,R,R], d_s [M,10], grad [134400 + 257 F + 92320 + 289 C], h1, h2, h3 [M,256], h4 [M,F], y1, y2, y3), F = 64 B B
+std::vector<Tensor> dec_grad_g(int64_t h, const Tensor& s_, const Tensor& o1_, double scale, double beta_o, int64_t seed, int64_t stage, int64_t pass,
+                               int64_t sample, int64_t row_offset, bool want_act) {
+    Ctx x(h);
+    Tensor s = x.f32(s_, "s"), o1 = x.f32(o1_, "o1");
+    const int64_t R = x.R, B = R == 32 ? 16 : R / 4, C = x.C;
+    const int M = rows(s, 10, "s");
+    TORCH_CHECK(o1.numel() == (int64_t)M * x.img(), "efe: o1 must be [M, ", C, ", ", R, ", ", R, "]");
+    const int64_t NP = x.param_count("po_net");
+    const efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    auto op = s.options();
+    const int64_t Ma = want_act ? M : 0;
+    Tensor nl = at::empty({M}, op), po = at::empty({M, C, R, R}, op), ds = at::empty({M, 10}, op), grad = at::empty({NP}, op);
+    Tensor h1 = at::empty({Ma, 256}, op), h2 = at::empty({Ma, 256}, op), h3 = at::empty({Ma, 256}, op), h4 = at::empty({Ma, 64 * B * B}, op);
+    Tensor y1 = at::empty({Ma, 64, B, B}, op), y2 = at::empty({Ma, 64, 2 * B, 2 * B}, op), y3 = at::empty({Ma, 32, R, R}, op);
+    auto A = [&](Tensor& t) { return want_act ? P(t) : nullptr; };
+    x.ok(efe_dec_grad_g(x.c, P(s), P(o1), M, (float)scale, (float)beta_o, &nz, P(nl), P(po), P(ds), P(grad), A(h1), A(h2), A(h3), A(h4), A(y1), A(y2),
+                        A(y3), x.stream()));
+    return {nl, po, ds, grad, h1, h2, h3, h4, y1, y2, y3};
+}
+
 // ---- backward of the encoder (csrc/train_enc.hip) ----
 // the vector-Jacobian product of qs_net for (g_mean, g_logvar) -> (mean [M,10], logvar [M,10], grad [349428], y1, y2, y3, y4, h1, h2, h3); the
 // activations are empty tensors unless want_act
@@ -766,8 +788,10 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
 // are pinned as a closed set (tests/test_abi.py), and these calls are additions beside them, not changes to them.
 TORCH_LIBRARY(efe_g, m) {
     m.def("dec_tail_grad(int ctx, Tensor h4, Tensor o1, float scale, float beta_o, bool want_y) -> (Tensor nlogpo1, Tensor po1, Tensor d_h4, Tensor grad, Tensor y1, Tensor y2, Tensor y3)");
+    m.def("dec_grad(int ctx, Tensor s, Tensor o1, float scale, float beta_o, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(efe_g, CUDA, m) {
     m.impl("dec_tail_grad", &dec_tail_grad_g);
+    m.impl("dec_grad", &dec_grad_g);
 }

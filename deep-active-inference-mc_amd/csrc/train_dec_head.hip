@@ -289,14 +289,23 @@ __global__ void __launch_bounds__(256) k_dech_small(const DecHeadArgs a) {
     }
 }
 
-void launch_dec_head_fwd(const DecHeadArgs& a, hipStream_t st) {
+// layers 0..2 do not depend on the geometry: train_dec_head_g.hip launches them on its own raw copy (a.w, a.s, a.h1 .. a.h3, a.rows, a.key)
+void launch_dec_head_fwd_small(const DecHeadArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_dech_fwd, dim3((a.rows + TR - 1) / TR), dim3(256), 0, st, a);
+}
+
+void launch_dec_head_fwd(const DecHeadArgs& a, hipStream_t st) {
+    launch_dec_head_fwd_small(a, st);
     hipLaunchKernelGGL(k_dech_fc4, dim3(16384 / 16 / 4), dim3(256), 0, st, a);
 }
 
+void launch_dec_head_gate(const float* h4, float* g, size_t n, hipStream_t st) {
+    const int n4 = (int)(n / 4);
+    hipLaunchKernelGGL(k_dech_gate, dim3((n4 + 255) / 256), dim3(256), 0, st, h4, g, n4);
+}
+
 void launch_dec_head_bwd(const DecHeadArgs& a, hipStream_t st) {
-    const int n4 = a.rows * (16384 / 4);
-    hipLaunchKernelGGL(k_dech_gate, dim3((n4 + 255) / 256), dim3(256), 0, st, a.h4, a.g4, n4);
+    launch_dec_head_gate(a.h4, a.g4, (size_t)a.rows * 16384, st);
     hipLaunchKernelGGL(k_dech_w4grad, dim3(16384 / 16 * 2 / 4), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_dech_dh3, dim3(DEC_HEAD_SEGS * 4), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_dech_small, dim3((a.rows + TR - 1) / TR), dim3(256), 0, st, a);

@@ -290,7 +290,31 @@ def grad_decoder(model_down, s, o1, *, scale=None, stage=None, pass_=PASS_FE_DOW
     return res + (tuple(out[4:]),) if return_activations else res
 
 
-ENC_KEYS = tuple(f'qs_net.{i}.{sfx}' for i in (0, 2, 4, 6, 9, 12, 15, 18) for sfx in ('weight', 'bias'))
+def grad_decoder_g(model_down, s, o1, *, scale=None, stage=None, pass_=PASS_FE_DOWN, sample=0, row_offset=None, return_activations=False):
+    """grad_decoder at every admitted geometry (csrc/train_dec_head_g.hip + csrc/train_dec_g.hip, efe_dec_grad_g): the sizes come from the
+    model.  With C colour channels, resolution R, B = R / 4 (16 at R = 32) and F = 64 B B: s [M,10], o1 [M,C,R,R] -> (nlogpo1 [M],
+    po1 [M,C,R,R], d_s [M,10], {state_dict key: dL / d tensor}) and, with return_activations, (h1, h2, h3 [M,256], h4 [M,F] in the
+    Unflatten's order, y1 [M,64,B,B], y2 [M,64,2B,2B], y3 [M,32,R,R]).  The four dropout masks are those `model_down.decoder(s, stage=,
+    pass_=, sample=, row_offset=)` draws at that geometry.  scale None = beta_o / M.  The gradients are views of one flat tensor over
+    DEC_HEAD_KEYS + DEC_CONVT_KEYS in parameters() order; the tail's are grad_decoder_convs_g's on the returned h4, bit for bit.
+    1 x 64 x 64 models run the same run-time-geometry kernels (grad_decoder is then a cross-check)."""
+    m = model_down._owner
+    if scale is not None and not float(scale) >= 0.0:
+        raise ValueError('grad_decoder_g: scale must be >= 0 (None = beta_o / M)')
+    e = m._ready()
+    C_, R = int(m.colour_channels), int(m.resolution)
+    s = e.tensor(s, (-1, m.s_dim))
+    M = s.shape[0]
+    o1 = e.tensor(o1, (M, C_, R, R))
+    nz = m._noise(stage, pass_, sample, row_offset)
+    out = torch.ops.efe_g.dec_grad(e.h, s, o1, -1.0 if scale is None else _f32(scale), _f32(m.beta_o), m._seed64(), nz.stage, pass_, sample,
+                                   nz.row_offset, bool(return_activations))
+    nl, po1, d_s, flat = out[:4]
+    res = (nl, po1, d_s, _views(flat, model_down._sd_host, DEC_HEAD_KEYS + DEC_CONVT_KEYS))
+    return res + (tuple(out[4:]),) if return_activations else res
+
+
+ENC_KEYS =tuple(f'qs_net.{i}.{sfx}' for i in (0, 2, 4, 6, 9, 12, 15, 18) for sfx in ('weight', 'bias'))
 
 
 def _down_model(model_down, who):

@@ -540,6 +540,22 @@ int efe_dec_tail_grad_g(efe_ctx*, const float* h4, const float* o1, int M, float
 int efe_dec_grad(efe_ctx*, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
                  float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream);
 
+/* ---- the same whole-decoder backward at every admitted geometry (csrc/train_dec_head_g.hip + csrc/train_dec_g.hip; additive to ABI 6) ------
+ * efe_dec_grad's arguments and meaning with the sizes taken from the context (C, R, B as efe_dec_tail_grad_g; F = 64 B B features of
+ * po_net.9, 5 184 .. 65 536):
+ *   s, d_s [M,10]   h1, h2, h3 [M,256]   h4 [M,F] (reference order c B B + p)   o1, po1 [M,C,R,R]   y1..y3 as efe_dec_tail_grad_g
+ *   grad [P], P = efe_param_count("po_net") = 134 400 + 257 F + 92 320 + 289 C, parameters() order (9.weight is [F][256], 9.bias [F])
+ * The masks are the forward decoder's at that geometry (efe_decoder; the F-feature mask keyed by the NHWC feature p 64 + c).  It runs
+ * kernels whose feature count is a run-time value at EVERY geometry, 1 x 64 x 64 included (there efe_dec_grad is a cross-check: both hold
+ * the fp64 rule; their bits are not promised equal).  Per row group it queues the head's forward, the tail exactly as efe_dec_tail_grad_g
+ * runs it, and the head's backward: the tail's gradient, po1, nlogpo1 and y1..y3 are bit-identical to efe_dec_tail_grad_g on the returned
+ * h4.  Same refusals as efe_dec_grad but the geometry's (every one before the first launch), same negative-scale rule, same per-row
+ * contract; a fixed-order sum that depends on the geometry and M alone: twice the same bits.  Rows are processed
+ * in groups of 64 (B <= 16) or 32: beside the tail's scratch at most 27 MB for the head (h4, d_h4 and the partial sums of d_h3, 8 MB each
+ * at resolution 128) and four partial gradients of 538 KB.  There is no optimiser step for this part yet. */
+int efe_dec_grad_g(efe_ctx*, const float* s, const float* o1, int M, float scale, float beta_o, const efe_noise* nz, float* nlogpo1, float* po1,
+                   float* d_s, float* grad, float* h1, float* h2, float* h3, float* h4, float* y1, float* y2, float* y3, void* stream);
+
 /* ---- gradient of F_down for all of ModelDown (csrc/train_enc.hip with the two decoder files; additive to ABI 6) --------------------------
  * train_model_down (src/torchloss.py:90-98) up to the gradient, at the 1 x 64 x 64 geometry: the encoder qs_net evaluated for training
  * (four stride-2 convolutions, Linear 576-256-256-256-20 with ReLU and Dropout(0.5) behind the first three, torchmodel.py:84-104, with
