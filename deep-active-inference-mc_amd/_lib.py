@@ -183,6 +183,8 @@ SIGNATURES = {
     'efe_dec_grad_g': (_i, (_p, _p, _p, _i, _f, _f, _nz) + (_p,) * 12),
     'efe_enc_grad': (_i, (_p, _p, _p, _p, _i, _nz) + (_p,) * 11),
     'efe_down_grad': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p, _p, _p, _p)),
+    'efe_enc_grad_g': (_i, (_p, _p, _p, _p, _i, _nz) + (_p,) * 11),
+    'efe_down_grad_g': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p, _p, _p, _p)),
     'efe_train_down': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p, _p, _ap, _p)),
     'efe_down_adam_step': (_i, (_p, _p, _p, _p, _ap, _p)),
     'efe_down_get_weights': (_i, (_p, _p, _l, _p)),

@@ -102,6 +102,8 @@ struct efe_ctx {
     float* dec_raw_g = nullptr;    // the whole po_net at ANY geometry, [134 400 + 257 * 64 base^2] (DecHeadGeo) then the tail: train_dec_head_g.hip
                                    // reads it.  dect_raw_g = dec_raw_g + the head's size; = dec_raw at 1 x 64 x 64, else a buffer of the current commit
     float* enc_raw = nullptr;      // the whole qs_net unpacked, flat in parameters() order (kernels.h EQ_*): train_enc.hip reads it
+    float* enc_raw_g = nullptr;    // the same at ANY geometry, [201 684 + 288 chan + 256 K] (EncGeo): train_enc_g.hip reads it.  = enc_raw at 1 x 64 x 64
+                                   // (so that it follows ModelDown's optimiser steps), else a buffer of the current commit; enc_raw stays null there
     // ModelDown's master copy at 1 x 64 x 64 (owned: it outlives a re-commit, as TrainPart::master): [DOWN_P], qs_net then po_net, so
     // enc_raw = down_master and dec_raw = down_master + ENC_P.  An optimiser step (train_down.hip) writes it and rebuilds every packed form
     // of the table down_repack (device; one entry per packed buffer of pack_heads / pack_encoder / pack_decoder, built at commit).

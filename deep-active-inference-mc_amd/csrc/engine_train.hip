@@ -184,49 +184,63 @@ int dec_grad(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4
     return 0;
 }
 
-// efe_dec_tail_grad_g and efe_dec_grad_g inside their call scope: the decoder's gradient by the run-time-geometry kernels (train_dec_g.hip,
+// efe_dec_tail_grad_g and efe_dec_grad_g inside their call scope, as the row groups of one call (open / group / close, so that efe_down_grad_g
+// can run the encoder's group around each of the decoder's): the decoder's gradient by the run-time-geometry kernels (train_dec_g.hip,
 // train_dec_head_g.hip), at every admitted geometry.  Row groups of geo.rows_per_pass() rows; scratch of one group from the arena: the
 // activations the caller gives no output for, the four gradients, and G slabs (none at G = 1: the gradient itself).
 // hd == nullptr: the tail alone, from the caller's h4 to the caller's d_h4 (nullable), grad [geo.P()].  Else the whole decoder, grad
 // [hg.P() + geo.P()], h4 / d_h4 unused: per group the head's forward, launch_dec_tail_g_group exactly as without the head (on the group's h4,
 // d_h4 to scratch), the head's backward; the head takes h1..h4 and d_h4 of one group and the S x rows x 256 partials of d_h3 as well.
-int dec_grad_g_run(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1,
-                   float* po1, float* d_h4, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
-    // (a context without the raw copy cannot exist once committed: the geometry test of the shared checks stands for "the copy is there")
-    const bool ptrs = (hd ? hd->s && hd->nz : h4 != nullptr) && o1 && nlogpo1 && grad;
-    if (dec_grad_checks(ctx, who, M, ptrs, hd ? ": s, o1, nz, nlogpo1 and grad must be non-NULL" : ": h4, o1, nlogpo1 and grad must be non-NULL",
-                        (hd ? ctx->dec_raw_g : ctx->dect_raw_g) != nullptr, scale, beta_o))
-        return 1;
-    const DecTailGeo geo{ctx->base, ctx->chan, ctx->last_s1 ? 1 : 2};
-    const DecHeadGeo hg{ctx->base};
-    const int C = std::min(geo.rows_per_pass(), M), G = dec_tail_slabs(M), P = geo.P();
-    const size_t n = (size_t)C;
-    float* tgrad = hd ? grad + hg.P() : grad;        // the tail's gradient
-    float* s1 = y1 ? nullptr : ctx->allocT<float>(n * geo.y1());
-    float* s2 = y2 ? nullptr : ctx->allocT<float>(n * geo.y2());
-    float* s3 = y3 ? nullptr : ctx->allocT<float>(n * geo.y3());
-    float* sp = po1 ? nullptr : ctx->allocT<float>(n * geo.img());
-    float* g4 = ctx->allocT<float>(n * geo.img());
-    float* g3 = ctx->allocT<float>(n * geo.y3());
-    float* g2 = ctx->allocT<float>(n * geo.y2());
-    float* g1 = ctx->allocT<float>(n * geo.y1());
-    float* slabs = G > 1 ? ctx->allocT<float>((size_t)G * P) : tgrad;
-    if ((!y1 && !s1) || (!y2 && !s2) || (!y3 && !s3) || (!po1 && !sp) || !g4 || !g3 || !g2 || !g1 || !slabs) return 1;
-    const int GH = dec_head_slabs(M);
+struct DecGradG {
+    efe_ctx* ctx; const DecHeadIO* hd; const float* h4; const float* o1; int M; float scale;
+    float *nlogpo1, *po1, *d_h4, *grad, *y1, *y2, *y3;
+    hipStream_t st;
+    DecTailGeo geo; DecHeadGeo hg;
+    int C, G, GH, P;
+    float *tgrad, *s1, *s2, *s3, *sp, *g4, *g3, *g2, *g1, *slabs;
     float *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr, *dh4 = nullptr, *part = nullptr, *hslabs = nullptr;
-    if (hd) {
-        if (!hd->h1) a1 = ctx->allocT<float>(n * 256);
-        if (!hd->h2) a2 = ctx->allocT<float>(n * 256);
-        if (!hd->h3) a3 = ctx->allocT<float>(n * 256);
-        if (!hd->h4) a4 = ctx->allocT<float>(n * geo.y1());
-        dh4 = ctx->allocT<float>(n * geo.y1());
-        part = ctx->allocT<float>((size_t)hg.segs() * n * 256);
-        hslabs = GH > 1 ? ctx->allocT<float>((size_t)GH * DEC_HEAD_SMALL_P) : grad;
-        if ((!hd->h1 && !a1) || (!hd->h2 && !a2) || (!hd->h3 && !a3) || (!hd->h4 && !a4) || !dh4 || !part || !hslabs) return 1;
+    int open(efe_ctx* ctx_, const char* who, const DecHeadIO* hd_, const float* h4_, const float* o1_, int M_, float scale_, float beta_o, float* nlogpo1_,
+             float* po1_, float* d_h4_, float* grad_, float* y1_, float* y2_, float* y3_, hipStream_t st_) {
+        ctx = ctx_; hd = hd_; h4 = h4_; o1 = o1_; M = M_; scale = scale_; nlogpo1 = nlogpo1_; po1 = po1_; d_h4 = d_h4_; grad = grad_;
+        y1 = y1_; y2 = y2_; y3 = y3_; st = st_;
+        // (a context without the raw copy cannot exist once committed: the geometry test of the shared checks stands for "the copy is there")
+        const bool ptrs = (hd ? hd->s && hd->nz : h4 != nullptr) && o1 && nlogpo1 && grad;
+        if (dec_grad_checks(ctx, who, M, ptrs, hd ? ": s, o1, nz, nlogpo1 and grad must be non-NULL" : ": h4, o1, nlogpo1 and grad must be non-NULL",
+                            (hd ? ctx->dec_raw_g : ctx->dect_raw_g) != nullptr, scale, beta_o))
+            return 1;
+        geo = DecTailGeo{ctx->base, ctx->chan, ctx->last_s1 ? 1 : 2};
+        hg = DecHeadGeo{ctx->base};
+        C = std::min(geo.rows_per_pass(), M); G = dec_tail_slabs(M); P = geo.P();
+        const size_t n = (size_t)C;
+        tgrad = hd ? grad + hg.P() : grad;        // the tail's gradient
+        s1 = y1 ? nullptr : ctx->allocT<float>(n * geo.y1());
+        s2 = y2 ? nullptr : ctx->allocT<float>(n * geo.y2());
+        s3 = y3 ? nullptr : ctx->allocT<float>(n * geo.y3());
+        sp = po1 ? nullptr : ctx->allocT<float>(n * geo.img());
+        g4 = ctx->allocT<float>(n * geo.img());
+        g3 = ctx->allocT<float>(n * geo.y3());
+        g2 = ctx->allocT<float>(n * geo.y2());
+        g1 = ctx->allocT<float>(n * geo.y1());
+        slabs = G > 1 ? ctx->allocT<float>((size_t)G * P) : tgrad;
+        if ((!y1 && !s1) || (!y2 && !s2) || (!y3 && !s3) || (!po1 && !sp) || !g4 || !g3 || !g2 || !g1 || !slabs) return 1;
+        GH = dec_head_slabs(M);
+        if (hd) {
+            if (!hd->h1) a1 = ctx->allocT<float>(n * 256);
+            if (!hd->h2) a2 = ctx->allocT<float>(n * 256);
+            if (!hd->h3) a3 = ctx->allocT<float>(n * 256);
+            if (!hd->h4) a4 = ctx->allocT<float>(n * geo.y1());
+            dh4 = ctx->allocT<float>(n * geo.y1());
+            part = ctx->allocT<float>((size_t)hg.segs() * n * 256);
+            hslabs = GH > 1 ? ctx->allocT<float>((size_t)GH * DEC_HEAD_SMALL_P) : grad;
+            if ((!hd->h1 && !a1) || (!hd->h2 && !a2) || (!hd->h3 && !a3) || (!hd->h4 && !a4) || !dh4 || !part || !hslabs) return 1;
+        }
+        return 0;
     }
-    for (int m0 = 0; m0 < M; m0 += C) {
+    int rows(int m0) const { return std::min(C, M - m0); }
+    const float* po_of(int m0) const { return po1 ? po1 + (size_t)m0 * geo.img() : sp; }      // the images (NCHW) of the group that starts at row m0
+    void group(int m0) {
         const size_t m = (size_t)m0;
-        const int rows = std::min(C, M - m0);
+        const int rows = this->rows(m0);
         DecHeadGArgs h{};
         if (hd) {
             h.geo = hg; h.w = ctx->dec_raw_g; h.s = hd->s + m * S_DIM;
@@ -245,13 +259,22 @@ int dec_grad_g_run(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const flo
         launch_dec_tail_g_group(a, st);
         if (hd) launch_dec_head_g_bwd(h, st);
     }
-    if (G > 1) launch_slab_sum(slabs, G, P, tgrad, st);
-    if (hd && GH > 1) launch_slab_sum(hslabs, GH, DEC_HEAD_SMALL_P, grad, st);
-    // forward, data gradient, weight gradient of the four layers: 2 x 36 864 B^2, 18 432 (2B)^2, 288 C R^2 multiply-adds each; of the head's
-    // four: 10 x 256, 2 x 256 x 256, 256 F
-    const int64_t BB = (int64_t)geo.B * geo.B, RR = (int64_t)geo.R() * geo.R();
-    ctx->last_macs += (int64_t)M * 3 * (2 * 36864 * BB + 18432 * 4 * BB + 288 * geo.C * RR);
-    if (hd) ctx->last_macs += (int64_t)M * 3 * (2560 + 131072 + 256 * (int64_t)hg.F());
+    void close() {
+        if (G > 1) launch_slab_sum(slabs, G, P, tgrad, st);
+        if (hd && GH > 1) launch_slab_sum(hslabs, GH, DEC_HEAD_SMALL_P, grad, st);
+        // forward, data gradient, weight gradient of the four layers: 2 x 36 864 B^2, 18 432 (2B)^2, 288 C R^2 multiply-adds each; of the head's
+        // four: 10 x 256, 2 x 256 x 256, 256 F
+        const int64_t BB = (int64_t)geo.B * geo.B, RR = (int64_t)geo.R() * geo.R();
+        ctx->last_macs += (int64_t)M * 3 * (2 * 36864 * BB + 18432 * 4 * BB + 288 * geo.C * RR);
+        if (hd) ctx->last_macs += (int64_t)M * 3 * (2560 + 131072 + 256 * (int64_t)hg.F());
+    }
+};
+int dec_grad_g_run(efe_ctx* ctx, const char* who, const DecHeadIO* hd, const float* h4, const float* o1, int M, float scale, float beta_o, float* nlogpo1,
+                   float* po1, float* d_h4, float* grad, float* y1, float* y2, float* y3, hipStream_t st) {
+    DecGradG d;
+    if (d.open(ctx, who, hd, h4, o1, M, scale, beta_o, nlogpo1, po1, d_h4, grad, y1, y2, y3, st)) return 1;
+    for (int m0 = 0; m0 < M; m0 += d.C) d.group(m0);
+    d.close();
     return 0;
 }
 
@@ -362,6 +385,120 @@ int down_grad_run(efe_ctx* ctx, const char* who, const float* o1, const float* p
     return 0;
 }
 
+// ---- the same at every admitted geometry (train_enc_g.hip): EncGrad's shape with the sizes from the context ------------------------------
+// Scratch of one row group from the arena: the activations the caller gives no output for, the four conv gradients, the S x rows x 256
+// partials of W9 y4, g_0, and the two sets of slabs (none at G = 1: the gradient itself).  dW9 / db9 go into the gradient in place.
+struct EncGradG {
+    efe_ctx* ctx; const float* o; const float *g_mean, *g_logvar; int M; const efe_noise* nz;
+    float *mean, *logvar, *grad, *y1, *y2, *y3, *y4, *h1, *h2, *h3;
+    hipStream_t st;
+    EncGeo geo;
+    int C, GC, GH;
+    float *s1, *s2, *s3, *s4, *a1, *a2, *a3, *g4, *g3, *g2, *g1, *part, *g0, *cslabs, *hslabs;
+    // every refusal of the geometry-independent kind; M and the pointers are the caller's to check first
+    int open(efe_ctx* ctx_, const char* who, const float* o_, int M_, const efe_noise* nz_, float* mean_, float* logvar_, float* grad_,
+             float* y1_, float* y2_, float* y3_, float* y4_, float* h1_, float* h2_, float* h3_, hipStream_t st_) {
+        ctx = ctx_; o = o_; M = M_; nz = nz_; mean = mean_; logvar = logvar_; grad = grad_;
+        y1 = y1_; y2 = y2_; y3 = y3_; y4 = y4_; h1 = h1_; h2 = h2_; h3 = h3_; st = st_; g_mean = g_logvar = nullptr;
+        const std::string w(who);
+        if (!ctx->enc_raw_g) return ctx->fail(w + ": the weights are not committed");
+        if (ctx->mfma_bf16x3) return ctx->fail(w + ": not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+        geo = EncGeo{ctx->chan, ctx->res};
+        const DecTailGeo dg{ctx->base, ctx->chan, ctx->last_s1 ? 1 : 2};
+        C = std::min(dg.rows_per_pass(), M); GC = enc_conv_slabs(M); GH = enc_head_slabs(M);
+        const size_t n = (size_t)C;
+        s1 = y1 ? nullptr : ctx->allocT<float>(n * geo.y1());
+        s2 = y2 ? nullptr : ctx->allocT<float>(n * geo.y2());
+        s3 = y3 ? nullptr : ctx->allocT<float>(n * geo.y3());
+        s4 = y4 ? nullptr : ctx->allocT<float>(n * geo.y4());
+        a1 = h1 ? nullptr : ctx->allocT<float>(n * 256);
+        a2 = h2 ? nullptr : ctx->allocT<float>(n * 256);
+        a3 = h3 ? nullptr : ctx->allocT<float>(n * 256);
+        g4 = ctx->allocT<float>(n * geo.y4()); g3 = ctx->allocT<float>(n * geo.y3()); g2 = ctx->allocT<float>(n * geo.y2()); g1 = ctx->allocT<float>(n * geo.y1());
+        part = ctx->allocT<float>((size_t)geo.segs() * n * 256);
+        g0 = ctx->allocT<float>(n * 256);
+        if (!mean) mean = ctx->allocT<float>((size_t)M * S_DIM);
+        if (!logvar) logvar = ctx->allocT<float>((size_t)M * S_DIM);
+        cslabs = GC > 1 ? ctx->allocT<float>((size_t)GC * geo.conv_P()) : grad;
+        hslabs = GH > 1 ? ctx->allocT<float>((size_t)GH * ENC_SMALL_P) : grad + geo.small();
+        if ((!y1 && !s1) || (!y2 && !s2) || (!y3 && !s3) || (!y4 && !s4) || (!h1 && !a1) || (!h2 && !a2) || (!h3 && !a3) || !g4 || !g3 || !g2 || !g1 ||
+            !part || !g0 || !mean || !logvar || !cslabs || !hslabs)
+            return 1;
+        return 0;
+    }
+    EncTrainGArgs args(int m0) const {
+        const size_t m = (size_t)m0;
+        EncTrainGArgs a{};
+        a.geo = geo; a.w = ctx->enc_raw_g; a.o = o + m * geo.img();
+        a.y1 = y1 ? y1 + m * geo.y1() : s1; a.y2 = y2 ? y2 + m * geo.y2() : s2; a.y3 = y3 ? y3 + m * geo.y3() : s3; a.y4 = y4 ? y4 + m * geo.y4() : s4;
+        a.h1 = h1 ? h1 + m * 256 : a1; a.h2 = h2 ? h2 + m * 256 : a2; a.h3 = h3 ? h3 + m * 256 : a3;
+        a.mean = mean + m * S_DIM; a.logvar = logvar + m * S_DIM;
+        a.g_mean = g_mean ? g_mean + m * S_DIM : nullptr; a.g_logvar = g_logvar ? g_logvar + m * S_DIM : nullptr;
+        a.g4 = g4; a.g3 = g3; a.g2 = g2; a.g1 = g1; a.part = part; a.g0 = g0; a.grad = grad; a.cslabs = cslabs; a.hslabs = hslabs;
+        a.rows = std::min(C, M - m0); a.GC = GC; a.first = m0 == 0; a.tile0 = m0 / 16; a.key = train_key(nz, (uint32_t)m0);
+        return a;
+    }
+    void fwd(int m0) { launch_enc_train_g_fwd(args(m0), st); }
+    void bwd(int m0) { launch_enc_train_g_bwd(args(m0), st); }
+    void close() {
+        if (GC > 1) launch_slab_sum(cslabs, GC, geo.conv_P(), grad, st);
+        if (GH > 1) launch_slab_sum(hslabs, GH, ENC_SMALL_P, grad + geo.small(), st);
+        // forward, data gradient, weight gradient: 288 C H1^2 + 9 216 H2^2 + 18 432 H3^2 + 36 864 H4^2 conv, 256 K + 2 x 65 536 + 5 120 dense
+        const int64_t a1_ = geo.H1(), a2_ = geo.H2(), a3_ = geo.H3(), a4_ = geo.H4();
+        ctx->last_macs += (int64_t)M * 3 * (288 * geo.C * a1_ * a1_ + 9216 * a2_ * a2_ + 18432 * a3_ * a3_ + 36864 * a4_ * a4_ + 256 * (int64_t)geo.K() + 136192);
+    }
+};
+
+// efe_down_grad_g inside its call scope: down_grad_run's loop with the run-time-geometry encoder and decoder.  Every refusal comes before
+// the first launch.
+int down_grad_g_run(efe_ctx* ctx, const char* who, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                    const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, hipStream_t st) {
+    const std::string w(who);
+    if (M <= 0) return ctx->fail(w + ": M must be >= 1");
+    if (!o1 || !ps1_mean || !ps1_logvar || !nz || !out || !grad)
+        return ctx->fail(w + ": o1, ps1_mean, ps1_logvar, params, nz, out and grad must be non-NULL");
+    if (fe_params(ctx, params, false, who)) return 1;
+    if (!out->F_down) return ctx->fail(w + ": out->F_down is required");
+    EncGradG e;
+    if (e.open(ctx, who, o1, M, nz, out->qs1_mean, out->qs1_logvar, grad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return 1;
+    float* qs1 = out->qs1 ? out->qs1 : ctx->allocT<float>((size_t)M * S_DIM);
+    float* d_s = ctx->allocT<float>((size_t)M * S_DIM);
+    float* nl = out->nlogpo1 ? out->nlogpo1 : ctx->allocT<float>((size_t)M);
+    float* gm = g_mean ? g_mean : ctx->allocT<float>((size_t)M * S_DIM);
+    float* gv = g_logvar ? g_logvar : ctx->allocT<float>((size_t)M * S_DIM);
+    if (!qs1 || !d_s || !nl || !gm || !gv) return 1;
+    e.g_mean = gm; e.g_logvar = gv;
+    const DecHeadIO hd{qs1, nz, d_s, nullptr, nullptr, nullptr, nullptr};
+    DecGradG d;
+    if (d.open(ctx, who, &hd, nullptr, o1, M, -1.0f, params->beta_o, nl, out->po1, nullptr, grad + e.geo.P(), nullptr, nullptr, nullptr, st)) return 1;
+    const float* omega = params->omega_mode == EFE_OMEGA_ARRAY ? params->omega : nullptr;
+    // F_down and its terms: k_fe_down's expressions on the training forward's po1 (NCHW here, whatever the context's forward store), mean and logvar
+    efe_fe_out fo{};
+    fo.F_down = out->F_down; fo.kl_s = out->kl_s; fo.kl_naive = out->kl_naive;
+    FeArgs fa = fe_down_args(ctx, M, o1, e.mean, ps1_mean, ps1_logvar, S_DIM, params, omega, &fo);
+    fa.q1_mean = e.mean; fa.q1_lv = e.logvar; fa.q1_ld = S_DIM; fa.nhwc4 = 0;
+    const uint32_t k0 = (uint32_t)nz->seed, k1 = (uint32_t)(nz->seed >> 32);
+    for (int m0 = 0; m0 < M; m0 += e.C) {           // (both cut the rows at multiples of rows_per_pass())
+        const int rows = d.rows(m0);
+        const size_t r10 = (size_t)m0 * S_DIM;
+        e.fwd(m0);
+        launch_reparam(e.mean + r10, e.logvar + r10, eps ? eps + r10 : nullptr, qs1 + r10, rows, S_DIM, k0, k1, nz->pass, nz->sample, nz->stage,
+                       nz->row_offset + (uint32_t)m0, st);
+        d.group(m0);
+        launch_fe_down(fa, d.po_of(m0), m0, rows, st);
+        DownLatentArgs la{};
+        la.d_s = d_s + r10; la.mean = e.mean + r10; la.logvar = e.logvar + r10; la.p1_mean = ps1_mean + r10; la.p1_lv = ps1_logvar + r10;
+        la.eps_inj = eps ? eps + r10 : nullptr; la.omega_in = omega ? omega + m0 : nullptr; la.omega_scalar = params->omega_scalar;
+        la.gamma = params->gamma; la.beta_s = params->beta_s; la.Mf = (float)M;
+        la.g_mean = gm + r10; la.g_logvar = gv + r10; la.rows = rows; la.key = train_key(nz, (uint32_t)m0);
+        launch_down_latent(la, st);
+        e.bwd(m0);
+    }
+    d.close();
+    e.close();
+    return 0;
+}
+
 // ModelDown's optimiser step (train_down.hip): the 1 x 64 x 64 geometry, exact fp32 planes only, sane hyper-parameters
 int down_step_args(efe_ctx* ctx, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, DownAdamArgs& a, const char* who) {
     const std::string w(who);
@@ -412,6 +549,11 @@ int64_t efe_param_count(efe_ctx* ctx, const char* part) {
     if (part && (!strcmp(part, "qs_net") || !strcmp(part, "down"))) {
         if (ctx->chan != 1 || ctx->res != 64) { ctx->fail("efe_param_count: \"qs_net\" and \"down\" are counted for the 1 x 64 x 64 geometry only"); return 0; }
         return !strcmp(part, "qs_net") ? ENC_P : DOWN_P;
+    }
+    // the same two at the context's own geometry (efe_enc_grad_g, efe_down_grad_g), likewise without an optimiser step
+    if (part && (!strcmp(part, "qs_net_g") || !strcmp(part, "down_g"))) {
+        const int64_t enc = EncGeo{ctx->chan, ctx->res}.P();
+        return !strcmp(part, "qs_net_g") ? enc : enc + DH_W3 + (int64_t)64 * ctx->base * ctx->base * 257 + DT_B3 + 32 + 32 * ctx->chan * 9 + ctx->chan;
     }
     if (!train_part(ctx, part, "efe_param_count")) return 0;
     return !strcmp(part, "top") ? part_param_count(TOP_NL, top_layer, ctx->pi_dim) : part_param_count(MID_NL, mid_layer, ctx->pi_dim);
@@ -518,6 +660,26 @@ int efe_down_grad(efe_ctx* ctx, const float* o1, const float* ps1_mean, const fl
                   const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream) {
     hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return 1;
     if (down_grad_run(ctx, "efe_down_grad", o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, g_mean, g_logvar, grad, st)) return 1;
+    return call.finish();
+}
+
+int efe_enc_grad_g(efe_ctx* ctx, const float* o, const float* g_mean, const float* g_logvar, int M, const efe_noise* nz, float* mean, float* logvar,
+                   float* grad, float* y1, float* y2, float* y3, float* y4, float* h1, float* h2, float* h3, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_enc_grad_g");
+    if (M <= 0) return ctx->fail("efe_enc_grad_g: M must be >= 1");
+    if (!o || !g_mean || !g_logvar || !nz || !grad) return ctx->fail("efe_enc_grad_g: o, g_mean, g_logvar, nz and grad must be non-NULL");
+    EncGradG e;
+    if (e.open(ctx, "efe_enc_grad_g", o, M, nz, mean, logvar, grad, y1, y2, y3, y4, h1, h2, h3, st)) return 1;
+    e.g_mean = g_mean; e.g_logvar = g_logvar;
+    for (int m0 = 0; m0 < M; m0 += e.C) { e.fwd(m0); e.bwd(m0); }
+    e.close();
+    return call.finish();
+}
+
+int efe_down_grad_g(efe_ctx* ctx, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                    const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return call.refused("efe_down_grad_g");
+    if (down_grad_g_run(ctx, "efe_down_grad_g", o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, g_mean, g_logvar, grad, st)) return 1;
     return call.finish();
 }
 

@@ -326,9 +326,11 @@ int pack_heads(efe_ctx* ctx) {
 // encoder (torchmodel.py:84-104): the convolution stack, then the head's first layer
 int pack_encoder(efe_ctx* ctx) {
     const int C = ctx->chan, F = ctx->enc_hw[4] * ctx->enc_hw[4];
-    ctx->enc_raw = nullptr;
-    if (C == 1 && ctx->res == 64) {     // the raw copy the training forward and backward read (train_enc.hip), beside the packed forward forms
+    ctx->enc_raw = ctx->enc_raw_g = nullptr;
+    {   // the raw copy the training forward and backward read (train_enc.hip, train_enc_g.hip), beside the packed forward forms
+        const EncGeo eg{C, ctx->res};
         std::vector<float> flat;
+        flat.reserve((size_t)eg.P());
         for (int i = 0; i < 8; ++i) {
             const LayerSpec s = i < 4 ? enc_conv_layer(i, C) : i == 4 ? LayerSpec{"down.qs_net.9", 256, F * 64} : ENC_HEAD[i - 5];
             const WB t = i < 4 ? weight_and_bias(ctx, s.key, {s.out, s.in, 3, 3}, {s.out}) : weight_and_bias(ctx, s.key, {s.out, s.in}, {s.out});
@@ -336,8 +338,12 @@ int pack_encoder(efe_ctx* ctx) {
             flat.insert(flat.end(), t.w->data.begin(), t.w->data.end());
             flat.insert(flat.end(), t.b->data.begin(), t.b->data.end());
         }
-        if (flat.size() != (size_t)ENC_P) return ctx->fail("encoder: unexpected parameter count");
-        if (!(ctx->enc_raw = upload_master(ctx, flat, 0))) return 1;
+        if (F * 64 != eg.K() || flat.size() != (size_t)eg.P()) return ctx->fail("encoder: unexpected parameter count");
+        if (C == 1 && ctx->res == 64) {     // inside ModelDown's master vector, so that it follows an optimiser step
+            if (flat.size() != (size_t)ENC_P) return ctx->fail("encoder: unexpected parameter count");
+            if (!(ctx->enc_raw = upload_master(ctx, flat, 0))) return 1;
+            ctx->enc_raw_g = ctx->enc_raw;
+        } else if (!(ctx->enc_raw_g = upload(ctx, flat))) return 1;      // any other geometry: a buffer of this commit
     }
     if (ctx->generic) {     // build-defined geometry: four k_conv_g layers ...
         for (int i = 0; i < 4; ++i) if (pack_conv(ctx, ctx->g_enc[i], enc_conv_layer(i, C), false)) return 1;
@@ -533,7 +539,7 @@ int efe_commit_weights(efe_ctx* ctx) {
         for (void* p : ctx->wbufs) (void)hipFree(p);
         ctx->wbufs.clear();
         ctx->fc4_b3 = nullptr; ctx->ct_b3[0] = ctx->ct_b3[1] = nullptr; ctx->ct3_b3 = nullptr; ctx->split_packed = 0;
-        ctx->dec_raw = ctx->dect_raw = ctx->dec_raw_g = ctx->dect_raw_g = ctx->enc_raw = nullptr;
+        ctx->dec_raw = ctx->dect_raw = ctx->dec_raw_g = ctx->dect_raw_g = ctx->enc_raw = ctx->enc_raw_g = nullptr;
     }
     ctx->committed = false;
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first

@@ -682,6 +682,61 @@ struct EncTrainArgs {                    // one row group (at most DEC_TAIL_ROWS
 };
 void launch_enc_train_fwd(const EncTrainArgs& a, hipStream_t st);     // o -> y1 .. y4, h1 .. h3, mean, logvar
 void launch_enc_train_bwd(const EncTrainArgs& a, hipStream_t st);     // (g_mean, g_logvar) -> the slabs of every parameter's gradient
+
+// ---- the same encoder at every admitted geometry (train_enc_g.hip): C input channels, resolution R, from the context ------------------
+// The flat vector in parameters() order: 0.weight [32][C][3][3], 0.bias, 2.weight .. 6.bias as above, 9.weight [256][K], 9.bias, then
+// 12.weight .. 18.bias (ENC_SMALL_P floats, the part whose gradient goes through the head's slabs).  P = 201 684 + 288 C + 256 K.
+constexpr int ENC_SMALL_P = 2 * (256 * 256 + 256) + 20 * 256 + 20;                  // 136 724: 12.weight .. 18.bias
+constexpr int EQS_W12 = 0, EQS_B12 = EQS_W12 + 256 * 256, EQS_W15 = EQS_B12 + 256, EQS_B15 = EQS_W15 + 256 * 256, EQS_W18 = EQS_B15 + 256,
+              EQS_B18 = EQS_W18 + 20 * 256;                                          // offsets inside that part
+struct EncGeo {
+    int C, R;
+    __host__ __device__ static int down(int h) { return (h - 3) / 2 + 1; }
+    __host__ __device__ int H1() const { return down(R); }                          // 15 .. 63
+    __host__ __device__ int H2() const { return down(H1()); }                       //  7 .. 31
+    __host__ __device__ int H3() const { return down(H2()); }                       //  3 .. 15
+    __host__ __device__ int H4() const { return down(H3()); }                       //  1 ..  7
+    __host__ __device__ int K() const { return 64 * H4() * H4(); }                  // inputs of qs_net.9: 64 .. 3 136, a multiple of 64
+    __host__ __device__ int segs() const { return (K() + 255) / 256; }              // K segments of W9 y4: 1 .. 13, the last may hold 64 inputs
+    __host__ __device__ int w1() const { return 0; }
+    __host__ __device__ int b1() const { return 288 * C; }
+    __host__ __device__ int w2() const { return b1() + 32; }
+    __host__ __device__ int b2() const { return w2() + 32 * 32 * 9; }
+    __host__ __device__ int w3() const { return b2() + 32; }
+    __host__ __device__ int b3() const { return w3() + 64 * 32 * 9; }
+    __host__ __device__ int w4() const { return b3() + 64; }
+    __host__ __device__ int b4() const { return w4() + 64 * 64 * 9; }
+    __host__ __device__ int conv_P() const { return b4() + 64; }                    // 64 704 + 288 C: one slab of the convolutions' gradient
+    __host__ __device__ int w9() const { return conv_P(); }
+    __host__ __device__ int b9() const { return w9() + 256 * K(); }
+    __host__ __device__ int small() const { return b9() + 256; }                    // 12.weight: where the ENC_SMALL_P floats begin
+    __host__ __device__ int P() const { return small() + ENC_SMALL_P; }
+    size_t img() const { return (size_t)C * R * R; }                                // floats per row
+    size_t y1() const { return (size_t)32 * H1() * H1(); }
+    size_t y2() const { return (size_t)32 * H2() * H2(); }
+    size_t y3() const { return (size_t)64 * H3() * H3(); }
+    size_t y4() const { return (size_t)K(); }
+};
+struct EncTrainGArgs {                   // one row group (DecTailGeo::rows_per_pass() rows at most): every row pointer is the group's first row
+    EncGeo geo;
+    const float* w;                      // raw parameters [geo.P()]
+    const float* o;                      // [rows][C][R][R], the caller's NCHW image
+    float *y1, *y2, *y3, *y4;            // stored forward: relu outputs [rows][32][H1][H1], [32][H2][H2], [64][H3][H3], [64][H4][H4] (NCHW)
+    float *h1, *h2, *h3;                 // ... of the head, after the mask [rows][256]
+    float *mean, *logvar;                // [rows][10]
+    const float *g_mean, *g_logvar;      // backward: the upstream pair [rows][10]
+    float *g4, *g3, *g2, *g1;            // dL / da of the four convolutions, shaped as y4 .. y1
+    float* part;                         // [geo.segs()][rows][256] partial sums of W9 y4
+    float* g0;                           // [rows][256] dL / da of qs_net.9
+    float* grad;                         // the caller's gradient: 9.weight / 9.bias are written (first) or added to in place
+    float* cslabs;                       // [GC][geo.conv_P()]; first != 0: written, else added to
+    float* hslabs;                       // [GH][ENC_SMALL_P]; a tile writes its slab if it is the slab's first, else adds to it
+    int rows, GC, first;                 // first: the call's first row group
+    int tile0;                           // global index of the group's first 16-row tile: tile t of the call goes to slab t mod ENC_HEAD_SLABS
+    TrainKey key;                        // row0 = the global row of the group's row 0
+};
+void launch_enc_train_g_fwd(const EncTrainGArgs& a, hipStream_t st);  // o -> y1 .. y4, h1 .. h3, mean, logvar
+void launch_enc_train_g_bwd(const EncTrainGArgs& a, hipStream_t st);  // (g_mean, g_logvar) -> every parameter's gradient (slabs, 9.* in place)
 // d mean(F_down) / d (qs1_mean, qs1_logvar) of one row group: the decoder's d_s through the sample plus the two KL terms of compute_loss_down
 struct DownLatentArgs {
     const float *d_s, *mean, *logvar, *p1_mean, *p1_lv;      // [rows][10] each

@@ -604,6 +604,47 @@ std::vector<Tensor> down_grad(int64_t h, const Tensor& o1_, const Tensor& pm_, c
     return {F, nl, kls, kln, po1, qs1, qm, qv, gm, gv, grad};
 }
 
+// ---- the same two at every admitted geometry (csrc/train_enc_g.hip): sizes from the context ----
+// -> (mean [M,10], logvar [M,10], grad [201684 + 288 C + 256 K], y1 [M,32,H1,H1], y2 [M,32,H2,H2], y3 [M,64,H3,H3], y4 [M,64,H4,H4], h1, h2, h3 [M,256]),
+// H_l = (H_{l-1} - 3) / 2 + 1 from R, K = 64 H4 H4
+std::vector<Tensor> enc_grad_g(int64_t h, const Tensor& o_, const Tensor& gm_, const Tensor& gv_, int64_t seed, int64_t stage, int64_t pass, int64_t sample,
+                               int64_t row_offset, bool want_act) {
+    Ctx x(h);
+    Tensor o = x.f32(o_, "o"), gm = x.f32(gm_, "d_mean"), gv = x.f32(gv_, "d_logvar");
+    const int M = rows(o, x.img(), "o");
+    TORCH_CHECK(gm.numel() == (int64_t)M * 10 && gv.numel() == (int64_t)M * 10, "efe: d_mean and d_logvar must be [M, 10]");
+    const int64_t NP = x.param_count("qs_net_g");
+    const efe_noise nz = noise(seed, stage, pass, sample, row_offset);
+    auto op = o.options();
+    const int64_t Ma = want_act ? M : 0;
+    const int64_t H1 = (x.R - 3) / 2 + 1, H2 = (H1 - 3) / 2 + 1, H3 = (H2 - 3) / 2 + 1, H4 = (H3 - 3) / 2 + 1;
+    Tensor mean = at::empty({M, 10}, op), lv = at::empty({M, 10}, op), grad = at::empty({NP}, op);
+    Tensor y1 = at::empty({Ma, 32, H1, H1}, op), y2 = at::empty({Ma, 32, H2, H2}, op), y3 = at::empty({Ma, 64, H3, H3}, op), y4 = at::empty({Ma, 64, H4, H4}, op);
+    Tensor h1 = at::empty({Ma, 256}, op), h2 = at::empty({Ma, 256}, op), h3 = at::empty({Ma, 256}, op);
+    auto A = [&](Tensor& t) { return want_act ? P(t) : nullptr; };
+    x.ok(efe_enc_grad_g(x.c, P(o), P(gm), P(gv), M, &nz, P(mean), P(lv), P(grad), A(y1), A(y2), A(y3), A(y4), A(h1), A(h2), A(h3), x.stream()));
+    return {mean, lv, grad, y1, y2, y3, y4, h1, h2, h3};
+}
+
+// -> (F_down [M], nlogpo1 [M], kl_s [M], kl_naive [M], po1 [M,C,R,R], qs1, qs1_mean, qs1_logvar [M,10], g_mean, g_logvar [M,10], grad [qs_net then po_net])
+std::vector<Tensor> down_grad_g(int64_t h, const Tensor& o1_, const Tensor& pm_, const Tensor& pv_, double gamma, double beta_s, double beta_o, int64_t omega_mode,
+                                const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample, int64_t row_offset,
+                                const OptT& eps) {
+    Ctx x(h);
+    const int64_t NP = x.param_count("down_g");
+    DownIn in = down_in(x, o1_, pm_, pv_, gamma, beta_s, beta_o, omega_mode, omega, omega_scalar, seed, stage, pass, sample, row_offset, eps);
+    auto op = in.o1.options();
+    const int64_t M = in.M;
+    Tensor F = at::empty({M}, op), nl = at::empty({M}, op), kls = at::empty({M}, op), kln = at::empty({M}, op), po1 = at::empty({M, x.C, x.R, x.R}, op);
+    Tensor qs1 = at::empty({M, 10}, op), qm = at::empty({M, 10}, op), qv = at::empty({M, 10}, op), gm = at::empty({M, 10}, op), gv = at::empty({M, 10}, op);
+    Tensor grad = at::empty({NP}, op);
+    efe_fe_out out{};
+    out.F_down = P(F); out.nlogpo1 = P(nl); out.kl_s = P(kls); out.kl_naive = P(kln); out.po1 = P(po1); out.qs1 = P(qs1);
+    out.qs1_mean = P(qm); out.qs1_logvar = P(qv);
+    x.ok(efe_down_grad_g(x.c, P(in.o1), P(in.pm), P(in.pv), in.M, &in.p, &in.nz, in.eps, &out, P(gm), P(gv), P(grad), x.stream()));
+    return {F, nl, kls, kln, po1, qs1, qm, qv, gm, gv, grad};
+}
+
 // train_model_down, torchloss.py:90-98 (csrc/train_down.hip behind the gradient) -> (F_down, nlogpo1, kl_s, kl_naive [M]) of the weights before the step
 std::vector<Tensor> train_down(int64_t h, const Tensor& o1_, const Tensor& pm_, const Tensor& pv_, double gamma, double beta_s, double beta_o, int64_t omega_mode,
                                const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample, int64_t row_offset,
@@ -789,9 +830,13 @@ TORCH_LIBRARY_IMPL(efe, CUDA, m) {       // the CUDA dispatch key is the HIP dev
 TORCH_LIBRARY(efe_g, m) {
     m.def("dec_tail_grad(int ctx, Tensor h4, Tensor o1, float scale, float beta_o, bool want_y) -> (Tensor nlogpo1, Tensor po1, Tensor d_h4, Tensor grad, Tensor y1, Tensor y2, Tensor y3)");
     m.def("dec_grad(int ctx, Tensor s, Tensor o1, float scale, float beta_o, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
+    m.def("enc_grad(int ctx, Tensor o, Tensor d_mean, Tensor d_logvar, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
+    m.def("down_grad(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(efe_g, CUDA, m) {
     m.impl("dec_tail_grad", &dec_tail_grad_g);
     m.impl("dec_grad", &dec_grad_g);
+    m.impl("enc_grad", &enc_grad_g);
+    m.impl("down_grad", &down_grad_g);
 }

@@ -361,6 +361,47 @@ def grad_down(model_down, o1, ps1_mean, ps1_logvar, omega, *, stage=None, pass_=
     return res + ((gm, gv),) if return_upstream else res
 
 
+def grad_encoder_g(model_down, o, d_mean, d_logvar, *, stage=None, pass_=PASS_FE_DOWN, sample=0, row_offset=None, return_activations=False):
+    """grad_encoder at every admitted geometry (csrc/train_enc_g.hip, efe_enc_grad_g): the sizes come from the model.  With C colour
+    channels, resolution R, H_l = (H_{l-1} - 3) // 2 + 1 from H_0 = R and K = 64 H4^2: o [M,C,R,R], d_mean, d_logvar [M,10] -> (qs_mean [M,10],
+    qs_logvar [M,10], {state_dict key: gradient}) and, with return_activations, (y1 [M,32,H1,H1], y2 [M,32,H2,H2], y3 [M,64,H3,H3],
+    y4 [M,64,H4,H4], h1, h2, h3 [M,256]).  The three dropout masks are those `model_down.encoder(o, stage=, pass_=, sample=, row_offset=)`
+    draws at that geometry.  The gradients are views of one flat tensor over ENC_KEYS in parameters() order (qs_net.9.weight is [256, K]).
+    1 x 64 x 64 models run the same run-time-geometry kernels (grad_encoder is then a cross-check)."""
+    m = model_down._owner
+    e = m._ready()
+    C_, R = int(m.colour_channels), int(m.resolution)
+    o = e.tensor(o, (-1, C_, R, R))
+    M = o.shape[0]
+    nz = m._noise(stage, pass_, sample, row_offset)
+    out = torch.ops.efe_g.enc_grad(e.h, o, e.tensor(d_mean, (M, m.s_dim)), e.tensor(d_logvar, (M, m.s_dim)), m._seed64(), nz.stage, pass_, sample,
+                                   nz.row_offset, bool(return_activations))
+    res = (out[0], out[1], _views(out[2], model_down._sd_host, ENC_KEYS))
+    return res + (tuple(out[3:]),) if return_activations else res
+
+
+def grad_down_g(model_down, o1, ps1_mean, ps1_logvar, omega, *, stage=None, pass_=PASS_FE_DOWN, sample=0, eps=None, row_offset=None,
+                return_upstream=False):
+    """grad_down at every admitted geometry (csrc/train_enc_g.hip around csrc/train_dec_head_g.hip + csrc/train_dec_g.hip, efe_down_grad_g):
+    o1 [M,C,R,R] of the model's geometry -> (F_down [M], (nlogpo1, kl_div_s, kl_div_s_naive) [M] each, po1 [M,C,R,R], qs1, qs1_mean,
+    qs1_logvar [M,10], {state_dict key: d mean(F_down) / d tensor}) and, with return_upstream, (g_mean, g_logvar) [M,10].  The gradients are
+    views of one flat tensor over all 32 keys of model_down in parameters() order (qs_net, then po_net): the po_net half, po1 and nlogpo1
+    are grad_decoder_g(qs1, o1)'s, the qs_net half grad_encoder_g's on the returned upstream pair, bit for bit.  Keys, constants and
+    hyper-parameters as grad_down.  1 x 64 x 64 models run the same run-time-geometry kernels (grad_down is then a cross-check)."""
+    m = model_down._owner
+    e = m._ready()
+    C_, R = int(m.colour_channels), int(m.resolution)
+    o1 = e.tensor(o1, (-1, C_, R, R))
+    M = o1.shape[0]
+    mode, om, sc = _omega(e, omega, M)
+    nz = m._noise(stage, pass_, sample, row_offset)
+    F, nl, kls, kln, po1, qs1, qm, qv, gm, gv, flat = torch.ops.efe_g.down_grad(
+        e.h, o1, e.tensor(ps1_mean, (M, m.s_dim)), e.tensor(ps1_logvar, (M, m.s_dim)), _f32(m.gamma), _f32(m.beta_s), _f32(m.beta_o),
+        mode, om, sc, m._seed64(), nz.stage, pass_, sample, nz.row_offset, _eps(m, e, eps, M, pass_, sample, nz.stage, row_offset))
+    res = (F, (nl, kls, kln), po1, qs1, qm, qv, _views(flat, model_down._sd_host, ENC_KEYS + DEC_HEAD_KEYS + DEC_CONVT_KEYS))
+    return res + ((gm, gv),) if return_upstream else res
+
+
 def train_model_down(model_down, o1, ps1_mean, ps1_logvar, omega, optimizer, *, stage=None, pass_=PASS_FE_DOWN, sample=0, eps=None,
                      row_offset=None):
     """torchloss.py:90-98: one optimiser step of the encoder and decoder on F_down.mean() -> (F_down [M], (nlogpo1, kl_div_s, kl_div_s_naive)

@@ -590,6 +590,27 @@ int efe_enc_grad(efe_ctx*, const float* o, const float* g_mean, const float* g_l
 int efe_down_grad(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
                   const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream);
 
+/* ---- the same gradient of F_down at every admitted geometry (csrc/train_enc_g.hip with the two run-time decoder files; additive to ABI 6) ----
+ * efe_enc_grad's and efe_down_grad's arguments and meaning with the sizes taken from the context: C = 1..3 channels, resolution R,
+ * conv extents H_l = (H_{l-1} - 3) / 2 + 1 from H_0 = R (84 -> 41, 20, 9, 4), K = 64 H4^2 inputs of qs_net.9 (64 .. 3 136):
+ *   o, o1, po1 [M,C,R,R] (the caller's NCHW image, read directly)   y1 [M,32,H1,H1]  y2 [M,32,H2,H2]  y3 [M,64,H3,H3]  y4 [M,64,H4,H4]
+ *   efe_param_count("qs_net_g") = 201 684 + 288 C + 256 K (9.weight is [256][K]); efe_param_count("down_g") = that + efe_param_count("po_net"),
+ *   qs_net first.  ("qs_net" and "down" keep counting the 1 x 64 x 64 geometry only.)  efe_adam_step and efe_get_weights refuse both names.
+ * They run kernels whose sizes are run-time values at EVERY geometry, 1 x 64 x 64 included (there efe_enc_grad / efe_down_grad are a
+ * cross-check: both hold the fp64 rule; their bits are not promised equal).  The masks are the forward encoder's and decoder's at that
+ * geometry.  A layer whose input extent is even never reads the last row and column of its input: the gradient there is an exact zero.
+ * efe_down_grad_g queues per row group the encoder's forward, the sample, efe_dec_grad_g's group at scale beta_o / M, F_down's terms, the
+ * gradient at the latent and the encoder's backward: the po_net gradient, po1 and nlogpo1 are bit-identical to efe_dec_grad_g(qs1, o1,
+ * scale < 0), the qs_net gradient to efe_enc_grad_g on the returned upstream pair.  Fixed-order sums that depend on the geometry and M
+ * alone: twice the same bits; per-row outputs depend on that row and its global row id only.  Rows are processed
+ * in groups of 64 (resolution <= 64) or 32; scratch comes from the context's arena.  Both return 1 with a message that names the function,
+ * before the first launch, for M <= 0, a NULL required pointer, a split-operand option (mfma_bf16x3 / mfma_f16x2) being on, or
+ * EFE_OMEGA_DERIVED.  There is no optimiser step at these geometries yet. */
+int efe_enc_grad_g(efe_ctx*, const float* o, const float* g_mean, const float* g_logvar, int M, const efe_noise* nz, float* mean, float* logvar,
+                   float* grad, float* y1, float* y2, float* y3, float* y4, float* h1, float* h2, float* h3, void* stream);
+int efe_down_grad_g(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                    const efe_noise* nz, const float* eps, efe_fe_out* out, float* g_mean, float* g_logvar, float* grad, void* stream);
+
 /* ---- the optimiser step of ModelDown: train_model_down (csrc/train_down.hip; additive to ABI 6) -------------------------------------------
  * torch.optim.Adam's default update over the flat [4 787 125] parameter vector of ModelDown (the order of efe_down_grad's gradient), at the
  * 1 x 64 x 64 geometry.  The engine owns a master copy of these parameters that survives efe_commit_weights; the step writes it and then
