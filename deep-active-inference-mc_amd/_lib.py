@@ -188,6 +188,9 @@ SIGNATURES = {
     'efe_train_down': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p, _p, _ap, _p)),
     'efe_down_adam_step': (_i, (_p, _p, _p, _p, _ap, _p)),
     'efe_down_get_weights': (_i, (_p, _p, _l, _p)),
+    'efe_train_down_g': (_i, (_p, _p, _p, _p, _i, _fp, _nz, _p, _fo, _p, _p, _ap, _p)),
+    'efe_down_adam_step_g': (_i, (_p, _p, _p, _p, _ap, _p)),
+    'efe_down_get_weights_g': (_i, (_p, _p, _l, _p)),
     'efe_train_step': (_i, (_p, C.POINTER(EfeStepIn), _i, _fp, _nz, _sa, _sa, _sa, C.POINTER(EfeStepOut), _p)),
     'efe_eval_stats': (_i, (_p, C.POINTER(EfeEvalIn), _i, _p, _p)),
     'efe_eval_mi': (_i, (_p, C.POINTER(EfeEvalMiIn), _i, _p, _p, _p)),

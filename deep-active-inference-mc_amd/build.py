@@ -10,7 +10,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ['csrc/kernels.hip', 'csrc/decoder.hip', 'csrc/encoder.hip', 'csrc/mcts.hip', 'csrc/agent.hip', 'csrc/agent_mcts.hip', 'csrc/agent_trace.hip', 'csrc/fused.hip', 'csrc/generic.hip', 'csrc/generic_dec.hip', 'csrc/generic_enc.hip', 'csrc/bf16x3.hip', 'csrc/loss.hip', 'csrc/eval.hip', 'csrc/eval_mi.hip', 'csrc/train.hip', 'csrc/train_dec.hip', 'csrc/train_dec_g.hip', 'csrc/train_dec_head.hip', 'csrc/train_dec_head_g.hip', 'csrc/train_enc.hip', 'csrc/train_enc_g.hip', 'csrc/train_down.hip',
+SOURCES = ['csrc/kernels.hip', 'csrc/decoder.hip', 'csrc/encoder.hip', 'csrc/mcts.hip', 'csrc/agent.hip', 'csrc/agent_mcts.hip', 'csrc/agent_trace.hip', 'csrc/fused.hip', 'csrc/generic.hip', 'csrc/generic_dec.hip', 'csrc/generic_enc.hip', 'csrc/bf16x3.hip', 'csrc/loss.hip', 'csrc/eval.hip', 'csrc/eval_mi.hip', 'csrc/train.hip', 'csrc/train_dec.hip', 'csrc/train_dec_g.hip', 'csrc/train_dec_head.hip', 'csrc/train_dec_head_g.hip', 'csrc/train_enc.hip', 'csrc/train_enc_g.hip', 'csrc/train_down.hip', 'csrc/train_down_g.hip',
            'csrc/engine_ctx.hip', 'csrc/engine_weights.hip', 'csrc/engine_forward.hip', 'csrc/engine_efe.hip', 'csrc/engine_control.hip', 'csrc/engine_loss.hip', 'csrc/engine_train.hip']
 HEADERS = ['csrc/kernels.h', 'csrc/philox.h', 'csrc/mfma_pipe.h', 'csrc/train_mlp.h', 'csrc/block_sum.h', 'csrc/train_conv.h', 'csrc/ctx_registry.h', 'csrc/engine.h', '../include/efe_engine.h']
 LIB = os.path.join(HERE, 'libefe_mi355x.so')

@@ -97,13 +97,13 @@ struct efe_ctx {
     float dec_bf = 0.f;
     float* dec_raw = nullptr;      // the whole po_net unpacked, flat in parameters() order (kernels.h DH_*, then DT_*): train_dec_head.hip reads it
     float* dect_raw = nullptr;     // its tail po_net.13 / .15 / .17 / .19 (= dec_raw + DEC_HEAD_P): train_dec.hip reads it
-    float* dect_raw_g = nullptr;   // the same tail at ANY geometry, [92 320 + 289 chan] (DecTailGeo): train_dec_g.hip reads it.  = dect_raw at 1 x 64 x 64
-                                   // (so that it follows ModelDown's optimiser steps), else a buffer of the current commit
+    float* dect_raw_g = nullptr;   // the same tail at ANY geometry, [92 320 + 289 chan] (DecTailGeo): train_dec_g.hip reads it.  = dect_raw at 1 x 64 x 64,
+                                   // else the tail of down_master_g (either way it follows ModelDown's optimiser steps)
     float* dec_raw_g = nullptr;    // the whole po_net at ANY geometry, [134 400 + 257 * 64 base^2] (DecHeadGeo) then the tail: train_dec_head_g.hip
-                                   // reads it.  dect_raw_g = dec_raw_g + the head's size; = dec_raw at 1 x 64 x 64, else a buffer of the current commit
+                                   // reads it.  dect_raw_g = dec_raw_g + the head's size; = dec_raw at 1 x 64 x 64, else down_master_g + EncGeo::P()
     float* enc_raw = nullptr;      // the whole qs_net unpacked, flat in parameters() order (kernels.h EQ_*): train_enc.hip reads it
-    float* enc_raw_g = nullptr;    // the same at ANY geometry, [201 684 + 288 chan + 256 K] (EncGeo): train_enc_g.hip reads it.  = enc_raw at 1 x 64 x 64
-                                   // (so that it follows ModelDown's optimiser steps), else a buffer of the current commit; enc_raw stays null there
+    float* enc_raw_g = nullptr;    // the same at ANY geometry, [201 684 + 288 chan + 256 K] (EncGeo): train_enc_g.hip reads it.  = enc_raw at 1 x 64 x 64,
+                                   // else down_master_g (either way it follows ModelDown's optimiser steps); enc_raw stays null there
     // ModelDown's master copy at 1 x 64 x 64 (owned: it outlives a re-commit, as TrainPart::master): [DOWN_P], qs_net then po_net, so
     // enc_raw = down_master and dec_raw = down_master + ENC_P.  An optimiser step (train_down.hip) writes it and rebuilds every packed form
     // of the table down_repack (device; one entry per packed buffer of pack_heads / pack_encoder / pack_decoder, built at commit).
@@ -111,6 +111,13 @@ struct efe_ctx {
     float* down_master = nullptr;
     RepackDesc* down_repack = nullptr; int down_repack_n = 0, down_repack_blocks = 0;
     bool down_dirty = false, dec_bf_stale = false;
+    // The same on a generic context (every other geometry): [down_g_count()], qs_net (EncGeo) then po_net (DecHeadGeo, then the tail), owned,
+    // allocated at the first commit and refilled by a re-commit; enc_raw_g / dec_raw_g / dect_raw_g are spans of it.  An optimiser step
+    // (efe_train_down_g / efe_down_adam_step_g) writes it and rebuilds every packed form of the table down_repack_g (train_down_g.hip;
+    // built at every commit from that commit's buffers).  g_bf_stale: the master copy is newer than the host floats g_bf.
+    float* down_master_g = nullptr;
+    RepackDesc* down_repack_g = nullptr; int down_repack_g_n = 0, down_repack_g_blocks = 0;
+    bool g_bf_stale = false;
     float* zeros = nullptr;
     std::vector<void*> owned;      // lives as long as the context
     std::vector<void*> wbufs;      // packed weights of the current commit (freed by the next one)
@@ -318,6 +325,7 @@ LayerSpec top_layer(int i, int A);
 LayerSpec mid_layer(int i, int A);
 int part_param_count(int nl, LayerSpec (*layer)(int, int), int A);
 int refresh_down_host(efe_ctx* ctx);
+int64_t down_g_count(const efe_ctx* ctx);       // floats of ModelDown at the context's geometry: efe_param_count("down_g")
 int pack_fc4_b3(efe_ctx* ctx, int mode);
 
 // ---- engine_forward.hip ------------------------------------------------------------------------------

@@ -162,6 +162,19 @@ size_t decoder_bytes(const efe_ctx* ctx, int64_t N) { return ctx->generic ? plan
 int run_decoder_g(efe_ctx* ctx, const float* dec_in, int N, const NoiseCfg& nc, int reward0, int store0, float* val, float* po_store,
                   hipStream_t st) {
     const int B = ctx->base, H2 = 2 * B, H3 = ctx->last_s1 ? 2 * B : 4 * B;
+    // po_net.19.bias goes to k_dec_bg / k_final_g by value: after a device-side optimiser step (efe_train_down_g / efe_down_adam_step_g) the
+    // host floats are stale, and the first decoder pass behind the step fetches them from the master copy's tail on its own stream, once
+    // (run_decoder's rule for dec_bf)
+    if (ctx->g_bf_stale) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return ctx->fail("decoder: the first pass after an optimiser step of ModelDown synchronises its stream once and cannot be captured");
+        const int64_t P = down_g_count(ctx);
+        if (!ctx->down_master_g || hipMemcpyAsync(ctx->g_bf, ctx->down_master_g + P - ctx->chan, (size_t)ctx->chan * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return ctx->fail("decoder: fetching po_net.19.bias after an optimiser step failed");
+        ctx->g_bf_stale = false;
+    }
     const DecGPlan p = dec_g_plan(ctx, N);
     const int C = p.C;
     float* hA = ctx->allocT<float>(p.hA);

@@ -533,6 +533,51 @@ int train_down_run(efe_ctx* ctx, const char* who, const float* o1, const float* 
     return 0;
 }
 
+// ---- ModelDown's optimiser step at every admitted geometry (train_down_g.hip behind k_adam_down) ------------------------------------------
+// The step's arguments at the context's own geometry.  1 x 64 x 64: down_step_args (the one master copy and the one table of that geometry,
+// shared with efe_train_down).  Else: the generic context's master copy, exact fp32 planes only, sane hyper-parameters.
+int down_step_g_args(efe_ctx* ctx, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, DownAdamArgs& a, const char* who) {
+    if (!ctx->generic) return down_step_args(ctx, exp_avg, exp_avg_sq, hp, a, who);
+    const std::string w(who);
+    if (!exp_avg || !exp_avg_sq) return ctx->fail(w + ": exp_avg and exp_avg_sq must be non-NULL");
+    AdamArgs s{};
+    if (adam_args(ctx, nullptr, hp, s, who)) return 1;
+    if (ctx->mfma_bf16x3) return ctx->fail(w + ": not available with the split-operand options (mfma_bf16x3 / mfma_f16x2) on");
+    if (!ctx->down_master_g || !ctx->down_repack_g_n) return ctx->fail(w + ": the weights are not committed");
+    a.m = exp_avg; a.v = exp_avg_sq; a.w = ctx->down_master_g; a.P = (int)down_g_count(ctx);
+    a.omb1 = s.omb1; a.b2 = s.b2; a.omb2 = s.omb2; a.bc2_sqrt = s.bc2_sqrt; a.step_size = s.step_size; a.eps = s.eps;
+    return 0;
+}
+// the update, then every packed forward form of the context from the new master copy (down_step at 1 x 64 x 64); the host tensors and the
+// host's copy of po_net.19.bias are stale from here
+void down_step_g(efe_ctx* ctx, const DownAdamArgs& a, hipStream_t st) {
+    if (!ctx->generic) { down_step(ctx, a, st); return; }
+    ctx->down_dirty = true; ctx->g_bf_stale = true;
+    launch_adam_down(a, st);
+    launch_repack_down_g(ctx->down_repack_g, ctx->down_repack_g_n, ctx->down_repack_g_blocks, ctx->down_master_g, st);
+}
+// efe_train_down_g inside its call scope.  Every refusal comes before the first launch: M and the pointers first, then the step's own.
+int train_down_g_run(efe_ctx* ctx, const char* who, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                     const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, hipStream_t st) {
+    const std::string w(who);
+    if (M <= 0) return ctx->fail(w + ": M must be >= 1");
+    if (!o1 || !ps1_mean || !ps1_logvar || !params || !nz || !out || !exp_avg || !exp_avg_sq)
+        return ctx->fail(w + ": o1, ps1_mean, ps1_logvar, params, nz, out, exp_avg and exp_avg_sq must be non-NULL");
+    DownAdamArgs a{};
+    if (down_step_g_args(ctx, exp_avg, exp_avg_sq, hp, a, who)) return 1;
+    float* grad = ctx->allocT<float>((size_t)a.P);
+    if (!grad) return 1;
+    if (down_grad_g_run(ctx, who, o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, nullptr, nullptr, grad, st)) return 1;
+    a.g = grad;
+    down_step_g(ctx, a, st);
+    return 0;
+}
+// the scope of a _g step's entry point did not open: an uncommitted context is refused under the entry point's name, like a stale handle
+int step_g_refused(const Call& call, const char* who) {
+    if (call.ctx && !call.ctx->committed) return call.ctx->fail(std::string(who) + ": weights not committed");
+    return call.refused(who);
+}
+
 }  // namespace
 
 extern "C" {
@@ -550,11 +595,10 @@ int64_t efe_param_count(efe_ctx* ctx, const char* part) {
         if (ctx->chan != 1 || ctx->res != 64) { ctx->fail("efe_param_count: \"qs_net\" and \"down\" are counted for the 1 x 64 x 64 geometry only"); return 0; }
         return !strcmp(part, "qs_net") ? ENC_P : DOWN_P;
     }
-    // the same two at the context's own geometry (efe_enc_grad_g, efe_down_grad_g), likewise without an optimiser step
-    if (part && (!strcmp(part, "qs_net_g") || !strcmp(part, "down_g"))) {
-        const int64_t enc = EncGeo{ctx->chan, ctx->res}.P();
-        return !strcmp(part, "qs_net_g") ? enc : enc + DH_W3 + (int64_t)64 * ctx->base * ctx->base * 257 + DT_B3 + 32 + 32 * ctx->chan * 9 + ctx->chan;
-    }
+    // the same two at the context's own geometry (efe_enc_grad_g, efe_down_grad_g).  "down_g" is also the length of the master copy and of the
+    // optimiser state of efe_train_down_g / efe_down_adam_step_g / efe_down_get_weights_g
+    if (part && (!strcmp(part, "qs_net_g") || !strcmp(part, "down_g")))
+        return !strcmp(part, "qs_net_g") ? (int64_t)EncGeo{ctx->chan, ctx->res}.P() : down_g_count(ctx);
     if (!train_part(ctx, part, "efe_param_count")) return 0;
     return !strcmp(part, "top") ? part_param_count(TOP_NL, top_layer, ctx->pi_dim) : part_param_count(MID_NL, mid_layer, ctx->pi_dim);
 }
@@ -773,6 +817,32 @@ int efe_down_adam_step(efe_ctx* ctx, const float* grad, float* exp_avg, float* e
     if (down_step_args(ctx, exp_avg, exp_avg_sq, hp, a, "efe_down_adam_step")) return 1;
     a.g = grad;
     down_step(ctx, a, st);
+    return call.finish();
+}
+
+int efe_train_down_g(efe_ctx* ctx, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                     const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return step_g_refused(call, "efe_train_down_g");
+    if (train_down_g_run(ctx, "efe_train_down_g", o1, ps1_mean, ps1_logvar, M, params, nz, eps, out, exp_avg, exp_avg_sq, hp, st)) return 1;
+    return call.finish();
+}
+
+int efe_down_adam_step_g(efe_ctx* ctx, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return step_g_refused(call, "efe_down_adam_step_g");
+    if (!grad) return ctx->fail("efe_down_adam_step_g: grad must be non-NULL");
+    DownAdamArgs a{};
+    if (down_step_g_args(ctx, exp_avg, exp_avg_sq, hp, a, "efe_down_adam_step_g")) return 1;
+    a.g = grad;
+    down_step_g(ctx, a, st);
+    return call.finish();
+}
+
+int efe_down_get_weights_g(efe_ctx* ctx, float* dst, int64_t n, void* stream) {
+    hipStream_t st = (hipStream_t)stream; Call call(ctx, Mode::scratch, st); if (!call) return step_g_refused(call, "efe_down_get_weights_g");
+    const float* master = ctx->generic ? ctx->down_master_g : ctx->down_master;
+    if (!master) return ctx->fail("efe_down_get_weights_g: the weights are not committed");
+    if (!dst || n != down_g_count(ctx)) return ctx->fail("efe_down_get_weights_g: dst must hold efe_param_count(\"down_g\") floats");
+    HIPCHK(hipMemcpyAsync(dst, master, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return call.finish();
 }
 

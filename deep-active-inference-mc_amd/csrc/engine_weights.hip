@@ -27,6 +27,18 @@ float* upload_master(efe_ctx* ctx, const std::vector<float>& v, size_t off) {
     return ctx->down_master + off;
 }
 
+// ... of the master copy of a generic context (owned, allocated at the first commit: the geometry, and with it the length, is the context's)
+float* upload_master_g(efe_ctx* ctx, const std::vector<float>& v, size_t off) {
+    const size_t P = (size_t)down_g_count(ctx);
+    if (off + v.size() > P) { ctx->err = "master copy: a span past the parameter count"; return nullptr; }
+    if (!ctx->down_master_g) {
+        if (hipMalloc((void**)&ctx->down_master_g, P * 4) != hipSuccess) { ctx->err = "master copy: hipMalloc failed"; return nullptr; }
+        ctx->owned.push_back(ctx->down_master_g);
+    }
+    if (hipMemcpy(ctx->down_master_g + off, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "master copy: hipMemcpy failed"; return nullptr; }
+    return ctx->down_master_g + off;
+}
+
 const HostTensor* need(efe_ctx* ctx, const std::string& key, std::initializer_list<int64_t> shape) {
     auto it = ctx->raw.find(key);
     if (it == ctx->raw.end()) { ctx->err = "missing weight " + key; return nullptr; }
@@ -239,59 +251,105 @@ const char* const DOWN_KEYS[16] = {"down.qs_net.0", "down.qs_net.2", "down.qs_ne
                                    "down.qs_net.18", "down.po_net.0", "down.po_net.3", "down.po_net.6", "down.po_net.9", "down.po_net.13", "down.po_net.15",
                                    "down.po_net.17", "down.po_net.19"};
 
-// the table k_repack_down works from (train_down.hip): one entry per packed buffer and bias table that pack_heads, pack_encoder and
-// pack_decoder fill on the 1 x 64 x 64 path, with the buffers of THIS commit; its kinds name the packers they invert
-int build_down_repack(efe_ctx* ctx) {
+// The table a repack kernel works from: one entry per packed buffer and bias table, with the buffers of THIS commit; the kinds name the
+// packers they invert.  blocks: the first workgroup of the next entry (256 owning threads each).
+struct RepackTable {
     std::vector<RepackDesc> t;
-    int blocks = 0;
-    auto add = [&](float* dst, int src, int kind, int n, int out, int in, int KC, int mtiles, int row_ch = 0, int row_pos = 0, int col_ch = 0, int col_pos = 0) {
+    int64_t blocks = 0;
+    void add(float* dst, int64_t src, int kind, int64_t n, int out, int in, int KC, int mtiles, int row_ch = 0, int row_pos = 0, int col_ch = 0, int col_pos = 0) {
         RepackDesc d{};
-        d.dst = dst; d.src = src; d.kind = kind; d.n = n; d.block0 = blocks; d.out = out; d.in = in; d.KC = KC; d.mtiles = mtiles;
+        d.dst = dst; d.src = (int)src; d.kind = kind; d.n = (int)n; d.block0 = (int)blocks; d.out = out; d.in = in; d.KC = KC; d.mtiles = mtiles;
         d.row_ch = row_ch; d.row_pos = row_pos; d.col_ch = col_ch; d.col_pos = col_pos;
         d.vec = (kind == RP_DENSE32 || kind == RP_DENSE16) && !col_ch && src % 4 == 0 && in % (kind == RP_DENSE32 ? 8 : 16) == 0;
         d.swizzle = kind == RP_DENSE32 && d.vec && KC % 4 == 0;
+        if (src > INT32_MAX || n > INT32_MAX) fits = false;
         blocks += (n + 255) / 256;
         t.push_back(d);
-    };
-    auto bias = [&](float* dst, int src, int out, int n, int row_ch = 0, int row_pos = 0) { add(dst, src, RP_BIAS, n, out, 0, 0, 0, row_ch, row_pos); };
-    auto dense32 = [&](const Layer& L, int w, int b, int out, int in, int row_ch = 0, int row_pos = 0, int col_ch = 0, int col_pos = 0) {
-        add(L.Wp, w, RP_DENSE32, L.mtiles * (L.cin / 8) * 64, out, in, L.cin / 8, L.mtiles, row_ch, row_pos, col_ch, col_pos);
+    }
+    bool fits = true;       // every offset, thread count and first block is an int of the device table
+    void bias(float* dst, int64_t src, int out, int n, int row_ch = 0, int row_pos = 0) { add(dst, src, RP_BIAS, n, out, 0, 0, 0, row_ch, row_pos); }
+    void dense32(const Layer& L, int64_t w, int64_t b, int out, int in, int row_ch = 0, int row_pos = 0, int col_ch = 0, int col_pos = 0) {
+        add(L.Wp, w, RP_DENSE32, (int64_t)L.mtiles * (L.cin / 8) * 64, out, in, L.cin / 8, L.mtiles, row_ch, row_pos, col_ch, col_pos);
         bias(L.bias, b, out, L.mtiles * 32, row_ch, row_pos);
-    };
-    auto dense16 = [&](const MlpW& net, int layer, int w, int b, int out, int in, int col_ch = 0, int col_pos = 0) {
+    }
+    void dense16(const MlpW& net, int layer, int64_t w, int64_t b, int out, int in, int col_ch = 0, int col_pos = 0) {
         const int mtiles = (out + 15) / 16, KC = (in + 15) / 16;
-        add(const_cast<float*>(reinterpret_cast<const float*>(net.w[layer])), w, RP_DENSE16, mtiles * KC * 64, out, in, KC, mtiles, 0, 0, col_ch, col_pos);
+        add(const_cast<float*>(reinterpret_cast<const float*>(net.w[layer])), w, RP_DENSE16, (int64_t)mtiles * KC * 64, out, in, KC, mtiles, 0, 0, col_ch, col_pos);
         bias(const_cast<float*>(net.b[layer]), b, out, mtiles * 16);
-    };
+    }
+    // a conv layer of nine taps in the 32x32x2 form (RP_CONV32 / RP_CONVT32) and its bias
+    void conv32(const Layer& L, int kind, int64_t w, int64_t b, int out, int in) {
+        add(L.Wp, w, kind, (int64_t)9 * L.mtiles * (L.cin / 8) * 64, out, in, L.cin / 8, L.mtiles);
+        bias(L.bias, b, out, L.mtiles * 32);
+    }
+    // checked and copied into the context's device table (owned, allocated once)
+    int commit(efe_ctx* ctx, RepackDesc*& dev, int& n, int& nblocks) const {
+        constexpr size_t CAP = 64;
+        if (t.size() > CAP) return ctx->fail("repack table: more entries than its buffer holds");
+        for (const RepackDesc& d : t) if (!d.dst) return ctx->fail("repack table: a packed buffer is missing");
+        if (!fits || blocks > INT32_MAX) return ctx->fail("repack table: an offset or a thread count does not fit the table's ints");
+        if (!dev) {
+            HIPCHK(hipMalloc((void**)&dev, CAP * sizeof(RepackDesc))); ctx->owned.push_back(dev);
+        }
+        HIPCHK(hipMemcpy(dev, t.data(), t.size() * sizeof(RepackDesc), hipMemcpyHostToDevice));
+        n = (int)t.size(); nblocks = (int)blocks;
+        return 0;
+    }
+};
+
+// the table k_repack_down works from (train_down.hip): pack_heads, pack_encoder and pack_decoder on the 1 x 64 x 64 path
+int build_down_repack(efe_ctx* ctx) {
+    RepackTable tb;
     const int D = ENC_P, T = ENC_P + DEC_HEAD_P;      // po_net and its ConvT tail inside the master copy
     // pack_heads
     const int dh[3][4] = {{DH_W0, DH_B0, 256, 10}, {DH_W1, DH_B1, 256, 256}, {DH_W2, DH_B2, 256, 256}};
     const int eh[3][4] = {{EQ_W12, EQ_B12, 256, 256}, {EQ_W15, EQ_B15, 256, 256}, {EQ_W18, EQ_B18, 20, 256}};
     for (int i = 0; i < 3; ++i) {
-        dense32(ctx->dec_fc[i], D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]); dense16(ctx->dec16, i, D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]);
-        dense32(ctx->enc_fc[i + 1], eh[i][0], eh[i][1], eh[i][2], eh[i][3]); dense16(ctx->enc16, i + 1, eh[i][0], eh[i][1], eh[i][2], eh[i][3]);
+        tb.dense32(ctx->dec_fc[i], D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]); tb.dense16(ctx->dec16, i, D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]);
+        tb.dense32(ctx->enc_fc[i + 1], eh[i][0], eh[i][1], eh[i][2], eh[i][3]); tb.dense16(ctx->enc16, i + 1, eh[i][0], eh[i][1], eh[i][2], eh[i][3]);
     }
     // pack_encoder: conv1 on the VALU, conv2 / conv3 as nine taps of the 32x32x2 form, conv4 in the 16x16x4 form, the head's first layer (columns NHWC)
-    add(ctx->enc_w1, EQ_W1, RP_TAP32, 288, 32, 1, 0, 0); bias(ctx->enc_b1, EQ_B1, 32, 32);
-    add(ctx->enc_conv[0].Wp, EQ_W2, RP_CONV32, 9 * 1 * 4 * 64, 32, 32, 4, 1); bias(ctx->enc_conv[0].bias, EQ_B2, 32, 32);
-    add(ctx->enc_conv[1].Wp, EQ_W3, RP_CONV32, 9 * 2 * 4 * 64, 64, 32, 4, 2); bias(ctx->enc_conv[1].bias, EQ_B3, 64, 64);
-    add(ctx->enc_conv[2].Wp, EQ_W4, RP_CONV16, 9 * 4 * 4 * 64, 64, 64, 4, 4); bias(ctx->enc_conv[2].bias, EQ_B4, 64, 64);
-    dense32(ctx->enc_fc[0], EQ_W9, EQ_B9, 256, 576, 0, 0, 64, 9); dense16(ctx->enc16, 0, EQ_W9, EQ_B9, 256, 576, 64, 9);
+    tb.add(ctx->enc_w1, EQ_W1, RP_TAP32, 288, 32, 1, 0, 0); tb.bias(ctx->enc_b1, EQ_B1, 32, 32);
+    tb.add(ctx->enc_conv[0].Wp, EQ_W2, RP_CONV32, 9 * 1 * 4 * 64, 32, 32, 4, 1); tb.bias(ctx->enc_conv[0].bias, EQ_B2, 32, 32);
+    tb.add(ctx->enc_conv[1].Wp, EQ_W3, RP_CONV32, 9 * 2 * 4 * 64, 64, 32, 4, 2); tb.bias(ctx->enc_conv[1].bias, EQ_B3, 64, 64);
+    tb.add(ctx->enc_conv[2].Wp, EQ_W4, RP_CONV16, 9 * 4 * 4 * 64, 64, 64, 4, 4); tb.bias(ctx->enc_conv[2].bias, EQ_B4, 64, 64);
+    tb.dense32(ctx->enc_fc[0], EQ_W9, EQ_B9, 256, 576, 0, 0, 64, 9); tb.dense16(ctx->enc16, 0, EQ_W9, EQ_B9, 256, 576, 64, 9);
     // pack_decoder: Linear(256, 16384) with its rows NHWC, the Winograd and F(2, 2) matrices, the final convolution (its bias: ctx->dec_bf)
-    dense32(ctx->dec_fc[3], D + DH_W3, D + DH_B3, 16384, 256, 64, 256);
-    add(ctx->dec_ct[0].Wp, T + DT_W1, RP_WINO, 16 * 2 * 8 * 64, 64, 64, 8, 2); bias(ctx->dec_ct[0].bias, T + DT_B1, 64, 64);
-    add(ctx->dec_ct[1].Wp, T + DT_W2, RP_F22, 16 * 4 * 4 * 64, 64, 64, 4, 4); bias(ctx->dec_ct[1].bias, T + DT_B2, 64, 64);
-    add(ctx->dec_ct[2].Wp, T + DT_W3, RP_F22, 16 * 2 * 4 * 64, 32, 64, 4, 2); bias(ctx->dec_ct[2].bias, T + DT_B3, 32, 32);
-    add(ctx->dec_wf, T + DT_W4, RP_TAP32, 288, 32, 1, 0, 0);
-    constexpr size_t CAP = 64;
-    if (t.size() > CAP) return ctx->fail("repack table: more entries than its buffer holds");
-    for (const RepackDesc& d : t) if (!d.dst) return ctx->fail("repack table: a packed buffer is missing");
-    if (!ctx->down_repack) {
-        HIPCHK(hipMalloc((void**)&ctx->down_repack, CAP * sizeof(RepackDesc))); ctx->owned.push_back(ctx->down_repack);
+    tb.dense32(ctx->dec_fc[3], D + DH_W3, D + DH_B3, 16384, 256, 64, 256);
+    tb.add(ctx->dec_ct[0].Wp, T + DT_W1, RP_WINO, 16 * 2 * 8 * 64, 64, 64, 8, 2); tb.bias(ctx->dec_ct[0].bias, T + DT_B1, 64, 64);
+    tb.add(ctx->dec_ct[1].Wp, T + DT_W2, RP_F22, 16 * 4 * 4 * 64, 64, 64, 4, 4); tb.bias(ctx->dec_ct[1].bias, T + DT_B2, 64, 64);
+    tb.add(ctx->dec_ct[2].Wp, T + DT_W3, RP_F22, 16 * 2 * 4 * 64, 32, 64, 4, 2); tb.bias(ctx->dec_ct[2].bias, T + DT_B3, 32, 32);
+    tb.add(ctx->dec_wf, T + DT_W4, RP_TAP32, 288, 32, 1, 0, 0);
+    return tb.commit(ctx, ctx->down_repack, ctx->down_repack_n, ctx->down_repack_blocks);
+}
+
+// the table k_repack_down_g works from (train_down_g.hip): the same three packers under ctx->generic, offsets from the context's geometry.
+// Largest geometry (3 x 128 x 128): 18.0 M floats of master copy, 4.2 M owning threads for g_fc4, 17 K workgroups: RepackTable::commit
+// checks that each fits an int.
+int build_down_repack_g(efe_ctx* ctx) {
+    RepackTable tb;
+    const int C = ctx->chan, B = ctx->base, F4 = ctx->enc_hw[4] * ctx->enc_hw[4];
+    const EncGeo eg{C, ctx->res};
+    const DecHeadGeo hg{B};
+    const int64_t S = eg.small(), D = eg.P(), T = D + (int64_t)hg.P();      // qs_net.12 ..; po_net; its ConvT tail, inside the master copy
+    // pack_heads
+    const int dh[3][4] = {{DH_W0, DH_B0, 256, 10}, {DH_W1, DH_B1, 256, 256}, {DH_W2, DH_B2, 256, 256}};
+    const int eh[3][4] = {{EQS_W12, EQS_B12, 256, 256}, {EQS_W15, EQS_B15, 256, 256}, {EQS_W18, EQS_B18, 20, 256}};
+    for (int i = 0; i < 3; ++i) {
+        tb.dense32(ctx->dec_fc[i], D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]); tb.dense16(ctx->dec16, i, D + dh[i][0], D + dh[i][1], dh[i][2], dh[i][3]);
+        tb.dense32(ctx->enc_fc[i + 1], S + eh[i][0], S + eh[i][1], eh[i][2], eh[i][3]); tb.dense16(ctx->enc16, i + 1, S + eh[i][0], S + eh[i][1], eh[i][2], eh[i][3]);
     }
-    HIPCHK(hipMemcpy(ctx->down_repack, t.data(), t.size() * sizeof(RepackDesc), hipMemcpyHostToDevice));
-    ctx->down_repack_n = (int)t.size(); ctx->down_repack_blocks = blocks;
-    return 0;
+    // pack_encoder: four k_conv_g layers (layer 0 reads C channels, padded to 8), layer 1 again for the LDS-tiled kernels, the head's first layer (columns NHWC)
+    const int ew[4] = {eg.w1(), eg.w2(), eg.w3(), eg.w4()}, eb[4] = {eg.b1(), eg.b2(), eg.b3(), eg.b4()};
+    for (int i = 0; i < 4; ++i) { const LayerSpec s = enc_conv_layer(i, C); tb.conv32(ctx->g_enc[i], RP_CONV32, ew[i], eb[i], s.out, s.in); }
+    tb.add(ctx->g_enc1p, eg.w1(), RP_ENC1P, 9 * 64 * 2, 32, C, 0, 0);
+    tb.dense32(ctx->enc_fc[0], eg.w9(), eg.b9(), 256, eg.K(), 0, 0, 64, F4); tb.dense16(ctx->enc16, 0, eg.w9(), eg.b9(), 256, eg.K(), 64, F4);
+    // pack_decoder: Linear(256, 64 B^2) with its rows NHWC, three transposed convolutions, the final convolution (its bias: ctx->g_bf)
+    tb.dense32(ctx->g_fc4, D + DH_W3, D + (int64_t)hg.b3(), hg.F(), 256, 64, B * B);
+    const int tw[3] = {DT_W1, DT_W2, DT_W3}, tbs[3] = {DT_B1, DT_B2, DT_B3};
+    for (int i = 0; i < 3; ++i) tb.conv32(ctx->g_ct[i], RP_CONVT32, T + tw[i], T + tbs[i], DEC_CT[i].out, DEC_CT[i].in);
+    tb.add(ctx->g_wf, T + DT_W4, RP_WF4, 9 * 32 * 4, C, 32, 0, 0);
+    return tb.commit(ctx, ctx->down_repack_g, ctx->down_repack_g_n, ctx->down_repack_g_blocks);
 }
 
 // the split-operand planes of pack_fc4_b3, released
@@ -343,7 +401,10 @@ int pack_encoder(efe_ctx* ctx) {
             if (flat.size() != (size_t)ENC_P) return ctx->fail("encoder: unexpected parameter count");
             if (!(ctx->enc_raw = upload_master(ctx, flat, 0))) return 1;
             ctx->enc_raw_g = ctx->enc_raw;
-        } else if (!(ctx->enc_raw_g = upload(ctx, flat))) return 1;      // any other geometry: a buffer of this commit
+        } else {                            // any other geometry: the head of that context's master copy; po_net behind it stays 16-byte aligned
+            if (eg.P() % 4) return ctx->fail("encoder: the parameter count is no multiple of 4 floats (the decoder's span of the master copy would be misaligned)");
+            if (!(ctx->enc_raw_g = upload_master_g(ctx, flat, 0))) return 1;
+        }
     }
     if (ctx->generic) {     // build-defined geometry: four k_conv_g layers ...
         for (int i = 0; i < 4; ++i) if (pack_conv(ctx, ctx->g_enc[i], enc_conv_layer(i, C), false)) return 1;
@@ -411,7 +472,7 @@ int pack_decoder(efe_ctx* ctx) {
             if (!(ctx->dec_raw = upload_master(ctx, flat, ENC_P))) return 1;
             ctx->dec_raw_g = ctx->dec_raw;
             ctx->dect_raw = ctx->dec_raw + DEC_HEAD_P;
-        } else if (!(ctx->dec_raw_g = upload(ctx, flat))) return 1;      // any other geometry: a buffer of this commit (train_dec_head_g.hip, train_dec_g.hip)
+        } else if (!(ctx->dec_raw_g = upload_master_g(ctx, flat, (size_t)EncGeo{C, ctx->res}.P()))) return 1;      // any other geometry: behind qs_net in that context's master copy (train_dec_head_g.hip, train_dec_g.hip)
         ctx->dect_raw_g = ctx->dec_raw_g + hg.P();
     }
     {   // Unflatten(1, (64, B, B)) is channel-major c*B*B + p (torchmodel.py:119); the layer emits NHWC p*64 + c directly
@@ -426,6 +487,7 @@ int pack_decoder(efe_ctx* ctx) {
         for (int t = 0; t < 9; ++t) for (int ci = 0; ci < 32; ++ci) for (int c = 0; c < C; ++c) wf[(t * 32 + ci) * 4 + c] = tf.W()[((size_t)ci * C + c) * 9 + t];
         if (!(ctx->g_wf = upload(ctx, wf))) return 1;
         for (int c = 0; c < 4; ++c) ctx->g_bf[c] = c < C ? tf.B()[c] : 0.f;
+        ctx->g_bf_stale = false;
         return 0;
     }
     if (ctx->mfma_bf16x3 && pack_fc4_b3(ctx, (int)ctx->mfma_bf16x3)) return 1;
@@ -459,13 +521,20 @@ LayerSpec mid_layer(int i, int A) {
 }
 int part_param_count(int nl, LayerSpec (*layer)(int, int), int A) { int n = 0; for (int i = 0; i < nl; ++i) { const LayerSpec s = layer(i, A); n += s.out * s.in + s.out; } return n; }
 
-// refresh_train_host for ModelDown's master copy, over DOWN_KEYS
+int64_t down_g_count(const efe_ctx* ctx) {
+    return (int64_t)EncGeo{ctx->chan, ctx->res}.P() + (int64_t)DecHeadGeo{ctx->base}.P() + DecTailGeo{ctx->base, ctx->chan, ctx->last_s1 ? 1 : 2}.P();
+}
+
+// refresh_train_host for ModelDown's master copy, over DOWN_KEYS: down_master at 1 x 64 x 64, down_master_g on a generic context (the
+// sizes are the host tensors' own; their sum is held to the geometry's parameter count)
 int refresh_down_host(efe_ctx* ctx) {
     if (!ctx->down_dirty) return 0;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipDeviceSynchronize());
-    std::vector<float> flat((size_t)DOWN_P);
-    HIPCHK(hipMemcpy(flat.data(), ctx->down_master, flat.size() * 4, hipMemcpyDeviceToHost));
+    const float* master = ctx->generic ? ctx->down_master_g : ctx->down_master;
+    if (!master) return ctx->fail("master copy: marked newer than the host tensors, but never allocated");
+    std::vector<float> flat((size_t)(ctx->generic ? down_g_count(ctx) : DOWN_P));
+    HIPCHK(hipMemcpy(flat.data(), master, flat.size() * 4, hipMemcpyDeviceToHost));
     size_t off = 0;
     for (const char* key : DOWN_KEYS)
         for (const char* sfx : {".weight", ".bias"}) {
@@ -476,7 +545,10 @@ int refresh_down_host(efe_ctx* ctx) {
             off += d.size();
         }
     if (off != flat.size()) return ctx->fail("master copy: the host tensors do not add up to the parameter count");
-    ctx->dec_bf = flat.back(); ctx->dec_bf_stale = false;
+    if (ctx->generic) {     // po_net.19.bias, the vector's last chan floats
+        for (int c = 0; c < 4; ++c) ctx->g_bf[c] = c < ctx->chan ? flat[flat.size() - (size_t)ctx->chan + c] : 0.f;
+        ctx->g_bf_stale = false;
+    } else { ctx->dec_bf = flat.back(); ctx->dec_bf_stale = false; }
     ctx->down_dirty = false;
     return 0;
 }
@@ -545,8 +617,9 @@ int efe_commit_weights(efe_ctx* ctx) {
     // a trained part is never reverted, whichever tensor the caller replaced: the host copies follow the device master copies first
     if (refresh_train_host(ctx, ctx->top_train) || refresh_train_host(ctx, ctx->mid_train) || refresh_down_host(ctx)) return 1;
     if (pack_top(ctx) || pack_mid(ctx) || pack_heads(ctx) || pack_encoder(ctx) || pack_decoder(ctx)) return 1;
-    ctx->down_repack_n = 0;
+    ctx->down_repack_n = ctx->down_repack_g_n = 0;
     if (!ctx->generic && ctx->enc_raw && ctx->dec_raw && build_down_repack(ctx)) return 1;
+    if (ctx->generic && build_down_repack_g(ctx)) return 1;
     // the host copies stay: a caller may update a single tensor with efe_set_weight and commit again
     ctx->committed = true;
     return 0;

@@ -777,6 +777,14 @@ struct RepackDesc {
     int vec, swizzle;                    // a lane's four source floats are one aligned float4; the 128-B-segment thread order (train_down.hip)
 };
 void launch_repack_down(const RepackDesc* table, int n, int blocks, const float* w, hipStream_t st);
+// ... and of the generic path's packed forms, as k_repack_down_g rebuilds them (train_down_g.hip): RP_BIAS, RP_DENSE32, RP_DENSE16 and RP_CONV32
+// as above, and three kinds of its own (an enum of its own: RepackKind is k_repack_down's)
+enum RepackKindG {
+    RP_CONVT32 = 8, // pack_conv (ConvTranspose2d, W [in][out][3][3]): nine taps of the 32x32x2 form
+    RP_ENC1P,       // g_enc1p [9 taps][64 lanes][2] of qs_net.0.weight [32][in][3][3], zero for ci >= in; n = 1152 floats
+    RP_WF4          // g_wf [9 taps][32][4] of po_net.19.weight [32][out][3][3], zero for c >= out; n = 1152 floats
+};
+void launch_repack_down_g(const RepackDesc* table, int n, int blocks, const float* w, hipStream_t st);
 
 void launch_pack_x(const float* pi, const float* s, float* x, int R, int pi_dim, int s_dim, hipStream_t st);
 void launch_pad16(const float* s, float* x, int R, int s_dim, hipStream_t st);

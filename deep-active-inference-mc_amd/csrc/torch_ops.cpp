@@ -673,6 +673,33 @@ void down_adam_step(int64_t h, const Tensor& grad_, Tensor exp_avg, Tensor exp_a
     x.ok(efe_down_adam_step(x.c, P(grad), x.state(exp_avg, "exp_avg", NP), x.state(exp_avg_sq, "exp_avg_sq", NP), &hp, x.stream()));
 }
 
+// the same two at every admitted geometry (csrc/train_down_g.hip behind k_adam_down): the flat vectors have efe_param_count("down_g") elements
+std::vector<Tensor> train_down_g(int64_t h, const Tensor& o1_, const Tensor& pm_, const Tensor& pv_, double gamma, double beta_s, double beta_o, int64_t omega_mode,
+                                 const OptT& omega, double omega_scalar, int64_t seed, int64_t stage, int64_t pass, int64_t sample, int64_t row_offset,
+                                 const OptT& eps, Tensor exp_avg, Tensor exp_avg_sq, double lr, double beta1, double beta2, double aeps, int64_t step) {
+    Ctx x(h);
+    const int64_t NP = x.param_count("down_g");
+    DownIn in = down_in(x, o1_, pm_, pv_, gamma, beta_s, beta_o, omega_mode, omega, omega_scalar, seed, stage, pass, sample, row_offset, eps);
+    auto op = in.o1.options();
+    const int64_t M = in.M;
+    Tensor F = at::empty({M}, op), nl = at::empty({M}, op), kls = at::empty({M}, op), kln = at::empty({M}, op);
+    efe_fe_out out{};
+    out.F_down = P(F); out.nlogpo1 = P(nl); out.kl_s = P(kls); out.kl_naive = P(kln);
+    const efe_adam_params hp = adam_params(lr, beta1, beta2, aeps, step);
+    x.ok(efe_train_down_g(x.c, P(in.o1), P(in.pm), P(in.pv), in.M, &in.p, &in.nz, in.eps, &out, x.state(exp_avg, "exp_avg", NP),
+                          x.state(exp_avg_sq, "exp_avg_sq", NP), &hp, x.stream()));
+    return {F, nl, kls, kln};
+}
+
+void down_adam_step_g(int64_t h, const Tensor& grad_, Tensor exp_avg, Tensor exp_avg_sq, double lr, double beta1, double beta2, double eps, int64_t step) {
+    Ctx x(h);
+    const int64_t NP = x.param_count("down_g");
+    Tensor grad = x.f32(grad_, "grad");
+    TORCH_CHECK(grad.numel() == NP, "efe: grad has ", grad.numel(), " elements, ModelDown has ", NP, " parameters");
+    const efe_adam_params hp = adam_params(lr, beta1, beta2, eps, step);
+    x.ok(efe_down_adam_step_g(x.c, P(grad), x.state(exp_avg, "exp_avg", NP), x.state(exp_avg_sq, "exp_avg_sq", NP), &hp, x.stream()));
+}
+
 // one whole training step, train.py:111-126 (efe_train_step) -> (kl_pi, omega, qs0, F_mid, ps1_mean, ps1_logvar, F_down, nlogpo1, kl_s, kl_naive); means
 // [EFE_STEP_MEANS] and the six state vectors are written in place.  hyper = (lr, beta1, beta2, eps) of the top, mid and down optimisers
 // (12 numbers), steps = their three step numbers
@@ -832,6 +859,8 @@ TORCH_LIBRARY(efe_g, m) {
     m.def("dec_grad(int ctx, Tensor s, Tensor o1, float scale, float beta_o, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
     m.def("enc_grad(int ctx, Tensor o, Tensor d_mean, Tensor d_logvar, int seed, int stage, int pass_id, int sample, int row_offset, bool want_act) -> Tensor[]");
     m.def("down_grad(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps) -> Tensor[]");
+    m.def("train_down(int ctx, Tensor o1, Tensor ps1_mean, Tensor ps1_logvar, float gamma, float beta_s, float beta_o, int omega_mode, Tensor? omega, float omega_scalar, int seed, int stage, int pass_id, int sample, int row_offset, Tensor? eps, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float adam_eps, int step) -> Tensor[]");
+    m.def("down_adam_step(int ctx, Tensor grad, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, float eps, int step) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(efe_g, CUDA, m) {
@@ -839,4 +868,6 @@ TORCH_LIBRARY_IMPL(efe_g, CUDA, m) {
     m.impl("dec_grad", &dec_grad_g);
     m.impl("enc_grad", &enc_grad_g);
     m.impl("down_grad", &down_grad_g);
+    m.impl("train_down", &train_down_g);
+    m.impl("down_adam_step", &down_adam_step_g);
 }

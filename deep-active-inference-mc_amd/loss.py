@@ -426,6 +426,33 @@ def train_model_down(model_down, o1, ps1_mean, ps1_logvar, omega, optimizer, *, 
     return F, (nl, kls, kln)
 
 
+def train_model_down_g(model_down, o1, ps1_mean, ps1_logvar, omega, optimizer, *, stage=None, pass_=PASS_FE_DOWN, sample=0, eps=None,
+                       row_offset=None):
+    """train_model_down at every admitted geometry (efe_train_down_g): o1 [M,C,R,R] of the model's geometry -> (F_down [M], (nlogpo1,
+    kl_div_s, kl_div_s_naive) [M] each) of the weights before the step.  One engine call: grad_down_g's row groups, Adam over all 32
+    tensors, and every packed forward form of the model's path rebuilt on the device (csrc/train_down_g.hip), with no host
+    synchronisation.  optimizer: daimc_amd.Adam(model_down, any_geometry=True).  Bit-identical to grad_down_g followed by
+    optimizer.step(grads).  At 1 x 64 x 64 the step is train_model_down's on the same master copy (the gradient is grad_down_g's)."""
+    if getattr(optimizer, '_module', None) is not model_down or not getattr(optimizer, '_any_geometry', False):
+        raise ValueError('train_model_down_g: optimizer must be a daimc_amd.Adam(model_down, any_geometry=True) over this model_down')
+    m = model_down._owner
+    e = m._ready()
+    C_, R = int(m.colour_channels), int(m.resolution)
+    o1 = e.tensor(o1, (-1, C_, R, R))
+    M = o1.shape[0]
+    mode, om, sc = _omega(e, omega, M)
+    nz = m._noise(stage, pass_, sample, row_offset)
+    ea, es = optimizer._buffers()
+    hyper = optimizer._hyper()
+    F, nl, kls, kln = torch.ops.efe_g.train_down(
+        e.h, o1, e.tensor(ps1_mean, (M, m.s_dim)), e.tensor(ps1_logvar, (M, m.s_dim)), _f32(m.gamma), _f32(m.beta_s), _f32(m.beta_o),
+        mode, om, sc, m._seed64(), nz.stage, pass_, sample, nz.row_offset, _eps(m, e, eps, M, pass_, sample, nz.stage, row_offset),
+        ea, es, *hyper, optimizer._step + 1)
+    optimizer._step += 1
+    model_down._stepped()
+    return F, (nl, kls, kln)
+
+
 def _step_optimizers(model, optimizers):
     """the reference's optimizers dict -> (top, mid, down) daimc_amd.Adam, each over this model's part"""
     out = []

@@ -172,11 +172,15 @@ class _TrainableModule(_Module):
     def _get_weights(self, e, part, buf, P):
         return e.lib.efe_get_weights(e.ctx, part, _lib.ptr(buf), P, e.stream())
 
+    def _count_part(self):
+        """the name efe_param_count gives the master copy's length under"""
+        return self._train_part
+
     def _download(self):
         """efe_get_weights: the device master copy (flat, parameters() order) -> the host state_dict"""
         e = self._owner._engine
         part = self._train_part.encode()
-        P = int(e.lib.efe_param_count(e.ctx, part))
+        P = int(e.lib.efe_param_count(e.ctx, self._count_part().encode()))
         buf = e.empty(P)
         with torch.cuda.device(e.device):
             e.check(self._get_weights(e, part, buf, P))
@@ -246,12 +250,20 @@ class ModelMid(_TrainableModule):
 class ModelDown(_TrainableModule):
     """torchmodel.py:69-146 (resolution 64, 1 colour channel; the first encoder Linear takes the 576
     features the conv trunk actually emits -- SURVEY appendix C).  Encoder and decoder are trainable on the device at 1 x 64 x 64
-    (loss.train_model_down); the optimiser step has C entry points of its own (efe_down_adam_step / efe_down_get_weights: it also
-    rebuilds the packed forward forms), so the string-part calls still refuse "down"."""
+    (loss.train_model_down) and at every admitted geometry (loss.train_model_down_g); the optimiser step has C entry points of its own
+    (efe_down_adam_step / efe_down_get_weights and their _g forms: it also rebuilds the packed forward forms), so the string-part calls
+    still refuse "down"."""
     _train_part = 'down'
 
+    def _at_64(self):
+        return (int(self.colour_channels), int(self.resolution)) == (1, 64)
+
+    def _count_part(self):
+        return 'down' if self._at_64() else 'down_g'
+
     def _get_weights(self, e, part, buf, P):
-        return e.lib.efe_down_get_weights(e.ctx, _lib.ptr(buf), P, e.stream())
+        get = e.lib.efe_down_get_weights if self._at_64() else e.lib.efe_down_get_weights_g
+        return get(e.ctx, _lib.ptr(buf), P, e.stream())
 
     def __init__(self, owner):
         super().__init__(owner, 'down')

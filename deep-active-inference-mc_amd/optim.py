@@ -5,7 +5,11 @@ holds one part.  The update runs on the engine's master copy of the weights: csr
 copies of the small nets) or, for ModelDown, csrc/train_down.hip (k_adam_down, then k_repack_down rebuilds every packed forward form;
 efe_down_adam_step).  This class holds the part's name, the optimiser state (exp_avg, exp_avg_sq: flat device tensors in parameters()
 order) and the step count, and speaks torch.optim.Adam's state_dict format for the part's parameters, so state moves both ways between
-the two."""
+the two.
+
+`Adam(model.model_down, any_geometry=True)` is the optimiser over ModelDown at the model's OWN geometry (C ABI count "down_g"; every
+admitted one, 1 x 64 x 64 included): the same state layout and state_dict format, the step through efe_down_adam_step_g
+(csrc/train_down_g.hip rebuilds the generic path's packed forms; at 1 x 64 x 64 it is the step above on the same master copy)."""
 import torch
 
 from .model import _TrainableModule
@@ -17,16 +21,20 @@ def _torch_group():
 
 
 class Adam:
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, any_geometry=False):
         mod = params if isinstance(params, _TrainableModule) else getattr(params, 'module', None)
         if not isinstance(mod, _TrainableModule):
             raise TypeError('daimc_amd.Adam takes model.model_top, model.model_mid, model.model_down or the parameters() of one of them '
                             '(the trainable parts)')
         own = mod._owner
-        if mod._train_part == 'down' and (own.colour_channels, own.resolution) != (1, 64):
+        if any_geometry and mod._train_part != 'down':
+            raise ValueError('daimc_amd.Adam: any_geometry selects the run-time-geometry step of ModelDown; the habit and transition '
+                             'networks have one geometry')
+        if mod._train_part == 'down' and not any_geometry and (own.colour_channels, own.resolution) != (1, 64):
             raise ValueError(f'daimc_amd.Adam: ModelDown is trainable on the engine at 1 x 64 x 64 only, this model is '
                              f'{own.colour_channels} x {own.resolution} x {own.resolution}')
         self._module = mod
+        self._any_geometry = bool(any_geometry)     # ModelDown through efe_g.down_adam_step / efe_g.train_down
         self._part = mod._train_part                # the part's name in the C ABI: "top" / "ps_net"; "down": the step's own entry point
         self._shapes = [tuple(t.shape) for t in mod._sd_host.values()]
         self._numel = [int(torch.Size(s).numel()) for s in self._shapes]
@@ -54,8 +62,8 @@ class Adam:
         """no-op: the engine never accumulates gradients"""
 
     def step(self, grad):
-        """one update with the caller's gradient: the dict loss.grad_top / grad_mid / grad_down returns, or the flat [P] tensor
-        (parameters() order)"""
+        """one update with the caller's gradient: the dict loss.grad_top / grad_mid / grad_down / grad_down_g returns, or the flat [P]
+        tensor (parameters() order)"""
         m = self._module._owner
         e = m._ready()
         if isinstance(grad, dict):
@@ -63,7 +71,9 @@ class Adam:
         grad = e.tensor(grad).reshape(-1)
         ea, es = self._buffers()
         hyper = self._hyper()
-        if self._part == 'down':
+        if self._any_geometry:
+            torch.ops.efe_g.down_adam_step(e.h, grad, ea, es, *hyper, self._step + 1)
+        elif self._part == 'down':
             e.ops.down_adam_step(e.h, grad, ea, es, *hyper, self._step + 1)
         else:
             e.ops.adam_step(e.h, self._part, grad, ea, es, *hyper, self._step + 1)

@@ -605,7 +605,7 @@ int efe_down_grad(efe_ctx*, const float* o1, const float* ps1_mean, const float*
  * alone: twice the same bits; per-row outputs depend on that row and its global row id only.  Rows are processed
  * in groups of 64 (resolution <= 64) or 32; scratch comes from the context's arena.  Both return 1 with a message that names the function,
  * before the first launch, for M <= 0, a NULL required pointer, a split-operand option (mfma_bf16x3 / mfma_f16x2) being on, or
- * EFE_OMEGA_DERIVED.  There is no optimiser step at these geometries yet. */
+ * EFE_OMEGA_DERIVED.  The optimiser step at these geometries: efe_train_down_g / efe_down_adam_step_g below. */
 int efe_enc_grad_g(efe_ctx*, const float* o, const float* g_mean, const float* g_logvar, int M, const efe_noise* nz, float* mean, float* logvar,
                    float* grad, float* y1, float* y2, float* y3, float* y4, float* h1, float* h2, float* h3, void* stream);
 int efe_down_grad_g(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
@@ -634,6 +634,30 @@ int efe_train_down(efe_ctx*, const float* o1, const float* ps1_mean, const float
                    const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
 int efe_down_adam_step(efe_ctx*, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
 int efe_down_get_weights(efe_ctx*, float* dst, int64_t n, void* stream);
+
+/* ---- the same step at EVERY admitted geometry: train_model_down_g (csrc/train_down_g.hip behind k_adam_down; additive to ABI 6) ---------------
+ * The three functions above with the sizes taken from the context: the flat vector has efe_param_count("down_g") floats (efe_down_grad_g's
+ * order).  A context of any other geometry than 1 x 64 x 64 owns a master copy of its own that survives efe_commit_weights; the step writes
+ * it and rebuilds, on the device, every packed form the generic forward path reads (the 32x32x2 and 16x16x4 fragment orders of the dense
+ * layers, po_net.9 with its rows and qs_net.9 with its columns in NHWC order, nine-tap forms of the four Conv2d and three ConvTranspose2d
+ * layers, the two small forms of qs_net.0 and po_net.19, padded bias tables): each holds exactly what a fresh commit of the new weights would
+ * have packed.  efe_set_weight of a "down." tensor and efe_commit_weights first bring the host tensors up to date, as above.  The first
+ * decoder pass behind a step fetches po_net.19.bias (C floats, handed to its kernel by value) on its own stream and synchronises that stream
+ * once; it cannot be captured into a graph, and a graph captured before a step holds the old bias.  At 1 x 64 x 64 these functions run
+ * efe_down_grad_g's kernels for the gradient and then THE SAME update and repack as the functions above, on the same master copy: the two
+ * families may be mixed freely there.
+ *   efe_train_down_g      : efe_down_grad_g's groups, the update and the repack queued on the stream, no host synchronisation; bit-identical
+ *                           to efe_down_grad_g followed by efe_down_adam_step_g.  out reports the weights BEFORE the step.
+ *   efe_down_adam_step_g  : update and repack from the caller's gradient; exp_avg / exp_avg_sq are the caller's state, all of "down_g" floats.
+ *   efe_down_get_weights_g: the master copy -> dst (device), n == efe_param_count("down_g"), ordered on the stream.
+ * Each returns 1 with a message that names the function, before the first launch, for M <= 0, a NULL required pointer, hp NULL or bad
+ * hyper-parameters, EFE_OMEGA_DERIVED, a split-operand option being on, weights that are not committed, or a handle that is not live; a
+ * refused call changes no weight, no optimiser state and no packed form.  efe_down_adam_step, efe_train_down and efe_down_get_weights keep
+ * refusing every geometry but 1 x 64 x 64. */
+int efe_train_down_g(efe_ctx*, const float* o1, const float* ps1_mean, const float* ps1_logvar, int M, const efe_fe_params* params,
+                     const efe_noise* nz, const float* eps, efe_fe_out* out, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
+int efe_down_adam_step_g(efe_ctx*, const float* grad, float* exp_avg, float* exp_avg_sq, const efe_adam_params* hp, void* stream);
+int efe_down_get_weights_g(efe_ctx*, float* dst, int64_t n, void* stream);
 
 /* ---- one whole training step: the loop body of the reference's train.py:111-126 (additive to ABI 6) --------------------------------------
  * One call, one call scope, everything queued on `stream`, no host synchronisation.  At the 1 x 64 x 64 geometry, in this order:
