@@ -133,7 +133,7 @@ def run_encoder(weights, o, d_mean, d_logvar, stage, dtype=torch.float32, gates=
 def run(weights, o1, ps1_mean, ps1_logvar, omega, stage, dtype=torch.float32, gamma=0.5, beta_s=1.0, beta_o=1.0, gates=None, dec_gates=None,
         eps=None, seed=SEED, pass_=PASS_FE_DOWN, sample=0, row_offset=0):
     """compute_loss_down and F.mean().backward().  omega: [M] or a number; eps: None (the Philox normals) or [M, 10].  -> dict(F_down,
-    nlogpo1, kl_s, kl_naive [M], po1, qs1, mean, logvar, g_mean, g_logvar [M, 10], grads {32 keys}, the encoder's y / h / a_conv / a_dense /
+    nlogpo1, kl_s, kl_naive [M], po1, qs1, mean, logvar, g_mean, g_logvar, d_s (the gradient at qs1) [M, 10], grads {32 keys}, the encoder's y / h / a_conv / a_dense /
     enc_masks, and the decoder's dec_h, dec_y, dec_a_head, dec_a, dec_masks), numpy arrays in `dtype`"""
     M = o1.shape[0]
     params = _params(weights, KEYS, dtype)
@@ -146,6 +146,7 @@ def run(weights, o1, ps1_mean, ps1_logvar, omega, stage, dtype=torch.float32, ga
     logvar.retain_grad()
     e = torch.as_tensor(np.asarray(eps, dtype=np.float32)) if eps is not None else normals(M, stage, seed, pass_, sample, row_offset)
     qs1 = e.to(dtype).reshape(M, 10) * torch.exp(logvar * 0.5) + mean
+    qs1.retain_grad()
     p, logpo1, dhs, dys, dpre_h, dpre = decode(params, qs1, o, dmk, dtype, dec_gates)
     w = torch.as_tensor(np.asarray(omega, dtype=np.float32)).to(dtype).reshape(-1, 1)
     if w.numel() == 1:
@@ -167,6 +168,6 @@ def run(weights, o1, ps1_mean, ps1_logvar, omega, stage, dtype=torch.float32, ga
         Fd = -bo * logpo1 + bs * (ga * kl_s + (1.0 - ga) * kl_naive)
     Fd.mean().backward()
     return dict(F_down=_n(Fd), nlogpo1=_n(-logpo1), kl_s=_n(kl_s), kl_naive=_n(kl_naive), po1=_n(p), qs1=_n(qs1), mean=_n(mean), logvar=_n(logvar),
-                g_mean=_n(mean.grad), g_logvar=_n(logvar.grad), grads={k: _n(v.grad) for k, v in params.items()},
+                g_mean=_n(mean.grad), g_logvar=_n(logvar.grad), d_s=_n(qs1.grad), grads={k: _n(v.grad) for k, v in params.items()},
                 dec_h=tuple(_n(h) for h in dhs), dec_y=tuple(_n(y) for y in dys), dec_a_head=tuple(_n(a) for a in dpre_h),
                 dec_a=tuple(_n(a) for a in dpre), dec_masks=tuple(m.numpy() for m in dmk), **_enc_out(out, ys, hs, pre_c, pre_d, mk))

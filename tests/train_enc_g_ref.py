@@ -115,6 +115,7 @@ def run(weights, o1, ps1_mean, ps1_logvar, omega, C, R, stage, dtype=torch.float
     logvar.retain_grad()
     e = torch.as_tensor(np.asarray(eps, dtype=np.float32)) if eps is not None else normals(M, stage, seed, pass_, sample, row_offset)
     qs1 = e.to(dtype).reshape(M, 10) * torch.exp(logvar * 0.5) + mean
+    qs1.retain_grad()
     p, logpo1, dhs, dys, dpre_h, dpre = decode(params, qs1, o, dmk, C, R, dtype, dec_gates)
     w = torch.as_tensor(np.asarray(omega, dtype=np.float32)).to(dtype).reshape(-1, 1)
     if w.numel() == 1:
@@ -136,6 +137,6 @@ def run(weights, o1, ps1_mean, ps1_logvar, omega, C, R, stage, dtype=torch.float
         Fd = -bo * logpo1 + bs * (ga * kl_s + (1.0 - ga) * kl_naive)
     Fd.mean().backward()
     return dict(F_down=_n(Fd), nlogpo1=_n(-logpo1), kl_s=_n(kl_s), kl_naive=_n(kl_naive), po1=_n(p), qs1=_n(qs1), mean=_n(mean), logvar=_n(logvar),
-                g_mean=_n(mean.grad), g_logvar=_n(logvar.grad), grads={k: _n(v.grad) for k, v in params.items()},
+                g_mean=_n(mean.grad), g_logvar=_n(logvar.grad), d_s=_n(qs1.grad), grads={k: _n(v.grad) for k, v in params.items()},
                 dec_h=tuple(_n(h) for h in dhs), dec_y=tuple(_n(y) for y in dys), dec_a_head=tuple(_n(a) for a in dpre_h),
                 dec_a=tuple(_n(a) for a in dpre), dec_masks=tuple(m.numpy() for m in dmk), **TDN._enc_out(out, ys, hs, pre_c, pre_d, mk))
